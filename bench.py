@@ -8,7 +8,9 @@ priority cuts (scheduler/batches.rs:97-171) couple every worker's block through 
 is ONE model of 8 205 columns, solved by price sweeps on the MI355X (k_price_sweep).  The ready-set columns are resident in HBM
 when the timed region starts (hqtick_upload_ready), worker / request tables too (hqtick_cluster_upload).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3p]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3p] [--dump-outputs DIR]
+  --dump-outputs DIR: after the timed steps, the last timed tick's outputs as float64 DIR/<name>.npy (dump_outputs below); the inputs depend on the arguments
+  alone (seeded workload), so two builds run with the same arguments can be compared array by array.
   N > 1: launched by torch.distributed.run, one rank per GPU (or self-launched): ONE scheduler whose workers are hash-sharded over the ranks
   (hyperqueue_amd/sharded.py); weak scaling — 1024 workers and 1 M ready tasks per GPU; every rank sweeps its own worker range
   (one small all-gather per sweep), one RCCL all-gather merges the shards' assignment vectors; value = tasks assigned by the whole job per second.
@@ -97,6 +99,75 @@ def write_extras(path: str, extras: dict):
         os.replace(tmp, path)
     except OSError as e:
         print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
+
+
+DUMP_LIMIT = 64 << 20  # bytes: what --dump-outputs may write in all
+
+
+def _f64(x) -> np.ndarray:
+    """float64 copy of an integer array; every value must survive the conversion exactly"""
+    x = np.asarray(x)
+    f = x.astype(np.float64)
+    assert x.size == 0 or (f.astype(x.dtype) == x).all(), "value not exact in float64"
+    return f
+
+
+def _ids(task) -> np.ndarray:
+    """u64 task ids as two float64 columns (job, task in job): exact whatever the job id"""
+    t = np.asarray(task, np.uint64)
+    return np.stack([_f64(t >> np.uint64(32)), _f64(t & np.uint64(0xFFFFFFFF))], axis=1) if len(t) else np.zeros((0, 2))
+
+
+def dump_outputs(out_dir: str, r) -> dict:
+    """--dump-outputs: what the timed path handed its caller in its last step (`r`: abi.Result of that tick), one float64
+    DIR/<name>.npy per array.  Tables, one row per item: status [status, is_optimal, is_canonical]; batches [rq, size, limit, limit_reached, is_blocker];
+    batch_cuts [batch, size]; cut_blockers [cut, rq, size or -1 = unbounded]; counts [rq, variant, worker index, count]; records [worker index, job, task in job,
+    variant, kind]; retracts [worker index, job, task in job]; redirects [job, task in job, worker index, variant, kind]; multi_node [job, task in job, worker
+    index]; new_free [worker index, resource].  Above DUMP_LIMIT in all, the largest tables keep a fixed sample of their rows (seed 0, in row order) and
+    <name>_rows.npy says which.  A table without rows gets no file.  Returns {name: shape} of the files written."""
+    from hyperqueue_amd import abi
+
+    cuts, blockers = [], []
+    for i, b in enumerate(r.batches):
+        for (size, bl) in b.cuts:
+            blockers += [(len(cuts), rq, -1 if s is None else s) for (rq, s) in bl]
+            cuts.append((i, size))
+    rec = [(w, t, v, k) for w, recs in enumerate(r.records) for (t, v, k) in recs]
+    ret = [(w, t) for w, ts in enumerate(r.retracts) for t in ts]
+    mn = [(t, w) for (t, ws) in r.mn for w in ws]
+    kinds = r.redirect_kinds or [abi.HQ_REDIRECT_FROM_PREFILL] * len(r.redirects)
+
+    def table(rows, n_cols):
+        return _f64(np.asarray(rows, np.int64).reshape(-1, n_cols))
+
+    arrays = {
+        "status": _f64(np.asarray([r.status, r.is_optimal, r.is_canonical], np.int64)),
+        "batches": table([(b.rq, b.size, b.limit, b.limit_reached, b.is_blocker) for b in r.batches], 5),
+        "batch_cuts": table(cuts, 2),
+        "cut_blockers": table(blockers, 3),
+        "counts": table(r.counts, 4),
+        "records": np.concatenate([table([x[:1] for x in rec], 1), _ids([x[1] for x in rec]), table([x[2:] for x in rec], 2)], axis=1),
+        "retracts": np.concatenate([table([x[:1] for x in ret], 1), _ids([x[1] for x in ret])], axis=1),
+        "redirects": np.concatenate([_ids([x[0] for x in r.redirects]), table([(w, v, k) for (_, w, v), k in zip(r.redirects, kinds)], 3)], axis=1),
+        "multi_node": np.concatenate([_ids([x[0] for x in mn]), table([x[1:] for x in mn], 1)], axis=1),
+        "new_free": _f64(r.new_free),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        excess, a = total - DUMP_LIMIT, arrays[name]
+        if excess <= 0:
+            break
+        row_bytes = a.nbytes // max(len(a), 1)
+        keep = max(0, (a.nbytes - excess) // (row_bytes + 8))  # (8 B more per kept row: its row number)
+        rows = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+        arrays[name], arrays[name + "_rows"] = a[rows], _f64(rows)
+        total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    arrays = {name: a for name, a in arrays.items() if a.size}  # a table without rows (e.g. no retracts on a cold tick) is not written
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(snap, ticks: int):
@@ -674,7 +745,11 @@ def main():
     ap.add_argument("--warm-caches", action="store_true", help="the timed region with the product's default cross-tick caches live (level table, Map-order memo): NOT the headline")
     ap.add_argument("--extras-file", default=os.path.join(ROOT, "bench_extras.json"), help="where everything that is not the headline line goes (neighbour workloads, loops, DAG, wire, notes)")
     ap.add_argument("--no-kernel-timing", action="store_true", help="HQTICK_FLAG_NO_KERNEL_TIMING: no HIP events inside the tick at all (the roofline object is then empty)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed tick handed its caller (records, counts, new free "
+                                                                       "rows, batches, status; an empty one gets no file) as float64 DIR/<name>.npy, at most 64 MB in all; same arguments, same inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.headline_only:
         args.cpu_ticks = args.priority_ticks = args.steady_steps = args.hetero_steps = args.dag_steps = args.wire_iters = 0
         args.roofline_sweep = False
@@ -839,6 +914,14 @@ def main():
     ncp = int(res.n_counts)
     gdp = dict(zip(zip(abi._np(res.count_rq, ncp, np.uint32).tolist(), abi._np(res.count_variant, ncp, np.uint8).tolist(), abi._np(res.count_worker, ncp, np.uint32).tolist()),
                    abi._np(res.count_value, ncp, np.uint32).tolist())) if (ncp and rank == 0) else {}
+    if args.dump_outputs and rank == 0:  # (also read here, before anything ticks this context again; outside the timed region)
+        last = abi.parse_result(res, W_all, snap.n_resources)
+        if st is not None:  # the sharded path: the records are the merged vector rank 0 pulled to the host
+            from hyperqueue_amd.sharded import merge_shards
+
+            last.records = merge_shards(host_merged.numpy(), world, W_all, st.cap)
+        shapes = dump_outputs(args.dump_outputs, last)
+        print(f"bench.py: outputs of the last timed tick in {args.dump_outputs}: {shapes}", file=sys.stderr)
     if rank != 0:
         if dist is not None:
             if args.multi_extras and not args.headline_only:
