@@ -8,7 +8,12 @@
 #include "price_emul.h"
 
 static thread_local int g_last_canonical = 0;
+static thread_local long g_last_hull[2] = {0, 0};
 extern "C" int hqtick_debug_milp_was_canonical(void) { return g_last_canonical; }
+extern "C" void hqtick_debug_milp_last_hull(long *solves, long *nonpacking) {
+    if (solves) *solves = g_last_hull[0];
+    if (nonpacking) *nonpacking = g_last_hull[1];
+}
 
 extern "C" int hqtick_debug_milp_solve(int ncols, const double *obj, const uint8_t *col_kind, int nrows, const uint8_t *row_type,
                                        const double *rhs, const int *row_off, const int *row_col, const double *row_coef,
@@ -25,6 +30,7 @@ extern "C" int hqtick_debug_milp_solve(int ncols, const double *obj, const uint8
     m.rcoef.assign(row_coef, row_coef + nnz);
     hqmilp::Result r = hqmilp::solve(m, time_limit_s, canonical != 0);
     g_last_canonical = r.canonical ? 1 : 0;
+    g_last_hull[0] = r.hull_solves; g_last_hull[1] = r.hull_solves_nonpacking;
     if (nodes_out) *nodes_out = r.nodes;
     if (!r.feasible) return 0;
     for (int j = 0; j < ncols; j++) x_out[j] = r.x[j];
@@ -60,6 +66,7 @@ extern "C" int hqtick_debug_milp_solve_priced(int ncols, const double *obj, cons
     if (min_cols) emu.min_cols = min_cols;
     hqmilp::Result r = hqmilp::solve(m, time_limit_s, true, hqmilp::REFERENCE_MIP_REL_GAP, use_sweeps ? &emu : nullptr);
     g_last_canonical = r.canonical ? 1 : 0;
+    g_last_hull[0] = r.hull_solves; g_last_hull[1] = r.hull_solves_nonpacking;
     if (stats_out) { stats_out[0] = r.price_sweeps; stats_out[1] = r.price_rounds; stats_out[2] = r.price_total_us; stats_out[3] = r.canonical ? 1.0 : 0.0; }
     if (!r.feasible) return 0;
     for (int j = 0; j < ncols; j++) x_out[j] = r.x[j];

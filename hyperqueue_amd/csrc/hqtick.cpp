@@ -2136,6 +2136,13 @@ void hqtick_debug_set_exchange(hqtick_exchange_fn fn, void *user, uint32_t rank,
 uint32_t hqtick_debug_last_exchange_calls(void) { return g_xcalls; }
 void hqtick_debug_last_stage_us(double *out3) { if (out3) for (int i = 0; i < 3; i++) out3[i] = g_last_stage_us[i]; }
 void hqtick_debug_last_price(uint32_t *sweeps, uint32_t *rounds) { if (sweeps) *sweeps = g_last_price_sweeps; if (rounds) *rounds = g_last_price_rounds; }
+static thread_local std::vector<uint32_t> g_last_mn_rq, g_last_mn_off{0}, g_last_mn_worker;
+uint32_t hqtick_debug_last_mn(const uint32_t **rq, const uint32_t **off, const uint32_t **worker) {
+    if (rq) *rq = g_last_mn_rq.data();
+    if (off) *off = g_last_mn_off.data();
+    if (worker) *worker = g_last_mn_worker.data();
+    return (uint32_t)g_last_mn_rq.size();
+}
 void hqtick_debug_set_block_emulation(int on, uint32_t budget) { g_block_emulation = on; if (budget) g_block_budget = budget; }
 void hqtick_debug_last_blocks(uint32_t *n_emulated, uint32_t *n_host) { if (n_emulated) *n_emulated = g_last_blocks_device; if (n_host) *n_host = g_last_blocks_host; }
 
@@ -2166,6 +2173,7 @@ int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot 
     std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
     std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
     memset(out, 0, sizeof(*out));
+    g_last_mn_rq.clear(); g_last_mn_off.assign(1, 0); g_last_mn_worker.clear();
     export_batches(ctx, batches, out);
     EmulatedBlocks emu(g_block_budget);
     emu.corrupt_mode = g_corrupt_mode; emu.corrupt_class = g_corrupt_class; emu.corrupt_fill = g_corrupt_fill;
@@ -2189,6 +2197,8 @@ int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot 
     g_last_memo = cnt.blocks_memo;
     g_last_blocks_device = cnt.blocks_device; g_last_blocks_host = cnt.blocks_host; g_last_price_sweeps = (uint32_t)cnt.price_sweeps; g_last_price_rounds = (uint32_t)cnt.price_rounds;
     g_last_stage_us[0] = cnt.t_classify_us; g_last_stage_us[1] = cnt.t_blocks_us; g_last_stage_us[2] = cnt.t_decode_us;
+    for (size_t i = 0; i < cnt.mn_rq.size(); i++)
+        for (auto &set : cnt.mn_sets[i]) { g_last_mn_rq.push_back(cnt.mn_rq[i]); g_last_mn_worker.insert(g_last_mn_worker.end(), set.begin(), set.end()); g_last_mn_off.push_back((uint32_t)g_last_mn_worker.size()); }
     ctx->cnt_rq.clear(); ctx->cnt_variant.clear(); ctx->cnt_worker.clear(); ctx->cnt_value.clear();
     cnt.pairs();
     for (size_t k = 0; k < cnt.keys.size(); k++)

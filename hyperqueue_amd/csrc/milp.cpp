@@ -265,6 +265,7 @@ struct CompSolver {
         bool ready = false, usable = false;
         std::vector<std::vector<int>> cols;      // per block: its columns
         std::vector<Rows> rows;                  // per block: the rows that live inside it (local column ids)
+        std::vector<uint8_t> packing;            // per block: 1 = down-closed (see find_hull_blocks)
         std::vector<uint8_t> row_internal;       // per row of R: 1 = inside one block
     } hb;
     void find_hull_blocks() {
@@ -290,9 +291,25 @@ struct CompSolver {
             for (int k = R.off[i]; k < R.off[i + 1]; k++) terms.push_back({local[R.col[k]], R.coef[k]});
             hb.rows[b].add(terms, R.lo[i], R.hi[i]);
         }
+        // A PACKING block (every internal row `<= hi` with hi >= 0 and coefficients >= 0, every lb = 0) is down-closed: lowering a column keeps the block's
+        // point feasible, so a column with r_j <= 0 can sit at 0 in the block solve and stay out of the cut.  Anything else — min_utilization's `cpu.x - need*y >= 0`
+        // with its zero-cost bool y, a multi-node group's `==` row, a negative coefficient — is not: there the block is solved over its columns' real bounds and
+        // every r_j != 0 term goes into the cut (with y pinned to 0 the pair forces every cpu column to 0, and the cut r.x <= ~0 would remove every integer point
+        // that uses the worker).
+        hb.packing.assign(nb, 1);
+        for (int b = 0; b < nb; b++) {
+            const Rows &br = hb.rows[b];
+            bool pk = true;
+            for (int i = 0; i < br.m && pk; i++) {
+                if (!(br.lo[i] <= -INF * 0.5) || !(br.hi[i] >= 0.0)) pk = false;
+                for (int k = br.off[i]; k < br.off[i + 1] && pk; k++) if (!(br.coef[k] >= 0.0)) pk = false;
+            }
+            for (int j : hb.cols[b]) if (lb[j] != 0.0) pk = false;
+            hb.packing[b] = pk ? 1 : 0;
+        }
         hb.usable = true;
     }
-    long hull_solves = 0;
+    long hull_solves = 0, hull_solves_nonpacking = 0;
     // one round: cuts for the blocks whose LP point beats their integer optimum at the current Lagrangian costs; returns how many were added to RC
     int hull_round(Tab &t, Rows &RC) {
         if (!hb.ready) find_hull_blocks();
@@ -316,23 +333,34 @@ struct CompSolver {
             for (int l = 0; l < nbc; l++) { const int j = bc[l]; lpv += r[j] * t.x[j]; rmax = std::max(rmax, std::fabs(r[j])); }
             if (!(rmax > 1e-12)) continue;
             if (lpv <= 1e-7 * rmax) continue;   // (V_b >= r . lb-point; with lb = 0 nothing below zero can be violated)
+            const bool packing = hb.packing[b] != 0;
             CompSolver sub; sub.n = nbc; sub.in_lns = true; sub.deadline = deadline; sub.node_cap = 4000; sub.tracing = false;
             sub.c.resize(nbc); sub.lb.resize(nbc); sub.ub.resize(nbc); sub.R = hb.rows[b];
-            for (int l = 0; l < nbc; l++) { const int j = bc[l]; sub.c[l] = r[j] / rmax; sub.lb[l] = lb[j]; sub.ub[l] = r[j] > 0.0 ? ub[j] : lb[j]; }   // a column that does not pay stays at its lower bound
+            for (int l = 0; l < nbc; l++) { const int j = bc[l]; sub.c[l] = r[j] / rmax; sub.lb[l] = lb[j]; sub.ub[l] = (!packing || r[j] > 0.0) ? ub[j] : lb[j]; }   // (packing: a column that does not pay stays at its lower bound)
             std::vector<double> xb;
             const int st = sub.run(false, xb);
             nodes += sub.nodes; work += sub.work; hull_solves++;
-            if (tracing && getenv("HQMILP_HULL_TRACE")) fprintf(stderr, "[hull] block %zu: %d cols st %d nodes %ld work %.3g\n", b, nbc, st, sub.nodes, sub.work);
+            if (!packing) hull_solves_nonpacking++;
+            if (tracing && getenv("HQMILP_HULL_TRACE")) fprintf(stderr, "[hull] block %zu: %d cols %s st %d nodes %ld work %.3g\n", b, nbc, packing ? "packing" : "non-packing", st, sub.nodes, sub.work);
             if (st != 1 || (int)xb.size() != nbc) continue;   // not solved to the end within its cap: no cut from this block
             double V = 0.0; for (int l = 0; l < nbc; l++) V += r[bc[l]] * xb[l];
             if (lpv <= V + 1e-6 * rmax * std::max(1.0, std::fabs(V / rmax))) continue;
             // r . x_b <= V, scaled to max |coef| = 1 and relaxed a hair; never against the incumbent (cannot be: it is an integer point of the block)
             terms.clear();
-            for (int l = 0; l < nbc; l++) { const int j = bc[l]; if (r[j] > 0.0 && std::fabs(r[j]) >= 1e-9 * rmax) terms.push_back({j, r[j] / rmax}); }
-            // (columns with r_j <= 0 were held at their lower bound in the block solve: dropping them from the cut keeps it valid only for lb = 0 — check)
-            bool lb0 = true; for (int l = 0; l < nbc; l++) if (lb[bc[l]] != 0.0) lb0 = false;
-            if (!lb0) continue;
-            double rhs = V / rmax; rhs += 1e-9 * (std::fabs(rhs) + 1.0);
+            double rhs = V / rmax;
+            for (int l = 0; l < nbc; l++) {
+                const int j = bc[l]; const double a = r[j] / rmax;
+                if (packing) { if (r[j] > 0.0 && std::fabs(r[j]) >= 1e-9 * rmax) terms.push_back({j, a}); continue; }
+                if (a == 0.0) continue;
+                // a tiny term leaves the cut against the bound that makes it largest (a relaxation); one that has no such bound stays
+                const double w = a > 0.0 ? lb[j] : ub[j];
+                if (std::fabs(a) < 1e-9 && std::fabs(w) < 1e9) rhs -= a * w;
+                else terms.push_back({j, a});
+            }
+            // (packing: columns with r_j <= 0 were held at their lower bound in the block solve: dropping them from the cut keeps it valid only for lb = 0 — which
+            // the classification checked; a non-packing block's cut holds every term)
+            if (terms.empty()) continue;
+            rhs += 1e-9 * (std::fabs(rhs) + 1.0);
             if (have) { double li = 0.0; for (auto &tm : terms) li += tm.second * bx[tm.first]; if (li > rhs) continue; }
             RC.add(terms, -INF, rhs);
             slack_unit.push_back(0.0);
@@ -1872,6 +1900,7 @@ static Result solve_classic(const Model &mdl_in, double time_limit_s, bool canon
         if (!cs.canonical_done || st == 2) res.canonical = false;
         res.nodes += cs.nodes; res.lp_iters += cs.lp_iters;
         res.price_sweeps += cs.price_sweeps; res.price_rounds += cs.price_rounds; res.price_total_us += cs.price_us;
+        res.hull_solves += cs.hull_solves; res.hull_solves_nonpacking += cs.hull_solves_nonpacking;
         if (st == 0) {
             if (cs.timed_out) {  // nothing found in time: all-zero placement with every blocker flag on (feasible for the tick's models)
                 res.optimal = false;

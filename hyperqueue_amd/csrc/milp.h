@@ -104,6 +104,7 @@ struct Result {
     int n_components = 0;
     int price_sweeps = 0, price_rounds = 0;      // block sweeps of the coupled solve / flag configurations tried (0: the host-only search ran)
     double price_bound_us = 0, price_total_us = 0;
+    long hull_solves = 0, hull_solves_nonpacking = 0;  // block solves of the root's block-hull rounds, and those of them on blocks that are not packings
 };
 
 // What the reference calls optimal: solve_bounded sets `time_limit` and nothing else (solver/highs.rs:65-68), so HiGHS runs with its default

@@ -45,6 +45,9 @@ int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *
 
 /* 1 if the last hqtick_debug_milp_solve on this thread completed its tie-break phase (Result::canonical, milp.h). */
 int hqtick_debug_milp_was_canonical(void);
+/* block solves of the root's block-hull cut rounds in the last hqtick_debug_milp_solve / _solve_priced call on this thread, and how many of them were on
+ * blocks that are not packings (a row other than `<= hi` with hi >= 0 and coefficients >= 0, or a lower bound other than 0) */
+void hqtick_debug_milp_last_hull(long *solves, long *nonpacking);
 
 /* Iteration order of a hashbrown Map<WorkerId,_> built by inserting `keys` (distinct u32) in the given order:
  * out_pos[i] = index into `keys` of the i-th element visited (scheduler/mapping.rs:43). */
@@ -96,6 +99,9 @@ void hqtick_debug_check_model_hints(int on);
 int hqtick_debug_model_hint_mismatches(void);
 /* sweeps over all blocks / flag configurations of the last hqtick_debug_host_stages call (0: the host search ran alone) */
 void hqtick_debug_last_price(uint32_t *sweeps, uint32_t *rounds);
+/* the multi-node placements of the last hqtick_debug_host_stages call on this thread (the counts carry single-node placements only): returns the number of
+ * placed multi-node tasks; task i is of request rq[i] and runs on the worker indices worker[off[i] .. off[i + 1]).  Valid until the next call. */
+uint32_t hqtick_debug_last_mn(const uint32_t **rq, const uint32_t **off, const uint32_t **worker);
 /* hqtick_debug_milp_solve on a model that carries the builder's structure hints (col_group: block of every column, -1 = a column of the whole model;
  * row_implied: rows implied for integer points by their block's other rows; both may be NULL), with the price sweeps run through the emulated
  * wavefront when use_sweeps != 0.  stats_out (optional, 4 doubles): sweeps, rounds, microseconds inside the price solve, canonical flag. */

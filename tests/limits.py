@@ -38,6 +38,30 @@ def model_point(model, counts):
     return x
 
 
+def completed_point(model, counts, mn=None):
+    """The counts as a point of the model with every other column chosen for the best objective: (x, c.x), or None when no choice satisfies every row.
+    The placement columns (col_type 0) are fixed to `counts`.  With `mn` — (rq, [worker indices]) per placed multi-node task — the multi-node placement
+    columns (col_type 1) are fixed too (1 on each worker of a placed task, 0 elsewhere); without it they are left free with the flag columns.  HiGHS
+    chooses only what is left: flags (blocker, min_utilization) and the multi-node group counts their rows imply."""
+    from oracle.oracle import solve_milp
+
+    cd = {(q, v, w): c for (q, v, w, c) in counts}
+    fixed = {0: cd}
+    if mn is not None:
+        fixed[1] = {(int(q), 0, int(w)): 1 for (q, ws) in mn for w in ws}
+    n = len(model["obj"])
+    roff, rcol, rcoef = list(model["roff"]), list(model["rcol"]), list(model["rcoef"])
+    rtype, rhs = list(model["rtype"]), list(model["rhs"])
+    for j in range(n):
+        t = int(model["ctype"][j])
+        if t in fixed:
+            v = fixed[t].get((int(model["crq"][j]), int(model["cvariant"][j]), int(model["cworker"][j])), 0)
+            for tp in (0, 1):  # x_j >= v and x_j <= v
+                rcol.append(j), rcoef.append(1.0), roff.append(len(rcol)), rtype.append(tp), rhs.append(float(v))
+    out = solve_milp(model["obj"], model["kind"], np.asarray(rtype, np.uint8), np.asarray(rhs, float), np.asarray(roff), np.asarray(rcol), np.asarray(rcoef, float), time_limit=60.0)
+    return None if out is None else (out[0], out[1])
+
+
 def rows_hold(model, x) -> bool:
     from scipy.sparse import csr_matrix
 

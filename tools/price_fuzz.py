@@ -2,7 +2,8 @@
 """CPU campaign of the price path (csrc/price.cpp + the emulated k_price_sweep): random coupled ticks of mid size — clusters mid-run with every worker its own
 free vector, several priority levels, ready sets that do not saturate — solved with the sweeps forced on from 16 model columns, against the host-only search.
 Both claim a 1e-4 certificate, so whenever both are optimal the objectives must agree to 1e-4; the sweeps' point is verified row by row inside the solver
-(CompSolver::polish_point).  Prints one line per disagreement and a summary.   python tools/price_fuzz.py [first_seed] [count] [procs]"""
+(CompSolver::polish_point).  Prints one line per disagreement and a summary.   python tools/price_fuzz.py [--variant mu|mu6|mn|blocked|mixed] [first_seed] [count] [procs]
+--variant takes the scenario of tests/coupled_cases.py instead: worker blocks that are not packings (min_utilization, multi-node groups, blocked requests)."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,13 +28,18 @@ def scenario(seed):
     return snap, W, levels, steady, n_ready
 
 
-def one(seed):
+def one(seed, variant=None):
     from hyperqueue_amd import abi
     from test_price import stages
     from test_host_stages import _objective
     from oracle.oracle import Oracle
 
     snap, W, levels, steady, n_ready = scenario(seed)
+    if variant:
+        import coupled_cases
+
+        snap = coupled_cases.case(variant, seed)
+        W, levels, n_ready = len(snap.worker_id), len(np.unique(snap.task_priority)), len(snap.task_id)  # (mn adds tasks and idles workers)
     t0 = time.time(); got, sweeps, rounds = stages(snap, True, min_cols=16, tl=5.0); tg = time.time() - t0
     t0 = time.time(); host, _, _ = stages(snap, False, tl=5.0); th = time.time() - t0
     with_highs = os.environ.get("PRICE_FUZZ_HIGHS") == "1"  # also time the reference-configured HiGHS (5 s limit) on the same snapshot
@@ -55,12 +61,21 @@ def one(seed):
 
 
 def main():
-    first = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-    count = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-    procs = int(sys.argv[3]) if len(sys.argv) > 3 else 6
+    from functools import partial
+
+    args = sys.argv[1:]
+    variant = None
+    if "--variant" in args:
+        k = args.index("--variant")
+        variant = args[k + 1]
+        del args[k:k + 2]
+        assert variant in ("mu", "mu6", "mn", "blocked", "mixed"), variant
+    first = int(args[0]) if len(args) > 0 else 0
+    count = int(args[1]) if len(args) > 1 else 200
+    procs = int(args[2]) if len(args) > 2 else 6
     from multiprocessing import Pool
     with Pool(procs) as p:
-        rows = p.map(one, range(first, first + count), chunksize=1)
+        rows = p.map(partial(one, variant=variant), range(first, first + count), chunksize=1)
     bad = [r for r in rows if r["bad"]]
     for r in bad:
         print("DISAGREE", r)
