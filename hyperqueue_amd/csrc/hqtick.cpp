@@ -1362,7 +1362,7 @@ uint32_t hqtick_abi_version(void) { return HQTICK_ABI_VERSION; }
 const char *hqtick_build_arch(void) { return "gfx950"; }
 
 int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
-    if (!config || !out_ctx || config->abi_version != HQTICK_ABI_VERSION) return HQTICK_E_INVALID;
+    if (!config || !out_ctx || (config->abi_version != HQTICK_ABI_VERSION && config->abi_version != 10u)) return HQTICK_E_INVALID;  // (11 added a function only: a config written for 10 is the same struct)
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || config->device_index < 0 || config->device_index >= n) return HQTICK_E_NO_DEVICE;
     hipDeviceProp_t prop;
@@ -2070,6 +2070,105 @@ static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_quer
     ctx->q_loaded.assign(fake->n_workers, 0);
     for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) ctx->q_loaded[wc.first] = 1;  // query.rs:73-81
     out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
+    return 0;
+}
+
+// The census of the resident set (census.hip) in place of phase A: level discovery (K0 / K0b) and the count kernel read the columns of `ctx` on ITS
+// stream — behind every add, remove, append and compaction queued there — and write only buffers of the query sub-context `q`; one synchronisation.
+static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc) {
+    sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
+    const uint64_t N = ctx->n_ready;
+    if (N == 0 || Q == 0 || ctx->n_live == 0) return 0;
+    const size_t tab_words = 4 + (size_t)std::min<uint64_t>(hqk::MAX_GROUPS, (uint64_t)Q * hqk::MAX_LEVELS);   // [err x 4][counts]: what the census can write for this Q
+    if (!q->d_set.ensure((size_t)(hqk::PRIO_SET_CAP + hqk::MAX_LEVELS) * 8) || !q->h_lv.ensure((size_t)(hqk::MAX_LEVELS + 4) * 8) || !q->d_flags.ensure(64) ||
+        !q->d_levels.ensure((size_t)(hqk::MAX_LEVELS + 2) * 8) || !q->d_nlevels.ensure(64) || !q->d_hist.ensure((4 + (size_t)hqk::MAX_GROUPS) * 4) || !q->h_a.ensure(tab_words * 4))
+        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc query census");
+    if (!q->set_clean) {   // (k_sort_levels leaves the set EMPTY and the flag words zero behind a discovery that succeeded)
+        HQ_HIP(hipMemsetAsync(q->d_set.p, 0xFF, (size_t)hqk::PRIO_SET_CAP * 8, ctx->stream));
+        HQ_HIP(hipMemsetAsync(q->d_flags.p, 0, 64, ctx->stream));
+    }
+    q->set_clean = false;
+    HQ_HIP(hipMemsetAsync(q->d_hist.p, 0, tab_words * 4, ctx->stream));
+    HQ_HIP(hqk::distinct_priorities(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), ctx->stream));
+    uint32_t *hl = q->h_lv.as<uint32_t>();
+    hl[0] = 0; hl[1] = 0; hl[2] = 0; hl[3] = 0;
+    const uint32_t lv_seq = ++q->lv_seq ? q->lv_seq : ++q->lv_seq;
+    HQ_HIP(hqk::sort_levels(q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->h_lv.dev<uint64_t>(), lv_seq, ctx->stream));
+    HQ_HIP(hqk::ready_census(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->d_hist.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hipMemcpyAsync(q->h_a.p, q->d_hist.p, tab_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t L = hl[0];
+    if (hl[2] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return fail(ctx, HQTICK_E_CAPACITY, "more than 4096 distinct priority levels in the ready set");
+    q->set_clean = true;
+    if (L == 0) return 0;   // only tombstones
+    if ((uint64_t)L * Q > hqk::MAX_GROUPS) return fail(ctx, HQTICK_E_CAPACITY, "levels x requests exceeds 16384 groups");
+    const uint32_t *h = q->h_a.as<uint32_t>();
+    if (h[0] & 2u) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
+    if (h[0]) return fail(ctx, HQTICK_E_DEVICE, "census: level table inconsistent with the ready set");
+    sc->L = L; sc->G = L * Q;
+    sc->levels.assign(q->h_lv.as<uint64_t>() + 2, q->h_lv.as<uint64_t>() + 2 + L);
+    sc->hist.assign(h + 4, h + 4 + sc->G);
+    return 0;
+}
+
+int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, hqtick_query_result *out, uint64_t *rq_ready) {
+    if (!ctx || !out || !fake) return HQTICK_E_INVALID;
+    if (!s) return fail(ctx, HQTICK_E_INVALID, "null snapshot");
+    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
+    if (!ctx->last_consumed) return fail(ctx, HQTICK_E_INVALID, "a selection of hqtick_run_resident is pending: call hqtick_ready_consume_last before hqtick_query_resident");
+    if (fake->n_workers && (!fake->worker_id || !fake->worker_total || !fake->worker_remaining_ns)) return fail(ctx, HQTICK_E_INVALID, "fake worker arrays missing");
+    // What the query reads of the snapshot: resources, requests, the prefill sets' sizes and priorities.  The real workers and everything indexed by them
+    // (blocked pairs, assignments, the prefill sets' workers, Retracting entries) are dropped, so W = 0, HQ_WORKERS_RESIDENT and a worker list answer alike.
+    hqtick_snapshot sub = *s;
+    sub.n_workers = 0; sub.worker_id = nullptr; sub.worker_total = nullptr; sub.worker_free = nullptr; sub.worker_remaining_ns = nullptr; sub.worker_min_utilization = nullptr;
+    sub.worker_flags = nullptr; sub.worker_group = nullptr; sub.worker_map_rank = nullptr;
+    sub.n_blocked = 0; sub.blocked_worker = nullptr; sub.blocked_rq = nullptr; sub.blocked_variant = nullptr;
+    sub.assigned_off = nullptr; sub.assigned_rq = nullptr; sub.assigned_variant = nullptr; sub.prefilled_off = nullptr; sub.prefilled_rq = nullptr;
+    sub.n_ready = 0; sub.task_id = nullptr; sub.task_priority = nullptr; sub.task_rq = nullptr;
+    sub.prefill_off = nullptr; sub.prefill_priority = nullptr; sub.prefill_task = nullptr; sub.prefill_worker = nullptr;
+    sub.n_retracting = 0; sub.retracting_task = nullptr; sub.retracting_worker = nullptr; sub.retracting_redirect_worker = nullptr; sub.retracting_redirect_variant = nullptr;
+    if (int rc = validate(ctx, &sub, false)) return rc;
+    const uint32_t R = s->n_resources, Q = s->n_requests;
+    if (s->prefill_off) {   // (queue_levels reads the sizes and priorities of the prefill sets)
+        for (uint32_t q = 0; q < Q; q++) if (s->prefill_off[q] > s->prefill_off[q + 1]) return fail(ctx, HQTICK_E_INVALID, "prefill_off not monotone");
+        if ((Q ? s->prefill_off[Q] : 0) && !s->prefill_priority) return fail(ctx, HQTICK_E_INVALID, "prefill arrays missing");
+        sub.prefill_off = s->prefill_off; sub.prefill_priority = s->prefill_priority;
+    }
+    HQ_HIP(hipSetDevice(ctx->device));
+    if (!ctx->qctx) {
+        hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
+        int rc = hqtick_create(&cfg, &ctx->qctx);
+        if (rc) { ctx->qctx = nullptr; return fail(ctx, rc, "creating the query sub-context failed"); }
+    }
+    hqtick_ctx *q = ctx->qctx;
+    Scan sc;
+    if (int rc = census_resident(ctx, q, Q, &sc)) return rc;
+    if (rq_ready) {
+        for (uint32_t r = 0; r < Q; r++) rq_ready[r] = 0;
+        for (uint32_t l = 0; l < sc.L; l++) for (uint32_t r = 0; r < Q; r++) rq_ready[r] += sc.hist[(size_t)l * Q + r];
+    }
+    // batches, model and solve on the sub-context, as hqtick_query
+    int rc;
+    WorkerEval ev_real, ev_fake;
+    if ((rc = eval_workers_sync(q, &sub, fake->n_workers, fake->worker_total, fake->worker_total, fake->worker_remaining_ns, &ev_fake))) { ctx->err = q->err; return rc; }
+    hqhost::Problem pb;
+    fill_problem(pb, &sub, q->cfg, ev_real);
+    hqhost::WorkerSet fw;
+    fw.n = fake->n_workers; fw.R = R; fw.id = fake->worker_id; fw.total = fake->worker_total; fw.free_ = fake->worker_total;
+    fw.remaining_ns = fake->worker_remaining_ns; fw.min_util = fake->worker_min_utilization; fw.flags = nullptr; fw.group = nullptr;
+    fw.vflags = ev_fake.flags; fw.vtmc = ev_fake.tmc; fw.n_variant_slots = Q ? s->rq_variant_off[Q] : 0;
+    fw.blocked.assign(fw.n, {});
+    hqhost::group_equal_rows(fw, true);
+    pb.custom = &fw;
+    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, &sub);
+    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
+    DeviceBlocks dev_blocks(q);
+    pb.blocks = &dev_blocks; pb.block_min_classes = q->block_min_classes; pb.pricer = q->pricer;
+    hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
+    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
+    q->q_loaded.assign(fake->n_workers, 0);
+    for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) q->q_loaded[wc.first] = 1;  // query.rs:73-81
+    out->n_workers = fake->n_workers; out->is_loaded = q->q_loaded.data(); out->is_optimal = cnt.is_optimal;
     return 0;
 }
 

@@ -157,6 +157,11 @@ hipError_t ready_live_count(const uint32_t *rq, uint64_t n, uint32_t *slice_cnt,
 hipError_t ready_rebuild(const uint64_t *oid, const uint64_t *oprio, const uint32_t *orq, uint64_t n, uint32_t n_live, const uint32_t *slice_off, const uint64_t *aid,
                    const uint64_t *aprio, const uint32_t *arq, uint32_t n_add, uint64_t *nid, uint64_t *nprio, uint32_t *nrq, uint8_t *pre8, uint32_t *err_flag, hipStream_t s);
 
+// hqtick_query_resident (census.hip): live tasks per (level, rq) of the resident columns, read-only on them.  levels / n_levels: the table and count of
+// sort_levels (HBM; the count is read by the kernel).  out (HBM, zeroed by the caller): [err u32 x 4][count u32 x MAX_GROUPS], count index level * Q + rq;
+// err[0] bit 0 = a priority the table lacks, bit 1 = rq >= Q, bit 2 = more than MAX_LEVELS levels or more than MAX_GROUPS groups (nothing counted)
+hipError_t ready_census(const uint64_t *prio, const uint32_t *rq, uint64_t n, uint32_t Q, const uint64_t *levels, const uint32_t *n_levels, uint32_t *out, hipStream_t s);
+
 // group key and rank-in-group of the wanted ids (0xFFFFFFFF key = not in the set); after scan_waves, same geometry
 hipError_t rank_of(const uint64_t *ids, const uint16_t *gkey, uint64_t n, const uint32_t *wave_off, WaveGeom geom, const uint64_t *want, uint32_t n_want,
              uint32_t *out_key, uint32_t *out_rank, hipStream_t s);

@@ -46,6 +46,7 @@ def _bind(lib):
     lib.hqtick_upload_ready.argtypes = [C.c_void_p, C.c_uint64, abi.u64p, abi.u64p, abi.u32p, C.c_int]
     lib.hqtick_run_resident.argtypes = [C.c_void_p, P(abi.SnapshotC), P(abi.ResultC)]
     lib.hqtick_query.argtypes = [C.c_void_p, P(abi.SnapshotC), P(abi.QueryWorkersC), P(abi.QueryResultC)]
+    lib.hqtick_query_resident.argtypes = [C.c_void_p, P(abi.SnapshotC), P(abi.QueryWorkersC), P(abi.QueryResultC), abi.u64p]
     lib.hqtick_last_error.restype = C.c_char_p
     lib.hqtick_last_error.argtypes = [C.c_void_p]
     lib.hqtick_abi_version.restype = C.c_uint32
@@ -329,6 +330,25 @@ class Tick:
         if rc < 0:
             raise HqTickError(rc, self._err())
         return abi._np(out.is_loaded, n, np.uint8).astype(bool), bool(out.is_optimal)
+
+    def query_resident(self, snap: abi.Snapshot, fake_ids, fake_total, fake_remaining=None, fake_min_util=None, resident_workers: bool = False):
+        """hqtick_query_resident (ABI 11): the query on the resident ready set; `snap` supplies requests and prefill sets (its task columns are ignored).
+        Returns (is_loaded per fake worker, is_optimal, rq_ready = live resident tasks per request).  resident_workers: the snapshot travels without its
+        worker side (n_workers = HQ_WORKERS_RESIDENT), as a host on hqtick_cluster_* sends it."""
+        sc = snap.to_c(resident_workers=resident_workers)
+        n = len(fake_ids)
+        ids = np.ascontiguousarray(fake_ids, np.uint32)
+        tot = np.ascontiguousarray(np.asarray(fake_total, np.uint64).reshape(-1))
+        rem = np.ascontiguousarray(fake_remaining if fake_remaining is not None else np.full(n, abi.HQ_NO_TIME_LIMIT), np.int64)
+        mu = np.ascontiguousarray(fake_min_util if fake_min_util is not None else np.zeros(n), np.float32)
+        q = abi.QueryWorkersC(n, ids.ctypes.data_as(abi.u32p), tot.ctypes.data_as(abi.u64p), rem.ctypes.data_as(abi.i64p), mu.ctypes.data_as(abi.f32p))
+        out = abi.QueryResultC()
+        Q = len(snap.requests)
+        rq_ready = np.zeros(max(Q, 1), np.uint64)
+        rc = self._lib.hqtick_query_resident(self._ctx, C.byref(sc), C.byref(q), C.byref(out), rq_ready.ctypes.data_as(abi.u64p))
+        if rc < 0:
+            raise HqTickError(rc, self._err())
+        return abi._np(out.is_loaded, n, np.uint8).astype(bool), bool(out.is_optimal), rq_ready[:Q].copy()
 
     def time_kernel(self, which: int, iters: int = 100) -> float:
         """hqtick_time_kernel (measurement library only: Tick(..., measure=True)): average duration (us) of `iters` back-to-back launches of K1 (0) / K4 (1)."""

@@ -40,7 +40,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HQTICK_ABI_VERSION 10u  /* 10: HQTICK_FLAG_NO_TICK_CACHES, hqtick_set_kernel_timing takes any non-zero value but 2 as 1, hqtick_graph_blevel leaves a pending hqtick_ready_consume_last alone; 9: hqtick_graph_blevel / _priorities (extension), hqtick_set_kernel_timing(ctx, 2), a failed CONSUME_IN_TICK tick restores its tasks; 8: HQ_WORKERS_RESIDENT, hqtick_cluster_last_reassigned; 7: hqtick_kernel_stats carries the price-sweep figures of coupled ticks; cluster membership deltas */
+#define HQTICK_ABI_VERSION 11u  /* 11: hqtick_query_resident (hqtick_create still accepts configs written for 10: the config struct is unchanged); 10: HQTICK_FLAG_NO_TICK_CACHES, hqtick_set_kernel_timing takes any non-zero value but 2 as 1, hqtick_graph_blevel leaves a pending hqtick_ready_consume_last alone; 9: hqtick_graph_blevel / _priorities (extension), hqtick_set_kernel_timing(ctx, 2), a failed CONSUME_IN_TICK tick restores its tasks; 8: HQ_WORKERS_RESIDENT, hqtick_cluster_last_reassigned; 7: hqtick_kernel_stats carries the price-sweep figures of coupled ticks; cluster membership deltas */
 
 /* ResourceAmount::MAX                                    common/resources/amount.rs:31 */
 #define HQ_AMOUNT_MAX UINT64_MAX
@@ -576,6 +576,27 @@ int hqtick_comm_destroy(hqtick_ctx *ctx);
  * and the dependency graph of `ctx` are left untouched, so a query may be issued between any two resident ticks. */
 int hqtick_query(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, const hqtick_query_workers *fake,
                  hqtick_query_result *out);
+
+/* compute_new_worker_query() on the RESIDENT ready set (ABI 11): what hqtick_query answers, with the ready set taken from HBM instead of the snapshot.
+ *   Ready set   the context's resident set (hqtick_upload_ready and the hqtick_ready_* / hqtick_graph_* deltas).  Every other field — resources,
+ *               requests, prefill sets — comes from `snapshot`, as for hqtick_run_resident; its task pointers and n_ready are ignored, and so are its
+ *               Retracting entries (they sit in the queues, so the resident set already counts them).
+ *   Workers     query.rs hands create_task_batches and run_scheduling_solver Some(fake_workers) (batches.rs:80-82, solver.rs:57): the real workers
+ *               are not read.  n_workers may be 0, HQ_WORKERS_RESIDENT or a worker list; the answer is the same in all three cases.  (The reference
+ *               does read them in one place: the limit of a multi-node batch counts the free real workers (batches.rs:65-78), and where that limit is
+ *               not 0 its solver panics on the fake workers' groups (solver.rs:104-106).  It answers only where every such limit is 0 — here it is 0 always.)
+ *   Result      `out` exactly as hqtick_query fills it (is_loaded per fake worker, is_optimal; valid until the next call on ctx).  rq_ready (may be
+ *               NULL) [snapshot->n_requests]: the live resident tasks of every request, queue.size() of query.rs:97-124 (multi_node_allocations).
+ *   Device      one read-only census kernel over the priority and request-id columns (12 B per physical slot, tombstones skipped) on the ctx's
+ *               stream, behind every queued delta; its level table and counts go to buffers of the private sub-context that hqtick_query uses,
+ *               where batches, model and solve run.  Nothing of ctx changes: columns, group keys, level table, wave table, the selection that
+ *               hqtick_ready_consume_last replays, the live count, the graph, the Retracting table.
+ *   Errors      HQTICK_E_INVALID without a resident set, and while a selection is pending (a hqtick_run_resident that placed tasks and no
+ *               hqtick_ready_consume_last after it: consume first; under HQTICK_FLAG_CONSUME_IN_TICK nothing is pending).  HQTICK_E_CAPACITY
+ *               beyond 4096 priority levels or 16384 (level, request) groups, as for the tick.
+ *   Shards      a replica of hqtick_set_shard answers as a single context would, with no exchange. */
+int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, const hqtick_query_workers *fake,
+                          hqtick_query_result *out, uint64_t *rq_ready);
 
 /* Text of the last error on this ctx (never NULL). */
 const char *hqtick_last_error(const hqtick_ctx *ctx);

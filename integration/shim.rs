@@ -18,6 +18,9 @@ use crate::internal::server::comm::Comm;
 use crate::internal::server::core::{Core, CoreSplitMut};
 use crate::internal::server::task::{ComputeTasksBuilder, TaskRuntimeState};
 use crate::{TaskId, WorkerId};
+use crate::control::{NewWorkerAllocationResponse, WorkerTypeQuery};                            // new_worker_query (below)
+use crate::gateway::MultiNodeAllocationResponse;
+use crate::resources::{ResourceAmount, ResourceDescriptorKind};
 
 /// TaskId <-> the ABI's u64: job_id in the high half, job_task_id in the low half — preserves `Ord` (common/ids.rs:17-21).
 #[inline] fn pack(t: TaskId) -> u64 { ((t.job_id().as_num() as u64) << 32) | t.job_task_id().as_num() as u64 }
@@ -40,7 +43,10 @@ pub(crate) struct SnapshotArena {
 
 impl SnapshotArena {
     /// One pass over the state the tick reads (INTEGRATION.md §3a has the field-by-field table).
-    pub(crate) fn from_core(core: &Core, now: Instant) -> Self {
+    pub(crate) fn from_core(core: &Core, now: Instant) -> Self { Self::from_core_opts(core, now, true) }
+
+    /// with_tasks = false: the ready set lives in HBM: the task columns stay empty, the prefill sets still travel.
+    pub(crate) fn from_core_opts(core: &Core, now: Instant, with_tasks: bool) -> Self {
         let mut a = SnapshotArena::default();
         let r = core.resource_map().size() as u32;                      // number of resource kinds registered so far
         a.n_resources = r;
@@ -98,7 +104,7 @@ impl SnapshotArena {
         let mut ready: Vec<(u64, u64, u32)> = Vec::new();
         a.prefill_off.push(0);
         for (rq_id, queue) in core.task_queues().iter() {
-            for (prio, ids) in queue.levels() { for t in ids { ready.push((pack(*t), prio.as_raw(), rq_id.as_num())); } }
+            if with_tasks { for (prio, ids) in queue.levels() { for t in ids { ready.push((pack(*t), prio.as_raw(), rq_id.as_num())); } } }
             if let Some((prio, set)) = queue.prefill() {
                 a.prefill_priority.push(prio.as_raw());
                 for t in set.iter() {
@@ -278,4 +284,58 @@ pub(crate) fn run_scheduling_inner(core: &mut Core, comm: &mut impl Comm, now: I
     let res = unsafe { res.assume_init() };                            // arrays inside are owned by the ctx, valid until its next call
     unsafe { apply_result(core, comm, &snap, &res) };                   // (b) apply
     match rc { HQTICK_DONE => SchedulerResult::Done, HQTICK_NEED_MORE_COMPUTE => SchedulerResult::NeedMoreCompute, _ => SchedulerResult::NoProgress }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// compute_new_worker_query (scheduler/query.rs:12-131) for a server on the resident protocol: the ready set is the one in HBM,
+// answered by hqtick_query_resident (ABI 11) without flattening the queues.  Same caveat as above: not compiled in this repository.
+// Call it after hqtick_ready_consume_last (a query between hqtick_run_resident and its consume is refused: HQTICK_E_INVALID).
+pub(crate) fn new_worker_query(core: &mut Core, queries: &[WorkerTypeQuery]) -> Result<NewWorkerAllocationResponse, String> {
+    for query in queries { for item in &query.descriptor.resources { core.get_or_create_resource_id(&item.name); } }   // query.rs:22-26
+    let now = Instant::now();
+    let snap = SnapshotArena::from_core_opts(core, now, false);
+    let r = snap.n_resources as usize;
+    // fake workers  query.rs:28-56: ids above worker_counter, MAX for the named resources a partial query leaves out, time limit, min_utilization
+    let resource_map = core.resource_map().create_resource_id_map();
+    let mut ids: Vec<u32> = Vec::new(); let mut total: Vec<u64> = Vec::new(); let mut rem: Vec<i64> = Vec::new(); let mut min_util: Vec<f32> = Vec::new();
+    let mut next = core.worker_counter() + 1;
+    for query in queries {
+        for _ in 0..query.max_sn_workers {
+            let mut row = vec![0u64; r];
+            if query.partial { for name in resource_map.iter_names() { row[resource_map.get_index(name).unwrap().as_usize()] = ResourceAmount::MAX.as_raw(); } }
+            for item in &query.descriptor.resources {
+                let rid = resource_map.get_index(&item.name).unwrap().as_usize();
+                row[rid] = match &item.kind { ResourceDescriptorKind::Sum { size } => size.as_raw(), kind => kind.size().as_raw() };
+            }
+            ids.push(next); next += 1;
+            total.extend_from_slice(&row);
+            rem.push(query.time_limit.map(|t| t.as_nanos().min(i64::MAX as u128) as i64).unwrap_or(HQ_NO_TIME_LIMIT));
+            min_util.push(query.min_utilization);
+        }
+    }
+    let fake = HqtickQueryWorkers { n_workers: ids.len() as u32, worker_id: ids.as_ptr(), worker_total: total.as_ptr(), worker_remaining_ns: rem.as_ptr(), worker_min_utilization: min_util.as_ptr() };
+    let ffi = snap.as_ffi();
+    let mut out = MaybeUninit::<HqtickQueryResult>::zeroed();
+    let mut rq_ready = vec![0u64; ffi.n_requests as usize];             // queue.size() per request: the host keeps no queues of its own in this mode
+    let ctx = core.scheduler_state_mut().hqtick_ctx();
+    let rc = unsafe { hqtick_query_resident(ctx, &ffi, &fake, out.as_mut_ptr(), rq_ready.as_mut_ptr()) };
+    if rc < 0 { return Err(format!("hqtick_query_resident: {rc}: {}", unsafe { std::ffi::CStr::from_ptr(hqtick_last_error(ctx)) }.to_string_lossy())); }
+    let out = unsafe { out.assume_init() };
+    let loaded = unsafe { std::slice::from_raw_parts(out.is_loaded, out.n_workers as usize) };
+    // single_node_workers_per_query  query.rs:84-95
+    let mut k = 0usize;
+    let single_node_workers_per_query = queries.iter().map(|q| { let n = q.max_sn_workers as usize; let c = loaded[k..k + n].iter().filter(|&&l| l != 0).count() as u32; k += n; c }).collect();
+    // multi_node_allocations  query.rs:97-125, max_allocations = the resident size of the queue
+    let mut multi_node_allocations: Vec<MultiNodeAllocationResponse> = (0..ffi.n_requests).filter_map(|rq| {
+        let rqv = core.get_resource_rq(ResourceRqId::new(rq));
+        if !rqv.is_multi_node() { return None; }                                                 // task_queues.iter(): one queue per request id, empty or not
+        let req = rqv.unwrap_first();
+        let n_nodes = req.n_nodes();
+        queries.iter().enumerate().find_map(|(i, wt)| {
+            if let Some(tl) = wt.time_limit && req.min_time() > tl { return None; }
+            (wt.max_workers_per_allocation >= n_nodes).then(|| MultiNodeAllocationResponse { worker_type: i, worker_per_allocation: n_nodes, max_allocations: rq_ready[rq as usize] as u32 })
+        })
+    }).collect();
+    multi_node_allocations.sort_unstable_by_key(|x| (x.worker_type, x.worker_per_allocation));
+    Ok(NewWorkerAllocationResponse { single_node_workers_per_query, multi_node_allocations })
 }
