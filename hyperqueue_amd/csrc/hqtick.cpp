@@ -55,7 +55,7 @@ struct PlanScratch {
     std::vector<uint32_t> q_total, pf_n, pf_start, seq_taken, pf_drained, zq_taken, new_pf_total, pfl_size, rq_sel_base;
     std::vector<uint32_t> key_seg, key_sum, key_rq, key_var_w, key_ord_off, ord_cnt, key_t_off, key_bits_off;
     std::vector<uint32_t> key_tr;   // per key: c > 0 = stored worker-major by K4 (kernels.h: MapKeys::key_tr)
-    std::vector<uint32_t> list_pos, pf_flag, pf_flag_prev, sn_ok, items, n_assign, asg_qw, has_pf, wm_order, pfq_src, pfq_size, out_off, take_base, mn_first;
+    std::vector<uint32_t> list_pos, pf_flag, pf_flag_prev, sn_ok, items, n_assign, asg_qw, has_pf, wm_order, pfq_src, pfq_size, out_off, take_base, mn_first, q_tnc;
     std::vector<uint8_t> now_mn;
     // the three per-(key | request, worker) tables of the plan are built IN the pinned buffer K4's ride-along workgroups copy from (a memcpy of ~100 KB per
     // tick otherwise): [wpos nkeys * W][wcnt nkeys * W][pfl_j Q * W] at its head, the small tables behind them (phase_c)
@@ -79,7 +79,7 @@ struct hqtick_ctx {
     bool k2_own_stream = false;    // HQTICK_K2_RIDE_ALONG=0: K2 as its own launch on stream2.  Measured (profiles/r02/README.md): K1 alone then takes 4.8 us instead of
                                    // 8.2 us (0.31 vs 0.18 of the HBM roofline), but the second stream's launch + synchronisation make phase A 36 us instead of 28 us:
                                    // the ride-along layout stays the default because the TICK is what counts
-    hipEvent_t ev[12] = {};
+    hipEvent_t ev[14] = {};  // (ev[12] / ev[13]: around the kernels of the ordered view)
     std::string err = "";
     // ready set
     DevBuf d_tid, d_tprio, d_trq; uint64_t n_ready = 0; bool resident = false;  // n_ready = physical length (tombstones included)
@@ -92,6 +92,13 @@ struct hqtick_ctx {
     uint64_t add_staged_n = 0;  // tasks hqtick_ready_add_stage made room for (0: nothing staged)
     // scans
     DevBuf d_set, d_flags, d_levels, d_nlevels, d_wave_tab, d_hist, d_gkey;
+    // the ordered view (order.hip): phase A's general path where the dense (level, request) table does not fit
+    DevBuf d_ord_hist, d_ord_tab, d_perm, d_perm2, d_ord_tiles, d_inv; PinBuf h_ord, h_ordh;
+    bool force_ordered = false;   // HQTICK_ORDERED_VIEW=1 (tests): every tick with a ready set takes the view
+    bool ordered_sticky = false;  // the last dense attempt did not fit: go straight to the view until a view fits the dense caps again
+    bool last_ordered = false;    // the pending selection (last_valid) is one of the view: consume / restore replay it with order_select
+    hqk::OrderSelect last_os{};   // ... its tables (HBM copy of the plan, the permutation)
+    uint32_t dbg_order_runs = 0, dbg_order_levels = 0; bool dbg_order = false; double dbg_order_us = 0;  // hqtick_debug_last_order
     uint32_t lv_seq = 0; bool set_clean = false; bool no_spec_scan = getenv("HQTICK_NO_SPEC_SCAN") != nullptr; bool levels_valid = false; uint32_t cached_L = 0; std::vector<uint64_t> h_levels; bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))  // level table of the previous tick (re-validated by K1 every tick)
     PinBuf h_up, h_up2, h_q, h_a, h_plan, h_rec, h_sinkhdr, h_add, h_addp, h_retr, h_blk, h_k5a, h_lv;   // (h_lv: the level table as k_sort_levels writes it)
     PinBuf h_blkprof; uint32_t n_blkprof = 0; bool block_profile = false;
@@ -371,9 +378,132 @@ void export_batches(hqtick_ctx *ctx, const std::vector<hqhost::TaskBatch> &batch
 struct Scan {  // result of GPU phase A
     uint32_t L = 0, Q = 0, G = 0;
     std::vector<uint64_t> levels;
-    std::vector<uint32_t> hist;  // [G], g = level*Q + rq
+    std::vector<uint32_t> hist;  // [G], g = level*Q + rq  (dense scan only)
     hqk::WaveGeom geom{};
+    // The sparse form every host stage walks: per request its RUNS (nonempty (request, priority) pairs) in descending priority, runs of request q at
+    // [run_off[q], run_off[q + 1]).  run_group = the selection plan's index of the run (dense: level * Q + rq; view: the run index itself), run_level = its
+    // level (dense: index into `levels`; view: the global level rank), run_start = its first position in the view's permutation (view only).
+    bool ordered = false;
+    std::vector<uint32_t> run_off, run_cnt, run_group, run_level, run_start;
+    std::vector<uint64_t> run_prio;
 };
+
+// the runs of a dense histogram: O(L * Q), which the dense scan's caps bound
+void runs_from_hist(Scan &sc) {
+    const uint32_t Q = sc.Q;
+    sc.ordered = false;
+    sc.run_off.assign(Q + 1, 0); sc.run_cnt.clear(); sc.run_group.clear(); sc.run_level.clear(); sc.run_start.clear(); sc.run_prio.clear();
+    for (uint32_t q = 0; q < Q; q++) {
+        for (uint32_t l = 0; l < sc.L; l++) {
+            const uint32_t c = sc.hist[(size_t)l * Q + q];
+            if (!c) continue;
+            sc.run_cnt.push_back(c); sc.run_group.push_back(l * Q + q); sc.run_level.push_back(l); sc.run_prio.push_back(sc.levels[l]);
+        }
+        sc.run_off[q + 1] = (uint32_t)sc.run_cnt.size();
+    }
+}
+
+// The ordered view (order.hip) of the columns prio / rq [0..N) on the buffers of `b` (ctx itself, or hqtick_query_resident's sub-context
+// reading ctx's columns): sc gets the runs, b->d_perm the permutation, b->d_inv its inverse.  One synchronisation after the digit histogram (which passes
+// to run, how many live slots), one after the run table.  Errors are reported on ctx.
+int build_view(hqtick_ctx *ctx, hqtick_ctx *b, const uint64_t *prio, const uint32_t *rq, uint64_t N, uint32_t Q, hipStream_t st, Scan *sc,
+               const std::function<void()> *while_gpu_runs) {
+    const size_t hw = (size_t)hqk::ORDER_DIGITS * 256 + 4;
+    sc->ordered = true; sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
+    sc->run_off.assign(Q + 1, 0); sc->run_cnt.clear(); sc->run_group.clear(); sc->run_level.clear(); sc->run_start.clear(); sc->run_prio.clear();
+    if (N > 0xFFFFFFF0ull) return fail(ctx, HQTICK_E_CAPACITY, "ordered view: more than 2^32 - 16 slots in the ready set");
+    if (!b->d_ord_hist.ensure(hw * 4) || !b->h_ordh.ensure(hw * 4)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ordered view");
+    if (b->timing) HQ_HIP(hipEventRecord(b->ev[12], st));
+    HQ_HIP(hqk::order_digits(prio, rq, N, Q, b->d_ord_hist.as<uint32_t>(), st));
+    HQ_HIP(hipMemcpyAsync(b->h_ordh.p, b->d_ord_hist.p, hw * 4, hipMemcpyDeviceToHost, st));
+    if (while_gpu_runs) (*while_gpu_runs)();
+    HQ_HIP(hipStreamSynchronize(st));
+    const uint32_t *gh = b->h_ordh.as<uint32_t>();
+    if (gh[hqk::ORDER_DIGITS * 256]) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
+    uint64_t n_live = 0;
+    for (uint32_t d = 0; d < 256; d++) n_live += gh[d];
+    if (n_live == 0) return 0;
+    const uint32_t n = (uint32_t)n_live;
+    // the passes: every digit that is not constant over the live set, least significant first (~priority bytes 0-7, then rq bytes 0-3)
+    std::vector<uint32_t> passes;
+    for (uint32_t dg = 0; dg < hqk::ORDER_DIGITS; dg++) {
+        bool constant = false;
+        for (uint32_t d = 0; d < 256 && !constant; d++) constant = gh[dg * 256 + d] == n;
+        if (!constant) passes.push_back(dg);
+    }
+    if (passes.empty()) passes.push_back(0);  // (one pass still drops the tombstones)
+    uint32_t level_after = 0;                 // the level ranks are read off the permutation after the last priority pass (no such pass: one priority, any order)
+    for (uint32_t i = 0; i < passes.size(); i++) if (passes[i] < 8) level_after = i;
+    const uint32_t tiles = hqk::order_tiles(N);
+    const size_t o_rq = 16, o_st = o_rq + (size_t)n * 4, o_rk = o_st + (size_t)n * 4, o_pr = (o_rk + (size_t)n * 4 + 7) & ~(size_t)7, h_bytes = o_pr + (size_t)n * 8 + 16;
+    if (!b->d_perm.ensure((size_t)n * 4 + 16) || !b->d_perm2.ensure((size_t)n * 4 + 16) || !b->d_ord_tab.ensure((size_t)tiles * 256 * 4 + 16) ||
+        !b->d_ord_tiles.ensure(((size_t)tiles + 1) * 4 + 16) || !b->d_inv.ensure(N * 8 + 16) || !b->h_ord.ensure(h_bytes))
+        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ordered view");
+    uint32_t *lrank = b->d_inv.as<uint32_t>() + N, *inv = b->d_inv.as<uint32_t>();  // [inv N][level rank N]
+    uint32_t *err = b->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 1;
+    const uint32_t *in = nullptr;
+    for (uint32_t i = 0; i < passes.size(); i++) {
+        uint32_t *out = ((passes.size() - 1 - i) % 2 == 0) ? b->d_perm.as<uint32_t>() : b->d_perm2.as<uint32_t>();  // (the last pass writes d_perm)
+        HQ_HIP(hqk::order_pass(prio, rq, i == 0 ? N : n, i == 0, in, passes[i], b->d_ord_hist.as<uint32_t>(), b->d_ord_tab.as<uint32_t>(), out, n, err, st));
+        in = out;
+        if (i == level_after) HQ_HIP(hqk::order_levels(prio, in, n, b->d_ord_tiles.as<uint32_t>(), lrank, b->h_ord.dev<uint32_t>() + 1, st));
+    }
+    uint8_t *hd = b->h_ord.dev<uint8_t>();
+    HQ_HIP(hqk::order_runs(prio, rq, in, n, b->d_ord_tiles.as<uint32_t>(), lrank, inv, b->h_ord.dev<uint32_t>(), reinterpret_cast<uint32_t *>(hd + o_rq),
+                           reinterpret_cast<uint32_t *>(hd + o_st), reinterpret_cast<uint32_t *>(hd + o_rk), reinterpret_cast<uint64_t *>(hd + o_pr), st));
+    HQ_HIP(hipMemcpyAsync(b->h_ordh.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 1, err, 4, hipMemcpyDeviceToHost, st));
+    if (b->timing) HQ_HIP(hipEventRecord(b->ev[13], st));
+    HQ_HIP(hipStreamSynchronize(st));
+    if (gh[hqk::ORDER_DIGITS * 256 + 1]) return fail(ctx, HQTICK_E_DEVICE, "ordered view: a pass's counts disagree with the digit histogram");
+    const uint8_t *hh = b->h_ord.as<uint8_t>();
+    const uint32_t nr = reinterpret_cast<const uint32_t *>(hh)[0], nl = reinterpret_cast<const uint32_t *>(hh)[1];
+    if (nr == 0 || nr > n || nl == 0 || nl > nr) return fail(ctx, HQTICK_E_DEVICE, "ordered view: inconsistent run table");
+    const uint32_t *rrq = reinterpret_cast<const uint32_t *>(hh + o_rq), *rst = reinterpret_cast<const uint32_t *>(hh + o_st), *rrk = reinterpret_cast<const uint32_t *>(hh + o_rk);
+    const uint64_t *rpr = reinterpret_cast<const uint64_t *>(hh + o_pr);
+    sc->run_start.assign(rst, rst + nr); sc->run_level.assign(rrk, rrk + nr); sc->run_prio.assign(rpr, rpr + nr);
+    sc->run_cnt.resize(nr); sc->run_group.resize(nr);
+    for (uint32_t r = 0; r < nr; r++) {
+        if (rrq[r] >= Q || (r && rrq[r] < rrq[r - 1])) return fail(ctx, HQTICK_E_DEVICE, "ordered view: runs out of request order");
+        sc->run_cnt[r] = (r + 1 < nr ? rst[r + 1] : n) - rst[r]; sc->run_group[r] = r; sc->run_off[rrq[r] + 1]++;
+    }
+    for (uint32_t q = 0; q < Q; q++) sc->run_off[q + 1] += sc->run_off[q];
+    sc->L = nl; sc->G = nr;
+    if (b->timing) { const double us_ = elapsed_us(b->ev[12], b->ev[13]); b->dbg_order_us = us_ >= 0 ? us_ : 0.0; }
+    b->dbg_order = true; b->dbg_order_runs = nr; b->dbg_order_levels = nl;
+    return 0;
+}
+
+// Phase A on the ordered view: K2 as its own launch, the view, the positions of the Retracting tasks (the same layout of h_retr as k_rank_of's).
+int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc, const std::function<void()> *while_gpu_runs) {
+    const uint32_t W = s->n_workers, R = s->n_resources, Q = s->n_requests;
+    const uint64_t N = ctx->n_ready;
+    const uint32_t nvs = Q ? s->rq_variant_off[Q] : 0;
+    const size_t nwv = (size_t)W * nvs, o_tmc = 16, o_fl = o_tmc + nwv * 4, bytes = o_fl + nwv + 16;
+    if (!ctx->h_a.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc phase A");
+    unsigned char *h = ctx->h_a.as<unsigned char>(), *hd = ctx->h_a.dev<unsigned char>();
+    memset(h, 0, 16);
+    UpView uv; int rc;
+    if (ctx->cluster_valid) { if ((rc = resident_tables(ctx, s, W, &uv))) return rc; }
+    else if ((rc = upload_tables(ctx, s, W, s->worker_total, s->worker_free, s->worker_remaining_ns, ctx->h_up, &uv))) return rc;
+    HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream));
+    ev->flags = h + o_fl; ev->tmc = reinterpret_cast<const uint32_t *>(h + o_tmc);
+    ctx->levels_valid = false;  // (the dense level table is rediscovered when a tick fits the dense caps again)
+    if ((rc = build_view(ctx, ctx, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, ctx->stream, sc, while_gpu_runs))) return rc;
+    if (!ctx->force_ordered && sc->L <= hqk::MAX_LEVELS && (uint64_t)sc->L * Q <= hqk::MAX_GROUPS) ctx->ordered_sticky = false;  // the next tick fits the dense scan again
+    if (s->n_retracting) {  // where do the Retracting tasks sit in their queues?  (mapping.rs:66-80 treats them apart)
+        const uint32_t nr = s->n_retracting;
+        if (!ctx->h_retr.ensure((size_t)nr * 16 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc retracting");
+        memcpy(ctx->h_retr.p, s->retracting_task, (size_t)nr * 8);
+        uint8_t *rd = ctx->h_retr.dev<uint8_t>();
+        if (sc->run_cnt.empty()) { uint32_t *k = reinterpret_cast<uint32_t *>(ctx->h_retr.as<uint8_t>() + (size_t)nr * 8); for (uint32_t i = 0; i < nr; i++) k[i] = 0xFFFFFFFFu; }
+        else {
+            HQ_HIP(hqk::order_rank_of(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, ctx->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(rd), nr,
+                                      reinterpret_cast<uint32_t *>(rd + (size_t)nr * 8), reinterpret_cast<uint32_t *>(rd + (size_t)nr * 12), ctx->stream));
+            HQ_HIP(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    return 0;
+}
 
 // GPU phase A: K2 on the real workers, level table (cached across ticks, re-validated by K1), K1 + K1b on the ready set in
 // ctx->d_t*.  One stream synchronisation in the steady state.
@@ -382,11 +512,15 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
     const uint32_t W = s->n_workers, R = s->n_resources, Q = s->n_requests;
     const uint64_t N = ctx->n_ready;
     sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
+    runs_from_hist(*sc);  // (no run until the scan has counted)
     if (!ctx->d_set.ensure((size_t)(hqk::PRIO_SET_CAP + hqk::MAX_LEVELS) * 8) || !ctx->h_lv.ensure((size_t)(hqk::MAX_LEVELS + 4) * 8) || !ctx->d_flags.ensure(64) || !ctx->d_levels.ensure((size_t)(hqk::MAX_LEVELS + 2) * 8) || !ctx->d_nlevels.ensure(64))   // (a 40-byte head: count + the first four levels, kernels.hip: k_sort_levels)
         return fail(ctx, HQTICK_E_DEVICE, "hipMalloc phase A");
     const bool scan = N != 0 && Q != 0;
     const uint32_t nvs = Q ? s->rq_variant_off[Q] : 0;
     const size_t nwv = (size_t)W * nvs;
+    ctx->dbg_order = false;
+    // the ordered view where the dense table does not fit: forced (HQTICK_ORDERED_VIEW=1), or the last dense attempt did not fit
+    if (scan && (ctx->force_ordered || ctx->ordered_sticky)) return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs);
     for (int attempt = 0; attempt < 2; attempt++) {
         uint32_t L = 0;
         bool levels_fresh = false;  // the level table was (re)built by this attempt
@@ -414,7 +548,9 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
                 // discovery, sized for four levels, and reads the table and its length from HBM (kernels.h: level_hist, n_levels_dev): no host round trip, no idle GPU
                 // between the two (K1 behind a 15-33 us gap took 6.4-7.2 us against 5.5, profiles/r06).  More than four levels: K1 refuses, the table is read below
                 // and this loop's second pass launches the general variant.
-                spec = attempt == 0 && (uint64_t)4 * Q <= 64 && !ctx->no_spec_scan;
+                // Not with Retracting tasks: k_rank_of reads the group keys K1 leaves, and a refused speculative K1 leaves none (a fresh context's key column is
+                // uninitialised: the keys would index the slice table out of bounds).
+                spec = attempt == 0 && (uint64_t)4 * Q <= 64 && !ctx->no_spec_scan && s->n_retracting == 0;
                 if (spec) L = 4;   // (levels_valid stays false until the table has been read, after the scan)
                 else
                 {   // wait on the kernel's own completion word (the stream synchronisation is the fallback after 2 s)
@@ -427,7 +563,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
                 if (!spec) {
                 L = hl[0];
                 const uint32_t flags[2] = {hl[1], hl[2]};
-                if (flags[1] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return fail(ctx, HQTICK_E_CAPACITY, "more than 4096 distinct priority levels in the ready set");
+                if (flags[1] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) { ctx->ordered_sticky = true; return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs); }  // more than 4096 levels
                 if (L == 0) return fail(ctx, HQTICK_E_DEVICE, "level discovery returned no level");
                 ctx->h_levels.assign(ctx->h_lv.as<uint64_t>() + 2, ctx->h_lv.as<uint64_t>() + 2 + L);
                 ctx->set_clean = true;
@@ -439,7 +575,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
             }
             L = spec ? 4u : ctx->cached_L;
             uint64_t G64 = (uint64_t)L * Q;
-            if (G64 > hqk::MAX_GROUPS) return fail(ctx, HQTICK_E_CAPACITY, "levels x requests exceeds 16384 groups");
+            if (G64 > hqk::MAX_GROUPS) { ctx->ordered_sticky = true; return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs); }  // levels x requests over 16384 groups
             sc->L = L; sc->G = (uint32_t)G64;
         }
         // host-visible outputs of phase A, written in place by the kernels: [flags 16][hist G*4][vtmc nwv*4][vflags nwv]
@@ -490,7 +626,11 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
         if (spec) {   // the discovery's own results, now that everything behind it has finished too
             const uint32_t *hl = ctx->h_lv.as<uint32_t>();
             const uint32_t La = hl[0];
-            if (hl[2] || La == 0xFFFFFFFFu || La > hqk::MAX_LEVELS) { ctx->levels_valid = false; return fail(ctx, HQTICK_E_CAPACITY, "more than 4096 distinct priority levels in the ready set"); }
+            if (hl[2] || La == 0xFFFFFFFFu || La > hqk::MAX_LEVELS) {  // more than 4096 levels:
+                // the view.  while_gpu_runs runs again: it has published the ADDRESSES of K2's output in the dense layout of h_a, and phase_a_ordered lays
+                // h_a out anew (fill_problem is idempotent)
+                ctx->levels_valid = false; ctx->ordered_sticky = true; return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs);
+            }
             if (La == 0) { ctx->levels_valid = false; return fail(ctx, HQTICK_E_DEVICE, "level discovery returned no level"); }
             ctx->h_levels.assign(ctx->h_lv.as<uint64_t>() + 2, ctx->h_lv.as<uint64_t>() + 2 + La);
             ctx->levels_valid = true; ctx->cached_L = La; ctx->set_clean = true;
@@ -520,6 +660,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
             if (ctx->timing || ctx->timing_k1) { const double us_ = elapsed_us(ctx->ev[2], ctx->ev[3]); if (us_ >= 0) ctx->stats.level_hist_us = us_; }
             if (ctx->timing && !spec) { const double us_ = elapsed_us(ctx->ev[0], ctx->ev[8]); if (us_ >= 0) ctx->stats.scan_us = us_; }  // (a speculative scan shares ev[0] with the discovery: K1b untimed on that tick)
         }
+        runs_from_hist(*sc);
         return 0;
     }
     return 0;
@@ -530,7 +671,7 @@ std::vector<hqhost::QueueLevels> queue_levels(const Scan &sc, const hqtick_snaps
     std::vector<hqhost::QueueLevels> qs(s->n_requests);
     for (uint32_t q = 0; q < s->n_requests; q++) {
         auto &lv = qs[q].levels;
-        for (uint32_t l = 0; l < sc.L; l++) { uint32_t c = sc.hist[(size_t)l * sc.Q + q]; if (c) lv.push_back({sc.levels[l], c}); }
+        for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) lv.push_back({sc.run_prio[r], sc.run_cnt[r]});
         uint32_t pfn = s->prefill_off ? s->prefill_off[q + 1] - s->prefill_off[q] : 0;
         if (pfn) {
             uint64_t pp = s->prefill_priority[q];
@@ -682,7 +823,7 @@ struct TickRun {
         : ctx(c), s(snap), out(o), use_resident(resident), ps(c->plan), pb(c->pb), W(snap->n_workers), R(snap->n_resources), Q(snap->n_requests) {}
 
     void mark() { if (ctx->ntl < 32) ctx->tl[ctx->ntl++] = now_us() - t0; }
-    uint32_t hist(uint32_t l, uint32_t q) const { return sc.hist[(size_t)l * Q + q]; }
+    uint32_t n_groups() const { return sc.ordered ? (uint32_t)sc.run_cnt.size() : sc.G; }  // entries of the selection plan
 
     // host mirror of the K5 arithmetic: the worker that receives the task at index idx of key k's take_tasks() vector
     uint32_t worker_of(uint32_t k, uint32_t idx) {
@@ -724,12 +865,10 @@ struct TickRun {
         // priority of the queue, else [prefilled][all levels]   (taskqueue.rs:320-355)
         ps.q_total.assign(Q, 0); ps.pf_n.assign(Q, 0); ps.pf_start.assign(Q, 0); ps.seq_taken.assign(Q, 0);
         for (uint32_t q = 0; q < Q; q++) {
-            for (uint32_t l = 0; l < L; l++) ps.q_total[q] += hist(l, q);
+            const uint32_t r0 = sc.run_off[q], r1 = sc.run_off[q + 1];
+            for (uint32_t r = r0; r < r1; r++) ps.q_total[q] += sc.run_cnt[r];
             ps.pf_n[q] = s->prefill_off ? s->prefill_off[q + 1] - s->prefill_off[q] : 0;
-            if (ps.pf_n[q]) {
-                uint32_t first = L; for (uint32_t l = 0; l < L; l++) if (hist(l, q)) { first = l; break; }
-                ps.pf_start[q] = (first < L && sc.levels[first] == s->prefill_priority[q]) ? hist(first, q) : 0;
-            }
+            if (ps.pf_n[q]) ps.pf_start[q] = (r0 < r1 && sc.run_prio[r0] == s->prefill_priority[q]) ? sc.run_cnt[r0] : 0;
         }
         nkeys = (uint32_t)cnt.keys.size();
         ps.key_seg.assign(nkeys, 0); ps.key_sum.assign(nkeys, 0); ps.key_rq.assign(nkeys, 0); ps.key_var_w.assign((nkeys + 3) / 4 + 1, 0);
@@ -739,7 +878,8 @@ struct TickRun {
         {   // the big tables live at the head of the pinned plan buffer; everything else of the plan (phase_c) is a few KB behind them
             ps.plan_head_words = (size_t)nkeys * W * 2 + (size_t)Q * W;
             size_t n_cnt0 = 0; for (uint32_t k = 0; k < nkeys; k++) n_cnt0 += cnt.key_size(k);
-            const size_t small = (size_t)9 * (nkeys + 4) + n_cnt0 + (size_t)6 * (Q + 2) + (W + 2) + (size_t)4 * sc.G + (size_t)2 * s->n_retracting + 64;
+            const size_t small = (size_t)9 * (nkeys + 4) + n_cnt0 + (size_t)6 * (Q + 2) + (W + 2) + (size_t)4 * n_groups() + (size_t)2 * s->n_retracting + 64 +
+                                 (sc.ordered ? (size_t)3 * (Q + 2) + (size_t)2 * n_groups() + 8 : 0);  // (the view's tables: run_off, q_tnc, run_start, run_rank)
             if (!ctx->h_plan.ensure((ps.plan_head_words + small) * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc plan");
             ps.wpos = ctx->h_plan.as<uint32_t>(); ps.wcnt = ps.wpos + (size_t)nkeys * W; ps.pfl_j = ps.wcnt + (size_t)nkeys * W; ps.pfl_rows = 0;
         }
@@ -849,8 +989,15 @@ struct TickRun {
             const uint32_t *rkey = reinterpret_cast<const uint32_t *>(rh + (size_t)nr * 8), *rrank = reinterpret_cast<const uint32_t *>(rh + (size_t)nr * 12);
             for (uint32_t i = 0; i < nr; i++) {
                 if (rkey[i] == 0xFFFFFFFFu || Q == 0) return fail(ctx, HQTICK_E_INVALID, "a retracting task is not in the ready set");
-                const uint32_t l = rkey[i] / Q, q = rkey[i] % Q;
-                uint32_t z = rrank[i]; for (uint32_t l2 = 0; l2 < l; l2++) z += hist(l2, q);         // position in the queue (levels, then id)
+                uint32_t q, z;                                                                        // request and position in its queue (levels, then id)
+                if (sc.ordered) {  // the view: rkey = rq, rrank = position in the permutation, whose segment of q starts at its first run
+                    q = rkey[i];
+                    if (q >= Q || sc.run_off[q] == sc.run_off[q + 1]) return fail(ctx, HQTICK_E_INVALID, "a retracting task is not in the ready set");
+                    z = rrank[i] - sc.run_start[sc.run_off[q]];
+                } else {
+                    const uint32_t l = rkey[i] / Q; q = rkey[i] % Q;
+                    z = rrank[i]; for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1] && sc.run_level[r] < l; r++) z += sc.run_cnt[r];
+                }
                 const uint32_t p = z < ps.pf_start[q] ? z : z + ps.pf_n[q];                             // position in the logical take sequence
                 retr_pos.push_back({q, z});
                 if (p >= ps.seq_taken[q]) continue;                                                   // stays in its queue
@@ -898,16 +1045,16 @@ struct TickRun {
         pfq_rq.clear();
         {
             // state of every queue after the takes: first level that still has tasks
-            std::vector<int> top_level(Q, -1); std::vector<uint32_t> top_left(Q, 0);
+            std::vector<int64_t> top_run(Q, -1); std::vector<uint32_t> top_left(Q, 0);  // (the run that is the queue's top after the takes)
             uint64_t global_top = 0;
             for (uint32_t q = 0; q < Q; q++) {
                 uint32_t left = ps.zq_taken[q];
-                for (uint32_t l = 0; l < L; l++) { uint32_t h = hist(l, q); if (h > left) { top_level[q] = (int)l; top_left[q] = h - left; break; } left -= h; }
-                if (top_level[q] >= 0) global_top = std::max(global_top, sc.levels[top_level[q]]);  // TaskQueues::top_priority  taskqueue.rs:62-68
+                for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) { uint32_t h = sc.run_cnt[r]; if (h > left) { top_run[q] = r; top_left[q] = h - left; break; } left -= h; }
+                if (top_run[q] >= 0) global_top = std::max(global_top, sc.run_prio[top_run[q]]);  // TaskQueues::top_priority  taskqueue.rs:62-68
             }
             size_t prev_row = SIZE_MAX;  // the pfl_j row that belongs to pf_flag_prev
             for (uint32_t q = 0; q < Q; q++) {
-                if (top_level[q] < 0 || sc.levels[top_level[q]] != global_top) continue;
+                if (top_run[q] < 0 || sc.run_prio[top_run[q]] != global_top) continue;
                 bool pf_left = ps.pf_n[q] > ps.pf_drained[q];
                 uint32_t tsz = (pf_left && s->prefill_priority[q] != global_top) ? 0 : top_left[q];  // top_size_no_prefill  taskqueue.rs:241-253
                 uint32_t size = tsz > ctx->cfg.proactive_filling_reserve ? tsz - ctx->cfg.proactive_filling_reserve : 0;
@@ -952,12 +1099,15 @@ struct TickRun {
         ps.rq_sel_base.assign(Q + 1, 0);
         for (uint32_t q = 0; q < Q; q++) ps.rq_sel_base[q + 1] = ps.rq_sel_base[q] + ps.zq_taken[q] + ps.new_pf_total[q];
         n_sel = ps.rq_sel_base[Q];
-        ps.take_base.assign((size_t)4 * sc.G, 0);  // [take][base][tnc][tsb] per (level, rq) group (kernels.hip: SelPlanN)
-        for (uint32_t q = 0; q < Q; q++) {
+        // (the view selects per request from rq_sel_base alone — order.hip: k_order_select — and needs only the worker-major form per request)
+        const size_t G = sc.ordered ? 0 : sc.G;
+        ps.take_base.assign((size_t)4 * G, 0);  // [take][base][tnc][tsb] per (level, rq) group (kernels.hip: SelPlanN)
+        ps.q_tnc.assign(sc.ordered ? Q : 0, 0);
+        if (!sc.ordered) for (uint32_t q = 0; q < Q; q++) {
             uint32_t want = ps.zq_taken[q] + ps.new_pf_total[q], cum = 0;
-            for (uint32_t l = 0; l < L; l++) {
-                uint32_t h = hist(l, q), t = want > cum ? std::min(h, want - cum) : 0;
-                ps.take_base[(size_t)l * Q + q] = t; ps.take_base[(size_t)sc.G + (size_t)l * Q + q] = ps.rq_sel_base[q] + cum;
+            for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) {
+                const uint32_t h = sc.run_cnt[r], t = want > cum ? std::min(h, want - cum) : 0, g = sc.run_group[r];
+                ps.take_base[g] = t; ps.take_base[G + g] = ps.rq_sel_base[q] + cum;
                 cum += h;
             }
         }
@@ -966,7 +1116,8 @@ struct TickRun {
             for (uint32_t k = 0; k < nkeys; k++) {
                 if (!ps.key_tr[k]) continue;
                 const uint32_t q = ps.key_rq[k], n = ps.key_ord_off[k + 1] - ps.key_ord_off[k];
-                for (uint32_t l = 0; l < L; l++) { ps.take_base[(size_t)2 * sc.G + (size_t)l * Q + q] = (n << 16) | ps.key_tr[k]; ps.take_base[(size_t)3 * sc.G + (size_t)l * Q + q] = ps.rq_sel_base[q]; }
+                if (sc.ordered) { ps.q_tnc[q] = (n << 16) | ps.key_tr[k]; continue; }
+                for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) { ps.take_base[2 * G + sc.run_group[r]] = (n << 16) | ps.key_tr[k]; ps.take_base[3 * G + sc.run_group[r]] = ps.rq_sel_base[q]; }
             }
         }
         for (uint32_t q : pfq_rq) { ps.pfq_src.push_back(ps.rq_sel_base[q] + ps.zq_taken[q]); ps.pfq_size.push_back(ps.pfl_size[q]); }
@@ -985,7 +1136,7 @@ struct TickRun {
         }
         n_rec = ps.out_off[W];
         may_reorder = sc.L > 1 || !ps.holes.empty() || (s->prefill_off && s->prefill_off[Q] > 0);
-        if (hqk::expand_mapping_lds(max_items, nkeys, compact ? max_out : 0, may_reorder) > 150 * 1024) return fail(ctx, HQTICK_E_CAPACITY, "a worker receives more tasks in one tick than the mapping kernel stages in LDS");
+        if (hqk::expand_mapping_lds(max_items, nkeys, compact ? max_out : 0, may_reorder, sc.ordered) > 150 * 1024) return fail(ctx, HQTICK_E_CAPACITY, "a worker receives more tasks in one tick than the mapping kernel stages in LDS");
         if (max_nk > hqk::SWEEP_MAX_WORKERS) return fail(ctx, HQTICK_E_CAPACITY, "more than 24576 workers share one (request, variant) placement: beyond the round-robin kernel's LDS staging");
         return 0;
     }
@@ -1063,7 +1214,7 @@ struct TickRun {
         h_rec_task = ctx->h_rec.as<uint64_t>(); h_rec_var = ctx->h_rec.as<uint8_t>() + o_rv; h_rec_kind = ctx->h_rec.as<uint8_t>() + o_rk;
         mn_ids = reinterpret_cast<uint64_t *>(ctx->h_rec.as<uint8_t>() + o_mn);
         if (n_sel) {
-            if (!ctx->d_sel_task.ensure((size_t)n_sel * 8) || !ctx->d_sel_level.ensure((size_t)n_sel * 2 + 2))
+            if (!ctx->d_sel_task.ensure((size_t)n_sel * 8) || !ctx->d_sel_level.ensure((size_t)n_sel * (sc.ordered ? 4 : 2) + 4))
                 return fail(ctx, HQTICK_E_DEVICE, "hipMalloc selection");
             // the plan in one upload: the big tables are already at the head of the pinned buffer (plan_keys / plan_prefill), the small ones go behind them
             uint32_t *hp = ctx->h_plan.as<uint32_t>();
@@ -1074,6 +1225,8 @@ struct TickRun {
                    o_boff = put(ps.key_bits_off), o_tr = put(ps.key_tr), o_base = put(ps.rq_sel_base), o_pfs = put(ps.pf_start), o_pfn = put(ps.pf_n),
                    o_pqs = put(ps.pfq_src), o_pqz = put(ps.pfq_size), o_out = put(ps.out_off);
             size_t o_tb = put(ps.take_base);
+            size_t o_roff = 0, o_qtnc = 0, o_rst = 0, o_rrk = 0;  // the view's tables (order.hip: k_order_select)
+            if (sc.ordered) { o_roff = put(sc.run_off); o_qtnc = put(ps.q_tnc); o_rst = put(sc.run_start); o_rrk = put(sc.run_level); }
             if (cur & 1) hp[cur++] = 0;  // 8-byte alignment for the u64 hole list
             const size_t o_holes = cur;
             for (uint64_t hk : ps.holes) { hp[cur++] = (uint32_t)(hk & 0xFFFFFFFFu); hp[cur++] = (uint32_t)(hk >> 32); }
@@ -1097,10 +1250,23 @@ struct TickRun {
             ctx->last_n_sel = n_sel; ctx->last_consumed = false;
             const bool consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;  // K4 writes the tombstones of what it selects
             ctx->last_geom = sc.geom; ctx->last_L = L; ctx->last_Q = Q; ctx->last_G = sc.G; ctx->last_tb = o_tb; ctx->last_plan_bytes = plan_words * 4; ctx->last_valid = true;
+            ctx->last_ordered = sc.ordered;
+            if (sc.ordered) {  // the plan into HBM, then K4 on the view (order.hip)
+                HQ_HIP(hqk::copy_pinned_to_hbm(ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4, ctx->stream));
+                hqk::OrderSelect os{};
+                os.task_id = ctx->d_tid.as<uint64_t>(); os.perm = ctx->d_perm.as<uint32_t>(); os.n_live = sc.run_cnt.empty() ? 0u : sc.run_start.back() + sc.run_cnt.back(); os.Q = Q;
+                os.n_runs = (uint32_t)sc.run_cnt.size(); os.rq_sel_base = d + o_base; os.run_off = d + o_roff; os.run_start = d + o_rst; os.run_rank = d + o_rrk; os.q_tnc = d + o_qtnc;
+                os.sel_task = ctx->d_sel_task.as<uint64_t>(); os.sel_rank = ctx->d_sel_level.as<uint32_t>(); os.err = ctx->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2;
+                ctx->last_os = os;  // (what hqtick_ready_consume_last and the restore of HQTICK_FLAG_CONSUME_IN_TICK replay)
+                if (consume_in_tick) { os.mark_rq = ctx->d_trq.as<uint32_t>(); os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 1; }
+                if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
+                HQ_HIP_TIMED(hqk::order_select(os, n_sel, ctx->stream));
+            } else {
             if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
             HQ_HIP_TIMED(hqk::select_scatter(ctx->d_tid.as<uint64_t>(), ctx->d_gkey.as<uint16_t>(), N, Q, sc.G, sc.geom, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + o_tb,
                                 d + o_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4,
                                 consume_in_tick ? ctx->d_trq.as<uint32_t>() : nullptr, ctx->stream, consume_in_tick ? 1u : 0u));
+            }
             if (consume_in_tick) { ctx->n_live -= n_sel; ctx->last_consumed = true; ctx->consumed_unconfirmed = true; }  // (confirmed when the tick returns without an error: run_tick)
             if (!sweep_launched && n_tr < nkeys) {
                 if (ctx->timing) hqk::time_next_launch(ctx->ev[1], ctx->ev[6]);
@@ -1127,9 +1293,15 @@ struct TickRun {
             if (compact) co = hqk::CompactOut{reinterpret_cast<uint32_t *>(drec), reinterpret_cast<uint2 *>(drec + o_rs), reinterpret_cast<uint32_t *>(drec + o_rf),
                                               delta16 ? reinterpret_cast<uint16_t *>(drec) : nullptr};
             bool expand_is_last = false;
-            HQ_HIP_LAST(hqk::expand_mapping(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), Q, max_items, k_task, k_var, k_kind,
+            if (sc.ordered) HQ_HIP_LAST(hqk::expand_mapping_wide(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint32_t>(), max_items, k_task, k_var, k_kind,
+                                                           reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream), expand_is_last);
+            else HQ_HIP_LAST(hqk::expand_mapping(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), Q, max_items, k_task, k_var, k_kind,
                                 reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream), expand_is_last);
             if (!cnt.mn_rq.empty()) expand_is_last = false;  // copies of the multi-node task ids follow
+            if (sc.ordered) {  // the selection's guard word follows (order.hip: a position outside its request's segment)
+                HQ_HIP(hipMemcpyAsync(ctx->h_ordh.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2, ctx->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+                expand_is_last = false;
+            }
             // multi-node tasks: the heads of their queues
             {
                 size_t pos = 0;
@@ -1144,6 +1316,7 @@ struct TickRun {
             if (expand_is_last) HQ_HIP(hipEventSynchronize(ctx->ev[11])); else HQ_HIP(hipStreamSynchronize(ctx->stream));
             ctx->sweep_inflight = false;
             if (flags[0]) return fail(ctx, HQTICK_E_CAPACITY, "mapping kernel capacity exceeded");
+            if (sc.ordered && ctx->h_ordh.as<uint32_t>()[hqk::ORDER_DIGITS * 256 + 2]) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the selection left its request's segment");
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[4], ctx->ev[5]); if (us_ >= 0) ctx->stats.select_us = us_; }
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[1], ctx->ev[6]); if (us_ >= 0) ctx->stats.sweep_us = us_; }
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[7], ctx->ev[11]); if (us_ >= 0) ctx->stats.other_us = us_; }
@@ -1321,7 +1494,12 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             // recoverable (k_restore_consumed: one pass over the key and request-id columns).  Only if THAT fails is the set dropped and the host uploads it again.
             const std::string why = ctx->err;
             bool restored = false;
-            if (hipStreamSynchronize(ctx->stream) == hipSuccess && ctx->last_valid && ctx->last_Q && ctx->h_q.ensure(64)) {
+            const bool synced = hipStreamSynchronize(ctx->stream) == hipSuccess;
+            if (synced && ctx->last_valid && ctx->last_ordered) {  // the view: the same selection writes the request ids back
+                hqk::OrderSelect os = ctx->last_os;
+                os.mark_rq = ctx->d_trq.as<uint32_t>(); os.mark_value = 0; os.mark_and_select = 0;
+                if (hqk::order_select(os, ctx->last_n_sel, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess) { ctx->n_live += ctx->last_n_sel; restored = true; }
+            } else if (synced && ctx->last_valid && !ctx->last_ordered && ctx->last_Q && ctx->h_q.ensure(64)) {
                 uint32_t *cntp = ctx->h_q.as<uint32_t>();
                 cntp[0] = 0;
                 if (hqk::ready_restore_consumed(ctx->d_gkey.as<uint16_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready, ctx->last_Q, ctx->h_q.dev<uint32_t>(), ctx->stream) == hipSuccess &&
@@ -1381,6 +1559,7 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     if (const char *e = getenv("HQTICK_K2_RIDE_ALONG")) { ctx->k2_own_stream = atoi(e) == 0; ctx->k2_on_hist = atoi(e) == 1; }
     if (const char *e = getenv("HQTICK_CHECK_CLUSTER")) ctx->cluster_check = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_WAIT_ON_KERNEL")) ctx->wait_on_kernel = atoi(e) != 0;
+    if (const char *e = getenv("HQTICK_ORDERED_VIEW")) ctx->force_ordered = atoi(e) != 0;  // (tests: every tick on the ordered view)
     {
         bool price = true; uint32_t min_cols = 0;
         if (const char *e = getenv("HQTICK_PRICE")) price = atoi(e) != 0;
@@ -1407,7 +1586,8 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     delete ctx->pricer; ctx->pricer = nullptr;
     DevBuf *bufs[] = {&ctx->d_tid, &ctx->d_tprio, &ctx->d_trq, &ctx->d_set, &ctx->d_flags, &ctx->d_levels, &ctx->d_nlevels, &ctx->d_wave_tab, &ctx->d_hist,
                       &ctx->d_up, &ctx->d_vflags, &ctx->d_vtmc, &ctx->d_sel_task, &ctx->d_gkey,
-                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_tid2, &ctx->d_tprio2, &ctx->d_trq2, &ctx->d_slice, &ctx->d_add, &ctx->d_pre8, &ctx->d_blk, &ctx->d_cluster};
+                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_tid2, &ctx->d_tprio2, &ctx->d_trq2, &ctx->d_slice, &ctx->d_add, &ctx->d_pre8, &ctx->d_blk, &ctx->d_cluster,
+                      &ctx->d_ord_hist, &ctx->d_ord_tab, &ctx->d_perm, &ctx->d_perm2, &ctx->d_ord_tiles, &ctx->d_inv};
     for (DevBuf *b : bufs) b->release();
     ctx->h_cl.release(); ctx->h_cld.release(); ctx->d_cluster2.release();
     if (ctx->cl_ev) hipEventDestroy(ctx->cl_ev);
@@ -1415,7 +1595,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     hipSetDevice(ctx->device);
     if (ctx->comm) { rccl_destroy_comm(ctx); }
     ctx->graph.release();
-    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_a.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_add.release(); ctx->h_addp.release(); ctx->h_retr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release(); ctx->h_lv.release();
+    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_a.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_add.release(); ctx->h_addp.release(); ctx->h_retr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release(); ctx->h_lv.release(); ctx->h_ord.release(); ctx->h_ordh.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1549,7 +1729,13 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) {
     if (!ctx->last_valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_consume_last needs a preceding hqtick_run_resident");
     HQ_HIP(hipSetDevice(ctx->device));
     const uint32_t *d = ctx->d_map.as<uint32_t>();
-    // the selection of the last tick once more, writing tombstones instead of the selected ids (same offsets table, same plan)
+    // the selection of the last tick once more, writing tombstones instead of the selected ids (same offsets table, same plan; the view's: the same
+    // permutation — which reads no priority, so hqtick_graph_blevel between the tick and this call changes nothing)
+    if (ctx->last_ordered) {
+        hqk::OrderSelect os = ctx->last_os;
+        os.mark_rq = ctx->d_trq.as<uint32_t>(); os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 0;
+        HQ_HIP(hqk::order_select(os, ctx->last_n_sel, ctx->stream));
+    } else
     HQ_HIP(hqk::select_scatter(ctx->d_tid.as<uint64_t>(), ctx->d_gkey.as<uint16_t>(), ctx->n_ready, ctx->last_Q, ctx->last_G, ctx->last_geom, ctx->d_wave_tab.as<uint32_t>(),
                                ctx->h_plan.as<uint32_t>() + ctx->last_tb, d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), nullptr, nullptr, 0,
                                ctx->d_trq.as<uint32_t>(), ctx->stream));
@@ -2077,6 +2263,7 @@ static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_quer
 // stream — behind every add, remove, append and compaction queued there — and write only buffers of the query sub-context `q`; one synchronisation.
 static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc) {
     sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
+    runs_from_hist(*sc);
     const uint64_t N = ctx->n_ready;
     if (N == 0 || Q == 0 || ctx->n_live == 0) return 0;
     const size_t tab_words = 4 + (size_t)std::min<uint64_t>(hqk::MAX_GROUPS, (uint64_t)Q * hqk::MAX_LEVELS);   // [err x 4][counts]: what the census can write for this Q
@@ -2098,16 +2285,18 @@ static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc)
     HQ_HIP(hipMemcpyAsync(q->h_a.p, q->d_hist.p, tab_words * 4, hipMemcpyDeviceToHost, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     const uint32_t L = hl[0];
-    if (hl[2] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return fail(ctx, HQTICK_E_CAPACITY, "more than 4096 distinct priority levels in the ready set");
+    // beyond the dense caps: the ordered view's run table, built on the sub-context's buffers from ctx's columns
+    if (hl[2] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return build_view(ctx, q, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, ctx->stream, sc, nullptr);
     q->set_clean = true;
     if (L == 0) return 0;   // only tombstones
-    if ((uint64_t)L * Q > hqk::MAX_GROUPS) return fail(ctx, HQTICK_E_CAPACITY, "levels x requests exceeds 16384 groups");
+    if ((uint64_t)L * Q > hqk::MAX_GROUPS) return build_view(ctx, q, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, ctx->stream, sc, nullptr);
     const uint32_t *h = q->h_a.as<uint32_t>();
     if (h[0] & 2u) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
     if (h[0]) return fail(ctx, HQTICK_E_DEVICE, "census: level table inconsistent with the ready set");
     sc->L = L; sc->G = L * Q;
     sc->levels.assign(q->h_lv.as<uint64_t>() + 2, q->h_lv.as<uint64_t>() + 2 + L);
     sc->hist.assign(h + 4, h + 4 + sc->G);
+    runs_from_hist(*sc);
     return 0;
 }
 
@@ -2145,7 +2334,7 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
     if (int rc = census_resident(ctx, q, Q, &sc)) return rc;
     if (rq_ready) {
         for (uint32_t r = 0; r < Q; r++) rq_ready[r] = 0;
-        for (uint32_t l = 0; l < sc.L; l++) for (uint32_t r = 0; r < Q; r++) rq_ready[r] += sc.hist[(size_t)l * Q + r];
+        for (uint32_t r = 0; r < Q; r++) for (uint32_t k = sc.run_off[r]; k < sc.run_off[r + 1]; k++) rq_ready[r] += sc.run_cnt[k];
     }
     // batches, model and solve on the sub-context, as hqtick_query
     int rc;
@@ -2242,6 +2431,13 @@ uint32_t hqtick_debug_last_mn(const uint32_t **rq, const uint32_t **off, const u
     if (worker) *worker = g_last_mn_worker.data();
     return (uint32_t)g_last_mn_rq.size();
 }
+int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n_levels, double *order_us) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (n_runs) *n_runs = ctx->dbg_order ? ctx->dbg_order_runs : 0;
+    if (n_levels) *n_levels = ctx->dbg_order ? ctx->dbg_order_levels : 0;
+    if (order_us) *order_us = ctx->dbg_order ? ctx->dbg_order_us : 0.0;
+    return ctx->dbg_order ? 1 : 0;
+}
 void hqtick_debug_set_block_emulation(int on, uint32_t budget) { g_block_emulation = on; if (budget) g_block_budget = budget; }
 void hqtick_debug_last_blocks(uint32_t *n_emulated, uint32_t *n_host) { if (n_emulated) *n_emulated = g_last_blocks_device; if (n_host) *n_host = g_last_blocks_host; }
 
@@ -2269,6 +2465,7 @@ int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot 
     fill_problem(pb, s, ctx->cfg, ev);
     Scan sc; sc.Q = s->n_requests; sc.L = n_levels; sc.G = n_levels * s->n_requests;
     sc.levels.assign(levels, levels + n_levels); sc.hist.assign(hist, hist + (size_t)n_levels * s->n_requests);
+    runs_from_hist(sc);
     std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
     std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
     memset(out, 0, sizeof(*out));
@@ -2331,6 +2528,7 @@ int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *
     pb.custom = &fw;
     Scan sc; sc.Q = Q; sc.L = n_levels; sc.G = n_levels * Q;
     sc.levels.assign(levels, levels + n_levels); sc.hist.assign(hist, hist + (size_t)n_levels * Q);
+    runs_from_hist(sc);
     std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
     std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
     EmulatedBlocks emu(g_block_budget);
@@ -2382,6 +2580,7 @@ int hqtick_set_record_sink(hqtick_ctx *ctx, void *device_ptr, size_t capacity_by
 int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     if (!ctx || !avg_us || iters <= 0) return HQTICK_E_INVALID;
     if (!ctx->last_valid || !ctx->resident) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel needs a preceding hqtick_run_resident tick that placed tasks");
+    if (ctx->last_ordered) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel times the dense scan: the last tick took the ordered view");
     HQ_HIP(hipSetDevice(ctx->device));
     const uint64_t N = ctx->n_ready; const hqk::WaveGeom g = ctx->last_geom;
     const uint32_t *d = ctx->d_map.as<uint32_t>();

@@ -134,7 +134,11 @@ hipError_t expand_mapping(MapKeys mk, uint32_t W, const uint64_t *sel_task, cons
                     uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s);
 // may_reorder: the tick has more than one priority level, Retracting holes or prefilled tasks in the queues — a worker's records then need the stable
 // sort of mapping.rs:128-131 (an LDS key array of the next power of two above max_items); without it the items are emitted in gather order
-size_t expand_mapping_lds(uint32_t max_items, uint32_t n_keys, uint32_t max_out, bool may_reorder);
+size_t expand_mapping_lds(uint32_t max_items, uint32_t n_keys, uint32_t max_out, bool may_reorder, bool wide_levels = false);
+// The same for a selection of the ordered view (order.hip): sel_rank[i] = the global level rank of selected task i (32 bits; the stable sort then runs on
+// 64-bit keys).  The LDS need is expand_mapping_lds(..., wide_levels = true).
+hipError_t expand_mapping_wide(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint32_t *sel_rank, uint32_t max_items,
+                               uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s);
 
 // Resident cluster tables (f1): rows of the worker table that changed, scattered into the HBM copy (inputs may sit in pinned host memory)
 hipError_t scatter_worker_rows(uint64_t *free_, int64_t *rem, uint32_t R, uint32_t n, const uint32_t *idx, const uint64_t *rows, const int64_t *new_rem, hipStream_t s);
@@ -169,5 +173,38 @@ hipError_t rank_of(const uint64_t *ids, const uint16_t *gkey, uint64_t n, const 
 // hqtick_upload_ready(sorted = 0): in-place bitonic sort of the three columns by id (buffers sized for n_pow2 elements, the next
 // power of two >= n; the padding is filled with sentinels here).  dup_flag |= 1 when two ids are equal.
 hipError_t sort_ready(uint64_t *id, uint64_t *prio, uint32_t *rq, uint64_t n, uint64_t n_pow2, uint32_t *dup_flag, hipStream_t s);
+
+// ---- the ordered view (order.hip): the general path of phase A where the dense (level, request) table does not fit ----
+// A permutation of the live slots ordered by (request asc, priority desc, slot asc) and its run table (one row per nonempty (request, priority) pair).
+static const uint32_t ORDER_DIGITS = 12;    // 8-bit digits of the sort key: 8 of ~priority, 4 of rq
+static const uint32_t ORDER_TILE = 2048;    // slots one wavefront ranks per pass
+inline uint32_t order_tiles(uint64_t n) { return (uint32_t)((n + ORDER_TILE - 1) / ORDER_TILE); }
+// one read pass: ghist[dg * 256 + d] = live slots whose digit dg is d; ghist[ORDER_DIGITS * 256] = 1 when a live rq >= Q.  Zeroes ghist first (ORDER_DIGITS * 256 + 4 words).
+hipError_t order_digits(const uint64_t *prio, const uint32_t *rq, uint64_t n, uint32_t Q, uint32_t *ghist, hipStream_t s);
+// one stable pass on digit dg: in[0..n_in) -> out[0..n_out) (first: the input is the column, slot = index, tombstones dropped).  tab: 256 * order_tiles(n_in) words.
+// err |= 1 if a position fell outside [0, n_out) (counts that disagree with ghist; nothing is written there)
+hipError_t order_pass(const uint64_t *prio, const uint32_t *rq, uint64_t n_in, bool first, const uint32_t *in, uint32_t dg, const uint32_t *ghist, uint32_t *tab,
+                      uint32_t *out, uint32_t n_out, uint32_t *err, hipStream_t s);
+// global level ranks from a priority-sorted permutation perm[0..n): lrank[slot] = distinct priorities above the slot's, n_levels[0].  tile_cnt: order_tiles(n) + 1 words.
+hipError_t order_levels(const uint64_t *prio, const uint32_t *perm, uint32_t n, uint32_t *tile_cnt, uint32_t *lrank, uint32_t *n_levels, hipStream_t s);
+// run table of the sorted view perm[0..n): run_rq / run_start / run_rank / run_prio [number of runs <= n], n_runs[0]; inv[slot] = position of the slot in perm.
+hipError_t order_runs(const uint64_t *prio, const uint32_t *rq, const uint32_t *perm, uint32_t n, uint32_t *tile_cnt, const uint32_t *lrank, uint32_t *inv,
+                      uint32_t *n_runs, uint32_t *run_rq, uint32_t *run_start, uint32_t *run_rank, uint64_t *run_prio, hipStream_t s);
+// K4 on the view: selected task j of request q is position j - rq_sel_base[q] of q's segment of perm (the tables are the HBM copy of the plan)
+struct OrderSelect {
+    const uint64_t *task_id; const uint32_t *perm; uint32_t n_live, Q, n_runs;
+    const uint32_t *rq_sel_base;  // [Q + 1]
+    const uint32_t *run_off;      // [Q + 1] runs of request q: [run_off[q], run_off[q + 1])
+    const uint32_t *run_start;    // [n_runs] position of the run's first task in perm
+    const uint32_t *run_rank;     // [n_runs] global level rank of the run's priority (what K5b sorts by)
+    const uint32_t *q_tnc;        // [Q] worker-major form (n << 16 | c, 0 = off; kernels.hip: k_select)
+    uint64_t *sel_task; uint32_t *sel_rank;
+    uint32_t *mark_rq; uint32_t mark_value; uint32_t mark_and_select;  // mark_rq: write mark_value (RQ_TOMBSTONE: consume; anything else: the request id back) at the selected slots
+    uint32_t *err;
+};
+hipError_t order_select(const OrderSelect &os, uint32_t n_sel, hipStream_t s);
+// (request, position in perm) of the wanted ids (0xFFFFFFFF = not a live task)
+hipError_t order_rank_of(const uint64_t *ids, const uint32_t *rq, uint64_t n, const uint32_t *inv, const uint64_t *want, uint32_t n_want, uint32_t *out_rq, uint32_t *out_pos,
+                         hipStream_t s);
 
 }  // namespace hqk

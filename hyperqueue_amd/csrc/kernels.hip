@@ -14,6 +14,8 @@
 #include "kernels.h"
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 namespace hqk {
 namespace { thread_local LaunchTimer g_timer; }
 void time_next_launch(hipEvent_t start, hipEvent_t stop) { g_timer.start = start; g_timer.stop = stop; }
@@ -555,8 +557,11 @@ static const uint32_t RUN_STAGE = 512;  // runs of one worker staged in LDS befo
 // Compact emission (HQTICK_FLAG_COMPACT_RECORDS): the records cross PCIe as 4 bytes each — the low half of the task id — plus one 10-byte RUN per
 // maximal stretch of a worker's records that share (job id, variant, kind).  LDS then also holds the worker's final sequence:
 // f_task u64[max_out] | f_meta u16[max_out] (variant | kind << 8) behind the tables above.
+// LV: the per-item level type.  uint16_t: sel_key is K4's group key, level = key / Q, sort keys (level << 16 | item) in 32 bits.  uint32_t (the ordered view,
+// order.hip): sel_key is the run's global level rank (the launch passes Q = 1), sort keys (level << 32 | item) in 64 bits.
+template <typename LV>
 __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, const uint64_t *__restrict__ sel_task,
-                                                        const uint16_t *__restrict__ sel_key, uint32_t Q, uint32_t max_items,
+                                                        const LV *__restrict__ sel_key, uint32_t Q, uint32_t max_items,
                                                         uint64_t *__restrict__ rec_task, uint8_t *__restrict__ rec_variant,
                                                         uint8_t *__restrict__ rec_kind, uint32_t *__restrict__ err_flag, CompactOut co, uint32_t max_out,
                                                         uint32_t sort_cap) {
@@ -564,16 +569,18 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
     const uint32_t nkeys = mk.n_keys;
     uint64_t *e_task = reinterpret_cast<uint64_t *>(smem);
     uint64_t *f_task = e_task + max_items;  // compact mode only (max_out == 0 otherwise)
-    uint16_t *e_lvl = reinterpret_cast<uint16_t *>(f_task + max_out);
-    uint16_t *e_meta = e_lvl + max_items;  // variant | valid << 8
+    typedef typename std::conditional<sizeof(LV) == 2, uint32_t, uint64_t>::type SK;  // sort key
+    LV *e_lvl = reinterpret_cast<LV *>(f_task + max_out);
+    uint16_t *e_meta = reinterpret_cast<uint16_t *>(e_lvl + max_items);  // variant | valid << 8
     uint16_t *f_meta = e_meta + max_items;
-    uint32_t *k_start = reinterpret_cast<uint32_t *>(f_meta + max_out + ((max_items * 2 + max_out) & 1u));  // keeps 4-byte alignment
+    uint32_t *k_start = reinterpret_cast<uint32_t *>((reinterpret_cast<uintptr_t>(f_meta + max_out) + 3) & ~(uintptr_t)3);  // keeps 4-byte alignment
     const bool compact = co.rec_lo != nullptr;
     uint32_t *k_pos = k_start + nkeys + 1;
     uint32_t *k_cnt = k_pos + nkeys, *k_rq = k_cnt + nkeys, *k_seg = k_rq + nkeys, *k_toff = k_seg + nkeys, *k_boff = k_toff + nkeys, *k_words = k_boff + nkeys;
     uint32_t *k_trc = k_words + nkeys;
     uint32_t *misc = k_trc + nkeys;  // [0] min level, [1] max level, [2] holes
-    uint32_t *s_key = misc + 4;        // [sort_cap] (level << 16 | item) keys of the stable sort; sort_cap = 0 on ticks that cannot reorder
+    SK *s_key = reinterpret_cast<SK *>((reinterpret_cast<uintptr_t>(misc + 4) + sizeof(SK) - 1) & ~(uintptr_t)(sizeof(SK) - 1));  // [sort_cap] (level << 16 | item) keys of the
+                                                                                                                                 // stable sort; sort_cap = 0 on ticks that cannot reorder
     uint8_t *k_var = reinterpret_cast<uint8_t *>(s_key + sort_cap);
     const uint32_t w = blockIdx.x, lane = lane_id();
     // Three rounds of global loads, each issued as one batch: (1) the worker's output range, its row of every per-key table and its prefill chunks;
@@ -595,7 +602,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
         p_j[pi] = j; p_cnt[pi] = j == 0xFFFFFFFFu ? 0u : c; p_src[pi] = mk.pfq_src[pi] + (j == 0xFFFFFFFFu ? 0u : j * c);
     }
     if (out1 == out0) return;  // no record for this worker (or the worker belongs to another rank's shard)
-    if (threadIdx.x == 0) { misc[0] = 0xFFFFu; misc[1] = 0; misc[2] = 0; }
+    if (threadIdx.x == 0) { misc[0] = (uint32_t)(LV)~(LV)0; misc[1] = 0; misc[2] = 0; }
     __syncthreads();
     if (threadIdx.x < 64) {  // exclusive scan of the per-key counts
         uint32_t carry = 0;
@@ -653,7 +660,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
             const uint32_t k = lo, s = e - k_start[k], pos = k_pos[k];
             if (k_trc[k]) {  // worker-major key: this worker's tasks are the k_trc[k] ids from its own offset on (no cell, no hole: the host transposes only plain queues)
                 const uint32_t src = mk.rq_sel_base[k_rq[k]] + pos * k_trc[k] + s;
-                const uint16_t lv = sort_cap ? (uint16_t)(sel_key[src] / Q) : (uint16_t)0;
+                const LV lv = sort_cap ? (LV)(sel_key[src] / Q) : (LV)0;
                 e_task[e] = sel_task[src];
                 e_lvl[e] = lv;
                 e_meta[e] = (uint16_t)(k_var[k] | 0x100u);
@@ -685,7 +692,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
                 const uint32_t src = sbase + (p >= pfs + pfn ? p - pfn : p);
                 // priority level of the task's group — only a tick that can reorder needs it (sort_cap != 0: several levels, holes or prefilled tasks): the cold
                 // tick skips one strided 2-byte gather per record (a 64-byte line each)
-                const uint16_t lv = sort_cap ? (uint16_t)(sel_key[src] / Q) : (uint16_t)0;
+                const LV lv = sort_cap ? (LV)(sel_key[src] / Q) : (LV)0;
                 e_task[e] = sel_task[src];
                 e_lvl[e] = lv;
                 e_meta[e] = (uint16_t)(k_var[k] | 0x100u);
@@ -708,14 +715,14 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
         if (P > sort_cap || P > 65536u) P = 0;  // cannot happen (the host sizes sort_cap from max_items); rank counting below stays correct
     }
     if (P) {
-        for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) s_key[i] = (i < n && (e_meta[i] & 0x100u)) ? ((uint32_t)e_lvl[i] << 16 | i) : 0xFFFFFFFFu;
+        for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) s_key[i] = (i < n && (e_meta[i] & 0x100u)) ? ((SK)e_lvl[i] << (sizeof(LV) * 8) | i) : ~(SK)0;
         __syncthreads();
         for (uint32_t k = 2; k <= P; k <<= 1) {
             for (uint32_t j = k >> 1; j > 0; j >>= 1) {
                 for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
                     const uint32_t o = i ^ j;
                     if (o > i) {
-                        const uint32_t a = s_key[i], b = s_key[o];
+                        const SK a = s_key[i], b = s_key[o];
                         if ((a > b) == ((i & k) == 0)) { s_key[i] = b; s_key[o] = a; }
                     }
                 }
@@ -726,18 +733,18 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
     for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) {
         uint32_t e = t, pos = t;  // trivial: already in final order
         if (P) {                  // position t takes the item the network put there
-            const uint32_t key = s_key[t];
-            if (key == 0xFFFFFFFFu) continue;
-            e = key & 0xFFFFu;
+            const SK key = s_key[t];
+            if (key == ~(SK)0) continue;
+            e = (uint32_t)(key & 0xFFFFFFFFu) & (sizeof(LV) == 2 ? 0xFFFFu : 0xFFFFFFFFu);
         }
         const uint16_t meta = e_meta[e];
         if (!(meta & 0x100u)) continue;
         if (!trivial && !P) {     // fallback: rank counting
-            const uint16_t lv = e_lvl[e];
+            const LV lv = e_lvl[e];
             pos = 0;
             for (uint32_t o = 0; o < n; o++) {
                 if (!(e_meta[o] & 0x100u)) continue;
-                const uint16_t lo_ = e_lvl[o];
+                const LV lo_ = e_lvl[o];
                 pos += (lo_ < lv || (lo_ == lv && o < e)) ? 1u : 0u;
             }
         }
@@ -1281,21 +1288,34 @@ hipError_t sweep_bits(MapKeys mk, uint32_t max_count, uint32_t max_workers_per_k
 
 uint32_t expand_mapping_sort_cap(uint32_t max_items) { uint32_t p = 1; while (p < max_items) p <<= 1; return p; }
 
-size_t expand_mapping_lds(uint32_t max_items, uint32_t n_keys, uint32_t max_out, bool may_reorder) {
-    return (size_t)max_items * 12 + (size_t)max_out * 10 + 2 + ((size_t)9 * n_keys + 1 + 4) * 4 + n_keys + 16 + (may_reorder ? (size_t)expand_mapping_sort_cap(max_items) * 4 : 0) +
+size_t expand_mapping_lds(uint32_t max_items, uint32_t n_keys, uint32_t max_out, bool may_reorder, bool wide_levels) {
+    return (size_t)max_items * (wide_levels ? 14 : 12) + (size_t)max_out * 10 + 2 + ((size_t)9 * n_keys + 1 + 4) * 4 + n_keys + 16 +
+           (may_reorder ? (size_t)expand_mapping_sort_cap(max_items) * (wide_levels ? 8 : 4) + (wide_levels ? 8 : 0) : 0) +
            (max_out ? (size_t)RUN_STAGE * 16 + 4 + (size_t)max_out * 6 + 8 : 0);  // max_out != 0 = compact emission: the run stage + the 16-bit unit stream (delta mode)
+}
+
+template <typename LV>
+static hipError_t expand_mapping_t(MapKeys mk, uint32_t W, const uint64_t *sel_task, const LV *sel_key, uint32_t Q, uint32_t max_items,
+                                   uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s) {
+    if (W == 0) return hipSuccess;
+    if (!co.rec_lo) max_out = 0;
+    size_t lds = expand_mapping_lds(max_items, mk.n_keys, max_out, may_reorder, sizeof(LV) == 4);
+    const uint32_t sort_cap = may_reorder ? expand_mapping_sort_cap(max_items) : 0;
+    hipError_t e;
+    auto kern = k_expand_mapping<LV>;
+    if (lds > 48 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+    HQK_TIMED_LAUNCH(kern, dim3(W), dim3(256), lds, s, mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, sort_cap);
+    return hipGetLastError();
 }
 
 hipError_t expand_mapping(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint16_t *sel_key, uint32_t Q, uint32_t max_items,
                     uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s) {
-    if (W == 0) return hipSuccess;
-    if (!co.rec_lo) max_out = 0;
-    size_t lds = expand_mapping_lds(max_items, mk.n_keys, max_out, may_reorder);
-    const uint32_t sort_cap = may_reorder ? expand_mapping_sort_cap(max_items) : 0;
-    hipError_t e;
-    if (lds > 48 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_expand_mapping), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    HQK_TIMED_LAUNCH(k_expand_mapping, dim3(W), dim3(256), lds, s, mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, sort_cap);
-    return hipGetLastError();
+    return expand_mapping_t<uint16_t>(mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, may_reorder, s);
+}
+
+hipError_t expand_mapping_wide(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint32_t *sel_rank, uint32_t max_items,
+                               uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s) {
+    return expand_mapping_t<uint32_t>(mk, W, sel_task, sel_rank, 1u, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, may_reorder, s);
 }
 
 hipError_t scatter_worker_rows(uint64_t *free_, int64_t *rem, uint32_t R, uint32_t n, const uint32_t *idx, const uint64_t *rows, const int64_t *new_rem, hipStream_t s) {

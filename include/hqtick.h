@@ -588,12 +588,14 @@ int hqtick_query(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, const hqtick_
  *   Result      `out` exactly as hqtick_query fills it (is_loaded per fake worker, is_optimal; valid until the next call on ctx).  rq_ready (may be
  *               NULL) [snapshot->n_requests]: the live resident tasks of every request, queue.size() of query.rs:97-124 (multi_node_allocations).
  *   Device      one read-only census kernel over the priority and request-id columns (12 B per physical slot, tombstones skipped) on the ctx's
- *               stream, behind every queued delta; its level table and counts go to buffers of the private sub-context that hqtick_query uses,
+ *               stream, behind every queued delta (beyond the census's caps: the ordered view's radix passes, read-only on the columns too); its level
+ *               table and counts go to buffers of the private sub-context that hqtick_query uses,
  *               where batches, model and solve run.  Nothing of ctx changes: columns, group keys, level table, wave table, the selection that
  *               hqtick_ready_consume_last replays, the live count, the graph, the Retracting table.
  *   Errors      HQTICK_E_INVALID without a resident set, and while a selection is pending (a hqtick_run_resident that placed tasks and no
- *               hqtick_ready_consume_last after it: consume first; under HQTICK_FLAG_CONSUME_IN_TICK nothing is pending).  HQTICK_E_CAPACITY
- *               beyond 4096 priority levels or 16384 (level, request) groups, as for the tick.
+ *               hqtick_ready_consume_last after it: consume first; under HQTICK_FLAG_CONSUME_IN_TICK nothing is pending).  Any number of
+ *               distinct priorities: beyond 4096 levels or 16384 (level, request) groups the census gives way to the run table of the ordered view
+ *               (DESIGN.md §8f), built on the same sub-context's buffers, as the tick does.
  *   Shards      a replica of hqtick_set_shard answers as a single context would, with no exchange. */
 int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, const hqtick_query_workers *fake,
                           hqtick_query_result *out, uint64_t *rq_ready);

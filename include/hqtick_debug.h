@@ -26,6 +26,11 @@ int hqtick_debug_milp_solve(int ncols, const double *obj, const uint8_t *col_kin
                             double time_limit_s, int canonical, double *x_out, double *obj_out, int *is_optimal,
                             long *nodes_out);
 
+/* Which form of phase A the last tick of ctx took (hqtick_query and hqtick_query_resident run on a private sub-context and are not reported here): 1 = the ordered view of the ready set (more distinct priorities or
+ * (level, request) groups than the dense scan holds, or HQTICK_ORDERED_VIEW=1), 0 = the dense scan.  On the view: n_runs = nonempty (request, priority)
+ * pairs, n_levels = distinct priorities, order_us = event time of the view's kernels (0 under HQTICK_FLAG_NO_KERNEL_TIMING); all 0 otherwise. */
+int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n_levels, double *order_us);
+
 /* The HOST stages of a tick — create_task_batches + run_scheduling_solver (scheduler/batches.rs:42-181, scheduler/solver.rs:36-483) — on
  * caller-supplied outputs of the GPU scans, so that this logic can be unit-tested on a machine without a GPU.  This is not a tick: the scans
  * (K0/K1/K2), the selection and the mapping have no CPU implementation, and nothing in the product calls this.
