@@ -1,0 +1,264 @@
+// Kernels of the assignment ledger (assigned.h).  gfx950 only.
+#include "assigned.h"
+
+#include "../../include/hqtick.h"
+
+namespace hqasg {
+
+namespace {
+
+constexpr uint32_t TPB = 256;
+inline unsigned nblk(uint64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+
+__device__ __forceinline__ uint32_t ht_hash(uint64_t k) {  // murmur3 finaliser (graph.hip's)
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return (uint32_t)k;
+}
+__device__ __forceinline__ uint32_t ht_find(const Table &t, uint64_t id) {
+    uint32_t h = ht_hash(id) & t.mask;
+    for (uint32_t probe = 0; probe <= t.mask; probe++) {
+        const uint64_t k = __atomic_load_n(&t.key[h], __ATOMIC_RELAXED);
+        if (k == id) return h;
+        if (k == HT_EMPTY) return NONE;
+        h = (h + 1) & t.mask;
+    }
+    return NONE;
+}
+// bucket of `id`: *fresh = 1 if this call claimed an empty bucket for it, 0 if it was there; NONE = table full.  Tombstones are not reused
+// (a probe sequence never changes under concurrent inserts); the host rebuilds the table before live + tombstones pass half the capacity.
+__device__ __forceinline__ uint32_t ht_claim(const Table &t, uint64_t id, int *fresh) {
+    uint32_t h = ht_hash(id) & t.mask;
+    for (uint32_t probe = 0; probe <= t.mask; probe++) {
+        const uint64_t k = __atomic_load_n(&t.key[h], __ATOMIC_RELAXED);
+        if (k == id) { *fresh = 0; return h; }
+        if (k == HT_EMPTY) {
+            const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long *>(&t.key[h]), (unsigned long long)HT_EMPTY, (unsigned long long)id);
+            if (old == HT_EMPTY) { *fresh = 1; return h; }
+            if (old == id) { *fresh = 0; return h; }
+        }
+        h = (h + 1) & t.mask;
+    }
+    return NONE;
+}
+// one atomic per wavefront for a per-lane flag (every lane of the wave must call)
+__device__ __forceinline__ void wave_add(uint32_t *c, bool v) {
+    const uint64_t m = __ballot(v);
+    if (m && __lane_id() == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(c, (uint32_t)__popcll(m));
+}
+// position of the calling lane among the lanes that want a slot; one atomic per wavefront (graph.hip's)
+__device__ __forceinline__ uint32_t wave_append(uint32_t *counter, bool want) {
+    const uint64_t m = __ballot(want);
+    if (m == 0) return 0;
+    const uint32_t lane = __lane_id(), leader = (uint32_t)__ffsll((long long)m) - 1u;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    base = __shfl(base, (int)leader);
+    return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+__device__ __forceinline__ uint32_t row_of(const Rows &r, uint32_t wid) {  // ids ascend in row order
+    uint32_t lo = 0, hi = r.W;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (r.wid[mid] < wid) lo = mid + 1; else hi = mid; }
+    return (lo < r.W && r.wid[lo] == wid) ? lo : NONE;
+}
+__device__ __forceinline__ bool variant_ok(const Req &q, uint32_t rq, uint32_t v) { return rq < q.Q && v < q.rq_off[rq + 1] - q.rq_off[rq]; }
+// free.remove of one entry (workerload.rs:156-166): AMOUNT subtracts with saturation, ALL sets 0 — order-free, so plain atomics do
+__device__ __forceinline__ void free_remove(uint64_t *f, uint8_t kind, uint64_t amount) {
+    if (kind == HQ_ENTRY_ALL) { atomicExch(reinterpret_cast<unsigned long long *>(f), 0ull); return; }
+    unsigned long long cur = __atomic_load_n(reinterpret_cast<unsigned long long *>(f), __ATOMIC_RELAXED);
+    for (;;) {
+        const unsigned long long want = cur > amount ? cur - amount : 0ull;
+        const unsigned long long got = atomicCAS(reinterpret_cast<unsigned long long *>(f), cur, want);
+        if (got == cur) return;
+        cur = got;
+    }
+}
+
+__global__ void k_clear(Table t) {
+    const uint32_t b = blockIdx.x * TPB + threadIdx.x;
+    if (b > t.mask) return;
+    t.key[b] = HT_EMPTY; t.claim[b] = NONE;
+}
+
+enum InsertStatus : int { S_SKIP = 0, S_FRESH, S_MOVED, S_DUP, S_BAD, S_FULL };
+__device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Rows &r, const Items &it, int upsert, int apply_free, uint32_t i) {
+    uint64_t id, prio = 0; uint32_t row, wid, rq = RQ_LOOKUP, v;
+    if (it.rec_task) {
+        if (it.rec_kind[i] != HQ_REC_ASSIGN) return S_SKIP;  // prefills do not enter the ledger
+        id = it.rec_task[i]; v = it.rec_variant[i];
+        uint32_t lo = 0, hi = r.W;  // the worker whose record range holds i: the last w with rec_off[w] <= i
+        while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (it.rec_off[mid] <= i) lo = mid; else hi = mid - 1; }
+        row = lo; wid = r.wid[row];
+    } else {
+        id = it.id[i]; wid = it.wid[i]; v = it.variant[i];
+        if (it.rq) rq = it.rq[i];
+        if (it.prio) prio = it.prio[i];
+        row = row_of(r, wid);
+    }
+    if (row == NONE || id >= HT_TOMB) return S_BAD;
+    if (rq == RQ_LOOKUP) {  // rq and priority of a task of the ready set (ids ascending; a consumed task keeps its id and priority)
+        uint64_t lo = 0, hi = it.col_n;
+        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (it.col_id[mid] < id) lo = mid + 1; else hi = mid; }
+        if (lo >= it.col_n || it.col_id[lo] != id) return S_BAD;
+        rq = it.col_rq[lo]; prio = it.col_prio[lo];
+    }
+    if (!variant_ok(q, rq, v) || q.rq_off[rq] + v >= r.stride) return S_BAD;
+    int fresh = 0;
+    const uint32_t b = ht_claim(t, id, &fresh);
+    if (b == NONE) return S_FULL;
+    if (!fresh) {
+        if (!upsert) return S_DUP;
+        const uint32_t orow = row_of(r, t.worker[b]);  // a re-targeted redirect: the old target's count goes back (its free row is the tick's)
+        if (orow != NONE) atomicSub(&r.counts[(size_t)orow * r.stride + q.rq_off[t.rq[b]] + t.variant[b]], 1u);
+    }
+    t.worker[b] = wid; t.rq[b] = rq; t.variant[b] = (uint8_t)v; t.prio[b] = prio; t.claim[b] = NONE;
+    const uint32_t slot = q.rq_off[rq] + v;
+    atomicAdd(&r.counts[(size_t)row * r.stride + slot], 1u);
+    if (apply_free)
+        for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) free_remove(&r.free_[(size_t)row * r.R + q.ent_res[e]], q.ent_kind[e], q.ent_amount[e]);
+    return fresh ? S_FRESH : S_MOVED;
+}
+__global__ void k_insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    const int st = i < it.n ? insert_one(t, q, r, it, upsert, apply_free, i) : S_SKIP;
+    wave_add(&ctr[C_DONE], st == S_FRESH || st == S_MOVED); wave_add(&ctr[C_OUT], st == S_FRESH);
+    wave_add(&ctr[C_DUP], st == S_DUP); wave_add(&ctr[C_BAD], st == S_BAD); wave_add(&ctr[C_FULL], st == S_FULL);
+}
+
+// release, pass 1: the bucket of every id; the first position of an id in the batch claims it (later ones are duplicates)
+__global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    uint32_t b = NONE;
+    if (i < n) {
+        b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
+        pos[i] = b;
+        if (b != NONE) atomicMin(&t.claim[b], i);
+    }
+    wave_add(&ctr[C_UNKNOWN], i < n && b == NONE);
+}
+// pass 2: per (worker row, resource) the position + 1 of the batch's last ALL entry
+__global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos, uint32_t *last_all, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    const uint32_t b = i < n ? pos[i] : NONE;
+    bool dup = false, bad = false;
+    if (b != NONE) {
+        const uint32_t row = row_of(r, t.worker[b]);
+        if (t.claim[b] != i) { pos[i] = NONE; dup = true; }
+        else if (row == NONE) { pos[i] = NONE; bad = true; t.claim[b] = NONE; }  // (left in the table, unclaimed: a later batch finds it as before)
+        else {
+            const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
+            for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++)
+                if (q.ent_kind[e] == HQ_ENTRY_ALL) atomicMax(&last_all[(size_t)row * r.R + q.ent_res[e]], i + 1);
+        }
+    }
+    wave_add(&ctr[C_DUP], dup); wave_add(&ctr[C_BAD], bad);
+}
+// pass 3: the AMOUNT entries behind the last ALL of their (row, resource) are summed; the entry leaves the table
+__global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    const uint32_t b = i < n ? pos[i] : NONE;
+    if (b != NONE) {
+        const uint32_t row = row_of(r, t.worker[b]);
+        const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
+        for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) {
+            const size_t j = (size_t)row * r.R + q.ent_res[e];
+            if (q.ent_kind[e] == HQ_ENTRY_AMOUNT && i + 1 > last_all[j]) atomicAdd(reinterpret_cast<unsigned long long *>(&delta[j]), (unsigned long long)q.ent_amount[e]);
+        }
+        atomicSub(&r.counts[(size_t)row * r.stride + slot], 1u);
+        t.key[b] = HT_TOMB; t.claim[b] = NONE;
+    }
+    wave_add(&ctr[C_DONE], b != NONE);
+}
+// pass 4: free.add per (row, resource) — ALL sets the total (workerload.rs:194-202), the AMOUNTs after it add
+__global__ void k_rel_rows(Rows r, uint32_t *last_all, uint64_t *delta) {
+    const uint32_t j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= r.W * r.R) return;
+    const uint32_t la = last_all[j]; const uint64_t d = delta[j];
+    if (la) r.free_[j] = r.total[j] + d; else if (d) r.free_[j] += d;
+    last_all[j] = 0; delta[j] = 0;
+}
+
+__global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr) {
+    const uint32_t b = blockIdx.x * TPB + threadIdx.x;
+    const uint64_t k = b <= t.mask ? t.key[b] : HT_EMPTY;
+    bool hit = false;
+    if (k < HT_TOMB) {
+        const uint32_t w = t.worker[b];
+        uint32_t lo = 0, hi = n_lost;
+        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (lost[mid] < w) lo = mid + 1; else hi = mid; }
+        hit = lo < n_lost && lost[lo] == w;
+    }
+    const uint32_t o = wave_append(&ctr[C_OUT], hit);
+    if (!hit || o >= cap_out) return;  // (the host sized the output by its live count: more is reported as an error and nothing is written past the end)
+    out_id[o] = k; out_rq[o] = t.rq[b]; out_prio[o] = t.prio[b];
+    t.key[b] = HT_TOMB;
+}
+
+__global__ void k_rehash(Table from, Table to, uint32_t *ctr) {
+    const uint32_t b = blockIdx.x * TPB + threadIdx.x;
+    const uint64_t k = b <= from.mask ? from.key[b] : HT_EMPTY;
+    uint32_t d = NONE;
+    if (k < HT_TOMB) {
+        int fresh = 0;
+        d = ht_claim(to, k, &fresh);
+        if (d != NONE) { to.worker[d] = from.worker[b]; to.rq[d] = from.rq[b]; to.variant[d] = from.variant[b]; to.prio[d] = from.prio[b]; to.claim[d] = NONE; }
+    }
+    wave_add(&ctr[C_DONE], k < HT_TOMB && d != NONE); wave_add(&ctr[C_FULL], k < HT_TOMB && d == NONE);
+}
+
+__global__ void k_repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride, uint32_t n_cols) {
+    const uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+    if (j >= (uint64_t)W_dst * n_cols) return;
+    const uint32_t w = (uint32_t)(j / n_cols), c = (uint32_t)(j % n_cols);
+    const uint32_t sr = src_row ? src_row[w] : w;
+    dst[(size_t)w * dst_stride + c] = sr < W_src ? src[(size_t)sr * src_stride + c] : 0u;
+}
+
+__global__ void k_lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
+    out_wid[i] = b == NONE ? HQ_NO_WORKER : t.worker[b];
+    out_variant[i] = b == NONE ? (uint8_t)0xFF : t.variant[b];
+}
+
+}  // namespace
+
+hipError_t clear(Table t, hipStream_t s) {
+    hipLaunchKernelGGL(k_clear, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t);
+    return hipGetLastError();
+}
+hipError_t insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr, hipStream_t s) {
+    if (!it.n) return hipSuccess;
+    hipLaunchKernelGGL(k_insert, dim3(nblk(it.n)), dim3(TPB), 0, s, t, q, r, it, upsert, apply_free, ctr);
+    return hipGetLastError();
+}
+hipError_t release(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_rel_claim, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, ctr);
+    hipLaunchKernelGGL(k_rel_last_all, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, ctr);
+    hipLaunchKernelGGL(k_rel_apply, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, delta, ctr);
+    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, r, last_all, delta);
+    return hipGetLastError();
+}
+hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr, hipStream_t s) {
+    if (!n_lost) return hipSuccess;
+    hipLaunchKernelGGL(k_evict, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, n_lost, lost, out_id, out_rq, out_prio, cap_out, ctr);
+    return hipGetLastError();
+}
+hipError_t rehash(Table from, Table to, uint32_t *ctr, hipStream_t s) {
+    hipLaunchKernelGGL(k_rehash, dim3(nblk((uint64_t)from.mask + 1)), dim3(TPB), 0, s, from, to, ctr);
+    return hipGetLastError();
+}
+hipError_t repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride,
+                         uint32_t n_cols, hipStream_t s) {
+    if (!W_dst || !n_cols) return hipSuccess;
+    hipLaunchKernelGGL(k_repack_counts, dim3(nblk((uint64_t)W_dst * n_cols)), dim3(TPB), 0, s, src, src_stride, W_src, src_row, W_dst, dst, dst_stride, n_cols);
+    return hipGetLastError();
+}
+hipError_t lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_lookup, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, out_wid, out_variant);
+    return hipGetLastError();
+}
+
+}  // namespace hqasg

@@ -1109,6 +1109,12 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
     std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_variant;
     auto build_agg = [&]() {
         agg_off.assign((size_t)ws.n + 1, 0);
+        if (!pb.custom && !ws.assigned_off && ws.agg_off) {  // the assignment ledger's counts: the same lists, no pass over the running tasks
+            agg_off.assign(ws.agg_off, ws.agg_off + ws.n + 1);
+            const uint32_t e = ws.agg_off[ws.n];
+            agg_rq.assign(ws.agg_rq, ws.agg_rq + e); agg_variant.assign(ws.agg_variant, ws.agg_variant + e); agg_cnt.assign(ws.agg_cnt, ws.agg_cnt + e);
+            return;
+        }
         if (pb.custom || !ws.assigned_off) return;
         // (counted per variant slot, not sorted: a busy worker runs a hundred tasks of a handful of kinds — sorting 1024 such lists was a millisecond of a 3 ms tick)
         std::vector<uint32_t> keys, cnt(NVS, 0);

@@ -75,7 +75,9 @@ struct WorkerSet {
     uint32_t n_blocked_lists = 0;   // entries in `blocked` (0: every list is empty and the vector can be reused as it is)
     // SingleNodeTaskAssignment::assigned_tasks as the snapshot's CSR (views, not copies; nullptr = nothing assigned)
     const uint32_t *assigned_off = nullptr, *assigned_rq = nullptr; const uint8_t *assigned_variant = nullptr;
-    uint32_t n_assigned(uint32_t w) const { return assigned_off ? assigned_off[w + 1] - assigned_off[w] : 0; }
+    // ... or (assignment ledger, assigned_off == nullptr) already aggregated: per worker its distinct (rq, variant) pairs ascending with their counts (all > 0)
+    const uint32_t *agg_off = nullptr, *agg_rq = nullptr, *agg_cnt = nullptr; const uint8_t *agg_variant = nullptr;
+    uint32_t n_assigned(uint32_t w) const { return assigned_off ? assigned_off[w + 1] - assigned_off[w] : agg_off ? agg_off[w + 1] - agg_off[w] : 0; }  // (0 iff none)
     bool is_sn(uint32_t w) const { return flags ? (flags[w] & HQ_WORKER_SN) != 0 : true; }
     bool stopping(uint32_t w) const { return flags ? (flags[w] & HQ_WORKER_STOPPING) != 0 : false; }
     bool is_free(uint32_t w) const { return is_sn(w) && n_assigned(w) == 0 && !stopping(w); }

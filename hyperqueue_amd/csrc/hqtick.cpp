@@ -36,6 +36,7 @@
 #endif
 #include "devbuf.h"
 #include "graph.h"
+#include "assigned.h"
 #include "hb_order.h"
 #include "host_model.h"
 #include "kernels.h"
@@ -66,6 +67,33 @@ struct PlanScratch {
     std::vector<std::pair<uint32_t, uint64_t>> retract_pairs;  // (old worker, task)
     // cached worker_map iteration order (emulated) for the last worker-id set
     std::vector<uint32_t> cached_ids, cached_order;
+};
+
+// The assignment ledger (hqtick_assigned_*, ABI 12; csrc/assigned.h): the tasks running on the resident worker set, in HBM.
+struct Ledger {
+    bool on = false;
+    DevBuf key, wid, rq, var, prio, claim; uint32_t cap = 0; uint64_t n_live = 0, n_tomb = 0;   // the hash table (cap: a power of two)
+    DevBuf key2, wid2, rq2, var2, prio2, claim2;                                                  // ... the target of a rebuild
+    DevBuf counts, counts2; uint32_t stride = 0;                                                  // [W x stride] per (worker row, variant slot)
+    DevBuf req, wids, scratch, saved_rq, batch;                                                   // request tables, worker ids in row order, kernel scratch
+    DevBuf ctr; PinBuf h_ctr, h_in;   // (counters of one operation: in HBM, copied back behind the kernels)
+    // the request tables of the last snapshot (ResourceRqMap only grows: a slot keeps its number)
+    std::vector<uint32_t> rq_off{0}, vent_off{0}, ent_res; std::vector<uint8_t> ent_kind; std::vector<uint64_t> ent_amt; bool req_dirty = true;
+    std::vector<uint32_t> h_counts; bool dirty = false;  // the device tables changed since the host mirror (free rows, counts) was read
+    uint64_t last_unknown = 0;
+    // a tick's placement waiting for hqtick_ready_consume_last (two-call form)
+    bool pending = false; bool pend_saved = false;
+    const uint64_t *pend_task = nullptr; const uint8_t *pend_var = nullptr, *pend_kind = nullptr; std::vector<uint32_t> pend_off; std::vector<uint64_t> pend_free;
+    std::vector<uint64_t> red_id, red_prio; std::vector<uint32_t> red_wid, red_rq; std::vector<uint8_t> red_var;
+    // hqtick_cluster_last_requeued
+    std::vector<uint64_t> rq_task, rq_prio; std::vector<uint32_t> rq_rq;
+    // what a ledger tick hands the host stages: per worker its distinct (rq, variant) pairs with counts (rebuilt from the count table when it changed)
+    std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_var; bool agg_dirty = true;
+    void release_all() {
+        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &req, &wids, &scratch, &saved_rq, &batch, &ctr};
+        for (DevBuf *x : b) x->release();
+        h_ctr.release(); h_in.release();
+    }
 };
 
 }  // namespace
@@ -140,6 +168,7 @@ struct hqtick_ctx {
     // launch state of the last tick (hqtick_time_kernel re-launches K1 / K4 on it)
     hqk::WaveGeom last_geom{}; uint32_t last_L = 0, last_Q = 0, last_G = 0; size_t last_tb = 0, last_plan_bytes = 0, last_hist_off = 0; bool last_valid = false;
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
+    Ledger asg;            // hqtick_assigned_* (ABI 12)
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
     // sharded placement solve: the ranks split the coupled solve's price sweeps and the separable solve's class blocks, one small all-gather of host
@@ -353,6 +382,7 @@ void fill_problem(hqhost::Problem &pb, const hqtick_snapshot *s, const hqtick_co
     ws.vflags = ev.flags; ws.vtmc = ev.tmc; ws.n_variant_slots = nv;
     if (ws.blocked.size() != ws.n || ws.n_blocked_lists) { ws.blocked.assign(ws.n, {}); ws.n_blocked_lists = 0; }  // (4096 empty lists re-made per tick cost more than the batches stage)
     ws.assigned_off = s->assigned_off; ws.assigned_rq = s->assigned_rq; ws.assigned_variant = s->assigned_variant;
+    ws.agg_off = nullptr; ws.agg_rq = nullptr; ws.agg_cnt = nullptr; ws.agg_variant = nullptr;
     for (uint32_t k = 0; k < s->n_blocked; k++) ws.blocked[s->blocked_worker[k]].push_back({s->blocked_rq[k], s->blocked_variant[k]});
     ws.n_blocked_lists = s->n_blocked;
     hqhost::group_equal_rows(ws, false);  // needs nothing of K2's output: in a tick this runs while the GPU works on phase A
@@ -1249,6 +1279,10 @@ struct TickRun {
             flags[0] = 0;  // K5b reports a capacity overflow straight into this pinned word
             ctx->last_n_sel = n_sel; ctx->last_consumed = false;
             const bool consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;  // K4 writes the tombstones of what it selects
+            if (consume_in_tick && ctx->asg.on) {  // the ledger reads the request ids of what K4 takes after K4 has tombstoned them (4 B per slot, device to device)
+                if (!ctx->asg.saved_rq.ensure(N * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids");
+                HQ_HIP(hipMemcpyAsync(ctx->asg.saved_rq.p, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            }
             ctx->last_geom = sc.geom; ctx->last_L = L; ctx->last_Q = Q; ctx->last_G = sc.G; ctx->last_tb = o_tb; ctx->last_plan_bytes = plan_words * 4; ctx->last_valid = true;
             ctx->last_ordered = sc.ordered;
             if (sc.ordered) {  // the plan into HBM, then K4 on the view (order.hip)
@@ -1380,6 +1414,10 @@ struct TickRun {
         // ---------------- GPU phase A ----------------
         const std::function<void()> prep = [&]() {   // request/worker views: no GPU output needed yet
             fill_problem(pb, s, ctx->cfg, ev);
+            if (ctx->asg.on && !s->assigned_off) {  // the ledger's per-worker (rq, variant) counts
+                const Ledger &a = ctx->asg;
+                pb.real.agg_off = a.agg_off.data(); pb.real.agg_rq = a.agg_rq.data(); pb.real.agg_cnt = a.agg_cnt.data(); pb.real.agg_variant = a.agg_var.data();
+            }
             // HQTICK_FLAG_CERTIFICATE_ONLY is for ONE scheduler: replicas (a shard of several, a record sink that is merged with others', an exchange) must return the
             // canonical point — what the merge compares byte for byte — so the flag is ignored there (include/hqtick.h).
             if (pb.certificate_only && (ctx->shard_count > 1 || ctx->sink || ctx->xfn || ctx->comm)) pb.certificate_only = false;
@@ -1441,9 +1479,273 @@ struct TickRun {
     }
 };
 
+
+// ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12; csrc/assigned.hip)
+bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm || ctx->sink; }
+
+// the request tables of a snapshot, kept when they differ from the ones the ledger has (a few hundred bytes compared)
+void ledger_take_requests(hqtick_ctx *ctx, const hqtick_snapshot *s) {
+    Ledger &a = ctx->asg;
+    const uint32_t Q = s->n_requests;
+    if (Q && (!s->rq_variant_off || !s->variant_entry_off)) return;  // (validate() reports it)
+    const uint32_t nv = Q ? s->rq_variant_off[Q] : 0, ne = nv ? s->variant_entry_off[nv] : 0;
+    if (ne && (!s->entry_resource || !s->entry_kind || !s->entry_amount)) return;
+    if (a.rq_off.size() == (size_t)Q + 1 && a.vent_off.size() == (size_t)nv + 1 && a.ent_res.size() == ne && std::equal(a.rq_off.begin(), a.rq_off.end(), s->rq_variant_off ? s->rq_variant_off : a.rq_off.data()) &&
+        (nv == 0 || std::equal(a.vent_off.begin(), a.vent_off.end(), s->variant_entry_off)) && (ne == 0 || (std::equal(a.ent_res.begin(), a.ent_res.end(), s->entry_resource) &&
+        std::equal(a.ent_kind.begin(), a.ent_kind.end(), s->entry_kind) && std::equal(a.ent_amt.begin(), a.ent_amt.end(), s->entry_amount))))
+        return;
+    a.rq_off.assign(1, 0); if (Q) a.rq_off.assign(s->rq_variant_off, s->rq_variant_off + Q + 1);
+    a.vent_off.assign(1, 0); if (nv) a.vent_off.assign(s->variant_entry_off, s->variant_entry_off + nv + 1);
+    a.ent_res.assign(s->entry_resource, s->entry_resource + ne); a.ent_kind.assign(s->entry_kind, s->entry_kind + ne); a.ent_amt.assign(s->entry_amount, s->entry_amount + ne);
+    a.req_dirty = true;
+}
+
+hqasg::Table ledger_table(Ledger &a, bool second = false) {
+    if (second) return hqasg::Table{a.key2.as<uint64_t>(), a.wid2.as<uint32_t>(), a.rq2.as<uint32_t>(), a.var2.as<uint8_t>(), a.prio2.as<uint64_t>(), a.claim2.as<uint32_t>(), 0};
+    return hqasg::Table{a.key.as<uint64_t>(), a.wid.as<uint32_t>(), a.rq.as<uint32_t>(), a.var.as<uint8_t>(), a.prio.as<uint64_t>(), a.claim.as<uint32_t>(), a.cap - 1};
+}
+hqasg::Rows ledger_rows(hqtick_ctx *ctx) {
+    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
+    unsigned char *base = ctx->d_cluster.as<unsigned char>();
+    return hqasg::Rows{ctx->asg.wids.as<uint32_t>(), W, R, reinterpret_cast<const uint64_t *>(base), reinterpret_cast<uint64_t *>(base + (size_t)W * R * 8), ctx->asg.counts.as<uint32_t>(), ctx->asg.stride};
+}
+hqasg::Req ledger_req(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    const size_t Q = a.rq_off.size() - 1, nv = a.vent_off.size() - 1, ne = a.ent_res.size();
+    const size_t o_vo = (Q + 1) * 4, o_res = o_vo + (nv + 1) * 4, o_amt = (o_res + ne * 4 + 7) & ~(size_t)7, o_kind = o_amt + ne * 8;
+    unsigned char *d = a.req.as<unsigned char>();
+    return hqasg::Req{reinterpret_cast<const uint32_t *>(d), reinterpret_cast<const uint32_t *>(d + o_vo), reinterpret_cast<const uint32_t *>(d + o_res), d + o_kind,
+                      reinterpret_cast<const uint64_t *>(d + o_amt), (uint32_t)Q};
+}
+// request tables + count-table width on the device, as the host has them
+int ledger_sync_req(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    const uint32_t nv = (uint32_t)a.vent_off.size() - 1, W = ctx->cl_W;
+    if (nv > a.stride) {  // new variant slots: a wider count table, rows copied over
+        const uint32_t ns = std::max<uint32_t>(16, (nv + 15) & ~15u);
+        if (!a.counts2.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
+        HQ_HIP(hipMemsetAsync(a.counts2.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
+        if (a.stride) HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W, nullptr, W, a.counts2.as<uint32_t>(), ns, a.stride, ctx->stream));
+        std::swap(a.counts, a.counts2); a.stride = ns;
+        a.dirty = true;
+    }
+    if (!a.req_dirty) return 0;
+    const size_t Q = a.rq_off.size() - 1, ne = a.ent_res.size();
+    const size_t o_vo = (Q + 1) * 4, o_res = o_vo + ((size_t)nv + 1) * 4, o_amt = (o_res + ne * 4 + 7) & ~(size_t)7, o_kind = o_amt + ne * 8, bytes = o_kind + ne + 64;
+    std::vector<unsigned char> h(bytes, 0);
+    memcpy(h.data(), a.rq_off.data(), (Q + 1) * 4); memcpy(h.data() + o_vo, a.vent_off.data(), ((size_t)nv + 1) * 4);
+    if (ne) { memcpy(h.data() + o_res, a.ent_res.data(), ne * 4); memcpy(h.data() + o_amt, a.ent_amt.data(), ne * 8); memcpy(h.data() + o_kind, a.ent_kind.data(), ne); }
+    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (the previous tables may still be read by a queued kernel)
+    if (!a.req.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request tables");
+    HQ_HIP(hipMemcpy(a.req.p, h.data(), bytes, hipMemcpyHostToDevice));
+    a.req_dirty = false;
+    return 0;
+}
+int ledger_upload_wids(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    const std::vector<uint32_t> &id = ctx->mirror.id;
+    if (!a.wids.ensure(id.size() * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger worker ids");
+    if (!id.empty()) HQ_HIP(hipMemcpyAsync(a.wids.p, id.data(), id.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
+    return 0;
+}
+uint32_t *ledger_ctr(hqtick_ctx *ctx) {
+    if (!ctx->asg.h_ctr.ensure(64) || !ctx->asg.ctr.ensure(64) || hipMemsetAsync(ctx->asg.ctr.p, 0, 64, ctx->stream) != hipSuccess) return nullptr;
+    uint32_t *c = ctx->asg.h_ctr.as<uint32_t>();
+    for (uint32_t i = 0; i < hqasg::C_N; i++) c[i] = 0;
+    return c;
+}
+// room for `more` entries: live + tombstones + more stay under half the capacity; otherwise the live entries move to a fresh table
+int ledger_reserve(hqtick_ctx *ctx, uint64_t more) {
+    Ledger &a = ctx->asg;
+    if (a.cap && (a.n_live + a.n_tomb + more) * 2 <= a.cap) return 0;
+    uint64_t want = 1024; while (want < (a.n_live + more) * 4) want <<= 1;
+    if (want > (1ull << 31)) return fail(ctx, HQTICK_E_CAPACITY, "assignment ledger: more than 2^29 entries");
+    const uint32_t nc = (uint32_t)want;
+    if (!a.key2.ensure((size_t)nc * 8) || !a.wid2.ensure((size_t)nc * 4) || !a.rq2.ensure((size_t)nc * 4) || !a.var2.ensure(nc) || !a.prio2.ensure((size_t)nc * 8) || !a.claim2.ensure((size_t)nc * 4))
+        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment ledger");
+    hqasg::Table to = ledger_table(a, true); to.mask = nc - 1;
+    HQ_HIP(hqasg::clear(to, ctx->stream));
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    if (a.cap) HQ_HIP(hqasg::rehash(ledger_table(a), to, a.ctr.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    if (a.cap && (c[hqasg::C_FULL] || c[hqasg::C_DONE] != a.n_live)) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: rebuild lost entries");
+    std::swap(a.key, a.key2); std::swap(a.wid, a.wid2); std::swap(a.rq, a.rq2); std::swap(a.var, a.var2); std::swap(a.prio, a.prio2); std::swap(a.claim, a.claim2);
+    a.cap = nc; a.n_tomb = 0;
+    return 0;
+}
+// an insert batch from host columns (staged in pinned memory, read in place)
+int ledger_insert_host(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free,
+                       const uint32_t *col_rq, uint32_t *fresh, uint32_t *bad, uint32_t *dup) {
+    Ledger &a = ctx->asg;
+    *fresh = *bad = *dup = 0;
+    if (!n) return 0;
+    if (int rc = ledger_reserve(ctx, n)) return rc;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    const size_t o_w = (size_t)n * 8, o_q = o_w + (size_t)n * 4, o_p = (o_q + (size_t)n * 4 + 7) & ~(size_t)7, o_v = o_p + (size_t)n * 8, bytes = o_v + n + 16;
+    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
+    memcpy(h, id, (size_t)n * 8); memcpy(h + o_w, wid, (size_t)n * 4); memcpy(h + o_v, var, n);
+    if (rq) memcpy(h + o_q, rq, (size_t)n * 4); else for (uint32_t i = 0; i < n; i++) reinterpret_cast<uint32_t *>(h + o_q)[i] = hqasg::RQ_LOOKUP;
+    if (prio) memcpy(h + o_p, prio, (size_t)n * 8); else memset(h + o_p, 0, (size_t)n * 8);
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    hqasg::Items it{};
+    it.n = n; it.id = reinterpret_cast<const uint64_t *>(d); it.wid = reinterpret_cast<const uint32_t *>(d + o_w); it.rq = reinterpret_cast<const uint32_t *>(d + o_q);
+    it.variant = d + o_v; it.prio = reinterpret_cast<const uint64_t *>(d + o_p);
+    it.col_id = ctx->d_tid.as<uint64_t>(); it.col_prio = ctx->d_tprio.as<uint64_t>(); it.col_rq = col_rq ? col_rq : ctx->d_trq.as<uint32_t>(); it.col_n = ctx->n_ready;
+    HQ_HIP(hqasg::insert(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), it, upsert, apply_free, a.ctr.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
+    *fresh = c[hqasg::C_OUT]; *bad = c[hqasg::C_BAD]; *dup = c[hqasg::C_DUP];
+    a.n_live += c[hqasg::C_OUT]; a.dirty = true;
+    return 0;
+}
+
+// a tick's placement becomes ledger state: its ASSIGN records and its redirects (upserts: a re-targeted task moves), free rows = the tick's new_free
+int ledger_apply_tick(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    a.pending = false;
+    const uint32_t W = ctx->cl_W, n_rec = a.pend_off.empty() ? 0u : a.pend_off.back();
+    const uint32_t *col_rq = a.pend_saved ? a.saved_rq.as<uint32_t>() : ctx->d_trq.as<uint32_t>();
+    if (a.pend_off.size() != (size_t)W + 1 || a.pend_free.size() != (size_t)W * ctx->cl_R) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the worker set changed under a pending tick");
+    if (n_rec) {
+        if (int rc = ledger_reserve(ctx, n_rec)) return rc;
+        if (int rc = ledger_sync_req(ctx)) return rc;
+        // the records cross once by DMA into HBM: [off W + 1][task n][variant n][kind n]
+        const size_t o_t = (((size_t)W + 1) * 4 + 7) & ~(size_t)7, o_v = o_t + (size_t)n_rec * 8, o_k = o_v + n_rec, bytes = o_k + n_rec + 16;
+        if (!a.batch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger batch");
+        unsigned char *d = a.batch.as<unsigned char>();
+        HQ_HIP(hipMemcpyAsync(d, a.pend_off.data(), ((size_t)W + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        HQ_HIP(hipMemcpyAsync(d + o_t, a.pend_task, (size_t)n_rec * 8, hipMemcpyHostToDevice, ctx->stream));
+        HQ_HIP(hipMemcpyAsync(d + o_v, a.pend_var, n_rec, hipMemcpyHostToDevice, ctx->stream));
+        HQ_HIP(hipMemcpyAsync(d + o_k, a.pend_kind, n_rec, hipMemcpyHostToDevice, ctx->stream));
+        uint32_t *c = ledger_ctr(ctx);
+        if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+        hqasg::Items it{};
+        it.n = n_rec; it.rec_off = reinterpret_cast<const uint32_t *>(d); it.rec_task = reinterpret_cast<const uint64_t *>(d + o_t); it.rec_variant = d + o_v; it.rec_kind = d + o_k;
+        it.col_id = ctx->d_tid.as<uint64_t>(); it.col_prio = ctx->d_tprio.as<uint64_t>(); it.col_rq = col_rq; it.col_n = ctx->n_ready;
+        HQ_HIP(hqasg::insert(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), it, 1, 0, a.ctr.as<uint32_t>(), ctx->stream));
+        HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+        HQ_HIP(hipStreamSynchronize(ctx->stream));
+        if (c[hqasg::C_FULL] || c[hqasg::C_BAD]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a record of the tick could not be entered");
+        a.n_live += c[hqasg::C_OUT];
+    }
+    if (!a.red_id.empty()) {
+        uint32_t fresh = 0, bad = 0, dup = 0;
+        if (int rc = ledger_insert_host(ctx, (uint32_t)a.red_id.size(), a.red_id.data(), a.red_wid.data(), a.red_rq.data(), a.red_var.data(), a.red_prio.data(), 1, 0, col_rq, &fresh, &bad, &dup)) return rc;
+        if (bad) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a redirect of the tick could not be entered");
+    }
+    // free rows: the tick's new_free (Worker::insert_sn_task / remove_sn_task of mapping.rs, computed by the tick itself)
+    if (W && ctx->cl_R) {
+        unsigned char *base = ctx->d_cluster.as<unsigned char>();
+        HQ_HIP(hipMemcpyAsync(base + (size_t)W * ctx->cl_R * 8, a.pend_free.data(), (size_t)W * ctx->cl_R * 8, hipMemcpyHostToDevice, ctx->stream));
+        HQ_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->mirror.free_ = a.pend_free;
+    }
+    a.dirty = true;
+    return 0;
+}
+
+// a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
+// (an add, a remove, a compaction, a graph call, an upload) clears last_valid or sets last_consumed — and with it the placement is dropped too
+bool ledger_pending_live(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    if (a.pending && !(ctx->last_valid && !ctx->last_consumed)) a.pending = false;
+    return a.pending;
+}
+int ledger_guard(hqtick_ctx *ctx) {
+    if (ctx->asg.on && ledger_pending_live(ctx)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the last tick's placement is pending (hqtick_ready_consume_last first)");
+    return 0;
+}
+// the count rows follow a membership change: row w of the new set = old row src[w] (>= W_old: a new worker, zero)
+int ledger_repack(hqtick_ctx *ctx, const std::vector<uint32_t> &src, uint32_t W_old) {
+    Ledger &a = ctx->asg;
+    const uint32_t W_new = (uint32_t)src.size();
+    if (!a.counts2.ensure((size_t)W_new * a.stride * 4 + 64) || !a.batch.ensure((size_t)W_new * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
+    if (W_new) HQ_HIP(hipMemcpyAsync(a.batch.p, src.data(), (size_t)W_new * 4, hipMemcpyHostToDevice, ctx->stream));
+    HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W_old, a.batch.as<uint32_t>(), W_new, a.counts2.as<uint32_t>(), a.stride, a.stride, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
+    std::swap(a.counts, a.counts2);
+    a.dirty = true;
+    return 0;
+}
+// every entry of the lost workers leaves the ledger; (id, rq, priority) come back ascending by id (hqtick_cluster_last_requeued)
+int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
+    Ledger &a = ctx->asg;
+    std::vector<uint32_t> lost(worker_id, worker_id + n);
+    std::sort(lost.begin(), lost.end());
+    const uint64_t cap_out = a.n_live + 1;
+    const size_t o_l = 0, o_id = ((size_t)n * 4 + 7) & ~(size_t)7, o_p = o_id + cap_out * 8, o_q = o_p + cap_out * 8, bytes = o_q + cap_out * 4 + 16;
+    if (!a.scratch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    unsigned char *d = a.scratch.as<unsigned char>();
+    HQ_HIP(hipMemcpyAsync(d + o_l, lost.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    HQ_HIP(hqasg::evict(ledger_table(a), n, reinterpret_cast<const uint32_t *>(d + o_l), reinterpret_cast<uint64_t *>(d + o_id), reinterpret_cast<uint32_t *>(d + o_q),
+                        reinterpret_cast<uint64_t *>(d + o_p), (uint32_t)cap_out, a.ctr.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t k = c[hqasg::C_OUT];
+    if (k > a.n_live || k >= cap_out) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
+    std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k);
+    if (k) {
+        HQ_HIP(hipMemcpy(id.data(), d + o_id, (size_t)k * 8, hipMemcpyDeviceToHost));
+        HQ_HIP(hipMemcpy(pr.data(), d + o_p, (size_t)k * 8, hipMemcpyDeviceToHost));
+        HQ_HIP(hipMemcpy(rq.data(), d + o_q, (size_t)k * 4, hipMemcpyDeviceToHost));
+    }
+    std::vector<uint32_t> ord(k);
+    for (uint32_t i = 0; i < k; i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return id[x] < id[y]; });
+    for (uint32_t i : ord) { a.rq_task.push_back(id[i]); a.rq_prio.push_back(pr[i]); a.rq_rq.push_back(rq[i]); }
+    a.n_live -= k; a.n_tomb += k; a.dirty = true;
+    return 0;
+}
+
+// the host mirror (free rows, counts) from the device tables: one synchronisation, two copies; then the assigned CSR of the host stages
+int ledger_sync_mirror(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    if (a.dirty) {
+        ctx->mirror.free_.resize((size_t)W * R); a.h_counts.resize((size_t)W * a.stride);
+        unsigned char *base = ctx->d_cluster.as<unsigned char>();
+        if (W && R) HQ_HIP(hipMemcpyAsync(ctx->mirror.free_.data(), base + (size_t)W * R * 8, (size_t)W * R * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (W && a.stride) HQ_HIP(hipMemcpyAsync(a.h_counts.data(), a.counts.p, (size_t)W * a.stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HQ_HIP(hipStreamSynchronize(ctx->stream));
+        a.dirty = false; a.agg_dirty = true;
+    }
+    if (!a.agg_dirty) return 0;
+    // O(W x variant slots), not O(running tasks): the count table is what GapCache and Worker::is_free need
+    const uint32_t Q = (uint32_t)a.rq_off.size() - 1;
+    a.agg_off.assign((size_t)W + 1, 0); a.agg_rq.clear(); a.agg_cnt.clear(); a.agg_var.clear();
+    for (uint32_t w = 0; w < W; w++) {
+        const uint32_t *row = a.h_counts.data() + (size_t)w * a.stride;
+        for (uint32_t q = 0; q < Q; q++)
+            for (uint32_t v = a.rq_off[q]; v < a.rq_off[q + 1]; v++)
+                if (row[v]) { a.agg_rq.push_back(q); a.agg_var.push_back((uint8_t)(v - a.rq_off[q])); a.agg_cnt.push_back(row[v]); }
+        a.agg_off[w + 1] = (uint32_t)a.agg_rq.size();
+    }
+    a.agg_dirty = false;
+    return 0;
+}
+
+
 int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool use_resident) {
     hqtick_snapshot full;
     bool copied = false;
+    if (ctx->asg.on && s) {  // the assignment ledger (ABI 12) is the tick's only source of the running tasks
+        if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "assignment ledger on a sharded or replica context");
+        if (s->worker_id || !(ctx->cluster_valid && ctx->mirror.valid)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
+        if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
+        HQ_HIP(hipSetDevice(ctx->device));
+        ctx->asg.pending = false;  // (a tick that was never consumed is abandoned, as its selection is)
+        ledger_take_requests(ctx, s);
+        if (int rc = ledger_sync_mirror(ctx)) return rc;
+    }
     if (s && s->n_workers == HQ_WORKERS_RESIDENT && !(s->worker_id == nullptr && ctx->cluster_valid && ctx->mirror.valid))
         return fail(ctx, HQTICK_E_INVALID, s->worker_id ? "n_workers == HQ_WORKERS_RESIDENT with worker arrays in the snapshot"
                                                          : "n_workers == HQ_WORKERS_RESIDENT without a resident worker set (hqtick_cluster_upload; dropped by hqtick_cluster_drop)");
@@ -1528,6 +1830,30 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             if (ctx->red_worker[i] < W) { e.has_redirect = true; e.target_id = s->worker_id[ctx->red_worker[i]]; e.variant = ctx->red_variant[i]; }
         }
     }
+    if (rc >= 0 && ctx->asg.on) {  // the placement enters the ledger when it becomes state: now, or at hqtick_ready_consume_last in the two-call form
+        Ledger &a = ctx->asg;
+        const uint32_t W = s->n_workers;
+        a.pend_off.assign(ctx->rec_off.begin(), ctx->rec_off.end()); a.pend_task = out->rec_task; a.pend_var = out->rec_variant; a.pend_kind = out->rec_kind;
+        a.pend_free = ctx->new_free;
+        a.red_id.clear(); a.red_wid.clear(); a.red_rq.clear(); a.red_var.clear(); a.red_prio.clear();
+        for (uint32_t i = 0; i < out->n_redirects; i++) {
+            uint32_t rq = hqasg::RQ_LOOKUP; uint64_t pr = 0;
+            if (out->redirect_kind[i] == HQ_REDIRECT_FROM_PREFILL && s->prefill_off)  // out of a prefill set: not in the ready set, the snapshot's prefill sets know it
+                for (uint32_t q = 0; q < s->n_requests && rq == hqasg::RQ_LOOKUP; q++)
+                    for (uint32_t j = s->prefill_off[q]; j < s->prefill_off[q + 1]; j++) if (s->prefill_task[j] == out->redirect_task[i]) { rq = q; pr = s->prefill_priority[q]; break; }
+            a.red_id.push_back(out->redirect_task[i]); a.red_wid.push_back(out->redirect_worker[i] < W ? s->worker_id[out->redirect_worker[i]] : HQ_NO_WORKER);
+            a.red_rq.push_back(rq); a.red_var.push_back(out->redirect_variant[i]); a.red_prio.push_back(pr);
+        }
+        const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
+        a.pend_saved = in_tick; a.pending = true;
+        if (!use_resident || in_tick) {
+            if (int r2 = ledger_apply_tick(ctx)) {  // (the tick's tasks have left the ready set: without the placement the ledger is no longer the truth)
+                a.on = false; a.pending = false;
+                ctx->err += " (the assignment ledger is switched off: upload the worker set and enable it again)";
+                return r2;
+            }
+        }
+    }
     return rc;
 }
 
@@ -1540,7 +1866,7 @@ uint32_t hqtick_abi_version(void) { return HQTICK_ABI_VERSION; }
 const char *hqtick_build_arch(void) { return "gfx950"; }
 
 int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
-    if (!config || !out_ctx || (config->abi_version != HQTICK_ABI_VERSION && config->abi_version != 10u)) return HQTICK_E_INVALID;  // (11 added a function only: a config written for 10 is the same struct)
+    if (!config || !out_ctx || (config->abi_version != HQTICK_ABI_VERSION && config->abi_version != 10u && config->abi_version != 11u)) return HQTICK_E_INVALID;  // (11 and 12 added functions only: a config written for 10 is the same struct)
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || config->device_index < 0 || config->device_index >= n) return HQTICK_E_NO_DEVICE;
     hipDeviceProp_t prop;
@@ -1595,6 +1921,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     hipSetDevice(ctx->device);
     if (ctx->comm) { rccl_destroy_comm(ctx); }
     ctx->graph.release();
+    ctx->asg.release_all();
     ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_a.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_add.release(); ctx->h_addp.release(); ctx->h_retr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release(); ctx->h_lv.release(); ctx->h_ord.release(); ctx->h_ordh.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
@@ -1635,7 +1962,7 @@ int hqtick_upload_ready(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, co
             HQ_HIP(hipStreamSynchronize(ctx->stream));
         }
     }
-    ctx->n_ready = n; ctx->n_live = n; ctx->resident = true; ctx->levels_valid = false; ctx->last_valid = false; ctx->last_consumed = true;
+    ctx->n_ready = n; ctx->n_live = n; ctx->resident = true; ctx->levels_valid = false; ctx->last_valid = false; ctx->last_consumed = true; ctx->asg.pending = false;
     ctx->max_id = 0; ctx->max_id_valid = true;
     if (sorted) { if (n) ctx->max_id = task_id[n - 1]; } else for (uint64_t i = 0; i < n; i++) ctx->max_id = std::max(ctx->max_id, task_id[i]);
     return 0;
@@ -1668,7 +1995,7 @@ int rebuild_ready(hqtick_ctx *ctx, const uint64_t *aid, const uint64_t *aprio, c
         if (flag[0] & 4u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: a task id is already in the ready set");
         if (flag[0] & 8u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: ids not strictly ascending");
         if (flag[0] & 16u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: request id 0xFFFFFFFF is reserved");
-        ctx->n_ready = N + n_add; ctx->n_live += n_add; ctx->last_valid = false; ctx->last_consumed = true; ctx->max_id = last_id; ctx->n_appends++;
+        ctx->n_ready = N + n_add; ctx->n_live += n_add; ctx->last_valid = false; ctx->last_consumed = true; ctx->max_id = last_id; ctx->n_appends++; ctx->asg.pending = false;
         if (ctx->n_ready > 4096 && ctx->n_live * 2 < ctx->n_ready) return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0);  // (see hqtick_ready_add_packed)
         return 0;
     }
@@ -1709,7 +2036,7 @@ int rebuild_ready(hqtick_ctx *ctx, const uint64_t *aid, const uint64_t *aprio, c
         if (new_n) { ctx->max_id = *last_back; ctx->max_id_valid = true; }  // (only of columns that are swapped in: a refused batch leaves the bound as it was)
     }
     std::swap(ctx->d_tid, ctx->d_tid2); std::swap(ctx->d_tprio, ctx->d_tprio2); std::swap(ctx->d_trq, ctx->d_trq2);
-    ctx->n_ready = new_n; ctx->n_live = new_n; ctx->last_valid = false; ctx->last_consumed = true;
+    ctx->n_ready = new_n; ctx->n_live = new_n; ctx->last_valid = false; ctx->last_consumed = true; ctx->asg.pending = false;
     if (N == 0 && n_add) { ctx->max_id = first_batch_last_id; ctx->max_id_valid = true; }  // (the validated batch's own last id, read back from the device: the bound later appends are decided by)
     return 0;
 }
@@ -1722,6 +2049,14 @@ uint64_t hqtick_ready_count(const hqtick_ctx *ctx) { return ctx && ctx->resident
 int hqtick_ready_consume_last(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (ledger_pending_live(ctx)) {  // the last tick's placement enters the assignment ledger (before the selection's request ids become tombstones)
+        HQ_HIP(hipSetDevice(ctx->device));
+        if (int rc = ledger_apply_tick(ctx)) {
+            ctx->asg.on = false;
+            ctx->err += " (the assignment ledger is switched off: upload the worker set and enable it again)";
+            return rc;
+        }
+    }
     if (ctx->last_consumed) {  // nothing handed out since the last consume (or the tick consumed it itself: HQTICK_FLAG_CONSUME_IN_TICK)
         if (ctx->n_ready > 4096 && ctx->n_live * 2 < ctx->n_ready) { HQ_HIP(hipSetDevice(ctx->device)); return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0); }
         return 0;
@@ -1757,7 +2092,7 @@ int hqtick_ready_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) {
     HQ_HIP(hipMemcpyAsync(ctx->d_add.p, ctx->h_add.p, n * 8, hipMemcpyHostToDevice, ctx->stream));
     HQ_HIP(hqk::ready_mark_removed(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready, ctx->d_add.as<uint64_t>(), (uint32_t)n, ctx->h_q.dev<uint32_t>(), ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->n_live -= cnt[0]; ctx->last_valid = false; ctx->last_consumed = true;
+    ctx->n_live -= cnt[0]; ctx->last_valid = false; ctx->last_consumed = true; ctx->asg.pending = false;
     return (int)cnt[0];  // number of tasks that were in the set
 }
 
@@ -1983,6 +2318,8 @@ int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) {
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     ctx->cl_rt.assign(h + L.o_amt, h + L.bytes);
     ctx->cl_W = W; ctx->cl_R = R; ctx->cluster_valid = true;
+    ctx->asg.on = false; ctx->asg.pending = false;  // a new worker set: the ledger is enabled (seeded) again for it
+    ledger_take_requests(ctx, s);
     {   // the host mirror (ABI 7)
         hqtick_ctx::ClusterMirror &m = ctx->mirror;
         m.id.assign(s->worker_id, s->worker_id + W);
@@ -2002,6 +2339,7 @@ int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) {
 int hqtick_cluster_update_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_index, const uint64_t *free_rows, const int64_t *remaining_ns) {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->cluster_valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_update_workers without hqtick_cluster_upload");
+    if (int rc = ledger_guard(ctx)) return rc;
     if (n == 0) return 0;
     if (!worker_index || !free_rows) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_update_workers: null array");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
@@ -2029,7 +2367,7 @@ int hqtick_cluster_update_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
 
 int hqtick_cluster_drop(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
-    ctx->cluster_valid = false; ctx->mirror.valid = false;
+    ctx->cluster_valid = false; ctx->mirror.valid = false; ctx->asg.on = false; ctx->asg.pending = false;
     return 0;
 }
 
@@ -2076,7 +2414,9 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
     for (uint32_t i = 0; i < W + n; i++) src[i] = i;
     std::vector<int64_t> rem(n, HQ_NO_TIME_LIMIT);
     if (remaining_ns) rem.assign(remaining_ns, remaining_ns + n);
+    if (int rc = ledger_guard(ctx)) return rc;
     if (int rc = cluster_repack(ctx, src, n, total_rows, free_rows, rem.data())) return rc;
+    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W)) return rc; }
     m.id.insert(m.id.end(), worker_id, worker_id + n);
     m.total.insert(m.total.end(), total_rows, total_rows + (size_t)n * R); m.free_.insert(m.free_.end(), free_rows, free_rows + (size_t)n * R);
     m.rem.insert(m.rem.end(), rem.begin(), rem.end());
@@ -2085,6 +2425,7 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
         m.group.push_back(group ? group[i] : 0u); if (group && group[i] + 1 > m.n_groups) m.n_groups = group[i] + 1;
     }
     m.blk_dirty = true;
+    if (ctx->asg.on) return ledger_upload_wids(ctx);
     return 0;
 }
 
@@ -2103,7 +2444,11 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     }
     std::vector<uint32_t> src; src.reserve(W - n);
     for (uint32_t w = 0; w < W; w++) if (!gone[w]) src.push_back(w);
+    if (int rc = ledger_guard(ctx)) return rc;
+    ctx->asg.rq_task.clear(); ctx->asg.rq_rq.clear(); ctx->asg.rq_prio.clear();
+    if (ctx->asg.on) { if (int rc = ledger_evict(ctx, n, worker_id)) return rc; }  // on_remove_worker: the lost workers' tasks leave the ledger (reactor.rs:64-147)
     if (int rc = cluster_repack(ctx, src, 0, nullptr, nullptr, nullptr)) return rc;
+    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W)) return rc; }
     uint32_t k = 0;
     for (uint32_t w = 0; w < W; w++) {
         if (gone[w]) { m.blocked.erase(m.id[w]); continue; }
@@ -2135,6 +2480,14 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     }
     m.id.resize(k); m.rem.resize(k); m.min_util.resize(k); m.flags.resize(k); m.group.resize(k); m.total.resize((size_t)k * R); m.free_.resize((size_t)k * R);
     m.blk_dirty = true;
+    if (ctx->asg.on) {
+        if (int rc = ledger_upload_wids(ctx)) return rc;
+        // ... and go back into the resident ready set with their priority and request (add_ready_task), ids ascending
+        if (!ctx->asg.rq_task.empty() && ctx->resident) {
+            const Ledger &a = ctx->asg;
+            if (int rc = hqtick_ready_add(ctx, a.rq_task.size(), a.rq_task.data(), a.rq_prio.data(), a.rq_rq.data())) return rc;
+        }
+    }
     return 0;
 }
 
@@ -2193,6 +2546,128 @@ int hqtick_retract_response(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, con
 }
 
 uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? (uint32_t)ctx->retr.size() : 0u; }
+
+// ---- assignment ledger (ABI 12; include/hqtick.h) ----
+int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
+    if (ctx->cfg.flags & (HQTICK_FLAG_COMPACT_RECORDS | HQTICK_FLAG_COMPACT_DELTA16)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not with compact records");
+    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
+    if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: null array");
+    HQ_HIP(hipSetDevice(ctx->device));
+    Ledger &a = ctx->asg;
+    a.on = false; a.pending = false; a.cap = 0; a.n_live = 0; a.n_tomb = 0; a.last_unknown = 0; a.stride = 0;
+    a.rq_task.clear(); a.rq_rq.clear(); a.rq_prio.clear();
+    if (int rc = ledger_reserve(ctx, n)) return rc;
+    HQ_HIP(hqasg::clear(ledger_table(a), ctx->stream));
+    a.req_dirty = true;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    const uint32_t W = ctx->cl_W;
+    if (!a.counts.ensure((size_t)W * a.stride * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
+    HQ_HIP(hipMemsetAsync(a.counts.p, 0, (size_t)W * a.stride * 4 + 64, ctx->stream));
+    if (int rc = ledger_upload_wids(ctx)) return rc;
+    uint32_t fresh = 0, bad = 0, dup = 0;
+    if (int rc = ledger_insert_host(ctx, n, task_id, worker_id, rq, variant, priority, 0, 0, nullptr, &fresh, &bad, &dup)) return rc;
+    if (bad || dup) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: an entry names an unknown worker, request or variant, or a task twice");
+    a.on = true; a.dirty = true;
+    return 0;
+}
+
+int hqtick_assigned_disable(hqtick_ctx *ctx) {
+    if (!ctx) return HQTICK_E_INVALID;
+    ctx->asg.on = false; ctx->asg.pending = false;
+    return 0;
+}
+
+static int ledger_pre(hqtick_ctx *ctx) {
+    if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
+    if (int rc = ledger_guard(ctx)) return rc;
+    HQ_HIP(hipSetDevice(ctx->device));
+    return 0;
+}
+
+int hqtick_assigned_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (int rc = ledger_pre(ctx)) return rc;
+    if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add: null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
+    uint32_t fresh = 0, bad = 0, dup = 0;
+    if (int rc = ledger_insert_host(ctx, n, task_id, worker_id, rq, variant, priority, 0, 1, nullptr, &fresh, &bad, &dup)) return rc;
+    ctx->asg.last_unknown = (uint64_t)bad + dup;
+    return (int)fresh;
+}
+
+int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (int rc = ledger_pre(ctx)) return rc;
+    if (n && !task_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_release: null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
+    Ledger &a = ctx->asg;
+    a.last_unknown = 0;
+    if (!n) return 0;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
+    // scratch: [ids n u64][delta W*R u64][pos n u32][last_all W*R u32]
+    const size_t o_dl = (size_t)n * 8, o_pos = o_dl + (size_t)W * R * 8, o_la = o_pos + (size_t)n * 4, bytes = o_la + (size_t)W * R * 4 + 16;
+    if (!a.scratch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    unsigned char *d = a.scratch.as<unsigned char>();
+    HQ_HIP(hipMemsetAsync(d + o_dl, 0, (size_t)W * R * 8, ctx->stream));
+    HQ_HIP(hipMemsetAsync(d + o_la, 0, (size_t)W * R * 4, ctx->stream));
+    if (!a.h_in.ensure((size_t)n * 8 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    memcpy(a.h_in.p, task_id, (size_t)n * 8);
+    HQ_HIP(hipMemcpyAsync(d, a.h_in.p, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    HQ_HIP(hqasg::release(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<uint32_t *>(d + o_pos),
+                          reinterpret_cast<uint32_t *>(d + o_la), reinterpret_cast<uint64_t *>(d + o_dl), a.ctr.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t done = c[hqasg::C_DONE];
+    a.n_live -= done; a.n_tomb += done; a.last_unknown = (uint64_t)c[hqasg::C_UNKNOWN] + c[hqasg::C_DUP]; a.dirty = true;  // (the others of the batch are released either way)
+    if (c[hqasg::C_BAD]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
+    return (int)done;
+}
+
+uint64_t hqtick_assigned_last_unknown(const hqtick_ctx *ctx) { return ctx ? ctx->asg.last_unknown : 0; }
+uint64_t hqtick_assigned_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on ? ctx->asg.n_live : 0; }
+
+int hqtick_assigned_lookup(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint32_t *worker_id, uint8_t *variant) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
+    if (n && (!task_id || !worker_id || !variant)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_lookup: null array");
+    if (!n) return 0;
+    HQ_HIP(hipSetDevice(ctx->device));
+    Ledger &a = ctx->asg;
+    const size_t o_w = (size_t)n * 8, o_v = o_w + (size_t)n * 4, bytes = o_v + n + 16;
+    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
+    memcpy(h, task_id, (size_t)n * 8);
+    HQ_HIP(hqasg::lookup(ledger_table(a), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<uint32_t *>(d + o_w), d + o_v, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(worker_id, h + o_w, (size_t)n * 4); memcpy(variant, h + o_v, n);
+    int found = 0;
+    for (uint32_t i = 0; i < n; i++) found += worker_id[i] != HQ_NO_WORKER;
+    return found;
+}
+
+int hqtick_assigned_free_rows(hqtick_ctx *ctx, uint32_t *n_workers, const uint64_t **free_rows) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
+    HQ_HIP(hipSetDevice(ctx->device));
+    if (int rc = ledger_sync_mirror(ctx)) return rc;
+    if (n_workers) *n_workers = ctx->cl_W;
+    if (free_rows) *free_rows = ctx->mirror.free_.data();
+    return 0;
+}
+
+int hqtick_cluster_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (n) *n = (uint32_t)ctx->asg.rq_task.size();
+    if (task_id) *task_id = ctx->asg.rq_task.data();
+    if (rq) *rq = ctx->asg.rq_rq.data();
+    if (priority) *priority = ctx->asg.rq_prio.data();
+    return 0;
+}
 
 int hqtick_ready_compact(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
@@ -2546,6 +3021,7 @@ int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *
 int hqtick_set_shard(hqtick_ctx *ctx, uint32_t shard_index, uint32_t shard_count) {
     if (!ctx) return HQTICK_E_INVALID;
     if (shard_count > 1 && shard_index >= shard_count) return fail(ctx, HQTICK_E_INVALID, "shard_index >= shard_count");
+    if (shard_count > 1 && ctx->asg.on) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_set_shard: the assignment ledger is on (hqtick_assigned_disable first)");
     ctx->shard_index = shard_count > 1 ? shard_index : 0; ctx->shard_count = shard_count > 1 ? shard_count : 1;
     return 0;
 }

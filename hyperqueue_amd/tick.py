@@ -160,6 +160,7 @@ class Tick:
         sc = snap.to_c() if hasattr(snap, "to_c") else snap
         self._lib.hqtick_cluster_upload.argtypes = [C.c_void_p, C.POINTER(abi.SnapshotC)]
         self._chk(self._lib.hqtick_cluster_upload(self._ctx, C.byref(sc)))
+        self._asg_R = int(sc.n_resources)
 
     def cluster_update_workers(self, worker_index, free_rows, remaining_ns=None):
         """rows whose free resources (and optionally remaining lifetime) changed since the last call"""
@@ -248,6 +249,76 @@ class Tick:
     def cluster_drop(self):
         self._lib.hqtick_cluster_drop.argtypes = [C.c_void_p]
         self._chk(self._lib.hqtick_cluster_drop(self._ctx))
+
+    # -- assignment ledger (include/hqtick.h, ABI 12) -------------------------------------------------------
+    def _asg_cols(self, entries):
+        """entries: [(task, worker id, rq, variant, priority)] -> five C columns"""
+        t = np.ascontiguousarray([e[0] for e in entries], np.uint64); w = np.ascontiguousarray([e[1] for e in entries], np.uint32)
+        q = np.ascontiguousarray([e[2] for e in entries], np.uint32); v = np.ascontiguousarray([e[3] for e in entries], np.uint8)
+        p = np.ascontiguousarray([e[4] for e in entries], np.uint64)
+        keep = (t, w, q, v, p)
+        return keep, [t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), q.ctypes.data_as(abi.u32p), v.ctypes.data_as(abi.u8p), p.ctypes.data_as(abi.u64p)]
+
+    def assigned_enable(self, entries=()):
+        """seed the ledger with [(task, worker id, rq, variant, priority)] (the free rows already count them)"""
+        keep, cols = self._asg_cols(list(entries))
+        f = self._lib.hqtick_assigned_enable
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u32p, abi.u8p, abi.u64p]
+        self._chk(f(self._ctx, len(keep[0]), *cols))
+
+    def assigned_disable(self):
+        self._lib.hqtick_assigned_disable.argtypes = [C.c_void_p]
+        self._chk(self._lib.hqtick_assigned_disable(self._ctx))
+
+    def assigned_add(self, entries) -> int:
+        """tasks that start outside a tick: [(task, worker id, rq, variant, priority)] -> number entered"""
+        keep, cols = self._asg_cols(list(entries))
+        f = self._lib.hqtick_assigned_add
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u32p, abi.u8p, abi.u64p]
+        return self._chk(f(self._ctx, len(keep[0]), *cols))
+
+    def assigned_release(self, task_id) -> int:
+        """remove_sn_task for the ids, in batch order -> number released"""
+        t = np.ascontiguousarray(task_id, np.uint64)
+        f = self._lib.hqtick_assigned_release
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p]
+        return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p)))
+
+    def assigned_last_unknown(self) -> int:
+        f = self._lib.hqtick_assigned_last_unknown
+        f.argtypes = [C.c_void_p]; f.restype = C.c_uint64
+        return int(f(self._ctx))
+
+    def assigned_count(self) -> int:
+        f = self._lib.hqtick_assigned_count
+        f.argtypes = [C.c_void_p]; f.restype = C.c_uint64
+        return int(f(self._ctx))
+
+    def assigned_lookup(self, task_id):
+        """-> (worker ids (HQ_NO_WORKER: not in the ledger), variants)"""
+        t = np.ascontiguousarray(task_id, np.uint64)
+        w = np.zeros(len(t), np.uint32); v = np.zeros(len(t), np.uint8)
+        f = self._lib.hqtick_assigned_lookup
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u8p]
+        self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), v.ctypes.data_as(abi.u8p)))
+        return w, v
+
+    def assigned_free_rows(self) -> np.ndarray:
+        n = C.c_uint32(); p = abi.u64p()
+        f = self._lib.hqtick_assigned_free_rows
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p)]
+        self._chk(f(self._ctx, C.byref(n), C.byref(p)))
+        R = getattr(self, "_asg_R", 0)
+        return abi._np(p, n.value * R, np.uint64).reshape(n.value, R).copy() if n.value and R else np.zeros((n.value, R), np.uint64)
+
+    def cluster_last_requeued(self):
+        """[(task, rq, priority)] the last cluster_remove_workers put back into the resident ready set (ABI 12)"""
+        n = C.c_uint32(); pt, pq, pp = abi.u64p(), abi.u32p(), abi.u64p()
+        f = self._lib.hqtick_cluster_last_requeued
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u64p)]
+        self._chk(f(self._ctx, C.byref(n), C.byref(pt), C.byref(pq), C.byref(pp)))
+        k = n.value
+        return list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pq, k, np.uint32).tolist(), abi._np(pp, k, np.uint64).tolist())) if k else []
 
     # -- device-resident dependency graph (include/hqtick.h, SURVEY §8 f1) --------------------------------------------------
     def _graph_last_ids(self) -> np.ndarray:

@@ -40,7 +40,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HQTICK_ABI_VERSION 11u  /* 11: hqtick_query_resident (hqtick_create still accepts configs written for 10: the config struct is unchanged); 10: HQTICK_FLAG_NO_TICK_CACHES, hqtick_set_kernel_timing takes any non-zero value but 2 as 1, hqtick_graph_blevel leaves a pending hqtick_ready_consume_last alone; 9: hqtick_graph_blevel / _priorities (extension), hqtick_set_kernel_timing(ctx, 2), a failed CONSUME_IN_TICK tick restores its tasks; 8: HQ_WORKERS_RESIDENT, hqtick_cluster_last_reassigned; 7: hqtick_kernel_stats carries the price-sweep figures of coupled ticks; cluster membership deltas */
+#define HQTICK_ABI_VERSION 12u  /* 12: the assignment ledger, hqtick_assigned_* and hqtick_cluster_last_requeued (hqtick_create still accepts configs written for 10 and 11); 11: hqtick_query_resident (hqtick_create still accepts configs written for 10: the config struct is unchanged); 10: HQTICK_FLAG_NO_TICK_CACHES, hqtick_set_kernel_timing takes any non-zero value but 2 as 1, hqtick_graph_blevel leaves a pending hqtick_ready_consume_last alone; 9: hqtick_graph_blevel / _priorities (extension), hqtick_set_kernel_timing(ctx, 2), a failed CONSUME_IN_TICK tick restores its tasks; 8: HQ_WORKERS_RESIDENT, hqtick_cluster_last_reassigned; 7: hqtick_kernel_stats carries the price-sweep figures of coupled ticks; cluster membership deltas */
 
 /* ResourceAmount::MAX                                    common/resources/amount.rs:31 */
 #define HQ_AMOUNT_MAX UINT64_MAX
@@ -453,6 +453,56 @@ int hqtick_retract_response(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, con
                             const uint32_t **assigned_worker_id, const uint8_t **assigned_variant);
 uint32_t hqtick_retracting_count(const hqtick_ctx *ctx);
 int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant);
+
+/*
+ * Assignment ledger (ABI 12): each worker's SingleNodeTaskAssignment (server/worker.rs:40-46) — its assigned / running single-node tasks
+ * and its free_resources — kept by the library on the resident worker set, so that the host no longer sends free rows for task starts and finishes
+ * (hqtick_cluster_update_workers) nor flattens the assigned CSR every tick.  OFF unless enabled; with it off every call behaves as in ABI 11.
+ *   hqtick_assigned_enable     seed: n tasks (ids, worker ids, rq, variant, priority) in state Assigned / Running, or Retracting and counted on their redirect
+ *                              target (worker.rs:249-252).  Needs a resident worker set (hqtick_cluster_upload), whose free rows already account for
+ *                              these tasks: the seed does not change them.  n = 0: an empty ledger.  A second call replaces the ledger.
+ *                              hqtick_cluster_upload (a new worker set) and hqtick_cluster_drop switch it off; hqtick_assigned_disable drops it.
+ *   hqtick_assigned_add        tasks that start outside a tick (task_from_prefilled_to_started, worker.rs:212-221; a Retracting task that starts on the
+ *                              worker it was retracting from, reactor.rs:296-333): insert + free.remove (AMOUNT subtracts with saturation, ALL sets 0,
+ *                              workerload.rs:156-166).  rq and priority come from the caller.  Returns the number entered; ids already in the ledger and
+ *                              entries naming an unknown worker / request / variant are counted (hqtick_assigned_last_unknown) and change nothing.
+ *   hqtick_assigned_release    tasks that finished, failed, were cancelled or rejected while Assigned, or a Retracting task's redirect target after
+ *                              try_remove_redirection: remove_sn_task (worker.rs:223-234), free.add — AMOUNT adds, ALL sets the resource back to the
+ *                              worker's TOTAL (workerload.rs:194-202).  The batch is applied IN ITS ORDER: on one worker "A (AMOUNT), then B (ALL)" leaves
+ *                              the total, "B, then A" the total + amount(A).  Unknown ids and repeats of an id within the batch are counted
+ *                              (hqtick_assigned_last_unknown) and change nothing (the reference's tolerance of stale task updates).  Returns the number released.
+ *   hqtick_assigned_count      entries in the ledger.
+ *   hqtick_assigned_lookup     per id the worker id holding it (HQ_NO_WORKER: not in the ledger) and its variant (0xFF then).  Returns the number found.
+ *   hqtick_assigned_free_rows  the resident worker set's free rows [W x R] as the ledger keeps them (valid until the next call on ctx).
+ *   hqtick_cluster_last_requeued  the tasks the last hqtick_cluster_remove_workers took out of the ledger (on_remove_worker, reactor.rs:64-147) and put
+ *                              back into the resident ready set with their priority and request (add_ready_task), ascending ids — if the context holds
+ *                              one (hqtick_upload_ready); without it they are only reported and the host puts them wherever its queues are.  The merge
+ *                              comes after the membership change: if it fails, the worker is gone and the tasks are out of the ledger, and the host
+ *                              re-adds the reported tasks itself (hqtick_ready_add).  The host still owes
+ *                              their instance-id bumps, crash counters (a task over its limit leaves with hqtick_ready_remove), prefill disposal and client
+ *                              events; it no longer re-adds them.  A Retracting task whose redirect target was lost is among them (the Retracting table drops
+ *                              the redirect, as before).  The lost worker's PREFILLED tasks are still the host's to re-add.
+ * The tick: with the ledger on, a tick runs on the resident worker set (n_workers = HQ_WORKERS_RESIDENT, worker_id = NULL) and assigned_off = NULL; it takes
+ * the per-worker (rq, variant) counts and the free rows from the ledger.  An assigned CSR in the snapshot is HQTICK_E_INVALID (the tick must not see two
+ * truths).  The tick's placement — its ASSIGN records and its redirects (FROM_PREFILL / SAME_WORKER insert on the target, RETARGET moves the task from its
+ * old target) with the free rows of result.new_free — enters the ledger when it becomes state: at hqtick_ready_consume_last in the two-call form, inside the
+ * tick under HQTICK_FLAG_CONSUME_IN_TICK (a tick that fails leaves ledger and free rows as they were), at once after hqtick_run.  Until a pending placement
+ * is consumed, ledger and membership calls are HQTICK_E_INVALID; a tick that is not consumed (any ready-set or graph delta, another tick) is abandoned with
+ * its selection and never enters.  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
+ * tasks have left the ready set, so the host uploads the worker set and enables the ledger again from its own view.
+ * PREFILL records, prefill sets and multi-node tasks stay the host's.  hqtick_cluster_update_workers still works (remaining lifetime, corrections).
+ * HQTICK_E_UNSUPPORTED on a sharded or replica context (hqtick_set_shard with more than one shard, an exchange, a communicator or a record sink) and with
+ * HQTICK_FLAG_COMPACT_RECORDS / _DELTA16.
+ */
+int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority);
+int hqtick_assigned_disable(hqtick_ctx *ctx);
+int hqtick_assigned_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority);
+int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id);
+uint64_t hqtick_assigned_last_unknown(const hqtick_ctx *ctx);
+uint64_t hqtick_assigned_count(const hqtick_ctx *ctx);
+int hqtick_assigned_lookup(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint32_t *worker_id, uint8_t *variant);
+int hqtick_assigned_free_rows(hqtick_ctx *ctx, uint32_t *n_workers, const uint64_t **free_rows);
+int hqtick_cluster_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority);
 
 /*
  * Device-resident dependency graph (BASELINE config 5): the `Waiting{unfinished_deps}` counters and the consumer

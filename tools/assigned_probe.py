@@ -1,0 +1,97 @@
+"""Assignment ledger at c3p scale: a resident add -> tick -> release loop with the ledger (context A) against the same loop on today's
+protocol (context B: the host keeps the free rows, sends the rows every start / finish touched, flattens the assigned CSR per tick).  Prints one JSON line:
+per-step wall clock of both loops (B's host bookkeeping included), the release call for the previous step's tasks, and the ledger's tick-side apply.
+
+    python tools/assigned_probe.py [--steps 20] [--tasks 1000000] [--workers 1024]
+"""
+import argparse
+import dataclasses
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from hyperqueue_amd import abi, workloads  # noqa: E402
+from hyperqueue_amd.tick import Tick  # noqa: E402
+
+
+def _resident(t, snap, csr=None):
+    sc = (csr or snap).to_c(resident_workers=True)
+    if csr is None:
+        sc.assigned_off = None; sc.assigned_rq = None; sc.assigned_variant = None
+    return t.tick_raw(sc, resident=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--tasks", type=int, default=1_000_000)
+    ap.add_argument("--workers", type=int, default=1024)
+    ap.add_argument("--add", type=int, default=188_000)
+    args = ap.parse_args()
+    snap = workloads.make_steady("c3p", seed=3, n_tasks=args.tasks, n_workers=args.workers)
+    W, R = len(snap.worker_id), snap.n_resources
+    snap = dataclasses.replace(snap, assigned=[[] for _ in range(W)], worker_free=np.array(snap.worker_total, np.uint64), _keep=[])
+    ent = [[[(int(r), int(k), int(a)) for (r, k, a) in v["entries"]] for v in rq] for rq in snap.requests]
+    cfg = abi.make_config(time_limit_s=20.0, flags=abi.HQTICK_FLAG_CONSUME_IN_TICK | abi.HQTICK_FLAG_NO_KERNEL_TIMING)
+    a, b = Tick(cfg), Tick(cfg)
+    for t in (a, b):
+        t.cluster_upload(snap); t.upload_ready(snap.task_id, snap.task_priority, snap.task_rq)
+    a.assigned_enable([])
+    total = np.asarray(snap.worker_total, np.uint64).reshape(W, R)
+    free = total.copy(); running = {}; rq_of = dict(zip(snap.task_id.tolist(), snap.task_rq.tolist()))
+    next_id = int(snap.task_id.max()) + 1
+    prev_a, prev_b = [], []
+    ta, tb, trel, ttick_a = [], [], [], []
+    for step in range(args.steps):
+        add = np.arange(next_id, next_id + args.add, dtype=np.uint64); next_id += args.add
+        prio = np.zeros(len(add), np.uint64); rqs = (np.arange(len(add)) % len(snap.requests)).astype(np.uint32)
+        rq_of.update(zip(add.tolist(), rqs.tolist()))
+        # A: release -> add -> tick
+        t0 = time.perf_counter()
+        if prev_a:
+            t1 = time.perf_counter(); a.assigned_release(prev_a); trel.append(time.perf_counter() - t1)
+        a.ready_add(add, prio, rqs)
+        t2 = time.perf_counter(); ra = _resident(a, snap); ttick_a.append(time.perf_counter() - t2)
+        ta.append(time.perf_counter() - t0)
+        pa = abi.parse_result(ra, W, R)
+        prev_a = [tid for recs in pa.records for (tid, v, k) in recs if k == abi.HQ_REC_ASSIGN]
+        # B: the host's bookkeeping as today
+        t0 = time.perf_counter()
+        if prev_b:
+            touched = set()
+            for tid in prev_b:
+                w, q, v = running.pop(tid)
+                for (res, kind, amount) in ent[q][v]:
+                    free[w, res] = total[w, res] if kind == abi.HQ_ENTRY_ALL else free[w, res] + np.uint64(amount)
+                touched.add(w)
+            idx = sorted(touched); b.cluster_update_workers(idx, free[idx])
+        b.ready_add(add, prio, rqs)
+        per_w = [[] for _ in range(W)]
+        for tid, (w, q, v) in running.items():
+            per_w[w].append((q, v))
+        sb = dataclasses.replace(snap, assigned=per_w, worker_free=free.copy(), _keep=[])
+        rb = abi.parse_result(_resident(b, snap, sb), W, R)
+        nf = np.asarray(rb.new_free, np.uint64).reshape(W, R)
+        changed = np.nonzero((nf != free).any(axis=1))[0].tolist(); free = nf.copy()
+        if changed:
+            b.cluster_update_workers(changed, free[changed])
+        prev_b = []
+        for w, recs in enumerate(rb.records):
+            for (tid, v, k) in recs:
+                if k == abi.HQ_REC_ASSIGN:
+                    running[tid] = (w, rq_of[tid], v); prev_b.append(tid)
+        tb.append(time.perf_counter() - t0)
+        assert pa.records == rb.records and a.assigned_count() == len(running)
+    med = lambda x: round(float(np.median(x[2:] if len(x) > 4 else x)) * 1e6, 1)  # noqa: E731
+    print(json.dumps({"steps": args.steps, "tasks": args.tasks, "workers": W, "added_per_step": args.add, "released_per_step": len(prev_a),
+                      "step_us_ledger": med(ta), "step_us_row_deltas": med(tb), "release_call_us": med(trel), "tick_call_us_ledger": med(ttick_a),
+                      "running": a.assigned_count()}))
+    a.close(); b.close()
+
+
+if __name__ == "__main__":
+    main()
