@@ -34,13 +34,21 @@ struct Rows {
     const uint64_t *total; uint64_t *free_;
     uint32_t *counts; uint32_t stride;
 };
-// an insert batch: explicit columns, or the records of a tick (task / variant / kind per record, rec_off [W + 1] gives the worker row)
+// an insert batch from explicit columns (wid: worker ids)
 struct Items {
     uint32_t n;
-    const uint64_t *id; const uint32_t *wid; const uint32_t *rq; const uint8_t *variant; const uint64_t *prio;  // explicit (wid: worker ids)
-    const uint64_t *rec_task; const uint8_t *rec_variant; const uint8_t *rec_kind; const uint32_t *rec_off;      // records (rec_task != nullptr)
-    // rq / priority of an item with rq == RQ_LOOKUP (all records): the ready-set columns, ids ascending
+    const uint64_t *id; const uint32_t *wid; const uint32_t *rq; const uint8_t *variant; const uint64_t *prio;
+    // rq / priority of an item with rq == RQ_LOOKUP: the ready-set columns, ids ascending
     const uint64_t *col_id; const uint64_t *col_prio; const uint32_t *col_rq; uint64_t col_n;
+};
+// a tick's placement as the mapping kernel staged it in HBM (kernels.h: hqk::Stage), one entry per record; meta = variant | kind << 8, entries whose kind
+// is not HQ_REC_ASSIGN are skipped.  The priority is levels[level] (the dense scan's level table, n_levels entries); levels == nullptr (the ordered view,
+// whose run table lives in host memory): the priority alone is looked up by id in the ready-set columns col_id / col_prio.
+struct Staged {
+    uint32_t n;
+    const uint64_t *task; const uint32_t *rq; const uint32_t *row; const uint32_t *level; const uint16_t *meta;
+    const uint64_t *levels; uint32_t n_levels;
+    const uint64_t *col_id; const uint64_t *col_prio; uint64_t col_n;
 };
 // counters of one operation, in device memory, one atomic per wavefront (insert: C_OUT = entries that were not there before; evict: entries gathered)
 enum Ctr : uint32_t { C_DONE = 0, C_UNKNOWN = 1, C_DUP = 2, C_FULL = 3, C_BAD = 4, C_OUT = 5, C_N = 8 };
@@ -49,6 +57,8 @@ hipError_t clear(Table t, hipStream_t s);
 // insert (upsert != 0: an id already present moves to the new worker / variant, its old count is given back; else it is counted as a duplicate).
 // apply_free != 0: Worker::insert_sn_task's free.remove on the worker's row (AMOUNT subtracts with saturation, ALL sets 0; these commute).
 hipError_t insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr, hipStream_t s);
+// the staged placement of a tick as upserts, free rows untouched (they become the tick's new_free)
+hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipStream_t s);
 // release in batch order with the last-ALL rule; scratch: pos [n] u32, last_all [W * R] u32, delta [W * R] u64 (zero on entry and on return)
 hipError_t release(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT]

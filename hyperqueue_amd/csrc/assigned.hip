@@ -80,27 +80,10 @@ __global__ void k_clear(Table t) {
 }
 
 enum InsertStatus : int { S_SKIP = 0, S_FRESH, S_MOVED, S_DUP, S_BAD, S_FULL };
-__device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Rows &r, const Items &it, int upsert, int apply_free, uint32_t i) {
-    uint64_t id, prio = 0; uint32_t row, wid, rq = RQ_LOOKUP, v;
-    if (it.rec_task) {
-        if (it.rec_kind[i] != HQ_REC_ASSIGN) return S_SKIP;  // prefills do not enter the ledger
-        id = it.rec_task[i]; v = it.rec_variant[i];
-        uint32_t lo = 0, hi = r.W;  // the worker whose record range holds i: the last w with rec_off[w] <= i
-        while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (it.rec_off[mid] <= i) lo = mid; else hi = mid - 1; }
-        row = lo; wid = r.wid[row];
-    } else {
-        id = it.id[i]; wid = it.wid[i]; v = it.variant[i];
-        if (it.rq) rq = it.rq[i];
-        if (it.prio) prio = it.prio[i];
-        row = row_of(r, wid);
-    }
-    if (row == NONE || id >= HT_TOMB) return S_BAD;
-    if (rq == RQ_LOOKUP) {  // rq and priority of a task of the ready set (ids ascending; a consumed task keeps its id and priority)
-        uint64_t lo = 0, hi = it.col_n;
-        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (it.col_id[mid] < id) lo = mid + 1; else hi = mid; }
-        if (lo >= it.col_n || it.col_id[lo] != id) return S_BAD;
-        rq = it.col_rq[lo]; prio = it.col_prio[lo];
-    }
+// the entry (id -> wid, rq, v, prio) enters its bucket and the count of (row, slot) is raised
+__device__ __forceinline__ int enter(const Table &t, const Req &q, const Rows &r, uint64_t id, uint32_t row, uint32_t wid, uint32_t rq, uint32_t v, uint64_t prio, int upsert,
+                                     int apply_free) {
+    if (row >= r.W || id >= HT_TOMB) return S_BAD;
     if (!variant_ok(q, rq, v) || q.rq_off[rq] + v >= r.stride) return S_BAD;
     int fresh = 0;
     const uint32_t b = ht_claim(t, id, &fresh);
@@ -117,11 +100,47 @@ __device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Ro
         for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) free_remove(&r.free_[(size_t)row * r.R + q.ent_res[e]], q.ent_kind[e], q.ent_amount[e]);
     return fresh ? S_FRESH : S_MOVED;
 }
-__global__ void k_insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr) {
-    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
-    const int st = i < it.n ? insert_one(t, q, r, it, upsert, apply_free, i) : S_SKIP;
+// index of `id` in the ascending ready-set id column, ~0 if absent (a consumed task keeps its id and priority)
+__device__ __forceinline__ uint64_t col_find(const uint64_t *col_id, uint64_t col_n, uint64_t id) {
+    uint64_t lo = 0, hi = col_n;
+    while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (col_id[mid] < id) lo = mid + 1; else hi = mid; }
+    return (lo < col_n && col_id[lo] == id) ? lo : ~0ull;
+}
+__device__ __forceinline__ void count_status(uint32_t *ctr, int st) {
     wave_add(&ctr[C_DONE], st == S_FRESH || st == S_MOVED); wave_add(&ctr[C_OUT], st == S_FRESH);
     wave_add(&ctr[C_DUP], st == S_DUP); wave_add(&ctr[C_BAD], st == S_BAD); wave_add(&ctr[C_FULL], st == S_FULL);
+}
+__device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Rows &r, const Items &it, int upsert, int apply_free, uint32_t i) {
+    const uint64_t id = it.id[i]; uint64_t prio = it.prio ? it.prio[i] : 0;
+    const uint32_t wid = it.wid[i], v = it.variant[i]; uint32_t rq = it.rq ? it.rq[i] : RQ_LOOKUP;
+    const uint32_t row = row_of(r, wid);
+    if (row == NONE || id >= HT_TOMB) return S_BAD;
+    if (rq == RQ_LOOKUP) {  // rq and priority of a task of the ready set
+        const uint64_t j = col_find(it.col_id, it.col_n, id);
+        if (j == ~0ull) return S_BAD;
+        rq = it.col_rq[j]; prio = it.col_prio[j];
+    }
+    return enter(t, q, r, id, row, wid, rq, v, prio, upsert, apply_free);
+}
+__global__ void k_insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    count_status(ctr, i < it.n ? insert_one(t, q, r, it, upsert, apply_free, i) : S_SKIP);
+}
+// the staged placement of a tick (K5b's extra output): every array is read once, coalesced; no search in the ready-set columns on the dense path
+__global__ void k_insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    int status = S_SKIP;
+    if (i < st.n) {
+        const uint32_t meta = st.meta[i];
+        if ((meta >> 8) == HQ_REC_ASSIGN) {  // prefills do not enter the ledger
+            const uint64_t id = st.task[i]; const uint32_t row = st.row[i], lvl = st.level[i], rq = st.rq[i];
+            uint64_t prio = 0; bool ok = row < r.W;
+            if (st.levels) { ok = ok && lvl < st.n_levels; if (ok) prio = st.levels[lvl]; }
+            else { const uint64_t j = col_find(st.col_id, st.col_n, id); ok = ok && j != ~0ull; if (ok) prio = st.col_prio[j]; }
+            status = ok ? enter(t, q, r, id, row, r.wid[row], rq, meta & 0xFFu, prio, 1, 0) : S_BAD;
+        }
+    }
+    count_status(ctr, status);
 }
 
 // release, pass 1: the bucket of every id; the first position of an id in the batch claims it (later ones are duplicates)
@@ -230,6 +249,11 @@ hipError_t clear(Table t, hipStream_t s) {
 hipError_t insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr, hipStream_t s) {
     if (!it.n) return hipSuccess;
     hipLaunchKernelGGL(k_insert, dim3(nblk(it.n)), dim3(TPB), 0, s, t, q, r, it, upsert, apply_free, ctr);
+    return hipGetLastError();
+}
+hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipStream_t s) {
+    if (!st.n) return hipSuccess;
+    hipLaunchKernelGGL(k_insert_staged, dim3(nblk(st.n)), dim3(TPB), 0, s, t, q, r, st, ctr);
     return hipGetLastError();
 }
 hipError_t release(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {

@@ -76,6 +76,9 @@ struct Ledger {
     DevBuf key2, wid2, rq2, var2, prio2, claim2;                                                  // ... the target of a rebuild
     DevBuf counts, counts2; uint32_t stride = 0;                                                  // [W x stride] per (worker row, variant slot)
     DevBuf req, wids, scratch, saved_rq, batch;                                                   // request tables, worker ids in row order, kernel scratch
+    // the placement staging K5b writes beside a tick's records (kernels.h: hqk::Stage): [task u64 | rq u32 | row u32 | level u32 | meta u16] x stage_n, in HBM
+    DevBuf stage; uint32_t stage_n = 0; bool stage_ordered = false; uint32_t stage_L = 0;
+    uint64_t last_host_bytes = 0;  // hqtick_assigned_last_host_bytes
     DevBuf ctr; PinBuf h_ctr, h_in;   // (counters of one operation: in HBM, copied back behind the kernels)
     // the request tables of the last snapshot (ResourceRqMap only grows: a slot keeps its number)
     std::vector<uint32_t> rq_off{0}, vent_off{0}, ent_res; std::vector<uint8_t> ent_kind; std::vector<uint64_t> ent_amt; bool req_dirty = true;
@@ -83,14 +86,14 @@ struct Ledger {
     uint64_t last_unknown = 0;
     // a tick's placement waiting for hqtick_ready_consume_last (two-call form)
     bool pending = false; bool pend_saved = false;
-    const uint64_t *pend_task = nullptr; const uint8_t *pend_var = nullptr, *pend_kind = nullptr; std::vector<uint32_t> pend_off; std::vector<uint64_t> pend_free;
+    uint32_t pend_W = 0; std::vector<uint64_t> pend_free;
     std::vector<uint64_t> red_id, red_prio; std::vector<uint32_t> red_wid, red_rq; std::vector<uint8_t> red_var;
     // hqtick_cluster_last_requeued
     std::vector<uint64_t> rq_task, rq_prio; std::vector<uint32_t> rq_rq;
     // what a ledger tick hands the host stages: per worker its distinct (rq, variant) pairs with counts (rebuilt from the count table when it changed)
     std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_var; bool agg_dirty = true;
     void release_all() {
-        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &req, &wids, &scratch, &saved_rq, &batch, &ctr};
+        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &req, &wids, &scratch, &saved_rq, &batch, &stage, &ctr};
         for (DevBuf *x : b) x->release();
         h_ctr.release(); h_in.release();
     }
@@ -1279,7 +1282,7 @@ struct TickRun {
             flags[0] = 0;  // K5b reports a capacity overflow straight into this pinned word
             ctx->last_n_sel = n_sel; ctx->last_consumed = false;
             const bool consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;  // K4 writes the tombstones of what it selects
-            if (consume_in_tick && ctx->asg.on) {  // the ledger reads the request ids of what K4 takes after K4 has tombstoned them (4 B per slot, device to device)
+            if (consume_in_tick && ctx->asg.on && s->n_retracting) {  // only the redirects of Retracting tasks still look their request id up after K4 has tombstoned it (4 B per slot, device to device)
                 if (!ctx->asg.saved_rq.ensure(N * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids");
                 HQ_HIP(hipMemcpyAsync(ctx->asg.saved_rq.p, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
             }
@@ -1326,11 +1329,20 @@ struct TickRun {
             hqk::CompactOut co{};
             if (compact) co = hqk::CompactOut{reinterpret_cast<uint32_t *>(drec), reinterpret_cast<uint2 *>(drec + o_rs), reinterpret_cast<uint32_t *>(drec + o_rf),
                                               delta16 ? reinterpret_cast<uint16_t *>(drec) : nullptr};
+            hqk::Stage stg{};
+            if (ctx->asg.on && n_rec) {  // the ledger's copy of the placement stays in HBM, whatever form the records leave in
+                Ledger &a = ctx->asg;
+                if (!a.stage.ensure((size_t)n_rec * 22 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger staging");
+                unsigned char *sp = a.stage.as<unsigned char>();
+                stg = hqk::Stage{reinterpret_cast<uint64_t *>(sp), reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 8), reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 12),
+                                 reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 16), reinterpret_cast<uint16_t *>(sp + (size_t)n_rec * 20)};
+                a.stage_n = n_rec; a.stage_ordered = sc.ordered; a.stage_L = sc.L;
+            }
             bool expand_is_last = false;
             if (sc.ordered) HQ_HIP_LAST(hqk::expand_mapping_wide(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint32_t>(), max_items, k_task, k_var, k_kind,
-                                                           reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream), expand_is_last);
+                                                           reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream, stg), expand_is_last);
             else HQ_HIP_LAST(hqk::expand_mapping(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), Q, max_items, k_task, k_var, k_kind,
-                                reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream), expand_is_last);
+                                reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream, stg), expand_is_last);
             if (!cnt.mn_rq.empty()) expand_is_last = false;  // copies of the multi-node task ids follow
             if (sc.ordered) {  // the selection's guard word follows (order.hip: a position outside its request's segment)
                 HQ_HIP(hipMemcpyAsync(ctx->h_ordh.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2, ctx->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1481,7 +1493,7 @@ struct TickRun {
 
 
 // ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12; csrc/assigned.hip)
-bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm || ctx->sink; }
+bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm; }  // (a record sink alone is one scheduler's output path, not a replica)
 
 // the request tables of a snapshot, kept when they differ from the ones the ledger has (a few hundred bytes compared)
 void ledger_take_requests(hqtick_ctx *ctx, const hqtick_snapshot *s) {
@@ -1609,26 +1621,23 @@ int ledger_insert_host(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const ui
 int ledger_apply_tick(hqtick_ctx *ctx) {
     Ledger &a = ctx->asg;
     a.pending = false;
-    const uint32_t W = ctx->cl_W, n_rec = a.pend_off.empty() ? 0u : a.pend_off.back();
+    const uint32_t W = ctx->cl_W, n_rec = a.stage_n;
     const uint32_t *col_rq = a.pend_saved ? a.saved_rq.as<uint32_t>() : ctx->d_trq.as<uint32_t>();
-    if (a.pend_off.size() != (size_t)W + 1 || a.pend_free.size() != (size_t)W * ctx->cl_R) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the worker set changed under a pending tick");
+    a.stage_n = 0; a.last_host_bytes = 0;  // (no record data crosses from the host: the entries are where K5b staged them)
+    if (a.pend_W != W || a.pend_free.size() != (size_t)W * ctx->cl_R) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the worker set changed under a pending tick");
     if (n_rec) {
         if (int rc = ledger_reserve(ctx, n_rec)) return rc;
         if (int rc = ledger_sync_req(ctx)) return rc;
-        // the records cross once by DMA into HBM: [off W + 1][task n][variant n][kind n]
-        const size_t o_t = (((size_t)W + 1) * 4 + 7) & ~(size_t)7, o_v = o_t + (size_t)n_rec * 8, o_k = o_v + n_rec, bytes = o_k + n_rec + 16;
-        if (!a.batch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger batch");
-        unsigned char *d = a.batch.as<unsigned char>();
-        HQ_HIP(hipMemcpyAsync(d, a.pend_off.data(), ((size_t)W + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        HQ_HIP(hipMemcpyAsync(d + o_t, a.pend_task, (size_t)n_rec * 8, hipMemcpyHostToDevice, ctx->stream));
-        HQ_HIP(hipMemcpyAsync(d + o_v, a.pend_var, n_rec, hipMemcpyHostToDevice, ctx->stream));
-        HQ_HIP(hipMemcpyAsync(d + o_k, a.pend_kind, n_rec, hipMemcpyHostToDevice, ctx->stream));
         uint32_t *c = ledger_ctr(ctx);
         if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-        hqasg::Items it{};
-        it.n = n_rec; it.rec_off = reinterpret_cast<const uint32_t *>(d); it.rec_task = reinterpret_cast<const uint64_t *>(d + o_t); it.rec_variant = d + o_v; it.rec_kind = d + o_k;
-        it.col_id = ctx->d_tid.as<uint64_t>(); it.col_prio = ctx->d_tprio.as<uint64_t>(); it.col_rq = col_rq; it.col_n = ctx->n_ready;
-        HQ_HIP(hqasg::insert(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), it, 1, 0, a.ctr.as<uint32_t>(), ctx->stream));
+        const unsigned char *sp = a.stage.as<unsigned char>();
+        hqasg::Staged st{};
+        st.n = n_rec; st.task = reinterpret_cast<const uint64_t *>(sp); st.rq = reinterpret_cast<const uint32_t *>(sp + (size_t)n_rec * 8);
+        st.row = reinterpret_cast<const uint32_t *>(sp + (size_t)n_rec * 12); st.level = reinterpret_cast<const uint32_t *>(sp + (size_t)n_rec * 16);
+        st.meta = reinterpret_cast<const uint16_t *>(sp + (size_t)n_rec * 20);
+        if (a.stage_ordered) { st.col_id = ctx->d_tid.as<uint64_t>(); st.col_prio = ctx->d_tprio.as<uint64_t>(); st.col_n = ctx->n_ready; }  // the view's run table is in host memory
+        else { st.levels = ctx->d_levels.as<uint64_t>(); st.n_levels = a.stage_L; }
+        HQ_HIP(hqasg::insert_staged(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), st, a.ctr.as<uint32_t>(), ctx->stream));
         HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
         HQ_HIP(hipStreamSynchronize(ctx->stream));
         if (c[hqasg::C_FULL] || c[hqasg::C_BAD]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a record of the tick could not be entered");
@@ -1742,7 +1751,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         if (s->worker_id || !(ctx->cluster_valid && ctx->mirror.valid)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
         if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
         HQ_HIP(hipSetDevice(ctx->device));
-        ctx->asg.pending = false;  // (a tick that was never consumed is abandoned, as its selection is)
+        ctx->asg.pending = false; ctx->asg.stage_n = 0;  // (a tick that was never consumed is abandoned, as its selection is; its staging is never read)
         ledger_take_requests(ctx, s);
         if (int rc = ledger_sync_mirror(ctx)) return rc;
     }
@@ -1833,7 +1842,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
     if (rc >= 0 && ctx->asg.on) {  // the placement enters the ledger when it becomes state: now, or at hqtick_ready_consume_last in the two-call form
         Ledger &a = ctx->asg;
         const uint32_t W = s->n_workers;
-        a.pend_off.assign(ctx->rec_off.begin(), ctx->rec_off.end()); a.pend_task = out->rec_task; a.pend_var = out->rec_variant; a.pend_kind = out->rec_kind;
+        a.pend_W = W;
         a.pend_free = ctx->new_free;
         a.red_id.clear(); a.red_wid.clear(); a.red_rq.clear(); a.red_var.clear(); a.red_prio.clear();
         for (uint32_t i = 0; i < out->n_redirects; i++) {
@@ -1845,7 +1854,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             a.red_rq.push_back(rq); a.red_var.push_back(out->redirect_variant[i]); a.red_prio.push_back(pr);
         }
         const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
-        a.pend_saved = in_tick; a.pending = true;
+        a.pend_saved = in_tick && s->n_retracting != 0; a.pending = true;  // (the column copy is taken only for the redirects of Retracting tasks)
         if (!use_resident || in_tick) {
             if (int r2 = ledger_apply_tick(ctx)) {  // (the tick's tasks have left the ready set: without the placement the ledger is no longer the truth)
                 a.on = false; a.pending = false;
@@ -2551,12 +2560,11 @@ uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? (uint32_t
 int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
     if (!ctx) return HQTICK_E_INVALID;
     if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
-    if (ctx->cfg.flags & (HQTICK_FLAG_COMPACT_RECORDS | HQTICK_FLAG_COMPACT_DELTA16)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not with compact records");
     if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
     if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: null array");
     HQ_HIP(hipSetDevice(ctx->device));
     Ledger &a = ctx->asg;
-    a.on = false; a.pending = false; a.cap = 0; a.n_live = 0; a.n_tomb = 0; a.last_unknown = 0; a.stride = 0;
+    a.on = false; a.pending = false; a.cap = 0; a.n_live = 0; a.n_tomb = 0; a.last_unknown = 0; a.stride = 0; a.stage_n = 0; a.last_host_bytes = 0;
     a.rq_task.clear(); a.rq_rq.clear(); a.rq_prio.clear();
     if (int rc = ledger_reserve(ctx, n)) return rc;
     HQ_HIP(hqasg::clear(ledger_table(a), ctx->stream));
@@ -2629,6 +2637,7 @@ int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id
 }
 
 uint64_t hqtick_assigned_last_unknown(const hqtick_ctx *ctx) { return ctx ? ctx->asg.last_unknown : 0; }
+uint64_t hqtick_assigned_last_host_bytes(const hqtick_ctx *ctx) { return ctx ? ctx->asg.last_host_bytes : 0; }
 uint64_t hqtick_assigned_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on ? ctx->asg.n_live : 0; }
 
 int hqtick_assigned_lookup(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint32_t *worker_id, uint8_t *variant) {

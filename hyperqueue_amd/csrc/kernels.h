@@ -130,15 +130,24 @@ struct CompactOut {
     uint16_t *units;        // HQTICK_FLAG_COMPACT_DELTA16 (else nullptr): [n_rec * 4] 16-bit unit streams, worker w's at unit 4 * rec_off[w]; rec_lo is unused and
                             // the runs are 4 words (+ the low id of the run's first record) = hqtick_rec_run16
 };
+// Placement staging for the assignment ledger (assigned.h): with task != nullptr K5b also writes, for record out_off[w] + i, what the
+// ledger stores — in HBM, one array per field.  PREFILL records get meta = 0 (kind HQ_REC_PREFILL: skipped).  task == nullptr: nothing is written or read.
+struct Stage {
+    uint64_t *task;   // [n_rec] task id
+    uint32_t *rq;     // [n_rec] request id of the record's key
+    uint32_t *row;    // [n_rec] worker row
+    uint32_t *level;  // [n_rec] the item's priority level: index into the dense level table, or the global level rank of the ordered view
+    uint16_t *meta;   // [n_rec] variant | kind << 8
+};
 hipError_t expand_mapping(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint16_t *sel_key, uint32_t Q, uint32_t max_items,
-                    uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s);
+                    uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s, Stage st = Stage{});
 // may_reorder: the tick has more than one priority level, Retracting holes or prefilled tasks in the queues — a worker's records then need the stable
 // sort of mapping.rs:128-131 (an LDS key array of the next power of two above max_items); without it the items are emitted in gather order
 size_t expand_mapping_lds(uint32_t max_items, uint32_t n_keys, uint32_t max_out, bool may_reorder, bool wide_levels = false);
 // The same for a selection of the ordered view (order.hip): sel_rank[i] = the global level rank of selected task i (32 bits; the stable sort then runs on
 // 64-bit keys).  The LDS need is expand_mapping_lds(..., wide_levels = true).
 hipError_t expand_mapping_wide(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint32_t *sel_rank, uint32_t max_items,
-                               uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s);
+                               uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s, Stage st = Stage{});
 
 // Resident cluster tables (f1): rows of the worker table that changed, scattered into the HBM copy (inputs may sit in pinned host memory)
 hipError_t scatter_worker_rows(uint64_t *free_, int64_t *rem, uint32_t R, uint32_t n, const uint32_t *idx, const uint64_t *rows, const int64_t *new_rem, hipStream_t s);

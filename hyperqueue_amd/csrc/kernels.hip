@@ -557,6 +557,9 @@ static const uint32_t RUN_STAGE = 512;  // runs of one worker staged in LDS befo
 // Compact emission (HQTICK_FLAG_COMPACT_RECORDS): the records cross PCIe as 4 bytes each — the low half of the task id — plus one 10-byte RUN per
 // maximal stretch of a worker's records that share (job id, variant, kind).  LDS then also holds the worker's final sequence:
 // f_task u64[max_out] | f_meta u16[max_out] (variant | kind << 8) behind the tables above.
+// Placement staging (st.task != nullptr: the assignment ledger is on): beside every record, in whatever form it leaves, the kernel stores the
+// ledger's entry into HBM at the record's index out_off[w] + i, one array per field (consecutive lanes store consecutive elements): task id, the key's
+// request id, this worker's row, the item's level and variant | kind << 8; PREFILL records get meta 0.  With st.task == nullptr nothing else changes.
 // LV: the per-item level type.  uint16_t: sel_key is K4's group key, level = key / Q, sort keys (level << 16 | item) in 32 bits.  uint32_t (the ordered view,
 // order.hip): sel_key is the run's global level rank (the launch passes Q = 1), sort keys (level << 32 | item) in 64 bits.
 template <typename LV>
@@ -564,7 +567,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
                                                         const LV *__restrict__ sel_key, uint32_t Q, uint32_t max_items,
                                                         uint64_t *__restrict__ rec_task, uint8_t *__restrict__ rec_variant,
                                                         uint8_t *__restrict__ rec_kind, uint32_t *__restrict__ err_flag, CompactOut co, uint32_t max_out,
-                                                        uint32_t sort_cap) {
+                                                        uint32_t sort_cap, Stage st) {
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t nkeys = mk.n_keys;
     uint64_t *e_task = reinterpret_cast<uint64_t *>(smem);
@@ -583,6 +586,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
                                                                                                                                  // stable sort; sort_cap = 0 on ticks that cannot reorder
     uint8_t *k_var = reinterpret_cast<uint8_t *>(s_key + sort_cap);
     const uint32_t w = blockIdx.x, lane = lane_id();
+    const bool ledger = st.task != nullptr;  // (a kernel argument: uniform over the launch)
     // Three rounds of global loads, each issued as one batch: (1) the worker's output range, its row of every per-key table and its prefill chunks;
     // (2) the round-robin cells of its items + the ids of its prefill records; (3) the ids and group keys of its items.  (Five dependent rounds —
     // range, tables, chunk index, chunk ids, cells, ids — cost the launch ~4 us more.)
@@ -635,6 +639,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
         if (j == 0xFFFFFFFFu) continue;
         const uint32_t cnt = mk.pfq_size[pi], src = mk.pfq_src[pi] + j * cnt;
         for (uint32_t t = threadIdx.x; t < cnt; t += blockDim.x) {
+            if (ledger && out0 + npf + t < out1) st.meta[out0 + npf + t] = 0;  // HQ_REC_PREFILL: the ledger skips it
             if (compact) { if (npf + t < max_out) { f_task[npf + t] = sel_task[src + t]; f_meta[npf + t] = 0x00FFu; } continue; }
             rec_task[out0 + npf + t] = sel_task[src + t];
             rec_variant[out0 + npf + t] = 0xFF;
@@ -660,12 +665,13 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
             const uint32_t k = lo, s = e - k_start[k], pos = k_pos[k];
             if (k_trc[k]) {  // worker-major key: this worker's tasks are the k_trc[k] ids from its own offset on (no cell, no hole: the host transposes only plain queues)
                 const uint32_t src = mk.rq_sel_base[k_rq[k]] + pos * k_trc[k] + s;
-                const LV lv = sort_cap ? (LV)(sel_key[src] / Q) : (LV)0;
+                const LV lv = (sort_cap || ledger) ? (LV)(sel_key[src] / Q) : (LV)0;
                 e_task[e] = sel_task[src];
                 e_lvl[e] = lv;
                 e_meta[e] = (uint16_t)(k_var[k] | 0x100u);
                 if (sort_cap) { atomicMin(&misc[0], (uint32_t)lv); atomicMax(&misc[1], (uint32_t)lv); }
                 if (do_pf) {
+                    if (ledger && out0 + u < out1) st.meta[out0 + u] = 0;
                     if (compact) { if (u < max_out) { f_task[u] = pf_id; f_meta[u] = 0x00FFu; } }
                     else { rec_task[out0 + u] = pf_id; rec_variant[out0 + u] = 0xFF; rec_kind[out0 + u] = 0; }
                 }
@@ -692,7 +698,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
                 const uint32_t src = sbase + (p >= pfs + pfn ? p - pfn : p);
                 // priority level of the task's group — only a tick that can reorder needs it (sort_cap != 0: several levels, holes or prefilled tasks): the cold
                 // tick skips one strided 2-byte gather per record (a 64-byte line each)
-                const LV lv = sort_cap ? (LV)(sel_key[src] / Q) : (LV)0;
+                const LV lv = (sort_cap || ledger) ? (LV)(sel_key[src] / Q) : (LV)0;
                 e_task[e] = sel_task[src];
                 e_lvl[e] = lv;
                 e_meta[e] = (uint16_t)(k_var[k] | 0x100u);
@@ -700,6 +706,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
             }
         }
         if (do_pf) {
+            if (ledger && out0 + u < out1) st.meta[out0 + u] = 0;
             if (compact) { if (u < max_out) { f_task[u] = pf_id; f_meta[u] = 0x00FFu; } }
             else { rec_task[out0 + u] = pf_id; rec_variant[out0 + u] = 0xFF; rec_kind[out0 + u] = 0; }  // HQ_REC_PREFILL
         }
@@ -748,8 +755,13 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
                 pos += (lo_ < lv || (lo_ == lv && o < e)) ? 1u : 0u;
             }
         }
-        if (compact) { if (npf + pos < max_out) { f_task[npf + pos] = e_task[e]; f_meta[npf + pos] = (uint16_t)((meta & 0xFFu) | 0x100u); } continue; }
         const uint32_t dst = out0 + npf + pos;
+        if (ledger && dst < out1) {  // the ledger's entry, beside the record in whatever form that leaves the device: full-lane contiguous stores per array
+            uint32_t lo = 0, hi = nkeys;  // the item's key (e is in key order): its request id
+            while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (k_start[mid] <= e) lo = mid; else hi = mid; }
+            st.task[dst] = e_task[e]; st.rq[dst] = k_rq[lo]; st.row[dst] = w; st.level[dst] = (uint32_t)e_lvl[e]; st.meta[dst] = (uint16_t)((meta & 0xFFu) | 0x100u);
+        }
+        if (compact) { if (npf + pos < max_out) { f_task[npf + pos] = e_task[e]; f_meta[npf + pos] = (uint16_t)((meta & 0xFFu) | 0x100u); } continue; }
         rec_task[dst] = e_task[e];
         rec_variant[dst] = (uint8_t)(meta & 0xFFu);
         rec_kind[dst] = 1;  // HQ_REC_ASSIGN
@@ -1296,7 +1308,7 @@ size_t expand_mapping_lds(uint32_t max_items, uint32_t n_keys, uint32_t max_out,
 
 template <typename LV>
 static hipError_t expand_mapping_t(MapKeys mk, uint32_t W, const uint64_t *sel_task, const LV *sel_key, uint32_t Q, uint32_t max_items,
-                                   uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s) {
+                                   uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s, Stage st) {
     if (W == 0) return hipSuccess;
     if (!co.rec_lo) max_out = 0;
     size_t lds = expand_mapping_lds(max_items, mk.n_keys, max_out, may_reorder, sizeof(LV) == 4);
@@ -1304,18 +1316,18 @@ static hipError_t expand_mapping_t(MapKeys mk, uint32_t W, const uint64_t *sel_t
     hipError_t e;
     auto kern = k_expand_mapping<LV>;
     if (lds > 48 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-    HQK_TIMED_LAUNCH(kern, dim3(W), dim3(256), lds, s, mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, sort_cap);
+    HQK_TIMED_LAUNCH(kern, dim3(W), dim3(256), lds, s, mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, sort_cap, st);
     return hipGetLastError();
 }
 
 hipError_t expand_mapping(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint16_t *sel_key, uint32_t Q, uint32_t max_items,
-                    uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s) {
-    return expand_mapping_t<uint16_t>(mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, may_reorder, s);
+                    uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s, Stage st) {
+    return expand_mapping_t<uint16_t>(mk, W, sel_task, sel_key, Q, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, may_reorder, s, st);
 }
 
 hipError_t expand_mapping_wide(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint32_t *sel_rank, uint32_t max_items,
-                               uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s) {
-    return expand_mapping_t<uint32_t>(mk, W, sel_task, sel_rank, 1u, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, may_reorder, s);
+                               uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s, Stage st) {
+    return expand_mapping_t<uint32_t>(mk, W, sel_task, sel_rank, 1u, max_items, rec_task, rec_variant, rec_kind, err_flag, co, max_out, may_reorder, s, st);
 }
 
 hipError_t scatter_worker_rows(uint64_t *free_, int64_t *rem, uint32_t R, uint32_t n, const uint32_t *idx, const uint64_t *rows, const int64_t *new_rem, hipStream_t s) {

@@ -294,6 +294,30 @@ class Tick:
         f.argtypes = [C.c_void_p]; f.restype = C.c_uint64
         return int(f(self._ctx))
 
+    def assigned_last_host_bytes(self) -> int:
+        """bytes of record data the last placement's entry into the ledger copied from host memory to the device (0: the records stayed in HBM)"""
+        f = self._lib.hqtick_assigned_last_host_bytes
+        f.argtypes = [C.c_void_p]; f.restype = C.c_uint64
+        return int(f(self._ctx))
+
+    def set_record_sink(self, sink, n_workers: Optional[int] = None):
+        """the tick's records go into `sink` (a contiguous device tensor of at least hqtick_sink_bytes(W, capacity) bytes, 16-byte aligned) instead of pinned
+        host memory; None removes the sink.  n_workers given: returns how many records the tensor holds for that many workers.  The caller keeps the tensor alive."""
+        f = self._lib.hqtick_set_record_sink
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        if sink is None:
+            self._chk(f(self._ctx, None, 0))
+            self._sink = None
+            return 0
+        nbytes = int(sink.numel() * sink.element_size())
+        self._chk(f(self._ctx, C.c_void_p(sink.data_ptr()), C.c_size_t(nbytes)))
+        self._sink = sink
+        if n_workers is None:
+            return 0
+        g = self._lib.hqtick_sink_capacity_records
+        g.argtypes = [C.c_uint32, C.c_size_t]; g.restype = C.c_uint32
+        return int(g(int(n_workers), nbytes))
+
     def assigned_lookup(self, task_id):
         """-> (worker ids (HQ_NO_WORKER: not in the ledger), variants)"""
         t = np.ascontiguousarray(task_id, np.uint64)

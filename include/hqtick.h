@@ -491,8 +491,15 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  * its selection and never enters.  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
  * tasks have left the ready set, so the host uploads the worker set and enables the ledger again from its own view.
  * PREFILL records, prefill sets and multi-node tasks stay the host's.  hqtick_cluster_update_workers still works (remaining lifetime, corrections).
- * HQTICK_E_UNSUPPORTED on a sharded or replica context (hqtick_set_shard with more than one shard, an exchange, a communicator or a record sink) and with
- * HQTICK_FLAG_COMPACT_RECORDS / _DELTA16.
+ * The ledger does not depend on the form in which the records leave the device: the mapping kernel stages, beside every record it emits, the entry the
+ * ledger stores (task, request, variant, worker row, priority level) in HBM, and the placement enters from there.  So the ledger works with plain records,
+ * with HQTICK_FLAG_COMPACT_RECORDS / _DELTA16, and with a record sink (hqtick_set_record_sink, set before or after hqtick_assigned_enable, removed again
+ * between ticks) on a context that is not sharded: with a sink the tick's records stay in HBM, hqwire_encode_device turns them into message bytes, and no
+ * task record crosses PCIe in either direction.  A sink too small for a tick is HQTICK_E_CAPACITY as without the ledger; ledger, counts and free rows stay
+ * as they were.
+ *   hqtick_assigned_last_host_bytes  bytes of record data (offsets, task ids, variants, kinds, in any form) that the last placement's entry into the ledger
+ *                              copied from host memory to the device: 0 in every form (redirects and the new_free rows are not counted).
+ * HQTICK_E_UNSUPPORTED on a sharded or replica context (hqtick_set_shard with more than one shard, an exchange or a communicator).
  */
 int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority);
 int hqtick_assigned_disable(hqtick_ctx *ctx);
@@ -500,6 +507,7 @@ int hqtick_assigned_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, co
 int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id);
 uint64_t hqtick_assigned_last_unknown(const hqtick_ctx *ctx);
 uint64_t hqtick_assigned_count(const hqtick_ctx *ctx);
+uint64_t hqtick_assigned_last_host_bytes(const hqtick_ctx *ctx);
 int hqtick_assigned_lookup(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint32_t *worker_id, uint8_t *variant);
 int hqtick_assigned_free_rows(hqtick_ctx *ctx, uint32_t *n_workers, const uint64_t **free_rows);
 int hqtick_cluster_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority);

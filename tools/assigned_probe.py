@@ -2,7 +2,10 @@
 protocol (context B: the host keeps the free rows, sends the rows every start / finish touched, flattens the assigned CSR per tick).  Prints one JSON line:
 per-step wall clock of both loops (B's host bookkeeping included), the release call for the previous step's tasks, and the ledger's tick-side apply.
 
-    python tools/assigned_probe.py [--steps 20] [--tasks 1000000] [--workers 1024]
+    python tools/assigned_probe.py [--steps 20] [--tasks 1000000] [--workers 1024] [--records plain|compact|delta16|sink]
+
+--records: the form in which context A's records leave the device (the ledger is fed from the mapping kernel's staging in HBM in every one of them; `sink`:
+a device record sink, read back outside the timed part only to compare).  `ledger_host_bytes` is hqtick_assigned_last_host_bytes after the last tick.
 """
 import argparse
 import dataclasses
@@ -12,6 +15,11 @@ import sys
 import time
 
 import numpy as np
+
+try:  # torch bundles its own HIP runtime: imported BEFORE libhqtick.so pulls in the system's, so that the process has one (--records sink hands it a tensor)
+    import torch
+except Exception:  # the other forms do not need it
+    torch = None
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hyperqueue_amd import abi, workloads  # noqa: E402
@@ -31,16 +39,24 @@ def main():
     ap.add_argument("--tasks", type=int, default=1_000_000)
     ap.add_argument("--workers", type=int, default=1024)
     ap.add_argument("--add", type=int, default=188_000)
+    ap.add_argument("--records", choices=["plain", "compact", "delta16", "sink"], default="plain")
     args = ap.parse_args()
     snap = workloads.make_steady("c3p", seed=3, n_tasks=args.tasks, n_workers=args.workers)
     W, R = len(snap.worker_id), snap.n_resources
     snap = dataclasses.replace(snap, assigned=[[] for _ in range(W)], worker_free=np.array(snap.worker_total, np.uint64), _keep=[])
     ent = [[[(int(r), int(k), int(a)) for (r, k, a) in v["entries"]] for v in rq] for rq in snap.requests]
     cfg = abi.make_config(time_limit_s=20.0, flags=abi.HQTICK_FLAG_CONSUME_IN_TICK | abi.HQTICK_FLAG_NO_KERNEL_TIMING)
-    a, b = Tick(cfg), Tick(cfg)
+    form = {"plain": 0, "compact": abi.HQTICK_FLAG_COMPACT_RECORDS, "delta16": abi.HQTICK_FLAG_COMPACT_RECORDS | abi.HQTICK_FLAG_COMPACT_DELTA16, "sink": 0}[args.records]
+    a, b = Tick(abi.make_config(time_limit_s=20.0, flags=cfg.flags | form)), Tick(cfg)
     for t in (a, b):
         t.cluster_upload(snap); t.upload_ready(snap.task_id, snap.task_priority, snap.task_rq)
     a.assigned_enable([])
+    sink = None
+    if args.records == "sink":
+        from hyperqueue_amd.sharded import sink_layout
+
+        sink = torch.zeros(sink_layout(W, 1 << 18)[4], dtype=torch.uint8, device="cuda:0")
+        sink_cap = a.set_record_sink(sink, W)
     total = np.asarray(snap.worker_total, np.uint64).reshape(W, R)
     free = total.copy(); running = {}; rq_of = dict(zip(snap.task_id.tolist(), snap.task_rq.tolist()))
     next_id = int(snap.task_id.max()) + 1
@@ -57,8 +73,15 @@ def main():
         a.ready_add(add, prio, rqs)
         t2 = time.perf_counter(); ra = _resident(a, snap); ttick_a.append(time.perf_counter() - t2)
         ta.append(time.perf_counter() - t0)
-        pa = abi.parse_result(ra, W, R)
-        prev_a = [tid for recs in pa.records for (tid, v, k) in recs if k == abi.HQ_REC_ASSIGN]
+        if sink is None:
+            rec_a = abi.parse_result(ra, W, R).records
+        else:  # the records are in the device tensor (layout: include/hqtick.h)
+            h = sink.cpu().numpy()
+            o_off, o_task, o_var, o_kind, _ = sink_layout(W, sink_cap)
+            off = h[o_off:o_off + (W + 1) * 4].view(np.uint32).tolist(); n = off[W]
+            col = list(zip(h[o_task:o_task + n * 8].view(np.uint64).tolist(), h[o_var:o_var + n].tolist(), h[o_kind:o_kind + n].tolist()))
+            rec_a = [col[off[w]:off[w + 1]] for w in range(W)]
+        prev_a = [tid for recs in rec_a for (tid, v, k) in recs if k == abi.HQ_REC_ASSIGN]
         # B: the host's bookkeeping as today
         t0 = time.perf_counter()
         if prev_b:
@@ -85,11 +108,11 @@ def main():
                 if k == abi.HQ_REC_ASSIGN:
                     running[tid] = (w, rq_of[tid], v); prev_b.append(tid)
         tb.append(time.perf_counter() - t0)
-        assert pa.records == rb.records and a.assigned_count() == len(running)
+        assert rec_a == rb.records and a.assigned_count() == len(running)
     med = lambda x: round(float(np.median(x[2:] if len(x) > 4 else x)) * 1e6, 1)  # noqa: E731
     print(json.dumps({"steps": args.steps, "tasks": args.tasks, "workers": W, "added_per_step": args.add, "released_per_step": len(prev_a),
                       "step_us_ledger": med(ta), "step_us_row_deltas": med(tb), "release_call_us": med(trel), "tick_call_us_ledger": med(ttick_a),
-                      "running": a.assigned_count()}))
+                      "running": a.assigned_count(), "records": args.records, "ledger_host_bytes": a.assigned_last_host_bytes()}))
     a.close(); b.close()
 
 
