@@ -74,3 +74,15 @@ extern "C" int hqtick_debug_milp_solve_priced(int ncols, const double *obj, cons
     *is_optimal = r.optimal ? 1 : 0;
     return 1;
 }
+
+// Equal-block runs of the coupled model (csrc/milp.h: Model::block_runs).  The probe the builder and the flattener write into is installed on this thread by
+// hqtick_debug_set_block_runs(0 / 1) and taken away again by hqtick_debug_set_block_runs(-1).
+static thread_local hqmilp::Probe g_block_run_probe;
+extern "C" void hqtick_debug_set_block_runs(int on) {
+    hqmilp::g_probe = on < 0 ? nullptr : &g_block_run_probe; hqmilp::set_block_runs(on);
+    if (on >= 0) { g_block_run_probe.model = g_block_run_probe.tables = g_block_run_probe.runs = g_block_run_probe.covered = 0; }   // (a tick that builds no coupled model leaves zeros)
+}
+extern "C" void hqtick_debug_corrupt_block_runs(int on) { g_block_run_probe.corrupt_runs = on != 0; }
+extern "C" void hqtick_debug_last_coupled_digest(uint64_t out[4]) {
+    out[0] = g_block_run_probe.model; out[1] = g_block_run_probe.tables; out[2] = g_block_run_probe.runs; out[3] = g_block_run_probe.covered;
+}

@@ -923,7 +923,13 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
         std::vector<double> s, wq; std::vector<uint32_t> slot, rq, ub;          // per column: cost without the order factor, weight, variant slot, request, bound
         std::vector<double> rhs; std::vector<uint8_t> implied; std::vector<int> roff{0}, rcol; std::vector<double> rcoef;   // per row (all `<=`, all of this block)
         std::vector<std::vector<int> *> cc;   // per column: its request's list of count columns (a node of count_cols: stays where it is) — not a map walk per column
+        int col0 = 0, row0 = 0, term0 = 0; uint32_t worker = 0;   // where the template's own block lies in the model, and whose it is
     } tmpl;
+    // Equal-block runs (milp.h: Model::block_runs): the template's block and its stamps lie back to back and differ in `obj` only — said to the flattener, which then
+    // works on the first block and copies; and used below, where one worker's answer is the run's.  stamp_first[w]: the worker whose block w's block is a stamp of.
+    const bool runs_on = hqmilp::block_runs_on();
+    std::vector<uint32_t> stamp_first, run_members; std::vector<int> blk_base;
+    if (runs_on) { stamp_first.assign(ws.n, UINT32_MAX); blk_base.assign(ws.n, -1); }
     std::vector<double> rec_s, rec_wq; std::vector<uint32_t> rec_slot, rec_rq;   // what the loop below records per placement column while it builds a block
     for (size_t wi = 0; wi < nw; wi++) {  // :95
         uint32_t w = solver_workers[wi];
@@ -931,7 +937,50 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
         const uint64_t *tot = ws.total + (size_t)w * R, *fre = ws.free_ + (size_t)w * R;
         double order_factor = (double)(nw - wi);
         const uint32_t my_group = (ws.rows.valid && !pb.custom) ? ws.rows.of[w] : UINT32_MAX;
-        if (tmpl.ok && my_group != UINT32_MAX && my_group == tmpl.group) {   // the template's block, for this worker
+        if (runs_on && tmpl.ok && my_group != UINT32_MAX && my_group == tmpl.group) {   // the template's block for the whole run of workers that follow with its group, in one go
+            run_members.clear();
+            size_t wj = wi;
+            for (; wj < nw; wj++) {   // (a worker that emits nothing does not end the run)
+                const uint32_t w2 = solver_workers[wj];
+                if (!worker_off.empty() && worker_off[w2]) continue;
+                if (ws.rows.of[w2] != tmpl.group) break;
+                run_members.push_back((uint32_t)wj);
+            }
+            const size_t nm = run_members.size(), nc = tmpl.s.size(), nr = tmpl.roff.size() - 1, nt = tmpl.rcol.size();
+            const int base0 = m.ncols(), rbase0 = m.nrows(); const size_t tbase0 = m.rcol.size();
+            m.obj.resize((size_t)base0 + nm * nc); m.kind.resize((size_t)base0 + nm * nc, hqmilp::COL_NAT); m.col_group.resize((size_t)base0 + nm * nc);
+            col_ub.resize((size_t)base0, UINT32_MAX); col_ub.resize((size_t)base0 + nm * nc);
+            m.rtype.resize((size_t)rbase0 + nm * nr, hqmilp::ROW_MAX); m.rhs.resize((size_t)rbase0 + nm * nr); m.roff.resize((size_t)rbase0 + 1 + nm * nr);
+            m.rcol.resize(tbase0 + nm * nt); m.rcoef.resize(tbase0 + nm * nt);
+            m.row_block.resize((size_t)rbase0, -1); m.row_block.resize((size_t)rbase0 + nm * nr);
+            bool any_implied = false; for (uint8_t f : tmpl.implied) if (f) any_implied = true;
+            if (any_implied) m.row_implied.resize((size_t)rbase0 + nm * nr, 0);
+            for (std::vector<int> *cc : tmpl.cc) cc->reserve(cc->size() + nm);
+            const double *ts = tmpl.s.data(), *twq = tmpl.wq.data(); const uint32_t *tslot = tmpl.slot.data(), *tub = tmpl.ub.data();
+            const int *troff = tmpl.roff.data(), *trcol = tmpl.rcol.data();
+            for (size_t i = 0; i < nm; i++) {
+                const size_t wi2 = run_members[i]; const uint32_t w2 = solver_workers[wi2];
+                const double of2 = (double)(nw - wi2);
+                const int base = base0 + (int)(i * nc), rbase = rbase0 + (int)(i * nr); const int tbase = (int)(tbase0 + i * nt);
+                double *ob = m.obj.data() + base; int32_t *cg = m.col_group.data() + base; int *pc = place_col.data() + (size_t)w2 * NVS;
+                for (size_t k = 0; k < nc; k++) { ob[k] = ts[k] * of2 * twq[k] / (double)nw; cg[k] = (int32_t)wi2; pc[tslot[k]] = base + (int)k; tmpl.cc[k]->push_back(base + (int)k); }
+                memcpy(col_ub.data() + base, tub, nc * sizeof(uint32_t));
+                memcpy(m.rhs.data() + rbase, tmpl.rhs.data(), nr * sizeof(double));
+                int *ro = m.roff.data() + rbase + 1; int32_t *rb = m.row_block.data() + rbase;
+                for (size_t r = 0; r < nr; r++) { ro[r] = tbase + troff[r + 1]; rb[r] = (int32_t)wi2; }
+                if (any_implied) for (size_t r = 0; r < nr; r++) if (tmpl.implied[r]) m.row_implied[(size_t)rbase + r] = 1;
+                int *rc = m.rcol.data() + tbase;
+                for (size_t t = 0; t < nt; t++) rc[t] = base + trcol[t];
+                memcpy(m.rcoef.data() + tbase, tmpl.rcoef.data(), nt * sizeof(double));
+                stamp_first[w2] = tmpl.worker; blk_base[w2] = base;
+            }
+            blk_base[tmpl.worker] = tmpl.col0;
+            m.block_runs.push_back({tmpl.col0, tmpl.row0, tmpl.term0, (int32_t)(1 + nm), (int32_t)nc, (int32_t)nr, (int32_t)nt});
+            tmpl.ok = false;   // (the next worker is of another group, or there is none)
+            wi = wj - 1;
+            continue;
+        }
+        if (tmpl.ok && my_group != UINT32_MAX && my_group == tmpl.group) {   // (HQMILP_BLOCK_RUNS=0: one worker at a time)
             const int base = m.ncols();
             for (size_t k = 0; k < tmpl.s.size(); k++) {
                 const int col = addc(tmpl.s[k] * order_factor * tmpl.wq[k] / (double)nw, hqmilp::COL_NAT, (int32_t)wi);
@@ -1030,7 +1079,7 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
             for (int i = rec_row0; i < m.nrows() && plain; i++) if (m.rtype[i] != hqmilp::ROW_MAX) plain = false;
             for (int t = rec_term0; t < (int)m.rcol.size() && plain; t++) if (m.rcol[t] < rec_col0) plain = false;
             if (plain) {
-                tmpl.group = my_group; tmpl.ok = true;
+                tmpl.group = my_group; tmpl.ok = true; tmpl.col0 = rec_col0; tmpl.row0 = rec_row0; tmpl.term0 = rec_term0; tmpl.worker = w;
                 tmpl.s = rec_s; tmpl.wq = rec_wq; tmpl.slot = rec_slot; tmpl.rq = rec_rq;
                 tmpl.cc.resize(tmpl.rq.size()); for (size_t k = 0; k < tmpl.rq.size(); k++) tmpl.cc[k] = &count_cols[tmpl.rq[k]];
                 tmpl.ub.assign(col_ub.begin() + rec_col0, col_ub.begin() + m.ncols());
@@ -1044,6 +1093,9 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
                 }
             }
         }
+    }
+    if (hqmilp::g_probe && hqmilp::g_probe->corrupt_runs && m.block_runs.size() >= 2) {   // tests: two neighbouring runs merged into one false claim (the flattener must refuse it)
+        m.block_runs[0].n_blocks += m.block_runs[1].n_blocks; m.block_runs.erase(m.block_runs.begin() + 1);
     }
     // multi-node group sizes  :193-227
     std::map<std::pair<uint32_t, uint32_t>, int> group_cols;
@@ -1101,7 +1153,7 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
     // the gap depends on the worker's total resources and on what runs there: workers with the same signature share one computation per (blocker, batch)
     // (signatures: a flat table of hashes over (total row, running kinds) with the first worker of each as its representative — the rows are compared where they lie)
     std::vector<uint32_t> gap_sig, sig_rep, sig_table; std::vector<uint64_t> sig_hash;
-    const size_t n_sig_cap = (size_t)ws.n + 1;  // signatures are numbered below the worker count
+    size_t n_sig_cap = (size_t)ws.n + 1;  // signatures are numbered below the worker count (gap_of narrows this to their number: every worker has its signature by then)
     // per (blocker, signature) — blockers numbered as they turn up: 0 not computed, 1 leftover in left_of (the general rule), 2 gap is 0 by rule, 3 leftover in left_row
     std::vector<int32_t> blocker_ord; uint32_t n_blockers_seen = 0;
     std::vector<uint8_t> left_state; std::vector<Amounts> left_of; std::vector<uint64_t> left_row;
@@ -1152,9 +1204,10 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
             return gap_sig[w] = id;
         }
     };
+    bool sigs_done = false;   // every solver worker has its signature
     // what the blocker leaves of the workers with signature sg (w: one of them), once per (blocker, signature); then how many tasks of the batch fit into that
     auto gap_of = [&](uint32_t brq, uint32_t low_rq, uint32_t sg, uint32_t w) -> uint32_t {
-        if (blocker_ord.empty()) blocker_ord.assign(pb.rqs.size(), -1);
+        if (blocker_ord.empty()) { blocker_ord.assign(pb.rqs.size(), -1); if (sigs_done) n_sig_cap = sig_rep.size() + 1; }
         if (blocker_ord[brq] < 0) {
             blocker_ord[brq] = (int32_t)n_blockers_seen++;
             left_state.resize((size_t)n_blockers_seen * n_sig_cap, 0); left_row.resize((size_t)n_blockers_seen * n_sig_cap * R); left_of.resize(left_state.size());
@@ -1172,9 +1225,9 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
         }
         return left_state[li] == 3 ? gaps.fit_row(low_rq, &left_row[li * R], R) : (left_state[li] == 1 ? gaps.fit(low_rq, left_of[li]) : 0);
     };
-    std::vector<uint32_t> gap_of_sig; bool sigs_done = false; uint32_t batch_no = UINT32_MAX;
-    std::vector<std::vector<uint8_t>> cap_cache; size_t n_triples = 0;
-    std::vector<uint32_t> bcols_off, bcols_end((size_t)ws.n, 0); std::vector<int> bcols; std::vector<uint64_t> bcols_ub; uint32_t bcols_batch = UINT32_MAX;
+    std::vector<uint32_t> gap_of_sig; uint32_t batch_no = UINT32_MAX;
+    std::vector<std::vector<uint8_t>> cap_cache; std::vector<int8_t> all_cap_cache; size_t n_triples = 0, n_decided_once = 0;
+    std::vector<uint32_t> bcols_off, bcols_end((size_t)ws.n, 0); std::vector<int> bcols; std::vector<uint64_t> bcols_ub; uint64_t bcols_ub_max = 0; uint32_t bcols_batch = UINT32_MAX;
     for (const TaskBatch &batch : batches) {
         batch_no++;
         auto cc = count_cols.find(batch.rq);
@@ -1188,7 +1241,9 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
         // What a blocker leaves of every worker depends on (batch, blocker) alone — not on the cut: the workers' gaps, the columns of the workers without a gap
         // (zero_cond) and the workers with one are worked out ONCE per pair and every cut of the batch against that blocker reads them (c3p at BASELINE size:
         // 91 (cut, blocker) passes over 1024 workers -> 16).  The rows and the flag columns come out in the reference's order all the same.
-        struct PairMemo { bool done = false; int lhs_id = -1; std::vector<int> no_gap; std::vector<std::pair<uint32_t, uint32_t>> with_gap; };  // with_gap: (worker, gap), ascending workers
+        // whole: no_gap is the batch's column list as it stands; max_excess: the largest (sum of the columns' bounds - gap) over with_gap — a cut of at least that size emits no row there
+        // all_gap: every solver worker carries the gap gap_all (with_gap stays empty: nothing to write down per worker)
+        struct PairMemo { bool done = false, whole = false, all_gap = false; uint32_t gap_all = 0; int lhs_id = -1; int64_t max_excess = INT64_MIN; std::vector<int> no_gap; std::vector<std::pair<uint32_t, uint32_t>> with_gap; };  // with_gap: (worker, gap), ascending workers
         std::vector<PairMemo> pair_memo;
         for (const PriorityCut &cut : batch.cuts) {
             for (auto &bl : cut.blockers) {
@@ -1212,23 +1267,37 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
                         std::vector<uint8_t> &cap_brq = cap_cache[brq];  // can the worker run the blocker at all (Worker::is_capable_to_run_rqv): once per request class, not per (batch, cut, blocker)
                         if (cap_brq.empty()) { cap_brq.assign(ws.n, 0); for (uint32_t w : solver_workers) cap_brq[w] = pb.capable_rqv(ws, w, brq) ? 1 : 0; }
                         if (bcols_batch != batch_no) {  // the batch's placement columns per worker and the sum of their bounds: once per batch
-                            bcols_batch = batch_no; bcols_off.assign((size_t)ws.n + 1, 0); bcols.clear(); bcols_ub.assign(ws.n, 0);
+                            bcols_batch = batch_no; bcols_off.assign((size_t)ws.n + 1, 0); bcols.clear(); bcols_ub.assign(ws.n, 0); bcols_ub_max = 0;
+                            if (runs_on) bcols.reserve((size_t)m.ncols());
                             for (uint32_t w : solver_workers) {
                                 bcols_off[w] = (uint32_t)bcols.size();
+                                if (runs_on && stamp_first[w] != UINT32_MAX) {   // a stamp: its run's first block's columns, moved to its own
+                                    const uint32_t f = stamp_first[w]; const int d = blk_base[w] - blk_base[f];
+                                    for (uint32_t i = bcols_off[f], e = bcols_end[f]; i < e; i++) { const int pc = bcols[i] + d; bcols.push_back(pc); }
+                                    bcols_ub[w] = bcols_ub[f];
+                                } else
                                 for (uint8_t v = 0; v < brv.n_variants; v++) { const int pc = place_get(w, batch.rq, v); if (pc >= 0) { bcols.push_back(pc); bcols_ub[w] += col_ub[(size_t)pc]; } }
-                                bcols_end[w] = (uint32_t)bcols.size();
+                                bcols_end[w] = (uint32_t)bcols.size(); bcols_ub_max = std::max(bcols_ub_max, bcols_ub[w]);
                             }
                         }
                         n_triples++;
                         if (!sigs_done) { for (uint32_t w : solver_workers) sig_of(w); sigs_done = true; }  // (every worker's signature up front: the table below is indexed by it)
                         gap_of_sig.assign(sig_rep.size(), UINT32_MAX);
                         bool all_capable = true;
+                        if (runs_on) {   // once per request, like cap_brq itself
+                            if (all_cap_cache.size() < pb.rqs.size()) all_cap_cache.resize(pb.rqs.size(), -1);
+                            if (all_cap_cache[brq] < 0) { all_cap_cache[brq] = 1; for (uint32_t w : solver_workers) if (!cap_brq[w]) { all_cap_cache[brq] = 0; break; } }
+                            all_capable = all_cap_cache[brq] != 0;
+                        } else
                         if (sig_rep.size() == 1) for (uint32_t w : solver_workers) if (!cap_brq[w]) { all_capable = false; break; }
                         if (sig_rep.size() == 1 && all_capable && !solver_workers.empty()) {
                             // identical workers (a cold cluster): ONE gap for all of them — either every worker's columns go into the no-gap list (which is then the
                             // batch's column list as it stands) or every worker carries the gap
                             const uint32_t w0 = solver_workers[0];
                             const uint32_t gap = gap_of(brq, batch.rq, gap_sig[w0], w0);
+                            if (runs_on) {   // (said, not written out per worker: the list is `bcols` itself, the gap one number)
+                                if (gap > 0) { pm.all_gap = true; pm.gap_all = gap; pm.max_excess = (int64_t)bcols_ub_max - (int64_t)gap; } else pm.whole = true;
+                            } else
                             if (gap > 0) { pm.with_gap.reserve(solver_workers.size()); for (uint32_t w : solver_workers) pm.with_gap.push_back({w, gap}); }
                             else pm.no_gap.assign(bcols.begin(), bcols.end());
                         } else {
@@ -1241,14 +1310,18 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
                             else pm.no_gap.insert(pm.no_gap.end(), bcols.data() + bcols_off[w], bcols.data() + bcols_end[w]);
                         }
                         }
-                        if (!pm.no_gap.empty()) {   // blockers that leave no gap on the same workers give the same list: one id (identical workers: every blocker of the batch)
-                            for (const PairMemo &o : pair_memo) if (&o != &pm && o.lhs_id >= 0 && o.no_gap == pm.no_gap) { pm.lhs_id = o.lhs_id; break; }
+                        auto list_of = [&](const PairMemo &q) -> const std::vector<int> & { return q.whole ? bcols : q.no_gap; };
+                        if (!list_of(pm).empty()) {   // blockers that leave no gap on the same workers give the same list: one id (identical workers: every blocker of the batch)
+                            // (two lists that are both the batch's column list as it stands are equal by construction, not by comparison)
+                            for (const PairMemo &o : pair_memo) if (&o != &pm && o.lhs_id >= 0 && ((o.whole && pm.whole) || list_of(o) == list_of(pm))) { pm.lhs_id = o.lhs_id; break; }
                             if (pm.lhs_id < 0) pm.lhs_id = next_lhs_id++;
                         }
+                        if (runs_on) for (auto &wg : pm.with_gap) pm.max_excess = std::max(pm.max_excess, (int64_t)bcols_ub[wg.first] - (int64_t)wg.second);
                     }
-                    no_gap = &pm.no_gap; no_gap_id = pm.lhs_id;
-                    for (auto &wg : pm.with_gap) {
-                        const uint32_t w = wg.first, gap = wg.second;
+                    no_gap = pm.whole ? &bcols : &pm.no_gap; no_gap_id = pm.lhs_id;
+                    // The pass below emits a row for a worker only where the sum of its columns' bounds exceeds cut.size + gap: decided ONCE for the pair where no worker's
+                    // does (equal workers share both figures).  The flag column is still created at this moment, as the pass would at its first worker.
+                    auto gap_rows = [&](const uint32_t w, const uint32_t gap) {
                         const int *wc = bcols.data() + bcols_off[w]; const size_t nwc = bcols_end[w] - bcols_off[w];
                         const uint64_t cols_ub = bcols_ub[w];
                         // (a row no point within the columns' own bounds can violate is not emitted: with cuts in the thousands and workers that hold
@@ -1257,10 +1330,15 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
                         // column) — the model's COLUMNS, and with them the canonical tie-break, stay exactly the reference's.
                         if (bounded && fl_cached == -2) fl_cached = short_flag(brq, bl.second);  // (created at its first use, as get_bvar does; the same flag for every worker of this pair)
                         const int fl = bounded ? fl_cached : -1;
-                        if (cols_ub <= (uint64_t)cut.size + gap) continue;
+                        if (cols_ub <= (uint64_t)cut.size + gap) return;
                         if (bounded && fl >= 0) { cols.assign(wc, wc + nwc); emit_plus(hqmilp::ROW_MAX, (double)cut.size + bsize + (double)gap, cols, fl, bsize); }
                         else if (!bounded) { m.begin_row(hqmilp::ROW_MAX, (double)cut.size + (double)gap); for (size_t k = 0; k < nwc; k++) m.term(wc[k], 1.0); m.end_row(); }
-                    }
+                    };
+                    if (runs_on && (pm.all_gap || !pm.with_gap.empty()) && pm.max_excess <= (int64_t)cut.size) {
+                        if (bounded) fl_cached = short_flag(brq, bl.second);
+                        n_decided_once++;
+                    } else if (pm.all_gap) for (uint32_t w : solver_workers) gap_rows(w, pm.gap_all);
+                    else for (auto &wg : pm.with_gap) gap_rows(wg.first, wg.second);
                 }
                 if (no_gap->empty()) continue;
                 int fl;
@@ -1284,8 +1362,19 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
     m.row_implied.resize(m.nrows(), 0);
     m.row_lhs.resize((size_t)m.nrows(), -1); m.row_lhs_len.resize((size_t)m.nrows(), 0); m.row_block.resize((size_t)m.nrows(), -1);
     m.col_ub = col_ub; m.col_ub.resize((size_t)m.ncols(), UINT32_MAX);
+    if (hqmilp::g_probe) {   // tests: every array of the model, and what was said about its runs
+        using hqmilp::fnv1a_vec;
+        uint64_t h = hqmilp::FNV_BASIS;
+        h = fnv1a_vec(h, m.obj); h = fnv1a_vec(h, m.kind); h = fnv1a_vec(h, m.rtype); h = fnv1a_vec(h, m.rhs); h = fnv1a_vec(h, m.roff); h = fnv1a_vec(h, m.rcol); h = fnv1a_vec(h, m.rcoef);
+        h = fnv1a_vec(h, m.start); h = fnv1a_vec(h, m.col_group); h = fnv1a_vec(h, m.row_implied); h = fnv1a_vec(h, m.row_lhs); h = fnv1a_vec(h, m.row_lhs_len);
+        h = fnv1a_vec(h, m.list_off); h = fnv1a_vec(h, m.list_col); h = fnv1a_vec(h, m.row_block); h = fnv1a_vec(h, m.col_ub);
+        hqmilp::g_probe->model = h; hqmilp::g_probe->runs = m.block_runs.size(); hqmilp::g_probe->tables = 0; hqmilp::g_probe->covered = 0;
+    }
     const double t_model1 = clock_us();
-    if (trace_model) fprintf(stderr, "[model] cuts done at %.3f ms: %d columns, %d rows, %zu terms, %zu worker signatures, %zu (batch, cut, blocker) passes over the workers\n", (t_model1 - t_model0) / 1e3, m.ncols(), m.nrows(), m.rcol.size(), sig_rep.size(), n_triples);
+    if (trace_model) {
+        size_t run_blocks = 0; for (const auto &br : m.block_runs) run_blocks += (size_t)br.n_blocks;
+        fprintf(stderr, "[model] cuts done at %.3f ms: %d columns, %d rows, %zu terms, %zu worker signatures, %zu (batch, cut, blocker) passes over the workers; %zu equal-block runs over %zu blocks, %zu (cut, blocker) passes decided once\n", (t_model1 - t_model0) / 1e3, m.ncols(), m.nrows(), m.rcol.size(), sig_rep.size(), n_triples, m.block_runs.size(), run_blocks, n_decided_once);
+    }
     hqmilp::Result sol = hqmilp::solve(m, pb.time_limit_s, !pb.certificate_only, hqmilp::REFERENCE_MIP_REL_GAP, pb.pricer);  // :432-438
     if (trace_model) fprintf(stderr, "[model] solve done %.3f ms after the model\n", (clock_us() - t_model1) / 1e3);
     out.pre_us = t_model0 - t_enter; out.model_us = t_model1 - t_model0; out.milp_us = clock_us() - t_model1; out.price_sweeps = sol.price_sweeps; out.price_rounds = sol.price_rounds; out.price_us = sol.price_total_us;

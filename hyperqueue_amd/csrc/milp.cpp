@@ -1531,6 +1531,13 @@ void columns_by_cost_desc(const double *c, int n, std::vector<int> &out) { order
 
 thread_local int g_fast_path = -1;
 void set_fast_path(int on) { g_fast_path = on; }
+thread_local int g_block_runs = -1;
+thread_local Probe *g_probe = nullptr;
+void set_block_runs(int on) { g_block_runs = on; }
+bool block_runs_on() {
+    static const bool env_on = !(getenv("HQMILP_BLOCK_RUNS") && atoi(getenv("HQMILP_BLOCK_RUNS")) == 0);  // (A/B switch)
+    return g_block_runs < 0 ? env_on : g_block_runs != 0;
+}
 
 // Row feasibility follows the solver the reference uses: HiGHS accepts a MIP solution whose rows are violated by at most
 // mip_feasibility_tolerance = 1e-6 (absolute, original units).  That matters for one kind of row: the min_utilization pair of
@@ -1555,14 +1562,20 @@ bool solve_fast(const Model &mdl_in, double time_limit_s, double rel_gap, hqpric
     static const bool fast_env = !(getenv("HQMILP_FAST") && atoi(getenv("HQMILP_FAST")) == 0);  // (A/B switch)
     const bool fast_on = g_fast_path < 0 ? fast_env : g_fast_path != 0;                          // (... and the tests' own: tests/test_price.py compares the two paths)
     const int FAST_MIN_COLS = 2048;   // (= LAZY_GREEDY_COLS below: the models that go to the sweeps without an incumbent of the host's)
-    if (fast_on && sweeper && rel_gap > 0.0 && mdl_in.ncols() >= FAST_MIN_COLS && mdl_in.ncols() >= (int)sweeper->min_cols && (int)mdl_in.col_group.size() == mdl_in.ncols() &&
-        (int)mdl_in.row_lhs.size() == mdl_in.nrows() && (int)mdl_in.row_lhs_len.size() == mdl_in.nrows() && (int)mdl_in.start.size() != mdl_in.ncols()) {
+    const bool hints_there = (int)mdl_in.col_group.size() == mdl_in.ncols() && (int)mdl_in.row_lhs.size() == mdl_in.nrows() && (int)mdl_in.row_lhs_len.size() == mdl_in.nrows();
+    const bool takes_it = fast_on && sweeper && rel_gap > 0.0 && mdl_in.ncols() >= FAST_MIN_COLS && mdl_in.ncols() >= (int)sweeper->min_cols && hints_there && (int)mdl_in.start.size() != mdl_in.ncols();
+    // (tests with a probe installed: a model the fast path does not take is flattened all the same, for its digest and the fate of its runs, and the tables dropped)
+    if (takes_it || (g_probe && hints_there)) {
         const int n = mdl_in.ncols(), m = mdl_in.nrows();
         hqprice::ModelView mv;
         mv.n = n; mv.m = m; mv.obj = mdl_in.obj.data(); mv.kind = mdl_in.kind.data(); mv.rtype = mdl_in.rtype.data(); mv.rhs = mdl_in.rhs.data();
         mv.roff = mdl_in.roff.data(); mv.rcol = mdl_in.rcol.data(); mv.rcoef = mdl_in.rcoef.data(); mv.col_group = mdl_in.col_group.data();
         mv.row_implied = (int)mdl_in.row_implied.size() == m ? mdl_in.row_implied.data() : nullptr; mv.row_lhs = mdl_in.row_lhs.data(); mv.row_lhs_len = mdl_in.row_lhs_len.data(); mv.list_off = mdl_in.list_off.data(); mv.list_col = mdl_in.list_col.data(); mv.n_lists = (int)mdl_in.list_off.size() - 1;
         if ((int)mdl_in.row_block.size() == m && (int)mdl_in.col_ub.size() == n) { mv.row_block = mdl_in.row_block.data(); mv.col_ub = mdl_in.col_ub.data(); }
+        static_assert(sizeof(Model::BlockRun) == 7 * sizeof(int32_t), "ModelView::block_runs reads seven int32 per run");
+        if (!mdl_in.block_runs.empty()) { mv.block_runs = &mdl_in.block_runs[0].col0; mv.n_block_runs = (int)mdl_in.block_runs.size(); }
+        mv.run_stats = g_probe ? &g_probe->covered : nullptr; mv.tables_digest = g_probe ? &g_probe->tables : nullptr;
+        if (!takes_it) { hqprice::flatten_for_probe(mv, tracing_solve); return false; }
         double cost_scale = 1.0;
         const double tf0 = wall();
         hqprice::Answer pa = hqprice::solve_model(mv, rel_gap, time_limit_s, ts0 + (time_limit_s > 0 ? time_limit_s : 1e18), tracing_solve, *sweeper, &cost_scale);

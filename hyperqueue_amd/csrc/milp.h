@@ -15,6 +15,7 @@
 // which is also what HiGHS returns there — and among placement columns ties go to earlier batches / lower worker ids,
 // the same direction the objective's (W - idx) factor pushes.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <algorithm>
 #include <vector>
@@ -76,6 +77,13 @@ struct Model {
     //                            floor(free / amount), in exact integers) — a bound the rows imply, handed over so that nobody has to derive it again
     std::vector<int32_t> row_block;
     std::vector<uint32_t> col_ub;
+    //   block_runs: n_blocks CONSECUTIVE blocks that start at column col0 / row row0 / term term0, each of n_cols columns, n_rows rows and n_terms terms laid out back
+    //               to back, are EQUAL in kinds, col_ub, row types, right-hand sides, row_implied, coefficients and block-relative column numbers — only obj differs
+    //               (the tick: workers whose snapshot rows are equal).  Their col_group values need not be consecutive (a worker that emits nothing lies between
+    //               two blocks without breaking the run).  Seven int32 per run, in this order: what csrc/price.cpp flattens once per run instead of once per block —
+    //               after comparing the blocks (a hint is checked, never trusted).
+    struct BlockRun { int32_t col0, row0, term0, n_blocks, n_cols, n_rows, n_terms; };
+    std::vector<BlockRun> block_runs;
     int ncols() const { return (int)obj.size(); }
     int nrows() const { return (int)rhs.size(); }
     int add_col(double w, uint8_t k) {
@@ -122,5 +130,15 @@ Result solve(const Model &m, double time_limit_s, bool canonical = true, double 
 void columns_by_cost_desc(const double *c, int n, std::vector<int> &out);
 // the coupled tick's fast path (solve(): large structured models straight to the price sweeps) for this thread: 1 on, 0 off, -1 the default (on unless HQMILP_FAST=0)
 void set_fast_path(int on);
+// the builder's equal-block runs (Model::block_runs) for this thread: 1 recorded, 0 not (the model and every table come out the same, block by block), -1 the default
+// (on unless HQMILP_BLOCK_RUNS=0).  block_runs_on(): what holds now.
+void set_block_runs(int on);
+bool block_runs_on();
+// Test probe (libhqtick_test.so sets one; nullptr in the product): FNV-1a digests of the last coupled model and of what the flattener made of it, and what became of the runs.
+struct Probe { uint64_t model = 0, tables = 0, runs = 0, covered = 0; bool corrupt_runs = false; };
+extern thread_local Probe *g_probe;
+inline uint64_t fnv1a(uint64_t h, const void *p, size_t bytes) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < bytes; i++) h = (h ^ b[i]) * 1099511628211ull; return h; }
+template <class T> inline uint64_t fnv1a_vec(uint64_t h, const std::vector<T> &v) { const uint64_t n = v.size(); h = fnv1a(h, &n, 8); return v.empty() ? h : fnv1a(h, v.data(), v.size() * sizeof(T)); }
+const uint64_t FNV_BASIS = 1469598103934665603ull;
 
 }  // namespace hqmilp

@@ -58,6 +58,7 @@ struct Prob {
     std::vector<CapRow> caps;
     std::vector<int32_t> base_cap;
     std::vector<int> block_of_flat;
+    int n_runs = 0, run_blocks = 0;   // equal-block runs of the model that passed the flattener's comparison, and the blocks they cover (statistics)
 };
 
 // round half away from zero without the call into libm (-msse4.1 gives floor / nearbyint as one instruction, not round); |v| < 2^51
@@ -960,6 +961,7 @@ Answer run_solver(Solver &S, const double tp0) {
     const Request &rq = S.rq; Sweeper &sw = S.sw;
     auto tmark = [&](const char *what) { if (rq.trace) fprintf(stderr, "[price] %s at %.3f ms (sweeps so far %.3f ms)\n", what, (now_us() - tp0) / 1e3, sw.stat_sweep_us / 1e3); };
     tmark("model flattened");
+    if (rq.trace) fprintf(stderr, "[price]   %d equal-block runs took %d of %u blocks from their first one\n", S.P.n_runs, S.P.run_blocks, S.P.T.n_blocks);
     Prob &P = S.P;
     if (rq.trace) fprintf(stderr, "[price] %u blocks, %u block columns, %d wide rows with %d distinct left-hand sides (%zu / %zu terms), %d flags, %zu conditional bounds\n", P.T.n_blocks, P.T.n_cols, P.K, P.KG, P.row_terms, P.T.w_row.size(), P.G, P.caps.size());
     const int K = P.K, G = P.G;
@@ -1305,7 +1307,7 @@ namespace {
 thread_local bool g_check_hints = false; thread_local int g_hint_mismatches = 0;
 // ---- the model as its builder wrote it -> blocks + wide rows (what build() does for a scaled component copy; same tables, same numbering) -------------------------
 // Returns nullptr on success, else what keeps the model on the classic path.  ub: the derived column bounds (model columns), c: obj / cmax.
-const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax) {
+const char *flatten_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax) {
     const int n = mv.n, m = mv.m;
     if (!mv.col_group || !mv.row_lhs || !mv.row_lhs_len) return "no structure hints";
     // blocks in order of their first column (the tick: worker order)
@@ -1366,6 +1368,47 @@ const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &
         const double bnd = std::floor(fam[(size_t)l].rhs_min + 1e-9);
         for (int k = mv.list_off[l]; k < mv.list_off[l + 1]; k++) { double &u = ub[mv.list_col[k]]; u = std::min(u, bnd); }
     }
+    // ---- equal-block runs (milp.h: Model::block_runs).  A hint like the others: every block of a run is compared with the run's first one — whole blocks with consecutive
+    // numbers, the same kinds, bounds (the builder's and the ones derived above), row types, right-hand sides, implied marks, coefficients and block-relative columns, rows
+    // that are their block's alone — and a run that fails anywhere is forgotten: its blocks are then flattened one by one like any other.
+    struct Run { int col0, row0, term0, nbk, nc, nr, nt, b0; };
+    std::vector<Run> runs;
+    if (hinted && mv.block_runs) {
+        long long col_end = 0, row_end = 0;
+        auto holds = [&](const int32_t *r) -> bool {
+            const long long col0 = r[0], row0 = r[1], term0 = r[2], nbk = r[3], nc = r[4], nr = r[5], nt = r[6];
+            if (nbk < 2 || nc < 1 || nc > NMAX_BLOCK || nr < 1 || nt < 1 || col0 < col_end || row0 < row_end) return false;
+            if (col0 + nbk * nc > n || row0 + nbk * nr > m) return false;
+            if (mv.roff[row0] != term0 || (long long)mv.roff[row0 + nbk * nr] != term0 + nbk * nt) return false;
+            const int b0 = blk[col0];
+            if (b0 < 0 || b0 + nbk > nb) return false;
+            for (long long t = 0; t < nt; t++) { const long long rel = (long long)mv.rcol[term0 + t] - col0; if (rel < 0 || rel >= nc) return false; }   // the first block's rows hold its own columns only
+            for (long long q = 0; q < nc; q++) if (blk[col0 + q] != b0) return false;
+            for (long long k = 0; k < nbk; k++) {   // whole blocks, and rows that are their block's alone
+                if (bsize[b0 + k] != nc) return false;
+                const int32_t gk = mv.col_group[col0 + k * nc];
+                const long long rk = row0 + k * nr;
+                for (long long q = 0; q < nr; q++) if (mv.row_lhs[rk + q] >= 0 || mv.row_block[rk + q] != gk) return false;
+            }
+            // every block against the one before it: the arrays compared with themselves, one block further on
+            const size_t cs = (size_t)((nbk - 1) * nc), rs = (size_t)((nbk - 1) * nr), ts = (size_t)((nbk - 1) * nt);
+            { const int *bp = blk.data() + col0; bool ok = true; for (size_t q = 0; q < cs; q++) ok &= bp[q + nc] == bp[q] + 1; if (!ok) return false; }
+            if (memcmp(mv.kind + col0 + nc, mv.kind + col0, cs) != 0 || memcmp(mv.col_ub + col0 + nc, mv.col_ub + col0, cs * sizeof(uint32_t)) != 0) return false;
+            if (memcmp(&ub[col0 + nc], &ub[col0], cs * sizeof(double)) != 0) return false;
+            if (memcmp(mv.rtype + row0 + nr, mv.rtype + row0, rs) != 0 || memcmp(mv.rhs + row0 + nr, mv.rhs + row0, rs * sizeof(double)) != 0) return false;
+            if (mv.row_implied && memcmp(mv.row_implied + row0 + nr, mv.row_implied + row0, rs) != 0) return false;
+            if (memcmp(mv.rcoef + term0 + nt, mv.rcoef + term0, ts * sizeof(double)) != 0) return false;
+            { const int *ro = mv.roff + row0; bool ok = true; for (size_t q = 0; q <= rs; q++) ok &= (long long)ro[q + nr] - ro[q] == nt; if (!ok) return false; }
+            { const int *rc = mv.rcol + term0; bool ok = true; for (size_t q = 0; q < ts; q++) ok &= (long long)rc[q + nt] - rc[q] == nc; if (!ok) return false; }
+            return true;
+        };
+        for (int q = 0; q < mv.n_block_runs; q++) {
+            const int32_t *r = mv.block_runs + (size_t)7 * q;
+            if (!holds(r)) continue;
+            runs.push_back({r[0], r[1], r[2], r[3], r[4], r[5], r[6], blk[r[0]]});
+            col_end = (long long)r[0] + (long long)r[3] * r[4]; row_end = (long long)r[1] + (long long)r[3] * r[5];
+        }
+    }
     if (hinted && g_check_hints) {   // tests: the builder's column bounds must be what the skipped single-block rows give — not tighter (a point lost), not looser
         std::vector<double> chk(n, INF);
         for (int j = 0; j < n; j++) if (mv.kind[j] == 1) chk[j] = 1.0;
@@ -1376,7 +1419,18 @@ const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &
             if (neg) continue;
             for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] > 0.0) chk[mv.rcol[k]] = std::min(chk[mv.rcol[k]], std::floor(mv.rhs[i] / mv.rcoef[k] + 1e-9));
         }
-        for (int j = 0; j < n; j++) if (mv.col_ub[j] != UINT32_MAX && chk[j] < INF && (double)mv.col_ub[j] != chk[j]) { g_hint_mismatches++; return "structure hint: col_ub differs from what the block's rows give"; }
+        // ... unless a row that is NOT one block's alone gives it (an unbounded resource's terms carried into the next worker's row make that row such a one): then it is
+        // a bound some row of the model states, which is all a hint has to be — `any` is the tightest bound a single row gives, over all rows
+        std::vector<double> any(chk);
+        for (int i = 0; i < m; i++) {
+            if (mv.row_block[i] >= 0 || mv.rtype[i] == 0) continue;
+            bool neg = false;
+            for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] < 0.0) neg = true;
+            if (neg) continue;
+            for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] > 0.0) any[mv.rcol[k]] = std::min(any[mv.rcol[k]], std::floor(mv.rhs[i] / mv.rcoef[k] + 1e-9));
+            if (mv.row_lhs[i] >= 0) for (int k = mv.list_off[mv.row_lhs[i]]; k < mv.list_off[mv.row_lhs[i] + 1]; k++) any[mv.list_col[k]] = std::min(any[mv.list_col[k]], std::floor(mv.rhs[i] + 1e-9));
+        }
+        for (int j = 0; j < n; j++) if (mv.col_ub[j] != UINT32_MAX && chk[j] < INF && ((double)mv.col_ub[j] > chk[j] || (double)mv.col_ub[j] < any[j])) { g_hint_mismatches++; return "structure hint: col_ub differs from what the block's rows give"; }
     }
     
     HostTables &T = P.T;
@@ -1416,7 +1470,32 @@ const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &
             if (sc.b0 == -2) sc.b0 = blk[j]; else if (blk[j] != sc.b0) sc.multi = true;
         }
     };
+    // a run's first block goes through the rows below like any block; what they made of it — rows kept, their order, grid coefficients, capacities — is then copied to
+    // the other blocks of the run, whose rows are passed over.  (Only where no earlier row has touched one of these blocks: the copy is then all there is to them.)
+    size_t run_i = 0; bool run_live = false;
+    auto stamp_run = [&](const Run &R) {
+        const uint32_t f0 = T.blk_off[R.b0];
+        const size_t col_bytes = (size_t)R.nc * MMAX_BLOCK * sizeof(double);
+        for (int k = 1; k < R.nbk; k++) {
+            const int b = R.b0 + k;
+            T.blk_m[b] = T.blk_m[R.b0];
+            memcpy(&T.blk_cap[(size_t)b * MMAX_BLOCK], &T.blk_cap[(size_t)R.b0 * MMAX_BLOCK], MMAX_BLOCK * sizeof(double));
+            memcpy(&T.col_a[(size_t)T.blk_off[b] * MMAX_BLOCK], &T.col_a[(size_t)f0 * MMAX_BLOCK], col_bytes);
+        }
+        P.n_runs++; P.run_blocks += R.nbk;
+    };
     for (int i = 0; i < m; i++) {
+        if (run_live && i == runs[run_i].row0 + runs[run_i].nr) {
+            stamp_run(runs[run_i]);
+            i = runs[run_i].row0 + runs[run_i].nbk * runs[run_i].nr;
+            run_live = false; run_i++;
+            if (i >= m) break;
+        }
+        if (!run_live && run_i < runs.size() && i == runs[run_i].row0) {
+            bool fresh = true;
+            for (int k = 0; k < runs[run_i].nbk && fresh; k++) if (T.blk_m[runs[run_i].b0 + k] != 0) fresh = false;
+            if (fresh) run_live = true; else run_i++;
+        }
         const int a = mv.roff[i], e = mv.roff[i + 1];
         if (a == e && mv.row_lhs[i] < 0) continue;
         const bool is_le = mv.rtype[i] == 1, is_ge = mv.rtype[i] == 0;
@@ -1522,6 +1601,7 @@ const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &
         if ((int)wide.size() > 1024) return "more than 1024 wide rows";
     }
     
+    if (run_live) stamp_run(runs[run_i]);   // (a run whose rows are the model's last)
     for (int b = 0; b < nb; b++) if (T.blk_m[b] == 0) {   // every resource row of this worker is slack at its column bounds: a never-binding row (the kernel wants one)
         double total = 0.0;
         for (uint32_t f = T.blk_off[b]; f < T.blk_off[b + 1]; f++) { T.col_a[(size_t)f * MMAX_BLOCK] = 1.0; total += (double)T.col_cap[f]; }
@@ -1568,6 +1648,36 @@ const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &
     
     P.base_cap = T.col_cap;
     return nullptr;
+}
+
+// FNV-1a over everything the flattening leaves (tests: two ways of getting there must agree in every byte)
+uint64_t digest_of(const Prob &P) {
+    using hqmilp::fnv1a; using hqmilp::fnv1a_vec;
+    const HostTables &T = P.T;
+    uint64_t h = hqmilp::FNV_BASIS;
+    const uint32_t dims[3] = {T.n_blocks, T.n_cols, T.K}; h = fnv1a(h, dims, sizeof dims);
+    h = fnv1a_vec(h, T.blk_off); h = fnv1a_vec(h, T.blk_m); h = fnv1a_vec(h, T.blk_cap); h = fnv1a_vec(h, T.col_cost); h = fnv1a_vec(h, T.col_a); h = fnv1a_vec(h, T.col_cap);
+    h = fnv1a_vec(h, T.col_woff); h = fnv1a_vec(h, T.w_row); h = fnv1a_vec(h, T.w_coef);
+    const int dims2[3] = {P.K, P.G, P.KG}; h = fnv1a(h, dims2, sizeof dims2);
+    h = fnv1a_vec(h, P.h); h = fnv1a_vec(h, P.ge); h = fnv1a_vec(h, P.grp_of); h = fnv1a_vec(h, P.g_off); h = fnv1a_vec(h, P.g_col); h = fnv1a_vec(h, P.g_coef);
+    h = fnv1a_vec(h, P.gr_off); h = fnv1a_vec(h, P.gr_row); h = fnv1a_vec(h, P.gmodel); h = fnv1a_vec(h, P.gcost); h = fnv1a_vec(h, P.flat_of); h = fnv1a_vec(h, P.model_of);
+    h = fnv1a_vec(h, P.block_of_flat); h = fnv1a_vec(h, P.base_cap);
+    for (const CapRow &cr : P.caps) { h = fnv1a(h, &cr.flat, sizeof cr.flat); h = fnv1a(h, &cr.rhs, sizeof cr.rhs); for (auto &t : cr.g) { h = fnv1a(h, &t.first, sizeof t.first); h = fnv1a(h, &t.second, sizeof t.second); } }
+    for (const auto &gr : P.g_rows) { const uint64_t nn = gr.size(); h = fnv1a(h, &nn, 8); for (auto &t : gr) { h = fnv1a(h, &t.first, sizeof t.first); h = fnv1a(h, &t.second, sizeof t.second); } }
+    return h;
+}
+
+const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax) {
+    const char *why = flatten_model(mv, P, ub, c, cmax);
+    if (!why && g_check_hints && mv.block_runs) {   // tests: everything the runs passed over, flattened block by block after all, must come out the same
+        ModelView plain = mv; plain.block_runs = nullptr; plain.n_block_runs = 0;
+        Prob P2; std::vector<double> ub2, c2; double cmax2 = 0.0;
+        const char *why2 = flatten_model(plain, P2, ub2, c2, cmax2);
+        if (why2 || digest_of(P2) != digest_of(P) || ub2 != ub || c2 != c || cmax2 != cmax) { g_hint_mismatches++; return "structure hint: a block run's tables differ from its blocks' own"; }
+    }
+    if (!why && mv.run_stats) *mv.run_stats += (uint64_t)P.run_blocks;
+    if (!why && mv.tables_digest) *mv.tables_digest = digest_of(P);
+    return why;
 }
 
 // The candidate point of a flag configuration against the flattened model, raised greedily (most valuable columns first) as far as the blocks' rows, the wide rows
@@ -1656,6 +1766,12 @@ Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, dou
     Polisher pol(S.P, mv.n);
     rq.polish = [&pol](std::vector<double> &x, double &value) { return pol.run(x, value); };
     return run_solver(S, tp0);
+}
+
+void flatten_for_probe(const ModelView &mv, bool trace) {
+    Prob P; std::vector<double> ub, c; double cmax = 1.0;
+    const char *why = build_from_model(mv, P, ub, c, cmax);
+    if (trace) fprintf(stderr, "[price] flattened for the probe alone: %s\n", why ? why : "tables built");
 }
 
 void set_check_hints(bool on) { g_check_hints = on; g_hint_mismatches = 0; }

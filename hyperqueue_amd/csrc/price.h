@@ -117,10 +117,17 @@ struct ModelView {
     const int32_t *row_lhs = nullptr, *row_lhs_len = nullptr;
     const int *list_off = nullptr, *list_col = nullptr; int n_lists = 0;   // the shared lists row_lhs names (milp.h: Model::list_off / list_col): coefficient 1 each, not among the rows' stored terms
     const int32_t *row_block = nullptr; const uint32_t *col_ub = nullptr;   // optional (milp.h: Model::row_block / col_ub)
+    // optional (milp.h: Model::block_runs): seven int32 per run — col0, row0, term0, n_blocks, n_cols, n_rows, n_terms.  Every run is compared block against block
+    // before anything is taken from it; one that fails counts as n_blocks single blocks.
+    const int32_t *block_runs = nullptr; int n_block_runs = 0;
+    uint64_t *run_stats = nullptr;       // tests: += blocks covered by the runs that passed the comparison
+    uint64_t *tables_digest = nullptr;   // tests: FNV-1a over the flattened problem and its tables
 };
 // tests: also check the builder's column bounds against the rows they stand for (this thread); mismatches since the last call that switched it on
 void set_check_hints(bool on);
 int hint_mismatches();
+// tests: the flattening alone (what it leaves goes to mv.run_stats / mv.tables_digest and is dropped)
+void flatten_for_probe(const ModelView &mv, bool trace);
 Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, double deadline_s, bool trace, Sweeper &sw, double *cost_scale);
 
 // All-gather of small host buffers between the ranks of a sharded scheduler: librccl inside the library (hqtick_comm_init) or a callback of the host

@@ -102,6 +102,16 @@ void hqtick_debug_set_fast_path(int on);
  * from the rows it stands for.  _mismatches: models refused for that reason since the check was switched on. */
 void hqtick_debug_check_model_hints(int on);
 int hqtick_debug_model_hint_mismatches(void);
+/* The builder's equal-block runs (csrc/milp.h: Model::block_runs: consecutive worker blocks that differ in their costs only, built and flattened once per run) for
+ * this thread: 1 recorded, 0 not — the model and every table must come out the same byte for byte —, -1 the default (on unless HQMILP_BLOCK_RUNS=0).  While it is 0 or 1
+ * the thread's coupled models are also digested (below), and one that is too small for the fast path is flattened all the same, for its digest alone. */
+void hqtick_debug_set_block_runs(int on);
+/* Of the last coupled model hqtick_debug_host_stages built on this thread while hqtick_debug_set_block_runs was 0 or 1: out[0] = 64-bit FNV-1a over every array of
+ * the model, out[1] = the same over what the fast path flattened it into (the problem and its sweep tables; 0: the model did not get there), out[2] = runs the builder
+ * recorded, out[3] = blocks covered by the runs that passed the flattener's comparison. */
+void hqtick_debug_last_coupled_digest(uint64_t out[4]);
+/* fault injection: on != 0 makes the builder merge its first two runs into one false claim (the flattener must refuse it and flatten those blocks one by one). */
+void hqtick_debug_corrupt_block_runs(int on);
 /* sweeps over all blocks / flag configurations of the last hqtick_debug_host_stages call (0: the host search ran alone) */
 void hqtick_debug_last_price(uint32_t *sweeps, uint32_t *rounds);
 /* the multi-node placements of the last hqtick_debug_host_stages call on this thread (the counts carry single-node placements only): returns the number of
