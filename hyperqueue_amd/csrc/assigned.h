@@ -7,6 +7,12 @@
 //     key u64 (HT_EMPTY / HT_TOMB) | worker id u32 | rq u32 | variant u8 | priority u64 | claim u32 (batch position of a release, else NONE)
 //   counts u32 [W x stride]: running tasks per (worker row, variant slot); slot = rq_variant_off[rq] + variant
 //   free / total rows: the resident worker set's own rows in HBM (hqtick_cluster_*), updated in place
+//   multi-node tasks (Worker::mn_task, server/worker.rs:134-175): three more columns per worker row, 10 B per row, re-packed with the count rows
+//     mn task u64 [W] (HT_EMPTY: the row holds none) | mn root u8 [W] (1: the row is its task's root) | flags u8 [W] (HQ_WORKER_* bits, the mirror's byte)
+//   and one table entry per task: key = task id, worker = the ROOT's worker id, rq, priority, variant = MN_VARIANT (0xFF: no single-node entry carries
+//   it — a request has fewer than 255 variants).  It counts in no (row, slot) and touches no free row while it runs.
+//   Invariant: a row's mn task is a live MN_VARIANT entry of the table.  Release and eviction tombstone the entry first; the row pass that follows resets
+//   every row whose task is no longer found (reset_mn_task: SN bit set, free row = total row, columns cleared).
 // Everything here is integer work bound by HBM latency; no MFMA.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +24,7 @@ namespace hqasg {
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint64_t HT_EMPTY = ~0ull, HT_TOMB = ~0ull - 1;  // task ids must be below HT_TOMB
 constexpr uint32_t RQ_LOOKUP = 0xFFFFFFFFu;              // insert item whose rq / priority come from the ready-set columns
+constexpr uint8_t MN_VARIANT = 0xFF;                     // variant column of a multi-node task's entry
 
 struct Table {
     uint64_t *key; uint32_t *worker; uint32_t *rq; uint8_t *variant; uint64_t *prio; uint32_t *claim;
@@ -33,6 +40,19 @@ struct Rows {
     const uint32_t *wid; uint32_t W, R;
     const uint64_t *total; uint64_t *free_;
     uint32_t *counts; uint32_t stride;
+};
+// the multi-node columns of the worker rows (all nullptr: a caller without them); live = multi-node entries in the table as the host counts them — a
+// uniform argument: with live == 0 no kernel reads the columns
+struct MnRows {
+    uint64_t *task; uint8_t *root; uint8_t *flags;
+    uint32_t live;
+};
+// multi-node placements: task i runs on the workers wid[off[i] .. off[i + 1]), root first.  prio == nullptr: the priority is looked up by id in the
+// ready-set columns col_id / col_prio (a consumed task keeps its id and priority)
+struct MnItems {
+    uint32_t n, n_wid;
+    const uint64_t *id; const uint32_t *rq; const uint64_t *prio; const uint32_t *off; const uint32_t *wid;
+    const uint64_t *col_id; const uint64_t *col_prio; uint64_t col_n;
 };
 // an insert batch from explicit columns (wid: worker ids)
 struct Items {
@@ -51,7 +71,8 @@ struct Staged {
     const uint64_t *col_id; const uint64_t *col_prio; uint64_t col_n;
 };
 // counters of one operation, in device memory, one atomic per wavefront (insert: C_OUT = entries that were not there before; evict: entries gathered)
-enum Ctr : uint32_t { C_DONE = 0, C_UNKNOWN = 1, C_DUP = 2, C_FULL = 3, C_BAD = 4, C_OUT = 5, C_N = 8 };
+// (C_MN: the multi-node entries among C_DONE of a release / C_OUT of an eviction)
+enum Ctr : uint32_t { C_DONE = 0, C_UNKNOWN = 1, C_DUP = 2, C_FULL = 3, C_BAD = 4, C_OUT = 5, C_MN = 6, C_N = 8 };
 
 hipError_t clear(Table t, hipStream_t s);
 // insert (upsert != 0: an id already present moves to the new worker / variant, its old count is given back; else it is counted as a duplicate).
@@ -59,15 +80,24 @@ hipError_t clear(Table t, hipStream_t s);
 hipError_t insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr, hipStream_t s);
 // the staged placement of a tick as upserts, free rows untouched (they become the tick's new_free)
 hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipStream_t s);
-// release in batch order with the last-ALL rule; scratch: pos [n] u32, last_all [W * R] u32, delta [W * R] u64 (zero on entry and on return)
-hipError_t release(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s);
-// every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT]
+// release in batch order with the last-ALL rule; scratch: pos [n] u32, last_all [W * R] u32, delta [W * R] u64 (zero on entry and on return).
+// A multi-node id of the batch leaves the table like the others (counted in C_DONE and C_MN); with m.live != 0 the W x R row pass resets its rows.
+hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s);
+// every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
+// A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
 hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr, hipStream_t s);
+// multi-node placements enter: owner is scratch [W] u32.  Task i enters only if every listed worker is resident, listed once, claimed by no task earlier in
+// the batch and holds no multi-node task, and the id is new; check != 0 (hqtick_assigned_add_mn) also wants every worker free of single-node tasks and
+// not STOPPING.  Then each row loses its SN bit and records the task (first row: root); free rows stay.  C_DONE entered, C_BAD / C_DUP refused.
+hipError_t mn_enter(Table t, Rows r, MnRows m, MnItems it, uint32_t *owner, int check, uint32_t *ctr, hipStream_t s);
+// reset_mn_task on every row whose multi-node task is no longer in the table (after an eviction; the release has this inside its own row pass)
+hipError_t mn_reset_rows(Table t, Rows r, MnRows m, hipStream_t s);
 // live entries of `from` re-inserted into the (cleared) table `to`
 hipError_t rehash(Table from, Table to, uint32_t *ctr, hipStream_t s);
-// dst row w = src row src_row[w] (NONE or >= W_src: a zero row), columns [0, n_cols)
+// dst row w = src row src_row[w] (NONE or >= W_src: a zero row), columns [0, n_cols).  With ms.task the multi-node columns move in the same launch
+// (md: the destination; a new row holds no task and takes its flags byte from new_flags [W_dst])
 hipError_t repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride,
-                         uint32_t n_cols, hipStream_t s);
+                         uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s);
 hipError_t lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant, hipStream_t s);
 
 }  // namespace hqasg

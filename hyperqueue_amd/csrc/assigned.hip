@@ -89,7 +89,7 @@ __device__ __forceinline__ int enter(const Table &t, const Req &q, const Rows &r
     const uint32_t b = ht_claim(t, id, &fresh);
     if (b == NONE) return S_FULL;
     if (!fresh) {
-        if (!upsert) return S_DUP;
+        if (!upsert || t.variant[b] == MN_VARIANT) return S_DUP;  // (a multi-node task never moves: it has no count to give back)
         const uint32_t orow = row_of(r, t.worker[b]);  // a re-targeted redirect: the old target's count goes back (its free row is the tick's)
         if (orow != NONE) atomicSub(&r.counts[(size_t)orow * r.stride + q.rq_off[t.rq[b]] + t.variant[b]], 1u);
     }
@@ -162,6 +162,7 @@ __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos
     if (b != NONE) {
         const uint32_t row = row_of(r, t.worker[b]);
         if (t.claim[b] != i) { pos[i] = NONE; dup = true; }
+        else if (t.variant[b] == MN_VARIANT) {}  // a multi-node task: no count, no entry of any resource (its rows are reset by pass 4)
         else if (row == NONE) { pos[i] = NONE; bad = true; t.claim[b] = NONE; }  // (left in the table, unclaimed: a later batch finds it as before)
         else {
             const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
@@ -175,25 +176,91 @@ __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos
 __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, uint32_t *ctr) {
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
+    bool mn = false;
     if (b != NONE) {
-        const uint32_t row = row_of(r, t.worker[b]);
-        const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
-        for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) {
-            const size_t j = (size_t)row * r.R + q.ent_res[e];
-            if (q.ent_kind[e] == HQ_ENTRY_AMOUNT && i + 1 > last_all[j]) atomicAdd(reinterpret_cast<unsigned long long *>(&delta[j]), (unsigned long long)q.ent_amount[e]);
+        mn = t.variant[b] == MN_VARIANT;
+        if (!mn) {
+            const uint32_t row = row_of(r, t.worker[b]);
+            const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
+            for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) {
+                const size_t j = (size_t)row * r.R + q.ent_res[e];
+                if (q.ent_kind[e] == HQ_ENTRY_AMOUNT && i + 1 > last_all[j]) atomicAdd(reinterpret_cast<unsigned long long *>(&delta[j]), (unsigned long long)q.ent_amount[e]);
+            }
+            atomicSub(&r.counts[(size_t)row * r.stride + slot], 1u);
         }
-        atomicSub(&r.counts[(size_t)row * r.stride + slot], 1u);
         t.key[b] = HT_TOMB; t.claim[b] = NONE;
     }
-    wave_add(&ctr[C_DONE], b != NONE);
+    wave_add(&ctr[C_DONE], b != NONE); wave_add(&ctr[C_MN], mn);
+}
+// reset_mn_task (worker.rs:172-175) of a row whose multi-node task has left the table: SN bit set, free row = total row, columns cleared
+__device__ __forceinline__ void mn_reset_row(const Table &t, const Rows &r, const MnRows &m, uint32_t row) {
+    const uint64_t id = m.task[row];
+    if (id == HT_EMPTY || ht_find(t, id) != NONE) return;
+    for (uint32_t c = 0; c < r.R; c++) r.free_[(size_t)row * r.R + c] = r.total[(size_t)row * r.R + c];
+    m.task[row] = HT_EMPTY; m.root[row] = 0; m.flags[row] = (uint8_t)(m.flags[row] | HQ_WORKER_SN);
 }
 // pass 4: free.add per (row, resource) — ALL sets the total (workerload.rs:194-202), the AMOUNTs after it add
-__global__ void k_rel_rows(Rows r, uint32_t *last_all, uint64_t *delta) {
+__global__ void k_rel_rows(Table t, Rows r, MnRows m, uint32_t *last_all, uint64_t *delta) {
     const uint32_t j = blockIdx.x * TPB + threadIdx.x;
     if (j >= r.W * r.R) return;
     const uint32_t la = last_all[j]; const uint64_t d = delta[j];
     if (la) r.free_[j] = r.total[j] + d; else if (d) r.free_[j] += d;
     last_all[j] = 0; delta[j] = 0;
+    // multi-node tasks of the batch (pass 3 took their entries out): the thread of a row's first resource resets the whole row.  A row that holds a multi-node
+    // task holds no single-node task (Worker::set_mn_task wants is_free), so no entry of the batch names it: la == 0 and d == 0 in all its R threads, nothing
+    // above wrote its free row, and the last-ALL ordering of the other rows is untouched.  m.live == 0 (uniform): the columns are not read at all.
+    if (m.live && j % r.R == 0) mn_reset_row(t, r, m, j / r.R);
+}
+__global__ void k_mn_reset_rows(Table t, Rows r, MnRows m) {
+    const uint32_t row = blockIdx.x * TPB + threadIdx.x;
+    if (row < r.W) mn_reset_row(t, r, m, row);
+}
+// multi-node placements, pass 1: per worker row the first task of the batch that lists it
+__global__ void k_mn_claim(Rows r, MnItems it, uint32_t *owner) {
+    const uint32_t j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= it.n_wid) return;
+    uint32_t lo = 0, hi = it.n;  // the task whose list holds position j: the last i with off[i] <= j
+    while (lo + 1 < hi) { const uint32_t mid = (lo + hi) >> 1; if (it.off[mid] <= j) lo = mid; else hi = mid; }
+    const uint32_t row = row_of(r, it.wid[j]);
+    if (row != NONE) atomicMin(&owner[row], lo);
+}
+// pass 2: one thread per task (a task has a handful of workers; a tick places few of them)
+__global__ void k_mn_enter(Table t, Rows r, MnRows m, MnItems it, const uint32_t *owner, int check, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    int status = S_SKIP;
+    if (i < it.n) {
+        const uint64_t id = it.id[i];
+        const uint32_t b0 = it.off[i], b1 = it.off[i + 1];
+        uint64_t prio = 0;
+        bool ok = id < HT_TOMB && b0 < b1 && b1 <= it.n_wid;
+        if (ok && it.prio) prio = it.prio[i];
+        else if (ok) { const uint64_t c = col_find(it.col_id, it.col_n, id); ok = c != ~0ull; if (ok) prio = it.col_prio[c]; }
+        for (uint32_t j = b0; ok && j < b1; j++) {
+            const uint32_t row = row_of(r, it.wid[j]);
+            ok = row != NONE && owner[row] == i && m.task[row] == HT_EMPTY;
+            for (uint32_t k = b0; ok && k < j; k++) ok = it.wid[k] != it.wid[j];
+            if (ok && check) {  // Worker::is_free (worker.rs:134-137), or a worker uploaded without its SN bit that holds nothing yet
+                ok = (m.flags[row] & HQ_WORKER_STOPPING) == 0;
+                for (uint32_t c = 0; ok && c < r.stride; c++) ok = r.counts[(size_t)row * r.stride + c] == 0;
+            }
+        }
+        status = S_BAD;
+        if (ok) {
+            int fresh = 0;
+            const uint32_t b = ht_claim(t, id, &fresh);
+            if (b == NONE) status = S_FULL;
+            else if (!fresh) status = S_DUP;
+            else {
+                t.worker[b] = it.wid[b0]; t.rq[b] = it.rq[i]; t.variant[b] = MN_VARIANT; t.prio[b] = prio; t.claim[b] = NONE;
+                for (uint32_t j = b0; j < b1; j++) {  // set_mn_task (worker.rs:160-166): the free row stays as it is
+                    const uint32_t row = row_of(r, it.wid[j]);
+                    m.task[row] = id; m.root[row] = j == b0 ? 1 : 0; m.flags[row] = (uint8_t)(m.flags[row] & ~HQ_WORKER_SN);
+                }
+                status = S_FRESH;
+            }
+        }
+    }
+    count_status(ctr, status);
 }
 
 __global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr) {
@@ -206,6 +273,7 @@ __global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t
         while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (lost[mid] < w) lo = mid + 1; else hi = mid; }
         hit = lo < n_lost && lost[lo] == w;
     }
+    wave_add(&ctr[C_MN], hit && t.variant[b] == MN_VARIANT);  // (its worker column is the root: a lost root evicts the task, reactor.rs:107-128)
     const uint32_t o = wave_append(&ctr[C_OUT], hit);
     if (!hit || o >= cap_out) return;  // (the host sized the output by its live count: more is reported as an error and nothing is written past the end)
     out_id[o] = k; out_rq[o] = t.rq[b]; out_prio[o] = t.prio[b];
@@ -224,12 +292,17 @@ __global__ void k_rehash(Table from, Table to, uint32_t *ctr) {
     wave_add(&ctr[C_DONE], k < HT_TOMB && d != NONE); wave_add(&ctr[C_FULL], k < HT_TOMB && d == NONE);
 }
 
-__global__ void k_repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride, uint32_t n_cols) {
+__global__ void k_repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride, uint32_t n_cols,
+                                MnRows ms, MnRows md, const uint8_t *new_flags) {
     const uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (j >= (uint64_t)W_dst * n_cols) return;
     const uint32_t w = (uint32_t)(j / n_cols), c = (uint32_t)(j % n_cols);
     const uint32_t sr = src_row ? src_row[w] : w;
     dst[(size_t)w * dst_stride + c] = sr < W_src ? src[(size_t)sr * src_stride + c] : 0u;
+    if (c == 0 && md.task) {  // the row's multi-node columns travel with its first count
+        const bool old = sr < W_src;
+        md.task[w] = old ? ms.task[sr] : HT_EMPTY; md.root[w] = old ? ms.root[sr] : (uint8_t)0; md.flags[w] = old ? ms.flags[sr] : new_flags[w];
+    }
 }
 
 __global__ void k_lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant) {
@@ -256,12 +329,12 @@ hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipSt
     hipLaunchKernelGGL(k_insert_staged, dim3(nblk(st.n)), dim3(TPB), 0, s, t, q, r, st, ctr);
     return hipGetLastError();
 }
-hipError_t release(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {
+hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_rel_claim, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, ctr);
     hipLaunchKernelGGL(k_rel_last_all, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, ctr);
     hipLaunchKernelGGL(k_rel_apply, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, delta, ctr);
-    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, r, last_all, delta);
+    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
 hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr, hipStream_t s) {
@@ -274,9 +347,20 @@ hipError_t rehash(Table from, Table to, uint32_t *ctr, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride,
-                         uint32_t n_cols, hipStream_t s) {
+                         uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s) {
     if (!W_dst || !n_cols) return hipSuccess;
-    hipLaunchKernelGGL(k_repack_counts, dim3(nblk((uint64_t)W_dst * n_cols)), dim3(TPB), 0, s, src, src_stride, W_src, src_row, W_dst, dst, dst_stride, n_cols);
+    hipLaunchKernelGGL(k_repack_counts, dim3(nblk((uint64_t)W_dst * n_cols)), dim3(TPB), 0, s, src, src_stride, W_src, src_row, W_dst, dst, dst_stride, n_cols, ms, md, new_flags);
+    return hipGetLastError();
+}
+hipError_t mn_enter(Table t, Rows r, MnRows m, MnItems it, uint32_t *owner, int check, uint32_t *ctr, hipStream_t s) {
+    if (!it.n || !it.n_wid) return hipSuccess;
+    hipLaunchKernelGGL(k_mn_claim, dim3(nblk(it.n_wid)), dim3(TPB), 0, s, r, it, owner);
+    hipLaunchKernelGGL(k_mn_enter, dim3(nblk(it.n)), dim3(TPB), 0, s, t, r, m, it, owner, check, ctr);
+    return hipGetLastError();
+}
+hipError_t mn_reset_rows(Table t, Rows r, MnRows m, hipStream_t s) {
+    if (!r.W) return hipSuccess;
+    hipLaunchKernelGGL(k_mn_reset_rows, dim3(nblk(r.W)), dim3(TPB), 0, s, t, r, m);
     return hipGetLastError();
 }
 hipError_t lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant, hipStream_t s) {

@@ -75,6 +75,11 @@ struct Ledger {
     DevBuf key, wid, rq, var, prio, claim; uint32_t cap = 0; uint64_t n_live = 0, n_tomb = 0;   // the hash table (cap: a power of two)
     DevBuf key2, wid2, rq2, var2, prio2, claim2;                                                  // ... the target of a rebuild
     DevBuf counts, counts2; uint32_t stride = 0;                                                  // [W x stride] per (worker row, variant slot)
+    // multi-node tasks (assigned.h): [mn task u64 W][mn root u8 W][flags u8 W] beside the count rows, re-packed with them; mn_live = their entries in the table
+    DevBuf mn, mn2; uint64_t mn_live = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)
+    std::vector<uint32_t> var_nodes;                                  // n_nodes per variant slot of the request tables
+    std::vector<uint64_t> pmn_id; std::vector<uint32_t> pmn_rq, pmn_off{0}, pmn_wid;  // a tick's multi-node placements waiting with its records (worker ids, root first)
+    std::vector<uint32_t> mnw_out; std::vector<unsigned char> mnw_cols;              // hqtick_assigned_mn_workers
     DevBuf req, wids, scratch, saved_rq, batch;                                                   // request tables, worker ids in row order, kernel scratch
     // the placement staging K5b writes beside a tick's records (kernels.h: hqk::Stage): [task u64 | rq u32 | row u32 | level u32 | meta u16] x stage_n, in HBM
     DevBuf stage; uint32_t stage_n = 0; bool stage_ordered = false; uint32_t stage_L = 0;
@@ -93,7 +98,7 @@ struct Ledger {
     // what a ledger tick hands the host stages: per worker its distinct (rq, variant) pairs with counts (rebuilt from the count table when it changed)
     std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_var; bool agg_dirty = true;
     void release_all() {
-        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &req, &wids, &scratch, &saved_rq, &batch, &stage, &ctr};
+        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &mn, &mn2, &req, &wids, &scratch, &saved_rq, &batch, &stage, &ctr};
         for (DevBuf *x : b) x->release();
         h_ctr.release(); h_in.release();
     }
@@ -162,7 +167,7 @@ struct hqtick_ctx {
     // results (host)
     std::vector<uint32_t> b_rq, b_size, b_limit, b_cut_off, c_size, c_bl_off, bl_rq, bl_size; std::vector<uint8_t> b_lr, b_blk;
     std::vector<uint32_t> cnt_rq, cnt_worker, cnt_value; std::vector<uint8_t> cnt_variant;
-    std::vector<uint32_t> rec_off, retract_off, red_worker, mn_off, mn_worker; std::vector<uint64_t> rec_task, retract_task, red_task, mn_task, new_free;
+    std::vector<uint32_t> rec_off, retract_off, red_worker, mn_off, mn_worker, mn_rq; std::vector<uint64_t> rec_task, retract_task, red_task, mn_task, new_free;
     std::vector<uint8_t> rec_variant, rec_kind, red_variant, red_kind, q_loaded;
     hqtick_kernel_stats stats{};
     uint32_t tpw_hint = 0;                            // HQTICK_TPW (tuning knob): tasks per wavefront slice
@@ -1379,11 +1384,11 @@ struct TickRun {
 
     void finish(double t1, double t2, double t3) {
         if (!assembled) assemble_host_part();
-        ctx->mn_task.clear(); ctx->mn_off.assign(1, 0); ctx->mn_worker.clear();
+        ctx->mn_task.clear(); ctx->mn_off.assign(1, 0); ctx->mn_worker.clear(); ctx->mn_rq.clear();
         {
             size_t pos = 0;
             for (size_t i = 0; i < cnt.mn_rq.size(); i++) for (auto &set : cnt.mn_sets[i]) {
-                ctx->mn_task.push_back(mn_ids[pos++]);
+                ctx->mn_task.push_back(mn_ids[pos++]); ctx->mn_rq.push_back(cnt.mn_rq[i]);
                 for (uint32_t w : set) ctx->mn_worker.push_back(w);
                 ctx->mn_off.push_back((uint32_t)ctx->mn_worker.size());
             }
@@ -1502,13 +1507,16 @@ void ledger_take_requests(hqtick_ctx *ctx, const hqtick_snapshot *s) {
     if (Q && (!s->rq_variant_off || !s->variant_entry_off)) return;  // (validate() reports it)
     const uint32_t nv = Q ? s->rq_variant_off[Q] : 0, ne = nv ? s->variant_entry_off[nv] : 0;
     if (ne && (!s->entry_resource || !s->entry_kind || !s->entry_amount)) return;
-    if (a.rq_off.size() == (size_t)Q + 1 && a.vent_off.size() == (size_t)nv + 1 && a.ent_res.size() == ne && std::equal(a.rq_off.begin(), a.rq_off.end(), s->rq_variant_off ? s->rq_variant_off : a.rq_off.data()) &&
+    std::vector<uint32_t> vn(nv, 0);
+    if (s->variant_n_nodes) vn.assign(s->variant_n_nodes, s->variant_n_nodes + nv);
+    if (a.rq_off.size() == (size_t)Q + 1 && a.vent_off.size() == (size_t)nv + 1 && a.ent_res.size() == ne && a.var_nodes == vn && std::equal(a.rq_off.begin(), a.rq_off.end(), s->rq_variant_off ? s->rq_variant_off : a.rq_off.data()) &&
         (nv == 0 || std::equal(a.vent_off.begin(), a.vent_off.end(), s->variant_entry_off)) && (ne == 0 || (std::equal(a.ent_res.begin(), a.ent_res.end(), s->entry_resource) &&
         std::equal(a.ent_kind.begin(), a.ent_kind.end(), s->entry_kind) && std::equal(a.ent_amt.begin(), a.ent_amt.end(), s->entry_amount))))
         return;
     a.rq_off.assign(1, 0); if (Q) a.rq_off.assign(s->rq_variant_off, s->rq_variant_off + Q + 1);
     a.vent_off.assign(1, 0); if (nv) a.vent_off.assign(s->variant_entry_off, s->variant_entry_off + nv + 1);
     a.ent_res.assign(s->entry_resource, s->entry_resource + ne); a.ent_kind.assign(s->entry_kind, s->entry_kind + ne); a.ent_amt.assign(s->entry_amount, s->entry_amount + ne);
+    a.var_nodes.swap(vn);
     a.req_dirty = true;
 }
 
@@ -1520,6 +1528,11 @@ hqasg::Rows ledger_rows(hqtick_ctx *ctx) {
     const uint32_t W = ctx->cl_W, R = ctx->cl_R;
     unsigned char *base = ctx->d_cluster.as<unsigned char>();
     return hqasg::Rows{ctx->asg.wids.as<uint32_t>(), W, R, reinterpret_cast<const uint64_t *>(base), reinterpret_cast<uint64_t *>(base + (size_t)W * R * 8), ctx->asg.counts.as<uint32_t>(), ctx->asg.stride};
+}
+// the multi-node columns of W rows in `buf`; live: the uniform argument of the kernels that may skip them
+hqasg::MnRows ledger_mn_rows(const DevBuf &buf, uint32_t W, uint64_t live) {
+    unsigned char *b = buf.as<unsigned char>();
+    return hqasg::MnRows{reinterpret_cast<uint64_t *>(b), b + (size_t)W * 8, b + (size_t)W * 9, (uint32_t)std::min<uint64_t>(live, 0xFFFFFFFFu)};
 }
 hqasg::Req ledger_req(hqtick_ctx *ctx) {
     Ledger &a = ctx->asg;
@@ -1537,7 +1550,7 @@ int ledger_sync_req(hqtick_ctx *ctx) {
         const uint32_t ns = std::max<uint32_t>(16, (nv + 15) & ~15u);
         if (!a.counts2.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
         HQ_HIP(hipMemsetAsync(a.counts2.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
-        if (a.stride) HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W, nullptr, W, a.counts2.as<uint32_t>(), ns, a.stride, ctx->stream));
+        if (a.stride) HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W, nullptr, W, a.counts2.as<uint32_t>(), ns, a.stride, hqasg::MnRows{}, hqasg::MnRows{}, nullptr, ctx->stream));
         std::swap(a.counts, a.counts2); a.stride = ns;
         a.dirty = true;
     }
@@ -1561,6 +1574,14 @@ int ledger_upload_wids(hqtick_ctx *ctx) {
     HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
     return 0;
 }
+// the flags column from the mirror (hqtick_assigned_enable, hqtick_cluster_set_flags: the host is the writer, the mirror is current)
+int ledger_upload_flags(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    const uint32_t W = ctx->cl_W;
+    if (W) HQ_HIP(hipMemcpyAsync(ledger_mn_rows(a.mn, W, 0).flags, ctx->mirror.flags.data(), W, hipMemcpyHostToDevice, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
+    return 0;
+}
 uint32_t *ledger_ctr(hqtick_ctx *ctx) {
     if (!ctx->asg.h_ctr.ensure(64) || !ctx->asg.ctr.ensure(64) || hipMemsetAsync(ctx->asg.ctr.p, 0, 64, ctx->stream) != hipSuccess) return nullptr;
     uint32_t *c = ctx->asg.h_ctr.as<uint32_t>();
@@ -1570,8 +1591,9 @@ uint32_t *ledger_ctr(hqtick_ctx *ctx) {
 // room for `more` entries: live + tombstones + more stay under half the capacity; otherwise the live entries move to a fresh table
 int ledger_reserve(hqtick_ctx *ctx, uint64_t more) {
     Ledger &a = ctx->asg;
-    if (a.cap && (a.n_live + a.n_tomb + more) * 2 <= a.cap) return 0;
-    uint64_t want = 1024; while (want < (a.n_live + more) * 4) want <<= 1;
+    const uint64_t live = a.n_live + a.mn_live;
+    if (a.cap && (live + a.n_tomb + more) * 2 <= a.cap) return 0;
+    uint64_t want = 1024; while (want < (live + more) * 4) want <<= 1;
     if (want > (1ull << 31)) return fail(ctx, HQTICK_E_CAPACITY, "assignment ledger: more than 2^29 entries");
     const uint32_t nc = (uint32_t)want;
     if (!a.key2.ensure((size_t)nc * 8) || !a.wid2.ensure((size_t)nc * 4) || !a.rq2.ensure((size_t)nc * 4) || !a.var2.ensure(nc) || !a.prio2.ensure((size_t)nc * 8) || !a.claim2.ensure((size_t)nc * 4))
@@ -1583,7 +1605,7 @@ int ledger_reserve(hqtick_ctx *ctx, uint64_t more) {
     if (a.cap) HQ_HIP(hqasg::rehash(ledger_table(a), to, a.ctr.as<uint32_t>(), ctx->stream));
     HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (a.cap && (c[hqasg::C_FULL] || c[hqasg::C_DONE] != a.n_live)) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: rebuild lost entries");
+    if (a.cap && (c[hqasg::C_FULL] || c[hqasg::C_DONE] != live)) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: rebuild lost entries");
     std::swap(a.key, a.key2); std::swap(a.wid, a.wid2); std::swap(a.rq, a.rq2); std::swap(a.var, a.var2); std::swap(a.prio, a.prio2); std::swap(a.claim, a.claim2);
     a.cap = nc; a.n_tomb = 0;
     return 0;
@@ -1614,6 +1636,39 @@ int ledger_insert_host(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const ui
     if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
     *fresh = c[hqasg::C_OUT]; *bad = c[hqasg::C_BAD]; *dup = c[hqasg::C_DUP];
     a.n_live += c[hqasg::C_OUT]; a.dirty = true;
+    return 0;
+}
+
+// multi-node placements (task i on the workers wid[off[i] .. off[i + 1]), root first) enter table and rows; prio == nullptr: looked up in the ready-set columns.
+// Few per call and built on the host, like the redirects: they are staged in pinned memory and read in place.
+int ledger_mn_enter(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid, int check,
+                    uint32_t *entered, uint32_t *refused) {
+    Ledger &a = ctx->asg;
+    *entered = *refused = 0;
+    if (!n) return 0;
+    const uint32_t W = ctx->cl_W, n_wid = off[n];
+    if (int rc = ledger_reserve(ctx, n)) return rc;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    const size_t o_p = (size_t)n * 8, o_q = o_p + (size_t)n * 8, o_o = o_q + (size_t)n * 4, o_w = o_o + ((size_t)n + 1) * 4, bytes = o_w + (size_t)n_wid * 4 + 16;
+    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    if (!a.scratch.ensure((size_t)W * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
+    memcpy(h, id, (size_t)n * 8); memcpy(h + o_q, rq, (size_t)n * 4); memcpy(h + o_o, off, ((size_t)n + 1) * 4); memcpy(h + o_w, wid, (size_t)n_wid * 4);
+    if (prio) memcpy(h + o_p, prio, (size_t)n * 8);
+    HQ_HIP(hipMemsetAsync(a.scratch.p, 0xFF, (size_t)W * 4 + 16, ctx->stream));
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    hqasg::MnItems it{};
+    it.n = n; it.n_wid = n_wid; it.id = reinterpret_cast<const uint64_t *>(d); it.prio = prio ? reinterpret_cast<const uint64_t *>(d + o_p) : nullptr;
+    it.rq = reinterpret_cast<const uint32_t *>(d + o_q); it.off = reinterpret_cast<const uint32_t *>(d + o_o); it.wid = reinterpret_cast<const uint32_t *>(d + o_w);
+    it.col_id = ctx->d_tid.as<uint64_t>(); it.col_prio = ctx->d_tprio.as<uint64_t>(); it.col_n = ctx->n_ready;
+    HQ_HIP(hqasg::mn_enter(ledger_table(a), ledger_rows(ctx), ledger_mn_rows(a.mn, W, a.mn_live), it, a.scratch.as<uint32_t>(), check, a.ctr.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
+    *entered = c[hqasg::C_OUT]; *refused = c[hqasg::C_BAD] + c[hqasg::C_DUP];
+    a.mn_live += c[hqasg::C_OUT];
+    if (c[hqasg::C_OUT]) { a.dirty = true; a.flags_dirty = true; }
     return 0;
 }
 
@@ -1648,6 +1703,12 @@ int ledger_apply_tick(hqtick_ctx *ctx) {
         if (int rc = ledger_insert_host(ctx, (uint32_t)a.red_id.size(), a.red_id.data(), a.red_wid.data(), a.red_rq.data(), a.red_var.data(), a.red_prio.data(), 1, 0, col_rq, &fresh, &bad, &dup)) return rc;
         if (bad) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a redirect of the tick could not be entered");
     }
+    if (!a.pmn_id.empty()) {  // the multi-node placements (mapping.rs:133-154): the solver took free workers, so nothing is checked twice
+        uint32_t entered = 0, refused = 0;
+        if (int rc = ledger_mn_enter(ctx, (uint32_t)a.pmn_id.size(), a.pmn_id.data(), a.pmn_rq.data(), nullptr, a.pmn_off.data(), a.pmn_wid.data(), 0, &entered, &refused)) return rc;
+        if (refused || entered != a.pmn_id.size()) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a multi-node placement of the tick could not be entered");
+        a.pmn_id.clear();
+    }
     // free rows: the tick's new_free (Worker::insert_sn_task / remove_sn_task of mapping.rs, computed by the tick itself)
     if (W && ctx->cl_R) {
         unsigned char *base = ctx->d_cluster.as<unsigned char>();
@@ -1671,14 +1732,19 @@ int ledger_guard(hqtick_ctx *ctx) {
     return 0;
 }
 // the count rows follow a membership change: row w of the new set = old row src[w] (>= W_old: a new worker, zero)
-int ledger_repack(hqtick_ctx *ctx, const std::vector<uint32_t> &src, uint32_t W_old) {
+// The multi-node columns move in the same launch; add_flags: the HQ_WORKER_* bytes of the new workers (nullptr: fresh single-node workers)
+int ledger_repack(hqtick_ctx *ctx, const std::vector<uint32_t> &src, uint32_t W_old, const uint8_t *add_flags) {
     Ledger &a = ctx->asg;
     const uint32_t W_new = (uint32_t)src.size();
-    if (!a.counts2.ensure((size_t)W_new * a.stride * 4 + 64) || !a.batch.ensure((size_t)W_new * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
-    if (W_new) HQ_HIP(hipMemcpyAsync(a.batch.p, src.data(), (size_t)W_new * 4, hipMemcpyHostToDevice, ctx->stream));
-    HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W_old, a.batch.as<uint32_t>(), W_new, a.counts2.as<uint32_t>(), a.stride, a.stride, ctx->stream));
+    if (!a.counts2.ensure((size_t)W_new * a.stride * 4 + 64) || !a.batch.ensure((size_t)W_new * 5 + 16) || !a.mn2.ensure((size_t)W_new * 10 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
+    std::vector<unsigned char> hb((size_t)W_new * 5 + 16, 0);  // [src row u32 W_new][flags of the new rows u8 W_new]: one copy
+    if (W_new) memcpy(hb.data(), src.data(), (size_t)W_new * 4);
+    for (uint32_t w = 0; w < W_new; w++) hb[(size_t)W_new * 4 + w] = src[w] >= W_old ? (add_flags ? add_flags[src[w] - W_old] : (uint8_t)HQ_WORKER_SN) : (uint8_t)0;
+    HQ_HIP(hipMemcpyAsync(a.batch.p, hb.data(), hb.size(), hipMemcpyHostToDevice, ctx->stream));
+    HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W_old, a.batch.as<uint32_t>(), W_new, a.counts2.as<uint32_t>(), a.stride, a.stride,
+                                ledger_mn_rows(a.mn, W_old, a.mn_live), ledger_mn_rows(a.mn2, W_new, a.mn_live), a.batch.as<uint8_t>() + (size_t)W_new * 4, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
-    std::swap(a.counts, a.counts2);
+    std::swap(a.counts, a.counts2); std::swap(a.mn, a.mn2);
     a.dirty = true;
     return 0;
 }
@@ -1687,7 +1753,7 @@ int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
     Ledger &a = ctx->asg;
     std::vector<uint32_t> lost(worker_id, worker_id + n);
     std::sort(lost.begin(), lost.end());
-    const uint64_t cap_out = a.n_live + 1;
+    const uint64_t cap_out = a.n_live + a.mn_live + 1;
     const size_t o_l = 0, o_id = ((size_t)n * 4 + 7) & ~(size_t)7, o_p = o_id + cap_out * 8, o_q = o_p + cap_out * 8, bytes = o_q + cap_out * 4 + 16;
     if (!a.scratch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
     unsigned char *d = a.scratch.as<unsigned char>();
@@ -1699,7 +1765,12 @@ int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
     HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     const uint32_t k = c[hqasg::C_OUT];
-    if (k > a.n_live || k >= cap_out) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
+    const uint32_t k_mn = c[hqasg::C_MN];
+    if (k >= cap_out || k_mn > k || k_mn > a.mn_live || k - k_mn > a.n_live) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
+    if (k_mn) {  // a lost ROOT (reactor.rs:107-128): the task's other rows are free single-node workers again, before the rows are re-packed
+        HQ_HIP(hqasg::mn_reset_rows(ledger_table(a), ledger_rows(ctx), ledger_mn_rows(a.mn, ctx->cl_W, a.mn_live), ctx->stream));
+        a.flags_dirty = true;
+    }
     std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k);
     if (k) {
         HQ_HIP(hipMemcpy(id.data(), d + o_id, (size_t)k * 8, hipMemcpyDeviceToHost));
@@ -1710,7 +1781,7 @@ int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
     for (uint32_t i = 0; i < k; i++) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return id[x] < id[y]; });
     for (uint32_t i : ord) { a.rq_task.push_back(id[i]); a.rq_prio.push_back(pr[i]); a.rq_rq.push_back(rq[i]); }
-    a.n_live -= k; a.n_tomb += k; a.dirty = true;
+    a.n_live -= k - k_mn; a.mn_live -= k_mn; a.n_tomb += k; a.dirty = true;
     return 0;
 }
 
@@ -1724,8 +1795,12 @@ int ledger_sync_mirror(hqtick_ctx *ctx) {
         unsigned char *base = ctx->d_cluster.as<unsigned char>();
         if (W && R) HQ_HIP(hipMemcpyAsync(ctx->mirror.free_.data(), base + (size_t)W * R * 8, (size_t)W * R * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (W && a.stride) HQ_HIP(hipMemcpyAsync(a.h_counts.data(), a.counts.p, (size_t)W * a.stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (W && a.flags_dirty) {  // a ledger call moved SN bits (set_mn_task / reset_mn_task): the tick reads worker_flags from the mirror
+            ctx->mirror.flags.resize(W);
+            HQ_HIP(hipMemcpyAsync(ctx->mirror.flags.data(), ledger_mn_rows(a.mn, W, 0).flags, W, hipMemcpyDeviceToHost, ctx->stream));
+        }
         HQ_HIP(hipStreamSynchronize(ctx->stream));
-        a.dirty = false; a.agg_dirty = true;
+        a.dirty = false; a.agg_dirty = true; a.flags_dirty = false;
     }
     if (!a.agg_dirty) return 0;
     // O(W x variant slots), not O(running tasks): the count table is what GapCache and Worker::is_free need
@@ -1852,6 +1927,12 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
                     for (uint32_t j = s->prefill_off[q]; j < s->prefill_off[q + 1]; j++) if (s->prefill_task[j] == out->redirect_task[i]) { rq = q; pr = s->prefill_priority[q]; break; }
             a.red_id.push_back(out->redirect_task[i]); a.red_wid.push_back(out->redirect_worker[i] < W ? s->worker_id[out->redirect_worker[i]] : HQ_NO_WORKER);
             a.red_rq.push_back(rq); a.red_var.push_back(out->redirect_variant[i]); a.red_prio.push_back(pr);
+        }
+        a.pmn_id.clear(); a.pmn_rq.clear(); a.pmn_off.assign(1, 0); a.pmn_wid.clear();
+        for (uint32_t i = 0; i < out->n_mn && i < ctx->mn_rq.size(); i++) {
+            a.pmn_id.push_back(out->mn_task[i]); a.pmn_rq.push_back(ctx->mn_rq[i]);
+            for (uint32_t j = out->mn_worker_off[i]; j < out->mn_worker_off[i + 1]; j++) a.pmn_wid.push_back(out->mn_worker[j] < W ? s->worker_id[out->mn_worker[j]] : HQ_NO_WORKER);
+            a.pmn_off.push_back((uint32_t)a.pmn_wid.size());
         }
         const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
         a.pend_saved = in_tick && s->n_retracting != 0; a.pending = true;  // (the column copy is taken only for the redirects of Retracting tasks)
@@ -2425,7 +2506,7 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
     if (remaining_ns) rem.assign(remaining_ns, remaining_ns + n);
     if (int rc = ledger_guard(ctx)) return rc;
     if (int rc = cluster_repack(ctx, src, n, total_rows, free_rows, rem.data())) return rc;
-    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W)) return rc; }
+    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W, flags)) return rc; }
     m.id.insert(m.id.end(), worker_id, worker_id + n);
     m.total.insert(m.total.end(), total_rows, total_rows + (size_t)n * R); m.free_.insert(m.free_.end(), free_rows, free_rows + (size_t)n * R);
     m.rem.insert(m.rem.end(), rem.begin(), rem.end());
@@ -2457,7 +2538,7 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     ctx->asg.rq_task.clear(); ctx->asg.rq_rq.clear(); ctx->asg.rq_prio.clear();
     if (ctx->asg.on) { if (int rc = ledger_evict(ctx, n, worker_id)) return rc; }  // on_remove_worker: the lost workers' tasks leave the ledger (reactor.rs:64-147)
     if (int rc = cluster_repack(ctx, src, 0, nullptr, nullptr, nullptr)) return rc;
-    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W)) return rc; }
+    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W, nullptr)) return rc; }
     uint32_t k = 0;
     for (uint32_t w = 0; w < W; w++) {
         if (gone[w]) { m.blocked.erase(m.id[w]); continue; }
@@ -2528,6 +2609,45 @@ int hqtick_cluster_workers(const hqtick_ctx *ctx, uint32_t *n_workers, const uin
     return 0;
 }
 
+int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint8_t *flags) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags without hqtick_cluster_upload");
+    if (int rc = ledger_guard(ctx)) return rc;
+    if (n == 0) return 0;
+    if (!worker_id || !flags) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: null array");
+    hqtick_ctx::ClusterMirror &m = ctx->mirror;
+    if (ctx->asg.on) {  // the ledger may have moved SN bits since the mirror was read
+        if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
+        if (int rc = ledger_sync_mirror(ctx)) return rc;
+    }
+    const uint32_t W = (uint32_t)m.id.size();
+    std::vector<uint32_t> row(n);
+    std::vector<uint8_t> seen(W, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        auto it = std::lower_bound(m.id.begin(), m.id.end(), worker_id[i]);
+        if (it == m.id.end() || *it != worker_id[i] || seen[it - m.id.begin()]) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: unknown (or repeated) worker id");
+        row[i] = (uint32_t)(it - m.id.begin()); seen[row[i]] = 1;
+        if (flags[i] & ~(uint8_t)(HQ_WORKER_SN | HQ_WORKER_STOPPING)) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: undefined flag bits");
+        if (ctx->asg.on && ((flags[i] ^ m.flags[row[i]]) & HQ_WORKER_SN))
+            return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: with the assignment ledger on, HQ_WORKER_SN follows the ledger's multi-node tasks");
+    }
+    for (uint32_t i = 0; i < n; i++) m.flags[row[i]] = flags[i];
+    if (ctx->asg.on) return ledger_upload_flags(ctx);
+    return 0;
+}
+
+int hqtick_cluster_worker_flags(const hqtick_ctx *cctx, uint32_t *n_workers, const uint8_t **flags) {
+    if (!cctx || !cctx->mirror.valid) return HQTICK_E_INVALID;
+    hqtick_ctx *ctx = const_cast<hqtick_ctx *>(cctx);  // (the mirror is a cache of the ledger's column: reading it may refresh it)
+    if (ctx->asg.on && ctx->asg.dirty) {
+        if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
+        if (int rc = ledger_sync_mirror(ctx)) return rc;
+    }
+    if (n_workers) *n_workers = (uint32_t)ctx->mirror.flags.size();
+    if (flags) *flags = ctx->mirror.flags.data();
+    return 0;
+}
+
 int hqtick_retracting_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id) {
     if (!ctx) return HQTICK_E_INVALID;
     if (n && (!task_id || !worker_id)) return fail(ctx, HQTICK_E_INVALID, "hqtick_retracting_add: null array");
@@ -2573,6 +2693,12 @@ int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id,
     const uint32_t W = ctx->cl_W;
     if (!a.counts.ensure((size_t)W * a.stride * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
     HQ_HIP(hipMemsetAsync(a.counts.p, 0, (size_t)W * a.stride * 4 + 64, ctx->stream));
+    // the multi-node columns: no row holds a task, the flags byte is the mirror's (a worker uploaded without its SN bit waits for hqtick_assigned_add_mn)
+    a.mn_live = 0; a.flags_dirty = false; a.pmn_id.clear();
+    if (!a.mn.ensure((size_t)W * 10 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment rows");
+    HQ_HIP(hipMemsetAsync(a.mn.p, 0xFF, (size_t)W * 8, ctx->stream));
+    HQ_HIP(hipMemsetAsync(a.mn.as<unsigned char>() + (size_t)W * 8, 0, (size_t)W * 2 + 64, ctx->stream));
+    if (int rc = ledger_upload_flags(ctx)) return rc;
     if (int rc = ledger_upload_wids(ctx)) return rc;
     uint32_t fresh = 0, bad = 0, dup = 0;
     if (int rc = ledger_insert_host(ctx, n, task_id, worker_id, rq, variant, priority, 0, 0, nullptr, &fresh, &bad, &dup)) return rc;
@@ -2626,14 +2752,66 @@ int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id
     HQ_HIP(hipMemcpyAsync(d, a.h_in.p, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     uint32_t *c = ledger_ctr(ctx);
     if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    HQ_HIP(hqasg::release(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<uint32_t *>(d + o_pos),
+    HQ_HIP(hqasg::release(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), ledger_mn_rows(a.mn, W, a.mn_live), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<uint32_t *>(d + o_pos),
                           reinterpret_cast<uint32_t *>(d + o_la), reinterpret_cast<uint64_t *>(d + o_dl), a.ctr.as<uint32_t>(), ctx->stream));
     HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
-    const uint32_t done = c[hqasg::C_DONE];
-    a.n_live -= done; a.n_tomb += done; a.last_unknown = (uint64_t)c[hqasg::C_UNKNOWN] + c[hqasg::C_DUP]; a.dirty = true;  // (the others of the batch are released either way)
+    const uint32_t done = c[hqasg::C_DONE], done_mn = std::min(c[hqasg::C_MN], done);  // (a multi-node task counts once, its rows were reset by the row pass)
+    if (done_mn) a.flags_dirty = true;
+    a.n_live -= done - done_mn; a.mn_live -= std::min<uint64_t>(done_mn, a.mn_live); a.n_tomb += done; a.last_unknown = (uint64_t)c[hqasg::C_UNKNOWN] + c[hqasg::C_DUP]; a.dirty = true;  // (the others of the batch are released either way)
     if (c[hqasg::C_BAD]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
     return (int)done;
+}
+
+int hqtick_assigned_add_mn(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (int rc = ledger_pre(ctx)) return rc;
+    if (n && (!task_id || !rq || !priority || !worker_off)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
+    Ledger &a = ctx->asg;
+    a.last_unknown = 0;
+    if (!n) return 0;
+    if (worker_off[0] != 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: worker_off[0] must be 0");
+    for (uint32_t i = 0; i < n; i++) if (worker_off[i + 1] < worker_off[i]) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: worker_off must not descend");
+    if (worker_off[n] && !worker_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: null array");
+    // a task whose request is not a multi-node one (n_nodes == 0, or unknown) never reaches the device
+    std::vector<uint64_t> id, pr; std::vector<uint32_t> q, off{0}, wid;
+    uint64_t skipped = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool mn_rq = (size_t)rq[i] + 1 < a.rq_off.size() && a.rq_off[rq[i]] < a.rq_off[rq[i] + 1] && a.rq_off[rq[i]] < a.var_nodes.size() && a.var_nodes[a.rq_off[rq[i]]] > 0;
+        if (!mn_rq || worker_off[i] == worker_off[i + 1]) { skipped++; continue; }
+        id.push_back(task_id[i]); pr.push_back(priority[i]); q.push_back(rq[i]);
+        wid.insert(wid.end(), worker_id + worker_off[i], worker_id + worker_off[i + 1]); off.push_back((uint32_t)wid.size());
+    }
+    uint32_t entered = 0, refused = 0;
+    if (int rc = ledger_mn_enter(ctx, (uint32_t)id.size(), id.data(), q.data(), pr.data(), off.data(), wid.data(), 1, &entered, &refused)) return rc;
+    a.last_unknown = skipped + refused;
+    return (int)entered;
+}
+
+uint64_t hqtick_assigned_mn_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on ? ctx->asg.mn_live : 0; }
+
+int hqtick_assigned_mn_workers(hqtick_ctx *ctx, uint64_t task_id, uint32_t *n, const uint32_t **worker_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
+    Ledger &a = ctx->asg;
+    a.mnw_out.clear();
+    const uint32_t W = ctx->cl_W;
+    if (a.mn_live && W && task_id < hqasg::HT_TOMB) {  // an accessor for tests and restore: the two columns come back, 9 B per row
+        HQ_HIP(hipSetDevice(ctx->device));
+        a.mnw_cols.resize((size_t)W * 9);
+        HQ_HIP(hipMemcpyAsync(a.mnw_cols.data(), a.mn.p, (size_t)W * 9, hipMemcpyDeviceToHost, ctx->stream));
+        HQ_HIP(hipStreamSynchronize(ctx->stream));
+        const unsigned char *root = a.mnw_cols.data() + (size_t)W * 8;
+        for (int pass = 0; pass < 2; pass++)  // the root first, the others in ascending id (= row) order
+            for (uint32_t w = 0; w < W; w++) {
+                uint64_t t; memcpy(&t, a.mnw_cols.data() + (size_t)w * 8, 8);
+                if (t == task_id && (root[w] != 0) == (pass == 0)) a.mnw_out.push_back(ctx->mirror.id[w]);
+            }
+    }
+    if (n) *n = (uint32_t)a.mnw_out.size();
+    if (worker_id) *worker_id = a.mnw_out.data();
+    return 0;
 }
 
 uint64_t hqtick_assigned_last_unknown(const hqtick_ctx *ctx) { return ctx ? ctx->asg.last_unknown : 0; }

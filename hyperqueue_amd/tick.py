@@ -226,6 +226,22 @@ class Tick:
         self._chk(self._lib.hqtick_cluster_workers(self._ctx, C.byref(n), C.byref(p)))
         return abi._np(p, n.value, np.uint32).copy() if n.value else np.zeros(0, np.uint32)
 
+    def cluster_set_flags(self, worker_id, flags):
+        """the HQ_WORKER_SN / HQ_WORKER_STOPPING bits of the listed resident workers, replaced (set_stop; set_mn_task / reset_mn_task without the ledger)"""
+        ids = np.ascontiguousarray(worker_id, np.uint32); fl = np.ascontiguousarray(flags, np.uint8)
+        assert len(ids) == len(fl)
+        f = self._lib.hqtick_cluster_set_flags
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u32p, abi.u8p]
+        self._chk(f(self._ctx, len(ids), ids.ctypes.data_as(abi.u32p), fl.ctypes.data_as(abi.u8p)))
+
+    def cluster_worker_flags(self) -> np.ndarray:
+        """the HQ_WORKER_* flags in row order"""
+        n = C.c_uint32(); p = abi.u8p()
+        f = self._lib.hqtick_cluster_worker_flags
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u8p)]
+        self._chk(f(self._ctx, C.byref(n), C.byref(p)))
+        return abi._np(p, n.value, np.uint8).copy() if n.value else np.zeros(0, np.uint8)
+
     def retracting_add(self, task_id, worker_id):
         """process_retracted outside a tick (ABI 7): tasks back in their queue as Retracting{worker id}"""
         t = np.ascontiguousarray(task_id, np.uint64); w = np.ascontiguousarray(worker_id, np.uint32)
@@ -283,6 +299,31 @@ class Tick:
         f = self._lib.hqtick_assigned_release
         f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p]
         return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p)))
+
+    def assigned_add_mn(self, entries) -> int:
+        """multi-node tasks seeded outside a tick: [(task, rq, priority, [worker ids, root first])] -> number entered"""
+        entries = list(entries)
+        t = np.ascontiguousarray([e[0] for e in entries], np.uint64); q = np.ascontiguousarray([e[1] for e in entries], np.uint32)
+        p = np.ascontiguousarray([e[2] for e in entries], np.uint64)
+        off = np.zeros(len(entries) + 1, np.uint32); off[1:] = np.cumsum([len(e[3]) for e in entries], dtype=np.uint64)
+        w = np.ascontiguousarray([x for e in entries for x in e[3]], np.uint32)
+        f = self._lib.hqtick_assigned_add_mn
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u64p, abi.u32p, abi.u32p]
+        return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), q.ctypes.data_as(abi.u32p), p.ctypes.data_as(abi.u64p), off.ctypes.data_as(abi.u32p),
+                           w.ctypes.data_as(abi.u32p)))
+
+    def assigned_mn_count(self) -> int:
+        f = self._lib.hqtick_assigned_mn_count
+        f.argtypes = [C.c_void_p]; f.restype = C.c_uint64
+        return int(f(self._ctx))
+
+    def assigned_mn_workers(self, task_id: int) -> list:
+        """the multi-node task's current worker ids, root first ([]: not a multi-node task of the ledger)"""
+        n = C.c_uint32(); p = abi.u32p()
+        f = self._lib.hqtick_assigned_mn_workers
+        f.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(abi.u32p)]
+        self._chk(f(self._ctx, int(task_id), C.byref(n), C.byref(p)))
+        return abi._np(p, n.value, np.uint32).tolist() if n.value else []
 
     def assigned_last_unknown(self) -> int:
         f = self._lib.hqtick_assigned_last_unknown

@@ -411,6 +411,13 @@ int hqtick_cluster_drop(hqtick_ctx *ctx);
  *                                  task_reject adds a pair (reactor.rs:365-445), EnableRequest removes it (request_enabled, reactor.rs:447-460),
  *                                  n = 0 clears.
  *   hqtick_cluster_workers         the current ids in row order (valid until the next membership call).
+ *   hqtick_cluster_set_flags       the HQ_WORKER_SN and HQ_WORKER_STOPPING bits of the listed resident workers, replaced: Worker::set_stop
+ *                                  (server/worker.rs:312-314) and, for a host without the assignment ledger, set_mn_task / reset_mn_task (:160-175).
+ *                                  Unknown ids, an id listed twice or a bit outside the two defined ones are HQTICK_E_INVALID and change nothing.  With the
+ *                                  assignment ledger on the SN bit belongs to the ledger (it follows the multi-node tasks): a call that would change a
+ *                                  worker's SN bit is HQTICK_E_INVALID; STOPPING may still change.  Refused while a placement waits for its consume, like the
+ *                                  other membership calls.  Works on sharded and replica contexts: every replica receives the same call.
+ *   hqtick_cluster_worker_flags    the flags in row order (valid until the next call on the context).
  * One re-pack kernel per membership call (rows read from HBM, new rows from pinned staging); nothing is re-uploaded.
  * A tick whose snapshot has worker_id == NULL takes the WHOLE worker side from the library: ids, total / free rows (as kept current by
  * hqtick_cluster_update_workers), remaining lifetime, min_utilization, flags, groups and the blocked pairs.  Say so with n_workers = HQ_WORKERS_RESIDENT: such a
@@ -424,6 +431,8 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
 int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id);
 int hqtick_cluster_set_blocked(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, const uint32_t *rq, const uint8_t *variant);
 int hqtick_cluster_workers(const hqtick_ctx *ctx, uint32_t *n_workers, const uint32_t **worker_id);
+int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint8_t *flags);
+int hqtick_cluster_worker_flags(const hqtick_ctx *ctx, uint32_t *n_workers, const uint8_t **flags);
 /*
  * Retracting tasks as deltas (ABI 7; on_retract_response, process_retracted — server/reactor.rs:34-62,462-508).  The table of tasks in state
  * Retracting{worker} — with their scheduler_state.redirects entry — can live in the library instead of travelling in every snapshot:
@@ -490,7 +499,25 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  * is consumed, ledger and membership calls are HQTICK_E_INVALID; a tick that is not consumed (any ready-set or graph delta, another tick) is abandoned with
  * its selection and never enters.  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
  * tasks have left the ready set, so the host uploads the worker set and enables the ledger again from its own view.
- * PREFILL records, prefill sets and multi-node tasks stay the host's.  hqtick_cluster_update_workers still works (remaining lifetime, corrections).
+ * PREFILL records and prefill sets stay the host's.  hqtick_cluster_update_workers still works (remaining lifetime, corrections).
+ * Multi-node tasks (n_nodes > 0; Worker::mn_task, server/worker.rs:134-175) are the ledger's as well: per worker row the task it holds and whether it is
+ * the root, per task one entry (root worker id, rq, priority).  A tick's multi-node placements (result.mn_*) enter with its ASSIGN records, at the same
+ * moment (an abandoned or failed tick enters nothing): every listed worker loses HQ_WORKER_SN and records the task, the first as root (mapping.rs:133-154);
+ * free rows stay as they are.  The next tick sees those workers as the reference does: no single-node placement on them.
+ *   hqtick_assigned_add_mn     seed multi-node tasks after hqtick_assigned_enable (restore, tests): task i runs on worker_id[worker_off[i] .. worker_off[i + 1]),
+ *                              root first.  A listed worker is either free (SN bit, nothing in the ledger, not STOPPING: Worker::is_free) or was uploaded
+ *                              with the SN bit clear and holds no task yet.  A task that names an unknown worker, a busy or stopping one, a worker twice or
+ *                              one an earlier task of the call took, whose id is in the ledger already or whose rq is not a multi-node request, is counted
+ *                              (hqtick_assigned_last_unknown) and enters nothing.  Returns the number of tasks entered.
+ *   hqtick_assigned_release    takes multi-node ids in the same batch: every row still holding the task gets reset_mn_task (worker.rs:172-175,
+ *                              reactor.rs:357-363: SN bit set, free row = total row), the entry leaves, the return value counts the task once.
+ *   hqtick_cluster_remove_workers  on_remove_worker (reactor.rs:107-128): a lost ROOT resets the task's other rows and the task is among
+ *                              hqtick_cluster_last_requeued (and back in the resident ready set); a lost NON-ROOT just leaves, the task keeps its
+ *                              remaining workers.  The outcome does not depend on the order of the ids within the call.
+ *   hqtick_assigned_mn_count   multi-node tasks in the ledger (hqtick_assigned_count stays the number of single-node entries).
+ *   hqtick_assigned_mn_workers the task's current workers, root first, the others by ascending id (valid until the next call on ctx); *n = 0: not a
+ *                              multi-node task of the ledger.  hqtick_assigned_lookup of such an id answers with the root's worker id and variant 0xFF.
+ * Not covered: a worker that takes a multi-node task while it still holds prefilled tasks (set_mn_task drops the set in the reference).
  * The ledger does not depend on the form in which the records leave the device: the mapping kernel stages, beside every record it emits, the entry the
  * ledger stores (task, request, variant, worker row, priority level) in HBM, and the placement enters from there.  So the ledger works with plain records,
  * with HQTICK_FLAG_COMPACT_RECORDS / _DELTA16, and with a record sink (hqtick_set_record_sink, set before or after hqtick_assigned_enable, removed again
@@ -511,6 +538,10 @@ uint64_t hqtick_assigned_last_host_bytes(const hqtick_ctx *ctx);
 int hqtick_assigned_lookup(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint32_t *worker_id, uint8_t *variant);
 int hqtick_assigned_free_rows(hqtick_ctx *ctx, uint32_t *n_workers, const uint64_t **free_rows);
 int hqtick_cluster_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority);
+int hqtick_assigned_add_mn(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off,
+                           const uint32_t *worker_id);
+uint64_t hqtick_assigned_mn_count(const hqtick_ctx *ctx);
+int hqtick_assigned_mn_workers(hqtick_ctx *ctx, uint64_t task_id, uint32_t *n, const uint32_t **worker_id);
 
 /*
  * Device-resident dependency graph (BASELINE config 5): the `Waiting{unfinished_deps}` counters and the consumer

@@ -2,10 +2,13 @@
 protocol (context B: the host keeps the free rows, sends the rows every start / finish touched, flattens the assigned CSR per tick).  Prints one JSON line:
 per-step wall clock of both loops (B's host bookkeeping included), the release call for the previous step's tasks, and the ledger's tick-side apply.
 
-    python tools/assigned_probe.py [--steps 20] [--tasks 1000000] [--workers 1024] [--records plain|compact|delta16|sink]
+    python tools/assigned_probe.py [--steps 20] [--tasks 1000000] [--workers 1024] [--records plain|compact|delta16|sink] [--mn K]
 
 --records: the form in which context A's records leave the device (the ledger is fed from the mapping kernel's staging in HBM in every one of them; `sink`:
 a device record sink, read back outside the timed part only to compare).  `ledger_host_bytes` is hqtick_assigned_last_host_bytes after the last tick.
+--mn K: K two-node tasks run on the last 2 K workers throughout: every step releases them in the same batch as the single-node ids and seeds K new ones
+on the same workers (hqtick_assigned_add_mn), so the release's row pass takes its multi-node branch; context B keeps those workers' SN bit clear with
+hqtick_cluster_set_flags.  0 (the default) is the workload as it always was: no multi-node request, none of the new calls.
 """
 import argparse
 import dataclasses
@@ -40,10 +43,15 @@ def main():
     ap.add_argument("--workers", type=int, default=1024)
     ap.add_argument("--add", type=int, default=188_000)
     ap.add_argument("--records", choices=["plain", "compact", "delta16", "sink"], default="plain")
+    ap.add_argument("--mn", type=int, default=0)
     args = ap.parse_args()
     snap = workloads.make_steady("c3p", seed=3, n_tasks=args.tasks, n_workers=args.workers)
     W, R = len(snap.worker_id), snap.n_resources
     snap = dataclasses.replace(snap, assigned=[[] for _ in range(W)], worker_free=np.array(snap.worker_total, np.uint64), _keep=[])
+    n_sn_rq = len(snap.requests)
+    if args.mn:  # one two-node request class behind the others (no task of the ready set has it)
+        assert 2 * args.mn < W
+        snap = dataclasses.replace(snap, requests=list(snap.requests) + [[dict(entries=[(0, abi.HQ_ENTRY_AMOUNT, 10_000)], n_nodes=2, min_time_ns=0, weight=10_000)]], _keep=[])
     ent = [[[(int(r), int(k), int(a)) for (r, k, a) in v["entries"]] for v in rq] for rq in snap.requests]
     cfg = abi.make_config(time_limit_s=20.0, flags=abi.HQTICK_FLAG_CONSUME_IN_TICK | abi.HQTICK_FLAG_NO_KERNEL_TIMING)
     form = {"plain": 0, "compact": abi.HQTICK_FLAG_COMPACT_RECORDS, "delta16": abi.HQTICK_FLAG_COMPACT_RECORDS | abi.HQTICK_FLAG_COMPACT_DELTA16, "sink": 0}[args.records]
@@ -51,6 +59,10 @@ def main():
     for t in (a, b):
         t.cluster_upload(snap); t.upload_ready(snap.task_id, snap.task_priority, snap.task_rq)
     a.assigned_enable([])
+    mn_w = [[int(snap.worker_id[W - 2 * args.mn + 2 * i]), int(snap.worker_id[W - 2 * args.mn + 2 * i + 1])] for i in range(args.mn)]
+    mn_ids, mn_next, tmn = [], 1 << 60, []
+    if args.mn:
+        b.cluster_set_flags([w for ws in mn_w for w in ws], [0] * (2 * args.mn))
     sink = None
     if args.records == "sink":
         from hyperqueue_amd.sharded import sink_layout
@@ -64,12 +76,16 @@ def main():
     ta, tb, trel, ttick_a = [], [], [], []
     for step in range(args.steps):
         add = np.arange(next_id, next_id + args.add, dtype=np.uint64); next_id += args.add
-        prio = np.zeros(len(add), np.uint64); rqs = (np.arange(len(add)) % len(snap.requests)).astype(np.uint32)
+        prio = np.zeros(len(add), np.uint64); rqs = (np.arange(len(add)) % n_sn_rq).astype(np.uint32)
         rq_of.update(zip(add.tolist(), rqs.tolist()))
         # A: release -> add -> tick
         t0 = time.perf_counter()
         if prev_a:
-            t1 = time.perf_counter(); a.assigned_release(prev_a); trel.append(time.perf_counter() - t1)
+            t1 = time.perf_counter(); a.assigned_release(prev_a + mn_ids); trel.append(time.perf_counter() - t1)
+        if args.mn:
+            mn_ids = list(range(mn_next, mn_next + args.mn)); mn_next += args.mn
+            t1 = time.perf_counter(); n_in = a.assigned_add_mn([(tid, n_sn_rq, 0, ws) for tid, ws in zip(mn_ids, mn_w)]); tmn.append(time.perf_counter() - t1)
+            assert n_in == args.mn and a.assigned_mn_count() == args.mn
         a.ready_add(add, prio, rqs)
         t2 = time.perf_counter(); ra = _resident(a, snap); ttick_a.append(time.perf_counter() - t2)
         ta.append(time.perf_counter() - t0)
@@ -112,7 +128,8 @@ def main():
     med = lambda x: round(float(np.median(x[2:] if len(x) > 4 else x)) * 1e6, 1)  # noqa: E731
     print(json.dumps({"steps": args.steps, "tasks": args.tasks, "workers": W, "added_per_step": args.add, "released_per_step": len(prev_a),
                       "step_us_ledger": med(ta), "step_us_row_deltas": med(tb), "release_call_us": med(trel), "tick_call_us_ledger": med(ttick_a),
-                      "running": a.assigned_count(), "records": args.records, "ledger_host_bytes": a.assigned_last_host_bytes()}))
+                      "running": a.assigned_count(), "records": args.records, "ledger_host_bytes": a.assigned_last_host_bytes(),
+                      **({"mn_tasks": args.mn, "add_mn_call_us": med(tmn)} if args.mn else {})}))
     a.close(); b.close()
 
 
