@@ -445,6 +445,26 @@ class SchedEnv:
         self.start_task(tid, 0)
         return tid
 
+    def start_prefilled_task(self, tid: int, variant: int = 0):
+        """on_task_update(Running) of a Prefilled task = task_from_prefilled_to_started  server/worker.rs:212-221: the task leaves the worker's prefilled set
+        and its queue's prefill set (remove_prefill_task, mapping.rs:85-88) and is a running single-node task of that worker with the variant it started."""
+        t = self.tasks[tid]
+        assert t.state == PREFILLED
+        w = self.workers[t.worker]
+        w.prefilled_tasks.discard(tid)
+        self.prefill[t.rq][1].remove(tid)
+        t.state, t.rv = RUNNING, variant
+        self._remove(w, t.rq, variant)
+        w.assigned_tasks.add(tid)
+
+    def cancel_prefilled_task(self, tid: int):
+        """on_cancel_tasks of a Prefilled task (server/reactor.rs:762-766): remove_prefill_task, and the task is gone"""
+        t = self.tasks[tid]
+        assert t.state == PREFILLED
+        self.workers[t.worker].prefilled_tasks.discard(tid)
+        self.prefill[t.rq][1].remove(tid)
+        t.state, t.worker = FINISHED, None
+
     def finish_task(self, tid: int, wid: int):
         """on_task_update(Finished) restricted to what the tick observes  server/reactor.rs:510-590."""
         t = self.tasks[tid]

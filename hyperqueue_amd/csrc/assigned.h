@@ -13,6 +13,11 @@
 //   it — a request has fewer than 255 variants).  It counts in no (row, slot) and touches no free row while it runs.
 //   Invariant: a row's mn task is a live MN_VARIANT entry of the table.  Release and eviction tombstone the entry first; the row pass that follows resets
 //   every row whose task is no longer found (reset_mn_task: SN bit set, free row = total row, columns cleared).
+//   prefilled tasks (SingleNodeTaskAssignment::prefilled_tasks, opt-in: hqtick_assigned_track_prefilled): one table entry per task, key = task id, worker = the
+//   worker it is prefilled on, rq, priority, variant = PF_VARIANT (0xFE: with tracking on a request has fewer than 254 variants).  It counts in no (row, slot)
+//   and touches no free row.  pf u32 [W x pf_stride]: prefilled tasks per (worker row, request), a second table re-packed by the count rows' launch.
+//   Invariant: pf[w][q] = live PF_VARIANT entries of worker w and request q.  Rows::pf == nullptr (tracking off): no kernel reads or writes the table and a
+//   PREFILL record of the staging is skipped, as before.
 // Everything here is integer work bound by HBM latency; no MFMA.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +30,7 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint64_t HT_EMPTY = ~0ull, HT_TOMB = ~0ull - 1;  // task ids must be below HT_TOMB
 constexpr uint32_t RQ_LOOKUP = 0xFFFFFFFFu;              // insert item whose rq / priority come from the ready-set columns
 constexpr uint8_t MN_VARIANT = 0xFF;                     // variant column of a multi-node task's entry
+constexpr uint8_t PF_VARIANT = 0xFE;                     // variant column of a prefilled task's entry
 
 struct Table {
     uint64_t *key; uint32_t *worker; uint32_t *rq; uint8_t *variant; uint64_t *prio; uint32_t *claim;
@@ -40,6 +46,7 @@ struct Rows {
     const uint32_t *wid; uint32_t W, R;
     const uint64_t *total; uint64_t *free_;
     uint32_t *counts; uint32_t stride;
+    uint32_t *pf; uint32_t pf_stride;  // prefilled tasks per (row, request); nullptr: not tracked (a uniform argument)
 };
 // the multi-node columns of the worker rows (all nullptr: a caller without them); live = multi-node entries in the table as the host counts them — a
 // uniform argument: with live == 0 no kernel reads the columns
@@ -62,7 +69,7 @@ struct Items {
     const uint64_t *col_id; const uint64_t *col_prio; const uint32_t *col_rq; uint64_t col_n;
 };
 // a tick's placement as the mapping kernel staged it in HBM (kernels.h: hqk::Stage), one entry per record; meta = variant | kind << 8, entries whose kind
-// is not HQ_REC_ASSIGN are skipped.  The priority is levels[level] (the dense scan's level table, n_levels entries); levels == nullptr (the ordered view,
+// is HQ_REC_PREFILL enter as PF_VARIANT entries when the prefilled tasks are tracked (Rows::pf) and are skipped otherwise.  The priority is levels[level] (the dense scan's level table, n_levels entries); levels == nullptr (the ordered view,
 // whose run table lives in host memory): the priority alone is looked up by id in the ready-set columns col_id / col_prio.
 struct Staged {
     uint32_t n;
@@ -72,20 +79,33 @@ struct Staged {
 };
 // counters of one operation, in device memory, one atomic per wavefront (insert: C_OUT = entries that were not there before; evict: entries gathered)
 // (C_MN: the multi-node entries among C_DONE of a release / C_OUT of an eviction)
-enum Ctr : uint32_t { C_DONE = 0, C_UNKNOWN = 1, C_DUP = 2, C_FULL = 3, C_BAD = 4, C_OUT = 5, C_MN = 6, C_N = 8 };
+// (C_PF: prefilled entries — entered by the staged placement or a seed, turned into assigned entries by an upsert, gathered by an eviction)
+enum Ctr : uint32_t { C_DONE = 0, C_UNKNOWN = 1, C_DUP = 2, C_FULL = 3, C_BAD = 4, C_OUT = 5, C_MN = 6, C_PF = 7, C_N = 8 };
 
 hipError_t clear(Table t, hipStream_t s);
 // insert (upsert != 0: an id already present moves to the new worker / variant, its old count is given back; else it is counted as a duplicate).
 // apply_free != 0: Worker::insert_sn_task's free.remove on the worker's row (AMOUNT subtracts with saturation, ALL sets 0; these commute).
+// An id that is a prefilled entry (a FROM_PREFILL redirect): rq and priority are the entry's own, the old worker's prefilled count drops and the entry becomes
+// the assigned entry on the new worker (counted in C_DONE and C_PF, not in C_OUT); without upsert it is a duplicate like any other.
 hipError_t insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr, hipStream_t s);
-// the staged placement of a tick as upserts, free rows untouched (they become the tick's new_free)
+// the staged placement of a tick as upserts, free rows untouched (they become the tick's new_free); with r.pf its PREFILL entries enter too (C_PF)
 hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipStream_t s);
 // release in batch order with the last-ALL rule; scratch: pos [n] u32, last_all [W * R] u32, delta [W * R] u64 (zero on entry and on return).
 // A multi-node id of the batch leaves the table like the others (counted in C_DONE and C_MN); with m.live != 0 the W x R row pass resets its rows.
+// A prefilled id is not the release's: it is counted as unknown and stays.
 hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
 // A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
-hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr, hipStream_t s);
+// out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF)
+hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint32_t cap_out, uint32_t *ctr, hipStream_t s);
+// prefilled tasks (r.pf != nullptr in all four).  seed: item i (id, worker id, rq, priority) enters as a PF_VARIANT entry if the worker is resident and has its SN
+// bit, the request exists and the id is new (C_DONE entered; C_BAD / C_DUP refused).  start: the entry of id[i] takes variant[i]: pf count down, (row, slot)
+// count up, free.remove — all commuting atomics, one pass (C_DONE started; C_UNKNOWN not a prefilled entry, C_BAD no such variant).  remove: the entry leaves,
+// pf count down (C_DONE removed, C_UNKNOWN not a prefilled entry).  drop_all: every PF_VARIANT entry leaves (C_DONE); the host clears the pf table.
+hipError_t pf_seed(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint64_t *prio, uint32_t *ctr, hipStream_t s);
+hipError_t pf_start(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint8_t *variant, uint32_t *ctr, hipStream_t s);
+hipError_t pf_remove(Table t, Rows r, uint32_t n, const uint64_t *id, uint32_t *ctr, hipStream_t s);
+hipError_t pf_drop_all(Table t, uint32_t *ctr, hipStream_t s);
 // multi-node placements enter: owner is scratch [W] u32.  Task i enters only if every listed worker is resident, listed once, claimed by no task earlier in
 // the batch and holds no multi-node task, and the id is new; check != 0 (hqtick_assigned_add_mn) also wants every worker free of single-node tasks and
 // not STOPPING.  Then each row loses its SN bit and records the task (first row: root); free rows stay.  C_DONE entered, C_BAD / C_DUP refused.
@@ -95,9 +115,11 @@ hipError_t mn_reset_rows(Table t, Rows r, MnRows m, hipStream_t s);
 // live entries of `from` re-inserted into the (cleared) table `to`
 hipError_t rehash(Table from, Table to, uint32_t *ctr, hipStream_t s);
 // dst row w = src row src_row[w] (NONE or >= W_src: a zero row), columns [0, n_cols).  With ms.task the multi-node columns move in the same launch
-// (md: the destination; a new row holds no task and takes its flags byte from new_flags [W_dst])
+// (md: the destination; a new row holds no task and takes its flags byte from new_flags [W_dst]).  With pf.dst the prefilled counts move in the same launch too:
+// columns [0, pf.n_cols), pf.n_cols <= n_cols
+struct PfMove { const uint32_t *src; uint32_t src_stride; uint32_t *dst; uint32_t dst_stride; uint32_t n_cols; };
 hipError_t repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride,
-                         uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s);
+                         uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s, PfMove pf = PfMove{});
 hipError_t lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant, hipStream_t s);
 
 }  // namespace hqasg

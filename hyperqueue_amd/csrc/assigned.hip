@@ -79,26 +79,39 @@ __global__ void k_clear(Table t) {
     t.key[b] = HT_EMPTY; t.claim[b] = NONE;
 }
 
-enum InsertStatus : int { S_SKIP = 0, S_FRESH, S_MOVED, S_DUP, S_BAD, S_FULL };
+enum InsertStatus : int { S_SKIP = 0, S_FRESH, S_MOVED, S_DUP, S_BAD, S_FULL, S_PF_IN, S_PF_OUT };  // (S_PF_IN: a prefilled entry entered; S_PF_OUT: one became an assigned entry)
 // the entry (id -> wid, rq, v, prio) enters its bucket and the count of (row, slot) is raised
 __device__ __forceinline__ int enter(const Table &t, const Req &q, const Rows &r, uint64_t id, uint32_t row, uint32_t wid, uint32_t rq, uint32_t v, uint64_t prio, int upsert,
                                      int apply_free) {
     if (row >= r.W || id >= HT_TOMB) return S_BAD;
     if (!variant_ok(q, rq, v) || q.rq_off[rq] + v >= r.stride) return S_BAD;
-    int fresh = 0;
+    int fresh = 0; bool from_pf = false;
     const uint32_t b = ht_claim(t, id, &fresh);
     if (b == NONE) return S_FULL;
     if (!fresh) {
         if (!upsert || t.variant[b] == MN_VARIANT) return S_DUP;  // (a multi-node task never moves: it has no count to give back)
         const uint32_t orow = row_of(r, t.worker[b]);  // a re-targeted redirect: the old target's count goes back (its free row is the tick's)
-        if (orow != NONE) atomicSub(&r.counts[(size_t)orow * r.stride + q.rq_off[t.rq[b]] + t.variant[b]], 1u);
+        from_pf = t.variant[b] == PF_VARIANT;          // out of a prefill set (remove_prefill_task, mapping.rs:85-88): the old worker's prefilled count instead
+        if (from_pf) { if (orow != NONE && r.pf && t.rq[b] < r.pf_stride) atomicSub(&r.pf[(size_t)orow * r.pf_stride + t.rq[b]], 1u); }
+        else if (orow != NONE) atomicSub(&r.counts[(size_t)orow * r.stride + q.rq_off[t.rq[b]] + t.variant[b]], 1u);
     }
     t.worker[b] = wid; t.rq[b] = rq; t.variant[b] = (uint8_t)v; t.prio[b] = prio; t.claim[b] = NONE;
     const uint32_t slot = q.rq_off[rq] + v;
     atomicAdd(&r.counts[(size_t)row * r.stride + slot], 1u);
     if (apply_free)
         for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) free_remove(&r.free_[(size_t)row * r.R + q.ent_res[e]], q.ent_kind[e], q.ent_amount[e]);
-    return fresh ? S_FRESH : S_MOVED;
+    return fresh ? S_FRESH : from_pf ? S_PF_OUT : S_MOVED;
+}
+// a prefilled task enters: no (row, slot) count, no free row — the prefilled count of (row, rq) alone.  The id must be new.
+__device__ __forceinline__ int enter_pf(const Table &t, const Req &q, const Rows &r, uint64_t id, uint32_t row, uint32_t wid, uint32_t rq, uint64_t prio) {
+    if (row >= r.W || id >= HT_TOMB || rq >= q.Q || rq >= r.pf_stride) return S_BAD;
+    int fresh = 0;
+    const uint32_t b = ht_claim(t, id, &fresh);
+    if (b == NONE) return S_FULL;
+    if (!fresh) return S_DUP;
+    t.worker[b] = wid; t.rq[b] = rq; t.variant[b] = PF_VARIANT; t.prio[b] = prio; t.claim[b] = NONE;
+    atomicAdd(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
+    return S_PF_IN;
 }
 // index of `id` in the ascending ready-set id column, ~0 if absent (a consumed task keeps its id and priority)
 __device__ __forceinline__ uint64_t col_find(const uint64_t *col_id, uint64_t col_n, uint64_t id) {
@@ -107,7 +120,8 @@ __device__ __forceinline__ uint64_t col_find(const uint64_t *col_id, uint64_t co
     return (lo < col_n && col_id[lo] == id) ? lo : ~0ull;
 }
 __device__ __forceinline__ void count_status(uint32_t *ctr, int st) {
-    wave_add(&ctr[C_DONE], st == S_FRESH || st == S_MOVED); wave_add(&ctr[C_OUT], st == S_FRESH);
+    wave_add(&ctr[C_DONE], st == S_FRESH || st == S_MOVED || st == S_PF_IN || st == S_PF_OUT); wave_add(&ctr[C_OUT], st == S_FRESH);
+    wave_add(&ctr[C_PF], st == S_PF_IN || st == S_PF_OUT);
     wave_add(&ctr[C_DUP], st == S_DUP); wave_add(&ctr[C_BAD], st == S_BAD); wave_add(&ctr[C_FULL], st == S_FULL);
 }
 __device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Rows &r, const Items &it, int upsert, int apply_free, uint32_t i) {
@@ -115,6 +129,10 @@ __device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Ro
     const uint32_t wid = it.wid[i], v = it.variant[i]; uint32_t rq = it.rq ? it.rq[i] : RQ_LOOKUP;
     const uint32_t row = row_of(r, wid);
     if (row == NONE || id >= HT_TOMB) return S_BAD;
+    if (r.pf && upsert) {  // a task out of a prefill set is in no queue: its prefilled entry knows request and priority
+        const uint32_t b = ht_find(t, id);
+        if (b != NONE && t.variant[b] == PF_VARIANT) { rq = t.rq[b]; prio = t.prio[b]; }
+    }
     if (rq == RQ_LOOKUP) {  // rq and priority of a task of the ready set
         const uint64_t j = col_find(it.col_id, it.col_n, id);
         if (j == ~0ull) return S_BAD;
@@ -132,12 +150,14 @@ __global__ void k_insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr
     int status = S_SKIP;
     if (i < st.n) {
         const uint32_t meta = st.meta[i];
-        if ((meta >> 8) == HQ_REC_ASSIGN) {  // prefills do not enter the ledger
+        const bool assign = (meta >> 8) == HQ_REC_ASSIGN;
+        if (assign || r.pf) {  // (r.pf == nullptr, uniform: prefills do not enter the ledger)
             const uint64_t id = st.task[i]; const uint32_t row = st.row[i], lvl = st.level[i], rq = st.rq[i];
             uint64_t prio = 0; bool ok = row < r.W;
             if (st.levels) { ok = ok && lvl < st.n_levels; if (ok) prio = st.levels[lvl]; }
             else { const uint64_t j = col_find(st.col_id, st.col_n, id); ok = ok && j != ~0ull; if (ok) prio = st.col_prio[j]; }
-            status = ok ? enter(t, q, r, id, row, r.wid[row], rq, meta & 0xFFu, prio, 1, 0) : S_BAD;
+            if (!ok) status = S_BAD;
+            else status = assign ? enter(t, q, r, id, row, r.wid[row], rq, meta & 0xFFu, prio, 1, 0) : enter_pf(t, q, r, id, row, r.wid[row], rq, prio);
         }
     }
     count_status(ctr, status);
@@ -149,6 +169,7 @@ __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *p
     uint32_t b = NONE;
     if (i < n) {
         b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
+        if (b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled task is not running: unknown to a release
         pos[i] = b;
         if (b != NONE) atomicMin(&t.claim[b], i);
     }
@@ -263,7 +284,7 @@ __global__ void k_mn_enter(Table t, Rows r, MnRows m, MnItems it, const uint32_t
     count_status(ctr, status);
 }
 
-__global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr) {
+__global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint32_t cap_out, uint32_t *ctr) {
     const uint32_t b = blockIdx.x * TPB + threadIdx.x;
     const uint64_t k = b <= t.mask ? t.key[b] : HT_EMPTY;
     bool hit = false;
@@ -274,10 +295,80 @@ __global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t
         hit = lo < n_lost && lost[lo] == w;
     }
     wave_add(&ctr[C_MN], hit && t.variant[b] == MN_VARIANT);  // (its worker column is the root: a lost root evicts the task, reactor.rs:107-128)
+    wave_add(&ctr[C_PF], hit && t.variant[b] == PF_VARIANT);  // (move_prefilled_task_to_ready; the row's prefilled counts go with the row in the re-pack)
     const uint32_t o = wave_append(&ctr[C_OUT], hit);
     if (!hit || o >= cap_out) return;  // (the host sized the output by its live count: more is reported as an error and nothing is written past the end)
-    out_id[o] = k; out_rq[o] = t.rq[b]; out_prio[o] = t.prio[b];
+    out_id[o] = k; out_rq[o] = t.rq[b]; out_prio[o] = t.prio[b]; out_var[o] = t.variant[b];
     t.key[b] = HT_TOMB;
+}
+
+// ---- prefilled tasks (r.pf != nullptr) ----
+__global__ void k_pf_seed(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint64_t *prio, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    int status = S_SKIP;
+    if (i < n) {
+        const uint32_t row = row_of(r, wid[i]);
+        status = (row == NONE || !(m.flags[row] & HQ_WORKER_SN)) ? S_BAD : enter_pf(t, q, r, id[i], row, wid[i], rq[i], prio[i]);
+    }
+    count_status(ctr, status);
+}
+// the variant byte of bucket b goes from PF_VARIANT to v, atomically on its 32-bit word (the buckets beside it may change in the same launch): true for the
+// one thread that made the change
+__device__ __forceinline__ bool pf_take_variant(const Table &t, uint32_t b, uint8_t v) {
+    unsigned int *word = reinterpret_cast<unsigned int *>(t.variant) + (b >> 2);
+    const unsigned int sh = (b & 3u) * 8u;
+    unsigned int cur = __atomic_load_n(word, __ATOMIC_RELAXED);
+    for (;;) {
+        if (((cur >> sh) & 0xFFu) != PF_VARIANT) return false;
+        const unsigned int want = (cur & ~(0xFFu << sh)) | ((unsigned int)v << sh);
+        const unsigned int got = atomicCAS(word, cur, want);
+        if (got == cur) return true;
+        cur = got;
+    }
+}
+// task_from_prefilled_to_started (worker.rs:212-221): every step is an atomic that commutes with the others of the batch
+__global__ void k_pf_start(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint8_t *variant, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    bool done = false, unknown = false, bad = false;
+    if (i < n) {
+        const uint32_t b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
+        if (b == NONE) unknown = true;
+        else {
+            const uint32_t rq = t.rq[b], v = variant[i], row = row_of(r, t.worker[b]);  // (these columns of a prefilled entry do not change in this launch)
+            if (v >= PF_VARIANT || !variant_ok(q, rq, v) || q.rq_off[rq] + v >= r.stride || row == NONE || rq >= r.pf_stride) {
+                const uint8_t cur = t.variant[b];
+                if (cur == PF_VARIANT) bad = true; else unknown = true;
+            } else if (!pf_take_variant(t, b, (uint8_t)v)) unknown = true;  // an assigned entry, or a repeat of the id within the batch
+            else {
+                const uint32_t slot = q.rq_off[rq] + v;
+                atomicSub(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
+                atomicAdd(&r.counts[(size_t)row * r.stride + slot], 1u);
+                for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) free_remove(&r.free_[(size_t)row * r.R + q.ent_res[e]], q.ent_kind[e], q.ent_amount[e]);
+                done = true;
+            }
+        }
+    }
+    wave_add(&ctr[C_DONE], done); wave_add(&ctr[C_UNKNOWN], unknown); wave_add(&ctr[C_BAD], bad);
+}
+// remove_prefill_task outside a tick: the one thread that turns the key into a tombstone takes the count down
+__global__ void k_pf_remove(Table t, Rows r, uint32_t n, const uint64_t *id, uint32_t *ctr) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    bool done = false;
+    if (i < n && id[i] < HT_TOMB) {
+        const uint32_t b = ht_find(t, id[i]);
+        if (b != NONE && t.variant[b] == PF_VARIANT) {
+            const uint32_t rq = t.rq[b], row = row_of(r, t.worker[b]);
+            done = atomicCAS(reinterpret_cast<unsigned long long *>(&t.key[b]), (unsigned long long)id[i], (unsigned long long)HT_TOMB) == id[i];
+            if (done && row != NONE && rq < r.pf_stride) atomicSub(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
+        }
+    }
+    wave_add(&ctr[C_DONE], done); wave_add(&ctr[C_UNKNOWN], i < n && !done);
+}
+__global__ void k_pf_drop_all(Table t, uint32_t *ctr) {
+    const uint32_t b = blockIdx.x * TPB + threadIdx.x;
+    const bool hit = b <= t.mask && t.key[b] < HT_TOMB && t.variant[b] == PF_VARIANT;
+    if (hit) t.key[b] = HT_TOMB;
+    wave_add(&ctr[C_DONE], hit);
 }
 
 __global__ void k_rehash(Table from, Table to, uint32_t *ctr) {
@@ -293,12 +384,13 @@ __global__ void k_rehash(Table from, Table to, uint32_t *ctr) {
 }
 
 __global__ void k_repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride, uint32_t n_cols,
-                                MnRows ms, MnRows md, const uint8_t *new_flags) {
+                                MnRows ms, MnRows md, const uint8_t *new_flags, PfMove pf) {
     const uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (j >= (uint64_t)W_dst * n_cols) return;
     const uint32_t w = (uint32_t)(j / n_cols), c = (uint32_t)(j % n_cols);
     const uint32_t sr = src_row ? src_row[w] : w;
     dst[(size_t)w * dst_stride + c] = sr < W_src ? src[(size_t)sr * src_stride + c] : 0u;
+    if (pf.dst && c < pf.n_cols) pf.dst[(size_t)w * pf.dst_stride + c] = sr < W_src ? pf.src[(size_t)sr * pf.src_stride + c] : 0u;  // (pf.dst == nullptr, uniform: not tracked)
     if (c == 0 && md.task) {  // the row's multi-node columns travel with its first count
         const bool old = sr < W_src;
         md.task[w] = old ? ms.task[sr] : HT_EMPTY; md.root[w] = old ? ms.root[sr] : (uint8_t)0; md.flags[w] = old ? ms.flags[sr] : new_flags[w];
@@ -337,9 +429,28 @@ hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t 
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
-hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint32_t cap_out, uint32_t *ctr, hipStream_t s) {
+hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint32_t cap_out, uint32_t *ctr, hipStream_t s) {
     if (!n_lost) return hipSuccess;
-    hipLaunchKernelGGL(k_evict, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, n_lost, lost, out_id, out_rq, out_prio, cap_out, ctr);
+    hipLaunchKernelGGL(k_evict, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, n_lost, lost, out_id, out_rq, out_prio, out_var, cap_out, ctr);
+    return hipGetLastError();
+}
+hipError_t pf_seed(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint64_t *prio, uint32_t *ctr, hipStream_t s) {
+    if (!n || !r.pf) return hipSuccess;
+    hipLaunchKernelGGL(k_pf_seed, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, m, n, id, wid, rq, prio, ctr);
+    return hipGetLastError();
+}
+hipError_t pf_start(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint8_t *variant, uint32_t *ctr, hipStream_t s) {
+    if (!n || !r.pf) return hipSuccess;
+    hipLaunchKernelGGL(k_pf_start, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, variant, ctr);
+    return hipGetLastError();
+}
+hipError_t pf_remove(Table t, Rows r, uint32_t n, const uint64_t *id, uint32_t *ctr, hipStream_t s) {
+    if (!n || !r.pf) return hipSuccess;
+    hipLaunchKernelGGL(k_pf_remove, dim3(nblk(n)), dim3(TPB), 0, s, t, r, n, id, ctr);
+    return hipGetLastError();
+}
+hipError_t pf_drop_all(Table t, uint32_t *ctr, hipStream_t s) {
+    hipLaunchKernelGGL(k_pf_drop_all, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, ctr);
     return hipGetLastError();
 }
 hipError_t rehash(Table from, Table to, uint32_t *ctr, hipStream_t s) {
@@ -347,9 +458,9 @@ hipError_t rehash(Table from, Table to, uint32_t *ctr, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride,
-                         uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s) {
+                         uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s, PfMove pf) {
     if (!W_dst || !n_cols) return hipSuccess;
-    hipLaunchKernelGGL(k_repack_counts, dim3(nblk((uint64_t)W_dst * n_cols)), dim3(TPB), 0, s, src, src_stride, W_src, src_row, W_dst, dst, dst_stride, n_cols, ms, md, new_flags);
+    hipLaunchKernelGGL(k_repack_counts, dim3(nblk((uint64_t)W_dst * n_cols)), dim3(TPB), 0, s, src, src_stride, W_src, src_row, W_dst, dst, dst_stride, n_cols, ms, md, new_flags, pf);
     return hipGetLastError();
 }
 hipError_t mn_enter(Table t, Rows r, MnRows m, MnItems it, uint32_t *owner, int check, uint32_t *ctr, hipStream_t s) {

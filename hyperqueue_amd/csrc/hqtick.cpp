@@ -77,6 +77,10 @@ struct Ledger {
     DevBuf counts, counts2; uint32_t stride = 0;                                                  // [W x stride] per (worker row, variant slot)
     // multi-node tasks (assigned.h): [mn task u64 W][mn root u8 W][flags u8 W] beside the count rows, re-packed with them; mn_live = their entries in the table
     DevBuf mn, mn2; uint64_t mn_live = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)
+    // prefilled tasks (assigned.h; hqtick_assigned_track_prefilled): pf u32 [W x pf_stride] per (worker row, request), re-packed with the count rows; pf_live = their
+    // entries in the table; h_pf: the host copy a tick reads (pf_dirty: a ledger call changed the table since)
+    bool pf_on = false; DevBuf pf, pf2; uint32_t pf_stride = 0; uint64_t pf_live = 0; std::vector<uint32_t> h_pf; bool pf_dirty = false;
+    std::vector<uint64_t> rq_pf_task;                                 // hqtick_cluster_last_requeued_prefilled
     std::vector<uint32_t> var_nodes;                                  // n_nodes per variant slot of the request tables
     std::vector<uint64_t> pmn_id; std::vector<uint32_t> pmn_rq, pmn_off{0}, pmn_wid;  // a tick's multi-node placements waiting with its records (worker ids, root first)
     std::vector<uint32_t> mnw_out; std::vector<unsigned char> mnw_cols;              // hqtick_assigned_mn_workers
@@ -98,7 +102,7 @@ struct Ledger {
     // what a ledger tick hands the host stages: per worker its distinct (rq, variant) pairs with counts (rebuilt from the count table when it changed)
     std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_var; bool agg_dirty = true;
     void release_all() {
-        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &mn, &mn2, &req, &wids, &scratch, &saved_rq, &batch, &stage, &ctr};
+        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &mn, &mn2, &pf, &pf2, &req, &wids, &scratch, &saved_rq, &batch, &stage, &ctr};
         for (DevBuf *x : b) x->release();
         h_ctr.release(); h_in.release();
     }
@@ -916,7 +920,7 @@ struct TickRun {
         {   // the big tables live at the head of the pinned plan buffer; everything else of the plan (phase_c) is a few KB behind them
             ps.plan_head_words = (size_t)nkeys * W * 2 + (size_t)Q * W;
             size_t n_cnt0 = 0; for (uint32_t k = 0; k < nkeys; k++) n_cnt0 += cnt.key_size(k);
-            const size_t small = (size_t)9 * (nkeys + 4) + n_cnt0 + (size_t)6 * (Q + 2) + (W + 2) + (size_t)4 * n_groups() + (size_t)2 * s->n_retracting + 64 +
+            const size_t small = (size_t)9 * (nkeys + 4) + n_cnt0 + (size_t)7 * (Q + 2) + (W + 2) + (size_t)4 * n_groups() + (size_t)2 * s->n_retracting + 64 +
                                  (sc.ordered ? (size_t)3 * (Q + 2) + (size_t)2 * n_groups() + 8 : 0);  // (the view's tables: run_off, q_tnc, run_start, run_rank)
             if (!ctx->h_plan.ensure((ps.plan_head_words + small) * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc plan");
             ps.wpos = ctx->h_plan.as<uint32_t>(); ps.wcnt = ps.wpos + (size_t)nkeys * W; ps.pfl_j = ps.wcnt + (size_t)nkeys * W; ps.pfl_rows = 0;
@@ -1000,6 +1004,11 @@ struct TickRun {
         ps.pf_drained.assign(Q, 0);
         ps.has_pf.assign((size_t)Q * W, 0);  // SingleNodeTaskAssignment::prefilled_tasks as per-(rq, worker) counts
         if (s->prefilled_off) for (uint32_t w = 0; w < W; w++) for (uint32_t i = s->prefilled_off[w]; i < s->prefilled_off[w + 1]; i++) if (s->prefilled_rq[i] < Q) ps.has_pf[(size_t)s->prefilled_rq[i] * W + w]++;
+        if (ctx->asg.on && ctx->asg.pf_on) {  // the ledger's prefilled counts (ledger_sync_mirror brought them back; a snapshot with prefilled_off was refused)
+            const Ledger &a = ctx->asg;
+            const uint32_t nq = std::min(Q, a.pf_stride);
+            if (a.h_pf.size() >= (size_t)W * a.pf_stride) for (uint32_t w = 0; w < W; w++) for (uint32_t q = 0; q < nq; q++) ps.has_pf[(size_t)q * W + w] = a.h_pf[(size_t)w * a.pf_stride + q];
+        }
         key_T.assign(nkeys, {});
         ctx->red_kind.clear();
         for (uint32_t k = 0; k < nkeys; k++) {
@@ -1262,6 +1271,7 @@ struct TickRun {
             size_t o_rq = put(ps.key_rq), o_var = put(ps.key_var_w), o_seg = put(ps.key_seg), o_ordoff = put(ps.key_ord_off), o_ord = put(ps.ord_cnt), o_toff = put(ps.key_t_off),
                    o_boff = put(ps.key_bits_off), o_tr = put(ps.key_tr), o_base = put(ps.rq_sel_base), o_pfs = put(ps.pf_start), o_pfn = put(ps.pf_n),
                    o_pqs = put(ps.pfq_src), o_pqz = put(ps.pfq_size), o_out = put(ps.out_off);
+            const size_t o_pqr = ctx->asg.on ? put(pfq_rq) : 0;  // the ledger's staging names the request of a PREFILL record
             size_t o_tb = put(ps.take_base);
             size_t o_roff = 0, o_qtnc = 0, o_rst = 0, o_rrk = 0;  // the view's tables (order.hip: k_order_select)
             if (sc.ordered) { o_roff = put(sc.run_off); o_qtnc = put(ps.q_tnc); o_rst = put(sc.run_start); o_rrk = put(sc.run_level); }
@@ -1341,6 +1351,7 @@ struct TickRun {
                 unsigned char *sp = a.stage.as<unsigned char>();
                 stg = hqk::Stage{reinterpret_cast<uint64_t *>(sp), reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 8), reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 12),
                                  reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 16), reinterpret_cast<uint16_t *>(sp + (size_t)n_rec * 20)};
+                stg.pfq_rq = ctx->d_map.as<uint32_t>() + o_pqr;
                 a.stage_n = n_rec; a.stage_ordered = sc.ordered; a.stage_L = sc.L;
             }
             bool expand_is_last = false;
@@ -1520,6 +1531,11 @@ void ledger_take_requests(hqtick_ctx *ctx, const hqtick_snapshot *s) {
     a.req_dirty = true;
 }
 
+uint32_t ledger_max_variants(const Ledger &a) {
+    uint32_t m = 0;
+    for (size_t q = 0; q + 1 < a.rq_off.size(); q++) m = std::max(m, a.rq_off[q + 1] - a.rq_off[q]);
+    return m;
+}
 hqasg::Table ledger_table(Ledger &a, bool second = false) {
     if (second) return hqasg::Table{a.key2.as<uint64_t>(), a.wid2.as<uint32_t>(), a.rq2.as<uint32_t>(), a.var2.as<uint8_t>(), a.prio2.as<uint64_t>(), a.claim2.as<uint32_t>(), 0};
     return hqasg::Table{a.key.as<uint64_t>(), a.wid.as<uint32_t>(), a.rq.as<uint32_t>(), a.var.as<uint8_t>(), a.prio.as<uint64_t>(), a.claim.as<uint32_t>(), a.cap - 1};
@@ -1527,7 +1543,8 @@ hqasg::Table ledger_table(Ledger &a, bool second = false) {
 hqasg::Rows ledger_rows(hqtick_ctx *ctx) {
     const uint32_t W = ctx->cl_W, R = ctx->cl_R;
     unsigned char *base = ctx->d_cluster.as<unsigned char>();
-    return hqasg::Rows{ctx->asg.wids.as<uint32_t>(), W, R, reinterpret_cast<const uint64_t *>(base), reinterpret_cast<uint64_t *>(base + (size_t)W * R * 8), ctx->asg.counts.as<uint32_t>(), ctx->asg.stride};
+    return hqasg::Rows{ctx->asg.wids.as<uint32_t>(), W, R, reinterpret_cast<const uint64_t *>(base), reinterpret_cast<uint64_t *>(base + (size_t)W * R * 8), ctx->asg.counts.as<uint32_t>(), ctx->asg.stride,
+                       ctx->asg.pf_on ? ctx->asg.pf.as<uint32_t>() : nullptr, ctx->asg.pf_on ? ctx->asg.pf_stride : 0u};
 }
 // the multi-node columns of W rows in `buf`; live: the uniform argument of the kernels that may skip them
 hqasg::MnRows ledger_mn_rows(const DevBuf &buf, uint32_t W, uint64_t live) {
@@ -1553,6 +1570,14 @@ int ledger_sync_req(hqtick_ctx *ctx) {
         if (a.stride) HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W, nullptr, W, a.counts2.as<uint32_t>(), ns, a.stride, hqasg::MnRows{}, hqasg::MnRows{}, nullptr, ctx->stream));
         std::swap(a.counts, a.counts2); a.stride = ns;
         a.dirty = true;
+    }
+    if (a.pf_on && a.rq_off.size() - 1 > a.pf_stride) {  // new requests: a wider prefilled table, rows copied over (Q <= variant slots: never wider than the count rows)
+        const uint32_t ns = std::max<uint32_t>(16, ((uint32_t)a.rq_off.size() - 1 + 15) & ~15u);
+        if (!a.pf2.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc prefilled counts");
+        HQ_HIP(hipMemsetAsync(a.pf2.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
+        HQ_HIP(hqasg::repack_counts(a.pf.as<uint32_t>(), a.pf_stride, W, nullptr, W, a.pf2.as<uint32_t>(), ns, a.pf_stride, hqasg::MnRows{}, hqasg::MnRows{}, nullptr, ctx->stream));
+        std::swap(a.pf, a.pf2); a.pf_stride = ns;
+        a.dirty = true; a.pf_dirty = true;
     }
     if (!a.req_dirty) return 0;
     const size_t Q = a.rq_off.size() - 1, ne = a.ent_res.size();
@@ -1591,7 +1616,7 @@ uint32_t *ledger_ctr(hqtick_ctx *ctx) {
 // room for `more` entries: live + tombstones + more stay under half the capacity; otherwise the live entries move to a fresh table
 int ledger_reserve(hqtick_ctx *ctx, uint64_t more) {
     Ledger &a = ctx->asg;
-    const uint64_t live = a.n_live + a.mn_live;
+    const uint64_t live = a.n_live + a.mn_live + (a.pf_on ? a.pf_live : 0);
     if (a.cap && (live + a.n_tomb + more) * 2 <= a.cap) return 0;
     uint64_t want = 1024; while (want < (live + more) * 4) want <<= 1;
     if (want > (1ull << 31)) return fail(ctx, HQTICK_E_CAPACITY, "assignment ledger: more than 2^29 entries");
@@ -1636,6 +1661,7 @@ int ledger_insert_host(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const ui
     if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
     *fresh = c[hqasg::C_OUT]; *bad = c[hqasg::C_BAD]; *dup = c[hqasg::C_DUP];
     a.n_live += c[hqasg::C_OUT]; a.dirty = true;
+    if (const uint32_t from_pf = std::min<uint64_t>(c[hqasg::C_PF], a.pf_live)) { a.pf_live -= from_pf; a.n_live += from_pf; a.pf_dirty = true; }  // FROM_PREFILL redirects: prefilled entries that are assigned entries now
     return 0;
 }
 
@@ -1695,8 +1721,9 @@ int ledger_apply_tick(hqtick_ctx *ctx) {
         HQ_HIP(hqasg::insert_staged(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), st, a.ctr.as<uint32_t>(), ctx->stream));
         HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
         HQ_HIP(hipStreamSynchronize(ctx->stream));
-        if (c[hqasg::C_FULL] || c[hqasg::C_BAD]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a record of the tick could not be entered");
+        if (c[hqasg::C_FULL] || c[hqasg::C_BAD] || (a.pf_on && c[hqasg::C_DUP])) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a record of the tick could not be entered");
         a.n_live += c[hqasg::C_OUT];
+        if (a.pf_on && c[hqasg::C_PF]) { a.pf_live += c[hqasg::C_PF]; a.pf_dirty = true; }  // its PREFILL records
     }
     if (!a.red_id.empty()) {
         uint32_t fresh = 0, bad = 0, dup = 0;
@@ -1737,14 +1764,21 @@ int ledger_repack(hqtick_ctx *ctx, const std::vector<uint32_t> &src, uint32_t W_
     Ledger &a = ctx->asg;
     const uint32_t W_new = (uint32_t)src.size();
     if (!a.counts2.ensure((size_t)W_new * a.stride * 4 + 64) || !a.batch.ensure((size_t)W_new * 5 + 16) || !a.mn2.ensure((size_t)W_new * 10 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
+    hqasg::PfMove pfm{};
+    if (a.pf_on) {  // the prefilled counts move in the same launch (pf_stride <= stride: both are the request tables' sizes rounded up alike)
+        if (a.pf_stride > a.stride) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: prefilled table wider than the count rows");
+        if (!a.pf2.ensure((size_t)W_new * a.pf_stride * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc prefilled counts");
+        pfm = hqasg::PfMove{a.pf.as<uint32_t>(), a.pf_stride, a.pf2.as<uint32_t>(), a.pf_stride, a.pf_stride};
+    }
     std::vector<unsigned char> hb((size_t)W_new * 5 + 16, 0);  // [src row u32 W_new][flags of the new rows u8 W_new]: one copy
     if (W_new) memcpy(hb.data(), src.data(), (size_t)W_new * 4);
     for (uint32_t w = 0; w < W_new; w++) hb[(size_t)W_new * 4 + w] = src[w] >= W_old ? (add_flags ? add_flags[src[w] - W_old] : (uint8_t)HQ_WORKER_SN) : (uint8_t)0;
     HQ_HIP(hipMemcpyAsync(a.batch.p, hb.data(), hb.size(), hipMemcpyHostToDevice, ctx->stream));
     HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W_old, a.batch.as<uint32_t>(), W_new, a.counts2.as<uint32_t>(), a.stride, a.stride,
-                                ledger_mn_rows(a.mn, W_old, a.mn_live), ledger_mn_rows(a.mn2, W_new, a.mn_live), a.batch.as<uint8_t>() + (size_t)W_new * 4, ctx->stream));
+                                ledger_mn_rows(a.mn, W_old, a.mn_live), ledger_mn_rows(a.mn2, W_new, a.mn_live), a.batch.as<uint8_t>() + (size_t)W_new * 4, ctx->stream, pfm));
     HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
     std::swap(a.counts, a.counts2); std::swap(a.mn, a.mn2);
+    if (a.pf_on) { std::swap(a.pf, a.pf2); a.pf_dirty = true; }
     a.dirty = true;
     return 0;
 }
@@ -1753,25 +1787,27 @@ int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
     Ledger &a = ctx->asg;
     std::vector<uint32_t> lost(worker_id, worker_id + n);
     std::sort(lost.begin(), lost.end());
-    const uint64_t cap_out = a.n_live + a.mn_live + 1;
-    const size_t o_l = 0, o_id = ((size_t)n * 4 + 7) & ~(size_t)7, o_p = o_id + cap_out * 8, o_q = o_p + cap_out * 8, bytes = o_q + cap_out * 4 + 16;
+    const uint64_t pf_live = a.pf_on ? a.pf_live : 0;
+    const uint64_t cap_out = a.n_live + a.mn_live + pf_live + 1;
+    const size_t o_l = 0, o_id = ((size_t)n * 4 + 7) & ~(size_t)7, o_p = o_id + cap_out * 8, o_q = o_p + cap_out * 8, o_v = o_q + cap_out * 4, bytes = o_v + cap_out + 16;
     if (!a.scratch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
     unsigned char *d = a.scratch.as<unsigned char>();
     HQ_HIP(hipMemcpyAsync(d + o_l, lost.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     uint32_t *c = ledger_ctr(ctx);
     if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
     HQ_HIP(hqasg::evict(ledger_table(a), n, reinterpret_cast<const uint32_t *>(d + o_l), reinterpret_cast<uint64_t *>(d + o_id), reinterpret_cast<uint32_t *>(d + o_q),
-                        reinterpret_cast<uint64_t *>(d + o_p), (uint32_t)cap_out, a.ctr.as<uint32_t>(), ctx->stream));
+                        reinterpret_cast<uint64_t *>(d + o_p), d + o_v, (uint32_t)cap_out, a.ctr.as<uint32_t>(), ctx->stream));
     HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     const uint32_t k = c[hqasg::C_OUT];
-    const uint32_t k_mn = c[hqasg::C_MN];
-    if (k >= cap_out || k_mn > k || k_mn > a.mn_live || k - k_mn > a.n_live) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
+    const uint32_t k_mn = c[hqasg::C_MN], k_pf = c[hqasg::C_PF];
+    if (k >= cap_out || (uint64_t)k_mn + k_pf > k || k_mn > a.mn_live || k_pf > pf_live || k - k_mn - k_pf > a.n_live) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
     if (k_mn) {  // a lost ROOT (reactor.rs:107-128): the task's other rows are free single-node workers again, before the rows are re-packed
         HQ_HIP(hqasg::mn_reset_rows(ledger_table(a), ledger_rows(ctx), ledger_mn_rows(a.mn, ctx->cl_W, a.mn_live), ctx->stream));
         a.flags_dirty = true;
     }
-    std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k);
+    std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k); std::vector<uint8_t> var(k);
+    if (k && k_pf) HQ_HIP(hipMemcpy(var.data(), d + o_v, k, hipMemcpyDeviceToHost));
     if (k) {
         HQ_HIP(hipMemcpy(id.data(), d + o_id, (size_t)k * 8, hipMemcpyDeviceToHost));
         HQ_HIP(hipMemcpy(pr.data(), d + o_p, (size_t)k * 8, hipMemcpyDeviceToHost));
@@ -1780,8 +1816,12 @@ int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
     std::vector<uint32_t> ord(k);
     for (uint32_t i = 0; i < k; i++) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return id[x] < id[y]; });
-    for (uint32_t i : ord) { a.rq_task.push_back(id[i]); a.rq_prio.push_back(pr[i]); a.rq_rq.push_back(rq[i]); }
-    a.n_live -= k - k_mn; a.mn_live -= k_mn; a.n_tomb += k; a.dirty = true;
+    for (uint32_t i : ord) {
+        a.rq_task.push_back(id[i]); a.rq_prio.push_back(pr[i]); a.rq_rq.push_back(rq[i]);
+        if (k_pf && var[i] == hqasg::PF_VARIANT) a.rq_pf_task.push_back(id[i]);  // move_prefilled_task_to_ready: the subset the host takes out of its prefill sets
+    }
+    a.n_live -= k - k_mn - k_pf; a.mn_live -= k_mn; a.n_tomb += k; a.dirty = true;
+    if (k_pf) { a.pf_live -= k_pf; a.pf_dirty = true; }
     return 0;
 }
 
@@ -1799,8 +1839,12 @@ int ledger_sync_mirror(hqtick_ctx *ctx) {
             ctx->mirror.flags.resize(W);
             HQ_HIP(hipMemcpyAsync(ctx->mirror.flags.data(), ledger_mn_rows(a.mn, W, 0).flags, W, hipMemcpyDeviceToHost, ctx->stream));
         }
+        if (a.pf_on && a.pf_dirty) {  // a ledger call changed the prefilled counts: what the tick's has_pf is filled from
+            a.h_pf.resize((size_t)W * a.pf_stride);
+            if (W) HQ_HIP(hipMemcpyAsync(a.h_pf.data(), a.pf.p, (size_t)W * a.pf_stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
         HQ_HIP(hipStreamSynchronize(ctx->stream));
-        a.dirty = false; a.agg_dirty = true; a.flags_dirty = false;
+        a.dirty = false; a.agg_dirty = true; a.flags_dirty = false; a.pf_dirty = false;
     }
     if (!a.agg_dirty) return 0;
     // O(W x variant slots), not O(running tasks): the count table is what GapCache and Worker::is_free need
@@ -1825,9 +1869,11 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "assignment ledger on a sharded or replica context");
         if (s->worker_id || !(ctx->cluster_valid && ctx->mirror.valid)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
         if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
+        if (ctx->asg.pf_on && s->prefilled_off) return fail(ctx, HQTICK_E_INVALID, "prefilled tracking on: the snapshot must not carry a prefilled CSR as well");
         HQ_HIP(hipSetDevice(ctx->device));
         ctx->asg.pending = false; ctx->asg.stage_n = 0;  // (a tick that was never consumed is abandoned, as its selection is; its staging is never read)
         ledger_take_requests(ctx, s);
+        if (ctx->asg.pf_on && ledger_max_variants(ctx->asg) >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "prefilled tracking: a request has 254 or more variants");
         if (int rc = ledger_sync_mirror(ctx)) return rc;
     }
     if (s && s->n_workers == HQ_WORKERS_RESIDENT && !(s->worker_id == nullptr && ctx->cluster_valid && ctx->mirror.valid))
@@ -1922,7 +1968,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         a.red_id.clear(); a.red_wid.clear(); a.red_rq.clear(); a.red_var.clear(); a.red_prio.clear();
         for (uint32_t i = 0; i < out->n_redirects; i++) {
             uint32_t rq = hqasg::RQ_LOOKUP; uint64_t pr = 0;
-            if (out->redirect_kind[i] == HQ_REDIRECT_FROM_PREFILL && s->prefill_off)  // out of a prefill set: not in the ready set, the snapshot's prefill sets know it
+            if (out->redirect_kind[i] == HQ_REDIRECT_FROM_PREFILL && s->prefill_off && !a.pf_on)  // (with tracking on the task's prefilled entry knows both)  out of a prefill set: not in the ready set, the snapshot's prefill sets know it
                 for (uint32_t q = 0; q < s->n_requests && rq == hqasg::RQ_LOOKUP; q++)
                     for (uint32_t j = s->prefill_off[q]; j < s->prefill_off[q + 1]; j++) if (s->prefill_task[j] == out->redirect_task[i]) { rq = q; pr = s->prefill_priority[q]; break; }
             a.red_id.push_back(out->redirect_task[i]); a.red_wid.push_back(out->redirect_worker[i] < W ? s->worker_id[out->redirect_worker[i]] : HQ_NO_WORKER);
@@ -2535,7 +2581,7 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     std::vector<uint32_t> src; src.reserve(W - n);
     for (uint32_t w = 0; w < W; w++) if (!gone[w]) src.push_back(w);
     if (int rc = ledger_guard(ctx)) return rc;
-    ctx->asg.rq_task.clear(); ctx->asg.rq_rq.clear(); ctx->asg.rq_prio.clear();
+    ctx->asg.rq_task.clear(); ctx->asg.rq_rq.clear(); ctx->asg.rq_prio.clear(); ctx->asg.rq_pf_task.clear();
     if (ctx->asg.on) { if (int rc = ledger_evict(ctx, n, worker_id)) return rc; }  // on_remove_worker: the lost workers' tasks leave the ledger (reactor.rs:64-147)
     if (int rc = cluster_repack(ctx, src, 0, nullptr, nullptr, nullptr)) return rc;
     if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W, nullptr)) return rc; }
@@ -2685,7 +2731,8 @@ int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id,
     HQ_HIP(hipSetDevice(ctx->device));
     Ledger &a = ctx->asg;
     a.on = false; a.pending = false; a.cap = 0; a.n_live = 0; a.n_tomb = 0; a.last_unknown = 0; a.stride = 0; a.stage_n = 0; a.last_host_bytes = 0;
-    a.rq_task.clear(); a.rq_rq.clear(); a.rq_prio.clear();
+    a.rq_task.clear(); a.rq_rq.clear(); a.rq_prio.clear(); a.rq_pf_task.clear();
+    a.pf_on = false; a.pf_live = 0; a.pf_stride = 0; a.pf_dirty = false;  // (tracking is asked for again on the new ledger)
     if (int rc = ledger_reserve(ctx, n)) return rc;
     HQ_HIP(hqasg::clear(ledger_table(a), ctx->stream));
     a.req_dirty = true;
@@ -2855,6 +2902,112 @@ int hqtick_cluster_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint6
     if (priority) *priority = ctx->asg.rq_prio.data();
     return 0;
 }
+
+int hqtick_cluster_last_requeued_prefilled(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (n) *n = (uint32_t)ctx->asg.rq_pf_task.size();
+    if (task_id) *task_id = ctx->asg.rq_pf_task.data();
+    return 0;
+}
+
+// ---- prefilled tasks in the ledger (SingleNodeTaskAssignment::prefilled_tasks) ----
+static int ledger_pf_pre(hqtick_ctx *ctx, const char *what) {
+    if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, std::string(what) + ": not on a sharded or replica context");
+    if (int rc = ledger_pre(ctx)) return rc;
+    return 0;
+}
+// one batch of ids (+ optional columns) staged in pinned memory and read in place; the counters come back behind the kernel
+static int ledger_pf_counters(hqtick_ctx *ctx) {
+    Ledger &a = ctx->asg;
+    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int hqtick_assigned_track_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint64_t *priority) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (int rc = ledger_pf_pre(ctx, "hqtick_assigned_track_prefilled")) return rc;
+    if (n && (!task_id || !worker_id || !rq || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_track_prefilled: null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
+    Ledger &a = ctx->asg;
+    if (ledger_max_variants(a) >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_track_prefilled: a request has 254 or more variants");
+    a.last_unknown = 0;
+    const uint32_t W = ctx->cl_W;
+    if (a.pf_on && a.pf_live) {  // a second call replaces the prefilled entries
+        uint32_t *c = ledger_ctr(ctx);
+        if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+        HQ_HIP(hqasg::pf_drop_all(ledger_table(a), a.ctr.as<uint32_t>(), ctx->stream));
+        if (int rc = ledger_pf_counters(ctx)) return rc;
+        a.n_tomb += c[hqasg::C_DONE]; a.pf_live = 0;
+    }
+    a.pf_on = false;  // (until the table below stands: ledger_sync_req must not widen a table that is being replaced)
+    if (int rc = ledger_reserve(ctx, n)) return rc;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    const uint32_t ns = std::max<uint32_t>(16, ((uint32_t)a.rq_off.size() - 1 + 15) & ~15u);
+    if (!a.pf.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc prefilled counts");
+    HQ_HIP(hipMemsetAsync(a.pf.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
+    a.pf_stride = ns; a.pf_on = true; a.pf_live = 0; a.pf_dirty = true; a.dirty = true;
+    if (!n) { HQ_HIP(hipStreamSynchronize(ctx->stream)); return 0; }
+    const size_t o_p = (size_t)n * 8, o_w = o_p + (size_t)n * 8, o_q = o_w + (size_t)n * 4, bytes = o_q + (size_t)n * 4 + 16;
+    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
+    memcpy(h, task_id, (size_t)n * 8); memcpy(h + o_p, priority, (size_t)n * 8); memcpy(h + o_w, worker_id, (size_t)n * 4); memcpy(h + o_q, rq, (size_t)n * 4);
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    HQ_HIP(hqasg::pf_seed(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), ledger_mn_rows(a.mn, W, a.mn_live), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<const uint32_t *>(d + o_w),
+                          reinterpret_cast<const uint32_t *>(d + o_q), reinterpret_cast<const uint64_t *>(d + o_p), a.ctr.as<uint32_t>(), ctx->stream));
+    if (int rc = ledger_pf_counters(ctx)) return rc;
+    if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
+    a.pf_live = c[hqasg::C_PF]; a.last_unknown = (uint64_t)c[hqasg::C_BAD] + c[hqasg::C_DUP];
+    return (int)c[hqasg::C_PF];
+}
+
+int hqtick_assigned_start_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint8_t *variant) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (int rc = ledger_pf_pre(ctx, "hqtick_assigned_start_prefilled")) return rc;
+    if (!ctx->asg.pf_on) return fail(ctx, HQTICK_E_INVALID, "prefilled tasks are not tracked (hqtick_assigned_track_prefilled)");
+    if (n && (!task_id || !variant)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_start_prefilled: null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
+    Ledger &a = ctx->asg;
+    a.last_unknown = 0;
+    if (!n) return 0;
+    if (int rc = ledger_sync_req(ctx)) return rc;
+    const size_t o_v = (size_t)n * 8, bytes = o_v + n + 16;
+    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
+    memcpy(h, task_id, (size_t)n * 8); memcpy(h + o_v, variant, n);
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    HQ_HIP(hqasg::pf_start(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), n, reinterpret_cast<const uint64_t *>(d), d + o_v, a.ctr.as<uint32_t>(), ctx->stream));
+    if (int rc = ledger_pf_counters(ctx)) return rc;
+    const uint32_t done = (uint32_t)std::min<uint64_t>(c[hqasg::C_DONE], a.pf_live);
+    a.pf_live -= done; a.n_live += done; a.last_unknown = (uint64_t)c[hqasg::C_UNKNOWN] + c[hqasg::C_BAD];
+    if (done) { a.dirty = true; a.pf_dirty = true; }
+    return (int)done;
+}
+
+int hqtick_assigned_unprefill(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (int rc = ledger_pf_pre(ctx, "hqtick_assigned_unprefill")) return rc;
+    if (!ctx->asg.pf_on) return fail(ctx, HQTICK_E_INVALID, "prefilled tasks are not tracked (hqtick_assigned_track_prefilled)");
+    if (n && !task_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_unprefill: null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
+    Ledger &a = ctx->asg;
+    a.last_unknown = 0;
+    if (!n) return 0;
+    if (!a.h_in.ensure((size_t)n * 8 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
+    memcpy(a.h_in.p, task_id, (size_t)n * 8);
+    uint32_t *c = ledger_ctr(ctx);
+    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
+    HQ_HIP(hqasg::pf_remove(ledger_table(a), ledger_rows(ctx), n, a.h_in.dev<uint64_t>(), a.ctr.as<uint32_t>(), ctx->stream));
+    if (int rc = ledger_pf_counters(ctx)) return rc;
+    const uint32_t done = (uint32_t)std::min<uint64_t>(c[hqasg::C_DONE], a.pf_live);
+    a.pf_live -= done; a.n_tomb += done; a.last_unknown = c[hqasg::C_UNKNOWN];
+    if (done) { a.dirty = true; a.pf_dirty = true; }
+    return (int)done;
+}
+
+uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on && ctx->asg.pf_on ? ctx->asg.pf_live : 0; }
 
 int hqtick_ready_compact(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;

@@ -131,13 +131,15 @@ struct CompactOut {
                             // the runs are 4 words (+ the low id of the run's first record) = hqtick_rec_run16
 };
 // Placement staging for the assignment ledger (assigned.h): with task != nullptr K5b also writes, for record out_off[w] + i, what the
-// ledger stores — in HBM, one array per field.  PREFILL records get meta = 0 (kind HQ_REC_PREFILL: skipped).  task == nullptr: nothing is written or read.
+// ledger stores — in HBM, one array per field.  PREFILL records get meta = 0 (kind HQ_REC_PREFILL) and the request id of their prefilling request
+// (pfq_rq [n_pfq], beside MapKeys::pfq_src): the ledger enters them only when it tracks prefilled tasks.  task == nullptr: nothing is written or read.
 struct Stage {
     uint64_t *task;   // [n_rec] task id
     uint32_t *rq;     // [n_rec] request id of the record's key
     uint32_t *row;    // [n_rec] worker row
     uint32_t *level;  // [n_rec] the item's priority level: index into the dense level table, or the global level rank of the ordered view
     uint16_t *meta;   // [n_rec] variant | kind << 8
+    const uint32_t *pfq_rq;  // [n_pfq] request id of prefilling request pi
 };
 hipError_t expand_mapping(MapKeys mk, uint32_t W, const uint64_t *sel_task, const uint16_t *sel_key, uint32_t Q, uint32_t max_items,
                     uint64_t *rec_task, uint8_t *rec_variant, uint8_t *rec_kind, uint32_t *err_flag, CompactOut co, uint32_t max_out, bool may_reorder, hipStream_t s, Stage st = Stage{});

@@ -559,9 +559,13 @@ static const uint32_t RUN_STAGE = 512;  // runs of one worker staged in LDS befo
 // f_task u64[max_out] | f_meta u16[max_out] (variant | kind << 8) behind the tables above.
 // Placement staging (st.task != nullptr: the assignment ledger is on): beside every record, in whatever form it leaves, the kernel stores the
 // ledger's entry into HBM at the record's index out_off[w] + i, one array per field (consecutive lanes store consecutive elements): task id, the key's
-// request id, this worker's row, the item's level and variant | kind << 8; PREFILL records get meta 0.  With st.task == nullptr nothing else changes.
+// request id, this worker's row, the item's level and variant | kind << 8; a PREFILL record gets the same fields with its prefilling request's id
+// (st.pfq_rq) and meta 0.  With st.task == nullptr nothing else changes.
 // LV: the per-item level type.  uint16_t: sel_key is K4's group key, level = key / Q, sort keys (level << 16 | item) in 32 bits.  uint32_t (the ordered view,
 // order.hip): sel_key is the run's global level rank (the launch passes Q = 1), sort keys (level << 32 | item) in 64 bits.
+__device__ __forceinline__ void stage_prefill(const Stage &st, uint32_t dst, uint64_t id, uint32_t pi, uint32_t w, uint32_t level) {
+    st.task[dst] = id; st.rq[dst] = st.pfq_rq[pi]; st.row[dst] = w; st.level[dst] = level; st.meta[dst] = 0;  // HQ_REC_PREFILL
+}
 template <typename LV>
 __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, const uint64_t *__restrict__ sel_task,
                                                         const LV *__restrict__ sel_key, uint32_t Q, uint32_t max_items,
@@ -639,7 +643,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
         if (j == 0xFFFFFFFFu) continue;
         const uint32_t cnt = mk.pfq_size[pi], src = mk.pfq_src[pi] + j * cnt;
         for (uint32_t t = threadIdx.x; t < cnt; t += blockDim.x) {
-            if (ledger && out0 + npf + t < out1) st.meta[out0 + npf + t] = 0;  // HQ_REC_PREFILL: the ledger skips it
+            if (ledger && out0 + npf + t < out1) stage_prefill(st, out0 + npf + t, sel_task[src + t], pi, w, (uint32_t)(sel_key[src + t] / Q));
             if (compact) { if (npf + t < max_out) { f_task[npf + t] = sel_task[src + t]; f_meta[npf + t] = 0x00FFu; } continue; }
             rec_task[out0 + npf + t] = sel_task[src + t];
             rec_variant[out0 + npf + t] = 0xFF;
@@ -653,11 +657,12 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
     for (uint32_t base = 0; base < (n > n_pf_staged ? n : n_pf_staged); base += blockDim.x) {
         const uint32_t u = base + threadIdx.x, e = u;
         const bool do_pf = u < n_pf_staged, do_item = e < n;
-        uint64_t pf_id = 0;
+        uint64_t pf_id = 0; uint32_t pf_pi = 0, pf_lv = 0;  // (pf_pi / pf_lv: the record's prefilling request and level, for the ledger's staging alone)
         if (do_pf) {
             uint32_t lo = 0, hi = mk.n_pfq;  // last chunk with p_start[pi] <= u (empty chunks have equal starts: the last one is the non-empty one)
             while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (p_start[mid] <= u) lo = mid; else hi = mid; }
             pf_id = sel_task[p_src[lo] + (u - p_start[lo])];
+            if (ledger) { pf_pi = lo; pf_lv = (uint32_t)(sel_key[p_src[lo] + (u - p_start[lo])] / Q); }
         }
         if (do_item) {
             uint32_t lo = 0, hi = nkeys;  // last key with k_start[k] <= e (it is the non-empty one)
@@ -671,7 +676,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
                 e_meta[e] = (uint16_t)(k_var[k] | 0x100u);
                 if (sort_cap) { atomicMin(&misc[0], (uint32_t)lv); atomicMax(&misc[1], (uint32_t)lv); }
                 if (do_pf) {
-                    if (ledger && out0 + u < out1) st.meta[out0 + u] = 0;
+                    if (ledger && out0 + u < out1) stage_prefill(st, out0 + u, pf_id, pf_pi, w, pf_lv);
                     if (compact) { if (u < max_out) { f_task[u] = pf_id; f_meta[u] = 0x00FFu; } }
                     else { rec_task[out0 + u] = pf_id; rec_variant[out0 + u] = 0xFF; rec_kind[out0 + u] = 0; }
                 }
@@ -706,7 +711,7 @@ __global__ void __launch_bounds__(256) k_expand_mapping(MapKeys mk, uint32_t W, 
             }
         }
         if (do_pf) {
-            if (ledger && out0 + u < out1) st.meta[out0 + u] = 0;
+            if (ledger && out0 + u < out1) stage_prefill(st, out0 + u, pf_id, pf_pi, w, pf_lv);
             if (compact) { if (u < max_out) { f_task[u] = pf_id; f_meta[u] = 0x00FFu; } }
             else { rec_task[out0 + u] = pf_id; rec_variant[out0 + u] = 0xFF; rec_kind[out0 + u] = 0; }  // HQ_REC_PREFILL
         }

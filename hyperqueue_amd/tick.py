@@ -385,6 +385,48 @@ class Tick:
         k = n.value
         return list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pq, k, np.uint32).tolist(), abi._np(pp, k, np.uint64).tolist())) if k else []
 
+    # -- prefilled tasks in the ledger (SingleNodeTaskAssignment::prefilled_tasks; opt-in on top of assigned_enable) --------
+    def assigned_track_prefilled(self, entries=()) -> int:
+        """tracking on, seeded with [(task, worker id, rq, priority)] in state Prefilled -> number entered"""
+        entries = list(entries)
+        t = np.ascontiguousarray([e[0] for e in entries], np.uint64); w = np.ascontiguousarray([e[1] for e in entries], np.uint32)
+        q = np.ascontiguousarray([e[2] for e in entries], np.uint32); p = np.ascontiguousarray([e[3] for e in entries], np.uint64)
+        f = self._lib.hqtick_assigned_track_prefilled
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u32p, abi.u64p]
+        return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), q.ctypes.data_as(abi.u32p), p.ctypes.data_as(abi.u64p)))
+
+    def assigned_start_prefilled(self, started, variants=None) -> int:
+        """task_from_prefilled_to_started for [(task, variant)] (or two columns: ids, variants) -> number started"""
+        if variants is None:
+            started = list(started)
+            t = np.ascontiguousarray([e[0] for e in started], np.uint64); v = np.ascontiguousarray([e[1] for e in started], np.uint8)
+        else:
+            t = np.ascontiguousarray(started, np.uint64); v = np.ascontiguousarray(variants, np.uint8)
+            assert len(t) == len(v)
+        f = self._lib.hqtick_assigned_start_prefilled
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u8p]
+        return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), v.ctypes.data_as(abi.u8p)))
+
+    def assigned_unprefill(self, task_id) -> int:
+        """remove_prefill_task for the ids (prefill disposal, cancel, reject outside a tick) -> number removed"""
+        t = np.ascontiguousarray(task_id, np.uint64)
+        f = self._lib.hqtick_assigned_unprefill
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p]
+        return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p)))
+
+    def assigned_prefilled_count(self) -> int:
+        f = self._lib.hqtick_assigned_prefilled_count
+        f.argtypes = [C.c_void_p]; f.restype = C.c_uint64
+        return int(f(self._ctx))
+
+    def cluster_last_requeued_prefilled(self) -> list:
+        """the ids among cluster_last_requeued() that were prefilled on a lost worker, ascending"""
+        n = C.c_uint32(); pt = abi.u64p()
+        f = self._lib.hqtick_cluster_last_requeued_prefilled
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p)]
+        self._chk(f(self._ctx, C.byref(n), C.byref(pt)))
+        return abi._np(pt, n.value, np.uint64).tolist() if n.value else []
+
     # -- device-resident dependency graph (include/hqtick.h, SURVEY §8 f1) --------------------------------------------------
     def _graph_last_ids(self) -> np.ndarray:
         n = C.c_uint64()

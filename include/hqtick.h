@@ -490,7 +490,8 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  *                              re-adds the reported tasks itself (hqtick_ready_add).  The host still owes
  *                              their instance-id bumps, crash counters (a task over its limit leaves with hqtick_ready_remove), prefill disposal and client
  *                              events; it no longer re-adds them.  A Retracting task whose redirect target was lost is among them (the Retracting table drops
- *                              the redirect, as before).  The lost worker's PREFILLED tasks are still the host's to re-add.
+ *                              the redirect, as before).  The lost worker's PREFILLED tasks are the host's to re-add unless prefilled tracking is on
+ *                              (hqtick_assigned_track_prefilled below): then they are among the reported tasks.
  * The tick: with the ledger on, a tick runs on the resident worker set (n_workers = HQ_WORKERS_RESIDENT, worker_id = NULL) and assigned_off = NULL; it takes
  * the per-worker (rq, variant) counts and the free rows from the ledger.  An assigned CSR in the snapshot is HQTICK_E_INVALID (the tick must not see two
  * truths).  The tick's placement — its ASSIGN records and its redirects (FROM_PREFILL / SAME_WORKER insert on the target, RETARGET moves the task from its
@@ -499,7 +500,36 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  * is consumed, ledger and membership calls are HQTICK_E_INVALID; a tick that is not consumed (any ready-set or graph delta, another tick) is abandoned with
  * its selection and never enters.  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
  * tasks have left the ready set, so the host uploads the worker set and enables the ledger again from its own view.
- * PREFILL records and prefill sets stay the host's.  hqtick_cluster_update_workers still works (remaining lifetime, corrections).
+ * hqtick_cluster_update_workers still works (remaining lifetime, corrections).
+ * Prefilled tasks (SingleNodeTaskAssignment::prefilled_tasks, server/worker.rs:40-46) are the ledger's too once tracking is switched on; with it off
+ * every call and every launch is as described above and the host sends prefilled_off / prefilled_rq with each snapshot.  A prefilled task is an entry
+ * of the same table with variant 0xFE (its worker: the one it is prefilled on; request and priority as for any entry); it counts in no (row, variant)
+ * slot and touches no free row, and raises a count of its own per (worker row, request) — what process_proactive_filling reads (mapping.rs:197-203).
+ *   hqtick_assigned_track_prefilled  tracking on, seeded with n prefilled tasks (ids, worker ids, rq, priority); n = 0 seeds nothing.  Needs an enabled
+ *                              ledger; a second call replaces the prefilled entries; whatever switches the ledger off switches tracking off.  Entries
+ *                              naming an unknown worker or request, an id already in the ledger or a worker without HQ_WORKER_SN are counted
+ *                              (hqtick_assigned_last_unknown) and enter nothing.  HQTICK_E_UNSUPPORTED if a request has 254 or more variants.  Returns the
+ *                              number entered.
+ *   hqtick_assigned_start_prefilled  task_from_prefilled_to_started (worker.rs:212-221) for n (id, variant) pairs: the entry takes the variant, the
+ *                              prefilled count drops, the (row, slot) count rises, free.remove is applied.  Request and priority are the entry's own.
+ *                              Ids that are not prefilled entries and variants the request does not have are counted and change nothing.  Returns the
+ *                              number started.
+ *   hqtick_assigned_unprefill  remove_prefill_task (mapping.rs:85-88) outside a tick: process_retracted of a dissolved prefill set (reactor.rs:34-62), cancel
+ *                              (:762-766), reject (:406-413), failed dependencies (:645-652).  The entry leaves, the prefilled count drops.  Ids that are
+ *                              not prefilled entries are counted and change nothing (an assigned entry is never touched).  Returns the number removed.  Where
+ *                              the task becomes Retracting the host calls hqtick_retracting_add as before.
+ *   hqtick_assigned_prefilled_count  prefilled entries (hqtick_assigned_count stays the number of assigned single-node entries).
+ *   hqtick_assigned_lookup     answers a prefilled id with its worker and variant 0xFE.
+ *   hqtick_assigned_release    of a prefilled id counts it as unknown; hqtick_assigned_add of one counts it as a duplicate.  Neither changes anything.
+ *   hqtick_cluster_remove_workers  the lost workers' prefilled entries leave with their other entries and are among hqtick_cluster_last_requeued, back in the
+ *                              resident ready set with their request and stored priority (move_prefilled_task_to_ready: a plain add).
+ *   hqtick_cluster_last_requeued_prefilled  the subset of the last hqtick_cluster_last_requeued that was prefilled, ascending: the host takes these out of
+ *                              its queue-side prefill sets and skips their crash counters.
+ * The tick with tracking on: a snapshot that carries prefilled_off is HQTICK_E_INVALID (two truths); the tick reads the per-(request, worker) prefilled counts
+ * from the ledger.  Its PREFILL records enter as prefilled entries with its ASSIGN records, at the same moment (an abandoned or failed tick enters nothing);
+ * a FROM_PREFILL redirect turns the task's prefilled entry into the assigned entry on the target, with the entry's own request and priority.
+ * Not covered by tracking: the queue-side prefill sets (prefill_off / _priority / _task / _worker stay in the snapshot, in the Set's iteration order);
+ * sharded contexts; integration/shim.rs.
  * Multi-node tasks (n_nodes > 0; Worker::mn_task, server/worker.rs:134-175) are the ledger's as well: per worker row the task it holds and whether it is
  * the root, per task one entry (root worker id, rq, priority).  A tick's multi-node placements (result.mn_*) enter with its ASSIGN records, at the same
  * moment (an abandoned or failed tick enters nothing): every listed worker loses HQ_WORKER_SN and records the task, the first as root (mapping.rs:133-154);
@@ -517,7 +547,8 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  *   hqtick_assigned_mn_count   multi-node tasks in the ledger (hqtick_assigned_count stays the number of single-node entries).
  *   hqtick_assigned_mn_workers the task's current workers, root first, the others by ascending id (valid until the next call on ctx); *n = 0: not a
  *                              multi-node task of the ledger.  hqtick_assigned_lookup of such an id answers with the root's worker id and variant 0xFF.
- * Not covered: a worker that takes a multi-node task while it still holds prefilled tasks (set_mn_task drops the set in the reference).
+ * Not covered: a worker that takes a multi-node task while it still holds prefilled tasks (set_mn_task drops the set in the reference; the ledger leaves
+ * its prefilled entries as they are).
  * The ledger does not depend on the form in which the records leave the device: the mapping kernel stages, beside every record it emits, the entry the
  * ledger stores (task, request, variant, worker row, priority level) in HBM, and the placement enters from there.  So the ledger works with plain records,
  * with HQTICK_FLAG_COMPACT_RECORDS / _DELTA16, and with a record sink (hqtick_set_record_sink, set before or after hqtick_assigned_enable, removed again
@@ -542,6 +573,11 @@ int hqtick_assigned_add_mn(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id,
                            const uint32_t *worker_id);
 uint64_t hqtick_assigned_mn_count(const hqtick_ctx *ctx);
 int hqtick_assigned_mn_workers(hqtick_ctx *ctx, uint64_t task_id, uint32_t *n, const uint32_t **worker_id);
+int hqtick_assigned_track_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint64_t *priority);
+int hqtick_assigned_start_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint8_t *variant);
+int hqtick_assigned_unprefill(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id);
+uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx);
+int hqtick_cluster_last_requeued_prefilled(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id);
 
 /*
  * Device-resident dependency graph (BASELINE config 5): the `Waiting{unfinished_deps}` counters and the consumer
