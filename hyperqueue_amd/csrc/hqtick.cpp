@@ -36,7 +36,7 @@
 #endif
 #include "devbuf.h"
 #include "graph.h"
-#include "assigned.h"
+#include "ledger.h"
 #include "hb_order.h"
 #include "host_model.h"
 #include "kernels.h"
@@ -68,46 +68,6 @@ struct PlanScratch {
     // cached worker_map iteration order (emulated) for the last worker-id set
     std::vector<uint32_t> cached_ids, cached_order;
 };
-
-// The assignment ledger (hqtick_assigned_*, ABI 12; csrc/assigned.h): the tasks running on the resident worker set, in HBM.
-struct Ledger {
-    bool on = false;
-    DevBuf key, wid, rq, var, prio, claim; uint32_t cap = 0; uint64_t n_live = 0, n_tomb = 0;   // the hash table (cap: a power of two)
-    DevBuf key2, wid2, rq2, var2, prio2, claim2;                                                  // ... the target of a rebuild
-    DevBuf counts, counts2; uint32_t stride = 0;                                                  // [W x stride] per (worker row, variant slot)
-    // multi-node tasks (assigned.h): [mn task u64 W][mn root u8 W][flags u8 W] beside the count rows, re-packed with them; mn_live = their entries in the table
-    DevBuf mn, mn2; uint64_t mn_live = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)
-    // prefilled tasks (assigned.h; hqtick_assigned_track_prefilled): pf u32 [W x pf_stride] per (worker row, request), re-packed with the count rows; pf_live = their
-    // entries in the table; h_pf: the host copy a tick reads (pf_dirty: a ledger call changed the table since)
-    bool pf_on = false; DevBuf pf, pf2; uint32_t pf_stride = 0; uint64_t pf_live = 0; std::vector<uint32_t> h_pf; bool pf_dirty = false;
-    std::vector<uint64_t> rq_pf_task;                                 // hqtick_cluster_last_requeued_prefilled
-    std::vector<uint32_t> var_nodes;                                  // n_nodes per variant slot of the request tables
-    std::vector<uint64_t> pmn_id; std::vector<uint32_t> pmn_rq, pmn_off{0}, pmn_wid;  // a tick's multi-node placements waiting with its records (worker ids, root first)
-    std::vector<uint32_t> mnw_out; std::vector<unsigned char> mnw_cols;              // hqtick_assigned_mn_workers
-    DevBuf req, wids, scratch, saved_rq, batch;                                                   // request tables, worker ids in row order, kernel scratch
-    // the placement staging K5b writes beside a tick's records (kernels.h: hqk::Stage): [task u64 | rq u32 | row u32 | level u32 | meta u16] x stage_n, in HBM
-    DevBuf stage; uint32_t stage_n = 0; bool stage_ordered = false; uint32_t stage_L = 0;
-    uint64_t last_host_bytes = 0;  // hqtick_assigned_last_host_bytes
-    DevBuf ctr; PinBuf h_ctr, h_in;   // (counters of one operation: in HBM, copied back behind the kernels)
-    // the request tables of the last snapshot (ResourceRqMap only grows: a slot keeps its number)
-    std::vector<uint32_t> rq_off{0}, vent_off{0}, ent_res; std::vector<uint8_t> ent_kind; std::vector<uint64_t> ent_amt; bool req_dirty = true;
-    std::vector<uint32_t> h_counts; bool dirty = false;  // the device tables changed since the host mirror (free rows, counts) was read
-    uint64_t last_unknown = 0;
-    // a tick's placement waiting for hqtick_ready_consume_last (two-call form)
-    bool pending = false; bool pend_saved = false;
-    uint32_t pend_W = 0; std::vector<uint64_t> pend_free;
-    std::vector<uint64_t> red_id, red_prio; std::vector<uint32_t> red_wid, red_rq; std::vector<uint8_t> red_var;
-    // hqtick_cluster_last_requeued
-    std::vector<uint64_t> rq_task, rq_prio; std::vector<uint32_t> rq_rq;
-    // what a ledger tick hands the host stages: per worker its distinct (rq, variant) pairs with counts (rebuilt from the count table when it changed)
-    std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_var; bool agg_dirty = true;
-    void release_all() {
-        DevBuf *b[] = {&key, &wid, &rq, &var, &prio, &claim, &key2, &wid2, &rq2, &var2, &prio2, &claim2, &counts, &counts2, &mn, &mn2, &pf, &pf2, &req, &wids, &scratch, &saved_rq, &batch, &stage, &ctr};
-        for (DevBuf *x : b) x->release();
-        h_ctr.release(); h_in.release();
-    }
-};
-
 }  // namespace
 
 struct hqtick_ctx {
@@ -180,7 +140,7 @@ struct hqtick_ctx {
     // launch state of the last tick (hqtick_time_kernel re-launches K1 / K4 on it)
     hqk::WaveGeom last_geom{}; uint32_t last_L = 0, last_Q = 0, last_G = 0; size_t last_tb = 0, last_plan_bytes = 0, last_hist_off = 0; bool last_valid = false;
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
-    Ledger asg;            // hqtick_assigned_* (ABI 12)
+    hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
     // sharded placement solve: the ranks split the coupled solve's price sweeps and the separable solve's class blocks, one small all-gather of host
@@ -1004,10 +964,11 @@ struct TickRun {
         ps.pf_drained.assign(Q, 0);
         ps.has_pf.assign((size_t)Q * W, 0);  // SingleNodeTaskAssignment::prefilled_tasks as per-(rq, worker) counts
         if (s->prefilled_off) for (uint32_t w = 0; w < W; w++) for (uint32_t i = s->prefilled_off[w]; i < s->prefilled_off[w + 1]; i++) if (s->prefilled_rq[i] < Q) ps.has_pf[(size_t)s->prefilled_rq[i] * W + w]++;
-        if (ctx->asg.on && ctx->asg.pf_on) {  // the ledger's prefilled counts (ledger_sync_mirror brought them back; a snapshot with prefilled_off was refused)
-            const Ledger &a = ctx->asg;
-            const uint32_t nq = std::min(Q, a.pf_stride);
-            if (a.h_pf.size() >= (size_t)W * a.pf_stride) for (uint32_t w = 0; w < W; w++) for (uint32_t q = 0; q < nq; q++) ps.has_pf[(size_t)q * W + w] = a.h_pf[(size_t)w * a.pf_stride + q];
+        if (ctx->asg.on && ctx->asg.tracking()) {  // the ledger's prefilled counts (its sync_mirror brought them back; a snapshot with prefilled_off was refused)
+            uint32_t pf_stride = 0;
+            const std::vector<uint32_t> &h_pf = ctx->asg.prefilled_host(&pf_stride);
+            const uint32_t nq = std::min(Q, pf_stride);
+            if (h_pf.size() >= (size_t)W * pf_stride) for (uint32_t w = 0; w < W; w++) for (uint32_t q = 0; q < nq; q++) ps.has_pf[(size_t)q * W + w] = h_pf[(size_t)w * pf_stride + q];
         }
         key_T.assign(nkeys, {});
         ctx->red_kind.clear();
@@ -1298,8 +1259,9 @@ struct TickRun {
             ctx->last_n_sel = n_sel; ctx->last_consumed = false;
             const bool consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;  // K4 writes the tombstones of what it selects
             if (consume_in_tick && ctx->asg.on && s->n_retracting) {  // only the redirects of Retracting tasks still look their request id up after K4 has tombstoned it (4 B per slot, device to device)
-                if (!ctx->asg.saved_rq.ensure(N * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids");
-                HQ_HIP(hipMemcpyAsync(ctx->asg.saved_rq.p, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                uint32_t *saved = ctx->asg.saved_rq(N);
+                if (!saved) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids");
+                HQ_HIP(hipMemcpyAsync(saved, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
             }
             ctx->last_geom = sc.geom; ctx->last_L = L; ctx->last_Q = Q; ctx->last_G = sc.G; ctx->last_tb = o_tb; ctx->last_plan_bytes = plan_words * 4; ctx->last_valid = true;
             ctx->last_ordered = sc.ordered;
@@ -1346,13 +1308,10 @@ struct TickRun {
                                               delta16 ? reinterpret_cast<uint16_t *>(drec) : nullptr};
             hqk::Stage stg{};
             if (ctx->asg.on && n_rec) {  // the ledger's copy of the placement stays in HBM, whatever form the records leave in
-                Ledger &a = ctx->asg;
-                if (!a.stage.ensure((size_t)n_rec * 22 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger staging");
-                unsigned char *sp = a.stage.as<unsigned char>();
-                stg = hqk::Stage{reinterpret_cast<uint64_t *>(sp), reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 8), reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 12),
-                                 reinterpret_cast<uint32_t *>(sp + (size_t)n_rec * 16), reinterpret_cast<uint16_t *>(sp + (size_t)n_rec * 20)};
+                hqasg::StageCols c{};
+                if (!ctx->asg.stage_for(n_rec, sc.ordered, sc.L, &c)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger staging");
+                stg = hqk::Stage{c.task, c.rq, c.row, c.level, c.meta};
                 stg.pfq_rq = ctx->d_map.as<uint32_t>() + o_pqr;
-                a.stage_n = n_rec; a.stage_ordered = sc.ordered; a.stage_L = sc.L;
             }
             bool expand_is_last = false;
             if (sc.ordered) HQ_HIP_LAST(hqk::expand_mapping_wide(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint32_t>(), max_items, k_task, k_var, k_kind,
@@ -1443,8 +1402,8 @@ struct TickRun {
         const std::function<void()> prep = [&]() {   // request/worker views: no GPU output needed yet
             fill_problem(pb, s, ctx->cfg, ev);
             if (ctx->asg.on && !s->assigned_off) {  // the ledger's per-worker (rq, variant) counts
-                const Ledger &a = ctx->asg;
-                pb.real.agg_off = a.agg_off.data(); pb.real.agg_rq = a.agg_rq.data(); pb.real.agg_cnt = a.agg_cnt.data(); pb.real.agg_variant = a.agg_var.data();
+                const hqasg::Agg g = ctx->asg.agg();
+                pb.real.agg_off = g.off; pb.real.agg_rq = g.rq; pb.real.agg_cnt = g.cnt; pb.real.agg_variant = g.var;
             }
             // HQTICK_FLAG_CERTIFICATE_ONLY is for ONE scheduler: replicas (a shard of several, a record sink that is merged with others', an exchange) must return the
             // canonical point — what the merge compares byte for byte — so the flag is ignored there (include/hqtick.h).
@@ -1507,360 +1466,20 @@ struct TickRun {
     }
 };
 
-
-// ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12; csrc/assigned.hip)
+// ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12): what hqasg::Ledger (ledger.h) is given of the context
 bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm; }  // (a record sink alone is one scheduler's output path, not a replica)
-
-// the request tables of a snapshot, kept when they differ from the ones the ledger has (a few hundred bytes compared)
-void ledger_take_requests(hqtick_ctx *ctx, const hqtick_snapshot *s) {
-    Ledger &a = ctx->asg;
-    const uint32_t Q = s->n_requests;
-    if (Q && (!s->rq_variant_off || !s->variant_entry_off)) return;  // (validate() reports it)
-    const uint32_t nv = Q ? s->rq_variant_off[Q] : 0, ne = nv ? s->variant_entry_off[nv] : 0;
-    if (ne && (!s->entry_resource || !s->entry_kind || !s->entry_amount)) return;
-    std::vector<uint32_t> vn(nv, 0);
-    if (s->variant_n_nodes) vn.assign(s->variant_n_nodes, s->variant_n_nodes + nv);
-    if (a.rq_off.size() == (size_t)Q + 1 && a.vent_off.size() == (size_t)nv + 1 && a.ent_res.size() == ne && a.var_nodes == vn && std::equal(a.rq_off.begin(), a.rq_off.end(), s->rq_variant_off ? s->rq_variant_off : a.rq_off.data()) &&
-        (nv == 0 || std::equal(a.vent_off.begin(), a.vent_off.end(), s->variant_entry_off)) && (ne == 0 || (std::equal(a.ent_res.begin(), a.ent_res.end(), s->entry_resource) &&
-        std::equal(a.ent_kind.begin(), a.ent_kind.end(), s->entry_kind) && std::equal(a.ent_amt.begin(), a.ent_amt.end(), s->entry_amount))))
-        return;
-    a.rq_off.assign(1, 0); if (Q) a.rq_off.assign(s->rq_variant_off, s->rq_variant_off + Q + 1);
-    a.vent_off.assign(1, 0); if (nv) a.vent_off.assign(s->variant_entry_off, s->variant_entry_off + nv + 1);
-    a.ent_res.assign(s->entry_resource, s->entry_resource + ne); a.ent_kind.assign(s->entry_kind, s->entry_kind + ne); a.ent_amt.assign(s->entry_amount, s->entry_amount + ne);
-    a.var_nodes.swap(vn);
-    a.req_dirty = true;
+hqasg::Env ledger_env(hqtick_ctx *ctx) {
+    return hqasg::Env{ctx->device, ctx->stream, ctx->d_cluster.as<unsigned char>(), ctx->cl_W, ctx->cl_R, ctx->d_tid.as<uint64_t>(), ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready,
+                      ctx->d_levels.as<uint64_t>(), &ctx->mirror.id, &ctx->mirror.flags, &ctx->mirror.free_};
 }
-
-uint32_t ledger_max_variants(const Ledger &a) {
-    uint32_t m = 0;
-    for (size_t q = 0; q + 1 < a.rq_off.size(); q++) m = std::max(m, a.rq_off[q + 1] - a.rq_off[q]);
-    return m;
-}
-hqasg::Table ledger_table(Ledger &a, bool second = false) {
-    if (second) return hqasg::Table{a.key2.as<uint64_t>(), a.wid2.as<uint32_t>(), a.rq2.as<uint32_t>(), a.var2.as<uint8_t>(), a.prio2.as<uint64_t>(), a.claim2.as<uint32_t>(), 0};
-    return hqasg::Table{a.key.as<uint64_t>(), a.wid.as<uint32_t>(), a.rq.as<uint32_t>(), a.var.as<uint8_t>(), a.prio.as<uint64_t>(), a.claim.as<uint32_t>(), a.cap - 1};
-}
-hqasg::Rows ledger_rows(hqtick_ctx *ctx) {
-    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
-    unsigned char *base = ctx->d_cluster.as<unsigned char>();
-    return hqasg::Rows{ctx->asg.wids.as<uint32_t>(), W, R, reinterpret_cast<const uint64_t *>(base), reinterpret_cast<uint64_t *>(base + (size_t)W * R * 8), ctx->asg.counts.as<uint32_t>(), ctx->asg.stride,
-                       ctx->asg.pf_on ? ctx->asg.pf.as<uint32_t>() : nullptr, ctx->asg.pf_on ? ctx->asg.pf_stride : 0u};
-}
-// the multi-node columns of W rows in `buf`; live: the uniform argument of the kernels that may skip them
-hqasg::MnRows ledger_mn_rows(const DevBuf &buf, uint32_t W, uint64_t live) {
-    unsigned char *b = buf.as<unsigned char>();
-    return hqasg::MnRows{reinterpret_cast<uint64_t *>(b), b + (size_t)W * 8, b + (size_t)W * 9, (uint32_t)std::min<uint64_t>(live, 0xFFFFFFFFu)};
-}
-hqasg::Req ledger_req(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    const size_t Q = a.rq_off.size() - 1, nv = a.vent_off.size() - 1, ne = a.ent_res.size();
-    const size_t o_vo = (Q + 1) * 4, o_res = o_vo + (nv + 1) * 4, o_amt = (o_res + ne * 4 + 7) & ~(size_t)7, o_kind = o_amt + ne * 8;
-    unsigned char *d = a.req.as<unsigned char>();
-    return hqasg::Req{reinterpret_cast<const uint32_t *>(d), reinterpret_cast<const uint32_t *>(d + o_vo), reinterpret_cast<const uint32_t *>(d + o_res), d + o_kind,
-                      reinterpret_cast<const uint64_t *>(d + o_amt), (uint32_t)Q};
-}
-// request tables + count-table width on the device, as the host has them
-int ledger_sync_req(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    const uint32_t nv = (uint32_t)a.vent_off.size() - 1, W = ctx->cl_W;
-    if (nv > a.stride) {  // new variant slots: a wider count table, rows copied over
-        const uint32_t ns = std::max<uint32_t>(16, (nv + 15) & ~15u);
-        if (!a.counts2.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
-        HQ_HIP(hipMemsetAsync(a.counts2.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
-        if (a.stride) HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W, nullptr, W, a.counts2.as<uint32_t>(), ns, a.stride, hqasg::MnRows{}, hqasg::MnRows{}, nullptr, ctx->stream));
-        std::swap(a.counts, a.counts2); a.stride = ns;
-        a.dirty = true;
-    }
-    if (a.pf_on && a.rq_off.size() - 1 > a.pf_stride) {  // new requests: a wider prefilled table, rows copied over (Q <= variant slots: never wider than the count rows)
-        const uint32_t ns = std::max<uint32_t>(16, ((uint32_t)a.rq_off.size() - 1 + 15) & ~15u);
-        if (!a.pf2.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc prefilled counts");
-        HQ_HIP(hipMemsetAsync(a.pf2.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
-        HQ_HIP(hqasg::repack_counts(a.pf.as<uint32_t>(), a.pf_stride, W, nullptr, W, a.pf2.as<uint32_t>(), ns, a.pf_stride, hqasg::MnRows{}, hqasg::MnRows{}, nullptr, ctx->stream));
-        std::swap(a.pf, a.pf2); a.pf_stride = ns;
-        a.dirty = true; a.pf_dirty = true;
-    }
-    if (!a.req_dirty) return 0;
-    const size_t Q = a.rq_off.size() - 1, ne = a.ent_res.size();
-    const size_t o_vo = (Q + 1) * 4, o_res = o_vo + ((size_t)nv + 1) * 4, o_amt = (o_res + ne * 4 + 7) & ~(size_t)7, o_kind = o_amt + ne * 8, bytes = o_kind + ne + 64;
-    std::vector<unsigned char> h(bytes, 0);
-    memcpy(h.data(), a.rq_off.data(), (Q + 1) * 4); memcpy(h.data() + o_vo, a.vent_off.data(), ((size_t)nv + 1) * 4);
-    if (ne) { memcpy(h.data() + o_res, a.ent_res.data(), ne * 4); memcpy(h.data() + o_amt, a.ent_amt.data(), ne * 8); memcpy(h.data() + o_kind, a.ent_kind.data(), ne); }
-    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (the previous tables may still be read by a queued kernel)
-    if (!a.req.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request tables");
-    HQ_HIP(hipMemcpy(a.req.p, h.data(), bytes, hipMemcpyHostToDevice));
-    a.req_dirty = false;
-    return 0;
-}
-int ledger_upload_wids(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    const std::vector<uint32_t> &id = ctx->mirror.id;
-    if (!a.wids.ensure(id.size() * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger worker ids");
-    if (!id.empty()) HQ_HIP(hipMemcpyAsync(a.wids.p, id.data(), id.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
-    return 0;
-}
-// the flags column from the mirror (hqtick_assigned_enable, hqtick_cluster_set_flags: the host is the writer, the mirror is current)
-int ledger_upload_flags(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    const uint32_t W = ctx->cl_W;
-    if (W) HQ_HIP(hipMemcpyAsync(ledger_mn_rows(a.mn, W, 0).flags, ctx->mirror.flags.data(), W, hipMemcpyHostToDevice, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
-    return 0;
-}
-uint32_t *ledger_ctr(hqtick_ctx *ctx) {
-    if (!ctx->asg.h_ctr.ensure(64) || !ctx->asg.ctr.ensure(64) || hipMemsetAsync(ctx->asg.ctr.p, 0, 64, ctx->stream) != hipSuccess) return nullptr;
-    uint32_t *c = ctx->asg.h_ctr.as<uint32_t>();
-    for (uint32_t i = 0; i < hqasg::C_N; i++) c[i] = 0;
-    return c;
-}
-// room for `more` entries: live + tombstones + more stay under half the capacity; otherwise the live entries move to a fresh table
-int ledger_reserve(hqtick_ctx *ctx, uint64_t more) {
-    Ledger &a = ctx->asg;
-    const uint64_t live = a.n_live + a.mn_live + (a.pf_on ? a.pf_live : 0);
-    if (a.cap && (live + a.n_tomb + more) * 2 <= a.cap) return 0;
-    uint64_t want = 1024; while (want < (live + more) * 4) want <<= 1;
-    if (want > (1ull << 31)) return fail(ctx, HQTICK_E_CAPACITY, "assignment ledger: more than 2^29 entries");
-    const uint32_t nc = (uint32_t)want;
-    if (!a.key2.ensure((size_t)nc * 8) || !a.wid2.ensure((size_t)nc * 4) || !a.rq2.ensure((size_t)nc * 4) || !a.var2.ensure(nc) || !a.prio2.ensure((size_t)nc * 8) || !a.claim2.ensure((size_t)nc * 4))
-        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment ledger");
-    hqasg::Table to = ledger_table(a, true); to.mask = nc - 1;
-    HQ_HIP(hqasg::clear(to, ctx->stream));
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    if (a.cap) HQ_HIP(hqasg::rehash(ledger_table(a), to, a.ctr.as<uint32_t>(), ctx->stream));
-    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (a.cap && (c[hqasg::C_FULL] || c[hqasg::C_DONE] != live)) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: rebuild lost entries");
-    std::swap(a.key, a.key2); std::swap(a.wid, a.wid2); std::swap(a.rq, a.rq2); std::swap(a.var, a.var2); std::swap(a.prio, a.prio2); std::swap(a.claim, a.claim2);
-    a.cap = nc; a.n_tomb = 0;
-    return 0;
-}
-// an insert batch from host columns (staged in pinned memory, read in place)
-int ledger_insert_host(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free,
-                       const uint32_t *col_rq, uint32_t *fresh, uint32_t *bad, uint32_t *dup) {
-    Ledger &a = ctx->asg;
-    *fresh = *bad = *dup = 0;
-    if (!n) return 0;
-    if (int rc = ledger_reserve(ctx, n)) return rc;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    const size_t o_w = (size_t)n * 8, o_q = o_w + (size_t)n * 4, o_p = (o_q + (size_t)n * 4 + 7) & ~(size_t)7, o_v = o_p + (size_t)n * 8, bytes = o_v + n + 16;
-    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
-    memcpy(h, id, (size_t)n * 8); memcpy(h + o_w, wid, (size_t)n * 4); memcpy(h + o_v, var, n);
-    if (rq) memcpy(h + o_q, rq, (size_t)n * 4); else for (uint32_t i = 0; i < n; i++) reinterpret_cast<uint32_t *>(h + o_q)[i] = hqasg::RQ_LOOKUP;
-    if (prio) memcpy(h + o_p, prio, (size_t)n * 8); else memset(h + o_p, 0, (size_t)n * 8);
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    hqasg::Items it{};
-    it.n = n; it.id = reinterpret_cast<const uint64_t *>(d); it.wid = reinterpret_cast<const uint32_t *>(d + o_w); it.rq = reinterpret_cast<const uint32_t *>(d + o_q);
-    it.variant = d + o_v; it.prio = reinterpret_cast<const uint64_t *>(d + o_p);
-    it.col_id = ctx->d_tid.as<uint64_t>(); it.col_prio = ctx->d_tprio.as<uint64_t>(); it.col_rq = col_rq ? col_rq : ctx->d_trq.as<uint32_t>(); it.col_n = ctx->n_ready;
-    HQ_HIP(hqasg::insert(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), it, upsert, apply_free, a.ctr.as<uint32_t>(), ctx->stream));
-    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
-    *fresh = c[hqasg::C_OUT]; *bad = c[hqasg::C_BAD]; *dup = c[hqasg::C_DUP];
-    a.n_live += c[hqasg::C_OUT]; a.dirty = true;
-    if (const uint32_t from_pf = std::min<uint64_t>(c[hqasg::C_PF], a.pf_live)) { a.pf_live -= from_pf; a.n_live += from_pf; a.pf_dirty = true; }  // FROM_PREFILL redirects: prefilled entries that are assigned entries now
-    return 0;
-}
-
-// multi-node placements (task i on the workers wid[off[i] .. off[i + 1]), root first) enter table and rows; prio == nullptr: looked up in the ready-set columns.
-// Few per call and built on the host, like the redirects: they are staged in pinned memory and read in place.
-int ledger_mn_enter(hqtick_ctx *ctx, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid, int check,
-                    uint32_t *entered, uint32_t *refused) {
-    Ledger &a = ctx->asg;
-    *entered = *refused = 0;
-    if (!n) return 0;
-    const uint32_t W = ctx->cl_W, n_wid = off[n];
-    if (int rc = ledger_reserve(ctx, n)) return rc;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    const size_t o_p = (size_t)n * 8, o_q = o_p + (size_t)n * 8, o_o = o_q + (size_t)n * 4, o_w = o_o + ((size_t)n + 1) * 4, bytes = o_w + (size_t)n_wid * 4 + 16;
-    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    if (!a.scratch.ensure((size_t)W * 4 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
-    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
-    memcpy(h, id, (size_t)n * 8); memcpy(h + o_q, rq, (size_t)n * 4); memcpy(h + o_o, off, ((size_t)n + 1) * 4); memcpy(h + o_w, wid, (size_t)n_wid * 4);
-    if (prio) memcpy(h + o_p, prio, (size_t)n * 8);
-    HQ_HIP(hipMemsetAsync(a.scratch.p, 0xFF, (size_t)W * 4 + 16, ctx->stream));
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    hqasg::MnItems it{};
-    it.n = n; it.n_wid = n_wid; it.id = reinterpret_cast<const uint64_t *>(d); it.prio = prio ? reinterpret_cast<const uint64_t *>(d + o_p) : nullptr;
-    it.rq = reinterpret_cast<const uint32_t *>(d + o_q); it.off = reinterpret_cast<const uint32_t *>(d + o_o); it.wid = reinterpret_cast<const uint32_t *>(d + o_w);
-    it.col_id = ctx->d_tid.as<uint64_t>(); it.col_prio = ctx->d_tprio.as<uint64_t>(); it.col_n = ctx->n_ready;
-    HQ_HIP(hqasg::mn_enter(ledger_table(a), ledger_rows(ctx), ledger_mn_rows(a.mn, W, a.mn_live), it, a.scratch.as<uint32_t>(), check, a.ctr.as<uint32_t>(), ctx->stream));
-    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
-    *entered = c[hqasg::C_OUT]; *refused = c[hqasg::C_BAD] + c[hqasg::C_DUP];
-    a.mn_live += c[hqasg::C_OUT];
-    if (c[hqasg::C_OUT]) { a.dirty = true; a.flags_dirty = true; }
-    return 0;
-}
-
-// a tick's placement becomes ledger state: its ASSIGN records and its redirects (upserts: a re-targeted task moves), free rows = the tick's new_free
-int ledger_apply_tick(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    a.pending = false;
-    const uint32_t W = ctx->cl_W, n_rec = a.stage_n;
-    const uint32_t *col_rq = a.pend_saved ? a.saved_rq.as<uint32_t>() : ctx->d_trq.as<uint32_t>();
-    a.stage_n = 0; a.last_host_bytes = 0;  // (no record data crosses from the host: the entries are where K5b staged them)
-    if (a.pend_W != W || a.pend_free.size() != (size_t)W * ctx->cl_R) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the worker set changed under a pending tick");
-    if (n_rec) {
-        if (int rc = ledger_reserve(ctx, n_rec)) return rc;
-        if (int rc = ledger_sync_req(ctx)) return rc;
-        uint32_t *c = ledger_ctr(ctx);
-        if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-        const unsigned char *sp = a.stage.as<unsigned char>();
-        hqasg::Staged st{};
-        st.n = n_rec; st.task = reinterpret_cast<const uint64_t *>(sp); st.rq = reinterpret_cast<const uint32_t *>(sp + (size_t)n_rec * 8);
-        st.row = reinterpret_cast<const uint32_t *>(sp + (size_t)n_rec * 12); st.level = reinterpret_cast<const uint32_t *>(sp + (size_t)n_rec * 16);
-        st.meta = reinterpret_cast<const uint16_t *>(sp + (size_t)n_rec * 20);
-        if (a.stage_ordered) { st.col_id = ctx->d_tid.as<uint64_t>(); st.col_prio = ctx->d_tprio.as<uint64_t>(); st.col_n = ctx->n_ready; }  // the view's run table is in host memory
-        else { st.levels = ctx->d_levels.as<uint64_t>(); st.n_levels = a.stage_L; }
-        HQ_HIP(hqasg::insert_staged(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), st, a.ctr.as<uint32_t>(), ctx->stream));
-        HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        if (c[hqasg::C_FULL] || c[hqasg::C_BAD] || (a.pf_on && c[hqasg::C_DUP])) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a record of the tick could not be entered");
-        a.n_live += c[hqasg::C_OUT];
-        if (a.pf_on && c[hqasg::C_PF]) { a.pf_live += c[hqasg::C_PF]; a.pf_dirty = true; }  // its PREFILL records
-    }
-    if (!a.red_id.empty()) {
-        uint32_t fresh = 0, bad = 0, dup = 0;
-        if (int rc = ledger_insert_host(ctx, (uint32_t)a.red_id.size(), a.red_id.data(), a.red_wid.data(), a.red_rq.data(), a.red_var.data(), a.red_prio.data(), 1, 0, col_rq, &fresh, &bad, &dup)) return rc;
-        if (bad) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a redirect of the tick could not be entered");
-    }
-    if (!a.pmn_id.empty()) {  // the multi-node placements (mapping.rs:133-154): the solver took free workers, so nothing is checked twice
-        uint32_t entered = 0, refused = 0;
-        if (int rc = ledger_mn_enter(ctx, (uint32_t)a.pmn_id.size(), a.pmn_id.data(), a.pmn_rq.data(), nullptr, a.pmn_off.data(), a.pmn_wid.data(), 0, &entered, &refused)) return rc;
-        if (refused || entered != a.pmn_id.size()) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: a multi-node placement of the tick could not be entered");
-        a.pmn_id.clear();
-    }
-    // free rows: the tick's new_free (Worker::insert_sn_task / remove_sn_task of mapping.rs, computed by the tick itself)
-    if (W && ctx->cl_R) {
-        unsigned char *base = ctx->d_cluster.as<unsigned char>();
-        HQ_HIP(hipMemcpyAsync(base + (size_t)W * ctx->cl_R * 8, a.pend_free.data(), (size_t)W * ctx->cl_R * 8, hipMemcpyHostToDevice, ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->mirror.free_ = a.pend_free;
-    }
-    a.dirty = true;
-    return 0;
-}
-
+int ledger_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->asg.err; return rc; }
 // a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
 // (an add, a remove, a compaction, a graph call, an upload) clears last_valid or sets last_consumed — and with it the placement is dropped too
-bool ledger_pending_live(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    if (a.pending && !(ctx->last_valid && !ctx->last_consumed)) a.pending = false;
-    return a.pending;
-}
+bool ledger_pending_live(hqtick_ctx *ctx) { return ctx->asg.pending_live(ctx->last_valid && !ctx->last_consumed); }
 int ledger_guard(hqtick_ctx *ctx) {
     if (ctx->asg.on && ledger_pending_live(ctx)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the last tick's placement is pending (hqtick_ready_consume_last first)");
     return 0;
 }
-// the count rows follow a membership change: row w of the new set = old row src[w] (>= W_old: a new worker, zero)
-// The multi-node columns move in the same launch; add_flags: the HQ_WORKER_* bytes of the new workers (nullptr: fresh single-node workers)
-int ledger_repack(hqtick_ctx *ctx, const std::vector<uint32_t> &src, uint32_t W_old, const uint8_t *add_flags) {
-    Ledger &a = ctx->asg;
-    const uint32_t W_new = (uint32_t)src.size();
-    if (!a.counts2.ensure((size_t)W_new * a.stride * 4 + 64) || !a.batch.ensure((size_t)W_new * 5 + 16) || !a.mn2.ensure((size_t)W_new * 10 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
-    hqasg::PfMove pfm{};
-    if (a.pf_on) {  // the prefilled counts move in the same launch (pf_stride <= stride: both are the request tables' sizes rounded up alike)
-        if (a.pf_stride > a.stride) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: prefilled table wider than the count rows");
-        if (!a.pf2.ensure((size_t)W_new * a.pf_stride * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc prefilled counts");
-        pfm = hqasg::PfMove{a.pf.as<uint32_t>(), a.pf_stride, a.pf2.as<uint32_t>(), a.pf_stride, a.pf_stride};
-    }
-    std::vector<unsigned char> hb((size_t)W_new * 5 + 16, 0);  // [src row u32 W_new][flags of the new rows u8 W_new]: one copy
-    if (W_new) memcpy(hb.data(), src.data(), (size_t)W_new * 4);
-    for (uint32_t w = 0; w < W_new; w++) hb[(size_t)W_new * 4 + w] = src[w] >= W_old ? (add_flags ? add_flags[src[w] - W_old] : (uint8_t)HQ_WORKER_SN) : (uint8_t)0;
-    HQ_HIP(hipMemcpyAsync(a.batch.p, hb.data(), hb.size(), hipMemcpyHostToDevice, ctx->stream));
-    HQ_HIP(hqasg::repack_counts(a.counts.as<uint32_t>(), a.stride, W_old, a.batch.as<uint32_t>(), W_new, a.counts2.as<uint32_t>(), a.stride, a.stride,
-                                ledger_mn_rows(a.mn, W_old, a.mn_live), ledger_mn_rows(a.mn2, W_new, a.mn_live), a.batch.as<uint8_t>() + (size_t)W_new * 4, ctx->stream, pfm));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));  // (pageable source)
-    std::swap(a.counts, a.counts2); std::swap(a.mn, a.mn2);
-    if (a.pf_on) { std::swap(a.pf, a.pf2); a.pf_dirty = true; }
-    a.dirty = true;
-    return 0;
-}
-// every entry of the lost workers leaves the ledger; (id, rq, priority) come back ascending by id (hqtick_cluster_last_requeued)
-int ledger_evict(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
-    Ledger &a = ctx->asg;
-    std::vector<uint32_t> lost(worker_id, worker_id + n);
-    std::sort(lost.begin(), lost.end());
-    const uint64_t pf_live = a.pf_on ? a.pf_live : 0;
-    const uint64_t cap_out = a.n_live + a.mn_live + pf_live + 1;
-    const size_t o_l = 0, o_id = ((size_t)n * 4 + 7) & ~(size_t)7, o_p = o_id + cap_out * 8, o_q = o_p + cap_out * 8, o_v = o_q + cap_out * 4, bytes = o_v + cap_out + 16;
-    if (!a.scratch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
-    unsigned char *d = a.scratch.as<unsigned char>();
-    HQ_HIP(hipMemcpyAsync(d + o_l, lost.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    HQ_HIP(hqasg::evict(ledger_table(a), n, reinterpret_cast<const uint32_t *>(d + o_l), reinterpret_cast<uint64_t *>(d + o_id), reinterpret_cast<uint32_t *>(d + o_q),
-                        reinterpret_cast<uint64_t *>(d + o_p), d + o_v, (uint32_t)cap_out, a.ctr.as<uint32_t>(), ctx->stream));
-    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    const uint32_t k = c[hqasg::C_OUT];
-    const uint32_t k_mn = c[hqasg::C_MN], k_pf = c[hqasg::C_PF];
-    if (k >= cap_out || (uint64_t)k_mn + k_pf > k || k_mn > a.mn_live || k_pf > pf_live || k - k_mn - k_pf > a.n_live) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
-    if (k_mn) {  // a lost ROOT (reactor.rs:107-128): the task's other rows are free single-node workers again, before the rows are re-packed
-        HQ_HIP(hqasg::mn_reset_rows(ledger_table(a), ledger_rows(ctx), ledger_mn_rows(a.mn, ctx->cl_W, a.mn_live), ctx->stream));
-        a.flags_dirty = true;
-    }
-    std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k); std::vector<uint8_t> var(k);
-    if (k && k_pf) HQ_HIP(hipMemcpy(var.data(), d + o_v, k, hipMemcpyDeviceToHost));
-    if (k) {
-        HQ_HIP(hipMemcpy(id.data(), d + o_id, (size_t)k * 8, hipMemcpyDeviceToHost));
-        HQ_HIP(hipMemcpy(pr.data(), d + o_p, (size_t)k * 8, hipMemcpyDeviceToHost));
-        HQ_HIP(hipMemcpy(rq.data(), d + o_q, (size_t)k * 4, hipMemcpyDeviceToHost));
-    }
-    std::vector<uint32_t> ord(k);
-    for (uint32_t i = 0; i < k; i++) ord[i] = i;
-    std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return id[x] < id[y]; });
-    for (uint32_t i : ord) {
-        a.rq_task.push_back(id[i]); a.rq_prio.push_back(pr[i]); a.rq_rq.push_back(rq[i]);
-        if (k_pf && var[i] == hqasg::PF_VARIANT) a.rq_pf_task.push_back(id[i]);  // move_prefilled_task_to_ready: the subset the host takes out of its prefill sets
-    }
-    a.n_live -= k - k_mn - k_pf; a.mn_live -= k_mn; a.n_tomb += k; a.dirty = true;
-    if (k_pf) { a.pf_live -= k_pf; a.pf_dirty = true; }
-    return 0;
-}
-
-// the host mirror (free rows, counts) from the device tables: one synchronisation, two copies; then the assigned CSR of the host stages
-int ledger_sync_mirror(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    if (a.dirty) {
-        ctx->mirror.free_.resize((size_t)W * R); a.h_counts.resize((size_t)W * a.stride);
-        unsigned char *base = ctx->d_cluster.as<unsigned char>();
-        if (W && R) HQ_HIP(hipMemcpyAsync(ctx->mirror.free_.data(), base + (size_t)W * R * 8, (size_t)W * R * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (W && a.stride) HQ_HIP(hipMemcpyAsync(a.h_counts.data(), a.counts.p, (size_t)W * a.stride * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (W && a.flags_dirty) {  // a ledger call moved SN bits (set_mn_task / reset_mn_task): the tick reads worker_flags from the mirror
-            ctx->mirror.flags.resize(W);
-            HQ_HIP(hipMemcpyAsync(ctx->mirror.flags.data(), ledger_mn_rows(a.mn, W, 0).flags, W, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (a.pf_on && a.pf_dirty) {  // a ledger call changed the prefilled counts: what the tick's has_pf is filled from
-            a.h_pf.resize((size_t)W * a.pf_stride);
-            if (W) HQ_HIP(hipMemcpyAsync(a.h_pf.data(), a.pf.p, (size_t)W * a.pf_stride * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        a.dirty = false; a.agg_dirty = true; a.flags_dirty = false; a.pf_dirty = false;
-    }
-    if (!a.agg_dirty) return 0;
-    // O(W x variant slots), not O(running tasks): the count table is what GapCache and Worker::is_free need
-    const uint32_t Q = (uint32_t)a.rq_off.size() - 1;
-    a.agg_off.assign((size_t)W + 1, 0); a.agg_rq.clear(); a.agg_cnt.clear(); a.agg_var.clear();
-    for (uint32_t w = 0; w < W; w++) {
-        const uint32_t *row = a.h_counts.data() + (size_t)w * a.stride;
-        for (uint32_t q = 0; q < Q; q++)
-            for (uint32_t v = a.rq_off[q]; v < a.rq_off[q + 1]; v++)
-                if (row[v]) { a.agg_rq.push_back(q); a.agg_var.push_back((uint8_t)(v - a.rq_off[q])); a.agg_cnt.push_back(row[v]); }
-        a.agg_off[w + 1] = (uint32_t)a.agg_rq.size();
-    }
-    a.agg_dirty = false;
-    return 0;
-}
-
 
 int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool use_resident) {
     hqtick_snapshot full;
@@ -1869,12 +1488,12 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "assignment ledger on a sharded or replica context");
         if (s->worker_id || !(ctx->cluster_valid && ctx->mirror.valid)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
         if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
-        if (ctx->asg.pf_on && s->prefilled_off) return fail(ctx, HQTICK_E_INVALID, "prefilled tracking on: the snapshot must not carry a prefilled CSR as well");
+        if (ctx->asg.tracking() && s->prefilled_off) return fail(ctx, HQTICK_E_INVALID, "prefilled tracking on: the snapshot must not carry a prefilled CSR as well");
         HQ_HIP(hipSetDevice(ctx->device));
-        ctx->asg.pending = false; ctx->asg.stage_n = 0;  // (a tick that was never consumed is abandoned, as its selection is; its staging is never read)
-        ledger_take_requests(ctx, s);
-        if (ctx->asg.pf_on && ledger_max_variants(ctx->asg) >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "prefilled tracking: a request has 254 or more variants");
-        if (int rc = ledger_sync_mirror(ctx)) return rc;
+        ctx->asg.abandon_tick();
+        ctx->asg.take_requests(s);
+        if (ctx->asg.tracking() && ctx->asg.max_variants() >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "prefilled tracking: a request has 254 or more variants");
+        if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     }
     if (s && s->n_workers == HQ_WORKERS_RESIDENT && !(s->worker_id == nullptr && ctx->cluster_valid && ctx->mirror.valid))
         return fail(ctx, HQTICK_E_INVALID, s->worker_id ? "n_workers == HQ_WORKERS_RESIDENT with worker arrays in the snapshot"
@@ -1961,30 +1580,11 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         }
     }
     if (rc >= 0 && ctx->asg.on) {  // the placement enters the ledger when it becomes state: now, or at hqtick_ready_consume_last in the two-call form
-        Ledger &a = ctx->asg;
-        const uint32_t W = s->n_workers;
-        a.pend_W = W;
-        a.pend_free = ctx->new_free;
-        a.red_id.clear(); a.red_wid.clear(); a.red_rq.clear(); a.red_var.clear(); a.red_prio.clear();
-        for (uint32_t i = 0; i < out->n_redirects; i++) {
-            uint32_t rq = hqasg::RQ_LOOKUP; uint64_t pr = 0;
-            if (out->redirect_kind[i] == HQ_REDIRECT_FROM_PREFILL && s->prefill_off && !a.pf_on)  // (with tracking on the task's prefilled entry knows both)  out of a prefill set: not in the ready set, the snapshot's prefill sets know it
-                for (uint32_t q = 0; q < s->n_requests && rq == hqasg::RQ_LOOKUP; q++)
-                    for (uint32_t j = s->prefill_off[q]; j < s->prefill_off[q + 1]; j++) if (s->prefill_task[j] == out->redirect_task[i]) { rq = q; pr = s->prefill_priority[q]; break; }
-            a.red_id.push_back(out->redirect_task[i]); a.red_wid.push_back(out->redirect_worker[i] < W ? s->worker_id[out->redirect_worker[i]] : HQ_NO_WORKER);
-            a.red_rq.push_back(rq); a.red_var.push_back(out->redirect_variant[i]); a.red_prio.push_back(pr);
-        }
-        a.pmn_id.clear(); a.pmn_rq.clear(); a.pmn_off.assign(1, 0); a.pmn_wid.clear();
-        for (uint32_t i = 0; i < out->n_mn && i < ctx->mn_rq.size(); i++) {
-            a.pmn_id.push_back(out->mn_task[i]); a.pmn_rq.push_back(ctx->mn_rq[i]);
-            for (uint32_t j = out->mn_worker_off[i]; j < out->mn_worker_off[i + 1]; j++) a.pmn_wid.push_back(out->mn_worker[j] < W ? s->worker_id[out->mn_worker[j]] : HQ_NO_WORKER);
-            a.pmn_off.push_back((uint32_t)a.pmn_wid.size());
-        }
         const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
-        a.pend_saved = in_tick && s->n_retracting != 0; a.pending = true;  // (the column copy is taken only for the redirects of Retracting tasks)
+        ctx->asg.collect_tick(s, out, ctx->new_free, ctx->mn_rq, in_tick && s->n_retracting != 0);  // (the column copy is taken only for the redirects of Retracting tasks)
         if (!use_resident || in_tick) {
-            if (int r2 = ledger_apply_tick(ctx)) {  // (the tick's tasks have left the ready set: without the placement the ledger is no longer the truth)
-                a.on = false; a.pending = false;
+            if (int r2 = ledger_fail(ctx, ctx->asg.apply_tick(ledger_env(ctx)))) {  // (the tick's tasks have left the ready set: without the placement the ledger is no longer the truth)
+                ctx->asg.on = false; ctx->asg.pending = false;
                 ctx->err += " (the assignment ledger is switched off: upload the worker set and enable it again)";
                 return r2;
             }
@@ -2187,7 +1787,7 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) {
     if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
     if (ledger_pending_live(ctx)) {  // the last tick's placement enters the assignment ledger (before the selection's request ids become tombstones)
         HQ_HIP(hipSetDevice(ctx->device));
-        if (int rc = ledger_apply_tick(ctx)) {
+        if (int rc = ledger_fail(ctx, ctx->asg.apply_tick(ledger_env(ctx)))) {
             ctx->asg.on = false;
             ctx->err += " (the assignment ledger is switched off: upload the worker set and enable it again)";
             return rc;
@@ -2455,7 +2055,7 @@ int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) {
     ctx->cl_rt.assign(h + L.o_amt, h + L.bytes);
     ctx->cl_W = W; ctx->cl_R = R; ctx->cluster_valid = true;
     ctx->asg.on = false; ctx->asg.pending = false;  // a new worker set: the ledger is enabled (seeded) again for it
-    ledger_take_requests(ctx, s);
+    ctx->asg.take_requests(s);
     {   // the host mirror (ABI 7)
         hqtick_ctx::ClusterMirror &m = ctx->mirror;
         m.id.assign(s->worker_id, s->worker_id + W);
@@ -2552,7 +2152,7 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
     if (remaining_ns) rem.assign(remaining_ns, remaining_ns + n);
     if (int rc = ledger_guard(ctx)) return rc;
     if (int rc = cluster_repack(ctx, src, n, total_rows, free_rows, rem.data())) return rc;
-    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W, flags)) return rc; }
+    if (ctx->asg.on) { if (int rc = ctx->asg.repack(ledger_env(ctx), src, W, flags)) return ledger_fail(ctx, rc); }
     m.id.insert(m.id.end(), worker_id, worker_id + n);
     m.total.insert(m.total.end(), total_rows, total_rows + (size_t)n * R); m.free_.insert(m.free_.end(), free_rows, free_rows + (size_t)n * R);
     m.rem.insert(m.rem.end(), rem.begin(), rem.end());
@@ -2561,7 +2161,7 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
         m.group.push_back(group ? group[i] : 0u); if (group && group[i] + 1 > m.n_groups) m.n_groups = group[i] + 1;
     }
     m.blk_dirty = true;
-    if (ctx->asg.on) return ledger_upload_wids(ctx);
+    if (ctx->asg.on) return ledger_fail(ctx, ctx->asg.upload_wids(ledger_env(ctx)));
     return 0;
 }
 
@@ -2581,10 +2181,10 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     std::vector<uint32_t> src; src.reserve(W - n);
     for (uint32_t w = 0; w < W; w++) if (!gone[w]) src.push_back(w);
     if (int rc = ledger_guard(ctx)) return rc;
-    ctx->asg.rq_task.clear(); ctx->asg.rq_rq.clear(); ctx->asg.rq_prio.clear(); ctx->asg.rq_pf_task.clear();
-    if (ctx->asg.on) { if (int rc = ledger_evict(ctx, n, worker_id)) return rc; }  // on_remove_worker: the lost workers' tasks leave the ledger (reactor.rs:64-147)
+    ctx->asg.clear_requeued();
+    if (ctx->asg.on) { if (int rc = ctx->asg.evict(ledger_env(ctx), n, worker_id)) return ledger_fail(ctx, rc); }  // on_remove_worker: the lost workers' tasks leave the ledger (reactor.rs:64-147)
     if (int rc = cluster_repack(ctx, src, 0, nullptr, nullptr, nullptr)) return rc;
-    if (ctx->asg.on) { if (int rc = ledger_repack(ctx, src, W, nullptr)) return rc; }
+    if (ctx->asg.on) { if (int rc = ctx->asg.repack(ledger_env(ctx), src, W, nullptr)) return ledger_fail(ctx, rc); }
     uint32_t k = 0;
     for (uint32_t w = 0; w < W; w++) {
         if (gone[w]) { m.blocked.erase(m.id[w]); continue; }
@@ -2617,10 +2217,10 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     m.id.resize(k); m.rem.resize(k); m.min_util.resize(k); m.flags.resize(k); m.group.resize(k); m.total.resize((size_t)k * R); m.free_.resize((size_t)k * R);
     m.blk_dirty = true;
     if (ctx->asg.on) {
-        if (int rc = ledger_upload_wids(ctx)) return rc;
+        if (int rc = ctx->asg.upload_wids(ledger_env(ctx))) return ledger_fail(ctx, rc);
         // ... and go back into the resident ready set with their priority and request (add_ready_task), ids ascending
-        if (!ctx->asg.rq_task.empty() && ctx->resident) {
-            const Ledger &a = ctx->asg;
+        const hqasg::Ledger &a = ctx->asg;
+        if (!a.rq_task.empty() && ctx->resident) {
             if (int rc = hqtick_ready_add(ctx, a.rq_task.size(), a.rq_task.data(), a.rq_prio.data(), a.rq_rq.data())) return rc;
         }
     }
@@ -2664,7 +2264,7 @@ int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker
     hqtick_ctx::ClusterMirror &m = ctx->mirror;
     if (ctx->asg.on) {  // the ledger may have moved SN bits since the mirror was read
         if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
-        if (int rc = ledger_sync_mirror(ctx)) return rc;
+        if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     }
     const uint32_t W = (uint32_t)m.id.size();
     std::vector<uint32_t> row(n);
@@ -2678,16 +2278,16 @@ int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker
             return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: with the assignment ledger on, HQ_WORKER_SN follows the ledger's multi-node tasks");
     }
     for (uint32_t i = 0; i < n; i++) m.flags[row[i]] = flags[i];
-    if (ctx->asg.on) return ledger_upload_flags(ctx);
+    if (ctx->asg.on) return ledger_fail(ctx, ctx->asg.upload_flags(ledger_env(ctx)));
     return 0;
 }
 
 int hqtick_cluster_worker_flags(const hqtick_ctx *cctx, uint32_t *n_workers, const uint8_t **flags) {
     if (!cctx || !cctx->mirror.valid) return HQTICK_E_INVALID;
     hqtick_ctx *ctx = const_cast<hqtick_ctx *>(cctx);  // (the mirror is a cache of the ledger's column: reading it may refresh it)
-    if (ctx->asg.on && ctx->asg.dirty) {
+    if (ctx->asg.on && ctx->asg.dirty()) {
         if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
-        if (int rc = ledger_sync_mirror(ctx)) return rc;
+        if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     }
     if (n_workers) *n_workers = (uint32_t)ctx->mirror.flags.size();
     if (flags) *flags = ctx->mirror.flags.data();
@@ -2722,36 +2322,14 @@ int hqtick_retract_response(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, con
 
 uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? (uint32_t)ctx->retr.size() : 0u; }
 
-// ---- assignment ledger (ABI 12; include/hqtick.h) ----
+// ---- assignment ledger (ABI 12; include/hqtick.h): arguments validated here, the operations are hqasg::Ledger's (ledger.h) ----
 int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
     if (!ctx) return HQTICK_E_INVALID;
     if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
     if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
     if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: null array");
     HQ_HIP(hipSetDevice(ctx->device));
-    Ledger &a = ctx->asg;
-    a.on = false; a.pending = false; a.cap = 0; a.n_live = 0; a.n_tomb = 0; a.last_unknown = 0; a.stride = 0; a.stage_n = 0; a.last_host_bytes = 0;
-    a.rq_task.clear(); a.rq_rq.clear(); a.rq_prio.clear(); a.rq_pf_task.clear();
-    a.pf_on = false; a.pf_live = 0; a.pf_stride = 0; a.pf_dirty = false;  // (tracking is asked for again on the new ledger)
-    if (int rc = ledger_reserve(ctx, n)) return rc;
-    HQ_HIP(hqasg::clear(ledger_table(a), ctx->stream));
-    a.req_dirty = true;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    const uint32_t W = ctx->cl_W;
-    if (!a.counts.ensure((size_t)W * a.stride * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment counts");
-    HQ_HIP(hipMemsetAsync(a.counts.p, 0, (size_t)W * a.stride * 4 + 64, ctx->stream));
-    // the multi-node columns: no row holds a task, the flags byte is the mirror's (a worker uploaded without its SN bit waits for hqtick_assigned_add_mn)
-    a.mn_live = 0; a.flags_dirty = false; a.pmn_id.clear();
-    if (!a.mn.ensure((size_t)W * 10 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc assignment rows");
-    HQ_HIP(hipMemsetAsync(a.mn.p, 0xFF, (size_t)W * 8, ctx->stream));
-    HQ_HIP(hipMemsetAsync(a.mn.as<unsigned char>() + (size_t)W * 8, 0, (size_t)W * 2 + 64, ctx->stream));
-    if (int rc = ledger_upload_flags(ctx)) return rc;
-    if (int rc = ledger_upload_wids(ctx)) return rc;
-    uint32_t fresh = 0, bad = 0, dup = 0;
-    if (int rc = ledger_insert_host(ctx, n, task_id, worker_id, rq, variant, priority, 0, 0, nullptr, &fresh, &bad, &dup)) return rc;
-    if (bad || dup) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: an entry names an unknown worker, request or variant, or a task twice");
-    a.on = true; a.dirty = true;
-    return 0;
+    return ledger_fail(ctx, ctx->asg.enable(ledger_env(ctx), n, task_id, worker_id, rq, variant, priority));
 }
 
 int hqtick_assigned_disable(hqtick_ctx *ctx) {
@@ -2760,80 +2338,33 @@ int hqtick_assigned_disable(hqtick_ctx *ctx) {
     return 0;
 }
 
-static int ledger_pre(hqtick_ctx *ctx) {
+// what opens every ledger delta: the ledger is on (prefilled: and not a replica's; tracked: and tracks prefilled tasks), no placement is pending, the device is set,
+// the arrays of a batch are there and the batch is one the kernels can index
+static int ledger_open(hqtick_ctx *ctx, const char *fn, uint32_t n, bool arrays, bool prefilled = false, bool tracked = false) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (prefilled && ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, std::string(fn) + ": not on a sharded or replica context");
     if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
     if (int rc = ledger_guard(ctx)) return rc;
     HQ_HIP(hipSetDevice(ctx->device));
+    if (tracked && !ctx->asg.tracking()) return fail(ctx, HQTICK_E_INVALID, "prefilled tasks are not tracked (hqtick_assigned_track_prefilled)");
+    if (n && !arrays) return fail(ctx, HQTICK_E_INVALID, std::string(fn) + ": null array");
+    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
     return 0;
 }
 
 int hqtick_assigned_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (int rc = ledger_pre(ctx)) return rc;
-    if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add: null array");
-    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
-    uint32_t fresh = 0, bad = 0, dup = 0;
-    if (int rc = ledger_insert_host(ctx, n, task_id, worker_id, rq, variant, priority, 0, 1, nullptr, &fresh, &bad, &dup)) return rc;
-    ctx->asg.last_unknown = (uint64_t)bad + dup;
-    return (int)fresh;
+    if (int rc = ledger_open(ctx, "hqtick_assigned_add", n, task_id && worker_id && rq && variant && priority)) return rc;
+    return ledger_fail(ctx, ctx->asg.add(ledger_env(ctx), n, task_id, worker_id, rq, variant, priority));
 }
 
 int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (int rc = ledger_pre(ctx)) return rc;
-    if (n && !task_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_release: null array");
-    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
-    Ledger &a = ctx->asg;
-    a.last_unknown = 0;
-    if (!n) return 0;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
-    // scratch: [ids n u64][delta W*R u64][pos n u32][last_all W*R u32]
-    const size_t o_dl = (size_t)n * 8, o_pos = o_dl + (size_t)W * R * 8, o_la = o_pos + (size_t)n * 4, bytes = o_la + (size_t)W * R * 4 + 16;
-    if (!a.scratch.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger scratch");
-    unsigned char *d = a.scratch.as<unsigned char>();
-    HQ_HIP(hipMemsetAsync(d + o_dl, 0, (size_t)W * R * 8, ctx->stream));
-    HQ_HIP(hipMemsetAsync(d + o_la, 0, (size_t)W * R * 4, ctx->stream));
-    if (!a.h_in.ensure((size_t)n * 8 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    memcpy(a.h_in.p, task_id, (size_t)n * 8);
-    HQ_HIP(hipMemcpyAsync(d, a.h_in.p, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    HQ_HIP(hqasg::release(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), ledger_mn_rows(a.mn, W, a.mn_live), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<uint32_t *>(d + o_pos),
-                          reinterpret_cast<uint32_t *>(d + o_la), reinterpret_cast<uint64_t *>(d + o_dl), a.ctr.as<uint32_t>(), ctx->stream));
-    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    const uint32_t done = c[hqasg::C_DONE], done_mn = std::min(c[hqasg::C_MN], done);  // (a multi-node task counts once, its rows were reset by the row pass)
-    if (done_mn) a.flags_dirty = true;
-    a.n_live -= done - done_mn; a.mn_live -= std::min<uint64_t>(done_mn, a.mn_live); a.n_tomb += done; a.last_unknown = (uint64_t)c[hqasg::C_UNKNOWN] + c[hqasg::C_DUP]; a.dirty = true;  // (the others of the batch are released either way)
-    if (c[hqasg::C_BAD]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
-    return (int)done;
+    if (int rc = ledger_open(ctx, "hqtick_assigned_release", n, task_id)) return rc;
+    return ledger_fail(ctx, ctx->asg.release(ledger_env(ctx), n, task_id));
 }
 
 int hqtick_assigned_add_mn(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (int rc = ledger_pre(ctx)) return rc;
-    if (n && (!task_id || !rq || !priority || !worker_off)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: null array");
-    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
-    Ledger &a = ctx->asg;
-    a.last_unknown = 0;
-    if (!n) return 0;
-    if (worker_off[0] != 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: worker_off[0] must be 0");
-    for (uint32_t i = 0; i < n; i++) if (worker_off[i + 1] < worker_off[i]) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: worker_off must not descend");
-    if (worker_off[n] && !worker_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_add_mn: null array");
-    // a task whose request is not a multi-node one (n_nodes == 0, or unknown) never reaches the device
-    std::vector<uint64_t> id, pr; std::vector<uint32_t> q, off{0}, wid;
-    uint64_t skipped = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const bool mn_rq = (size_t)rq[i] + 1 < a.rq_off.size() && a.rq_off[rq[i]] < a.rq_off[rq[i] + 1] && a.rq_off[rq[i]] < a.var_nodes.size() && a.var_nodes[a.rq_off[rq[i]]] > 0;
-        if (!mn_rq || worker_off[i] == worker_off[i + 1]) { skipped++; continue; }
-        id.push_back(task_id[i]); pr.push_back(priority[i]); q.push_back(rq[i]);
-        wid.insert(wid.end(), worker_id + worker_off[i], worker_id + worker_off[i + 1]); off.push_back((uint32_t)wid.size());
-    }
-    uint32_t entered = 0, refused = 0;
-    if (int rc = ledger_mn_enter(ctx, (uint32_t)id.size(), id.data(), q.data(), pr.data(), off.data(), wid.data(), 1, &entered, &refused)) return rc;
-    a.last_unknown = skipped + refused;
-    return (int)entered;
+    if (int rc = ledger_open(ctx, "hqtick_assigned_add_mn", n, task_id && rq && priority && worker_off)) return rc;
+    return ledger_fail(ctx, ctx->asg.add_mn(ledger_env(ctx), n, task_id, rq, priority, worker_off, worker_id));
 }
 
 uint64_t hqtick_assigned_mn_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on ? ctx->asg.mn_live : 0; }
@@ -2841,24 +2372,7 @@ uint64_t hqtick_assigned_mn_count(const hqtick_ctx *ctx) { return ctx && ctx->as
 int hqtick_assigned_mn_workers(hqtick_ctx *ctx, uint64_t task_id, uint32_t *n, const uint32_t **worker_id) {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
-    Ledger &a = ctx->asg;
-    a.mnw_out.clear();
-    const uint32_t W = ctx->cl_W;
-    if (a.mn_live && W && task_id < hqasg::HT_TOMB) {  // an accessor for tests and restore: the two columns come back, 9 B per row
-        HQ_HIP(hipSetDevice(ctx->device));
-        a.mnw_cols.resize((size_t)W * 9);
-        HQ_HIP(hipMemcpyAsync(a.mnw_cols.data(), a.mn.p, (size_t)W * 9, hipMemcpyDeviceToHost, ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        const unsigned char *root = a.mnw_cols.data() + (size_t)W * 8;
-        for (int pass = 0; pass < 2; pass++)  // the root first, the others in ascending id (= row) order
-            for (uint32_t w = 0; w < W; w++) {
-                uint64_t t; memcpy(&t, a.mnw_cols.data() + (size_t)w * 8, 8);
-                if (t == task_id && (root[w] != 0) == (pass == 0)) a.mnw_out.push_back(ctx->mirror.id[w]);
-            }
-    }
-    if (n) *n = (uint32_t)a.mnw_out.size();
-    if (worker_id) *worker_id = a.mnw_out.data();
-    return 0;
+    return ledger_fail(ctx, ctx->asg.mn_workers(ledger_env(ctx), task_id, n, worker_id));
 }
 
 uint64_t hqtick_assigned_last_unknown(const hqtick_ctx *ctx) { return ctx ? ctx->asg.last_unknown : 0; }
@@ -2871,24 +2385,14 @@ int hqtick_assigned_lookup(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id,
     if (n && (!task_id || !worker_id || !variant)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_lookup: null array");
     if (!n) return 0;
     HQ_HIP(hipSetDevice(ctx->device));
-    Ledger &a = ctx->asg;
-    const size_t o_w = (size_t)n * 8, o_v = o_w + (size_t)n * 4, bytes = o_v + n + 16;
-    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
-    memcpy(h, task_id, (size_t)n * 8);
-    HQ_HIP(hqasg::lookup(ledger_table(a), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<uint32_t *>(d + o_w), d + o_v, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(worker_id, h + o_w, (size_t)n * 4); memcpy(variant, h + o_v, n);
-    int found = 0;
-    for (uint32_t i = 0; i < n; i++) found += worker_id[i] != HQ_NO_WORKER;
-    return found;
+    return ledger_fail(ctx, ctx->asg.lookup(ledger_env(ctx), n, task_id, worker_id, variant));
 }
 
 int hqtick_assigned_free_rows(hqtick_ctx *ctx, uint32_t *n_workers, const uint64_t **free_rows) {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
     HQ_HIP(hipSetDevice(ctx->device));
-    if (int rc = ledger_sync_mirror(ctx)) return rc;
+    if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     if (n_workers) *n_workers = ctx->cl_W;
     if (free_rows) *free_rows = ctx->mirror.free_.data();
     return 0;
@@ -2911,103 +2415,22 @@ int hqtick_cluster_last_requeued_prefilled(const hqtick_ctx *ctx, uint32_t *n, c
 }
 
 // ---- prefilled tasks in the ledger (SingleNodeTaskAssignment::prefilled_tasks) ----
-static int ledger_pf_pre(hqtick_ctx *ctx, const char *what) {
-    if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, std::string(what) + ": not on a sharded or replica context");
-    if (int rc = ledger_pre(ctx)) return rc;
-    return 0;
-}
-// one batch of ids (+ optional columns) staged in pinned memory and read in place; the counters come back behind the kernel
-static int ledger_pf_counters(hqtick_ctx *ctx) {
-    Ledger &a = ctx->asg;
-    HQ_HIP(hipMemcpyAsync(a.h_ctr.p, a.ctr.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
 int hqtick_assigned_track_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint64_t *priority) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (int rc = ledger_pf_pre(ctx, "hqtick_assigned_track_prefilled")) return rc;
-    if (n && (!task_id || !worker_id || !rq || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_track_prefilled: null array");
-    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
-    Ledger &a = ctx->asg;
-    if (ledger_max_variants(a) >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_track_prefilled: a request has 254 or more variants");
-    a.last_unknown = 0;
-    const uint32_t W = ctx->cl_W;
-    if (a.pf_on && a.pf_live) {  // a second call replaces the prefilled entries
-        uint32_t *c = ledger_ctr(ctx);
-        if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-        HQ_HIP(hqasg::pf_drop_all(ledger_table(a), a.ctr.as<uint32_t>(), ctx->stream));
-        if (int rc = ledger_pf_counters(ctx)) return rc;
-        a.n_tomb += c[hqasg::C_DONE]; a.pf_live = 0;
-    }
-    a.pf_on = false;  // (until the table below stands: ledger_sync_req must not widen a table that is being replaced)
-    if (int rc = ledger_reserve(ctx, n)) return rc;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    const uint32_t ns = std::max<uint32_t>(16, ((uint32_t)a.rq_off.size() - 1 + 15) & ~15u);
-    if (!a.pf.ensure((size_t)W * ns * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc prefilled counts");
-    HQ_HIP(hipMemsetAsync(a.pf.p, 0, (size_t)W * ns * 4 + 64, ctx->stream));
-    a.pf_stride = ns; a.pf_on = true; a.pf_live = 0; a.pf_dirty = true; a.dirty = true;
-    if (!n) { HQ_HIP(hipStreamSynchronize(ctx->stream)); return 0; }
-    const size_t o_p = (size_t)n * 8, o_w = o_p + (size_t)n * 8, o_q = o_w + (size_t)n * 4, bytes = o_q + (size_t)n * 4 + 16;
-    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
-    memcpy(h, task_id, (size_t)n * 8); memcpy(h + o_p, priority, (size_t)n * 8); memcpy(h + o_w, worker_id, (size_t)n * 4); memcpy(h + o_q, rq, (size_t)n * 4);
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    HQ_HIP(hqasg::pf_seed(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), ledger_mn_rows(a.mn, W, a.mn_live), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<const uint32_t *>(d + o_w),
-                          reinterpret_cast<const uint32_t *>(d + o_q), reinterpret_cast<const uint64_t *>(d + o_p), a.ctr.as<uint32_t>(), ctx->stream));
-    if (int rc = ledger_pf_counters(ctx)) return rc;
-    if (c[hqasg::C_FULL]) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: table full");
-    a.pf_live = c[hqasg::C_PF]; a.last_unknown = (uint64_t)c[hqasg::C_BAD] + c[hqasg::C_DUP];
-    return (int)c[hqasg::C_PF];
+    if (int rc = ledger_open(ctx, "hqtick_assigned_track_prefilled", n, task_id && worker_id && rq && priority, true)) return rc;
+    return ledger_fail(ctx, ctx->asg.track_prefilled(ledger_env(ctx), n, task_id, worker_id, rq, priority));
 }
 
 int hqtick_assigned_start_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint8_t *variant) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (int rc = ledger_pf_pre(ctx, "hqtick_assigned_start_prefilled")) return rc;
-    if (!ctx->asg.pf_on) return fail(ctx, HQTICK_E_INVALID, "prefilled tasks are not tracked (hqtick_assigned_track_prefilled)");
-    if (n && (!task_id || !variant)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_start_prefilled: null array");
-    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
-    Ledger &a = ctx->asg;
-    a.last_unknown = 0;
-    if (!n) return 0;
-    if (int rc = ledger_sync_req(ctx)) return rc;
-    const size_t o_v = (size_t)n * 8, bytes = o_v + n + 16;
-    if (!a.h_in.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    unsigned char *h = a.h_in.as<unsigned char>(), *d = a.h_in.dev<unsigned char>();
-    memcpy(h, task_id, (size_t)n * 8); memcpy(h + o_v, variant, n);
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    HQ_HIP(hqasg::pf_start(ledger_table(a), ledger_req(ctx), ledger_rows(ctx), n, reinterpret_cast<const uint64_t *>(d), d + o_v, a.ctr.as<uint32_t>(), ctx->stream));
-    if (int rc = ledger_pf_counters(ctx)) return rc;
-    const uint32_t done = (uint32_t)std::min<uint64_t>(c[hqasg::C_DONE], a.pf_live);
-    a.pf_live -= done; a.n_live += done; a.last_unknown = (uint64_t)c[hqasg::C_UNKNOWN] + c[hqasg::C_BAD];
-    if (done) { a.dirty = true; a.pf_dirty = true; }
-    return (int)done;
+    if (int rc = ledger_open(ctx, "hqtick_assigned_start_prefilled", n, task_id && variant, true, true)) return rc;
+    return ledger_fail(ctx, ctx->asg.start_prefilled(ledger_env(ctx), n, task_id, variant));
 }
 
 int hqtick_assigned_unprefill(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (int rc = ledger_pf_pre(ctx, "hqtick_assigned_unprefill")) return rc;
-    if (!ctx->asg.pf_on) return fail(ctx, HQTICK_E_INVALID, "prefilled tasks are not tracked (hqtick_assigned_track_prefilled)");
-    if (n && !task_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_unprefill: null array");
-    if (n > 0x7FFFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta");
-    Ledger &a = ctx->asg;
-    a.last_unknown = 0;
-    if (!n) return 0;
-    if (!a.h_in.ensure((size_t)n * 8 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc ledger staging");
-    memcpy(a.h_in.p, task_id, (size_t)n * 8);
-    uint32_t *c = ledger_ctr(ctx);
-    if (!c) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-    HQ_HIP(hqasg::pf_remove(ledger_table(a), ledger_rows(ctx), n, a.h_in.dev<uint64_t>(), a.ctr.as<uint32_t>(), ctx->stream));
-    if (int rc = ledger_pf_counters(ctx)) return rc;
-    const uint32_t done = (uint32_t)std::min<uint64_t>(c[hqasg::C_DONE], a.pf_live);
-    a.pf_live -= done; a.n_tomb += done; a.last_unknown = c[hqasg::C_UNKNOWN];
-    if (done) { a.dirty = true; a.pf_dirty = true; }
-    return (int)done;
+    if (int rc = ledger_open(ctx, "hqtick_assigned_unprefill", n, task_id, true, true)) return rc;
+    return ledger_fail(ctx, ctx->asg.unprefill(ledger_env(ctx), n, task_id));
 }
 
-uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on && ctx->asg.pf_on ? ctx->asg.pf_live : 0; }
+uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on && ctx->asg.tracking() ? ctx->asg.pf_live : 0; }
 
 int hqtick_ready_compact(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;

@@ -1,0 +1,149 @@
+// The host side of the assignment ledger (hqtick_assigned_*, ABI 12): the buffers of csrc/assigned.h's tables, the host's counts of what they
+// hold, and one method per ledger operation.  The kernels are assigned.hip's; hqtick.cpp validates the arguments of the C ABI, builds an Env and forwards.
+// Like hqgraph::Graph, a method returns an HQTICK_E_* code (negative) with `err` set; it enqueues on the Env's stream and has synchronised it when it returns.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/hqtick.h"
+#include "assigned.h"
+#include "devbuf.h"
+
+namespace hqasg {
+
+// What a ledger call reads of the context it belongs to, built by hqtick.cpp for the call (by value: the cluster tables move at a membership change).
+struct Env {
+    int device; hipStream_t stream;
+    unsigned char *cluster; uint32_t W, R;  // the resident worker rows in HBM: [total W x R u64][free W x R u64] ...
+    const uint64_t *col_id, *col_prio; const uint32_t *col_rq; uint64_t col_n;  // the resident ready-set columns (physical length)
+    const uint64_t *levels;                 // the dense scan's level table
+    const std::vector<uint32_t> *id; std::vector<uint8_t> *flags; std::vector<uint64_t> *free_;  // the host mirror of the worker set: ids in row order, flags, free rows
+};
+
+// the placement staging K5b writes beside a tick's records and insert_staged reads: [task u64 | rq u32 | row u32 | level u32 | meta u16] x n_rec
+struct StageCols { uint64_t *task; uint32_t *rq, *row, *level; uint16_t *meta; };
+// per worker its distinct (rq, variant) pairs with counts, as a CSR over the workers
+struct Agg { const uint32_t *off, *rq, *cnt; const uint8_t *var; };
+
+class Ledger {
+  public:
+    // Plain state hqtick.cpp reads (and, for `on` and `pending`, sets); the buffers and whatever an operation keeps consistent with them are private.
+    bool on = false;       // hqtick_assigned_enable .. _disable / a new worker set / a tick's placement that could not be entered
+    bool pending = false;  // a tick's placement waits for hqtick_ready_consume_last (two-call form)
+    std::string err;
+    uint64_t n_live = 0, mn_live = 0, pf_live = 0;  // single-node, multi-node and (with tracking()) prefilled entries of the table
+    uint64_t last_unknown = 0, last_host_bytes = 0;
+    std::vector<uint64_t> rq_task, rq_prio, rq_pf_task; std::vector<uint32_t> rq_rq;  // hqtick_cluster_last_requeued(_prefilled): what the last evict() took out
+
+    // ---- the C ABI's operations (arguments validated by the caller)
+    int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
+    int add(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
+    int release(const Env &e, uint32_t n, const uint64_t *id);
+    int add_mn(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid);
+    int mn_workers(const Env &e, uint64_t id, uint32_t *n, const uint32_t **wid);
+    int lookup(const Env &e, uint32_t n, const uint64_t *id, uint32_t *wid, uint8_t *var);
+    int track_prefilled(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint64_t *prio);
+    int start_prefilled(const Env &e, uint32_t n, const uint64_t *id, const uint8_t *var) { return pf_leave(e, n, id, var); }
+    int unprefill(const Env &e, uint32_t n, const uint64_t *id) { return pf_leave(e, n, id, nullptr); }
+    // ---- the worker set changes (hqtick_cluster_*)
+    void take_requests(const hqtick_snapshot *s);  // the request tables of a snapshot, kept when they differ from the ones the ledger has
+    int upload_wids(const Env &e);
+    int upload_flags(const Env &e);
+    int repack(const Env &e, const std::vector<uint32_t> &src, uint32_t W_old, const uint8_t *add_flags);
+    int evict(const Env &e, uint32_t n, const uint32_t *worker_id);
+    void clear_requeued() { rq_task.clear(); rq_rq.clear(); rq_prio.clear(); rq_pf_task.clear(); }
+    // ---- a tick
+    void abandon_tick() { pending = false; stage_n = 0; }  // (a tick that was never consumed is abandoned, as its selection is; its staging is never read)
+    int sync_mirror(const Env &e);  // free rows, flags and counts back on the host; then agg()
+    // the staging of n_rec records for K5b (false: no memory); ordered / L: how insert_staged will find their priorities
+    bool stage_for(uint32_t n_rec, bool ordered, uint32_t L, StageCols *c);
+    uint32_t *saved_rq(size_t n) { return buf[B_SAVED_RQ].ensure(n * 4 + 16) ? buf[B_SAVED_RQ].as<uint32_t>() : nullptr; }  // the request-id column as it was before K4's tombstones
+    // the tick's redirects and multi-node placements (worker ids) and its new_free wait with its staged records; saved: their request ids are in saved_rq()
+    void collect_tick(const hqtick_snapshot *s, const hqtick_result *out, const std::vector<uint64_t> &new_free, const std::vector<uint32_t> &mn_rq, bool saved);
+    int apply_tick(const Env &e);  // ... and become ledger state
+    // a waiting placement is live only while the tick's selection is (selection: last_valid && !last_consumed)
+    bool pending_live(bool selection) { if (pending && !selection) pending = false; return pending; }
+    uint32_t max_variants() const { uint32_t m = 0; for (size_t q = 0; q + 1 < rq_off.size(); q++) m = std::max(m, rq_off[q + 1] - rq_off[q]); return m; }
+    bool tracking() const { return pf_on; }
+    bool dirty() const { return dirty_; }
+    const std::vector<uint32_t> &prefilled_host(uint32_t *stride) const { *stride = pf_stride; return h_pf; }  // pf [W x stride] as sync_mirror read it
+    Agg agg() const { return Agg{agg_off.data(), agg_rq.data(), agg_cnt.data(), agg_var.data()}; }
+    void release_all();
+
+  private:
+    using DevBuf = hqbuf::DevBuf;
+    struct TableCols {  // the hash table's columns (assigned.h: Table), `cap` buckets
+        DevBuf key, wid, rq, var, prio, claim;
+        bool ensure(size_t cap) { return key.ensure(cap * 8) && wid.ensure(cap * 4) && rq.ensure(cap * 4) && var.ensure(cap) && prio.ensure(cap * 8) && claim.ensure(cap * 4); }
+        Table view(uint32_t mask) const { return Table{key.as<uint64_t>(), wid.as<uint32_t>(), rq.as<uint32_t>(), var.as<uint8_t>(), prio.as<uint64_t>(), claim.as<uint32_t>(), mask}; }
+        void release() { for (DevBuf *b : {&key, &wid, &rq, &var, &prio, &claim}) b->release(); }
+    };
+    struct RowPair { DevBuf cur, next; void swap() { std::swap(cur, next); } void release() { cur.release(); next.release(); } };  // a per-worker-row table and the target of its next re-pack
+    // Columns one behind the other in a buffer that has the room (h: its host side, nullptr for device memory; dv: the same bytes as the device sees them).
+    // put() copies a column there (src == nullptr: left as it is) and returns where the device finds it.
+    struct Pack {
+        unsigned char *h = nullptr, *dv = nullptr; size_t end = 0;
+        template <typename T> T *put(const T *src, size_t n, size_t align = 1) {
+            end = (end + align - 1) & ~(align - 1);
+            if (h && src) memcpy(h + end, src, n * sizeof(T));
+            T *p = reinterpret_cast<T *>(dv + end); end += n * sizeof(T); return p;
+        }
+        template <typename T> T *host(const T *p) const { return reinterpret_cast<T *>(h + (reinterpret_cast<const unsigned char *>(p) - dv)); }
+    };
+    static uint32_t row_stride(size_t cols) { return std::max<uint32_t>(16, ((uint32_t)cols + 15) & ~15u); }
+    int fail(int code, const std::string &m) { err = m; return code; }
+    Table table() const { return tab.view(cap - 1); }
+    Rows rows(const Env &e) const {
+        return Rows{buf[B_WIDS].as<uint32_t>(), e.W, e.R, reinterpret_cast<const uint64_t *>(e.cluster), reinterpret_cast<uint64_t *>(e.cluster + (size_t)e.W * e.R * 8), counts.cur.as<uint32_t>(), stride,
+                    pf_on ? pf.cur.as<uint32_t>() : nullptr, pf_on ? pf_stride : 0u};
+    }
+    // the multi-node columns of W rows in `b`; live: the uniform argument of the kernels that may skip them
+    MnRows mn_rows(const DevBuf &b, uint32_t W, uint64_t live) const { return MnRows{b.as<uint64_t>(), b.as<uint8_t>() + (size_t)W * 8, b.as<uint8_t>() + (size_t)W * 9, (uint32_t)std::min<uint64_t>(live, 0xFFFFFFFFu)}; }
+    size_t req_bytes() const { return (((rq_off.size() + vent_off.size() + ent_res.size()) * 4 + 7) & ~(size_t)7) + ent_res.size() * 9 + 64; }
+    Req req(unsigned char *h = nullptr) const;  // the request tables in buf[B_REQ] (h: packed there as well)
+    int stage_in(size_t bytes, Pack *pk) { if (!h_in.ensure(bytes + 16)) return fail(HQTICK_E_DEVICE, "hipHostMalloc ledger staging"); *pk = Pack{h_in.as<unsigned char>(), h_in.dev<unsigned char>()}; return 0; }
+    // One operation's counters: zeroed on the stream, `launch` (given the device counters), 32 B copied back behind it, one synchronisation -> c (pinned).
+    // c is the LAST operation's: insert_host and mn_enter end with theirs, and their callers read it before anything else runs.
+    template <class F> int counted(hipStream_t s, const char *what, F &&launch) {
+        if (!h_ctr.ensure(64) || !buf[B_CTR].ensure(64) || hipMemsetAsync(buf[B_CTR].p, 0, 64, s) != hipSuccess) return fail(HQTICK_E_DEVICE, "hipHostMalloc");
+        c = h_ctr.as<uint32_t>(); std::fill_n(h_ctr.as<uint32_t>(), (size_t)C_N, 0u);
+        hipError_t rc = launch(buf[B_CTR].as<uint32_t>());
+        if (rc == hipSuccess) rc = hipMemcpyAsync(h_ctr.p, buf[B_CTR].p, 32, hipMemcpyDeviceToHost, s);
+        if (rc == hipSuccess) rc = hipStreamSynchronize(s);
+        return rc == hipSuccess ? 0 : fail(HQTICK_E_DEVICE, std::string(what) + ": " + hipGetErrorString(rc));
+    }
+    int widen(const Env &e, RowPair &t, uint32_t &stride, size_t cols, const char *what);
+    int sync_req(const Env &e);
+    int reserve(const Env &e, uint64_t more);
+    int insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free, const uint32_t *col_rq);
+    int mn_enter(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid, int check);
+    int pf_leave(const Env &e, uint32_t n, const uint64_t *id, const uint8_t *var);
+
+    TableCols tab, tab2;      // the hash table; the target of a rebuild
+    RowPair counts, mn, pf;   // counts u32 [W x stride]; [mn task u64 W][mn root u8 W][flags u8 W]; pf u32 [W x pf_stride]
+    // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation
+    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_N }; DevBuf buf[B_N];
+    hqbuf::PinBuf h_ctr, h_in;
+    const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
+    uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones
+    uint32_t stride = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)
+    bool pf_on = false; uint32_t pf_stride = 0; std::vector<uint32_t> h_pf; bool pf_dirty = false;  // (pf_dirty: ... the prefilled table since h_pf was read)
+    std::vector<uint32_t> var_nodes;          // n_nodes per variant slot of the request tables
+    // the request tables of the last snapshot (ResourceRqMap only grows: a slot keeps its number)
+    std::vector<uint32_t> rq_off{0}, vent_off{0}, ent_res; std::vector<uint8_t> ent_kind; std::vector<uint64_t> ent_amt; bool req_dirty = true;
+    std::vector<uint32_t> h_counts; bool dirty_ = false;  // the device tables changed since the host mirror (free rows, counts) was read
+    std::vector<uint32_t> agg_off, agg_rq, agg_cnt; std::vector<uint8_t> agg_var; bool agg_dirty = true;
+    // a tick's placement until it is applied
+    uint32_t stage_n = 0; bool stage_ordered = false; uint32_t stage_L = 0; StageCols stage_c{};
+    bool pend_saved = false; uint32_t pend_W = 0; std::vector<uint64_t> pend_free;
+    std::vector<uint64_t> red_id, red_prio; std::vector<uint32_t> red_wid, red_rq; std::vector<uint8_t> red_var;
+    std::vector<uint64_t> pmn_id; std::vector<uint32_t> pmn_rq, pmn_off{0}, pmn_wid;  // (worker ids, root first)
+    std::vector<uint32_t> mnw_out; std::vector<unsigned char> mnw_cols;              // hqtick_assigned_mn_workers
+};
+
+}  // namespace hqasg
