@@ -3,6 +3,9 @@
 // hashbrown-order helper are reachable here.
 #include "../../include/hqtick_debug.h"
 
+#include <algorithm>
+#include <cstring>
+
 #include "hb_order.h"
 #include "milp.h"
 #include "price_emul.h"
@@ -85,4 +88,13 @@ extern "C" void hqtick_debug_set_block_runs(int on) {
 extern "C" void hqtick_debug_corrupt_block_runs(int on) { g_block_run_probe.corrupt_runs = on != 0; }
 extern "C" void hqtick_debug_last_coupled_digest(uint64_t out[4]) {
     out[0] = g_block_run_probe.model; out[1] = g_block_run_probe.tables; out[2] = g_block_run_probe.runs; out[3] = g_block_run_probe.covered;
+}
+// The zero-price sweep launched from inside the flattening (csrc/price.h: set_early_sweep) and the first cut of this thread's coupled solves (capture_first_cut).
+extern "C" void hqtick_debug_set_early_sweep(int on) { hqprice::set_early_sweep(on); }
+extern "C" uint32_t hqtick_debug_early_sweeps(void) { return hqprice::early_sweeps(); }
+extern "C" void hqtick_debug_capture_first_cut(int on) { hqprice::capture_first_cut(on != 0); }
+extern "C" uint32_t hqtick_debug_first_cut(unsigned char *out, uint32_t cap) {
+    const std::vector<unsigned char> &b = hqprice::first_cut_bytes();
+    if (out && cap) memcpy(out, b.data(), std::min<size_t>(cap, b.size()));
+    return (uint32_t)b.size();
 }

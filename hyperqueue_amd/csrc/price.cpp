@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -34,6 +35,7 @@ constexpr double BP_MAX_WORK = 3.0e9; // ... and tableau elements its masters ma
                                       // costs milliseconds, and a 10 k-column model spent 8 s here against a 5 s time limit before this cap (deterministic like the counts)
 
 double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+thread_local uint32_t g_early_sweeps = 0;   // tests: sweeps launched on the block tables alone (Solver::launch_on_blocks)
 
 struct CapRow { int flat; double rhs; std::vector<std::pair<int, double>> g; };  // x_flat + sum_g coef B_g <= rhs (the column's own coefficient divided out)
 
@@ -299,7 +301,56 @@ struct Solver {
     // branch-and-price: the node whose bounds the device tables carry right now (empty lo list = the model's own bounds), and what its lower bounds add per sweep
     std::vector<std::pair<uint32_t, int32_t>> node_lo, node_caps; double node_cl = 0.0; std::vector<double> node_Al; bool at_root = true;
     bool base_caps = true;        // the sweeps run under the model's own column bounds (only those bound the relaxed model)
+    // The zero-price sweep launched from inside the flattening, on the block tables alone (price.h: Sweeper::begin_blocks; solve_model's hook).
+    enum { EARLY_NONE = 0, EARLY_LAUNCHED, EARLY_REFUSED, EARLY_FAILED };
+    int early = EARLY_NONE;
+    bool early_begun = false;     // begin_blocks took the tables: the sweeper is owed an end()
+    bool host_acts = false;       // the sweep in flight ran without the wide rows' entries: its activities are added up here, from its patterns
+    double tp0 = 0.0;             // start of the solve (the trace's clock)
     Solver(const Request &r, Sweeper &s) : rq(r), sw(s) {}
+
+    // what a solve sets on its sweeper before the first sweep
+    void prepare_sweeper() {
+        sw.stat_sweeps = 0; sw.stat_sweep_us = 0;
+        sw.guard_s = rq.deadline_s - 0.3 * rq.time_limit_s; sw.time_up = false;  // (first read at the first sweep)
+        max_sweeps = (int)std::min<size_t>(4096, std::max<size_t>(256, ((size_t)64 << 20) / ((size_t)P.T.n_cols * 2 + 1)));  // the device keeps every sweep's patterns: at most 64 MB of them
+    }
+    // The flattener's hook: P.T's block arrays are final (n_blocks, n_cols, blk_off, blk_m, blk_cap, col_cost, col_a, col_cap), nothing else of P is.  At zero prices
+    // that is all a sweep needs: it is on the device while the host builds the wide rows' tables.
+    void launch_on_blocks() {
+        prepare_sweeper();
+        const int took = sw.begin_blocks(P.T, (uint32_t)max_sweeps);
+        if (took < 0) return;   // (a sweeper without the split: begin() and the launch once the model is flattened)
+        if (took == 0) { early = EARLY_REFUSED; return; }
+        early_begun = true;
+        const double zero = 0.0, t0 = now_us();
+        sw.pending_k = 0;
+        if (!sw.sweep_launch(&zero)) { early = EARLY_FAILED; return; }
+        sw.stat_sweep_us += now_us() - t0;
+        early = EARLY_LAUNCHED; host_acts = true; g_early_sweeps++;
+        if (rq.trace) fprintf(stderr, "[price] first sweep (prices 0) launched on the block tables at %.3f ms\n", (now_us() - tp0) / 1e3);
+    }
+    // The activities of a sweep that ran without the wide rows' entries: sum coef . x over its patterns (read where the sweep left them) and the column-wise entries,
+    // per part and in total — the integers the device's 64-bit atomics add up, which are exact and order-free.
+    bool activities_from_patterns(uint32_t sweep, SweepTotals &tot) {
+        const HostTables &T = P.T;
+        const uint16_t *x = sw.patterns(sweep, 1);
+        if (!x) return false;
+        const size_t KG = (size_t)P.KG;
+        const uint32_t per = (T.n_blocks + PARTS - 1) / PARTS;
+        tot.act.assign(KG, 0); tot.part_act.assign((size_t)PARTS * KG, 0);
+        const uint32_t *woff = T.col_woff.data(); const uint16_t *wr = T.w_row.data(); const int32_t *wc = T.w_coef.data();
+        for (uint32_t b = 0; b < T.n_blocks; b++) {
+            long long *pa = &tot.part_act[(size_t)(b / per) * KG];
+            for (uint32_t f = T.blk_off[b]; f < T.blk_off[b + 1]; f++) {
+                const long long xv = (long long)x[f];
+                if (!xv) continue;
+                for (uint32_t e = woff[f]; e < woff[f + 1]; e++) pa[wr[e]] += (long long)wc[e] * xv;
+            }
+        }
+        for (int p = 0; p < PARTS; p++) for (size_t k = 0; k < KG; k++) tot.act[k] += tot.part_act[(size_t)p * KG + k];
+        return true;
+    }
 
     // one sweep at pi; returns the cut's index or -1.  In two halves for the caller with work to do meanwhile: evaluate_launch(pi), ..., evaluate(pi, true).
     bool evaluate_launch(const std::vector<double> &pi) {
@@ -316,8 +367,10 @@ struct Solver {
         if ((int)cuts.size() >= max_sweeps) return -1;
         SweepTotals tot;
         const double t0 = now_us();
-        if (launched) { if (!sw.sweep_finish(tot)) { failed = true; return -1; } }
-        else {
+        if (launched) {
+            if (!sw.sweep_finish(tot)) { failed = true; return -1; }
+            if (host_acts) { host_acts = false; if (!activities_from_patterns((uint32_t)cuts.size(), tot)) { failed = true; return -1; } }
+        } else {
             std::vector<double> pig(P.KG, 0.0);
             for (int k = 0; k < P.K; k++) pig[P.grp_of[k]] += pi[k];
             if (!sw.sweep(pig.data(), tot)) { failed = true; return -1; }
@@ -955,6 +1008,7 @@ struct Solver {
 }  // namespace
 
 namespace {
+thread_local bool g_capture_cut = false; thread_local std::vector<unsigned char> g_first_cut;
 // everything after the model has been flattened into S.P
 Answer run_solver(Solver &S, const double tp0) {
     Answer ans;
@@ -965,15 +1019,22 @@ Answer run_solver(Solver &S, const double tp0) {
     Prob &P = S.P;
     if (rq.trace) fprintf(stderr, "[price] %u blocks, %u block columns, %d wide rows with %d distinct left-hand sides (%zu / %zu terms), %d flags, %zu conditional bounds\n", P.T.n_blocks, P.T.n_cols, P.K, P.KG, P.row_terms, P.T.w_row.size(), P.G, P.caps.size());
     const int K = P.K, G = P.G;
-    sw.stat_sweeps = 0; sw.stat_sweep_us = 0;
-    sw.guard_s = rq.deadline_s - 0.3 * rq.time_limit_s; sw.time_up = false;  // (first read at the first sweep)
-    S.max_sweeps = (int)std::min<size_t>(4096, std::max<size_t>(256, ((size_t)64 << 20) / ((size_t)P.T.n_cols * 2 + 1)));  // the device keeps every sweep's patterns: at most 64 MB of them
-    if (!sw.begin(P.T, (uint32_t)S.max_sweeps)) { ans.why = "sweeper refused the model"; return ans; }
-    struct Ender { Sweeper &s; ~Ender() { s.end(); } } ender{sw};
-    tmark("tables handed to the sweeper");
-    // the first sweep runs at zero prices: it needs the tables and nothing else, so it is on its way while the host works out the price caps
+    struct Ender { Sweeper *s; ~Ender() { if (s) s->end(); } } ender{S.early_begun ? &sw : nullptr};
     std::vector<double> pi0(K, 0.0);
-    if (!S.evaluate_launch(pi0)) { ans.why = "sweep failed"; return ans; }
+    if (S.early == Solver::EARLY_REFUSED) { ans.why = "sweeper refused the model"; return ans; }
+    if (S.early == Solver::EARLY_FAILED) { S.failed = true; ans.why = "sweep failed"; return ans; }
+    if (S.early == Solver::EARLY_LAUNCHED) {
+        // the first sweep has been on its way since the block tables were final (Solver::launch_on_blocks); the wide rows' tables follow it on the stream
+        if (!sw.begin_wide()) { ans.why = "sweeper refused the model"; return ans; }
+        tmark("wide tables handed to the sweeper");
+    } else {
+        S.prepare_sweeper();
+        if (!sw.begin(P.T, (uint32_t)S.max_sweeps)) { ans.why = "sweeper refused the model"; return ans; }
+        ender.s = &sw;
+        tmark("tables handed to the sweeper");
+        // the first sweep runs at zero prices: it needs the tables and nothing else, so it is on its way while the host works out the price caps
+        if (!S.evaluate_launch(pi0)) { ans.why = "sweep failed"; return ans; }
+    }
     // price caps: beyond pmax every column of the row has a negative reduced cost (`<=` rows); for `>=` rows a multiple of the largest cost per unit
     S.pmax.assign(K, 0.0);
     {
@@ -994,6 +1055,13 @@ Answer run_solver(Solver &S, const double tp0) {
     tmark("price caps done");
     if (S.evaluate(pi0, true) < 0) { ans.why = "sweep failed"; return ans; }
     tmark("first sweep (prices 0) done");
+    if (g_capture_cut) {
+        const Cut &c0 = S.cuts[0];
+        auto put = [](const void *p, size_t bytes) { const unsigned char *b = (const unsigned char *)p; g_first_cut.insert(g_first_cut.end(), b, b + bytes); };
+        g_first_cut.clear();
+        put(c0.act.data(), c0.act.size() * sizeof(long long)); put(c0.pact.data(), c0.pact.size() * sizeof(long long));
+        put(&c0.cx, sizeof c0.cx); put(&c0.bnd, sizeof c0.bnd); put(c0.pcx.data(), c0.pcx.size() * sizeof(double));
+    }
     S.theta_scale = std::max(S.cuts[0].bnd, 1e-9);
     ans.ran = true;
     double best_value = rq.incumbent ? rq.incumbent_value : -INF;
@@ -1305,9 +1373,16 @@ Answer run_solver(Solver &S, const double tp0) {
 namespace {
 
 thread_local bool g_check_hints = false; thread_local int g_hint_mismatches = 0;
+thread_local int g_early_sweep = -1;
+bool early_sweep_on() {
+    static const bool env_on = !(getenv("HQPRICE_EARLY_SWEEP") && atoi(getenv("HQPRICE_EARLY_SWEEP")) == 0);   // (A/B switch)
+    return g_early_sweep < 0 ? env_on : g_early_sweep != 0;
+}
 // ---- the model as its builder wrote it -> blocks + wide rows (what build() does for a scaled component copy; same tables, same numbering) -------------------------
 // Returns nullptr on success, else what keeps the model on the classic path.  ub: the derived column bounds (model columns), c: obj / cmax.
-const char *flatten_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax) {
+// after_blocks (optional) is called once, when the block tables — T.n_blocks, T.n_cols, blk_off, blk_m, blk_cap, col_cost, col_a, col_cap — are final: behind the rows
+// loop, the last run's copies and the never-binding rows.  What follows builds the wide rows' groups and changes none of the eight.
+const char *flatten_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax, const std::function<void()> *after_blocks = nullptr) {
     const int n = mv.n, m = mv.m;
     if (!mv.col_group || !mv.row_lhs || !mv.row_lhs_len) return "no structure hints";
     // blocks in order of their first column (the tick: worker order)
@@ -1608,6 +1683,7 @@ const char *flatten_model(const ModelView &mv, Prob &P, std::vector<double> &ub,
         T.blk_cap[(size_t)b * MMAX_BLOCK] = total;
         T.blk_m[b] = 1;
     }
+    if (after_blocks && *after_blocks) (*after_blocks)();
     P.K = (int)wide.size();
     if (P.K == 0) return "no wide row";
     P.h.resize(P.K); P.ge.resize(P.K); P.g_rows.assign(P.G, {});
@@ -1667,8 +1743,8 @@ uint64_t digest_of(const Prob &P) {
     return h;
 }
 
-const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax) {
-    const char *why = flatten_model(mv, P, ub, c, cmax);
+const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax, const std::function<void()> *after_blocks = nullptr) {
+    const char *why = flatten_model(mv, P, ub, c, cmax, after_blocks);   // (the checking flatten below and flatten_for_probe have no hook)
     if (!why && g_check_hints && mv.block_runs) {   // tests: everything the runs passed over, flattened block by block after all, must come out the same
         ModelView plain = mv; plain.block_runs = nullptr; plain.n_block_runs = 0;
         Prob P2; std::vector<double> ub2, c2; double cmax2 = 0.0;
@@ -1760,9 +1836,15 @@ Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, dou
     Request rq;
     rq.n = mv.n; rq.m = mv.m; rq.rel_gap = rel_gap; rq.time_limit_s = time_limit_s; rq.deadline_s = deadline_s; rq.trace = trace;
     Solver S(rq, sw);
+    S.tp0 = tp0;
+    if (g_capture_cut) g_first_cut.clear();
     std::vector<double> ub, c; double cmax = 1.0;
-        if (const char *why = build_from_model(mv, S.P, ub, c, cmax)) { Answer ans; ans.why = why; return ans; }
-        if (cost_scale) *cost_scale = cmax;
+    const std::function<void()> hook = [&S]() { S.launch_on_blocks(); };
+    if (const char *why = build_from_model(mv, S.P, ub, c, cmax, early_sweep_on() ? &hook : nullptr)) {
+        if (S.early_begun) sw.end();   // (refused behind the hook: a sweep may be in flight on tables that S.P owns — end() waits for it)
+        Answer ans; ans.why = why; return ans;
+    }
+    if (cost_scale) *cost_scale = cmax;
     Polisher pol(S.P, mv.n);
     rq.polish = [&pol](std::vector<double> &x, double &value) { return pol.run(x, value); };
     return run_solver(S, tp0);
@@ -1775,6 +1857,10 @@ void flatten_for_probe(const ModelView &mv, bool trace) {
 }
 
 void set_check_hints(bool on) { g_check_hints = on; g_hint_mismatches = 0; }
+void set_early_sweep(int on) { g_early_sweep = on; g_early_sweeps = 0; }
+uint32_t early_sweeps() { return g_early_sweeps; }
+void capture_first_cut(bool on) { g_capture_cut = on; g_first_cut.clear(); }
+const std::vector<unsigned char> &first_cut_bytes() { return g_first_cut; }
 int hint_mismatches() { return g_hint_mismatches; }
 
 Answer solve(const Request &rq, Sweeper &sw) {

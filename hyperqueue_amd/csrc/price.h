@@ -49,6 +49,13 @@ void totals_from_blocks(uint32_t n_blocks, uint32_t K, const double *cx, const d
 struct Sweeper {
     virtual ~Sweeper() {}
     virtual bool begin(const HostTables &t, uint32_t max_sweeps) = 0;       // false: cannot run this model (the host search takes over)
+    // begin() in two halves, for the flattener (price.cpp: flatten_model), whose block tables are final well before its wide rows' tables are.  begin_blocks takes
+    // t.n_blocks, t.n_cols and the six block arrays (blk_off, blk_m, blk_cap, col_cost, col_a, col_cap) — the rest of `t` is not read — and allows ONE sweep_launch
+    // with no prices at all (K = 0: every column without wide-row entries, no activities; at zero prices the blocks' patterns, c.x, reduced values and bounds are the
+    // same).  begin_wide then takes t.K, col_woff, w_row and w_coef from the same `t`: from there on the sweeper is where begin() would have left it.
+    // begin_blocks: 1 = taken, 0 = refused like begin(), -1 = no split here (the caller calls begin() once the tables are complete).
+    virtual int begin_blocks(const HostTables &t, uint32_t max_sweeps) { (void)t; (void)max_sweeps; return -1; }
+    virtual bool begin_wide() { return false; }
     virtual bool set_caps(const int32_t *col_cap) = 0;                      // new column bounds for the following sweeps
     virtual bool set_block_caps(const double *blk_cap) = 0;                 // new row capacities [n_blocks * 4] (a branch that fixes part of a block's content)
     virtual bool sweep(const double *pi, SweepTotals &out) = 0;             // sweep number = count of sweeps since begin()
@@ -126,6 +133,13 @@ struct ModelView {
 // tests: also check the builder's column bounds against the rows they stand for (this thread); mismatches since the last call that switched it on
 void set_check_hints(bool on);
 int hint_mismatches();
+// The zero-price sweep launched from inside the flattening, on the block tables alone (Sweeper::begin_blocks), for this thread: 1 on, 0 off (begin() and the first
+// launch once the model is flattened), -1 the default (on unless HQPRICE_EARLY_SWEEP=0).
+void set_early_sweep(int on);
+uint32_t early_sweeps();   // tests: sweeps launched that way on this thread since the last set_early_sweep
+// tests: keep the first cut of this thread's following solves — act [K], part_act [PARTS * K] (int64), c.x, bound, part_cx [PARTS] (f64), in this order, as bytes
+void capture_first_cut(bool on);
+const std::vector<unsigned char> &first_cut_bytes();
 // tests: the flattening alone (what it leaves goes to mv.run_stats / mv.tables_digest and is dropped)
 void flatten_for_probe(const ModelView &mv, bool trace);
 Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, double deadline_s, bool trace, Sweeper &sw, double *cost_scale);
@@ -155,7 +169,7 @@ struct ShardedSweeper : Sweeper {
     uint32_t min_blocks = 1025;   // models with fewer blocks are swept whole by every rank (one round of resident workgroups: a sweep costs ~70 us whatever its block count up to 1024)
     bool pass = false;            // ... decided in begin(), the same on every rank
     ShardedSweeper(Sweeper &in, Exchange &e, uint32_t min_blocks_) : inner(in), ex(e), min_blocks(min_blocks_) { min_cols = in.min_cols; budget = in.budget; }
-    bool begin(const HostTables &t, uint32_t max_sweeps) override;
+    bool begin(const HostTables &t, uint32_t max_sweeps) override;   // (no begin_blocks here: whether the ranks sweep at all is settled by an exchange, which wants the whole model — DESIGN.md §7)
     bool set_caps(const int32_t *col_cap) override { return inner.set_caps(col_cap); }
     bool set_block_caps(const double *blk_cap) override { return inner.set_block_caps(blk_cap); }
     bool sweep(const double *pi, SweepTotals &out) override;

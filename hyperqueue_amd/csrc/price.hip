@@ -231,24 +231,38 @@ double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::
 
 DeviceSweeper::~DeviceSweeper() { h_stage.release(); h_res.release(); h_pats.release(); h_pin.release(); h_blkv.release(); d_tab.release(); d_pats.release(); d_blk.release(); d_sync.release(); d_prof.release(); }
 
-bool DeviceSweeper::begin(const HostTables &t, uint32_t max_sweeps) {
-    if (t.K > (uint32_t)KMAX || t.n_blocks == 0) return false;
+// the part of begin() that does not depend on the wide rows: the sweep's state, the working-set size, the offsets of the block arrays and of col_woff / w_row, every
+// buffer but h_stage / d_tab
+bool DeviceSweeper::size_buffers(const HostTables &t, uint32_t max_sweeps) {
     if (profile && (!h_prof.ensure((size_t)t.n_blocks * PSLOTS * 8 + 64) || !d_prof.ensure((size_t)t.n_blocks * PSLOTS * 8 + 64))) return false;
-    T = &t; n_sweeps = 0; cap_sweeps = max_sweeps;
+    T = &t; n_sweeps = 0; cap_sweeps = max_sweeps; blocks_only = false;
     max_block_cols = 0;
     for (uint32_t b = 0; b < t.n_blocks; b++) max_block_cols = std::max(max_block_cols, t.blk_off[b + 1] - t.blk_off[b]);
     if (force_nmax) max_block_cols = (uint32_t)hqblock::NMAX;   // (HQTICK_PRICE_NMAX=1: the full-size working set whatever the model — A/B switch)
-    const size_t nw = t.w_row.size();
     o_off = 0; o_m = al16(o_off + (size_t)(t.n_blocks + 1) * 4); o_cap = al16(o_m + t.n_blocks); o_cost = al16(o_cap + (size_t)t.n_blocks * MMAX * 8);
     o_a = al16(o_cost + (size_t)t.n_cols * 8); o_ccap = al16(o_a + (size_t)t.n_cols * MMAX * 8); o_woff = al16(o_ccap + (size_t)t.n_cols * 4);
-    o_wrow = al16(o_woff + (size_t)(t.n_cols + 1) * 4); o_wcoef = al16(o_wrow + nw * 2); tab_bytes = al16(o_wcoef + nw * 4);
-    if (!h_stage.ensure(tab_bytes) || !d_tab.ensure(tab_bytes) || !h_res.ensure(sizeof(SweepResult) + 64)) return false;
+    o_wrow = al16(o_woff + (size_t)(t.n_cols + 1) * 4);
+    if (!h_res.ensure(sizeof(SweepResult) + 64)) return false;
     if (!h_pin.ensure((size_t)std::min<uint32_t>(max_sweeps, PIN_SWEEPS) * t.n_cols * 2 + 64)) return false;
     in_flight = false;
-    if (!d_pats.ensure((size_t)max_sweeps * t.n_cols * 2) || !d_blk.ensure((size_t)t.n_blocks * 28 + 64) || !d_sync.ensure(SYNC_BYTES)) return false;
+    return d_pats.ensure((size_t)max_sweeps * t.n_cols * 2) && d_blk.ensure((size_t)t.n_blocks * 28 + 64) && d_sync.ensure(SYNC_BYTES);
+}
+
+void DeviceSweeper::stage_blocks(const HostTables &t) {
     unsigned char *h = h_stage.as<unsigned char>();
     memcpy(h + o_off, t.blk_off.data(), (size_t)(t.n_blocks + 1) * 4); memcpy(h + o_m, t.blk_m.data(), t.n_blocks); memcpy(h + o_cap, t.blk_cap.data(), (size_t)t.n_blocks * MMAX * 8);
     memcpy(h + o_cost, t.col_cost.data(), (size_t)t.n_cols * 8); memcpy(h + o_a, t.col_a.data(), (size_t)t.n_cols * MMAX * 8); memcpy(h + o_ccap, t.col_cap.data(), (size_t)t.n_cols * 4);
+}
+
+bool DeviceSweeper::begin(const HostTables &t, uint32_t max_sweeps) {
+    if (t.K > (uint32_t)KMAX || t.n_blocks == 0) return false;
+    if (!size_buffers(t, max_sweeps)) return false;
+    const size_t nw = t.w_row.size();
+    wide_room = std::max(wide_room, nw);
+    o_wcoef = al16(o_wrow + nw * 2); tab_bytes = al16(o_wcoef + nw * 4);
+    if (!h_stage.ensure(tab_bytes) || !d_tab.ensure(tab_bytes)) return false;
+    unsigned char *h = h_stage.as<unsigned char>();
+    stage_blocks(t);
     memcpy(h + o_woff, t.col_woff.data(), (size_t)(t.n_cols + 1) * 4);
     if (nw) { memcpy(h + o_wrow, t.w_row.data(), nw * 2); memcpy(h + o_wcoef, t.w_coef.data(), nw * 4); }
     if (hipMemcpyAsync(d_tab.p, h, tab_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return false;
@@ -257,6 +271,55 @@ bool DeviceSweeper::begin(const HostTables &t, uint32_t max_sweeps) {
     if (!sync_clean) { if (hipMemsetAsync(d_sync.p, 0, SYNC_BYTES, stream) != hipSuccess) return false; }
     SweepResult *r = h_res.as<SweepResult>();
     seq = r->seq;  // (whatever the last solve left: the next sweep writes seq + 1)
+    return true;
+}
+
+// The block arrays and an all-zero col_woff: what a sweep without prices reads (price_core.h: with every column's entry range empty and K = 0 it stages no price and no
+// entry, and adds to no accumulator; price.hip's tail loads, zeroes and stores the activity vectors for k < K only).  t.K, t.col_woff, t.w_row and t.w_coef are not read.
+int DeviceSweeper::begin_blocks(const HostTables &t, uint32_t max_sweeps) {
+    if (t.n_blocks == 0 || !size_buffers(t, max_sweeps)) return 0;
+    // room for the wide rows' entries, which are not known yet: the most any model had so far, at least four per column (c3p has two) — begin_wide grows the buffers
+    // if that is not enough, after waiting for the sweep
+    const size_t room = std::max(wide_room, (size_t)t.n_cols * 4);
+    o_wcoef = o_wrow; tab_bytes = o_wrow;   // (until begin_wide: the kernel's w_row / w_coef pointers stay inside the buffer; it reads neither)
+    const size_t dev_bytes = al16(al16(o_wrow + room * 2) + room * 4);
+    if (!h_stage.ensure(o_wrow + (dev_bytes - o_woff)) || !d_tab.ensure(dev_bytes)) return 0;
+    unsigned char *h = h_stage.as<unsigned char>();
+    stage_blocks(t);
+    memset(h + o_woff, 0, o_wrow - o_woff);
+    if (hipMemcpyAsync(d_tab.p, h, o_wrow, hipMemcpyHostToDevice, stream) != hipSuccess) return 0;
+    if (!sync_clean) { if (hipMemsetAsync(d_sync.p, 0, SYNC_BYTES, stream) != hipSuccess) return 0; }
+    seq = h_res.as<SweepResult>()->seq;
+    blocks_only = true;
+    return 1;
+}
+
+// col_woff, w_row, w_coef behind the sweep in flight, on its stream: the device's table then holds the bytes begin() uploads.
+bool DeviceSweeper::begin_wide() {
+    if (!T || !blocks_only) return false;
+    const HostTables &t = *T;
+    if (t.K > (uint32_t)KMAX || t.col_woff.size() != (size_t)t.n_cols + 1) return false;
+    const size_t nw = t.w_row.size();
+    wide_room = std::max(wide_room, nw);
+    o_wcoef = al16(o_wrow + nw * 2); tab_bytes = al16(o_wcoef + nw * 4);
+    const size_t wide_bytes = tab_bytes - o_woff;
+    if (o_wrow + wide_bytes > h_stage.cap || tab_bytes > d_tab.cap) {
+        // more entries than there was room left for: nothing may move under the sweep, so it is waited for (its result stays in pinned memory for sweep_finish), the
+        // buffers grow and the whole table goes up again
+        if (hipStreamSynchronize(stream) != hipSuccess) return false;
+        if (!h_stage.ensure(o_wrow + wide_bytes) || !d_tab.ensure(tab_bytes)) return false;
+        unsigned char *h = h_stage.as<unsigned char>();
+        stage_blocks(t);
+        memcpy(h + o_woff, t.col_woff.data(), (size_t)(t.n_cols + 1) * 4);
+        if (nw) { memcpy(h + o_wrow, t.w_row.data(), nw * 2); memcpy(h + o_wcoef, t.w_coef.data(), nw * 4); }
+        if (hipMemcpyAsync(d_tab.p, h, tab_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return false;
+    } else {
+        unsigned char *h = h_stage.as<unsigned char>() + o_wrow;   // image of the device's bytes [o_woff, tab_bytes)
+        memcpy(h, t.col_woff.data(), (size_t)(t.n_cols + 1) * 4);
+        if (nw) { memcpy(h + (o_wrow - o_woff), t.w_row.data(), nw * 2); memcpy(h + (o_wcoef - o_woff), t.w_coef.data(), nw * 4); }
+        if (hipMemcpyAsync(d_tab.as<unsigned char>() + o_woff, h, wide_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return false;
+    }
+    blocks_only = false;
     return true;
 }
 
@@ -297,10 +360,12 @@ bool DeviceSweeper::sweep_finish(SweepTotals &out) { return wait_done(&out); }
 
 bool DeviceSweeper::launch_only(const double *pi, uint32_t b0, uint32_t b1, bool local) {
     if (!T || n_sweeps >= cap_sweeps || b1 <= b0 || in_flight) return false;
+    if (blocks_only && (n_sweeps != 0 || local)) return false;   // (between begin_blocks and begin_wide: the one sweep without prices)
     const HostTables &t = *T;
+    const uint32_t K = blocks_only ? 0u : t.K;
     unsigned char *d = d_tab.as<unsigned char>();
     SweepArgs a;
-    a.t = Tables{t.n_blocks, t.n_cols, t.K, (const uint32_t *)(d + o_off), (const uint8_t *)(d + o_m), (const double *)(d + o_cap), (const double *)(d + o_cost), (const double *)(d + o_a),
+    a.t = Tables{t.n_blocks, t.n_cols, K, (const uint32_t *)(d + o_off), (const uint8_t *)(d + o_m), (const double *)(d + o_cap), (const double *)(d + o_cost), (const double *)(d + o_a),
                  (const int32_t *)(d + o_ccap), (const uint32_t *)(d + o_woff), (const uint16_t *)(d + o_wrow), (const int32_t *)(d + o_wcoef)};
     unsigned char *blk = d_blk.as<unsigned char>();
     // the patterns of the first PIN_SWEEPS sweeps go straight into pinned host memory (16 B per block over PCIe, complete when the completion word is: every block waits
@@ -314,7 +379,7 @@ bool DeviceSweeper::launch_only(const double *pi, uint32_t b0, uint32_t b1, bool
     if (local) { unsigned char *lv = h_blkv.dev<unsigned char>(); a.lv_cx = (double *)lv; a.lv_rc = (double *)(lv + (size_t)t.n_blocks * 8); a.lv_bnd = (double *)(lv + (size_t)t.n_blocks * 16); a.lv_steps = (uint32_t *)(lv + (size_t)t.n_blocks * 24); }
     else { a.lv_cx = a.lv_rc = a.lv_bnd = nullptr; a.lv_steps = nullptr; }
     memset(a.pi, 0, sizeof(a.pi));
-    memcpy(a.pi, pi, (size_t)t.K * 8);
+    if (K) memcpy(a.pi, pi, (size_t)K * 8);
     const double t0 = now_us();
     // wavefronts per block: four.  (Measured on configs[3]'s 4096 sixteen-column blocks as well, where the helpers cost residency — six blocks per CU instead of
     // nine: 193 us per sweep against 219 with two and 226 with one; profiles/r06/price_sweep_waves.txt.)
@@ -328,7 +393,7 @@ bool DeviceSweeper::launch_only(const double *pi, uint32_t b0, uint32_t b1, bool
 #undef HQ_SWEEP_N
 #undef HQ_SWEEP
     if (hipGetLastError() != hipSuccess) return false;
-    in_flight = true; sync_clean = false; flight_t0 = t0; flight_blocks = b1 - b0;
+    in_flight = true; sync_clean = false; flight_t0 = t0; flight_blocks = b1 - b0; flight_k = K;
     return true;
 }
 
@@ -371,11 +436,12 @@ bool DeviceSweeper::wait_done(SweepTotals *outp) {
     if (!outp) return true;
     SweepTotals &out = *outp;
     out.cx = r->cx; out.rc = r->rc; out.bnd = r->bnd; out.n_budget = r->n_budget; out.max_steps = r->max_steps;
-    out.act.resize(t.K);
-    for (uint32_t k = 0; k < t.K; k++) out.act[k] = r->act[k];
+    const uint32_t K = flight_k;   // (0: the sweep ran without the wide rows — no activities; the caller adds them up from the patterns)
+    out.act.resize(K);
+    for (uint32_t k = 0; k < K; k++) out.act[k] = r->act[k];
     out.part_cx.assign(r->part_cx, r->part_cx + ASLOTS);
-    out.part_act.resize((size_t)ASLOTS * t.K);
-    for (size_t i = 0; i < (size_t)ASLOTS * t.K; i++) out.part_act[i] = r->part_act[i];
+    out.part_act.resize((size_t)ASLOTS * K);
+    for (size_t i = 0; i < (size_t)ASLOTS * K; i++) out.part_act[i] = r->part_act[i];
     return true;
 }
 
@@ -401,7 +467,7 @@ void DeviceSweeper::end() {
         fprintf(stderr, "  most search steps of a block %.0f; sweep as the host saw it %.1f us\n", prof_steps / prof_n, total_us / (double)std::max<uint64_t>(1, total_sweeps));
         for (int st = 0; st < NPROF; st++) prof_med[st] = prof_max[st] = 0; prof_steps = 0; prof_span = prof_tail = 0; prof_n = 0;
     }
-    T = nullptr;
+    T = nullptr; blocks_only = false;
 }
 
 }  // namespace hqprice

@@ -19,6 +19,12 @@ struct DeviceSweeper : Sweeper {
     hqbuf::DevBuf d_tab, d_pats, d_blk, d_sync, d_prof;
     const HostTables *T = nullptr;
     size_t o_off = 0, o_m = 0, o_cap = 0, o_cost = 0, o_a = 0, o_ccap = 0, o_woff = 0, o_wrow = 0, o_wcoef = 0, tab_bytes = 0;
+    // begin() in two halves (price.h): between begin_blocks and begin_wide the device holds the block arrays and an all-zero col_woff, and one sweep without prices
+    // (K = 0) may run.  Staging (h_stage): [0, o_wrow) is the image of the device's bytes [0, o_wrow) — block arrays + the zero col_woff —, which the first copy reads;
+    // begin_wide stages the device's bytes [o_woff, tab_bytes) BEHIND it, at o_wrow, so that nothing the first copy may still be reading is written again.
+    bool blocks_only = false;
+    uint32_t flight_k = 0;        // wide left-hand sides of the sweep in flight (0: launched between the two halves)
+    size_t wide_room = 0;         // most wide-row entries of a model so far: what begin_blocks leaves room for, so that begin_wide need not grow a buffer under a sweep
     uint32_t n_sweeps = 0, cap_sweeps = 0, seq = 0;
     uint32_t max_block_cols = 0;   // widest block of the model at hand: picks the kernel's working-set size (price.hip)
     bool force_nmax = getenv("HQTICK_PRICE_NMAX") != nullptr;
@@ -30,6 +36,10 @@ struct DeviceSweeper : Sweeper {
     explicit DeviceSweeper(hipStream_t s) : stream(s) {}
     ~DeviceSweeper() override;
     bool begin(const HostTables &t, uint32_t max_sweeps) override;
+    int begin_blocks(const HostTables &t, uint32_t max_sweeps) override;
+    bool begin_wide() override;
+    bool size_buffers(const HostTables &t, uint32_t max_sweeps);   // everything but the tables' own two buffers
+    void stage_blocks(const HostTables &t);                        // the six block arrays -> h_stage
     bool set_caps(const int32_t *col_cap) override;
     bool set_block_caps(const double *blk_cap) override;
     bool sweep(const double *pi, SweepTotals &out) override;

@@ -18,7 +18,16 @@ struct EmulatedSweeper : Sweeper {
     uint32_t n_sweeps = 0, cap_sweeps = 0;
     // fault injection (hqtick_debug_set_price_fault): begin() refuses the model (fail_at == 0) / the sweep number fail_at - 1 fails (fail_at >= 1); -1: off
     int fail_at = -1;
+    // begin() in two halves (price.h), in the order the device walks them: the sweep launched between the halves runs AT the launch, on the block arrays and an
+    // all-zero col_woff with K = 0 — the wide rows' tables need not exist yet —, and its totals wait for sweep_finish
+    bool blocks_only = false, held_there = false;
+    std::vector<uint32_t> zero_woff;
+    SweepTotals held;
     bool begin(const HostTables &t, uint32_t max_sweeps) override;
+    int begin_blocks(const HostTables &t, uint32_t max_sweeps) override;
+    bool begin_wide() override;
+    bool sweep_launch(const double *pi) override;
+    bool sweep_finish(SweepTotals &out) override;
     bool set_caps(const int32_t *col_cap) override;
     bool set_block_caps(const double *blk_cap) override;
     bool sweep(const double *pi, SweepTotals &out) override;

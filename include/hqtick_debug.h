@@ -110,6 +110,15 @@ void hqtick_debug_set_block_runs(int on);
  * the model, out[1] = the same over what the fast path flattened it into (the problem and its sweep tables; 0: the model did not get there), out[2] = runs the builder
  * recorded, out[3] = blocks covered by the runs that passed the flattener's comparison. */
 void hqtick_debug_last_coupled_digest(uint64_t out[4]);
+/* The first sweep of a coupled solve (zero prices) launched from inside the flattening, as soon as the block tables are final (csrc/price.h: Sweeper::begin_blocks),
+ * for this thread: 1 on, 0 off (the sweeper gets the complete tables, then the first launch), -1 the default (on unless HQPRICE_EARLY_SWEEP=0).  Both orders must
+ * give the same tables, cuts and answers in every byte. */
+void hqtick_debug_set_early_sweep(int on);
+uint32_t hqtick_debug_early_sweeps(void);   /* sweeps launched that way on this thread since the last hqtick_debug_set_early_sweep */
+/* on != 0: this thread's fast-path solves keep their first cut; hqtick_debug_first_cut copies up to cap bytes of the last one to out and returns its size —
+ * act [K] and part_act [16 * K] as int64, then c.x, the bound and part_cx [16] as f64 (0: no solve got to its first cut). */
+void hqtick_debug_capture_first_cut(int on);
+uint32_t hqtick_debug_first_cut(unsigned char *out, uint32_t cap);
 /* fault injection: on != 0 makes the builder merge its first two runs into one false claim (the flattener must refuse it and flatten those blocks one by one). */
 void hqtick_debug_corrupt_block_runs(int on);
 /* sweeps over all blocks / flag configurations of the last hqtick_debug_host_stages call (0: the host search ran alone) */
