@@ -99,6 +99,7 @@ struct hqtick_ctx {
     bool last_ordered = false;    // the pending selection (last_valid) is one of the view: consume / restore replay it with order_select
     hqk::OrderSelect last_os{};   // ... its tables (HBM copy of the plan, the permutation)
     uint32_t dbg_order_runs = 0, dbg_order_levels = 0; bool dbg_order = false; double dbg_order_us = 0;  // hqtick_debug_last_order
+    uint32_t dbg_scan_L = 0, dbg_scan_G = 0, dbg_scan_shape[4] = {0, 0, 0, 0}; bool dbg_scan = false, dbg_census = false;  // hqtick_debug_last_scan: what the last dense scan (phase_a) / census (census_resident, on the query sub-context) left in h_a, h_levels, h_lv
     uint32_t lv_seq = 0; bool set_clean = false; bool no_spec_scan = getenv("HQTICK_NO_SPEC_SCAN") != nullptr; bool levels_valid = false; uint32_t cached_L = 0; std::vector<uint64_t> h_levels; bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))  // level table of the previous tick (re-validated by K1 every tick)
     PinBuf h_up, h_up2, h_q, h_a, h_plan, h_rec, h_sinkhdr, h_add, h_addp, h_retr, h_blk, h_k5a, h_lv;   // (h_lv: the level table as k_sort_levels writes it)
     PinBuf h_blkprof; uint32_t n_blkprof = 0; bool block_profile = false;
@@ -520,7 +521,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
     const bool scan = N != 0 && Q != 0;
     const uint32_t nvs = Q ? s->rq_variant_off[Q] : 0;
     const size_t nwv = (size_t)W * nvs;
-    ctx->dbg_order = false;
+    ctx->dbg_order = false; ctx->dbg_scan = false; ctx->dbg_census = false;   // (h_a and h_lv are rewritten from here on)
     // the ordered view where the dense table does not fit: forced (HQTICK_ORDERED_VIEW=1), or the last dense attempt did not fit
     if (scan && (ctx->force_ordered || ctx->ordered_sticky)) return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs);
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -661,6 +662,10 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
             }
             if (ctx->timing || ctx->timing_k1) { const double us_ = elapsed_us(ctx->ev[2], ctx->ev[3]); if (us_ >= 0) ctx->stats.level_hist_us = us_; }
             if (ctx->timing && !spec) { const double us_ = elapsed_us(ctx->ev[0], ctx->ev[8]); if (us_ >= 0) ctx->stats.scan_us = us_; }  // (a speculative scan shares ev[0] with the discovery: K1b untimed on that tick)
+        }
+        if (scan) {
+            ctx->dbg_scan = true; ctx->dbg_scan_L = sc->L; ctx->dbg_scan_G = sc->G;
+            ctx->dbg_scan_shape[0] = sc->geom.waves_per_block; ctx->dbg_scan_shape[1] = sc->geom.tasks_per_wave; ctx->dbg_scan_shape[2] = sc->geom.n_waves; ctx->dbg_scan_shape[3] = hqk::lds_levels_for(sc->L) ? 1u : 0u;
         }
         runs_from_hist(*sc);
         return 0;
@@ -2502,6 +2507,7 @@ static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_quer
 static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc) {
     sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
     runs_from_hist(*sc);
+    q->dbg_census = false;
     const uint64_t N = ctx->n_ready;
     if (N == 0 || Q == 0 || ctx->n_live == 0) return 0;
     const size_t tab_words = 4 + (size_t)std::min<uint64_t>(hqk::MAX_GROUPS, (uint64_t)Q * hqk::MAX_LEVELS);   // [err x 4][counts]: what the census can write for this Q
@@ -2534,6 +2540,7 @@ static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc)
     sc->L = L; sc->G = L * Q;
     sc->levels.assign(q->h_lv.as<uint64_t>() + 2, q->h_lv.as<uint64_t>() + 2 + L);
     sc->hist.assign(h + 4, h + 4 + sc->G);
+    q->dbg_census = true; q->dbg_scan_L = sc->L; q->dbg_scan_G = sc->G;
     runs_from_hist(*sc);
     return 0;
 }
@@ -2675,6 +2682,22 @@ int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n
     if (n_levels) *n_levels = ctx->dbg_order ? ctx->dbg_order_levels : 0;
     if (order_us) *order_us = ctx->dbg_order ? ctx->dbg_order_us : 0.0;
     return ctx->dbg_order ? 1 : 0;
+}
+int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels, uint32_t *n_groups, uint32_t shape[4], uint64_t *levels, uint32_t cap_levels, uint32_t *hist,
+                           uint32_t cap_groups) {
+    if (!ctx || (which != 0 && which != 1)) return HQTICK_E_INVALID;
+    const hqtick_ctx *c = which == 0 ? ctx : ctx->qctx;
+    if (!c || !(which == 0 ? c->dbg_scan : c->dbg_census)) return 0;
+    const uint32_t L = c->dbg_scan_L, G = c->dbg_scan_G;
+    // both forms keep 16 bytes in front of the counts in h_a: phase A its flag words, the census its four error words
+    const uint64_t *lv = which == 0 ? c->h_levels.data() : c->h_lv.as<uint64_t>() + 2;
+    const uint32_t *hs = reinterpret_cast<const uint32_t *>(c->h_a.as<unsigned char>() + 16);
+    if (n_levels) *n_levels = L;
+    if (n_groups) *n_groups = G;
+    if (shape) for (int i = 0; i < 4; i++) shape[i] = which == 0 ? c->dbg_scan_shape[i] : 0u;
+    if (levels) for (uint32_t i = 0; i < L && i < cap_levels; i++) levels[i] = lv[i];
+    if (hist) for (uint32_t i = 0; i < G && i < cap_groups; i++) hist[i] = hs[i];
+    return 1;
 }
 void hqtick_debug_set_block_emulation(int on, uint32_t budget) { g_block_emulation = on; if (budget) g_block_budget = budget; }
 void hqtick_debug_last_blocks(uint32_t *n_emulated, uint32_t *n_host) { if (n_emulated) *n_emulated = g_last_blocks_device; if (n_host) *n_host = g_last_blocks_host; }

@@ -46,6 +46,7 @@ hipError_t level_hist(const uint64_t *prio, const uint32_t *rq, uint64_t n, cons
                 const uint32_t *n_levels_dev = nullptr);
 // n_levels_dev (device, may be NULL): the launch does not know the level table yet — k_sort_levels is still ahead of it on the stream.  L is then the bound the launch
 // is sized for (<= 4), the kernel reads the count and the table from HBM and sets bit 4 of err_flag if there are more levels than that (or none).
+uint32_t lds_levels_for(uint32_t L);  // entries of the level table K1 stages in LDS (0: more than 1024 levels, the table is searched in HBM; up to four levels travel in the kernel arguments instead)
 // K1b: exclusive scan of every wave_tab row (in place -> offsets) and the row totals into hist[G].
 // err_in (device) is forwarded to err_out (may be pinned host memory) by the same launch.
 hipError_t empty_like_level_hist(WaveGeom geom, hipStream_t s);  // an empty kernel of K1's grid (calibration of the per-dispatch timing)

@@ -1152,7 +1152,7 @@ __global__ void __launch_bounds__(256) k_scan_rows_wg(uint32_t *__restrict__ wav
     if (threadIdx.x == 0) hist[row] = carry;
 }
 
-static uint32_t lds_levels_for(uint32_t L) { return L <= 1024 ? L : 0; }
+uint32_t lds_levels_for(uint32_t L) { return L <= 1024 ? L : 0; }
 
 // An empty kernel of K1's grid, launched the way the measured kernels are: what a dispatch bracketed by its own start / stop events records when the kernel does
 // nothing (bench.py: `roofline.empty_launch_us` — the floor of the duration `roofline.frac` is priced on).

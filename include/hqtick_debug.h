@@ -31,6 +31,15 @@ int hqtick_debug_milp_solve(int ncols, const double *obj, const uint8_t *col_kin
  * pairs, n_levels = distinct priorities, order_us = event time of the view's kernels (0 under HQTICK_FLAG_NO_KERNEL_TIMING); all 0 otherwise. */
 int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n_levels, double *order_us);
 
+/* What the dense (level, request) scan left in host memory, read back without a copy, a launch or a synchronisation.  GPU only.
+ * which = 0: the dense scan of the context's last tick.  which = 1: the census of its last hqtick_query_resident.
+ * Returns 1 and fills the outputs if that call ran the dense table, 0 (nothing written) if it took the ordered view or scanned nothing.
+ * levels: up to cap_levels values, descending; hist: up to cap_groups counts, index level * Q + rq; either may be NULL.
+ * shape[4] (which = 0): waves_per_block, tasks_per_wave, n_waves, 1 if the level table was staged in LDS (or, with at most four levels, travelled in the
+ * kernel arguments) and 0 if K1 searched it in HBM; zeros for which = 1. */
+int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels, uint32_t *n_groups, uint32_t shape[4],
+                           uint64_t *levels, uint32_t cap_levels, uint32_t *hist, uint32_t cap_groups);
+
 /* The HOST stages of a tick — create_task_batches + run_scheduling_solver (scheduler/batches.rs:42-181, scheduler/solver.rs:36-483) — on
  * caller-supplied outputs of the GPU scans, so that this logic can be unit-tested on a machine without a GPU.  This is not a tick: the scans
  * (K0/K1/K2), the selection and the mapping have no CPU implementation, and nothing in the product calls this.
