@@ -3,7 +3,9 @@
 `WireTables` / `WireRecords` flatten the host's view -- task attributes, interned `TaskConfiguration`s, the tick's mapping -- into the SoA
 arrays of the ABI.  `encode_device` places them in HBM (torch tensors, plumbing only) and runs the three kernels of
 `hqwire_encode_device`; `encode_host_debug` hands host arrays to `hqwire_debug_encode_host`, which executes the same phase functions on
-the CPU (tests only).  There is no Python encoder here: the oracle lives in `oracle/wire_oracle.py` and is imported by tests only.
+the CPU (tests only).  `WireTable` is the attribute table kept resident by the library instead (`hqwire_table_*`): deltas in, a view for the encoder
+out; both encode entry points take one in place of a `WireTables` and then upload no table.  There is no Python encoder here: the oracle lives in
+`oracle/wire_oracle.py` and is imported by tests only.
 """
 from __future__ import annotations
 
@@ -15,7 +17,8 @@ import numpy as np
 
 from . import tick
 
-HQWIRE_ABI_VERSION = 2
+HQWIRE_ABI_VERSION = 3
+HQWIRE_TABLE_TILE = 256
 HQWIRE_MAX_FRAGMENTS = 16
 HQWIRE_MAX_RECORDS = 2048
 SLOT_OK, SLOT_OVERSIZE, SLOT_UNKNOWN, SLOT_TOO_MANY = 0, 1, 2, 3
@@ -41,7 +44,40 @@ class OutputC(C.Structure):
                 ("scratch_bytes", C.c_uint64), ("slot_nfrag", _vp), ("frag_end", _vp), ("msg_size_limit", C.c_uint64)]
 
 
-SYMBOLS = ["hqwire_scratch_bytes", "hqwire_encode_device", "hqwire_abi_version"]
+class TableConfigC(C.Structure):
+    _fields_ = [("initial_rows", C.c_uint64), ("initial_blob_bytes", C.c_uint64), ("initial_configs", C.c_uint64), ("initial_body_bytes", C.c_uint64)]
+
+
+class TableStatsC(C.Structure):
+    _fields_ = [("live_rows", C.c_uint64), ("physical_rows", C.c_uint64), ("blob_bytes", C.c_uint64), ("dead_blob_bytes", C.c_uint64), ("n_configs", C.c_uint64),
+                ("body_bytes", C.c_uint64), ("appends", C.c_uint64), ("merges", C.c_uint64), ("compactions", C.c_uint64), ("growths", C.c_uint64),
+                ("hbm_bytes", C.c_uint64), ("last_kernel_us", C.c_double)]
+
+
+SYMBOLS = ["hqwire_scratch_bytes", "hqwire_encode_device", "hqwire_abi_version", "hqwire_table_create", "hqwire_table_destroy", "hqwire_table_add_configs",
+           "hqwire_table_add_tasks", "hqwire_table_remove_tasks", "hqwire_table_set_instance", "hqwire_table_compact", "hqwire_table_view", "hqwire_table_copy_out",
+           "hqwire_table_get_stats", "hqwire_table_last_unknown", "hqwire_table_last_error"]
+
+
+def _table_prototypes(lib: C.CDLL) -> C.CDLL:
+    lib.hqwire_table_create.argtypes = [C.POINTER(_vp), C.POINTER(TableConfigC), _vp]
+    lib.hqwire_table_destroy.argtypes = [_vp]
+    lib.hqwire_table_destroy.restype = None
+    lib.hqwire_table_add_configs.argtypes = [_vp, C.c_uint32] + [_vp] * 5
+    lib.hqwire_table_add_tasks.argtypes = [_vp, C.c_uint64] + [_vp] * 8
+    lib.hqwire_table_remove_tasks.argtypes = [_vp, C.c_uint64, _vp]
+    lib.hqwire_table_set_instance.argtypes = [_vp, C.c_uint64, _vp, _vp]
+    for f in (lib.hqwire_table_add_configs, lib.hqwire_table_add_tasks, lib.hqwire_table_remove_tasks, lib.hqwire_table_set_instance):
+        f.restype = C.c_int64
+    lib.hqwire_table_compact.argtypes = [_vp]
+    lib.hqwire_table_view.argtypes = [_vp, C.POINTER(TablesC)]
+    lib.hqwire_table_copy_out.argtypes = [_vp, C.POINTER(TablesC)]
+    lib.hqwire_table_get_stats.argtypes = [_vp, C.POINTER(TableStatsC)]
+    lib.hqwire_table_last_unknown.argtypes = [_vp]
+    lib.hqwire_table_last_unknown.restype = C.c_uint64
+    lib.hqwire_table_last_error.argtypes = [_vp]
+    lib.hqwire_table_last_error.restype = C.c_char_p
+    return lib
 
 
 def load() -> C.CDLL:
@@ -50,7 +86,7 @@ def load() -> C.CDLL:
     lib.hqwire_scratch_bytes.restype = C.c_uint64
     lib.hqwire_encode_device.argtypes = [C.POINTER(TablesC), C.POINTER(RecordsC), C.POINTER(OutputC), _vp]
     lib.hqwire_abi_version.restype = C.c_uint32
-    return lib
+    return _table_prototypes(lib)
 
 
 @dataclass
@@ -153,6 +189,117 @@ class WireRecords:
                 self.mn_worker_off, self.mn_worker]
 
 
+class WireTable:
+    """`hqwire_table`: the attribute table resident in HBM, fed by deltas (numpy arrays in, counts out).  `host_order=None`: the product's table on the
+    device, its deltas enqueued on `stream` (a hipStream_t handle, e.g. `torch.cuda.current_stream().cuda_stream`; default the null stream).
+    `host_order=0/1/2`: the same class on host memory through `hqwire_debug_table_create_host` of libhqtick_test.so (tests only)."""
+
+    def __init__(self, initial_rows: int = 0, initial_blob_bytes: int = 0, initial_configs: int = 0, initial_body_bytes: int = 0, stream: int = 0,
+                 host_order: Optional[int] = None):
+        self.host_order = host_order
+        cfg = TableConfigC(initial_rows, initial_blob_bytes, initial_configs, initial_body_bytes)
+        h = _vp()
+        if host_order is None:
+            import torch  # noqa: F401  (torch bundles a HIP runtime of its own: it goes first, as in encode_device, so that the process ends up with one)
+
+            self.lib = load()
+            rc = self.lib.hqwire_table_create(C.byref(h), C.byref(cfg), _vp(stream))
+        else:
+            from . import _testhooks
+
+            self.lib = _table_prototypes(_testhooks.load())
+            self.lib.hqwire_debug_table_create_host.argtypes = [C.POINTER(_vp), C.POINTER(TableConfigC), C.c_int]
+            rc = self.lib.hqwire_debug_table_create_host(C.byref(h), C.byref(cfg), host_order)
+        if rc != 0:
+            raise tick.HqTickError(rc, "hqwire_table_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.hqwire_table_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _check(self, rc: int, what: str) -> int:
+        if rc < 0:
+            raise tick.HqTickError(int(rc), f"{what}: {self.last_error()}")
+        return int(rc)
+
+    @staticmethod
+    def _arr(a, dtype):
+        return None if a is None else np.ascontiguousarray(a, dtype)
+
+    @staticmethod
+    def _p(a):
+        return None if a is None else _vp(a.ctypes.data)
+
+    def add_configs(self, configs: Sequence[Tuple[Optional[Tuple[int, int]], bytes]]) -> int:
+        """configs: [(time_limit (secs, nanos) or None, body)] as `WireTables.build` takes them; returns the index of the first one."""
+        some = np.array([c[0] is not None for c in configs], np.uint8)
+        secs = np.array([c[0][0] if c[0] else 0 for c in configs], np.uint64)
+        nanos = np.array([c[0][1] if c[0] else 0 for c in configs], np.uint32)
+        off = np.zeros(len(configs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(c[1]) for c in configs], dtype=np.uint64) if configs else []
+        body = np.frombuffer(b"".join(c[1] for c in configs) or b"\0", np.uint8)
+        return self._check(self.lib.hqwire_table_add_configs(self.h, len(configs), self._p(some), self._p(secs), self._p(nanos), self._p(off), self._p(body)),
+                           "hqwire_table_add_configs")
+
+    def add_tasks_arrays(self, task_id, task_rq, task_instance, task_priority, task_config, entry_some=None, entry_off=None, entry_blob=None) -> int:
+        a = [self._arr(task_id, np.uint64), self._arr(task_rq, np.uint32), self._arr(task_instance, np.uint32), self._arr(task_priority, np.uint64),
+             self._arr(task_config, np.uint32), self._arr(entry_some, np.uint8), self._arr(entry_off, np.uint64), self._arr(entry_blob, np.uint8)]
+        return self._check(self.lib.hqwire_table_add_tasks(self.h, len(a[0]), *[self._p(x) for x in a]), "hqwire_table_add_tasks")
+
+    def add_tasks(self, attrs: Dict[int, Tuple[int, int, int, int, Optional[bytes]]]) -> int:
+        """attrs: task id -> (rq, instance_id, priority, config index, entry or None), as `WireTables.build` takes them (sent in ascending id order)."""
+        t = WireTables.build(attrs, [])
+        return self.add_tasks_arrays(t.task_id, t.task_rq, t.task_instance, t.task_priority, t.task_config, t.entry_some, t.entry_off, t.entry_blob)
+
+    def remove_tasks(self, ids) -> int:
+        a = self._arr(ids, np.uint64)
+        return self._check(self.lib.hqwire_table_remove_tasks(self.h, len(a), self._p(a)), "hqwire_table_remove_tasks")
+
+    def set_instance(self, ids, values=None) -> int:
+        a, v = self._arr(ids, np.uint64), self._arr(values, np.uint32)
+        return self._check(self.lib.hqwire_table_set_instance(self.h, len(a), self._p(a), self._p(v)), "hqwire_table_set_instance")
+
+    def compact(self) -> None:
+        self._check(self.lib.hqwire_table_compact(self.h), "hqwire_table_compact")
+
+    def view(self) -> TablesC:
+        """the pointers and counts `hqwire_encode_device` takes (device pointers; host pointers on the debug backend); valid until the next delta"""
+        tc = TablesC()
+        self._check(self.lib.hqwire_table_view(self.h, C.byref(tc)), "hqwire_table_view")
+        return tc
+
+    def stats(self) -> TableStatsC:
+        st = TableStatsC()
+        self._check(self.lib.hqwire_table_get_stats(self.h, C.byref(st)), "hqwire_table_get_stats")
+        return st
+
+    def counters(self) -> Dict[str, int]:
+        st = self.stats()
+        return {f: int(getattr(st, f)) for f, _ in TableStatsC._fields_ if f not in ("hbm_bytes", "last_kernel_us")}
+
+    def last_unknown(self) -> int:
+        return int(self.lib.hqwire_table_last_unknown(self.h))
+
+    def last_error(self) -> str:
+        return (self.lib.hqwire_table_last_error(self.h) or b"").decode()
+
+    def copy_out(self) -> WireTables:
+        """every array of the view on the host (dead rows included until a compaction); blobs padded to one byte when empty, as `WireTables.build` does"""
+        st = self.stats()
+        n, c = int(st.physical_rows), int(st.n_configs)
+        t = WireTables(np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint8),
+                       np.zeros(n + 1, np.uint64), np.zeros(max(1, int(st.blob_bytes)), np.uint8), np.zeros(c, np.uint8), np.zeros(c, np.uint64), np.zeros(c, np.uint32),
+                       np.zeros(c + 1, np.uint64), np.zeros(max(1, int(st.body_bytes)), np.uint8))
+        tc = TablesC(n, *[_vp(a.ctypes.data) for a in t.arrays()[:8]], c, *[_vp(a.ctypes.data) for a in t.arrays()[8:]])
+        self._check(self.lib.hqwire_table_copy_out(self.h, C.byref(tc)), "hqwire_table_copy_out")
+        assert tc.n_tasks == n and tc.n_configs == c
+        return t
+
+
 @dataclass
 class WireResult:
     status: int                    # HQWIRE_OK / HQWIRE_CAPACITY
@@ -189,7 +336,7 @@ def _padded(a: np.ndarray) -> np.ndarray:
 
 
 def _structs(t: WireTables, r: WireRecords, ptrs_t: List[int], ptrs_r: List[int]):
-    tc = TablesC(t.n_tasks, *ptrs_t[:8], t.n_configs, *ptrs_t[8:])
+    tc = t.view() if isinstance(t, WireTable) else TablesC(t.n_tasks, *ptrs_t[:8], t.n_configs, *ptrs_t[8:])
     rc = RecordsC(r.n_workers, r.n_records, *ptrs_r[:7], r.n_mn, *ptrs_r[7:])
     return tc, rc
 
@@ -203,7 +350,10 @@ def encode_host_debug(t: WireTables, r: WireRecords, capacity: int, order: int =
     lib.hqwire_scratch_bytes.argtypes = [C.c_uint64, C.c_uint64]
     lib.hqwire_scratch_bytes.restype = C.c_uint64
     lib.hqwire_debug_encode_host_order.argtypes = [C.POINTER(TablesC), C.POINTER(RecordsC), C.POINTER(OutputC), C.c_int]
-    ta, ra = [_padded(np.ascontiguousarray(a)) for a in t.arrays()], [_padded(np.ascontiguousarray(a)) for a in r.arrays()]
+    if isinstance(t, WireTable) and t.host_order is None:
+        raise ValueError("encode_host_debug takes a WireTable of the host debug backend")
+    ta = [] if isinstance(t, WireTable) else [_padded(np.ascontiguousarray(a)) for a in t.arrays()]
+    ra = [_padded(np.ascontiguousarray(a)) for a in r.arrays()]
     tc, rc = _structs(t, r, [a.ctypes.data for a in ta], [a.ctypes.data for a in ra])
     S = r.n_workers + r.n_mn
     data, slot_off, status, header = np.zeros(max(1, capacity), np.uint8), np.zeros(2 * S + 1, np.uint64), np.zeros(max(1, S), np.uint8), np.zeros(4, np.uint32)
@@ -238,16 +388,25 @@ def _run_device(lib, torch, dev, tc: TablesC, rc: RecordsC, n_slots: int, n_rec_
                       nfrag.cpu().numpy().view(np.uint32)[:n_slots].copy(), frag_end.cpu().numpy().view(np.uint64).copy())
 
 
+uploaded_bytes = 0  # what this binding has copied to the device (tests: an encode on a WireTable uploads no table)
+
+
 def _upload(torch, dev, arrays: List[np.ndarray]):
+    global uploaded_bytes
+    uploaded_bytes += sum(_padded(a).nbytes for a in arrays)
     return [torch.from_numpy(_padded(np.ascontiguousarray(a)).view(np.uint8).copy()).to(dev) for a in arrays]
 
 
 def encode_device(t: WireTables, r: WireRecords, capacity: int, device: str = "cuda:0", limit: int = 0) -> WireResult:
-    """`hqwire_encode_device`: tables and records in HBM, three kernels on torch's current stream, result copied back for inspection."""
+    """`hqwire_encode_device`: tables and records in HBM, three kernels on torch's current stream, result copied back for inspection.  With a `WireTable`
+    for `t` no table is uploaded: the encoder reads the resident one through its view (the table's deltas drain its stream before they return, so the
+    encode is ordered behind them whatever stream it runs on)."""
     import torch
 
     lib, dev = load(), torch.device(device)
-    tt, rt = _upload(torch, dev, t.arrays()), _upload(torch, dev, r.arrays())
+    if isinstance(t, WireTable) and t.host_order is not None:
+        raise ValueError("encode_device takes a WireTable of the device backend")
+    tt, rt = ([] if isinstance(t, WireTable) else _upload(torch, dev, t.arrays())), _upload(torch, dev, r.arrays())
     tc, rc = _structs(t, r, [x.data_ptr() for x in tt], [x.data_ptr() for x in rt])
     return _run_device(lib, torch, dev, tc, rc, r.n_workers + r.n_mn, r.n_records + r.n_mn, capacity, limit)
 
@@ -268,11 +427,11 @@ def encode_from_sink(t: WireTables, sink, n_workers: int, sink_cap_records: int,
     if sink_cap_records and cap != sink_cap_records:
         raise ValueError(f"sink of {sink.numel()} bytes holds {cap} records, caller assumed {sink_cap_records}")
     o_off, o_task, o_var, o_kind, _total = sink_layout(n_workers, cap)
-    tt, st = _upload(torch, dev, t.arrays()), _upload(torch, dev, side.arrays())
+    tt, st = ([] if isinstance(t, WireTable) else _upload(torch, dev, t.arrays())), _upload(torch, dev, side.arrays())
     base = sink.data_ptr()
     ptrs_r = [st[0].data_ptr(), base + o_off, base + o_task, base + o_var, base + o_kind, st[5].data_ptr(), st[6].data_ptr(), st[7].data_ptr(),
               st[8].data_ptr(), st[9].data_ptr()]
-    tc = TablesC(t.n_tasks, *[x.data_ptr() for x in tt[:8]], t.n_configs, *[x.data_ptr() for x in tt[8:]])
+    tc = t.view() if isinstance(t, WireTable) else TablesC(t.n_tasks, *[x.data_ptr() for x in tt[:8]], t.n_configs, *[x.data_ptr() for x in tt[8:]])
     rc = RecordsC(n_workers, n_records, *ptrs_r[:7], side.n_mn, *ptrs_r[7:])
     return _run_device(lib, torch, dev, tc, rc, n_workers + side.n_mn, n_records + side.n_mn, capacity)
 

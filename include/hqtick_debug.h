@@ -152,6 +152,12 @@ int hqwire_debug_encode_host(const struct hqwire_tables *tables, const struct hq
 /* As above with the emulated threads of every phase run in another sequence (0 ascending, 1 descending, 2 a fixed permutation): the bytes
  * must not depend on it -- a phase that did would be a data race on the GPU. */
 int hqwire_debug_encode_host_order(const struct hqwire_tables *tables, const struct hqwire_records *records, const struct hqwire_output *out, int order);
+/* The resident attribute table of include/hqwire.h (hqwire_table_*) on HOST memory: the same class on a backend whose buffers are heap blocks and whose
+ * launches run the kernels' phase functions (csrc/wire_table_core.h) one emulated thread after the other, in the given order (0, 1 or 2 as above).  Every
+ * other hqwire_table_* call then works on the table; its view holds host pointers that hqwire_debug_encode_host accepts. */
+struct hqwire_table;
+struct hqwire_table_config;
+int hqwire_debug_table_create_host(struct hqwire_table **out, const struct hqwire_table_config *cfg, int order);
 
 /* The guard on the class blocks' answers (csrc/host_model.cpp; hqtick_kernel_stats.n_classes_verified / _mismatch / _rejected) under fault injection: `verify` classes
  * of the launch are re-solved by the host (window starting at tick_seq * verify; UINT32_MAX = all), and the emulated blocks corrupt the answer of launch position

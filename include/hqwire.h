@@ -28,6 +28,23 @@
  *   HQWIRE_SLOT_TOO_MANY  more than HQWIRE_MAX_RECORDS records for one worker in one tick (device-side dedup table)
  *   HQWIRE_SLOT_UNKNOWN   a record names a task id that is not in the attribute table
  * No CPU implementation behind this entry point: without a gfx950 device it returns HQTICK_E_NO_DEVICE.
+ *
+ * The resident attribute table (ABI 3).  hqwire_table is the task-attribute table of `hqwire_tables` owned by the library, kept in HBM and changed by
+ * the reactor events that feed the other resident structures: on_new_tasks -> hqwire_table_add_tasks; a task finished, failed or cancelled ->
+ * hqwire_table_remove_tasks; a lost worker's tasks (what hqtick_cluster_last_requeued reports; increment_instance_id, server/reactor.rs:95,100,119) ->
+ * hqwire_table_set_instance with values == NULL; a client's assignment (server/client.rs:53-60) -> the same call with values.  hqwire_table_view hands
+ * the encoder a plain hqwire_tables; the encoder does not know the difference.
+ *   Dead rows.  A removed row STAYS IN PLACE with its id until the next compaction, so the id column stays ascending and the encoder's row search is
+ *   undisturbed; liveness is a bitmap kept outside the view.  Hence A DEAD ID STAYS FINDABLE BY THE ENCODER UNTIL THE NEXT COMPACTION: a record that names
+ *   a removed task is encoded with the attributes the task had, not reported HQWIRE_SLOT_UNKNOWN.  A tick never names a finished task, which is what makes
+ *   this lazy drop sound.  For records that name live tasks an encode on the view gives the bytes of an encode on a table built from the live tasks alone;
+ *   after hqwire_table_compact every array of the view is byte for byte that table.
+ *   Compaction runs by itself at the end of a remove that leaves more dead rows than live rows or more dead blob bytes than live blob bytes, and inside
+ *   every add that has to merge (below).
+ *   Ordering.  Every operation of a table is enqueued on the stream given at hqwire_table_create, and every mutating call returns after that stream has
+ *   drained.  An encode enqueued on the table's stream is ordered behind the deltas by the stream itself.  An encode on ANOTHER stream is the caller's to
+ *   order: it must have finished before the next mutating call on the table, which may move the arrays of the view and release the old ones.
+ *   Calls on one table are not thread safe.  Errors are the negative HQTICK_E_* codes (include/hqtick.h); hqwire_table_last_error has the text.
  */
 #ifndef HQWIRE_H
 #define HQWIRE_H
@@ -42,7 +59,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HQWIRE_ABI_VERSION 2u
+#define HQWIRE_ABI_VERSION 3u
 #define HQWIRE_MAX_RECORDS 2048u                 /* records per worker message handled on the device */
 #define HQWIRE_MAX_TASK_MSG_SIZE (32u << 20)     /* MAX_FRAME_SIZE / 4 (crates/tako/src/lib.rs:31, server/task.rs:315) */
 #define HQWIRE_MAX_FRAGMENTS 16u                 /* ComputeTasks messages one slot may be cut into on the device */
@@ -108,6 +125,76 @@ uint64_t hqwire_scratch_bytes(uint64_t n_records_incl_mn, uint64_t n_slots);
  * valid once the stream has drained.  On HQWIRE_CAPACITY nothing is written to `bytes` (header[2..3] still hold the size needed).
  * Returns 0, HQTICK_E_INVALID (-1), HQTICK_E_NO_DEVICE (-2) or HQTICK_E_DEVICE (-3) (include/hqtick.h). */
 int hqwire_encode_device(const hqwire_tables *tables, const hqwire_records *records, const hqwire_output *out, void *hip_stream);
+
+/* ---- the resident attribute table (ABI 3) ------------------------------------------------------------------------------------------------ */
+#define HQWIRE_TABLE_TILE 256u  /* rows per compaction tile (one workgroup) */
+
+typedef struct hqwire_table hqwire_table;
+
+/* Initial allocations, 0 = the default (65536 rows, 1 MiB of entries, 64 configurations, 64 KiB of bodies).  Buffers double when a call needs more;
+ * tests use tiny values to reach the growth paths. */
+typedef struct hqwire_table_config {
+    uint64_t initial_rows;
+    uint64_t initial_blob_bytes;
+    uint64_t initial_configs;
+    uint64_t initial_body_bytes;
+} hqwire_table_config;
+
+typedef struct hqwire_table_stats {
+    uint64_t live_rows;        /* tasks in the table                                                                  */
+    uint64_t physical_rows;    /* rows of the view = live + dead                                                      */
+    uint64_t blob_bytes;       /* entry bytes of the view = entry_off[physical_rows]                                  */
+    uint64_t dead_blob_bytes;  /* of which belong to dead rows                                                        */
+    uint64_t n_configs;
+    uint64_t body_bytes;
+    uint64_t appends;          /* add_tasks calls that took the append path                                           */
+    uint64_t merges;           /* ... the merge path                                                                  */
+    uint64_t compactions;      /* forced, automatic and those inside a merge, each counted when it dropped dead rows  */
+    uint64_t growths;          /* calls that had to enlarge the row / entry / configuration buffers                   */
+    uint64_t hbm_bytes;        /* device memory held now                                                              */
+    double last_kernel_us;     /* event time of the last mutating call's device work (0 on the host debug backend)    */
+} hqwire_table_stats;
+
+/* cfg may be NULL.  hip_stream: a hipStream_t, NULL = the null stream.  HQTICK_E_NO_DEVICE without a gfx950 device: no CPU path in the product. */
+int hqwire_table_create(hqwire_table **out, const hqwire_table_config *cfg, void *hip_stream);
+void hqwire_table_destroy(hqwire_table *t);
+
+/* Appends n interned TaskConfigurations (append-only) and returns the index of the first one, or a negative error.  body_off has n + 1 entries into
+ * body_blob (any base); time_secs / time_nanos are read where time_some is set. */
+int64_t hqwire_table_add_configs(hqwire_table *t, uint32_t n, const uint8_t *time_some, const uint64_t *time_secs, const uint32_t *time_nanos,
+                                 const uint64_t *body_off, const uint8_t *body_blob);
+
+/* on_new_tasks.  task_id ascends strictly inside the batch; task_instance == NULL: zeros; entry_some == NULL: every entry is None (entry_off / entry_blob may
+ * then be NULL too); entry_off has n + 1 entries into entry_blob (any base).  Returns n.  The batch is refused as a whole (HQTICK_E_INVALID, table unchanged) when
+ * the ids do not ascend, an id equals a live row's id, a configuration index is >= the number of configurations, entry_off is not monotone, a row has
+ * entry_some == 0 and a non-zero length, an id is reserved (>= 0xFFFFFFFFFFFFFFFE) or the physical row count would reach 0xFFFFFFFF.
+ * A batch whose first id lies above every resident id (dead rows included) is appended behind the columns; any other batch is merged: dead rows are dropped
+ * first, then the two sorted tables are merged into the second set of buffers.  A merged id whose row is dead is accepted: the new attributes stand. */
+int64_t hqwire_table_add_tasks(hqwire_table *t, uint64_t n, const uint64_t *task_id, const uint32_t *task_rq, const uint32_t *task_instance,
+                               const uint64_t *task_priority, const uint32_t *task_config, const uint8_t *entry_some, const uint64_t *entry_off,
+                               const uint8_t *entry_blob);
+
+/* Finished, failed and cancelled tasks.  Returns the number of live rows removed; ids that are unknown, already removed or repeated inside the batch
+ * change nothing and are counted in hqwire_table_last_unknown. */
+int64_t hqwire_table_remove_tasks(hqwire_table *t, uint64_t n, const uint64_t *task_id);
+
+/* values == NULL: instance id + 1 for every listed id, an id listed twice rising by two.  With values: task_instance = values[i]; an id listed twice
+ * with different values keeps either.  Returns the number of live rows found; unknown and dead ids are counted in hqwire_table_last_unknown. */
+int64_t hqwire_table_set_instance(hqwire_table *t, uint64_t n, const uint64_t *task_id, const uint32_t *values);
+
+/* Drops the dead rows now (nothing happens without any). */
+int hqwire_table_compact(hqwire_table *t);
+
+/* DEVICE pointers and counts to hand to hqwire_encode_device; valid until the next mutating call on the table.  Launches nothing, waits for nothing. */
+int hqwire_table_view(const hqwire_table *t, hqwire_tables *out);
+
+/* The arrays of the view copied to HOST buffers the caller sized from hqwire_table_get_stats (physical_rows rows, physical_rows + 1 offsets, blob_bytes,
+ * n_configs, n_configs + 1 offsets, body_bytes); n_tasks and n_configs are filled in.  NULL pointers are skipped.  Tests, journalling, restore. */
+int hqwire_table_copy_out(const hqwire_table *t, hqwire_tables *host);
+
+int hqwire_table_get_stats(const hqwire_table *t, hqwire_table_stats *out);
+uint64_t hqwire_table_last_unknown(const hqwire_table *t);
+const char *hqwire_table_last_error(const hqwire_table *t);
 
 uint32_t hqwire_abi_version(void);
 
