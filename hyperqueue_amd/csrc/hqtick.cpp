@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "block_solve.h"
+#include "cluster.h"
 #include "price_dev.h"
 #ifdef HQTICK_TEST_HOOKS
 #include "price_emul.h"
@@ -43,6 +44,7 @@
 
 using hqbuf::DevBuf;
 using hqbuf::PinBuf;
+using hqcluster::UpView;
 
 namespace {
 
@@ -107,22 +109,8 @@ struct hqtick_ctx {
     uint32_t block_budget = 4096, block_min_classes = 12;  // k_block_solve: search steps per class before the host solver takes it; classes below which the host solves alone
     // workers / requests
     DevBuf d_up, d_vflags, d_vtmc, d_blk;
-    // cluster tables resident in HBM (hqtick_cluster_*): worker rows + request tables in the layout of upload_tables; the host sends rows that changed
-    DevBuf d_cluster; PinBuf h_cl, h_cld; bool cluster_valid = false, cluster_check = false, cl_pending = false; uint32_t cl_W = 0, cl_R = 0;
-    std::vector<unsigned char> cl_rt;  // host copy of the request-table part as uploaded (compared per tick: a few hundred bytes)
-    hipEvent_t cl_ev = nullptr;
-    // host mirror of the resident worker set (ABI 7): what a snapshot with worker_id == NULL is completed from, kept current by the hqtick_cluster_* deltas
-    struct ClusterMirror {
-        bool valid = false; uint32_t n_groups = 1;
-        std::vector<uint32_t> id, group; std::vector<uint64_t> total, free_; std::vector<int64_t> rem; std::vector<float> min_util; std::vector<uint8_t> flags;
-        std::map<uint32_t, std::vector<std::pair<uint32_t, uint8_t>>> blocked;   // worker id -> (rq, variant)
-        std::vector<uint32_t> blk_worker, blk_rq; std::vector<uint8_t> blk_variant; bool blk_dirty = true;  // the same as (worker index, rq, variant) triples
-    } mirror;
-    DevBuf d_cluster2;  // the re-packed tables of a membership change (swapped with d_cluster)
-    // resident table of Retracting tasks (ABI 7): task -> (worker id it is retracting from, still in its queue?, redirect target id / variant)
-    struct RetrEntry { uint32_t old_id; bool in_queue; bool has_redirect; uint32_t target_id; uint8_t variant; };
-    std::map<uint64_t, RetrEntry> retr;
-    std::vector<uint64_t> retr_task, resp_task; std::vector<uint32_t> retr_worker, retr_red_worker, resp_worker; std::vector<uint8_t> retr_red_variant, resp_variant;
+    hqcluster::WorkerSet ws;      // hqtick_cluster_* (ABI 5 and 7; cluster.h): the worker / request tables resident in HBM and their host mirror
+    hqcluster::Retracting retr;   // hqtick_retracting_* (ABI 7): the table of Retracting tasks
     bool sweep_inflight = false;  // an early K5a launch not yet covered by a stream synchronisation
     bool wait_on_kernel = true;   // HQ_HIP_LAST; HQTICK_WAIT_ON_KERNEL=0: hipStreamSynchronize at every wait (A/B)
     // selection + mapping
@@ -244,86 +232,22 @@ int validate(hqtick_ctx *ctx, const hqtick_snapshot *s, bool need_tasks) {
 
 struct WorkerEval { const uint8_t *flags = nullptr; const uint32_t *tmc = nullptr; };
 
-// Packs worker tables + request tables into ONE pinned, device-mapped staging buffer that K2 reads in place (every byte
+// Packs worker tables + request tables (cluster.h: TabLayout) into ONE pinned, device-mapped staging buffer that K2 reads in place (every byte
 // crosses PCIe once per workgroup; no H2D copy command).
-struct UpView { const uint64_t *total, *free_; const int64_t *rem; hqk::RequestTable rt; uint32_t n_entries; };
-struct TabLayout { size_t o_tot, o_free, o_rem, o_amt, o_time, o_off, o_res, o_kind, bytes; uint32_t nv, ne; };
-TabLayout table_layout(const hqtick_snapshot *s, uint32_t W) {
-    TabLayout L{};
-    const uint32_t R = s->n_resources;
-    L.nv = s->n_requests ? s->rq_variant_off[s->n_requests] : 0;
-    L.ne = L.nv ? s->variant_entry_off[L.nv] : 0;
-    L.o_tot = 0; L.o_free = L.o_tot + (size_t)W * R * 8; L.o_rem = L.o_free + (size_t)W * R * 8; L.o_amt = L.o_rem + (size_t)W * 8; L.o_time = L.o_amt + (size_t)L.ne * 8;
-    L.o_off = L.o_time + (size_t)L.nv * 8; L.o_res = L.o_off + (size_t)(L.nv + 1) * 4; L.o_kind = L.o_res + (size_t)L.ne * 4; L.bytes = L.o_kind + L.ne + 64;
-    return L;
-}
-void pack_worker_rows(unsigned char *h, const TabLayout &L, uint32_t W, uint32_t R, const uint64_t *total, const uint64_t *free_, const int64_t *rem) {
-    if (W && R) { memcpy(h + L.o_tot, total, (size_t)W * R * 8); memcpy(h + L.o_free, free_, (size_t)W * R * 8); }
-    int64_t *hr = reinterpret_cast<int64_t *>(h + L.o_rem);
-    if (rem) memcpy(hr, rem, (size_t)W * 8); else for (uint32_t w = 0; w < W; w++) hr[w] = HQ_NO_TIME_LIMIT;
-}
-void pack_request_tables(unsigned char *h, const TabLayout &L, const hqtick_snapshot *s) {
-    if (!L.nv) return;
-    memcpy(h + L.o_amt, s->entry_amount, (size_t)L.ne * 8);
-    if (s->variant_min_time_ns) memcpy(h + L.o_time, s->variant_min_time_ns, (size_t)L.nv * 8); else memset(h + L.o_time, 0, (size_t)L.nv * 8);
-    memcpy(h + L.o_off, s->variant_entry_off, (size_t)(L.nv + 1) * 4);
-    memcpy(h + L.o_res, s->entry_resource, (size_t)L.ne * 4);
-    memcpy(h + L.o_kind, s->entry_kind, L.ne);
-}
-void view_tables(unsigned char *d, const TabLayout &L, UpView *uv) {
-    uv->total = (const uint64_t *)(d + L.o_tot); uv->free_ = (const uint64_t *)(d + L.o_free); uv->rem = (const int64_t *)(d + L.o_rem);
-    uv->rt.entry_amount = (const uint64_t *)(d + L.o_amt); uv->rt.variant_min_time_ns = (const uint64_t *)(d + L.o_time);
-    uv->rt.variant_entry_off = (const uint32_t *)(d + L.o_off); uv->rt.entry_resource = (const uint32_t *)(d + L.o_res);
-    uv->rt.entry_kind = (const uint8_t *)(d + L.o_kind); uv->rt.n_variants = L.nv; uv->n_entries = L.ne;
-}
 int upload_tables(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const uint64_t *total, const uint64_t *free_, const int64_t *rem, PinBuf &buf, UpView *uv) {
     const uint32_t R = s->n_resources;
-    const TabLayout L = table_layout(s, W);
+    const hqcluster::TabLayout L = hqcluster::table_layout(s, W);
     if (hqk::worker_eval_lds(R, L.nv, L.ne) > 150 * 1024) return fail(ctx, HQTICK_E_CAPACITY, "request table + 32 worker rows exceed the 150 KiB the worker-evaluation kernel stages in LDS");
     if (!buf.ensure(L.bytes)) return fail(ctx, HQTICK_E_DEVICE, "allocating upload staging");
     unsigned char *h = buf.as<unsigned char>();
-    pack_worker_rows(h, L, W, R, total, free_, rem);
-    pack_request_tables(h, L, s);
-    view_tables(buf.dev<unsigned char>(), L, uv);
+    hqcluster::pack_worker_rows(h, L, W, R, total, free_, rem);
+    hqcluster::pack_request_tables(h, L, s);
+    hqcluster::view_tables(buf.dev<unsigned char>(), L, uv);
     return 0;
 }
 
-// The same tables from HBM (hqtick_cluster_upload): worker rows are the caller's responsibility (hqtick_cluster_update_workers), the request tables are
-// compared with what was uploaded and re-sent when the snapshot brings new request classes.
-int resident_tables(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, UpView *uv) {
-    const uint32_t R = s->n_resources;
-    if (W != ctx->cl_W || R != ctx->cl_R) return fail(ctx, HQTICK_E_INVALID, "cluster tables in HBM were uploaded for another worker set (hqtick_cluster_upload after workers join or leave)");
-    const TabLayout L = table_layout(s, W);
-    if (hqk::worker_eval_lds(R, L.nv, L.ne) > 150 * 1024) return fail(ctx, HQTICK_E_CAPACITY, "request table + 32 worker rows exceed the 150 KiB the worker-evaluation kernel stages in LDS");
-    const size_t rt_bytes = L.bytes - L.o_amt;
-    if (ctx->cl_pending) { HQ_HIP(hipEventSynchronize(ctx->cl_ev)); ctx->cl_pending = false; }  // h_cl is the staging of the previous request-table upload
-    if (L.bytes > ctx->d_cluster.cap) {  // the request tables outgrew the allocation: move the worker rows over
-        DevBuf nb;
-        if (!nb.ensure(L.bytes * 2)) return fail(ctx, HQTICK_E_DEVICE, "allocating cluster tables");
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        HQ_HIP(hipMemcpy(nb.p, ctx->d_cluster.p, L.o_amt, hipMemcpyDeviceToDevice));
-        ctx->d_cluster.release(); ctx->d_cluster = nb;
-    }
-    if (!ctx->h_cl.ensure(L.bytes)) return fail(ctx, HQTICK_E_DEVICE, "allocating cluster tables");
-    unsigned char *h = ctx->h_cl.as<unsigned char>();
-    memset(h + L.o_amt, 0, rt_bytes);
-    pack_request_tables(h, L, s);
-    if (ctx->cl_rt.size() != rt_bytes || memcmp(ctx->cl_rt.data(), h + L.o_amt, rt_bytes) != 0) {  // new request classes: a few hundred bytes, stream-ordered before K2
-        HQ_HIP(hipMemcpyAsync(ctx->d_cluster.as<unsigned char>() + L.o_amt, h + L.o_amt, rt_bytes, hipMemcpyHostToDevice, ctx->stream));
-        HQ_HIP(hipEventRecord(ctx->cl_ev, ctx->stream)); ctx->cl_pending = true;
-        ctx->cl_rt.assign(h + L.o_amt, h + L.o_amt + rt_bytes);
-    }
-    if (ctx->cluster_check) {  // HQTICK_CHECK_CLUSTER=1 (tests): the rows in HBM must be the rows of the snapshot
-        std::vector<unsigned char> dev(L.o_amt);
-        HQ_HIP(hipMemcpyAsync(dev.data(), ctx->d_cluster.p, L.o_amt, hipMemcpyDeviceToHost, ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        std::vector<unsigned char> want(L.o_amt);
-        pack_worker_rows(want.data(), L, W, R, s->worker_total, s->worker_free, s->worker_remaining_ns);
-        if (memcmp(dev.data(), want.data(), L.o_amt) != 0) return fail(ctx, HQTICK_E_INVALID, "cluster tables in HBM differ from the snapshot's worker rows (a missed hqtick_cluster_update_workers)");
-    }
-    view_tables(ctx->d_cluster.as<unsigned char>(), L, uv);
-    return 0;
-}
+// ... or from HBM, where a worker set is resident (hqcluster::WorkerSet::tables)
+int cluster_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->ws.err; return rc; }
 
 // K2 on a worker set, synchronous (used for the fake workers of hqtick_query); results land in pinned memory
 int eval_workers_sync(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const uint64_t *total, const uint64_t *free_, const int64_t *rem, WorkerEval *out) {
@@ -486,7 +410,7 @@ int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, S
     unsigned char *h = ctx->h_a.as<unsigned char>(), *hd = ctx->h_a.dev<unsigned char>();
     memset(h, 0, 16);
     UpView uv; int rc;
-    if (ctx->cluster_valid) { if ((rc = resident_tables(ctx, s, W, &uv))) return rc; }
+    if (ctx->ws.valid()) { if ((rc = cluster_fail(ctx, ctx->ws.tables(ctx->stream, s, W, &uv)))) return rc; }
     else if ((rc = upload_tables(ctx, s, W, s->worker_total, s->worker_free, s->worker_remaining_ns, ctx->h_up, &uv))) return rc;
     HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream));
     ev->flags = h + o_fl; ev->tmc = reinterpret_cast<const uint32_t *>(h + o_tmc);
@@ -589,7 +513,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
         // K2 reads the packed tables from pinned memory; with a ready set to scan it rides along the K1 launch
         bool scan_is_last = false;  // K1b was launched and nothing follows it on the stream
         UpView uv; int rc;
-        if (ctx->cluster_valid) { if ((rc = resident_tables(ctx, s, W, &uv))) return rc; }
+        if (ctx->ws.valid()) { if ((rc = cluster_fail(ctx, ctx->ws.tables(ctx->stream, s, W, &uv)))) return rc; }
         else if ((rc = upload_tables(ctx, s, W, s->worker_total, s->worker_free, s->worker_remaining_ns, ctx->h_up, &uv))) return rc;
         hqk::WorkerEvalArgs wea{uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc)};
         if (scan) {
@@ -1474,8 +1398,8 @@ struct TickRun {
 // ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12): what hqasg::Ledger (ledger.h) is given of the context
 bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm; }  // (a record sink alone is one scheduler's output path, not a replica)
 hqasg::Env ledger_env(hqtick_ctx *ctx) {
-    return hqasg::Env{ctx->device, ctx->stream, ctx->d_cluster.as<unsigned char>(), ctx->cl_W, ctx->cl_R, ctx->d_tid.as<uint64_t>(), ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready,
-                      ctx->d_levels.as<uint64_t>(), &ctx->mirror.id, &ctx->mirror.flags, &ctx->mirror.free_};
+    return hqasg::Env{ctx->device, ctx->stream, ctx->ws.rows(), ctx->ws.W(), ctx->ws.R(), ctx->d_tid.as<uint64_t>(), ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready,
+                      ctx->d_levels.as<uint64_t>(), &ctx->ws.ids(), ctx->ws.flags(), ctx->ws.free_rows()};
 }
 int ledger_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->asg.err; return rc; }
 // a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
@@ -1488,10 +1412,9 @@ int ledger_guard(hqtick_ctx *ctx) {
 
 int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool use_resident) {
     hqtick_snapshot full;
-    bool copied = false;
     if (ctx->asg.on && s) {  // the assignment ledger (ABI 12) is the tick's only source of the running tasks
         if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "assignment ledger on a sharded or replica context");
-        if (s->worker_id || !(ctx->cluster_valid && ctx->mirror.valid)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
+        if (s->worker_id || !ctx->ws.valid()) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
         if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
         if (ctx->asg.tracking() && s->prefilled_off) return fail(ctx, HQTICK_E_INVALID, "prefilled tracking on: the snapshot must not carry a prefilled CSR as well");
         HQ_HIP(hipSetDevice(ctx->device));
@@ -1500,43 +1423,12 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         if (ctx->asg.tracking() && ctx->asg.max_variants() >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "prefilled tracking: a request has 254 or more variants");
         if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     }
-    if (s && s->n_workers == HQ_WORKERS_RESIDENT && !(s->worker_id == nullptr && ctx->cluster_valid && ctx->mirror.valid))
-        return fail(ctx, HQTICK_E_INVALID, s->worker_id ? "n_workers == HQ_WORKERS_RESIDENT with worker arrays in the snapshot"
-                                                         : "n_workers == HQ_WORKERS_RESIDENT without a resident worker set (hqtick_cluster_upload; dropped by hqtick_cluster_drop)");
-    if (s && s->worker_id == nullptr && ctx->cluster_valid && ctx->mirror.valid) {  // the worker side lives in the library (hqtick_cluster_*, ABI 7)
-        hqtick_ctx::ClusterMirror &m = ctx->mirror;
-        const uint32_t W = (uint32_t)m.id.size();
-        if (s->n_workers != 0 && s->n_workers != HQ_WORKERS_RESIDENT && s->n_workers != W) return fail(ctx, HQTICK_E_INVALID, "snapshot without worker arrays: n_workers must be HQ_WORKERS_RESIDENT, 0 or the resident worker count");
-        if (s->n_resources != ctx->cl_R) return fail(ctx, HQTICK_E_INVALID, "snapshot without worker arrays: n_resources differs from the resident tables");
-        if (m.blk_dirty) {
-            m.blk_worker.clear(); m.blk_rq.clear(); m.blk_variant.clear();
-            for (uint32_t w = 0; w < W; w++) { auto it = m.blocked.find(m.id[w]); if (it == m.blocked.end()) continue; for (auto &p : it->second) { m.blk_worker.push_back(w); m.blk_rq.push_back(p.first); m.blk_variant.push_back(p.second); } }
-            m.blk_dirty = false;
-        }
-        full = *s; copied = true;
-        full.n_workers = W; full.worker_id = m.id.data(); full.worker_total = m.total.data(); full.worker_free = m.free_.data(); full.worker_remaining_ns = m.rem.data();
-        full.worker_min_utilization = m.min_util.data(); full.worker_flags = m.flags.data(); full.worker_group = m.group.data(); full.n_groups = m.n_groups; full.worker_map_rank = nullptr;
-        full.n_blocked = (uint32_t)m.blk_worker.size(); full.blocked_worker = m.blk_worker.data(); full.blocked_rq = m.blk_rq.data(); full.blocked_variant = m.blk_variant.data();
+    if (s) {  // the worker side may live in the library (hqtick_cluster_*, ABI 7), and so may the Retracting tasks of the queues (hqtick_retracting_*)
+        if (int rc = cluster_fail(ctx, ctx->ws.complete(s, &full))) return rc;
         s = &full;
     }
     const bool retr_resident = s && s->n_retracting == HQ_RETRACTING_RESIDENT;
-    if (retr_resident) {  // the Retracting tasks of the queues come from the library's table (hqtick_retracting_*, ABI 7)
-        if (!s->worker_id) return fail(ctx, HQTICK_E_INVALID, "resident retracting table without worker ids (hqtick_cluster_upload, or worker arrays in the snapshot)");
-        const uint32_t W = s->n_workers;
-        auto index_of = [&](uint32_t id) -> uint32_t { const uint32_t *b = s->worker_id, *e = b + W, *it = std::lower_bound(b, e, id); return (it != e && *it == id) ? (uint32_t)(it - b) : HQ_NO_WORKER; };
-        ctx->retr_task.clear(); ctx->retr_worker.clear(); ctx->retr_red_worker.clear(); ctx->retr_red_variant.clear();
-        for (auto &kv : ctx->retr) {  // (std::map: ascending task id, as the snapshot wants it)
-            if (!kv.second.in_queue) continue;
-            const uint32_t oi = index_of(kv.second.old_id);
-            if (oi == HQ_NO_WORKER) return fail(ctx, HQTICK_E_INVALID, "a Retracting task's worker is not in the worker set");
-            ctx->retr_task.push_back(kv.first); ctx->retr_worker.push_back(oi);
-            ctx->retr_red_worker.push_back(kv.second.has_redirect ? index_of(kv.second.target_id) : HQ_NO_WORKER); ctx->retr_red_variant.push_back(kv.second.variant);
-        }
-        if (!copied) { full = *s; copied = true; s = &full; }
-        full.n_retracting = (uint32_t)ctx->retr_task.size();
-        full.retracting_task = ctx->retr_task.data(); full.retracting_worker = ctx->retr_worker.data();
-        full.retracting_redirect_worker = ctx->retr_red_worker.data(); full.retracting_redirect_variant = ctx->retr_red_variant.data();
-    }
+    if (retr_resident) { if (int rc = ctx->retr.to_snapshot(s->worker_id, s->n_workers, &full)) return fail(ctx, rc, ctx->retr.err); }
     int rc;
     {
         TickRun run(ctx, s, out, use_resident);
@@ -1570,20 +1462,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             else { ctx->resident = false; ctx->err += " (HQTICK_FLAG_CONSUME_IN_TICK: the tick had already taken its tasks and they could not be put back; the resident ready set is dropped, upload it again)"; }
         }
     }
-    if (rc >= 0 && retr_resident) {  // what create_task_mapping did to task states and redirects (mapping.rs:66-101), applied to the table
-        const uint32_t W = s->n_workers;
-        for (uint32_t w = 0; w < W && w + 1 < ctx->retract_off.size(); w++)   // Prefilled{old} -> Retracting{old}: out of a prefill set, not in a queue
-            for (uint32_t i = ctx->retract_off[w]; i < ctx->retract_off[w + 1]; i++) ctx->retr[ctx->retract_task[i]] = hqtick_ctx::RetrEntry{s->worker_id[w], false, false, 0, 0};
-        for (size_t i = 0; i < ctx->red_task.size(); i++) {
-            auto it = ctx->retr.find(ctx->red_task[i]);
-            if (it == ctx->retr.end()) continue;
-            hqtick_ctx::RetrEntry &e = it->second;
-            const uint8_t kind = i < ctx->red_kind.size() ? ctx->red_kind[i] : (uint8_t)HQ_REDIRECT_FROM_PREFILL;
-            e.in_queue = false;  // take_tasks removed it from its queue (or it came out of a prefill set)
-            if (kind == HQ_REDIRECT_SAME_WORKER) continue;  // back on the worker it is retracting from: insert_sn_task(old) only, the redirect table is untouched (mapping.rs:66-80)
-            if (ctx->red_worker[i] < W) { e.has_redirect = true; e.target_id = s->worker_id[ctx->red_worker[i]]; e.variant = ctx->red_variant[i]; }
-        }
-    }
+    if (rc >= 0 && retr_resident) ctx->retr.apply_tick(s->worker_id, s->n_workers, ctx->retract_off, ctx->retract_task, ctx->red_task, ctx->red_worker, ctx->red_variant, ctx->red_kind);
     if (rc >= 0 && ctx->asg.on) {  // the placement enters the ledger when it becomes state: now, or at hqtick_ready_consume_last in the two-call form
         const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
         ctx->asg.collect_tick(s, out, ctx->new_free, ctx->mn_rq, in_tick && s->n_retracting != 0);  // (the column copy is taken only for the redirects of Retracting tasks)
@@ -1624,7 +1503,6 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
     if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) { hipStreamDestroy(ctx->stream); delete ctx; return HQTICK_E_DEVICE; }
     if (const char *e = getenv("HQTICK_K2_RIDE_ALONG")) { ctx->k2_own_stream = atoi(e) == 0; ctx->k2_on_hist = atoi(e) == 1; }
-    if (const char *e = getenv("HQTICK_CHECK_CLUSTER")) ctx->cluster_check = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_WAIT_ON_KERNEL")) ctx->wait_on_kernel = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_ORDERED_VIEW")) ctx->force_ordered = atoi(e) != 0;  // (tests: every tick on the ordered view)
     {
@@ -1637,7 +1515,7 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     if (const char *e = getenv("HQTICK_SHARD_SOLVE")) ctx->shard_solve = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_SHARD_MIN_BLOCKS")) { long v = atol(e); if (v >= 0) ctx->shard_min_blocks = (uint32_t)v; }
     if (const char *e = getenv("HQTICK_SHARD_MIN_CLASSES")) { long v = atol(e); if (v >= 0) ctx->shard_min_classes = (uint32_t)v; }
-    if (hipEventCreate(&ctx->cl_ev) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
+    if (ctx->ws.init()) { delete ctx; return HQTICK_E_DEVICE; }
     for (auto &e : ctx->ev) if (hipEventCreate(&e) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
     if (!ctx->d_flags.ensure(64) || hipMemset(ctx->d_flags.p, 0, 64) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
     *out_ctx = ctx;
@@ -1653,11 +1531,10 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     delete ctx->pricer; ctx->pricer = nullptr;
     DevBuf *bufs[] = {&ctx->d_tid, &ctx->d_tprio, &ctx->d_trq, &ctx->d_set, &ctx->d_flags, &ctx->d_levels, &ctx->d_nlevels, &ctx->d_wave_tab, &ctx->d_hist,
                       &ctx->d_up, &ctx->d_vflags, &ctx->d_vtmc, &ctx->d_sel_task, &ctx->d_gkey,
-                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_tid2, &ctx->d_tprio2, &ctx->d_trq2, &ctx->d_slice, &ctx->d_add, &ctx->d_pre8, &ctx->d_blk, &ctx->d_cluster,
+                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_tid2, &ctx->d_tprio2, &ctx->d_trq2, &ctx->d_slice, &ctx->d_add, &ctx->d_pre8, &ctx->d_blk,
                       &ctx->d_ord_hist, &ctx->d_ord_tab, &ctx->d_perm, &ctx->d_perm2, &ctx->d_ord_tiles, &ctx->d_inv};
     for (DevBuf *b : bufs) b->release();
-    ctx->h_cl.release(); ctx->h_cld.release(); ctx->d_cluster2.release();
-    if (ctx->cl_ev) hipEventDestroy(ctx->cl_ev);
+    ctx->ws.release();
     if (ctx->qctx) { hqtick_destroy(ctx->qctx); ctx->qctx = nullptr; }
     hipSetDevice(ctx->device);
     if (ctx->comm) { rccl_destroy_comm(ctx); }
@@ -2040,187 +1917,73 @@ int hqtick_graph_get_stats(const hqtick_ctx *ctx, hqtick_graph_stats *out) {
     return 0;
 }
 
-// ---- cluster tables resident in HBM (row f1: the reactor's worker bookkeeping as deltas) ----
+// ---- the resident worker set (row f1: the reactor's worker bookkeeping as deltas): arguments validated here, the operations are hqcluster::WorkerSet's
+// and hqcluster::Retracting's (cluster.h), the ledger's steps (ledger.h) interleaved ----
 int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) {
     if (!ctx || !s) return HQTICK_E_INVALID;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
-    int rc = validate(ctx, s, false);
-    if (rc) return rc;
-    const uint32_t W = s->n_workers, R = s->n_resources;
-    const TabLayout L = table_layout(s, W);
-    if (ctx->cl_pending) { HQ_HIP(hipEventSynchronize(ctx->cl_ev)); ctx->cl_pending = false; }
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    if (!ctx->h_cl.ensure(L.bytes) || !ctx->d_cluster.ensure(L.bytes + 65536)) return fail(ctx, HQTICK_E_DEVICE, "allocating cluster tables");
-    unsigned char *h = ctx->h_cl.as<unsigned char>();
-    memset(h, 0, L.bytes);
-    pack_worker_rows(h, L, W, R, s->worker_total, s->worker_free, s->worker_remaining_ns);
-    pack_request_tables(h, L, s);
-    HQ_HIP(hipMemcpyAsync(ctx->d_cluster.p, h, L.bytes, hipMemcpyHostToDevice, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->cl_rt.assign(h + L.o_amt, h + L.bytes);
-    ctx->cl_W = W; ctx->cl_R = R; ctx->cluster_valid = true;
+    if (int rc = validate(ctx, s, false)) return rc;
+    if (int rc = cluster_fail(ctx, ctx->ws.upload(ctx->stream, s))) return rc;
     ctx->asg.on = false; ctx->asg.pending = false;  // a new worker set: the ledger is enabled (seeded) again for it
     ctx->asg.take_requests(s);
-    {   // the host mirror (ABI 7)
-        hqtick_ctx::ClusterMirror &m = ctx->mirror;
-        m.id.assign(s->worker_id, s->worker_id + W);
-        m.total.assign(s->worker_total, s->worker_total + (size_t)W * R); m.free_.assign(s->worker_free, s->worker_free + (size_t)W * R);
-        m.rem.assign(W, HQ_NO_TIME_LIMIT); if (s->worker_remaining_ns) m.rem.assign(s->worker_remaining_ns, s->worker_remaining_ns + W);
-        m.min_util.assign(W, 0.0f); if (s->worker_min_utilization) m.min_util.assign(s->worker_min_utilization, s->worker_min_utilization + W);
-        m.flags.assign(W, HQ_WORKER_SN); if (s->worker_flags) m.flags.assign(s->worker_flags, s->worker_flags + W);
-        m.group.assign(W, 0); if (s->worker_group) m.group.assign(s->worker_group, s->worker_group + W);
-        m.n_groups = s->n_groups ? s->n_groups : 1;
-        m.blocked.clear();
-        for (uint32_t i = 0; i < s->n_blocked; i++) m.blocked[s->worker_id[s->blocked_worker[i]]].push_back({s->blocked_rq[i], s->blocked_variant[i]});
-        m.blk_dirty = true; m.valid = true;
-    }
+    return 0;
+}
+
+// what opens every delta of the worker set: there is one
+static int cluster_open(hqtick_ctx *ctx, const char *fn) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ws.valid()) return fail(ctx, HQTICK_E_INVALID, std::string(fn) + " without hqtick_cluster_upload");
     return 0;
 }
 
 int hqtick_cluster_update_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_index, const uint64_t *free_rows, const int64_t *remaining_ns) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->cluster_valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_update_workers without hqtick_cluster_upload");
+    if (int rc = cluster_open(ctx, "hqtick_cluster_update_workers")) return rc;
     if (int rc = ledger_guard(ctx)) return rc;
     if (n == 0) return 0;
     if (!worker_index || !free_rows) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_update_workers: null array");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
-    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
-    for (uint32_t i = 0; i < n; i++) if (worker_index[i] >= W) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_update_workers: worker index out of range");
-    // staging: [free n*R u64][rem n i64][index n u32]; the scatter kernel reads it in place (pinned, device-mapped) — wait for the previous one first
-    if (ctx->cl_pending) { HQ_HIP(hipEventSynchronize(ctx->cl_ev)); ctx->cl_pending = false; }
-    const size_t o_rem = (size_t)n * R * 8, o_idx = o_rem + (size_t)n * 8, bytes = o_idx + (size_t)n * 4 + 16;
-    if (!ctx->h_cld.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "allocating delta staging");
-    unsigned char *h = ctx->h_cld.as<unsigned char>(), *d = ctx->h_cld.dev<unsigned char>();
-    memcpy(h, free_rows, o_rem);
-    if (remaining_ns) memcpy(h + o_rem, remaining_ns, (size_t)n * 8);
-    memcpy(h + o_idx, worker_index, (size_t)n * 4);
-    if (ctx->mirror.valid) for (uint32_t i = 0; i < n; i++) {  // the host mirror follows
-        memcpy(ctx->mirror.free_.data() + (size_t)worker_index[i] * R, free_rows + (size_t)i * R, (size_t)R * 8);
-        if (remaining_ns) ctx->mirror.rem[worker_index[i]] = remaining_ns[i];
-    }
-    unsigned char *base = ctx->d_cluster.as<unsigned char>();
-    const size_t WR8 = (size_t)W * R * 8;
-    HQ_HIP(hqk::scatter_worker_rows(reinterpret_cast<uint64_t *>(base + WR8), reinterpret_cast<int64_t *>(base + 2 * WR8), R, n, reinterpret_cast<const uint32_t *>(d + o_idx),
-                                    reinterpret_cast<const uint64_t *>(d), remaining_ns ? reinterpret_cast<const int64_t *>(d + o_rem) : nullptr, ctx->stream));
-    HQ_HIP(hipEventRecord(ctx->cl_ev, ctx->stream)); ctx->cl_pending = true;
-    return 0;
+    return cluster_fail(ctx, ctx->ws.update_rows(ctx->stream, n, worker_index, free_rows, remaining_ns));
 }
 
 int hqtick_cluster_drop(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
-    ctx->cluster_valid = false; ctx->mirror.valid = false; ctx->asg.on = false; ctx->asg.pending = false;
+    ctx->ws.drop(); ctx->asg.on = false; ctx->asg.pending = false;
     return 0;
 }
 
-// Membership change: the rows `src` (old row index, or W_old + k for the k-th staged new worker) become the new table; one re-pack kernel, request tables copied
-// device to device.  The staging of `add_*` rows sits behind the index list in the pinned delta buffer.
-static int cluster_repack(hqtick_ctx *ctx, const std::vector<uint32_t> &src, uint32_t n_add, const uint64_t *add_total, const uint64_t *add_free, const int64_t *add_rem) {
-    const uint32_t W_old = ctx->cl_W, R = ctx->cl_R, W_new = (uint32_t)src.size();
-    HQ_HIP(hipSetDevice(ctx->device));
-    if (ctx->cl_pending) { HQ_HIP(hipEventSynchronize(ctx->cl_ev)); ctx->cl_pending = false; }
-    const size_t rt_bytes = ctx->cl_rt.size();
-    const size_t o_amt_old = ((size_t)2 * W_old * R + W_old) * 8, o_amt_new = ((size_t)2 * W_new * R + W_new) * 8;
-    if (!ctx->d_cluster2.ensure(o_amt_new + rt_bytes + 65536)) return fail(ctx, HQTICK_E_DEVICE, "allocating cluster tables");
-    const size_t o_tot = ((size_t)W_new * 4 + 15) & ~(size_t)15, o_fr = o_tot + (size_t)n_add * R * 8, o_rem = o_fr + (size_t)n_add * R * 8, bytes = o_rem + (size_t)n_add * 8 + 64;
-    if (!ctx->h_cld.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "allocating delta staging");
-    unsigned char *h = ctx->h_cld.as<unsigned char>(), *d = ctx->h_cld.dev<unsigned char>();
-    memcpy(h, src.data(), (size_t)W_new * 4);
-    if (n_add) { memcpy(h + o_tot, add_total, (size_t)n_add * R * 8); memcpy(h + o_fr, add_free, (size_t)n_add * R * 8); memcpy(h + o_rem, add_rem, (size_t)n_add * 8); }
-    unsigned char *ob = ctx->d_cluster.as<unsigned char>(), *nb = ctx->d_cluster2.as<unsigned char>();
-    const size_t WR8o = (size_t)W_old * R * 8, WR8n = (size_t)W_new * R * 8;
-    HQ_HIP(hqk::repack_worker_rows(reinterpret_cast<const uint64_t *>(ob), reinterpret_cast<const uint64_t *>(ob + WR8o), reinterpret_cast<const int64_t *>(ob + 2 * WR8o), W_old, R, W_new,
-                                   reinterpret_cast<const uint32_t *>(d), reinterpret_cast<const uint64_t *>(d + o_tot), reinterpret_cast<const uint64_t *>(d + o_fr), reinterpret_cast<const int64_t *>(d + o_rem),
-                                   reinterpret_cast<uint64_t *>(nb), reinterpret_cast<uint64_t *>(nb + WR8n), reinterpret_cast<int64_t *>(nb + 2 * WR8n), ctx->stream));
-    if (rt_bytes) HQ_HIP(hipMemcpyAsync(nb + o_amt_new, ob + o_amt_old, rt_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    HQ_HIP(hipEventRecord(ctx->cl_ev, ctx->stream)); ctx->cl_pending = true;
-    std::swap(ctx->d_cluster, ctx->d_cluster2);
-    ctx->cl_W = W_new;
-    return 0;
-}
-
+// Membership changes.  The order of the steps is load-bearing: the ledger's re-pack runs on an Env that already has the new worker count and still has the old mirror.
 int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint64_t *total_rows, const uint64_t *free_rows, const int64_t *remaining_ns,
                                const float *min_utilization, const uint8_t *flags, const uint32_t *group) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_add_workers without hqtick_cluster_upload");
+    if (int rc = cluster_open(ctx, "hqtick_cluster_add_workers")) return rc;
     if (n == 0) return 0;
     if (!worker_id || !total_rows || !free_rows) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_add_workers: null array");
-    hqtick_ctx::ClusterMirror &m = ctx->mirror;
-    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t prev = i ? worker_id[i - 1] : (W ? m.id[W - 1] : 0u);
-        if ((i || W) && worker_id[i] <= prev) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_add_workers: ids must ascend above every id present");
-        if (group && group[i] >= 65536) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_add_workers: group index");
-    }
-    std::vector<uint32_t> src(W + n);
-    for (uint32_t i = 0; i < W + n; i++) src[i] = i;
-    std::vector<int64_t> rem(n, HQ_NO_TIME_LIMIT);
-    if (remaining_ns) rem.assign(remaining_ns, remaining_ns + n);
+    const uint32_t W = ctx->ws.W();
+    std::vector<uint32_t> src;
+    if (int rc = cluster_fail(ctx, ctx->ws.plan_add(n, worker_id, group, &src))) return rc;
     if (int rc = ledger_guard(ctx)) return rc;
-    if (int rc = cluster_repack(ctx, src, n, total_rows, free_rows, rem.data())) return rc;
+    HQ_HIP(hipSetDevice(ctx->device));
+    if (int rc = cluster_fail(ctx, ctx->ws.repack(ctx->stream, src, n, total_rows, free_rows, remaining_ns))) return rc;
     if (ctx->asg.on) { if (int rc = ctx->asg.repack(ledger_env(ctx), src, W, flags)) return ledger_fail(ctx, rc); }
-    m.id.insert(m.id.end(), worker_id, worker_id + n);
-    m.total.insert(m.total.end(), total_rows, total_rows + (size_t)n * R); m.free_.insert(m.free_.end(), free_rows, free_rows + (size_t)n * R);
-    m.rem.insert(m.rem.end(), rem.begin(), rem.end());
-    for (uint32_t i = 0; i < n; i++) {
-        m.min_util.push_back(min_utilization ? min_utilization[i] : 0.0f); m.flags.push_back(flags ? flags[i] : (uint8_t)HQ_WORKER_SN);
-        m.group.push_back(group ? group[i] : 0u); if (group && group[i] + 1 > m.n_groups) m.n_groups = group[i] + 1;
-    }
-    m.blk_dirty = true;
+    ctx->ws.add_rows(n, worker_id, total_rows, free_rows, remaining_ns, min_utilization, flags, group);
     if (ctx->asg.on) return ledger_fail(ctx, ctx->asg.upload_wids(ledger_env(ctx)));
     return 0;
 }
 
 int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_remove_workers without hqtick_cluster_upload");
+    if (int rc = cluster_open(ctx, "hqtick_cluster_remove_workers")) return rc;
     if (n == 0) return 0;
     if (!worker_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_remove_workers: null array");
-    hqtick_ctx::ClusterMirror &m = ctx->mirror;
-    const uint32_t W = ctx->cl_W, R = ctx->cl_R;
-    std::vector<uint8_t> gone(W, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        auto it = std::lower_bound(m.id.begin(), m.id.end(), worker_id[i]);
-        if (it == m.id.end() || *it != worker_id[i] || gone[it - m.id.begin()]) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_remove_workers: unknown (or repeated) worker id");
-        gone[it - m.id.begin()] = 1;
-    }
-    std::vector<uint32_t> src; src.reserve(W - n);
-    for (uint32_t w = 0; w < W; w++) if (!gone[w]) src.push_back(w);
+    const uint32_t W = ctx->ws.W();
+    std::vector<uint32_t> src;
+    if (int rc = cluster_fail(ctx, ctx->ws.plan_remove(n, worker_id, &src))) return rc;
     if (int rc = ledger_guard(ctx)) return rc;
     ctx->asg.clear_requeued();
     if (ctx->asg.on) { if (int rc = ctx->asg.evict(ledger_env(ctx), n, worker_id)) return ledger_fail(ctx, rc); }  // on_remove_worker: the lost workers' tasks leave the ledger (reactor.rs:64-147)
-    if (int rc = cluster_repack(ctx, src, 0, nullptr, nullptr, nullptr)) return rc;
+    HQ_HIP(hipSetDevice(ctx->device));
+    if (int rc = cluster_fail(ctx, ctx->ws.repack(ctx->stream, src, 0, nullptr, nullptr, nullptr))) return rc;
     if (ctx->asg.on) { if (int rc = ctx->asg.repack(ledger_env(ctx), src, W, nullptr)) return ledger_fail(ctx, rc); }
-    uint32_t k = 0;
-    for (uint32_t w = 0; w < W; w++) {
-        if (gone[w]) { m.blocked.erase(m.id[w]); continue; }
-        if (k != w) {
-            m.id[k] = m.id[w]; m.rem[k] = m.rem[w]; m.min_util[k] = m.min_util[w]; m.flags[k] = m.flags[w]; m.group[k] = m.group[w];
-            memmove(m.total.data() + (size_t)k * R, m.total.data() + (size_t)w * R, (size_t)R * 8); memmove(m.free_.data() + (size_t)k * R, m.free_.data() + (size_t)w * R, (size_t)R * 8);
-        }
-        k++;
-    }
-    ctx->resp_task.clear(); ctx->resp_worker.clear(); ctx->resp_variant.clear();
-    if (!ctx->retr.empty()) {  // on_remove_worker's two passes over the Retracting tasks (server/reactor.rs:86-147), one pass over the table whatever n is
-        std::vector<uint32_t> lost(worker_id, worker_id + n);
-        std::sort(lost.begin(), lost.end());
-        auto is_lost = [&](uint32_t id) { return std::binary_search(lost.begin(), lost.end(), id); };
-        for (auto it = ctx->retr.begin(); it != ctx->retr.end();) {
-            hqtick_ctx::RetrEntry &e = it->second;
-            if (is_lost(e.old_id)) {
-                // the worker it was retracting from is gone: with a redirect (to a worker that stays) the task is Assigned{target} now and the host sends its
-                // ComputeTasks message (reactor.rs:131-141) — reported through hqtick_cluster_last_reassigned; without one it is a Waiting task of its queue
-                if (e.has_redirect && !is_lost(e.target_id)) { ctx->resp_task.push_back(it->first); ctx->resp_worker.push_back(e.target_id); ctx->resp_variant.push_back(e.variant); }
-                it = ctx->retr.erase(it);
-                continue;
-            }
-            // the redirect TARGET is gone: the redirect is dropped and the task goes back into its queue, still Retracting{old} (reactor.rs:89-94: redirects.remove +
-            // add_ready_task) — the host re-adds it to the resident ready set with the other tasks of the lost worker; the next tick sees it as Retracting again
-            if (e.has_redirect && is_lost(e.target_id)) { e.has_redirect = false; e.in_queue = true; }
-            ++it;
-        }
-    }
-    m.id.resize(k); m.rem.resize(k); m.min_util.resize(k); m.flags.resize(k); m.group.resize(k); m.total.resize((size_t)k * R); m.free_.resize((size_t)k * R);
-    m.blk_dirty = true;
+    ctx->ws.keep_rows(src);
+    ctx->retr.workers_removed(n, worker_id);
     if (ctx->asg.on) {
         if (int rc = ctx->asg.upload_wids(ledger_env(ctx))) return ledger_fail(ctx, rc);
         // ... and go back into the resident ready set with their priority and request (add_ready_task), ids ascending
@@ -2234,75 +1997,52 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
 
 int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (n) *n = (uint32_t)ctx->resp_task.size();
-    if (task_id) *task_id = ctx->resp_task.data();
-    if (worker_id) *worker_id = ctx->resp_worker.data();
-    if (variant) *variant = ctx->resp_variant.data();
+    ctx->retr.last.get(n, task_id, worker_id, variant);
     return 0;
 }
 
 int hqtick_cluster_set_blocked(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, const uint32_t *rq, const uint8_t *variant) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_blocked without hqtick_cluster_upload");
-    hqtick_ctx::ClusterMirror &m = ctx->mirror;
-    if (!std::binary_search(m.id.begin(), m.id.end(), worker_id)) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_blocked: unknown worker id");
-    if (n && (!rq || !variant)) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_blocked: null array");
-    if (n == 0) m.blocked.erase(worker_id);
-    else { auto &v = m.blocked[worker_id]; v.clear(); for (uint32_t i = 0; i < n; i++) v.push_back({rq[i], variant[i]}); }
-    m.blk_dirty = true;
-    return 0;
+    if (int rc = cluster_open(ctx, "hqtick_cluster_set_blocked")) return rc;
+    return cluster_fail(ctx, ctx->ws.set_blocked(worker_id, n, rq, variant));
 }
 
 int hqtick_cluster_workers(const hqtick_ctx *ctx, uint32_t *n_workers, const uint32_t **worker_id) {
-    if (!ctx || !ctx->mirror.valid) return HQTICK_E_INVALID;
-    if (n_workers) *n_workers = (uint32_t)ctx->mirror.id.size();
-    if (worker_id) *worker_id = ctx->mirror.id.data();
+    if (!ctx || !ctx->ws.valid()) return HQTICK_E_INVALID;
+    if (n_workers) *n_workers = ctx->ws.W();
+    if (worker_id) *worker_id = ctx->ws.ids().data();
     return 0;
 }
 
 int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint8_t *flags) {
-    if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags without hqtick_cluster_upload");
+    if (int rc = cluster_open(ctx, "hqtick_cluster_set_flags")) return rc;
     if (int rc = ledger_guard(ctx)) return rc;
     if (n == 0) return 0;
     if (!worker_id || !flags) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: null array");
-    hqtick_ctx::ClusterMirror &m = ctx->mirror;
     if (ctx->asg.on) {  // the ledger may have moved SN bits since the mirror was read
         if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
         if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     }
-    const uint32_t W = (uint32_t)m.id.size();
-    std::vector<uint32_t> row(n);
-    std::vector<uint8_t> seen(W, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        auto it = std::lower_bound(m.id.begin(), m.id.end(), worker_id[i]);
-        if (it == m.id.end() || *it != worker_id[i] || seen[it - m.id.begin()]) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: unknown (or repeated) worker id");
-        row[i] = (uint32_t)(it - m.id.begin()); seen[row[i]] = 1;
-        if (flags[i] & ~(uint8_t)(HQ_WORKER_SN | HQ_WORKER_STOPPING)) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: undefined flag bits");
-        if (ctx->asg.on && ((flags[i] ^ m.flags[row[i]]) & HQ_WORKER_SN))
-            return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_set_flags: with the assignment ledger on, HQ_WORKER_SN follows the ledger's multi-node tasks");
-    }
-    for (uint32_t i = 0; i < n; i++) m.flags[row[i]] = flags[i];
+    if (int rc = cluster_fail(ctx, ctx->ws.set_flags(n, worker_id, flags, ctx->asg.on))) return rc;
     if (ctx->asg.on) return ledger_fail(ctx, ctx->asg.upload_flags(ledger_env(ctx)));
     return 0;
 }
 
 int hqtick_cluster_worker_flags(const hqtick_ctx *cctx, uint32_t *n_workers, const uint8_t **flags) {
-    if (!cctx || !cctx->mirror.valid) return HQTICK_E_INVALID;
+    if (!cctx || !cctx->ws.valid()) return HQTICK_E_INVALID;
     hqtick_ctx *ctx = const_cast<hqtick_ctx *>(cctx);  // (the mirror is a cache of the ledger's column: reading it may refresh it)
     if (ctx->asg.on && ctx->asg.dirty()) {
         if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
         if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
     }
-    if (n_workers) *n_workers = (uint32_t)ctx->mirror.flags.size();
-    if (flags) *flags = ctx->mirror.flags.data();
+    if (n_workers) *n_workers = ctx->ws.W();
+    if (flags) *flags = ctx->ws.flags()->data();
     return 0;
 }
 
 int hqtick_retracting_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id) {
     if (!ctx) return HQTICK_E_INVALID;
     if (n && (!task_id || !worker_id)) return fail(ctx, HQTICK_E_INVALID, "hqtick_retracting_add: null array");
-    for (uint32_t i = 0; i < n; i++) ctx->retr[task_id[i]] = hqtick_ctx::RetrEntry{worker_id[i], true, false, 0, 0};
+    ctx->retr.add(n, task_id, worker_id);
     return 0;
 }
 
@@ -2310,28 +2050,18 @@ int hqtick_retract_response(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, con
                             const uint32_t **assigned_worker_id, const uint8_t **assigned_variant) {
     if (!ctx) return HQTICK_E_INVALID;
     if (n && !task_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_retract_response: null array");
-    ctx->resp_task.clear(); ctx->resp_worker.clear(); ctx->resp_variant.clear();
-    int left = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        auto it = ctx->retr.find(task_id[i]);
-        if (it == ctx->retr.end() || it->second.old_id != worker_id) continue;  // "retracted task is in invalid state"  reactor.rs:476-481
-        if (it->second.has_redirect) { ctx->resp_task.push_back(task_id[i]); ctx->resp_worker.push_back(it->second.target_id); ctx->resp_variant.push_back(it->second.variant); }
-        ctx->retr.erase(it); left++;
-    }
-    if (n_assigned) *n_assigned = (uint32_t)ctx->resp_task.size();
-    if (assigned_task) *assigned_task = ctx->resp_task.data();
-    if (assigned_worker_id) *assigned_worker_id = ctx->resp_worker.data();
-    if (assigned_variant) *assigned_variant = ctx->resp_variant.data();
+    const int left = ctx->retr.response(worker_id, n, task_id);
+    ctx->retr.last.get(n_assigned, assigned_task, assigned_worker_id, assigned_variant);
     return left;
 }
 
-uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? (uint32_t)ctx->retr.size() : 0u; }
+uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? ctx->retr.count() : 0u; }
 
 // ---- assignment ledger (ABI 12; include/hqtick.h): arguments validated here, the operations are hqasg::Ledger's (ledger.h) ----
 int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
     if (!ctx) return HQTICK_E_INVALID;
     if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
-    if (!ctx->cluster_valid || !ctx->mirror.valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
+    if (!ctx->ws.valid()) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
     if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: null array");
     HQ_HIP(hipSetDevice(ctx->device));
     return ledger_fail(ctx, ctx->asg.enable(ledger_env(ctx), n, task_id, worker_id, rq, variant, priority));
@@ -2398,8 +2128,8 @@ int hqtick_assigned_free_rows(hqtick_ctx *ctx, uint32_t *n_workers, const uint64
     if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
     HQ_HIP(hipSetDevice(ctx->device));
     if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
-    if (n_workers) *n_workers = ctx->cl_W;
-    if (free_rows) *free_rows = ctx->mirror.free_.data();
+    if (n_workers) *n_workers = ctx->ws.W();
+    if (free_rows) *free_rows = ctx->ws.free_rows()->data();
     return 0;
 }
 
