@@ -1,5 +1,6 @@
 // hqcluster::WorkerSet and hqcluster::Retracting — the host side of the resident worker set (cluster.h; kernels: kernels.hip).
 #include "cluster.h"
+#include "clock_core.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -48,9 +49,9 @@ int WorkerSet::init() {
     return 0;
 }
 void WorkerSet::release() {
-    d_tab.release(); d_next.release(); h_tab.release(); h_delta.release();
+    d_tab.release(); d_next.release(); h_tab.release(); h_delta.release(); d_deadline.release(); h_deadline.release();
     if (ev) hipEventDestroy(ev);
-    ev = nullptr; pending = false; valid_ = false;
+    ev = nullptr; pending = false; valid_ = false; clock_mode_ = false;
 }
 int WorkerSet::wait() {
     if (pending) { HQ_HIP(hipEventSynchronize(ev)); pending = false; }
@@ -74,7 +75,7 @@ int WorkerSet::upload(hipStream_t st, const hqtick_snapshot *s) {
     HQ_HIP(hipMemcpyAsync(d_tab.p, h, L.bytes, hipMemcpyHostToDevice, st));
     HQ_HIP(hipStreamSynchronize(st));
     rt.assign(h + L.o_amt, h + L.bytes);
-    W_ = W; R_ = R; valid_ = true;
+    W_ = W; R_ = R; valid_ = true; clock_mode_ = false;
     id.assign(s->worker_id, s->worker_id + W);
     total.assign(s->worker_total, s->worker_total + (size_t)W * R); free_.assign(s->worker_free, s->worker_free + (size_t)W * R);
     rem.assign(W, HQ_NO_TIME_LIMIT); if (s->worker_remaining_ns) rem.assign(s->worker_remaining_ns, s->worker_remaining_ns + W);
@@ -97,15 +98,18 @@ int WorkerSet::update_rows(hipStream_t st, uint32_t n, const uint32_t *worker_in
     if (!h_delta.ensure(bytes)) return fail(HQTICK_E_DEVICE, "allocating delta staging");
     unsigned char *h = h_delta.as<unsigned char>(), *d = h_delta.dev<unsigned char>();
     memcpy(h, free_rows, o_rem);
+    const bool to_deadline = remaining_ns && clock_mode_;  // clock mode: a remaining lifetime is one at the current clock and moves the row's deadline, not the column
     if (remaining_ns) memcpy(h + o_rem, remaining_ns, (size_t)n * 8);
     memcpy(h + o_idx, worker_index, (size_t)n * 4);
     for (uint32_t i = 0; i < n; i++) {  // the host mirror follows
         memcpy(free_.data() + (size_t)worker_index[i] * R, free_rows + (size_t)i * R, (size_t)R * 8);
-        if (remaining_ns) rem[worker_index[i]] = remaining_ns[i];
+        if (to_deadline) deadline[worker_index[i]] = hqclock::deadline_of(now_, remaining_ns[i]);
+        else if (remaining_ns) rem[worker_index[i]] = remaining_ns[i];
     }
+    if (to_deadline) dl_dirty = rem_dirty = true;
     const TabLayout L = table_layout(W_, R, 0, 0);
     HQ_HIP(hqk::scatter_worker_rows(reinterpret_cast<uint64_t *>(rows() + L.o_free), reinterpret_cast<int64_t *>(rows() + L.o_rem), R, n, reinterpret_cast<const uint32_t *>(d + o_idx),
-                                    reinterpret_cast<const uint64_t *>(d), remaining_ns ? reinterpret_cast<const int64_t *>(d + o_rem) : nullptr, st));
+                                    reinterpret_cast<const uint64_t *>(d), remaining_ns && !to_deadline ? reinterpret_cast<const int64_t *>(d + o_rem) : nullptr, st));
     return staged(st);
 }
 
@@ -174,7 +178,9 @@ void WorkerSet::add_rows(uint32_t n, const uint32_t *worker_id, const uint64_t *
     for (uint32_t i = 0; i < n; i++) {
         rem.push_back(rem_ns ? rem_ns[i] : (int64_t)HQ_NO_TIME_LIMIT); min_util.push_back(mu ? mu[i] : 0.0f); flags_.push_back(fl ? fl[i] : (uint8_t)HQ_WORKER_SN);
         group.push_back(grp ? grp[i] : 0u); if (grp && grp[i] + 1 > n_groups) n_groups = grp[i] + 1;
+        if (clock_mode_) deadline.push_back(hqclock::deadline_of(now_, rem.back()));  // (the re-pack wrote the plain lifetime into the column: the next tick's k_clock_rows replaces it)
     }
+    if (clock_mode_) dl_dirty = rem_dirty = true;
     blk_dirty = true;
 }
 
@@ -185,12 +191,25 @@ void WorkerSet::keep_rows(const std::vector<uint32_t> &src) {
         if (k == src.size() || src[k] != w) { blocked.erase(id[w]); continue; }
         if (k != w) {
             id[k] = id[w]; rem[k] = rem[w]; min_util[k] = min_util[w]; flags_[k] = flags_[w]; group[k] = group[w];
+            if (clock_mode_) deadline[k] = deadline[w];
             memmove(total.data() + (size_t)k * R, total.data() + (size_t)w * R, (size_t)R * 8); memmove(free_.data() + (size_t)k * R, free_.data() + (size_t)w * R, (size_t)R * 8);
         }
         k++;
     }
     id.resize(k); rem.resize(k); min_util.resize(k); flags_.resize(k); group.resize(k); total.resize((size_t)k * R); free_.resize((size_t)k * R);
+    if (clock_mode_) { deadline.resize(k); dl_dirty = rem_dirty = true; }
     blk_dirty = true;
+}
+
+int WorkerSet::set_clock(int64_t now_ns) {
+    if (!clock_mode_) {  // a host that uploaded lifetimes taken at now_ns loses nothing
+        deadline.resize(W_);
+        for (uint32_t w = 0; w < W_; w++) deadline[w] = hqclock::deadline_of(now_ns, rem[w]);
+        thr_src.clear(); thr.clear();
+        clock_mode_ = true; dl_dirty = rem_dirty = true;
+    } else if (now_ns != now_) rem_dirty = true;
+    now_ = now_ns;
+    return 0;
 }
 
 int WorkerSet::set_blocked(uint32_t worker_id, uint32_t n, const uint32_t *rq, const uint8_t *variant) {
@@ -221,6 +240,7 @@ int WorkerSet::complete(const hqtick_snapshot *s, hqtick_snapshot *full) {
     if (s->n_workers == HQ_WORKERS_RESIDENT && !mine)
         return fail(HQTICK_E_INVALID, s->worker_id ? "n_workers == HQ_WORKERS_RESIDENT with worker arrays in the snapshot"
                                                    : "n_workers == HQ_WORKERS_RESIDENT without a resident worker set (hqtick_cluster_upload; dropped by hqtick_cluster_drop)");
+    if (clock_mode_ && valid_ && !mine) return fail(HQTICK_E_INVALID, "clock mode (hqtick_cluster_set_clock): the tick runs on the resident worker set, the snapshot must not carry worker arrays as well");
     if (!mine) return 0;
     const uint32_t W = W_;
     if (s->n_workers != 0 && s->n_workers != HQ_WORKERS_RESIDENT && s->n_workers != W) return fail(HQTICK_E_INVALID, "snapshot without worker arrays: n_workers must be HQ_WORKERS_RESIDENT, 0 or the resident worker count");
@@ -229,6 +249,22 @@ int WorkerSet::complete(const hqtick_snapshot *s, hqtick_snapshot *full) {
         blk_worker.clear(); blk_rq.clear(); blk_variant.clear();
         for (uint32_t w = 0; w < W; w++) { auto it = blocked.find(id[w]); if (it == blocked.end()) continue; for (auto &p : it->second) { blk_worker.push_back(w); blk_rq.push_back(p.first); blk_variant.push_back(p.second); } }
         blk_dirty = false;
+    }
+    if (clock_mode_) {  // the mirror's remaining lifetimes against this snapshot's thresholds: what k_clock_rows writes into the column (tables(), behind the request tables)
+        const uint32_t nv = s->n_requests ? s->rq_variant_off[s->n_requests] : 0;
+        const bool zeros = !s->variant_min_time_ns;  // (packed as zeros)
+        bool same_thr = thr_src.size() == nv;
+        for (uint32_t v = 0; same_thr && v < nv; v++) same_thr = thr_src[v] == (zeros ? 0 : s->variant_min_time_ns[v]);
+        if (!same_thr) {
+            thr_src.resize(nv);
+            for (uint32_t v = 0; v < nv; v++) thr_src[v] = zeros ? 0 : s->variant_min_time_ns[v];
+            thr = thr_src; std::sort(thr.begin(), thr.end()); thr.erase(std::unique(thr.begin(), thr.end()), thr.end());
+            rem_dirty = true;
+        }
+        if (rem_dirty) {
+            for (uint32_t w = 0; w < W; w++) rem[w] = hqclock::canonical_sorted(deadline[w], now_, thr.data(), (uint32_t)thr.size());
+            rem_dirty = false; kernel_due = true;
+        }
     }
     full->n_workers = W; full->worker_id = id.data(); full->worker_total = total.data(); full->worker_free = free_.data(); full->worker_remaining_ns = rem.data();
     full->worker_min_utilization = min_util.data(); full->worker_flags = flags_.data(); full->worker_group = group.data(); full->n_groups = n_groups; full->worker_map_rank = nullptr;
@@ -258,6 +294,16 @@ int WorkerSet::tables(hipStream_t st, const hqtick_snapshot *s, uint32_t W, UpVi
         HQ_HIP(hipMemcpyAsync(rows() + L.o_amt, h + L.o_amt, rt_bytes, hipMemcpyHostToDevice, st));
         if (int rc = staged(st)) return rc;
         rt.assign(h + L.o_amt, h + L.o_amt + rt_bytes);
+    }
+    if (clock_mode_ && kernel_due) {  // something k_clock_rows reads changed since its last run: the clock, a deadline, the membership or the thresholds (complete())
+        if (dl_dirty) {
+            if (!h_deadline.ensure((size_t)W * 8 + 64) || !d_deadline.ensure((size_t)W * 8 + 64)) return fail(HQTICK_E_DEVICE, "allocating the deadline column");
+            if (W) { memcpy(h_deadline.p, deadline.data(), (size_t)W * 8); HQ_HIP(hipMemcpyAsync(d_deadline.p, h_deadline.p, (size_t)W * 8, hipMemcpyHostToDevice, st)); }
+            dl_dirty = false;
+        }
+        HQ_HIP(hqk::clock_rows(d_deadline.as<int64_t>(), now_, reinterpret_cast<const uint64_t *>(rows() + L.o_time), L.nv, W, reinterpret_cast<int64_t *>(rows() + L.o_rem), st));
+        if (int rc = staged(st)) return rc;
+        kernel_due = false; n_clock_launches++;
     }
     if (check) {  // HQTICK_CHECK_CLUSTER=1 (tests): the rows in HBM must be the rows of the snapshot
         std::vector<unsigned char> dev(L.o_amt);

@@ -44,7 +44,14 @@ class WorkerSet {
     std::vector<uint64_t> *free_rows() { return &free_; }
     // ---- the set as a whole
     int upload(hipStream_t st, const hqtick_snapshot *s);  // (validated by the caller)
-    void drop() { valid_ = false; }
+    void drop() { valid_ = false; clock_mode_ = false; }
+    // ---- clock mode (hqtick_cluster_set_clock): the termination times are resident and a tick takes only the clock.  The first call turns every row's remaining
+    // lifetime into a deadline at `now_ns`; from then on `rem` and the column in HBM hold the canonical value of clock_core.h, rewritten (complete() on the host,
+    // k_clock_rows from tables()) when the clock, a deadline, the membership or the request table's min_time thresholds changed.  upload() and drop() leave the mode.
+    int set_clock(int64_t now_ns);
+    bool clock_mode() const { return clock_mode_; }
+    const std::vector<int64_t> &deadlines() const { return deadline; }
+    uint32_t clock_launches() const { return n_clock_launches; }  // k_clock_rows launches of this set so far (test hook)
     // ---- deltas
     int update_rows(hipStream_t st, uint32_t n, const uint32_t *worker_index, const uint64_t *free_rows, const int64_t *remaining_ns);
     // A membership change in three steps, between which hqtick.cpp runs the ledger's: the row map `src` of the new table (old row index, or W + k for the k-th new
@@ -78,6 +85,10 @@ class WorkerSet {
     // the host mirror (ABI 7): what a snapshot without worker arrays is completed from, kept current by the deltas
     uint32_t n_groups = 1;
     std::vector<uint32_t> id, group; std::vector<uint64_t> total, free_; std::vector<int64_t> rem; std::vector<float> min_util; std::vector<uint8_t> flags_;
+    // clock mode: the clock, the deadline mirror and its column in HBM, the thresholds as the last tick's request table had them and sorted without duplicates
+    bool clock_mode_ = false, dl_dirty = false, rem_dirty = false, kernel_due = false; int64_t now_ = 0; uint32_t n_clock_launches = 0;
+    std::vector<int64_t> deadline; hqbuf::DevBuf d_deadline; hqbuf::PinBuf h_deadline;
+    std::vector<uint64_t> thr_src, thr;
     std::map<uint32_t, std::vector<std::pair<uint32_t, uint8_t>>> blocked;   // worker id -> (rq, variant)
     std::vector<uint32_t> blk_worker, blk_rq; std::vector<uint8_t> blk_variant; bool blk_dirty = true;  // the same as (worker index, rq, variant) triples
 };

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "clock_core.h"
 #include "hb_order.h"
 #include "milp.h"
 #include "price_emul.h"
@@ -98,3 +99,24 @@ extern "C" uint32_t hqtick_debug_first_cut(unsigned char *out, uint32_t cap) {
     if (out && cap) memcpy(out, b.data(), std::min<size_t>(cap, b.size()));
     return (uint32_t)b.size();
 }
+
+// clock mode: the phase function of k_clock_rows over arrays, in the linear form the kernel folds and in the sorted form of the host mirror
+extern "C" int hqtick_debug_clock_rows(uint32_t n, const int64_t *deadline_ns, int64_t now_ns, uint32_t nv, const uint64_t *min_time_ns, int sorted_form, int64_t *remaining_out) {
+    if ((n && (!deadline_ns || !remaining_out)) || (nv && !min_time_ns)) return HQTICK_E_INVALID;
+    if (!sorted_form) {
+        for (uint32_t w = 0; w < n; w++) {  // the table in chunks, as the kernel stages it
+            if (deadline_ns[w] == hqclock::NO_LIMIT) { remaining_out[w] = hqclock::NO_LIMIT; continue; }
+            const int64_t r = hqclock::sat_sub(deadline_ns[w], now_ns);
+            uint64_t best = 0;
+            for (uint32_t v0 = 0; r >= 0 && v0 < nv; v0 += hqclock::CHUNK) best = hqclock::fold_thresholds(best, r, min_time_ns + v0, std::min(hqclock::CHUNK, nv - v0));
+            remaining_out[w] = r < 0 ? -1 : (int64_t)best;
+        }
+        return 0;
+    }
+    std::vector<uint64_t> thr(min_time_ns, min_time_ns + nv);
+    std::sort(thr.begin(), thr.end()); thr.erase(std::unique(thr.begin(), thr.end()), thr.end());
+    for (uint32_t w = 0; w < n; w++) remaining_out[w] = hqclock::canonical_sorted(deadline_ns[w], now_ns, thr.data(), (uint32_t)thr.size());
+    return 0;
+}
+extern "C" int64_t hqtick_debug_clock_deadline(int64_t now_ns, int64_t remaining_ns) { return hqclock::deadline_of(now_ns, remaining_ns); }
+extern "C" int64_t hqtick_debug_clock_remaining(int64_t deadline_ns, int64_t now_ns) { return hqclock::remaining_of(deadline_ns, now_ns); }

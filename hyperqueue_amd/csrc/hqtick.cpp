@@ -111,6 +111,7 @@ struct hqtick_ctx {
     DevBuf d_up, d_vflags, d_vtmc, d_blk;
     hqcluster::WorkerSet ws;      // hqtick_cluster_* (ABI 5 and 7; cluster.h): the worker / request tables resident in HBM and their host mirror
     hqcluster::Retracting retr;   // hqtick_retracting_* (ABI 7): the table of Retracting tasks
+    uint32_t last_row_groups = 0; // hqtick_cluster_last_row_groups
     bool sweep_inflight = false;  // an early K5a launch not yet covered by a stream synchronisation
     bool wait_on_kernel = true;   // HQ_HIP_LAST; HQTICK_WAIT_ON_KERNEL=0: hipStreamSynchronize at every wait (A/B)
     // selection + mapping
@@ -1330,6 +1331,7 @@ struct TickRun {
         // ---------------- GPU phase A ----------------
         const std::function<void()> prep = [&]() {   // request/worker views: no GPU output needed yet
             fill_problem(pb, s, ctx->cfg, ev);
+            ctx->last_row_groups = (uint32_t)pb.real.rows.rep.size();
             if (ctx->asg.on && !s->assigned_off) {  // the ledger's per-worker (rq, variant) counts
                 const hqasg::Agg g = ctx->asg.agg();
                 pb.real.agg_off = g.off; pb.real.agg_rq = g.rq; pb.real.agg_cnt = g.cnt; pb.real.agg_variant = g.var;
@@ -1951,6 +1953,24 @@ int hqtick_cluster_drop(hqtick_ctx *ctx) {
     return 0;
 }
 
+// Clock mode: the termination times stay with the worker set and a tick takes only the clock (hqcluster::WorkerSet::set_clock)
+int hqtick_cluster_set_clock(hqtick_ctx *ctx, int64_t now_ns) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_cluster_set_clock: not on a sharded or replica context");
+    if (int rc = cluster_open(ctx, "hqtick_cluster_set_clock")) return rc;
+    if (int rc = ledger_guard(ctx)) return rc;
+    return cluster_fail(ctx, ctx->ws.set_clock(now_ns));
+}
+
+int hqtick_cluster_deadlines(const hqtick_ctx *ctx, uint32_t *n_workers, const int64_t **deadline_ns) {
+    if (!ctx || !ctx->ws.valid() || !ctx->ws.clock_mode()) return HQTICK_E_INVALID;
+    if (n_workers) *n_workers = (uint32_t)ctx->ws.deadlines().size();
+    if (deadline_ns) *deadline_ns = ctx->ws.deadlines().data();
+    return 0;
+}
+
+uint32_t hqtick_cluster_last_row_groups(const hqtick_ctx *ctx) { return ctx ? ctx->last_row_groups : 0u; }
+
 // Membership changes.  The order of the steps is load-bearing: the ledger's re-pack runs on an Env that already has the new worker count and still has the old mirror.
 int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint64_t *total_rows, const uint64_t *free_rows, const int64_t *remaining_ns,
                                const float *min_utilization, const uint8_t *flags, const uint32_t *group) {
@@ -2406,6 +2426,7 @@ uint32_t hqtick_debug_last_mn(const uint32_t **rq, const uint32_t **off, const u
     if (worker) *worker = g_last_mn_worker.data();
     return (uint32_t)g_last_mn_rq.size();
 }
+uint32_t hqtick_debug_clock_launches(const hqtick_ctx *ctx) { return ctx ? ctx->ws.clock_launches() : 0u; }
 int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n_levels, double *order_us) {
     if (!ctx) return HQTICK_E_INVALID;
     if (n_runs) *n_runs = ctx->dbg_order ? ctx->dbg_order_runs : 0;

@@ -159,6 +159,9 @@ hipError_t scatter_worker_rows(uint64_t *free_, int64_t *rem, uint32_t R, uint32
 hipError_t repack_worker_rows(const uint64_t *old_total, const uint64_t *old_free, const int64_t *old_rem, uint32_t W_old, uint32_t R, uint32_t W_new, const uint32_t *src,
                               const uint64_t *add_total, const uint64_t *add_free, const int64_t *add_rem, uint64_t *new_total, uint64_t *new_free, int64_t *new_rem, hipStream_t s);
 
+// Clock mode: rem[w] = the canonical remaining lifetime (clock_core.h) of deadline[w] at `now` against the nv min_time thresholds of the request table in HBM
+hipError_t clock_rows(const int64_t *deadline, int64_t now, const uint64_t *min_time, uint32_t nv, uint32_t W, int64_t *rem, hipStream_t s);
+
 // Resident ready-set deltas: tombstone the given ids (sorted id column, binary search), count live tasks per
 // 256-task slice, and rebuild the columns dropping tombstones while merging a sorted batch of new tasks.
 hipError_t ready_restore_consumed(const uint16_t *gkey, uint32_t *rq, uint64_t n, uint32_t Q, uint32_t *n_done, hipStream_t s);

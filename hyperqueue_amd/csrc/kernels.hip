@@ -12,6 +12,7 @@
 // K5a/K5b expand per-(request, variant, worker) counts into per-worker records (mapping.rs:36-131): K5a one wavefront per
 // (key, sweep) builds ballot bit rows of the round-robin, K5b one workgroup per worker gathers its records.
 #include "kernels.h"
+#include "clock_core.h"
 #include <hip/hip_ext.h>
 
 #include <type_traits>
@@ -871,6 +872,27 @@ __global__ void __launch_bounds__(256) k_repack_worker_rows(const uint64_t *__re
     }
 }
 
+// Clock mode (hqtick_cluster_set_clock): the remaining-lifetime column from the resident termination times and the clock, one lane per worker row.  What is written
+// is the canonical value of clock_core.h — the largest min_time of the request table in HBM that `deadline - now` still passes — so workers that differ in their
+// deadlines only stay equal rows for the host's grouping.  The thresholds pass through LDS in chunks of one per thread: nv is not bounded here.
+__global__ void __launch_bounds__(256) k_clock_rows(const int64_t *__restrict__ deadline, int64_t now, const uint64_t *__restrict__ min_time, uint32_t nv, uint32_t W,
+                                                    int64_t *__restrict__ rem) {
+    static_assert(hqclock::CHUNK == 256, "one threshold per thread of the workgroup");
+    __shared__ uint64_t s_thr[hqclock::CHUNK];
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t d = w < W ? deadline[w] : hqclock::NO_LIMIT;
+    const int64_t r = d == hqclock::NO_LIMIT ? -1 : hqclock::sat_sub(d, now);  // (r < 0: nothing to fold — no limit, past the deadline, or no row)
+    uint64_t best = 0;
+    for (uint32_t v0 = 0; v0 < nv; v0 += hqclock::CHUNK) {  // (nv is uniform: every thread meets every barrier)
+        const uint32_t n = nv - v0 < hqclock::CHUNK ? nv - v0 : hqclock::CHUNK;
+        __syncthreads();  // the previous chunk has been read
+        if (threadIdx.x < n) s_thr[threadIdx.x] = min_time[v0 + threadIdx.x];
+        __syncthreads();
+        if (r >= 0) best = hqclock::fold_thresholds(best, r, s_thr, n);  // every lane reads the same word: an LDS broadcast
+    }
+    if (w < W) rem[w] = d == hqclock::NO_LIMIT ? hqclock::NO_LIMIT : (r < 0 ? (int64_t)-1 : (int64_t)best);
+}
+
 // ------------------------------------------------------------------------------------------------ resident ready-set deltas (f1)
 // TaskQueues::add_ready_task / take_tasks / remove on the HBM-resident columns (scheduler/taskqueue.rs:37-43,146-217,304-355).
 // Removal is a tombstone in the rq column (RQ_TOMBSTONE); k_rebuild drops tombstones and merges a sorted batch of new tasks.
@@ -1345,6 +1367,12 @@ hipError_t repack_worker_rows(const uint64_t *old_total, const uint64_t *old_fre
                               const uint64_t *add_total, const uint64_t *add_free, const int64_t *add_rem, uint64_t *new_total, uint64_t *new_free, int64_t *new_rem, hipStream_t s) {
     if (W_new == 0 || R == 0) return hipSuccess;
     hipLaunchKernelGGL(k_repack_worker_rows, dim3((W_new * R + 255) / 256), dim3(256), 0, s, old_total, old_free, old_rem, W_old, R, W_new, src, add_total, add_free, add_rem, new_total, new_free, new_rem);
+    return hipGetLastError();
+}
+
+hipError_t clock_rows(const int64_t *deadline, int64_t now, const uint64_t *min_time, uint32_t nv, uint32_t W, int64_t *rem, hipStream_t s) {
+    if (W == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_clock_rows, dim3((W + 255) / 256), dim3(256), 0, s, deadline, now, min_time, nv, W, rem);
     return hipGetLastError();
 }
 

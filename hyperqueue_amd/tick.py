@@ -262,6 +262,27 @@ class Tick:
         self._lib.hqtick_retracting_count.argtypes = [C.c_void_p]
         return int(self._lib.hqtick_retracting_count(self._ctx))
 
+    # -- clock mode: termination times resident, a tick takes only the clock (include/hqtick.h) -----------------------------------
+    def cluster_set_clock(self, now_ns: int):
+        """the clock of the resident worker set; the first call turns the uploaded remaining lifetimes into termination times at now_ns"""
+        f = self._lib.hqtick_cluster_set_clock
+        f.argtypes = [C.c_void_p, C.c_int64]
+        self._chk(f(self._ctx, int(now_ns)))
+
+    def cluster_deadlines(self) -> np.ndarray:
+        """the termination times in row order (HQ_NO_TIME_LIMIT: none); clock mode only"""
+        n = C.c_uint32(); p = C.POINTER(C.c_int64)()
+        f = self._lib.hqtick_cluster_deadlines
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_int64))]
+        self._chk(f(self._ctx, C.byref(n), C.byref(p)))
+        return abi._np(p, n.value, np.int64).copy() if n.value else np.zeros(0, np.int64)
+
+    def cluster_last_row_groups(self) -> int:
+        """groups of equal worker rows the host stages of the last tick found"""
+        f = self._lib.hqtick_cluster_last_row_groups
+        f.argtypes = [C.c_void_p]; f.restype = C.c_uint32
+        return int(f(self._ctx))
+
     def cluster_drop(self):
         self._lib.hqtick_cluster_drop.argtypes = [C.c_void_p]
         self._chk(self._lib.hqtick_cluster_drop(self._ctx))

@@ -434,6 +434,28 @@ int hqtick_cluster_workers(const hqtick_ctx *ctx, uint32_t *n_workers, const uin
 int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint8_t *flags);
 int hqtick_cluster_worker_flags(const hqtick_ctx *ctx, uint32_t *n_workers, const uint8_t **flags);
 /*
+ * Workers with a time limit: CLOCK MODE (functions added under ABI 12).  worker_remaining_ns is termination time - now: it changes on every tick for every such
+ * worker, and workers that connected microseconds apart never have equal rows.  Instead the library keeps each worker's termination time and is told the time:
+ *   hqtick_cluster_set_clock       the clock of the resident worker set (any int64 nanosecond count; it may move in either direction).  The FIRST call switches
+ *                                  the set to clock mode: every row gets the deadline now_ns + its remaining lifetime (saturating; HQ_NO_TIME_LIMIT stays), so a
+ *                                  host that uploaded lifetimes taken at now_ns loses nothing.  Needs a resident worker set (HQTICK_E_INVALID); refused while a
+ *                                  placement waits for its consume, like the other cluster calls; HQTICK_E_UNSUPPORTED on sharded and replica contexts.
+ *   hqtick_cluster_deadlines       the termination times in row order (valid until the next call on the context); HQTICK_E_INVALID outside clock mode.
+ *   hqtick_cluster_last_row_groups test accessor: the groups of equal worker rows the host stages of the last tick found.
+ * In clock mode the other calls keep their meaning relative to the clock: remaining_ns of hqtick_cluster_add_workers and of hqtick_cluster_update_workers
+ * (a correction) is the remaining lifetime at the current clock and sets the row's deadline to clock + remaining_ns.  hqtick_cluster_upload and
+ * hqtick_cluster_drop leave clock mode, like everything else about a worker set.  A tick runs on the resident worker set (n_workers = HQ_WORKERS_RESIDENT,
+ * worker_id = NULL); a snapshot that brings worker arrays is HQTICK_E_INVALID (the tick must not see two truths).
+ * What a tick reads as a worker's remaining lifetime is then CANONICAL: HQ_NO_TIME_LIMIT without a limit, -1 past the deadline, else the largest
+ * variant_min_time_ns of the snapshot's request table that deadline - clock still covers (0 if none).  Every variant's time test answers as for the true value,
+ * and workers that pass the same tests are equal rows whatever their exact deadlines.  One small kernel (k_clock_rows) rewrites the column in HBM, and only when
+ * the clock, a deadline, the membership or the request table changed since its last run; nothing is uploaded per tick.  A context that never sets the clock
+ * launches nothing new.
+ */
+int hqtick_cluster_set_clock(hqtick_ctx *ctx, int64_t now_ns);
+int hqtick_cluster_deadlines(const hqtick_ctx *ctx, uint32_t *n_workers, const int64_t **deadline_ns);
+uint32_t hqtick_cluster_last_row_groups(const hqtick_ctx *ctx);
+/*
  * Retracting tasks as deltas (ABI 7; on_retract_response, process_retracted — server/reactor.rs:34-62,462-508).  The table of tasks in state
  * Retracting{worker} — with their scheduler_state.redirects entry — can live in the library instead of travelling in every snapshot:
  *   hqtick_retracting_add      process_retracted outside a tick: a higher-priority arrival dissolved a prefill set (check_dispose_prefill,
@@ -500,7 +522,9 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  * is consumed, ledger and membership calls are HQTICK_E_INVALID; a tick that is not consumed (any ready-set or graph delta, another tick) is abandoned with
  * its selection and never enters.  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
  * tasks have left the ready set, so the host uploads the worker set and enables the ledger again from its own view.
- * hqtick_cluster_update_workers still works (remaining lifetime, corrections).
+ * Remaining lifetimes: hqtick_cluster_update_workers needs the free rows of every row it lists, which a ledger host no longer holds, so time limits running
+ * down go through the clock instead (hqtick_cluster_set_clock above: 8 bytes per tick, no rows).  hqtick_cluster_update_workers remains for corrections by a host
+ * that does hold the rows.
  * Prefilled tasks (SingleNodeTaskAssignment::prefilled_tasks, server/worker.rs:40-46) are the ledger's too once tracking is switched on; with it off
  * every call and every launch is as described above and the host sends prefilled_off / prefilled_rq with each snapshot.  A prefilled task is an entry
  * of the same table with variant 0xFE (its worker: the one it is prefilled on; request and priority as for any entry); it counts in no (row, variant)

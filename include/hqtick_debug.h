@@ -175,6 +175,15 @@ void hqtick_debug_set_exchange(hqtick_exchange_fn fn, void *user, uint32_t rank,
 uint32_t hqtick_debug_last_exchange_calls(void);
 /* one exchange of the sharded solve through the library's RCCL communicator (hqtick_comm_init): recv gets world x bytes_per_rank bytes */
 int hqtick_debug_exchange(hqtick_ctx *ctx, const void *send, void *recv, size_t bytes_per_rank);
+
+/* Clock mode (hqtick_cluster_set_clock; csrc/clock_core.h).  hqtick_debug_clock_rows runs the phase function of k_clock_rows on the CPU: remaining_out[w] = the
+ * canonical remaining lifetime of deadline_ns[w] at now_ns against min_time_ns[0..nv) — sorted_form = 0: the linear fold over the table in the kernel's chunks,
+ * 1: the binary search over a sorted copy without duplicates that the host mirror runs.  _clock_deadline / _clock_remaining: now + remaining and deadline - now as
+ * the library computes them (saturating, HQ_NO_TIME_LIMIT kept).  _clock_launches: k_clock_rows launches of the context's worker set so far (GPU only). */
+int hqtick_debug_clock_rows(uint32_t n, const int64_t *deadline_ns, int64_t now_ns, uint32_t nv, const uint64_t *min_time_ns, int sorted_form, int64_t *remaining_out);
+int64_t hqtick_debug_clock_deadline(int64_t now_ns, int64_t remaining_ns);
+int64_t hqtick_debug_clock_remaining(int64_t deadline_ns, int64_t now_ns);
+uint32_t hqtick_debug_clock_launches(const hqtick_ctx *ctx);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
