@@ -101,6 +101,7 @@ struct hqtick_ctx {
     bool last_ordered = false;    // the pending selection (last_valid) is one of the view: consume / restore replay it with order_select
     hqk::OrderSelect last_os{};   // ... its tables (HBM copy of the plan, the permutation)
     uint32_t dbg_order_runs = 0, dbg_order_levels = 0; bool dbg_order = false; double dbg_order_us = 0;  // hqtick_debug_last_order
+    uint32_t dbg_order_passes = 0;  // bit dg: the last view built on these buffers ran a pass on digit dg (hqtick_debug_order_view)
     uint32_t dbg_scan_L = 0, dbg_scan_G = 0, dbg_scan_shape[4] = {0, 0, 0, 0}; bool dbg_scan = false, dbg_census = false;  // hqtick_debug_last_scan: what the last dense scan (phase_a) / census (census_resident, on the query sub-context) left in h_a, h_levels, h_lv
     uint32_t lv_seq = 0; bool set_clean = false; bool no_spec_scan = getenv("HQTICK_NO_SPEC_SCAN") != nullptr; bool levels_valid = false; uint32_t cached_L = 0; std::vector<uint64_t> h_levels; bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))  // level table of the previous tick (re-validated by K1 every tick)
     PinBuf h_up, h_up2, h_q, h_a, h_plan, h_rec, h_sinkhdr, h_add, h_addp, h_retr, h_blk, h_k5a, h_lv;   // (h_lv: the level table as k_sort_levels writes it)
@@ -132,6 +133,8 @@ struct hqtick_ctx {
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
     hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
+    hqtick_ctx *vctx = nullptr;  // hqtick_debug_order_view's private sub-context (test library only); the view it holds is described by its dbg_view
+    struct { bool valid = false; const void *ids = nullptr; uint64_t N = 0; uint32_t Q = 0, n_live = 0; bool rq_copy = false; std::vector<uint32_t> run_off, run_start, run_rank; } dbg_view;
     ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
     // sharded placement solve: the ranks split the coupled solve's price sweeps and the separable solve's class blocks, one small all-gather of host
     // buffers per sweep / per launch — through the host's callback (hqtick_set_exchange) or the library's own RCCL communicator
@@ -331,6 +334,13 @@ void runs_from_hist(Scan &sc) {
     }
 }
 
+// the run table of a view of n live slots as order_runs writes it into h_ord: [n_runs, n_levels, pad][run_rq n][run_start n][run_rank n][run_prio n]
+struct OrderTabLayout { size_t o_rq, o_st, o_rk, o_pr, bytes; };
+OrderTabLayout order_tab_layout(uint32_t n) {
+    OrderTabLayout l; l.o_rq = 16; l.o_st = l.o_rq + (size_t)n * 4; l.o_rk = l.o_st + (size_t)n * 4; l.o_pr = (l.o_rk + (size_t)n * 4 + 7) & ~(size_t)7; l.bytes = l.o_pr + (size_t)n * 8 + 16;
+    return l;
+}
+
 // The ordered view (order.hip) of the columns prio / rq [0..N) on the buffers of `b` (ctx itself, or hqtick_query_resident's sub-context
 // reading ctx's columns): sc gets the runs, b->d_perm the permutation, b->d_inv its inverse.  One synchronisation after the digit histogram (which passes
 // to run, how many live slots), one after the run table.  Errors are reported on ctx.
@@ -363,7 +373,8 @@ int build_view(hqtick_ctx *ctx, hqtick_ctx *b, const uint64_t *prio, const uint3
     uint32_t level_after = 0;                 // the level ranks are read off the permutation after the last priority pass (no such pass: one priority, any order)
     for (uint32_t i = 0; i < passes.size(); i++) if (passes[i] < 8) level_after = i;
     const uint32_t tiles = hqk::order_tiles(N);
-    const size_t o_rq = 16, o_st = o_rq + (size_t)n * 4, o_rk = o_st + (size_t)n * 4, o_pr = (o_rk + (size_t)n * 4 + 7) & ~(size_t)7, h_bytes = o_pr + (size_t)n * 8 + 16;
+    const OrderTabLayout tl = order_tab_layout(n);
+    const size_t o_rq = tl.o_rq, o_st = tl.o_st, o_rk = tl.o_rk, o_pr = tl.o_pr, h_bytes = tl.bytes;
     if (!b->d_perm.ensure((size_t)n * 4 + 16) || !b->d_perm2.ensure((size_t)n * 4 + 16) || !b->d_ord_tab.ensure((size_t)tiles * 256 * 4 + 16) ||
         !b->d_ord_tiles.ensure(((size_t)tiles + 1) * 4 + 16) || !b->d_inv.ensure(N * 8 + 16) || !b->h_ord.ensure(h_bytes))
         return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ordered view");
@@ -398,6 +409,7 @@ int build_view(hqtick_ctx *ctx, hqtick_ctx *b, const uint64_t *prio, const uint3
     sc->L = nl; sc->G = nr;
     if (b->timing) { const double us_ = elapsed_us(b->ev[12], b->ev[13]); b->dbg_order_us = us_ >= 0 ? us_ : 0.0; }
     b->dbg_order = true; b->dbg_order_runs = nr; b->dbg_order_levels = nl;
+    b->dbg_order_passes = 0; for (uint32_t dg : passes) b->dbg_order_passes |= 1u << dg;
     return 0;
 }
 
@@ -1538,6 +1550,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     for (DevBuf *b : bufs) b->release();
     ctx->ws.release();
     if (ctx->qctx) { hqtick_destroy(ctx->qctx); ctx->qctx = nullptr; }
+    if (ctx->vctx) { hqtick_destroy(ctx->vctx); ctx->vctx = nullptr; }
     hipSetDevice(ctx->device);
     if (ctx->comm) { rccl_destroy_comm(ctx); }
     ctx->graph.release();
@@ -2450,6 +2463,125 @@ int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels,
     if (hist) for (uint32_t i = 0; i < G && i < cap_groups; i++) hist[i] = hs[i];
     return 1;
 }
+// The ordered view by itself ("The view hooks"): built by build_view on a sub-context of its own, so that ctx keeps its permutation, its pending
+// selection, ordered_sticky, levels_valid and its dbg_* fields; every device array comes back by one copy, here and nowhere on a tick's path.
+int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t counts[4], uint32_t *perm, uint32_t *inv, uint32_t *lrank, uint64_t cap_slots, uint32_t *run_rq,
+                            uint32_t *run_start, uint32_t *run_rank, uint64_t *run_prio, uint32_t cap_runs) {
+    if (!ctx || !counts) return HQTICK_E_INVALID;
+    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
+    HQ_HIP(hipSetDevice(ctx->device));
+    if (!ctx->vctx) {
+        hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
+        int rc = hqtick_create(&cfg, &ctx->vctx);
+        if (rc) { ctx->vctx = nullptr; return fail(ctx, rc, "creating the view sub-context failed"); }
+    }
+    hqtick_ctx *v = ctx->vctx;
+    const uint64_t N = ctx->n_ready;
+    v->dbg_view.valid = false; v->dbg_view.rq_copy = false; v->dbg_order = false; v->dbg_order_passes = 0;
+    for (int i = 0; i < 4; i++) counts[i] = 0;
+    Scan sc;
+    if (int rc = build_view(ctx, v, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, n_requests, ctx->stream, &sc, nullptr)) return rc;
+    const uint32_t nr = (uint32_t)sc.run_cnt.size(), n = nr ? sc.run_start.back() + sc.run_cnt.back() : 0u;
+    if ((nr != 0) != v->dbg_order) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the run table and the debug record disagree");
+    counts[0] = n; counts[1] = nr; counts[2] = sc.L; counts[3] = v->dbg_order_passes;
+    if (n > cap_slots || N > cap_slots || nr > cap_runs) return fail(ctx, HQTICK_E_CAPACITY, "hqtick_debug_order_view: output arrays too small");
+    if (n) {
+        if (perm) HQ_HIP(hipMemcpy(perm, v->d_perm.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (inv) HQ_HIP(hipMemcpy(inv, v->d_inv.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+        if (lrank) HQ_HIP(hipMemcpy(lrank, v->d_inv.as<uint32_t>() + N, (size_t)N * 4, hipMemcpyDeviceToHost));
+        const OrderTabLayout tl = order_tab_layout(n);  // (the run table is in pinned host memory already: build_view has synchronised)
+        const uint8_t *hh = v->h_ord.as<uint8_t>();
+        if (run_rq) memcpy(run_rq, hh + tl.o_rq, (size_t)nr * 4);
+        if (run_start) memcpy(run_start, hh + tl.o_st, (size_t)nr * 4);
+        if (run_rank) memcpy(run_rank, hh + tl.o_rk, (size_t)nr * 4);
+        if (run_prio) memcpy(run_prio, hh + tl.o_pr, (size_t)nr * 8);
+    }
+    v->dbg_view.ids = ctx->d_tid.p; v->dbg_view.N = N; v->dbg_view.Q = n_requests; v->dbg_view.n_live = n;
+    v->dbg_view.run_off = std::move(sc.run_off); v->dbg_view.run_start = std::move(sc.run_start); v->dbg_view.run_rank = std::move(sc.run_level);
+    v->dbg_view.valid = true;
+    return 0;
+}
+
+namespace {
+// the view hqtick_debug_order_view last built, if ctx's columns are still the ones it was built on
+hqtick_ctx *debug_view_of(hqtick_ctx *ctx) {
+    hqtick_ctx *v = ctx->vctx;
+    if (!v || !v->dbg_view.valid || !ctx->resident || v->dbg_view.ids != ctx->d_tid.p || v->dbg_view.N != ctx->n_ready) return nullptr;
+    return v;
+}
+}  // namespace
+
+// k_order_select on that view.  mark_mode 0: select; 1: consume (RQ_TOMBSTONE at the selected slots, nothing selected); 2: restore (the request ids back, nothing
+// selected); 3: consume and select in one launch (HQTICK_FLAG_CONSUME_IN_TICK).  The marks go to a copy of the rq column — a fresh one for modes 0, 1 and 3, the copy as the
+// previous call left it for mode 2 — never to ctx's column.  The plan is checked on the host before the launch: no destination outside its request's range.
+int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, const uint32_t *q_tnc, uint32_t n_sel, int mark_mode, uint64_t *sel_task, uint32_t *sel_rank,
+                              uint32_t *rq_after, uint32_t *err) {
+    if (!ctx || !rq_sel_base || !q_tnc || !sel_task || !sel_rank || !err || mark_mode < 0 || mark_mode > 3) return HQTICK_E_INVALID;
+    hqtick_ctx *v = debug_view_of(ctx);
+    if (!v) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: no view of the current ready set (hqtick_debug_order_view)");
+    const uint32_t Q = v->dbg_view.Q, n = v->dbg_view.n_live, nr = (uint32_t)v->dbg_view.run_start.size();
+    const uint64_t N = v->dbg_view.N;
+    if (Q == 0 || n_sel == 0 || n == 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: nothing to select from");
+    if (rq_sel_base[0] != 0 || rq_sel_base[Q] != n_sel) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: rq_sel_base does not span [0, n_sel]");
+    for (uint32_t q = 0; q < Q; q++) {
+        if (rq_sel_base[q] > rq_sel_base[q + 1]) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: rq_sel_base not monotone");
+        const uint32_t take = rq_sel_base[q + 1] - rq_sel_base[q], nw = q_tnc[q] >> 16, c = q_tnc[q] & 0xFFFFu;
+        if (!q_tnc[q]) continue;
+        if (nw == 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: worker-major form without workers");
+        for (uint32_t p = 0; p < take && p < nw * c; p++)
+            if ((uint64_t)(p % nw) * c + p / nw >= take) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: a worker-major destination leaves its request's range");
+    }
+    if (mark_mode == 2 && !v->dbg_view.rq_copy) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: restore needs the copy a consume left");
+    HQ_HIP(hipSetDevice(ctx->device));
+    // the tables in HBM, as a tick's plan carries them: [rq_sel_base Q + 1][run_off Q + 1][q_tnc Q][run_start nr][run_rank nr]
+    std::vector<uint32_t> tab;
+    tab.insert(tab.end(), rq_sel_base, rq_sel_base + Q + 1);
+    tab.insert(tab.end(), v->dbg_view.run_off.begin(), v->dbg_view.run_off.end());
+    tab.insert(tab.end(), q_tnc, q_tnc + Q);
+    tab.insert(tab.end(), v->dbg_view.run_start.begin(), v->dbg_view.run_start.end());
+    tab.insert(tab.end(), v->dbg_view.run_rank.begin(), v->dbg_view.run_rank.end());
+    if (!v->d_map.ensure(tab.size() * 4 + 16) || !v->d_sel_task.ensure((size_t)n_sel * 8 + 16) || !v->d_sel_level.ensure((size_t)n_sel * 4 + 16) || !v->d_trq.ensure(N * 4 + 8))
+        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc view selection");
+    HQ_HIP(hipMemcpy(v->d_map.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    uint32_t *derr = v->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2;
+    HQ_HIP(hipMemsetAsync(derr, 0, 4, ctx->stream));
+    HQ_HIP(hipMemsetAsync(v->d_sel_task.p, 0xFF, (size_t)n_sel * 8, ctx->stream));   // the sentinel: a j the kernel did not write stays 0xFF..FF
+    HQ_HIP(hipMemsetAsync(v->d_sel_level.p, 0xFF, (size_t)n_sel * 4, ctx->stream));
+    if (mark_mode != 2) { HQ_HIP(hipMemcpyAsync(v->d_trq.p, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream)); v->dbg_view.rq_copy = true; }
+    const uint32_t *d = v->d_map.as<uint32_t>();
+    hqk::OrderSelect os{};
+    os.task_id = ctx->d_tid.as<uint64_t>(); os.perm = v->d_perm.as<uint32_t>(); os.n_live = n; os.Q = Q; os.n_runs = nr;
+    os.rq_sel_base = d; os.run_off = d + (Q + 1); os.q_tnc = d + 2 * (size_t)(Q + 1); os.run_start = os.q_tnc + Q; os.run_rank = os.run_start + nr;
+    os.sel_task = v->d_sel_task.as<uint64_t>(); os.sel_rank = v->d_sel_level.as<uint32_t>(); os.err = derr;
+    if (mark_mode) { os.mark_rq = v->d_trq.as<uint32_t>(); os.mark_value = mark_mode == 2 ? 0u : hqk::RQ_TOMBSTONE; os.mark_and_select = mark_mode == 3 ? 1u : 0u; }
+    HQ_HIP(hqk::order_select(os, n_sel, ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    HQ_HIP(hipMemcpy(sel_task, v->d_sel_task.p, (size_t)n_sel * 8, hipMemcpyDeviceToHost));
+    HQ_HIP(hipMemcpy(sel_rank, v->d_sel_level.p, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
+    if (rq_after) HQ_HIP(hipMemcpy(rq_after, v->d_trq.p, N * 4, hipMemcpyDeviceToHost));
+    HQ_HIP(hipMemcpy(err, derr, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// k_order_rank_of on that view: (request, position in the view) of the wanted ids against ctx's id and rq columns; 0xFFFFFFFF twice = not a live task of the set
+int hqtick_debug_order_rank_of(hqtick_ctx *ctx, const uint64_t *want, uint32_t n_want, uint32_t *out_rq, uint32_t *out_pos) {
+    if (!ctx || (n_want && (!want || !out_rq || !out_pos))) return HQTICK_E_INVALID;
+    hqtick_ctx *v = debug_view_of(ctx);
+    if (!v) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_rank_of: no view of the current ready set (hqtick_debug_order_view)");
+    if (n_want == 0) return 0;
+    if (v->dbg_view.n_live == 0) { for (uint32_t i = 0; i < n_want; i++) out_rq[i] = out_pos[i] = 0xFFFFFFFFu; return 0; }  // (as phase A: no view, no launch)
+    HQ_HIP(hipSetDevice(ctx->device));
+    if (!v->d_add.ensure((size_t)n_want * 16 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc wanted ids");
+    uint8_t *dw = v->d_add.as<uint8_t>();
+    HQ_HIP(hipMemcpy(dw, want, (size_t)n_want * 8, hipMemcpyHostToDevice));
+    HQ_HIP(hqk::order_rank_of(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), v->dbg_view.N, v->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(dw), n_want,
+                              reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 8), reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 12), ctx->stream));
+    HQ_HIP(hipStreamSynchronize(ctx->stream));
+    HQ_HIP(hipMemcpy(out_rq, dw + (size_t)n_want * 8, (size_t)n_want * 4, hipMemcpyDeviceToHost));
+    HQ_HIP(hipMemcpy(out_pos, dw + (size_t)n_want * 12, (size_t)n_want * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 void hqtick_debug_set_block_emulation(int on, uint32_t budget) { g_block_emulation = on; if (budget) g_block_budget = budget; }
 void hqtick_debug_last_blocks(uint32_t *n_emulated, uint32_t *n_host) { if (n_emulated) *n_emulated = g_last_blocks_device; if (n_host) *n_host = g_last_blocks_host; }
 

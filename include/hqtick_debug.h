@@ -40,6 +40,27 @@ int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n
 int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels, uint32_t *n_groups, uint32_t shape[4],
                            uint64_t *levels, uint32_t cap_levels, uint32_t *hist, uint32_t cap_groups);
 
+/* The ordered view (csrc/order.hip) by itself, so that tests can compare ALL of it with a plain sort.  GPU only.  None of the three touches a tick:
+ * the view is built on a sub-context of its own, every device array comes back by one copy made here.
+ * _order_view builds the view of ctx's resident ready set (its priority and rq columns as they are, tombstones included) for n_requests requests, through the same
+ * build_view a tick calls.  counts[4] = n_live, n_runs, n_levels, a mask with bit dg set for every digit that got a radix pass (0-7: bytes of ~priority, 8-11: bytes
+ * of rq).  perm[n_live]: the live slots by (rq ascending, priority descending, slot ascending); inv[N] / lrank[N] (N = physical slots; defined at live slots only):
+ * position of the slot in perm / number of distinct priorities above the slot's; run_*[n_runs]: one row per nonempty (rq, priority) pair in perm's order — its request, first
+ * position in perm, level rank, priority.  cap_slots >= N and cap_runs >= n_runs, else HQTICK_E_CAPACITY (counts are filled all the same); any array may be NULL.
+ * Errors are build_view's: a live rq >= n_requests is HQTICK_E_INVALID.  A set without a live slot gives counts of 0 and writes nothing. */
+int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t counts[4], uint32_t *perm, uint32_t *inv, uint32_t *lrank, uint64_t cap_slots, uint32_t *run_rq,
+                            uint32_t *run_start, uint32_t *run_rank, uint64_t *run_prio, uint32_t cap_runs);
+/* k_order_select on the view _order_view last built (HQTICK_E_INVALID if ctx's columns were rebuilt since).  rq_sel_base[Q + 1] (0 first, n_sel last, monotone) and
+ * q_tnc[Q] (n_workers << 16 | tasks per worker, 0 = off) are the plan; a worker-major destination outside its request's range is refused before the launch.
+ * mark_mode 0: select only; 1: consume — RQ_TOMBSTONE at the selected slots, nothing selected; 2: restore — the request ids back, nothing selected; 3: consume and select
+ * in one launch.  The marks go to a COPY of the rq column (fresh for modes 0, 1, 3; as the previous call left it for mode 2): the resident column and the live count stay.
+ * sel_task[n_sel] / sel_rank[n_sel] are pre-filled with all-ones bytes, so a j the kernel left alone reads 2^64 - 1 / 2^32 - 1; rq_after[N] (may be NULL) = the copy
+ * after the launch; err = the kernel's guard word (1: a position outside its request's segment, or a request without runs — that j is not written). */
+int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, const uint32_t *q_tnc, uint32_t n_sel, int mark_mode, uint64_t *sel_task, uint32_t *sel_rank,
+                              uint32_t *rq_after, uint32_t *err);
+/* k_order_rank_of on that view: out_rq[k] / out_pos[k] = request and position in perm of want[k]; 2^32 - 1 twice for an id that is absent or tombstoned. */
+int hqtick_debug_order_rank_of(hqtick_ctx *ctx, const uint64_t *want, uint32_t n_want, uint32_t *out_rq, uint32_t *out_pos);
+
 /* The HOST stages of a tick — create_task_batches + run_scheduling_solver (scheduler/batches.rs:42-181, scheduler/solver.rs:36-483) — on
  * caller-supplied outputs of the GPU scans, so that this logic can be unit-tested on a machine without a GPU.  This is not a tick: the scans
  * (K0/K1/K2), the selection and the mapping have no CPU implementation, and nothing in the product calls this.
