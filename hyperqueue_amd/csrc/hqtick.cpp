@@ -32,6 +32,7 @@
 #include "block_solve.h"
 #include "cluster.h"
 #include "price_dev.h"
+#include "ready.h"
 #ifdef HQTICK_TEST_HOOKS
 #include "price_emul.h"
 #endif
@@ -83,28 +84,21 @@ struct hqtick_ctx {
                                    // the ride-along layout stays the default because the TICK is what counts
     hipEvent_t ev[14] = {};  // (ev[12] / ev[13]: around the kernels of the ordered view)
     std::string err = "";
-    // ready set
-    DevBuf d_tid, d_tprio, d_trq; uint64_t n_ready = 0; bool resident = false;  // n_ready = physical length (tombstones included)
-    DevBuf d_tid2, d_tprio2, d_trq2, d_slice, d_add, d_pre8;   // alternate columns + scratch of the resident deltas (hqtick_ready_*)
-    uint64_t n_live = 0; uint32_t last_n_sel = 0; bool last_consumed = true;
-    uint64_t max_id = 0; bool max_id_valid = false;  // an upper bound of every resident id (the last one after an upload / a rebuild): a batch that starts above it is appended
-    uint32_t n_appends = 0;
-    bool consumed_unconfirmed = false;  // HQTICK_FLAG_CONSUME_IN_TICK: the running tick has written its tombstones; cleared when it returns without an error
+    hqready::ReadySet ready;       // hqtick_upload_ready, hqtick_ready_* (ready.h): the ready set's columns in HBM (resident, or a tick's own), their deltas, the last selection's state
     hqhost::BlockMemo block_memo;  // host class blocks of earlier ticks (host_model.h)
-    uint64_t add_staged_n = 0;  // tasks hqtick_ready_add_stage made room for (0: nothing staged)
     // scans
     DevBuf d_set, d_flags, d_levels, d_nlevels, d_wave_tab, d_hist, d_gkey;
     // the ordered view (order.hip): phase A's general path where the dense (level, request) table does not fit
     DevBuf d_ord_hist, d_ord_tab, d_perm, d_perm2, d_ord_tiles, d_inv; PinBuf h_ord, h_ordh;
     bool force_ordered = false;   // HQTICK_ORDERED_VIEW=1 (tests): every tick with a ready set takes the view
     bool ordered_sticky = false;  // the last dense attempt did not fit: go straight to the view until a view fits the dense caps again
-    bool last_ordered = false;    // the pending selection (last_valid) is one of the view: consume / restore replay it with order_select
+    bool last_ordered = false;    // the pending selection (ready.selection_valid()) is one of the view: consume / restore replay it with order_select
     hqk::OrderSelect last_os{};   // ... its tables (HBM copy of the plan, the permutation)
     uint32_t dbg_order_runs = 0, dbg_order_levels = 0; bool dbg_order = false; double dbg_order_us = 0;  // hqtick_debug_last_order
     uint32_t dbg_order_passes = 0;  // bit dg: the last view built on these buffers ran a pass on digit dg (hqtick_debug_order_view)
     uint32_t dbg_scan_L = 0, dbg_scan_G = 0, dbg_scan_shape[4] = {0, 0, 0, 0}; bool dbg_scan = false, dbg_census = false;  // hqtick_debug_last_scan: what the last dense scan (phase_a) / census (census_resident, on the query sub-context) left in h_a, h_levels, h_lv
     uint32_t lv_seq = 0; bool set_clean = false; bool no_spec_scan = getenv("HQTICK_NO_SPEC_SCAN") != nullptr; bool levels_valid = false; uint32_t cached_L = 0; std::vector<uint64_t> h_levels; bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))  // level table of the previous tick (re-validated by K1 every tick)
-    PinBuf h_up, h_up2, h_q, h_a, h_plan, h_rec, h_sinkhdr, h_add, h_addp, h_retr, h_blk, h_k5a, h_lv;   // (h_lv: the level table as k_sort_levels writes it)
+    PinBuf h_up, h_up2, h_q, h_a, h_plan, h_rec, h_sinkhdr, h_retr, h_blk, h_k5a, h_lv;   // (h_lv: the level table as k_sort_levels writes it)
     PinBuf h_blkprof; uint32_t n_blkprof = 0; bool block_profile = false;
     hqprice::DeviceSweeper *pricer = nullptr;  // k_price_sweep: the block sweeps of the coupled placement (csrc/price.hip); HQTICK_PRICE=0 keeps coupled ticks on the host search
     uint32_t block_budget = 4096, block_min_classes = 12;  // k_block_solve: search steps per class before the host solver takes it; classes below which the host solves alone
@@ -129,12 +123,13 @@ struct hqtick_ctx {
     uint32_t shard_index = 0, shard_count = 1;       // hqtick_set_shard
     void *sink = nullptr; size_t sink_bytes = 0;      // hqtick_set_record_sink (device memory)
     // launch state of the last tick (hqtick_time_kernel re-launches K1 / K4 on it)
-    hqk::WaveGeom last_geom{}; uint32_t last_L = 0, last_Q = 0, last_G = 0; size_t last_tb = 0, last_plan_bytes = 0, last_hist_off = 0; bool last_valid = false;
+    hqk::WaveGeom last_geom{}; uint32_t last_L = 0, last_Q = 0, last_G = 0; size_t last_tb = 0, last_plan_bytes = 0, last_hist_off = 0;
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
     hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     hqtick_ctx *vctx = nullptr;  // hqtick_debug_order_view's private sub-context (test library only); the view it holds is described by its dbg_view
     struct { bool valid = false; const void *ids = nullptr; uint64_t N = 0; uint32_t Q = 0, n_live = 0; bool rq_copy = false; std::vector<uint32_t> run_off, run_start, run_rank; } dbg_view;
+    DevBuf d_dbg_rq, d_dbg_want;  // ... and its scratch: the copy of the request column hqtick_debug_order_select marks, the ids hqtick_debug_order_rank_of looks up
     ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
     // sharded placement solve: the ranks split the coupled solve's price sweeps and the separable solve's class blocks, one small all-gather of host
     // buffers per sweep / per launch — through the host's callback (hqtick_set_exchange) or the library's own RCCL communicator
@@ -252,6 +247,10 @@ int upload_tables(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const u
 
 // ... or from HBM, where a worker set is resident (hqcluster::WorkerSet::tables)
 int cluster_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->ws.err; return rc; }
+
+// the ready set (hqready::ReadySet, ready.h): what it is given of the context (ev[11]: the completion event an append's dispatch carries), and its errors
+hqready::Env ready_env(hqtick_ctx *ctx) { return hqready::Env{ctx->device, ctx->stream, ctx->ev[11], ctx->wait_on_kernel}; }
+int ready_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->ready.err; return rc; }
 
 // K2 on a worker set, synchronous (used for the fake workers of hqtick_query); results land in pinned memory
 int eval_workers_sync(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const uint64_t *total, const uint64_t *free_, const int64_t *rem, WorkerEval *out) {
@@ -416,7 +415,7 @@ int build_view(hqtick_ctx *ctx, hqtick_ctx *b, const uint64_t *prio, const uint3
 // Phase A on the ordered view: K2 as its own launch, the view, the positions of the Retracting tasks (the same layout of h_retr as k_rank_of's).
 int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc, const std::function<void()> *while_gpu_runs) {
     const uint32_t W = s->n_workers, R = s->n_resources, Q = s->n_requests;
-    const uint64_t N = ctx->n_ready;
+    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
     const uint32_t nvs = Q ? s->rq_variant_off[Q] : 0;
     const size_t nwv = (size_t)W * nvs, o_tmc = 16, o_fl = o_tmc + nwv * 4, bytes = o_fl + nwv + 16;
     if (!ctx->h_a.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc phase A");
@@ -428,7 +427,7 @@ int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, S
     HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream));
     ev->flags = h + o_fl; ev->tmc = reinterpret_cast<const uint32_t *>(h + o_tmc);
     ctx->levels_valid = false;  // (the dense level table is rediscovered when a tick fits the dense caps again)
-    if ((rc = build_view(ctx, ctx, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, ctx->stream, sc, while_gpu_runs))) return rc;
+    if ((rc = build_view(ctx, ctx, cols.prio, cols.rq, N, Q, ctx->stream, sc, while_gpu_runs))) return rc;
     if (!ctx->force_ordered && sc->L <= hqk::MAX_LEVELS && (uint64_t)sc->L * Q <= hqk::MAX_GROUPS) ctx->ordered_sticky = false;  // the next tick fits the dense scan again
     if (s->n_retracting) {  // where do the Retracting tasks sit in their queues?  (mapping.rs:66-80 treats them apart)
         const uint32_t nr = s->n_retracting;
@@ -437,7 +436,7 @@ int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, S
         uint8_t *rd = ctx->h_retr.dev<uint8_t>();
         if (sc->run_cnt.empty()) { uint32_t *k = reinterpret_cast<uint32_t *>(ctx->h_retr.as<uint8_t>() + (size_t)nr * 8); for (uint32_t i = 0; i < nr; i++) k[i] = 0xFFFFFFFFu; }
         else {
-            HQ_HIP(hqk::order_rank_of(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, ctx->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(rd), nr,
+            HQ_HIP(hqk::order_rank_of(cols.id, cols.rq, N, ctx->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(rd), nr,
                                       reinterpret_cast<uint32_t *>(rd + (size_t)nr * 8), reinterpret_cast<uint32_t *>(rd + (size_t)nr * 12), ctx->stream));
             HQ_HIP(hipStreamSynchronize(ctx->stream));
         }
@@ -446,11 +445,11 @@ int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, S
 }
 
 // GPU phase A: K2 on the real workers, level table (cached across ticks, re-validated by K1), K1 + K1b on the ready set in
-// ctx->d_t*.  One stream synchronisation in the steady state.
+// ctx->ready's columns.  One stream synchronisation in the steady state.
 // `while_gpu_runs` (may be null) is host work that needs only the ADDRESSES of K2's output, run between the launches and the sync.
 int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc, const std::function<void()> *while_gpu_runs = nullptr) {
     const uint32_t W = s->n_workers, R = s->n_resources, Q = s->n_requests;
-    const uint64_t N = ctx->n_ready;
+    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
     sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
     runs_from_hist(*sc);  // (no run until the scan has counted)
     if (!ctx->d_set.ensure((size_t)(hqk::PRIO_SET_CAP + hqk::MAX_LEVELS) * 8) || !ctx->h_lv.ensure((size_t)(hqk::MAX_LEVELS + 4) * 8) || !ctx->d_flags.ensure(64) || !ctx->d_levels.ensure((size_t)(hqk::MAX_LEVELS + 2) * 8) || !ctx->d_nlevels.ensure(64))   // (a 40-byte head: count + the first four levels, kernels.hip: k_sort_levels)
@@ -476,7 +475,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
                 ctx->set_clean = false;   // until this tick has seen the discovery's result
                 const bool time_k0 = ctx->timing;   // (two marker packets around K0: only when every kernel is timed)
                 if (time_k0) HQ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-                HQ_HIP(hqk::distinct_priorities(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, ctx->d_set.as<uint64_t>(), ctx->d_flags.as<uint32_t>(), ctx->stream));
+                HQ_HIP(hqk::distinct_priorities(cols.prio, cols.rq, N, ctx->d_set.as<uint64_t>(), ctx->d_flags.as<uint32_t>(), ctx->stream));
                 levels_fresh = true;
                 if (time_k0) HQ_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
                 // (the sort kernel writes count, flags and the table straight into pinned memory and clears the flag words for the scan: one synchronisation, no copy)
@@ -541,7 +540,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
             if (!ctx->d_wave_tab.ensure((size_t)g.tab_stride * sc->G * 4) || !ctx->d_gkey.ensure(N * 2 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc histogram");
             if (ctx->timing || ctx->timing_k1) hqk::time_next_launch(ctx->ev[2], ctx->ev[3]);
             if (ctx->k2_own_stream) HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream2));
-            HQ_HIP_TIMED(hqk::level_hist(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, ctx->d_levels.as<uint64_t>(), ctx->h_levels.data(), L, Q, g, ctx->d_wave_tab.as<uint32_t>(),
+            HQ_HIP_TIMED(hqk::level_hist(cols.prio, cols.rq, N, ctx->d_levels.as<uint64_t>(), ctx->h_levels.data(), L, Q, g, ctx->d_wave_tab.as<uint32_t>(),
                                    ctx->d_gkey.as<uint16_t>(), ctx->d_flags.as<uint32_t>() + 2, ctx->k2_on_hist ? &wea : nullptr, ctx->stream, spec ? ctx->d_nlevels.as<uint32_t>() : nullptr));
             hqk::time_next_launch((ctx->timing && !spec) ? ctx->ev[0] : nullptr, ctx->ev[8]);  // ev[8]: K1b's completion — what the host waits on below
             HQ_HIP_LAST(hqk::scan_waves(ctx->d_wave_tab.as<uint32_t>(), g, sc->G, reinterpret_cast<uint32_t *>(hd + o_hist), ctx->d_flags.as<uint32_t>() + 2,
@@ -552,7 +551,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
                 if (!ctx->h_retr.ensure((size_t)nr * 16 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc retracting");
                 memcpy(ctx->h_retr.p, s->retracting_task, (size_t)nr * 8);
                 uint8_t *rd = ctx->h_retr.dev<uint8_t>();
-                HQ_HIP(hqk::rank_of(ctx->d_tid.as<uint64_t>(), ctx->d_gkey.as<uint16_t>(), N, ctx->d_wave_tab.as<uint32_t>(), g, reinterpret_cast<const uint64_t *>(rd), nr,
+                HQ_HIP(hqk::rank_of(cols.id, ctx->d_gkey.as<uint16_t>(), N, ctx->d_wave_tab.as<uint32_t>(), g, reinterpret_cast<const uint64_t *>(rd), nr,
                                     reinterpret_cast<uint32_t *>(rd + (size_t)nr * 8), reinterpret_cast<uint32_t *>(rd + (size_t)nr * 12), ctx->stream));
             }
         } else {
@@ -789,16 +788,10 @@ struct TickRun {
     // the ready set: uploaded with the snapshot, or already resident
     int load_ready_set() {
         if (!use_resident) {
-            uint64_t N = s->n_ready;
-            if (!ctx->d_tid.ensure(N * 8 + 8) || !ctx->d_tprio.ensure(N * 8 + 8) || !ctx->d_trq.ensure(N * 4 + 8)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ready set");
-            if (N) {
-                HQ_HIP(hipMemcpyAsync(ctx->d_tid.p, s->task_id, N * 8, hipMemcpyHostToDevice, ctx->stream));
-                HQ_HIP(hipMemcpyAsync(ctx->d_tprio.p, s->task_priority, N * 8, hipMemcpyHostToDevice, ctx->stream));
-                HQ_HIP(hipMemcpyAsync(ctx->d_trq.p, s->task_rq, N * 4, hipMemcpyHostToDevice, ctx->stream));
-            }
-            ctx->n_ready = N; ctx->resident = false; ctx->levels_valid = false;
-        } else if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "hqtick_run_resident without hqtick_upload_ready");
-        N = ctx->n_ready;
+            if (int rc = ready_fail(ctx, ctx->ready.load(ctx->stream, s, true))) return rc;
+            ctx->levels_valid = false;
+        } else if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "hqtick_run_resident without hqtick_upload_ready");
+        N = ctx->ready.cols().n;
         return 0;
     }
 
@@ -818,7 +811,7 @@ struct TickRun {
         ps.key_seg.assign(nkeys, 0); ps.key_sum.assign(nkeys, 0); ps.key_rq.assign(nkeys, 0); ps.key_var_w.assign((nkeys + 3) / 4 + 1, 0);
         ps.key_ord_off.assign(nkeys + 1, 0); ps.key_t_off.assign(nkeys + 1, 0); ps.key_bits_off.assign(nkeys + 1, 0);
         const bool by_class = cnt.by_class && cnt.wclass.size() == W && cnt.key_col.size() == nkeys;
-        ctx->last_valid = false;  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
+        ctx->ready.selection_void();  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
         {   // the big tables live at the head of the pinned plan buffer; everything else of the plan (phase_c) is a few KB behind them
             ps.plan_head_words = (size_t)nkeys * W * 2 + (size_t)Q * W;
             size_t n_cnt0 = 0; for (uint32_t k = 0; k < nkeys; k++) n_cnt0 += cnt.key_size(k);
@@ -1198,32 +1191,33 @@ struct TickRun {
             mk.n_pfq = n_pfq; mk.pfq_src = d + o_pqs; mk.pfq_size = d + o_pqz; mk.pfl_j = d + o_pflj; mk.out_off = d + o_out;
             uint32_t *flags = reinterpret_cast<uint32_t *>(ctx->h_rec.as<uint8_t>() + o_fl);
             flags[0] = 0;  // K5b reports a capacity overflow straight into this pinned word
-            ctx->last_n_sel = n_sel; ctx->last_consumed = false;
+            ctx->ready.selected(n_sel);  // (of the plan whose launch state is recorded below)
+            const hqready::Cols cols = ctx->ready.cols();
             const bool consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;  // K4 writes the tombstones of what it selects
             if (consume_in_tick && ctx->asg.on && s->n_retracting) {  // only the redirects of Retracting tasks still look their request id up after K4 has tombstoned it (4 B per slot, device to device)
                 uint32_t *saved = ctx->asg.saved_rq(N);
-                if (!saved) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids");
-                HQ_HIP(hipMemcpyAsync(saved, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                if (!saved) { ctx->ready.selection_void(); return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids"); }
+                HQ_HIP(hipMemcpyAsync(saved, cols.rq, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
             }
-            ctx->last_geom = sc.geom; ctx->last_L = L; ctx->last_Q = Q; ctx->last_G = sc.G; ctx->last_tb = o_tb; ctx->last_plan_bytes = plan_words * 4; ctx->last_valid = true;
+            ctx->last_geom = sc.geom; ctx->last_L = L; ctx->last_Q = Q; ctx->last_G = sc.G; ctx->last_tb = o_tb; ctx->last_plan_bytes = plan_words * 4;
             ctx->last_ordered = sc.ordered;
             if (sc.ordered) {  // the plan into HBM, then K4 on the view (order.hip)
                 HQ_HIP(hqk::copy_pinned_to_hbm(ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4, ctx->stream));
                 hqk::OrderSelect os{};
-                os.task_id = ctx->d_tid.as<uint64_t>(); os.perm = ctx->d_perm.as<uint32_t>(); os.n_live = sc.run_cnt.empty() ? 0u : sc.run_start.back() + sc.run_cnt.back(); os.Q = Q;
+                os.task_id = cols.id; os.perm = ctx->d_perm.as<uint32_t>(); os.n_live = sc.run_cnt.empty() ? 0u : sc.run_start.back() + sc.run_cnt.back(); os.Q = Q;
                 os.n_runs = (uint32_t)sc.run_cnt.size(); os.rq_sel_base = d + o_base; os.run_off = d + o_roff; os.run_start = d + o_rst; os.run_rank = d + o_rrk; os.q_tnc = d + o_qtnc;
                 os.sel_task = ctx->d_sel_task.as<uint64_t>(); os.sel_rank = ctx->d_sel_level.as<uint32_t>(); os.err = ctx->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2;
                 ctx->last_os = os;  // (what hqtick_ready_consume_last and the restore of HQTICK_FLAG_CONSUME_IN_TICK replay)
-                if (consume_in_tick) { os.mark_rq = ctx->d_trq.as<uint32_t>(); os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 1; }
+                if (consume_in_tick) { os.mark_rq = cols.rq; os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 1; }
                 if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
                 HQ_HIP_TIMED(hqk::order_select(os, n_sel, ctx->stream));
             } else {
             if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
-            HQ_HIP_TIMED(hqk::select_scatter(ctx->d_tid.as<uint64_t>(), ctx->d_gkey.as<uint16_t>(), N, Q, sc.G, sc.geom, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + o_tb,
+            HQ_HIP_TIMED(hqk::select_scatter(cols.id, ctx->d_gkey.as<uint16_t>(), N, Q, sc.G, sc.geom, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + o_tb,
                                 d + o_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4,
-                                consume_in_tick ? ctx->d_trq.as<uint32_t>() : nullptr, ctx->stream, consume_in_tick ? 1u : 0u));
+                                consume_in_tick ? cols.rq : nullptr, ctx->stream, consume_in_tick ? 1u : 0u));
             }
-            if (consume_in_tick) { ctx->n_live -= n_sel; ctx->last_consumed = true; ctx->consumed_unconfirmed = true; }  // (confirmed when the tick returns without an error: run_tick)
+            if (consume_in_tick) ctx->ready.consumed_in_tick();  // (confirmed when the tick returns without an error: run_tick)
             if (!sweep_launched && n_tr < nkeys) {
                 if (ctx->timing) hqk::time_next_launch(ctx->ev[1], ctx->ev[6]);
                 HQ_HIP_TIMED(hqk::sweep_bits(mk, max_count, max_nk, ctx->stream));
@@ -1284,7 +1278,7 @@ struct TickRun {
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[1], ctx->ev[6]); if (us_ >= 0) ctx->stats.sweep_us = us_; }
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[7], ctx->ev[11]); if (us_ >= 0) ctx->stats.other_us = us_; }
         }
-        if (!n_sel) { ctx->last_n_sel = 0; ctx->last_consumed = true; }
+        if (!n_sel) ctx->ready.selected(0);
         if (!n_sel && ctx->sink) {  // nothing placed: still publish an empty, well-formed sink
             if (hqtick_sink_bytes(W, 0) > ctx->sink_bytes) return fail(ctx, HQTICK_E_CAPACITY, "record sink too small for this tick");
             std::vector<uint32_t> &hdr = ps.sink_hdr; hdr.assign(4 + W + 1, 0);
@@ -1412,13 +1406,15 @@ struct TickRun {
 // ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12): what hqasg::Ledger (ledger.h) is given of the context
 bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm; }  // (a record sink alone is one scheduler's output path, not a replica)
 hqasg::Env ledger_env(hqtick_ctx *ctx) {
-    return hqasg::Env{ctx->device, ctx->stream, ctx->ws.rows(), ctx->ws.W(), ctx->ws.R(), ctx->d_tid.as<uint64_t>(), ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready,
+    const hqready::Cols c = ctx->ready.cols();
+    return hqasg::Env{ctx->device, ctx->stream, ctx->ws.rows(), ctx->ws.W(), ctx->ws.R(), c.id, c.prio, c.rq, c.n,
                       ctx->d_levels.as<uint64_t>(), &ctx->ws.ids(), ctx->ws.flags(), ctx->ws.free_rows()};
 }
 int ledger_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->asg.err; return rc; }
 // a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
-// (an add, a remove, a compaction, a graph call, an upload) clears last_valid or sets last_consumed — and with it the placement is dropped too
-bool ledger_pending_live(hqtick_ctx *ctx) { return ctx->asg.pending_live(ctx->last_valid && !ctx->last_consumed); }
+// (an add, a remove, a compaction, a graph call, an upload) ends ready.selection_live() — and with it the placement is dropped too: Ledger::pending is read nowhere
+// but here, so the ready set need not know the ledger to clear it
+bool ledger_pending_live(hqtick_ctx *ctx) { return ctx->asg.pending_live(ctx->ready.selection_live()); }
 int ledger_guard(hqtick_ctx *ctx) {
     if (ctx->asg.on && ledger_pending_live(ctx)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the last tick's placement is pending (hqtick_ready_consume_last first)");
     return 0;
@@ -1448,8 +1444,8 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         TickRun run(ctx, s, out, use_resident);
         rc = run.run();
     }
-    if (ctx->consumed_unconfirmed) {  // HQTICK_FLAG_CONSUME_IN_TICK: the selection has written its tombstones
-        ctx->consumed_unconfirmed = false;
+    if (ctx->ready.unconfirmed()) {  // HQTICK_FLAG_CONSUME_IN_TICK: the selection has written its tombstones
+        ctx->ready.confirm();
         if (rc < 0) {
             // ... and the tick did not come back (a record sink too small, a mapping capacity exceeded, a failed exchange: errors a host can recover from).  What it took
             // goes back: this tick's K1 left a valid group key on every task that was live, so the tombstones K4 wrote are recognisable and their request ids
@@ -1457,23 +1453,23 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             const std::string why = ctx->err;
             bool restored = false;
             const bool synced = hipStreamSynchronize(ctx->stream) == hipSuccess;
-            if (synced && ctx->last_valid && ctx->last_ordered) {  // the view: the same selection writes the request ids back
+            const hqready::Cols cols = ctx->ready.cols();
+            const uint32_t n_sel = ctx->ready.selected_count();
+            if (synced && ctx->ready.selection_valid() && ctx->last_ordered) {  // the view: the same selection writes the request ids back
                 hqk::OrderSelect os = ctx->last_os;
-                os.mark_rq = ctx->d_trq.as<uint32_t>(); os.mark_value = 0; os.mark_and_select = 0;
-                if (hqk::order_select(os, ctx->last_n_sel, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess) { ctx->n_live += ctx->last_n_sel; restored = true; }
-            } else if (synced && ctx->last_valid && !ctx->last_ordered && ctx->last_Q && ctx->h_q.ensure(64)) {
+                os.mark_rq = cols.rq; os.mark_value = 0; os.mark_and_select = 0;
+                restored = hqk::order_select(os, n_sel, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
+            } else if (synced && ctx->ready.selection_valid() && !ctx->last_ordered && ctx->last_Q && ctx->h_q.ensure(64)) {
                 uint32_t *cntp = ctx->h_q.as<uint32_t>();
                 cntp[0] = 0;
-                if (hqk::ready_restore_consumed(ctx->d_gkey.as<uint16_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready, ctx->last_Q, ctx->h_q.dev<uint32_t>(), ctx->stream) == hipSuccess &&
-                    hipStreamSynchronize(ctx->stream) == hipSuccess && cntp[0] <= ctx->last_n_sel) {
-                    ctx->n_live += ctx->last_n_sel;   // (what the tick had subtracted when it launched the selection; the kernel may have run for any part of it)
-                    restored = true;
-                }
+                restored = hqk::ready_restore_consumed(ctx->d_gkey.as<uint16_t>(), cols.rq, cols.n, ctx->last_Q, ctx->h_q.dev<uint32_t>(), ctx->stream) == hipSuccess &&
+                           hipStreamSynchronize(ctx->stream) == hipSuccess && cntp[0] <= n_sel;
             }
-            ctx->last_valid = false; ctx->last_consumed = true; ctx->last_n_sel = 0;   // nothing of this tick is left to consume
+            // nothing of this tick is left to consume; a restore gives the count back what the tick had subtracted when it launched the selection (the kernel may have run for any part of it)
+            if (restored) ctx->ready.put_back(); else ctx->ready.lost();
             ctx->err = why;
             if (restored) ctx->err += " (HQTICK_FLAG_CONSUME_IN_TICK: what the tick had taken is back in the resident ready set)";
-            else { ctx->resident = false; ctx->err += " (HQTICK_FLAG_CONSUME_IN_TICK: the tick had already taken its tasks and they could not be put back; the resident ready set is dropped, upload it again)"; }
+            else { ctx->err += " (HQTICK_FLAG_CONSUME_IN_TICK: the tick had already taken its tasks and they could not be put back; the resident ready set is dropped, upload it again)"; }
         }
     }
     if (rc >= 0 && retr_resident) ctx->retr.apply_tick(s->worker_id, s->n_workers, ctx->retract_off, ctx->retract_task, ctx->red_task, ctx->red_worker, ctx->red_variant, ctx->red_kind);
@@ -1543,11 +1539,12 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
     delete ctx->pricer; ctx->pricer = nullptr;
-    DevBuf *bufs[] = {&ctx->d_tid, &ctx->d_tprio, &ctx->d_trq, &ctx->d_set, &ctx->d_flags, &ctx->d_levels, &ctx->d_nlevels, &ctx->d_wave_tab, &ctx->d_hist,
+    DevBuf *bufs[] = {&ctx->d_set, &ctx->d_flags, &ctx->d_levels, &ctx->d_nlevels, &ctx->d_wave_tab, &ctx->d_hist,
                       &ctx->d_up, &ctx->d_vflags, &ctx->d_vtmc, &ctx->d_sel_task, &ctx->d_gkey,
-                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_tid2, &ctx->d_tprio2, &ctx->d_trq2, &ctx->d_slice, &ctx->d_add, &ctx->d_pre8, &ctx->d_blk,
+                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_blk, &ctx->d_dbg_rq, &ctx->d_dbg_want,
                       &ctx->d_ord_hist, &ctx->d_ord_tab, &ctx->d_perm, &ctx->d_perm2, &ctx->d_ord_tiles, &ctx->d_inv};
     for (DevBuf *b : bufs) b->release();
+    ctx->ready.release();
     ctx->ws.release();
     if (ctx->qctx) { hqtick_destroy(ctx->qctx); ctx->qctx = nullptr; }
     if (ctx->vctx) { hqtick_destroy(ctx->vctx); ctx->vctx = nullptr; }
@@ -1555,7 +1552,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     if (ctx->comm) { rccl_destroy_comm(ctx); }
     ctx->graph.release();
     ctx->asg.release_all();
-    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_a.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_add.release(); ctx->h_addp.release(); ctx->h_retr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release(); ctx->h_lv.release(); ctx->h_ord.release(); ctx->h_ordh.release();
+    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_a.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_retr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release(); ctx->h_lv.release(); ctx->h_ord.release(); ctx->h_ordh.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1575,29 +1572,8 @@ int hqtick_upload_ready(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, co
     if (sorted) for (uint64_t i = 1; i < n; i++) if (task_id[i - 1] >= task_id[i]) return fail(ctx, HQTICK_E_INVALID, "ready set not sorted by task id");
     for (uint64_t i = 0; i < n; i++) if (task_rq[i] == 0xFFFFFFFFu) return fail(ctx, HQTICK_E_INVALID, "request id 0xFFFFFFFF is reserved");
     HQ_HIP(hipSetDevice(ctx->device));
-    ctx->resident = false;  // whatever was resident is being overwritten: only a complete upload makes the set usable again
-    uint64_t n_pow2 = 1; while (n_pow2 < n) n_pow2 <<= 1;
-    const uint64_t cap = sorted ? n : n_pow2;
-    if (!ctx->d_tid.ensure(cap * 8 + 8) || !ctx->d_tprio.ensure(cap * 8 + 8) || !ctx->d_trq.ensure(cap * 4 + 8)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ready set");
-    if (n) {
-        // blocking copies: the caller's columns are pageable memory, and this is the one call whose result every later tick trusts (a level table built from
-        // a column that was still arriving would list whatever the buffer held before; seen once under rocprofv3 with the asynchronous form)
-        HQ_HIP(hipMemcpy(ctx->d_tid.p, task_id, n * 8, hipMemcpyHostToDevice));
-        HQ_HIP(hipMemcpy(ctx->d_tprio.p, task_priority, n * 8, hipMemcpyHostToDevice));
-        HQ_HIP(hipMemcpy(ctx->d_trq.p, task_rq, n * 4, hipMemcpyHostToDevice));
-        if (!sorted) {  // the host handed over its queues in whatever order it walked them: sort by id on the device, once
-            if (!ctx->h_q.ensure(64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-            uint32_t *flag = ctx->h_q.as<uint32_t>(); flag[0] = 0;
-            HQ_HIP(hqk::sort_ready(ctx->d_tid.as<uint64_t>(), ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), n, n_pow2, ctx->h_q.dev<uint32_t>(), ctx->stream));
-            HQ_HIP(hipStreamSynchronize(ctx->stream));
-            if (flag[0]) return fail(ctx, HQTICK_E_INVALID, "ready set holds a task id twice (or the id 2^64 - 1)");
-        } else {
-            HQ_HIP(hipStreamSynchronize(ctx->stream));
-        }
-    }
-    ctx->n_ready = n; ctx->n_live = n; ctx->resident = true; ctx->levels_valid = false; ctx->last_valid = false; ctx->last_consumed = true; ctx->asg.pending = false;
-    ctx->max_id = 0; ctx->max_id_valid = true;
-    if (sorted) { if (n) ctx->max_id = task_id[n - 1]; } else for (uint64_t i = 0; i < n; i++) ctx->max_id = std::max(ctx->max_id, task_id[i]);
+    if (int rc = ready_fail(ctx, ctx->ready.upload(ready_env(ctx), n, task_id, task_priority, task_rq, sorted != 0))) return rc;
+    ctx->levels_valid = false;
     return 0;
 }
 
@@ -1606,82 +1582,12 @@ int hqtick_run_resident(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, hqtick
     return run_tick(ctx, snapshot, out, true);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------- resident ready-set deltas (f1)
-namespace {
-// Drops tombstones and merges `n_add` new tasks (device arrays, ids ascending) into fresh columns; swaps them in.
-bool append_enabled() { static const bool on = !(getenv("HQTICK_APPEND") && atoi(getenv("HQTICK_APPEND")) == 0); return on; }
-// `first_id` / `last_id`: the batch's smallest and largest id when the caller knows them on the host (0 / 0: it does not — the device graph's releases).
-int rebuild_ready(hqtick_ctx *ctx, const uint64_t *aid, const uint64_t *aprio, const uint32_t *arq, uint32_t n_add, uint64_t first_id = 0, uint64_t last_id = 0) {
-    const uint64_t N = ctx->n_ready, new_n = ctx->n_live + n_add;
-    if (append_enabled() && N > 0 && n_add > 0 && last_id >= first_id && first_id > 0 && ctx->max_id_valid && first_id > ctx->max_id &&
-        ctx->d_tid.cap >= (N + n_add) * 8 + 8 && ctx->d_tprio.cap >= (N + n_add) * 8 + 8 && ctx->d_trq.cap >= (N + n_add) * 4 + 8) {
-        // Fresh ids behind everything resident, and room at the tail: ONE kernel instead of four (the columns are not re-written; what the ticks consumed stays as
-        // tombstones until hqtick_ready_consume_last / _compact find more tombstones than tasks).  The steady loop's add: 136 -> ~50 us.
-        if (!ctx->h_q.ensure(64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-        uint32_t *flag = ctx->h_q.as<uint32_t>(); flag[0] = 0;
-        bool waits_on_kernel = false;
-        hqk::time_next_launch(nullptr, ctx->ev[11]);
-        HQ_HIP_LAST(hqk::ready_append(aid, aprio, arq, n_add, ctx->max_id, ctx->d_tid.as<uint64_t>() + N, ctx->d_tprio.as<uint64_t>() + N, ctx->d_trq.as<uint32_t>() + N, ctx->h_q.dev<uint32_t>(), ctx->stream), waits_on_kernel);
-        if (waits_on_kernel) HQ_HIP(hipEventSynchronize(ctx->ev[11])); else HQ_HIP(hipStreamSynchronize(ctx->stream));  // (the dispatch's own completion signal: HQ_HIP_LAST)
-        if (flag[0] & 4u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: a task id is already in the ready set");
-        if (flag[0] & 8u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: ids not strictly ascending");
-        if (flag[0] & 16u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: request id 0xFFFFFFFF is reserved");
-        ctx->n_ready = N + n_add; ctx->n_live += n_add; ctx->last_valid = false; ctx->last_consumed = true; ctx->max_id = last_id; ctx->n_appends++; ctx->asg.pending = false;
-        if (ctx->n_ready > 4096 && ctx->n_live * 2 < ctx->n_ready) return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0);  // (see hqtick_ready_add_packed)
-        return 0;
-    }
-    // (a rebuild leaves room behind the columns: the next fresh batches are appended)
-    const uint64_t room = new_n + std::max<uint64_t>(new_n, 4096);
-    if (!ctx->d_tid2.ensure(room * 8 + 8) || !ctx->d_tprio2.ensure(room * 8 + 8) || !ctx->d_trq2.ensure(room * 4 + 8)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ready set (rebuild)");
-    uint64_t first_batch_last_id = 0;
-    if (N == 0) {  // nothing resident: the batch becomes the ready set — through the same validation as an appended one (ascending ids, no reserved request id:
-                   // a refused batch leaves the set as it was, here: empty), written by the kernel that checks it
-        if (n_add) {
-            if (!ctx->h_q.ensure(64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-            uint32_t *flag = ctx->h_q.as<uint32_t>(); flag[0] = 0;
-            HQ_HIP(hqk::ready_append(aid, aprio, arq, n_add, 0xFFFFFFFFFFFFFFFFull, ctx->d_tid2.as<uint64_t>(), ctx->d_tprio2.as<uint64_t>(), ctx->d_trq2.as<uint32_t>(), ctx->h_q.dev<uint32_t>(), ctx->stream));
-            uint64_t *last_back = reinterpret_cast<uint64_t *>(ctx->h_q.as<unsigned char>() + 16);
-            HQ_HIP(hipMemcpyAsync(last_back, ctx->d_tid2.as<uint64_t>() + (n_add - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-            // (the batch came through the pinned staging buffer: the caller may stage the NEXT batch into it as soon as this call returns, so the kernel must be over by then)
-            HQ_HIP(hipStreamSynchronize(ctx->stream));
-            if (flag[0] & 8u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: ids not strictly ascending");
-            if (flag[0] & 16u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: request id 0xFFFFFFFF is reserved");
-            first_batch_last_id = *last_back;
-        }
-    } else {
-        const uint32_t n_slices = (uint32_t)((N + 255) / 256), stride = (n_slices + 15u) & ~15u;
-        if (!ctx->d_slice.ensure((size_t)stride * 4 + 64) || !ctx->h_q.ensure(64) || !ctx->d_pre8.ensure(N + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc slice table");
-        uint32_t *flag = ctx->h_q.as<uint32_t>(); flag[0] = 0; flag[1] = 0;
-        hqk::WaveGeom g{256, n_slices, 4, stride};
-        HQ_HIP(hqk::ready_live_count(ctx->d_trq.as<uint32_t>(), N, ctx->d_slice.as<uint32_t>(), ctx->stream));
-        HQ_HIP(hqk::scan_waves(ctx->d_slice.as<uint32_t>(), g, 1, ctx->h_q.dev<uint32_t>() + 1, nullptr, nullptr, ctx->stream));
-        HQ_HIP(hqk::ready_rebuild(ctx->d_tid.as<uint64_t>(), ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, (uint32_t)ctx->n_live, ctx->d_slice.as<uint32_t>(), aid, aprio, arq, n_add,
-                                  ctx->d_tid2.as<uint64_t>(), ctx->d_tprio2.as<uint64_t>(), ctx->d_trq2.as<uint32_t>(), ctx->d_pre8.as<uint8_t>(), ctx->h_q.dev<uint32_t>(), ctx->stream));
-        uint64_t *last_back = reinterpret_cast<uint64_t *>(ctx->h_q.as<unsigned char>() + 16);  // the new last id comes back with the flags: the bound appends are decided by
-        if (new_n) HQ_HIP(hipMemcpyAsync(last_back, ctx->d_tid2.as<uint64_t>() + (new_n - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        if (flag[1] != ctx->n_live) return fail(ctx, HQTICK_E_DEVICE, "resident ready set: live-task count out of sync");
-        if (flag[0] & 4u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: a task id is already in the ready set");
-        if (flag[0] & 8u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: ids not strictly ascending");
-        if (flag[0] & 16u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: request id 0xFFFFFFFF is reserved");
-        if (new_n) { ctx->max_id = *last_back; ctx->max_id_valid = true; }  // (only of columns that are swapped in: a refused batch leaves the bound as it was)
-    }
-    std::swap(ctx->d_tid, ctx->d_tid2); std::swap(ctx->d_tprio, ctx->d_tprio2); std::swap(ctx->d_trq, ctx->d_trq2);
-    ctx->n_ready = new_n; ctx->n_live = new_n; ctx->last_valid = false; ctx->last_consumed = true; ctx->asg.pending = false;
-    if (N == 0 && n_add) { ctx->max_id = first_batch_last_id; ctx->max_id_valid = true; }  // (the validated batch's own last id, read back from the device: the bound later appends are decided by)
-    return 0;
-}
-}  // namespace
-
-extern "C" {
-
-uint64_t hqtick_ready_count(const hqtick_ctx *ctx) { return ctx && ctx->resident ? ctx->n_live : 0; }
+// ---- the resident ready set's deltas (f1): arguments validated here, the operations are hqready::ReadySet's (ready.h) ----
+uint64_t hqtick_ready_count(const hqtick_ctx *ctx) { return ctx && ctx->ready.resident() ? ctx->ready.live() : 0; }
 
 int hqtick_ready_consume_last(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
     if (ledger_pending_live(ctx)) {  // the last tick's placement enters the assignment ledger (before the selection's request ids become tombstones)
         HQ_HIP(hipSetDevice(ctx->device));
         if (int rc = ledger_fail(ctx, ctx->asg.apply_tick(ledger_env(ctx)))) {
@@ -1690,150 +1596,74 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) {
             return rc;
         }
     }
-    if (ctx->last_consumed) {  // nothing handed out since the last consume (or the tick consumed it itself: HQTICK_FLAG_CONSUME_IN_TICK)
-        if (ctx->n_ready > 4096 && ctx->n_live * 2 < ctx->n_ready) { HQ_HIP(hipSetDevice(ctx->device)); return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0); }
-        return 0;
+    if (!ctx->ready.selection_pending()) {  // nothing handed out since the last consume (or the tick consumed it itself: HQTICK_FLAG_CONSUME_IN_TICK)
+        if (!ctx->ready.compact_due()) return 0;
+        HQ_HIP(hipSetDevice(ctx->device));
+        return ready_fail(ctx, ctx->ready.compact(ready_env(ctx)));
     }
-    if (!ctx->last_valid) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_consume_last needs a preceding hqtick_run_resident");
+    if (!ctx->ready.selection_valid()) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_consume_last needs a preceding hqtick_run_resident");
     HQ_HIP(hipSetDevice(ctx->device));
     const uint32_t *d = ctx->d_map.as<uint32_t>();
+    const hqready::Cols cols = ctx->ready.cols();
     // the selection of the last tick once more, writing tombstones instead of the selected ids (same offsets table, same plan; the view's: the same
     // permutation — which reads no priority, so hqtick_graph_blevel between the tick and this call changes nothing)
     if (ctx->last_ordered) {
         hqk::OrderSelect os = ctx->last_os;
-        os.mark_rq = ctx->d_trq.as<uint32_t>(); os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 0;
-        HQ_HIP(hqk::order_select(os, ctx->last_n_sel, ctx->stream));
+        os.mark_rq = cols.rq; os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 0;
+        HQ_HIP(hqk::order_select(os, ctx->ready.selected_count(), ctx->stream));
     } else
-    HQ_HIP(hqk::select_scatter(ctx->d_tid.as<uint64_t>(), ctx->d_gkey.as<uint16_t>(), ctx->n_ready, ctx->last_Q, ctx->last_G, ctx->last_geom, ctx->d_wave_tab.as<uint32_t>(),
+    HQ_HIP(hqk::select_scatter(cols.id, ctx->d_gkey.as<uint16_t>(), cols.n, ctx->last_Q, ctx->last_G, ctx->last_geom, ctx->d_wave_tab.as<uint32_t>(),
                                ctx->h_plan.as<uint32_t>() + ctx->last_tb, d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), nullptr, nullptr, 0,
-                               ctx->d_trq.as<uint32_t>(), ctx->stream));
-    ctx->n_live -= ctx->last_n_sel; ctx->last_consumed = true; ctx->last_valid = false;
-    if (ctx->n_ready > 4096 && ctx->n_live * 2 < ctx->n_ready) return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0);  // more tombstones than tasks: compact
-    return 0;
+                               cols.rq, ctx->stream));
+    return ready_fail(ctx, ctx->ready.consumed(ready_env(ctx)));
 }
 
 int hqtick_ready_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) {
     if (!ctx || (n && !task_id)) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
-    if (n == 0 || ctx->n_ready == 0) return 0;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (n == 0 || ctx->ready.cols().n == 0) return 0;
     if (n > 0x7FFFFFFFull) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta (the count of removed tasks is the int return value)");
     HQ_HIP(hipSetDevice(ctx->device));
-    if (!ctx->d_add.ensure(n * 8 + 8) || !ctx->h_q.ensure(64)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc delta staging");
-    uint32_t *cnt = ctx->h_q.as<uint32_t>(); cnt[0] = 0;
-    if (!ctx->h_add.ensure(n * 8 + 8)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc delta staging");
-    memcpy(ctx->h_add.p, task_id, n * 8);
-    HQ_HIP(hipMemcpyAsync(ctx->d_add.p, ctx->h_add.p, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HQ_HIP(hqk::ready_mark_removed(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready, ctx->d_add.as<uint64_t>(), (uint32_t)n, ctx->h_q.dev<uint32_t>(), ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->n_live -= cnt[0]; ctx->last_valid = false; ctx->last_consumed = true; ctx->asg.pending = false;
-    return (int)cnt[0];  // number of tasks that were in the set
+    return ready_fail(ctx, ctx->ready.remove(ready_env(ctx), n, task_id));
 }
 
 // The batch of new ready tasks is staged in pinned memory (a pageable hipMemcpy of a few MB costs ~1 ms in page pinning).  The caller can write it there
 // directly: hqtick_ready_add_stage hands out the three column pointers for n tasks, hqtick_ready_add_staged merges what was written (no copy on the host);
 // hqtick_ready_add = stage + memcpy + merge for callers that have the columns elsewhere.
-namespace {
-struct AddLayout { size_t o_p, o_q, bytes; };
-AddLayout add_layout(uint64_t n) { AddLayout L; L.o_p = (n * 8 + 15) & ~(size_t)15; L.o_q = L.o_p * 2; L.bytes = L.o_q + n * 4 + 16; return L; }
-}  // namespace
-
 int hqtick_ready_add_stage(hqtick_ctx *ctx, uint64_t n, uint64_t **task_id, uint64_t **task_priority, uint32_t **task_rq) {
     if (!ctx || !task_id || !task_priority || !task_rq) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     if (n > 0xFFFFFFFFull) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^32 ids in one delta");
     HQ_HIP(hipSetDevice(ctx->device));
-    const AddLayout L = add_layout(n);
-    if (!ctx->h_add.ensure(L.bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc delta staging");
-    unsigned char *h = ctx->h_add.as<unsigned char>();
-    *task_id = reinterpret_cast<uint64_t *>(h); *task_priority = reinterpret_cast<uint64_t *>(h + L.o_p); *task_rq = reinterpret_cast<uint32_t *>(h + L.o_q);
-    ctx->add_staged_n = n;
-    return 0;
+    return ready_fail(ctx, ctx->ready.stage(n, task_id, task_priority, task_rq));
 }
 
 int hqtick_ready_add_staged(hqtick_ctx *ctx, uint64_t n) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
-    if (n > ctx->add_staged_n) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_staged: more tasks than hqtick_ready_add_stage made room for");
-    const AddLayout L = add_layout(ctx->add_staged_n);  // the layout the pointers were handed out for
-    ctx->add_staged_n = 0;
-    if (n == 0) return 0;
-    const unsigned char *h = ctx->h_add.as<unsigned char>();
-    const uint64_t *task_id = reinterpret_cast<const uint64_t *>(h); const uint32_t *task_rq = reinterpret_cast<const uint32_t *>(h + L.o_q);
-    if (ctx->n_ready == 0) {  // nothing resident: the batch is copied as it is, so it is checked here; otherwise the merge kernel validates it
-        for (uint64_t i = 1; i < n; i++) if (task_id[i - 1] >= task_id[i]) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: ids not strictly ascending");
-        for (uint64_t i = 0; i < n; i++) if (task_rq[i] == 0xFFFFFFFFu) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: request id 0xFFFFFFFF is reserved");
-    }
-    HQ_HIP(hipSetDevice(ctx->device));
-    if (!ctx->d_add.ensure(L.bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc delta staging");
-    unsigned char *d = ctx->d_add.as<unsigned char>();
-    HQ_HIP(hipMemcpyAsync(d, h, L.o_q + n * 4, hipMemcpyHostToDevice, ctx->stream));
-    return rebuild_ready(ctx, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<const uint64_t *>(d + L.o_p), reinterpret_cast<const uint32_t *>(d + L.o_q), (uint32_t)n, task_id[0], task_id[n - 1]);
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
+    return ready_fail(ctx, ctx->ready.add_staged(ready_env(ctx), n));
 }
 
 int hqtick_ready_add_packed(hqtick_ctx *ctx, uint64_t n, uint32_t n_id_runs, const uint64_t *id_run_start, const uint32_t *id_run_len, const uint32_t *id_off,
                             uint32_t n_prio_runs, const uint64_t *prio_run_value, const uint32_t *prio_run_len, const uint16_t *task_rq) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     if (n == 0) return 0;
     if (n > 0xFFFFFFFFull) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^32 ids in one delta");
     if (!n_id_runs || !n_prio_runs || !id_run_start || !id_run_len || !prio_run_value || !prio_run_len || !task_rq) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_packed: null array");
     // the small run tables are checked here (a handful of entries); ids ascending across the whole batch, duplicates against the resident set and the reserved
-    // request id are checked by the merge kernel, as for hqtick_ready_add
+    // request id are checked by the append / merge kernel, as for hqtick_ready_add
     uint64_t tot = 0; for (uint32_t r = 0; r < n_id_runs; r++) { if (!id_run_len[r]) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_packed: empty id run"); tot += id_run_len[r]; }
     if (tot != n) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_packed: the id runs do not add up to n");
     tot = 0; for (uint32_t r = 0; r < n_prio_runs; r++) { if (!prio_run_len[r]) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_packed: empty priority run"); tot += prio_run_len[r]; }
     if (tot != n) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_packed: the priority runs do not add up to n");
     HQ_HIP(hipSetDevice(ctx->device));
-    auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_is = 0, o_if = al(o_is + (size_t)n_id_runs * 8), o_pv = al(o_if + (size_t)(n_id_runs + 1) * 4), o_pf = al(o_pv + (size_t)n_prio_runs * 8), o_off = al(o_pf + (size_t)(n_prio_runs + 1) * 4),
-                 o_rq = al(o_off + (id_off ? (size_t)n * 4 : 0)), bytes = al(o_rq + (size_t)n * 2);
-    static const bool trace_add = getenv("HQTICK_TRACE_ADD") != nullptr;  // (experiments: where the microseconds of an add go, one line per call on stderr)
-    const double ta0 = trace_add ? now_us() : 0.0;
-    if (!ctx->h_addp.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc packed delta staging");
-    const AddLayout L = add_layout(n);
-    if (!ctx->d_add.ensure(L.bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc delta staging");
-    unsigned char *h = ctx->h_addp.as<unsigned char>(), *hd = ctx->h_addp.dev<unsigned char>(), *d = ctx->d_add.as<unsigned char>();
-    memcpy(h + o_is, id_run_start, (size_t)n_id_runs * 8); memcpy(h + o_pv, prio_run_value, (size_t)n_prio_runs * 8);
-    uint32_t *idf = reinterpret_cast<uint32_t *>(h + o_if), *pf = reinterpret_cast<uint32_t *>(h + o_pf);
-    idf[0] = 0; for (uint32_t r = 0; r < n_id_runs; r++) idf[r + 1] = idf[r] + id_run_len[r];
-    pf[0] = 0; for (uint32_t r = 0; r < n_prio_runs; r++) pf[r + 1] = pf[r] + prio_run_len[r];
-    if (id_off) memcpy(h + o_off, id_off, (size_t)n * 4);
-    memcpy(h + o_rq, task_rq, (size_t)n * 2);
-    // the batch's id range, from the run tables: what decides between appending and merging
-    const uint64_t first_id = id_run_start[0] + (id_off ? id_off[0] : 0u);
-    const uint64_t last_id = id_run_start[n_id_runs - 1] + (id_off ? id_off[n - 1] : id_run_len[n_id_runs - 1] - 1u);
-    const uint64_t N = ctx->n_ready;
-    if (append_enabled() && N > 0 && ctx->max_id_valid && first_id > ctx->max_id && last_id >= first_id &&
-        ctx->d_tid.cap >= (N + n) * 8 + 8 && ctx->d_tprio.cap >= (N + n) * 8 + 8 && ctx->d_trq.cap >= (N + n) * 4 + 8) {
-        // fresh ids, room at the tail: the expansion kernel writes the batch where it belongs and validates it — the whole add is this one launch
-        const double ta1 = trace_add ? now_us() : 0.0;
-        if (!ctx->h_q.ensure(64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-        uint32_t *flag = ctx->h_q.as<uint32_t>(); flag[0] = 0;
-        bool waits_on_kernel = false;
-        hqk::time_next_launch(nullptr, ctx->ev[11]);
-        HQ_HIP_LAST(hqk::ready_unpack_adds((uint32_t)n, n_id_runs, reinterpret_cast<const uint64_t *>(hd + o_is), reinterpret_cast<const uint32_t *>(hd + o_if), id_off ? reinterpret_cast<const uint32_t *>(hd + o_off) : nullptr,
-                                      n_prio_runs, reinterpret_cast<const uint64_t *>(hd + o_pv), reinterpret_cast<const uint32_t *>(hd + o_pf), reinterpret_cast<const uint16_t *>(hd + o_rq),
-                                      ctx->d_tid.as<uint64_t>() + N, ctx->d_tprio.as<uint64_t>() + N, ctx->d_trq.as<uint32_t>() + N, ctx->max_id, ctx->h_q.dev<uint32_t>(), ctx->stream), waits_on_kernel);
-        const double ta2 = trace_add ? now_us() : 0.0;
-        if (waits_on_kernel) HQ_HIP(hipEventSynchronize(ctx->ev[11])); else HQ_HIP(hipStreamSynchronize(ctx->stream));  // (the dispatch's own completion signal: HQ_HIP_LAST)
-        if (trace_add) fprintf(stderr, "hqtick add (append, packed): n %llu prepare %.1f us, launch %.1f us, wait %.1f us\n", (unsigned long long)n, ta1 - ta0, ta2 - ta1, now_us() - ta2);
-        if (flag[0] & 4u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: a task id is already in the ready set");
-        if (flag[0] & 8u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: ids not strictly ascending");
-        if (flag[0] & 16u) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add: request id 0xFFFFFFFF is reserved");
-        ctx->n_ready = N + n; ctx->n_live += n; ctx->last_valid = false; ctx->last_consumed = true; ctx->max_id = last_id; ctx->n_appends++;
-        if (ctx->n_ready > 4096 && ctx->n_live * 2 < ctx->n_ready) return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0);  // (a host that never calls consume_last — HQTICK_FLAG_CONSUME_IN_TICK — compacts here)
-        return 0;
-    }
-    // the expansion kernel reads the packed batch in place (pinned, device-mapped): what crosses PCIe is the packed form
-    HQ_HIP(hqk::ready_unpack_adds((uint32_t)n, n_id_runs, reinterpret_cast<const uint64_t *>(hd + o_is), reinterpret_cast<const uint32_t *>(hd + o_if), id_off ? reinterpret_cast<const uint32_t *>(hd + o_off) : nullptr,
-                                  n_prio_runs, reinterpret_cast<const uint64_t *>(hd + o_pv), reinterpret_cast<const uint32_t *>(hd + o_pf), reinterpret_cast<const uint16_t *>(hd + o_rq),
-                                  reinterpret_cast<uint64_t *>(d), reinterpret_cast<uint64_t *>(d + L.o_p), reinterpret_cast<uint32_t *>(d + L.o_q), 0, nullptr, ctx->stream));
-    return rebuild_ready(ctx, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<const uint64_t *>(d + L.o_p), reinterpret_cast<const uint32_t *>(d + L.o_q), (uint32_t)n, first_id, last_id);
+    return ready_fail(ctx, ctx->ready.add_packed(ready_env(ctx), n, n_id_runs, id_run_start, id_run_len, id_off, n_prio_runs, prio_run_value, prio_run_len, task_rq));
 }
 
 int hqtick_ready_add(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq) {
     if (!ctx || (n && (!task_id || !task_priority || !task_rq))) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     if (n == 0) return 0;
     uint64_t *hi = nullptr, *hp = nullptr; uint32_t *hq = nullptr;
     if (int rc = hqtick_ready_add_stage(ctx, n, &hi, &hp, &hq)) return rc;
@@ -1845,7 +1675,7 @@ int hqtick_ready_add(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const
 namespace {
 int graph_fail(hqtick_ctx *ctx, int rc) { ctx->err = ctx->graph.err; return rc; }
 int graph_pre(hqtick_ctx *ctx) {
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_DEVICE, "hipSetDevice");
     return 0;
 }
@@ -1858,7 +1688,7 @@ int hqtick_graph_add_tasks(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id,
     if (int rc = graph_pre(ctx)) return rc;
     int r = ctx->graph.add(n, task_id, task_priority, task_rq, dep_off, dep_task_id, ctx->stream);
     if (r < 0) return graph_fail(ctx, r);
-    if (r > 0) { if (int rc = rebuild_ready(ctx, ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), (uint32_t)r)) return rc; }
+    if (r > 0) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), (uint32_t)r))) return rc; }
     return r;
 }
 
@@ -1868,7 +1698,7 @@ int hqtick_graph_finish(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) {
     int r = ctx->graph.finish(n, task_id, ctx->stream);
     // released consumers join the ready set even when the call reports ERR_NOT_READY: the graph itself is consistent
     const uint32_t rel = ctx->graph.n_out();
-    if (rel) { if (int rc = rebuild_ready(ctx, ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), rel)) return rc; }
+    if (rel) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), rel))) return rc; }
     if (r < 0) return graph_fail(ctx, r);
     return r;
 }
@@ -1878,12 +1708,8 @@ int hqtick_graph_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, in
     if (int rc = graph_pre(ctx)) return rc;
     int r = ctx->graph.remove(n, task_id, recursive != 0, ctx->stream);
     if (r < 0) return graph_fail(ctx, r);
-    if (r > 0 && ctx->n_ready) {  // TaskQueue::remove for the ones that were ready  core.rs:227-231
-        if (!ctx->h_q.ensure(64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc");
-        uint32_t *cnt = ctx->h_q.as<uint32_t>(); cnt[0] = 0;
-        HQ_HIP(hqk::ready_mark_removed(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), ctx->n_ready, ctx->graph.out_id(), (uint32_t)r, ctx->h_q.dev<uint32_t>(), ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->n_live -= cnt[0]; ctx->last_valid = false; ctx->last_consumed = true;
+    if (r > 0 && ctx->ready.cols().n) {  // TaskQueue::remove for the ones that were ready  core.rs:227-231
+        if (int rc = ready_fail(ctx, ctx->ready.remove_device(ready_env(ctx), ctx->graph.out_id(), (uint32_t)r)); rc < 0) return rc;
     }
     return r;
 }
@@ -1907,8 +1733,9 @@ int hqtick_graph_blevel(hqtick_ctx *ctx, uint32_t flags, uint32_t *max_level, ui
     if (!ctx) return HQTICK_E_INVALID;
     if (flags & ~(uint32_t)HQTICK_BLEVEL_UPDATE_READY) return fail(ctx, HQTICK_E_INVALID, "hqtick_graph_blevel: unknown flag");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_DEVICE, "hipSetDevice");
-    const bool upd = (flags & HQTICK_BLEVEL_UPDATE_READY) && ctx->resident && ctx->n_ready;
-    int r = ctx->graph.blevel(max_level, upd ? ctx->d_tid.as<uint64_t>() : nullptr, upd ? ctx->d_trq.as<uint32_t>() : nullptr, upd ? ctx->d_tprio.as<uint64_t>() : nullptr, upd ? ctx->n_ready : 0,
+    const hqready::Cols cols = ctx->ready.cols();
+    const bool upd = (flags & HQTICK_BLEVEL_UPDATE_READY) && ctx->ready.resident() && cols.n;
+    int r = ctx->graph.blevel(max_level, upd ? cols.id : nullptr, upd ? cols.rq : nullptr, upd ? cols.prio : nullptr, upd ? cols.n : 0,
                               n_ready_updated, ctx->stream);
     if (r < 0) return graph_fail(ctx, r);
     // the ready set's priorities changed: the next tick rediscovers its levels.  A pending hqtick_ready_consume_last is left alone — its replay reads the group keys, the
@@ -2021,7 +1848,7 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
         if (int rc = ctx->asg.upload_wids(ledger_env(ctx))) return ledger_fail(ctx, rc);
         // ... and go back into the resident ready set with their priority and request (add_ready_task), ids ascending
         const hqasg::Ledger &a = ctx->asg;
-        if (!a.rq_task.empty() && ctx->resident) {
+        if (!a.rq_task.empty() && ctx->ready.resident()) {
             if (int rc = hqtick_ready_add(ctx, a.rq_task.size(), a.rq_task.data(), a.rq_prio.data(), a.rq_rq.data())) return rc;
         }
     }
@@ -2202,10 +2029,10 @@ uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx) { return ctx && 
 
 int hqtick_ready_compact(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
-    if (ctx->n_live == ctx->n_ready) return 0;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (ctx->ready.live() == ctx->ready.cols().n) return 0;  // no tombstone
     HQ_HIP(hipSetDevice(ctx->device));
-    return rebuild_ready(ctx, nullptr, nullptr, nullptr, 0);
+    return ready_fail(ctx, ctx->ready.compact(ready_env(ctx)));
 }
 
 }  // extern "C"
@@ -2232,13 +2059,7 @@ static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_quer
     if (rc) return rc;
     HQ_HIP(hipSetDevice(ctx->device));
     const uint32_t R = s->n_resources, Q = s->n_requests;
-    uint64_t N = s->n_ready;
-    if (!ctx->d_tid.ensure(N * 8 + 8) || !ctx->d_tprio.ensure(N * 8 + 8) || !ctx->d_trq.ensure(N * 4 + 8)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ready set");
-    if (N) {
-        HQ_HIP(hipMemcpyAsync(ctx->d_tprio.p, s->task_priority, N * 8, hipMemcpyHostToDevice, ctx->stream));
-        HQ_HIP(hipMemcpyAsync(ctx->d_trq.p, s->task_rq, N * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    ctx->n_ready = N; ctx->resident = false;
+    if ((rc = ready_fail(ctx, ctx->ready.load(ctx->stream, s, false)))) return rc;  // (the query reads no task id)
     ctx->levels_valid = false;
     WorkerEval ev_real, ev_fake;
     if ((rc = eval_workers_sync(ctx, s, fake->n_workers, fake->worker_total, fake->worker_total, fake->worker_remaining_ns, &ev_fake))) return rc;  // fresh fake workers: free == total
@@ -2271,8 +2092,8 @@ static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc)
     sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
     runs_from_hist(*sc);
     q->dbg_census = false;
-    const uint64_t N = ctx->n_ready;
-    if (N == 0 || Q == 0 || ctx->n_live == 0) return 0;
+    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
+    if (N == 0 || Q == 0 || ctx->ready.live() == 0) return 0;
     const size_t tab_words = 4 + (size_t)std::min<uint64_t>(hqk::MAX_GROUPS, (uint64_t)Q * hqk::MAX_LEVELS);   // [err x 4][counts]: what the census can write for this Q
     if (!q->d_set.ensure((size_t)(hqk::PRIO_SET_CAP + hqk::MAX_LEVELS) * 8) || !q->h_lv.ensure((size_t)(hqk::MAX_LEVELS + 4) * 8) || !q->d_flags.ensure(64) ||
         !q->d_levels.ensure((size_t)(hqk::MAX_LEVELS + 2) * 8) || !q->d_nlevels.ensure(64) || !q->d_hist.ensure((4 + (size_t)hqk::MAX_GROUPS) * 4) || !q->h_a.ensure(tab_words * 4))
@@ -2283,20 +2104,20 @@ static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc)
     }
     q->set_clean = false;
     HQ_HIP(hipMemsetAsync(q->d_hist.p, 0, tab_words * 4, ctx->stream));
-    HQ_HIP(hqk::distinct_priorities(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hqk::distinct_priorities(cols.prio, cols.rq, N, q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), ctx->stream));
     uint32_t *hl = q->h_lv.as<uint32_t>();
     hl[0] = 0; hl[1] = 0; hl[2] = 0; hl[3] = 0;
     const uint32_t lv_seq = ++q->lv_seq ? q->lv_seq : ++q->lv_seq;
     HQ_HIP(hqk::sort_levels(q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->h_lv.dev<uint64_t>(), lv_seq, ctx->stream));
-    HQ_HIP(hqk::ready_census(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->d_hist.as<uint32_t>(), ctx->stream));
+    HQ_HIP(hqk::ready_census(cols.prio, cols.rq, N, Q, q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->d_hist.as<uint32_t>(), ctx->stream));
     HQ_HIP(hipMemcpyAsync(q->h_a.p, q->d_hist.p, tab_words * 4, hipMemcpyDeviceToHost, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     const uint32_t L = hl[0];
     // beyond the dense caps: the ordered view's run table, built on the sub-context's buffers from ctx's columns
-    if (hl[2] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return build_view(ctx, q, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, ctx->stream, sc, nullptr);
+    if (hl[2] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return build_view(ctx, q, cols.prio, cols.rq, N, Q, ctx->stream, sc, nullptr);
     q->set_clean = true;
     if (L == 0) return 0;   // only tombstones
-    if ((uint64_t)L * Q > hqk::MAX_GROUPS) return build_view(ctx, q, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, Q, ctx->stream, sc, nullptr);
+    if ((uint64_t)L * Q > hqk::MAX_GROUPS) return build_view(ctx, q, cols.prio, cols.rq, N, Q, ctx->stream, sc, nullptr);
     const uint32_t *h = q->h_a.as<uint32_t>();
     if (h[0] & 2u) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
     if (h[0]) return fail(ctx, HQTICK_E_DEVICE, "census: level table inconsistent with the ready set");
@@ -2311,8 +2132,8 @@ static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc)
 int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, hqtick_query_result *out, uint64_t *rq_ready) {
     if (!ctx || !out || !fake) return HQTICK_E_INVALID;
     if (!s) return fail(ctx, HQTICK_E_INVALID, "null snapshot");
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
-    if (!ctx->last_consumed) return fail(ctx, HQTICK_E_INVALID, "a selection of hqtick_run_resident is pending: call hqtick_ready_consume_last before hqtick_query_resident");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
+    if (ctx->ready.selection_pending()) return fail(ctx, HQTICK_E_INVALID, "a selection of hqtick_run_resident is pending: call hqtick_ready_consume_last before hqtick_query_resident");
     if (fake->n_workers && (!fake->worker_id || !fake->worker_total || !fake->worker_remaining_ns)) return fail(ctx, HQTICK_E_INVALID, "fake worker arrays missing");
     // What the query reads of the snapshot: resources, requests, the prefill sets' sizes and priorities.  The real workers and everything indexed by them
     // (blocked pairs, assignments, the prefill sets' workers, Retracting entries) are dropped, so W = 0, HQ_WORKERS_RESIDENT and a worker list answer alike.
@@ -2468,7 +2289,7 @@ int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels,
 int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t counts[4], uint32_t *perm, uint32_t *inv, uint32_t *lrank, uint64_t cap_slots, uint32_t *run_rq,
                             uint32_t *run_start, uint32_t *run_rank, uint64_t *run_prio, uint32_t cap_runs) {
     if (!ctx || !counts) return HQTICK_E_INVALID;
-    if (!ctx->resident) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
     HQ_HIP(hipSetDevice(ctx->device));
     if (!ctx->vctx) {
         hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
@@ -2476,11 +2297,11 @@ int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t count
         if (rc) { ctx->vctx = nullptr; return fail(ctx, rc, "creating the view sub-context failed"); }
     }
     hqtick_ctx *v = ctx->vctx;
-    const uint64_t N = ctx->n_ready;
+    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
     v->dbg_view.valid = false; v->dbg_view.rq_copy = false; v->dbg_order = false; v->dbg_order_passes = 0;
     for (int i = 0; i < 4; i++) counts[i] = 0;
     Scan sc;
-    if (int rc = build_view(ctx, v, ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, n_requests, ctx->stream, &sc, nullptr)) return rc;
+    if (int rc = build_view(ctx, v, cols.prio, cols.rq, N, n_requests, ctx->stream, &sc, nullptr)) return rc;
     const uint32_t nr = (uint32_t)sc.run_cnt.size(), n = nr ? sc.run_start.back() + sc.run_cnt.back() : 0u;
     if ((nr != 0) != v->dbg_order) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the run table and the debug record disagree");
     counts[0] = n; counts[1] = nr; counts[2] = sc.L; counts[3] = v->dbg_order_passes;
@@ -2496,7 +2317,7 @@ int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t count
         if (run_rank) memcpy(run_rank, hh + tl.o_rk, (size_t)nr * 4);
         if (run_prio) memcpy(run_prio, hh + tl.o_pr, (size_t)nr * 8);
     }
-    v->dbg_view.ids = ctx->d_tid.p; v->dbg_view.N = N; v->dbg_view.Q = n_requests; v->dbg_view.n_live = n;
+    v->dbg_view.ids = cols.id; v->dbg_view.N = N; v->dbg_view.Q = n_requests; v->dbg_view.n_live = n;
     v->dbg_view.run_off = std::move(sc.run_off); v->dbg_view.run_start = std::move(sc.run_start); v->dbg_view.run_rank = std::move(sc.run_level);
     v->dbg_view.valid = true;
     return 0;
@@ -2506,7 +2327,7 @@ namespace {
 // the view hqtick_debug_order_view last built, if ctx's columns are still the ones it was built on
 hqtick_ctx *debug_view_of(hqtick_ctx *ctx) {
     hqtick_ctx *v = ctx->vctx;
-    if (!v || !v->dbg_view.valid || !ctx->resident || v->dbg_view.ids != ctx->d_tid.p || v->dbg_view.N != ctx->n_ready) return nullptr;
+    if (!v || !v->dbg_view.valid || !ctx->ready.resident() || v->dbg_view.ids != ctx->ready.cols().id || v->dbg_view.N != ctx->ready.cols().n) return nullptr;
     return v;
 }
 }  // namespace
@@ -2540,25 +2361,25 @@ int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, cons
     tab.insert(tab.end(), q_tnc, q_tnc + Q);
     tab.insert(tab.end(), v->dbg_view.run_start.begin(), v->dbg_view.run_start.end());
     tab.insert(tab.end(), v->dbg_view.run_rank.begin(), v->dbg_view.run_rank.end());
-    if (!v->d_map.ensure(tab.size() * 4 + 16) || !v->d_sel_task.ensure((size_t)n_sel * 8 + 16) || !v->d_sel_level.ensure((size_t)n_sel * 4 + 16) || !v->d_trq.ensure(N * 4 + 8))
+    if (!v->d_map.ensure(tab.size() * 4 + 16) || !v->d_sel_task.ensure((size_t)n_sel * 8 + 16) || !v->d_sel_level.ensure((size_t)n_sel * 4 + 16) || !v->d_dbg_rq.ensure(N * 4 + 8))
         return fail(ctx, HQTICK_E_DEVICE, "hipMalloc view selection");
     HQ_HIP(hipMemcpy(v->d_map.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     uint32_t *derr = v->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2;
     HQ_HIP(hipMemsetAsync(derr, 0, 4, ctx->stream));
     HQ_HIP(hipMemsetAsync(v->d_sel_task.p, 0xFF, (size_t)n_sel * 8, ctx->stream));   // the sentinel: a j the kernel did not write stays 0xFF..FF
     HQ_HIP(hipMemsetAsync(v->d_sel_level.p, 0xFF, (size_t)n_sel * 4, ctx->stream));
-    if (mark_mode != 2) { HQ_HIP(hipMemcpyAsync(v->d_trq.p, ctx->d_trq.p, N * 4, hipMemcpyDeviceToDevice, ctx->stream)); v->dbg_view.rq_copy = true; }
+    if (mark_mode != 2) { HQ_HIP(hipMemcpyAsync(v->d_dbg_rq.p, ctx->ready.cols().rq, N * 4, hipMemcpyDeviceToDevice, ctx->stream)); v->dbg_view.rq_copy = true; }
     const uint32_t *d = v->d_map.as<uint32_t>();
     hqk::OrderSelect os{};
-    os.task_id = ctx->d_tid.as<uint64_t>(); os.perm = v->d_perm.as<uint32_t>(); os.n_live = n; os.Q = Q; os.n_runs = nr;
+    os.task_id = ctx->ready.cols().id; os.perm = v->d_perm.as<uint32_t>(); os.n_live = n; os.Q = Q; os.n_runs = nr;
     os.rq_sel_base = d; os.run_off = d + (Q + 1); os.q_tnc = d + 2 * (size_t)(Q + 1); os.run_start = os.q_tnc + Q; os.run_rank = os.run_start + nr;
     os.sel_task = v->d_sel_task.as<uint64_t>(); os.sel_rank = v->d_sel_level.as<uint32_t>(); os.err = derr;
-    if (mark_mode) { os.mark_rq = v->d_trq.as<uint32_t>(); os.mark_value = mark_mode == 2 ? 0u : hqk::RQ_TOMBSTONE; os.mark_and_select = mark_mode == 3 ? 1u : 0u; }
+    if (mark_mode) { os.mark_rq = v->d_dbg_rq.as<uint32_t>(); os.mark_value = mark_mode == 2 ? 0u : hqk::RQ_TOMBSTONE; os.mark_and_select = mark_mode == 3 ? 1u : 0u; }
     HQ_HIP(hqk::order_select(os, n_sel, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     HQ_HIP(hipMemcpy(sel_task, v->d_sel_task.p, (size_t)n_sel * 8, hipMemcpyDeviceToHost));
     HQ_HIP(hipMemcpy(sel_rank, v->d_sel_level.p, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
-    if (rq_after) HQ_HIP(hipMemcpy(rq_after, v->d_trq.p, N * 4, hipMemcpyDeviceToHost));
+    if (rq_after) HQ_HIP(hipMemcpy(rq_after, v->d_dbg_rq.p, N * 4, hipMemcpyDeviceToHost));
     HQ_HIP(hipMemcpy(err, derr, 4, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2571,10 +2392,10 @@ int hqtick_debug_order_rank_of(hqtick_ctx *ctx, const uint64_t *want, uint32_t n
     if (n_want == 0) return 0;
     if (v->dbg_view.n_live == 0) { for (uint32_t i = 0; i < n_want; i++) out_rq[i] = out_pos[i] = 0xFFFFFFFFu; return 0; }  // (as phase A: no view, no launch)
     HQ_HIP(hipSetDevice(ctx->device));
-    if (!v->d_add.ensure((size_t)n_want * 16 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc wanted ids");
-    uint8_t *dw = v->d_add.as<uint8_t>();
+    if (!v->d_dbg_want.ensure((size_t)n_want * 16 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc wanted ids");
+    uint8_t *dw = v->d_dbg_want.as<uint8_t>();
     HQ_HIP(hipMemcpy(dw, want, (size_t)n_want * 8, hipMemcpyHostToDevice));
-    HQ_HIP(hqk::order_rank_of(ctx->d_tid.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), v->dbg_view.N, v->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(dw), n_want,
+    HQ_HIP(hqk::order_rank_of(ctx->ready.cols().id, ctx->ready.cols().rq, v->dbg_view.N, v->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(dw), n_want,
                               reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 8), reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 12), ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     HQ_HIP(hipMemcpy(out_rq, dw + (size_t)n_want * 8, (size_t)n_want * 4, hipMemcpyDeviceToHost));
@@ -2724,10 +2545,10 @@ int hqtick_set_record_sink(hqtick_ctx *ctx, void *device_ptr, size_t capacity_by
 #ifdef HQTICK_TEST_HOOKS  // measurement hooks of the tools (include/hqtick_debug.h): libhqtick_test.so only
 int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     if (!ctx || !avg_us || iters <= 0) return HQTICK_E_INVALID;
-    if (!ctx->last_valid || !ctx->resident) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel needs a preceding hqtick_run_resident tick that placed tasks");
+    if (!ctx->ready.selection_valid() || !ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel needs a preceding hqtick_run_resident tick that placed tasks");
     if (ctx->last_ordered) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel times the dense scan: the last tick took the ordered view");
     HQ_HIP(hipSetDevice(ctx->device));
-    const uint64_t N = ctx->n_ready; const hqk::WaveGeom g = ctx->last_geom;
+    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n; const hqk::WaveGeom g = ctx->last_geom;
     const uint32_t *d = ctx->d_map.as<uint32_t>();
     uint32_t *hist_dev = reinterpret_cast<uint32_t *>(ctx->h_a.dev<unsigned char>() + 16);
     if (which == 2) {  // calibration: an EMPTY kernel of K1's grid, each launch bracketed by its own start / stop events like the stats pass of a tick
@@ -2748,9 +2569,9 @@ int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     if (as_graph) HQ_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     else HQ_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
     for (int i = 0; i < iters; i++) {
-        if (which == 0) HQ_HIP(hqk::level_hist(ctx->d_tprio.as<uint64_t>(), ctx->d_trq.as<uint32_t>(), N, ctx->d_levels.as<uint64_t>(), ctx->h_levels.data(), ctx->last_L, ctx->last_Q, g, ctx->d_wave_tab.as<uint32_t>(),
+        if (which == 0) HQ_HIP(hqk::level_hist(cols.prio, cols.rq, N, ctx->d_levels.as<uint64_t>(), ctx->h_levels.data(), ctx->last_L, ctx->last_Q, g, ctx->d_wave_tab.as<uint32_t>(),
                                               ctx->d_gkey.as<uint16_t>(), ctx->d_flags.as<uint32_t>() + 2, nullptr, ctx->stream));
-        else if (which == 1) HQ_HIP(hqk::select_scatter(ctx->d_tid.as<uint64_t>(), ctx->d_gkey.as<uint16_t>(), N, ctx->last_Q, ctx->last_G, g, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + ctx->last_tb,
+        else if (which == 1) HQ_HIP(hqk::select_scatter(cols.id, ctx->d_gkey.as<uint16_t>(), N, ctx->last_Q, ctx->last_G, g, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + ctx->last_tb,
                                                         d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, ctx->last_plan_bytes, nullptr, ctx->stream));
         else return fail(ctx, HQTICK_E_INVALID, "which: 0 = level_hist, 1 = select_scatter, 2 = empty kernel of level_hist's grid");
     }
@@ -2797,7 +2618,7 @@ int hqtick_set_kernel_timing(hqtick_ctx *ctx, int on) {
 int hqtick_kernel_stats_last(const hqtick_ctx *ctx, hqtick_kernel_stats *out) {
     if (!ctx || !out) return HQTICK_E_INVALID;
     *out = ctx->stats;
-    out->ready_appends = ctx->n_appends;
+    out->ready_appends = ctx->ready.appends();
     return 0;
 }
 
