@@ -33,6 +33,7 @@
 #include "cluster.h"
 #include "price_dev.h"
 #include "ready.h"
+#include "scan.h"
 #ifdef HQTICK_TEST_HOOKS
 #include "price_emul.h"
 #endif
@@ -46,6 +47,8 @@
 using hqbuf::DevBuf;
 using hqbuf::PinBuf;
 using hqcluster::UpView;
+using hqscan::Scan;
+using hqscan::WorkerEval;
 
 namespace {
 
@@ -71,6 +74,14 @@ struct PlanScratch {
     // cached worker_map iteration order (emulated) for the last worker-id set
     std::vector<uint32_t> cached_ids, cached_order;
 };
+// The ordered view by itself (hqtick_debug_order_view and the two hooks that run on the view it built): a scanner of its own, so that the context keeps its
+// permutation, its pending selection and its cached level table; what is known of that view; the hooks' scratch in HBM.
+struct ViewHooks {
+    hqscan::Scanner scan;
+    bool valid = false; const void *ids = nullptr; uint64_t N = 0; uint32_t Q = 0, n_live = 0; bool rq_copy = false; std::vector<uint32_t> run_off, run_start, run_rank;
+    DevBuf d_map, d_sel_task, d_sel_rank, d_rq, d_want;  // the selection's tables and output, the copy of the request column hqtick_debug_order_select marks, the ids hqtick_debug_order_rank_of looks up
+    void release() { scan.release(); d_map.release(); d_sel_task.release(); d_sel_rank.release(); d_rq.release(); d_want.release(); }
+};
 }  // namespace
 
 struct hqtick_ctx {
@@ -86,19 +97,11 @@ struct hqtick_ctx {
     std::string err = "";
     hqready::ReadySet ready;       // hqtick_upload_ready, hqtick_ready_* (ready.h): the ready set's columns in HBM (resident, or a tick's own), their deltas, the last selection's state
     hqhost::BlockMemo block_memo;  // host class blocks of earlier ticks (host_model.h)
-    // scans
-    DevBuf d_set, d_flags, d_levels, d_nlevels, d_wave_tab, d_hist, d_gkey;
-    // the ordered view (order.hip): phase A's general path where the dense (level, request) table does not fit
-    DevBuf d_ord_hist, d_ord_tab, d_perm, d_perm2, d_ord_tiles, d_inv; PinBuf h_ord, h_ordh;
-    bool force_ordered = false;   // HQTICK_ORDERED_VIEW=1 (tests): every tick with a ready set takes the view
-    bool ordered_sticky = false;  // the last dense attempt did not fit: go straight to the view until a view fits the dense caps again
+    hqscan::Scanner scan;          // GPU phase A (scan.h): the dense scan with its cached level table, the ordered view, the census — on the query sub-context, a query's
     bool last_ordered = false;    // the pending selection (ready.selection_valid()) is one of the view: consume / restore replay it with order_select
     hqk::OrderSelect last_os{};   // ... its tables (HBM copy of the plan, the permutation)
-    uint32_t dbg_order_runs = 0, dbg_order_levels = 0; bool dbg_order = false; double dbg_order_us = 0;  // hqtick_debug_last_order
-    uint32_t dbg_order_passes = 0;  // bit dg: the last view built on these buffers ran a pass on digit dg (hqtick_debug_order_view)
-    uint32_t dbg_scan_L = 0, dbg_scan_G = 0, dbg_scan_shape[4] = {0, 0, 0, 0}; bool dbg_scan = false, dbg_census = false;  // hqtick_debug_last_scan: what the last dense scan (phase_a) / census (census_resident, on the query sub-context) left in h_a, h_levels, h_lv
-    uint32_t lv_seq = 0; bool set_clean = false; bool no_spec_scan = getenv("HQTICK_NO_SPEC_SCAN") != nullptr; bool levels_valid = false; uint32_t cached_L = 0; std::vector<uint64_t> h_levels; bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))  // level table of the previous tick (re-validated by K1 every tick)
-    PinBuf h_up, h_up2, h_q, h_a, h_plan, h_rec, h_sinkhdr, h_retr, h_blk, h_k5a, h_lv;   // (h_lv: the level table as k_sort_levels writes it)
+    bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))
+    PinBuf h_up, h_up2, h_q, h_plan, h_rec, h_sinkhdr, h_blk, h_k5a;
     PinBuf h_blkprof; uint32_t n_blkprof = 0; bool block_profile = false;
     hqprice::DeviceSweeper *pricer = nullptr;  // k_price_sweep: the block sweeps of the coupled placement (csrc/price.hip); HQTICK_PRICE=0 keeps coupled ticks on the host search
     uint32_t block_budget = 4096, block_min_classes = 12;  // k_block_solve: search steps per class before the host solver takes it; classes below which the host solves alone
@@ -127,9 +130,7 @@ struct hqtick_ctx {
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
     hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
-    hqtick_ctx *vctx = nullptr;  // hqtick_debug_order_view's private sub-context (test library only); the view it holds is described by its dbg_view
-    struct { bool valid = false; const void *ids = nullptr; uint64_t N = 0; uint32_t Q = 0, n_live = 0; bool rq_copy = false; std::vector<uint32_t> run_off, run_start, run_rank; } dbg_view;
-    DevBuf d_dbg_rq, d_dbg_want;  // ... and its scratch: the copy of the request column hqtick_debug_order_select marks, the ids hqtick_debug_order_rank_of looks up
+    ViewHooks *view_hooks = nullptr;  // hqtick_debug_order_view's scanner and scratch (test library only), allocated on first use; nothing of it is touched on a tick's path
     ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
     // sharded placement solve: the ranks split the coupled solve's price sweeps and the separable solve's class blocks, one small all-gather of host
     // buffers per sweep / per launch — through the host's callback (hqtick_set_exchange) or the library's own RCCL communicator
@@ -229,8 +230,6 @@ int validate(hqtick_ctx *ctx, const hqtick_snapshot *s, bool need_tasks) {
     return 0;
 }
 
-struct WorkerEval { const uint8_t *flags = nullptr; const uint32_t *tmc = nullptr; };
-
 // Packs worker tables + request tables (cluster.h: TabLayout) into ONE pinned, device-mapped staging buffer that K2 reads in place (every byte
 // crosses PCIe once per workgroup; no H2D copy command).
 int upload_tables(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const uint64_t *total, const uint64_t *free_, const int64_t *rem, PinBuf &buf, UpView *uv) {
@@ -305,308 +304,35 @@ void export_batches(hqtick_ctx *ctx, const std::vector<hqhost::TaskBatch> &batch
     out->cut_size = ctx->c_size.data(); out->cut_blocker_off = ctx->c_bl_off.data(); out->blocker_rq = ctx->bl_rq.data(); out->blocker_size = ctx->bl_size.data();
 }
 
-struct Scan {  // result of GPU phase A
-    uint32_t L = 0, Q = 0, G = 0;
-    std::vector<uint64_t> levels;
-    std::vector<uint32_t> hist;  // [G], g = level*Q + rq  (dense scan only)
-    hqk::WaveGeom geom{};
-    // The sparse form every host stage walks: per request its RUNS (nonempty (request, priority) pairs) in descending priority, runs of request q at
-    // [run_off[q], run_off[q + 1]).  run_group = the selection plan's index of the run (dense: level * Q + rq; view: the run index itself), run_level = its
-    // level (dense: index into `levels`; view: the global level rank), run_start = its first position in the view's permutation (view only).
-    bool ordered = false;
-    std::vector<uint32_t> run_off, run_cnt, run_group, run_level, run_start;
-    std::vector<uint64_t> run_prio;
-};
+// GPU phase A (hqscan::Scanner, scan.h): what it is given of the context (ev[0] / ev[1] around K0, ev[2] / ev[3] around K1, ev[8] K1b's completion, ev[12] / ev[13]
+// around the kernels of the ordered view), and its errors
+hqscan::Env scan_env(hqtick_ctx *ctx) {
+    return hqscan::Env{ctx->stream, ctx->stream2, ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->ev[8], ctx->ev[12], ctx->ev[13],
+                       ctx->timing, ctx->timing_k1, ctx->wait_on_kernel, ctx->k2_on_hist, ctx->k2_own_stream, ctx->tpw_hint};
+}
+int scan_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->scan.err; return rc; }
 
-// the runs of a dense histogram: O(L * Q), which the dense scan's caps bound
-void runs_from_hist(Scan &sc) {
-    const uint32_t Q = sc.Q;
-    sc.ordered = false;
-    sc.run_off.assign(Q + 1, 0); sc.run_cnt.clear(); sc.run_group.clear(); sc.run_level.clear(); sc.run_start.clear(); sc.run_prio.clear();
-    for (uint32_t q = 0; q < Q; q++) {
-        for (uint32_t l = 0; l < sc.L; l++) {
-            const uint32_t c = sc.hist[(size_t)l * Q + q];
-            if (!c) continue;
-            sc.run_cnt.push_back(c); sc.run_group.push_back(l * Q + q); sc.run_level.push_back(l); sc.run_prio.push_back(sc.levels[l]);
-        }
-        sc.run_off[q + 1] = (uint32_t)sc.run_cnt.size();
-    }
+// K2's tables for the scanner: from HBM where a worker set is resident, else packed from the snapshot
+struct TablesOf { hqtick_ctx *ctx; const hqtick_snapshot *s; };
+int worker_tables(void *user, UpView *uv, std::string *err) {
+    hqtick_ctx *ctx = static_cast<TablesOf *>(user)->ctx; const hqtick_snapshot *s = static_cast<TablesOf *>(user)->s;
+    const int rc = ctx->ws.valid() ? cluster_fail(ctx, ctx->ws.tables(ctx->stream, s, s->n_workers, uv))
+                                   : upload_tables(ctx, s, s->n_workers, s->worker_total, s->worker_free, s->worker_remaining_ns, ctx->h_up, uv);
+    if (rc) *err = ctx->err;
+    return rc;
 }
 
-// the run table of a view of n live slots as order_runs writes it into h_ord: [n_runs, n_levels, pad][run_rq n][run_start n][run_rank n][run_prio n]
-struct OrderTabLayout { size_t o_rq, o_st, o_rk, o_pr, bytes; };
-OrderTabLayout order_tab_layout(uint32_t n) {
-    OrderTabLayout l; l.o_rq = 16; l.o_st = l.o_rq + (size_t)n * 4; l.o_rk = l.o_st + (size_t)n * 4; l.o_pr = (l.o_rk + (size_t)n * 4 + 7) & ~(size_t)7; l.bytes = l.o_pr + (size_t)n * 8 + 16;
-    return l;
-}
-
-// The ordered view (order.hip) of the columns prio / rq [0..N) on the buffers of `b` (ctx itself, or hqtick_query_resident's sub-context
-// reading ctx's columns): sc gets the runs, b->d_perm the permutation, b->d_inv its inverse.  One synchronisation after the digit histogram (which passes
-// to run, how many live slots), one after the run table.  Errors are reported on ctx.
-int build_view(hqtick_ctx *ctx, hqtick_ctx *b, const uint64_t *prio, const uint32_t *rq, uint64_t N, uint32_t Q, hipStream_t st, Scan *sc,
-               const std::function<void()> *while_gpu_runs) {
-    const size_t hw = (size_t)hqk::ORDER_DIGITS * 256 + 4;
-    sc->ordered = true; sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
-    sc->run_off.assign(Q + 1, 0); sc->run_cnt.clear(); sc->run_group.clear(); sc->run_level.clear(); sc->run_start.clear(); sc->run_prio.clear();
-    if (N > 0xFFFFFFF0ull) return fail(ctx, HQTICK_E_CAPACITY, "ordered view: more than 2^32 - 16 slots in the ready set");
-    if (!b->d_ord_hist.ensure(hw * 4) || !b->h_ordh.ensure(hw * 4)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ordered view");
-    if (b->timing) HQ_HIP(hipEventRecord(b->ev[12], st));
-    HQ_HIP(hqk::order_digits(prio, rq, N, Q, b->d_ord_hist.as<uint32_t>(), st));
-    HQ_HIP(hipMemcpyAsync(b->h_ordh.p, b->d_ord_hist.p, hw * 4, hipMemcpyDeviceToHost, st));
-    if (while_gpu_runs) (*while_gpu_runs)();
-    HQ_HIP(hipStreamSynchronize(st));
-    const uint32_t *gh = b->h_ordh.as<uint32_t>();
-    if (gh[hqk::ORDER_DIGITS * 256]) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
-    uint64_t n_live = 0;
-    for (uint32_t d = 0; d < 256; d++) n_live += gh[d];
-    if (n_live == 0) return 0;
-    const uint32_t n = (uint32_t)n_live;
-    // the passes: every digit that is not constant over the live set, least significant first (~priority bytes 0-7, then rq bytes 0-3)
-    std::vector<uint32_t> passes;
-    for (uint32_t dg = 0; dg < hqk::ORDER_DIGITS; dg++) {
-        bool constant = false;
-        for (uint32_t d = 0; d < 256 && !constant; d++) constant = gh[dg * 256 + d] == n;
-        if (!constant) passes.push_back(dg);
-    }
-    if (passes.empty()) passes.push_back(0);  // (one pass still drops the tombstones)
-    uint32_t level_after = 0;                 // the level ranks are read off the permutation after the last priority pass (no such pass: one priority, any order)
-    for (uint32_t i = 0; i < passes.size(); i++) if (passes[i] < 8) level_after = i;
-    const uint32_t tiles = hqk::order_tiles(N);
-    const OrderTabLayout tl = order_tab_layout(n);
-    const size_t o_rq = tl.o_rq, o_st = tl.o_st, o_rk = tl.o_rk, o_pr = tl.o_pr, h_bytes = tl.bytes;
-    if (!b->d_perm.ensure((size_t)n * 4 + 16) || !b->d_perm2.ensure((size_t)n * 4 + 16) || !b->d_ord_tab.ensure((size_t)tiles * 256 * 4 + 16) ||
-        !b->d_ord_tiles.ensure(((size_t)tiles + 1) * 4 + 16) || !b->d_inv.ensure(N * 8 + 16) || !b->h_ord.ensure(h_bytes))
-        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ordered view");
-    uint32_t *lrank = b->d_inv.as<uint32_t>() + N, *inv = b->d_inv.as<uint32_t>();  // [inv N][level rank N]
-    uint32_t *err = b->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 1;
-    const uint32_t *in = nullptr;
-    for (uint32_t i = 0; i < passes.size(); i++) {
-        uint32_t *out = ((passes.size() - 1 - i) % 2 == 0) ? b->d_perm.as<uint32_t>() : b->d_perm2.as<uint32_t>();  // (the last pass writes d_perm)
-        HQ_HIP(hqk::order_pass(prio, rq, i == 0 ? N : n, i == 0, in, passes[i], b->d_ord_hist.as<uint32_t>(), b->d_ord_tab.as<uint32_t>(), out, n, err, st));
-        in = out;
-        if (i == level_after) HQ_HIP(hqk::order_levels(prio, in, n, b->d_ord_tiles.as<uint32_t>(), lrank, b->h_ord.dev<uint32_t>() + 1, st));
-    }
-    uint8_t *hd = b->h_ord.dev<uint8_t>();
-    HQ_HIP(hqk::order_runs(prio, rq, in, n, b->d_ord_tiles.as<uint32_t>(), lrank, inv, b->h_ord.dev<uint32_t>(), reinterpret_cast<uint32_t *>(hd + o_rq),
-                           reinterpret_cast<uint32_t *>(hd + o_st), reinterpret_cast<uint32_t *>(hd + o_rk), reinterpret_cast<uint64_t *>(hd + o_pr), st));
-    HQ_HIP(hipMemcpyAsync(b->h_ordh.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 1, err, 4, hipMemcpyDeviceToHost, st));
-    if (b->timing) HQ_HIP(hipEventRecord(b->ev[13], st));
-    HQ_HIP(hipStreamSynchronize(st));
-    if (gh[hqk::ORDER_DIGITS * 256 + 1]) return fail(ctx, HQTICK_E_DEVICE, "ordered view: a pass's counts disagree with the digit histogram");
-    const uint8_t *hh = b->h_ord.as<uint8_t>();
-    const uint32_t nr = reinterpret_cast<const uint32_t *>(hh)[0], nl = reinterpret_cast<const uint32_t *>(hh)[1];
-    if (nr == 0 || nr > n || nl == 0 || nl > nr) return fail(ctx, HQTICK_E_DEVICE, "ordered view: inconsistent run table");
-    const uint32_t *rrq = reinterpret_cast<const uint32_t *>(hh + o_rq), *rst = reinterpret_cast<const uint32_t *>(hh + o_st), *rrk = reinterpret_cast<const uint32_t *>(hh + o_rk);
-    const uint64_t *rpr = reinterpret_cast<const uint64_t *>(hh + o_pr);
-    sc->run_start.assign(rst, rst + nr); sc->run_level.assign(rrk, rrk + nr); sc->run_prio.assign(rpr, rpr + nr);
-    sc->run_cnt.resize(nr); sc->run_group.resize(nr);
-    for (uint32_t r = 0; r < nr; r++) {
-        if (rrq[r] >= Q || (r && rrq[r] < rrq[r - 1])) return fail(ctx, HQTICK_E_DEVICE, "ordered view: runs out of request order");
-        sc->run_cnt[r] = (r + 1 < nr ? rst[r + 1] : n) - rst[r]; sc->run_group[r] = r; sc->run_off[rrq[r] + 1]++;
-    }
-    for (uint32_t q = 0; q < Q; q++) sc->run_off[q + 1] += sc->run_off[q];
-    sc->L = nl; sc->G = nr;
-    if (b->timing) { const double us_ = elapsed_us(b->ev[12], b->ev[13]); b->dbg_order_us = us_ >= 0 ? us_ : 0.0; }
-    b->dbg_order = true; b->dbg_order_runs = nr; b->dbg_order_levels = nl;
-    b->dbg_order_passes = 0; for (uint32_t dg : passes) b->dbg_order_passes |= 1u << dg;
-    return 0;
-}
-
-// Phase A on the ordered view: K2 as its own launch, the view, the positions of the Retracting tasks (the same layout of h_retr as k_rank_of's).
-int phase_a_ordered(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc, const std::function<void()> *while_gpu_runs) {
-    const uint32_t W = s->n_workers, R = s->n_resources, Q = s->n_requests;
-    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
-    const uint32_t nvs = Q ? s->rq_variant_off[Q] : 0;
-    const size_t nwv = (size_t)W * nvs, o_tmc = 16, o_fl = o_tmc + nwv * 4, bytes = o_fl + nwv + 16;
-    if (!ctx->h_a.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc phase A");
-    unsigned char *h = ctx->h_a.as<unsigned char>(), *hd = ctx->h_a.dev<unsigned char>();
-    memset(h, 0, 16);
-    UpView uv; int rc;
-    if (ctx->ws.valid()) { if ((rc = cluster_fail(ctx, ctx->ws.tables(ctx->stream, s, W, &uv)))) return rc; }
-    else if ((rc = upload_tables(ctx, s, W, s->worker_total, s->worker_free, s->worker_remaining_ns, ctx->h_up, &uv))) return rc;
-    HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream));
-    ev->flags = h + o_fl; ev->tmc = reinterpret_cast<const uint32_t *>(h + o_tmc);
-    ctx->levels_valid = false;  // (the dense level table is rediscovered when a tick fits the dense caps again)
-    if ((rc = build_view(ctx, ctx, cols.prio, cols.rq, N, Q, ctx->stream, sc, while_gpu_runs))) return rc;
-    if (!ctx->force_ordered && sc->L <= hqk::MAX_LEVELS && (uint64_t)sc->L * Q <= hqk::MAX_GROUPS) ctx->ordered_sticky = false;  // the next tick fits the dense scan again
-    if (s->n_retracting) {  // where do the Retracting tasks sit in their queues?  (mapping.rs:66-80 treats them apart)
-        const uint32_t nr = s->n_retracting;
-        if (!ctx->h_retr.ensure((size_t)nr * 16 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc retracting");
-        memcpy(ctx->h_retr.p, s->retracting_task, (size_t)nr * 8);
-        uint8_t *rd = ctx->h_retr.dev<uint8_t>();
-        if (sc->run_cnt.empty()) { uint32_t *k = reinterpret_cast<uint32_t *>(ctx->h_retr.as<uint8_t>() + (size_t)nr * 8); for (uint32_t i = 0; i < nr; i++) k[i] = 0xFFFFFFFFu; }
-        else {
-            HQ_HIP(hqk::order_rank_of(cols.id, cols.rq, N, ctx->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(rd), nr,
-                                      reinterpret_cast<uint32_t *>(rd + (size_t)nr * 8), reinterpret_cast<uint32_t *>(rd + (size_t)nr * 12), ctx->stream));
-            HQ_HIP(hipStreamSynchronize(ctx->stream));
-        }
-    }
-    return 0;
-}
-
-// GPU phase A: K2 on the real workers, level table (cached across ticks, re-validated by K1), K1 + K1b on the ready set in
-// ctx->ready's columns.  One stream synchronisation in the steady state.
-// `while_gpu_runs` (may be null) is host work that needs only the ADDRESSES of K2's output, run between the launches and the sync.
+// K2 on the real workers and the scan of ctx->ready's columns; `while_gpu_runs` (may be null): hqscan::Scanner::scan
 int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc, const std::function<void()> *while_gpu_runs = nullptr) {
-    const uint32_t W = s->n_workers, R = s->n_resources, Q = s->n_requests;
-    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
-    sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
-    runs_from_hist(*sc);  // (no run until the scan has counted)
-    if (!ctx->d_set.ensure((size_t)(hqk::PRIO_SET_CAP + hqk::MAX_LEVELS) * 8) || !ctx->h_lv.ensure((size_t)(hqk::MAX_LEVELS + 4) * 8) || !ctx->d_flags.ensure(64) || !ctx->d_levels.ensure((size_t)(hqk::MAX_LEVELS + 2) * 8) || !ctx->d_nlevels.ensure(64))   // (a 40-byte head: count + the first four levels, kernels.hip: k_sort_levels)
-        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc phase A");
-    const bool scan = N != 0 && Q != 0;
-    const uint32_t nvs = Q ? s->rq_variant_off[Q] : 0;
-    const size_t nwv = (size_t)W * nvs;
-    ctx->dbg_order = false; ctx->dbg_scan = false; ctx->dbg_census = false;   // (h_a and h_lv are rewritten from here on)
-    // the ordered view where the dense table does not fit: forced (HQTICK_ORDERED_VIEW=1), or the last dense attempt did not fit
-    if (scan && (ctx->force_ordered || ctx->ordered_sticky)) return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs);
-    for (int attempt = 0; attempt < 2; attempt++) {
-        uint32_t L = 0;
-        bool levels_fresh = false;  // the level table was (re)built by this attempt
-        bool spec = false;          // ... and the scan was launched behind the discovery without waiting for it (sized for four levels)
-        if (scan) {
-            if (!ctx->levels_valid) {
-                // (the set and the flag words are EMPTY / zero between ticks: k_sort_levels clears what a discovery used, the scan clears its own flag — the two fills are for
-                // the first discovery of a context and for the one after a tick that did not come back)
-                if (!ctx->set_clean) {
-                    HQ_HIP(hipMemsetAsync(ctx->d_set.p, 0xFF, (size_t)hqk::PRIO_SET_CAP * 8, ctx->stream));
-                    HQ_HIP(hipMemsetAsync(ctx->d_flags.p, 0, 64, ctx->stream));
-                }
-                ctx->set_clean = false;   // until this tick has seen the discovery's result
-                const bool time_k0 = ctx->timing;   // (two marker packets around K0: only when every kernel is timed)
-                if (time_k0) HQ_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
-                HQ_HIP(hqk::distinct_priorities(cols.prio, cols.rq, N, ctx->d_set.as<uint64_t>(), ctx->d_flags.as<uint32_t>(), ctx->stream));
-                levels_fresh = true;
-                if (time_k0) HQ_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
-                // (the sort kernel writes count, flags and the table straight into pinned memory and clears the flag words for the scan: one synchronisation, no copy)
-                volatile uint32_t *hl = ctx->h_lv.as<uint32_t>();
-                const uint32_t lv_seq = ++ctx->lv_seq ? ctx->lv_seq : ++ctx->lv_seq;   // (never 0)
-                hl[0] = 0; hl[1] = 0; hl[2] = 0; hl[3] = 0;
-                HQ_HIP(hqk::sort_levels(ctx->d_set.as<uint64_t>(), ctx->d_flags.as<uint32_t>(), ctx->d_levels.as<uint64_t>(), ctx->d_nlevels.as<uint32_t>(), ctx->h_lv.dev<uint64_t>(), lv_seq, ctx->stream));
-                // SPECULATIVE SCAN (round 6): with at most 4 levels x Q <= 64 groups — the variant of K1 the BASELINE ticks run — the scan is launched right behind the
-                // discovery, sized for four levels, and reads the table and its length from HBM (kernels.h: level_hist, n_levels_dev): no host round trip, no idle GPU
-                // between the two (K1 behind a 15-33 us gap took 6.4-7.2 us against 5.5, profiles/r06).  More than four levels: K1 refuses, the table is read below
-                // and this loop's second pass launches the general variant.
-                // Not with Retracting tasks: k_rank_of reads the group keys K1 leaves, and a refused speculative K1 leaves none (a fresh context's key column is
-                // uninitialised: the keys would index the slice table out of bounds).
-                spec = attempt == 0 && (uint64_t)4 * Q <= 64 && !ctx->no_spec_scan && s->n_retracting == 0;
-                if (spec) L = 4;   // (levels_valid stays false until the table has been read, after the scan)
-                else
-                {   // wait on the kernel's own completion word (the stream synchronisation is the fallback after 2 s)
-                    const double w0 = now_us();
-                    for (uint64_t spins = 0;; spins++) {
-                        if (__atomic_load_n(&ctx->h_lv.as<uint32_t>()[3], __ATOMIC_ACQUIRE) == lv_seq) break;
-                        if ((spins & 0xFFFF) == 0xFFFF && now_us() - w0 > 2.0e6) { HQ_HIP(hipStreamSynchronize(ctx->stream)); if (__atomic_load_n(&ctx->h_lv.as<uint32_t>()[3], __ATOMIC_ACQUIRE) != lv_seq) return fail(ctx, HQTICK_E_DEVICE, "level discovery did not complete"); break; }
-                    }
-                }
-                if (!spec) {
-                L = hl[0];
-                const uint32_t flags[2] = {hl[1], hl[2]};
-                if (flags[1] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) { ctx->ordered_sticky = true; return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs); }  // more than 4096 levels
-                if (L == 0) return fail(ctx, HQTICK_E_DEVICE, "level discovery returned no level");
-                ctx->h_levels.assign(ctx->h_lv.as<uint64_t>() + 2, ctx->h_lv.as<uint64_t>() + 2 + L);
-                ctx->set_clean = true;
-                }
-                float ms = 0;
-                if (!spec && time_k0)
-                if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess || (hipEventSynchronize(ctx->ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess)) ctx->stats.distinct_us = ms * 1000.0;  // (the kernel behind ev[1] has finished: the wait, if the runtime has not noticed yet, is short)
-                if (!spec) { ctx->levels_valid = true; ctx->cached_L = L; }
-            }
-            L = spec ? 4u : ctx->cached_L;
-            uint64_t G64 = (uint64_t)L * Q;
-            if (G64 > hqk::MAX_GROUPS) { ctx->ordered_sticky = true; return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs); }  // levels x requests over 16384 groups
-            sc->L = L; sc->G = (uint32_t)G64;
-        }
-        // host-visible outputs of phase A, written in place by the kernels: [flags 16][hist G*4][vtmc nwv*4][vflags nwv]
-        size_t o_hist = 16, o_tmc = o_hist + (size_t)sc->G * 4, o_fl = o_tmc + nwv * 4, bytes = o_fl + nwv + 16;
-        if (!ctx->h_a.ensure(bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc phase A");
-        unsigned char *h = ctx->h_a.as<unsigned char>(), *hd = ctx->h_a.dev<unsigned char>();
-        memset(h, 0, 16);
-        // K2 reads the packed tables from pinned memory; with a ready set to scan it rides along the K1 launch
-        bool scan_is_last = false;  // K1b was launched and nothing follows it on the stream
-        UpView uv; int rc;
-        if (ctx->ws.valid()) { if ((rc = cluster_fail(ctx, ctx->ws.tables(ctx->stream, s, W, &uv)))) return rc; }
-        else if ((rc = upload_tables(ctx, s, W, s->worker_total, s->worker_free, s->worker_remaining_ns, ctx->h_up, &uv))) return rc;
-        hqk::WorkerEvalArgs wea{uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc)};
-        if (scan) {
-            hqk::WaveGeom &g = sc->geom;
-            g.waves_per_block = sc->G <= hqk::MAX_GROUPS_4W ? 4 : 1;
-            uint64_t tpw = ctx->tpw_hint ? ctx->tpw_hint : 256;
-            while (((N + tpw - 1) / tpw) * sc->G > (1ull << 24)) tpw *= 2;  // keep the per-slice table under 64 MiB
-            if (!ctx->tpw_hint) while ((N + tpw - 1) / tpw > 32768) tpw *= 2;  // and the rows K1b scans short: one wavefront scans a row of n_waves entries, 4096 per
-                                                                                 // step (64 M tasks at 256 per slice: 250 k entries = 400 us for K1b against 160 us for K1;
-                                                                                 // 32 k slices of 2048 tasks keep K1 / K4 at 8 k workgroups and K1b at 8 steps)
-            g.tasks_per_wave = (uint32_t)tpw; g.n_waves = (uint32_t)((N + tpw - 1) / tpw); g.tab_stride = (g.n_waves + 15u) & ~15u;
-            if (!ctx->d_wave_tab.ensure((size_t)g.tab_stride * sc->G * 4) || !ctx->d_gkey.ensure(N * 2 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc histogram");
-            if (ctx->timing || ctx->timing_k1) hqk::time_next_launch(ctx->ev[2], ctx->ev[3]);
-            if (ctx->k2_own_stream) HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream2));
-            HQ_HIP_TIMED(hqk::level_hist(cols.prio, cols.rq, N, ctx->d_levels.as<uint64_t>(), ctx->h_levels.data(), L, Q, g, ctx->d_wave_tab.as<uint32_t>(),
-                                   ctx->d_gkey.as<uint16_t>(), ctx->d_flags.as<uint32_t>() + 2, ctx->k2_on_hist ? &wea : nullptr, ctx->stream, spec ? ctx->d_nlevels.as<uint32_t>() : nullptr));
-            hqk::time_next_launch((ctx->timing && !spec) ? ctx->ev[0] : nullptr, ctx->ev[8]);  // ev[8]: K1b's completion — what the host waits on below
-            HQ_HIP_LAST(hqk::scan_waves(ctx->d_wave_tab.as<uint32_t>(), g, sc->G, reinterpret_cast<uint32_t *>(hd + o_hist), ctx->d_flags.as<uint32_t>() + 2,
-                                   reinterpret_cast<uint32_t *>(hd) + 2, ctx->stream, (ctx->k2_own_stream || ctx->k2_on_hist) ? nullptr : &wea), scan_is_last);
-            if (s->n_retracting) scan_is_last = false;  // k_rank_of follows
-            if (s->n_retracting) {  // where do the Retracting tasks sit in their queues?  (mapping.rs:66-80 treats them apart)
-                const uint32_t nr = s->n_retracting;
-                if (!ctx->h_retr.ensure((size_t)nr * 16 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc retracting");
-                memcpy(ctx->h_retr.p, s->retracting_task, (size_t)nr * 8);
-                uint8_t *rd = ctx->h_retr.dev<uint8_t>();
-                HQ_HIP(hqk::rank_of(cols.id, ctx->d_gkey.as<uint16_t>(), N, ctx->d_wave_tab.as<uint32_t>(), g, reinterpret_cast<const uint64_t *>(rd), nr,
-                                    reinterpret_cast<uint32_t *>(rd + (size_t)nr * 8), reinterpret_cast<uint32_t *>(rd + (size_t)nr * 12), ctx->stream));
-            }
-        } else {
-            HQ_HIP(hqk::worker_eval(uv.total, uv.free_, uv.rem, W, R, uv.rt, uv.n_entries, hd + o_fl, reinterpret_cast<uint32_t *>(hd + o_tmc), ctx->stream));
-        }
-        ev->flags = h + o_fl; ev->tmc = reinterpret_cast<const uint32_t *>(h + o_tmc);
-        if (while_gpu_runs) (*while_gpu_runs)();
-        if (scan && scan_is_last) HQ_HIP(hipEventSynchronize(ctx->ev[8])); else HQ_HIP(hipStreamSynchronize(ctx->stream));
-        if (scan && ctx->k2_own_stream) HQ_HIP(hipStreamSynchronize(ctx->stream2));
-        const uint32_t *flags = reinterpret_cast<const uint32_t *>(h);
-        if (spec) {   // the discovery's own results, now that everything behind it has finished too
-            const uint32_t *hl = ctx->h_lv.as<uint32_t>();
-            const uint32_t La = hl[0];
-            if (hl[2] || La == 0xFFFFFFFFu || La > hqk::MAX_LEVELS) {  // more than 4096 levels:
-                // the view.  while_gpu_runs runs again: it has published the ADDRESSES of K2's output in the dense layout of h_a, and phase_a_ordered lays
-                // h_a out anew (fill_problem is idempotent)
-                ctx->levels_valid = false; ctx->ordered_sticky = true; return phase_a_ordered(ctx, s, ev, sc, while_gpu_runs);
-            }
-            if (La == 0) { ctx->levels_valid = false; return fail(ctx, HQTICK_E_DEVICE, "level discovery returned no level"); }
-            ctx->h_levels.assign(ctx->h_lv.as<uint64_t>() + 2, ctx->h_lv.as<uint64_t>() + 2 + La);
-            ctx->levels_valid = true; ctx->cached_L = La; ctx->set_clean = true;
-            float ms = 0;
-            if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->stats.distinct_us = ms * 1000.0;
-            if ((flags[2] & 4u) || La > 4) continue;   // more levels than the speculative launch was sized for: the table is known now, scan again with the right variant
-            sc->L = La; sc->G = La * Q;                // (group keys and the rows of the per-slice table do not depend on how many levels the launch was sized for)
-        }
-        if (scan && (flags[2] & 2u)) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
-        if (scan && (flags[2] & 1u)) {  // a priority the cached level table does not know: rebuild the table once
-            ctx->levels_valid = false;
-            if (attempt == 0) continue;
-            return fail(ctx, HQTICK_E_DEVICE, "level table inconsistent with the ready set");
-        }
-        ev->flags = h + o_fl; ev->tmc = reinterpret_cast<const uint32_t *>(h + o_tmc);
-        if (scan) {
-            sc->levels = ctx->h_levels;
-            sc->hist.assign(reinterpret_cast<const uint32_t *>(h + o_hist), reinterpret_cast<const uint32_t *>(h + o_hist) + sc->G);
-            // A level without a single task (its tasks were handed out or cancelled since the table was built — or the table was built from a column that
-            // was still being written) only costs: more groups, and beyond 4 levels / 2048 groups the slower kernel variants.  This tick is right either
-            // way (empty levels take part in nothing); the next one rediscovers the levels.
-            for (uint32_t l = 0; l < sc->L && ctx->levels_valid && !levels_fresh; l++) {  // (a table built in this very tick is not questioned: no rediscovery loop)
-                uint64_t tot = 0;
-                for (uint32_t q = 0; q < Q; q++) tot += sc->hist[(size_t)l * Q + q];
-                if (tot == 0) ctx->levels_valid = false;
-            }
-            if (ctx->timing || ctx->timing_k1) { const double us_ = elapsed_us(ctx->ev[2], ctx->ev[3]); if (us_ >= 0) ctx->stats.level_hist_us = us_; }
-            if (ctx->timing && !spec) { const double us_ = elapsed_us(ctx->ev[0], ctx->ev[8]); if (us_ >= 0) ctx->stats.scan_us = us_; }  // (a speculative scan shares ev[0] with the discovery: K1b untimed on that tick)
-        }
-        if (scan) {
-            ctx->dbg_scan = true; ctx->dbg_scan_L = sc->L; ctx->dbg_scan_G = sc->G;
-            ctx->dbg_scan_shape[0] = sc->geom.waves_per_block; ctx->dbg_scan_shape[1] = sc->geom.tasks_per_wave; ctx->dbg_scan_shape[2] = sc->geom.n_waves; ctx->dbg_scan_shape[3] = hqk::lds_levels_for(sc->L) ? 1u : 0u;
-        }
-        runs_from_hist(*sc);
-        return 0;
-    }
-    return 0;
+    TablesOf t{ctx, s};
+    const uint32_t W = s->n_workers, Q = s->n_requests;
+    const int rc = ctx->scan.scan(scan_env(ctx), ctx->ready.cols(), hqscan::Shape{Q, s->n_retracting, s->retracting_task},
+                                  hqscan::Workers{W, s->n_resources, (size_t)W * (Q ? s->rq_variant_off[Q] : 0), worker_tables, &t}, ev, sc, while_gpu_runs);
+    const hqscan::Timings &tm = ctx->scan.timings();
+    if (tm.distinct_us >= 0) ctx->stats.distinct_us = tm.distinct_us;
+    if (tm.level_hist_us >= 0) ctx->stats.level_hist_us = tm.level_hist_us;
+    if (tm.scan_us >= 0) ctx->stats.scan_us = tm.scan_us;
+    return scan_fail(ctx, rc);
 }
 
 // TaskQueue::iter_priority_sizes (taskqueue.rs:273-302) for every request, from the histogram and the prefill sets
@@ -789,7 +515,7 @@ struct TickRun {
     int load_ready_set() {
         if (!use_resident) {
             if (int rc = ready_fail(ctx, ctx->ready.load(ctx->stream, s, true))) return rc;
-            ctx->levels_valid = false;
+            ctx->scan.columns_changed();
         } else if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "hqtick_run_resident without hqtick_upload_ready");
         N = ctx->ready.cols().n;
         return 0;
@@ -928,8 +654,7 @@ struct TickRun {
         if (s->n_retracting) {
             if (N == 0) return fail(ctx, HQTICK_E_INVALID, "retracting tasks without a ready set");
             const uint32_t nr = s->n_retracting;
-            const uint8_t *rh = ctx->h_retr.as<uint8_t>();
-            const uint32_t *rkey = reinterpret_cast<const uint32_t *>(rh + (size_t)nr * 8), *rrank = reinterpret_cast<const uint32_t *>(rh + (size_t)nr * 12);
+            const uint32_t *rkey = ctx->scan.retracting_keys(), *rrank = ctx->scan.retracting_ranks();
             for (uint32_t i = 0; i < nr; i++) {
                 if (rkey[i] == 0xFFFFFFFFu || Q == 0) return fail(ctx, HQTICK_E_INVALID, "a retracting task is not in the ready set");
                 uint32_t q, z;                                                                        // request and position in its queue (levels, then id)
@@ -1204,16 +929,16 @@ struct TickRun {
             if (sc.ordered) {  // the plan into HBM, then K4 on the view (order.hip)
                 HQ_HIP(hqk::copy_pinned_to_hbm(ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4, ctx->stream));
                 hqk::OrderSelect os{};
-                os.task_id = cols.id; os.perm = ctx->d_perm.as<uint32_t>(); os.n_live = sc.run_cnt.empty() ? 0u : sc.run_start.back() + sc.run_cnt.back(); os.Q = Q;
+                os.task_id = cols.id; os.perm = ctx->scan.perm(); os.n_live = sc.run_cnt.empty() ? 0u : sc.run_start.back() + sc.run_cnt.back(); os.Q = Q;
                 os.n_runs = (uint32_t)sc.run_cnt.size(); os.rq_sel_base = d + o_base; os.run_off = d + o_roff; os.run_start = d + o_rst; os.run_rank = d + o_rrk; os.q_tnc = d + o_qtnc;
-                os.sel_task = ctx->d_sel_task.as<uint64_t>(); os.sel_rank = ctx->d_sel_level.as<uint32_t>(); os.err = ctx->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2;
+                os.sel_task = ctx->d_sel_task.as<uint64_t>(); os.sel_rank = ctx->d_sel_level.as<uint32_t>(); os.err = ctx->scan.select_err_dev();
                 ctx->last_os = os;  // (what hqtick_ready_consume_last and the restore of HQTICK_FLAG_CONSUME_IN_TICK replay)
                 if (consume_in_tick) { os.mark_rq = cols.rq; os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 1; }
                 if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
                 HQ_HIP_TIMED(hqk::order_select(os, n_sel, ctx->stream));
             } else {
             if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
-            HQ_HIP_TIMED(hqk::select_scatter(cols.id, ctx->d_gkey.as<uint16_t>(), N, Q, sc.G, sc.geom, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + o_tb,
+            HQ_HIP_TIMED(hqk::select_scatter(cols.id, ctx->scan.group_keys(), N, Q, sc.G, sc.geom, ctx->scan.slice_table(), ctx->h_plan.as<uint32_t>() + o_tb,
                                 d + o_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4,
                                 consume_in_tick ? cols.rq : nullptr, ctx->stream, consume_in_tick ? 1u : 0u));
             }
@@ -1256,7 +981,7 @@ struct TickRun {
                                 reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream, stg), expand_is_last);
             if (!cnt.mn_rq.empty()) expand_is_last = false;  // copies of the multi-node task ids follow
             if (sc.ordered) {  // the selection's guard word follows (order.hip: a position outside its request's segment)
-                HQ_HIP(hipMemcpyAsync(ctx->h_ordh.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2, ctx->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+                HQ_HIP(hipMemcpyAsync(ctx->scan.select_err_host(), ctx->scan.select_err_dev(), 4, hipMemcpyDeviceToHost, ctx->stream));
                 expand_is_last = false;
             }
             // multi-node tasks: the heads of their queues
@@ -1273,7 +998,7 @@ struct TickRun {
             if (expand_is_last) HQ_HIP(hipEventSynchronize(ctx->ev[11])); else HQ_HIP(hipStreamSynchronize(ctx->stream));
             ctx->sweep_inflight = false;
             if (flags[0]) return fail(ctx, HQTICK_E_CAPACITY, "mapping kernel capacity exceeded");
-            if (sc.ordered && ctx->h_ordh.as<uint32_t>()[hqk::ORDER_DIGITS * 256 + 2]) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the selection left its request's segment");
+            if (sc.ordered && *ctx->scan.select_err_host()) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the selection left its request's segment");
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[4], ctx->ev[5]); if (us_ >= 0) ctx->stats.select_us = us_; }
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[1], ctx->ev[6]); if (us_ >= 0) ctx->stats.sweep_us = us_; }
             if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[7], ctx->ev[11]); if (us_ >= 0) ctx->stats.other_us = us_; }
@@ -1327,7 +1052,7 @@ struct TickRun {
     int run() {
         t0 = now_us();
         ctx->ntl = 0;
-        if (ctx->cfg.flags & HQTICK_FLAG_NO_TICK_CACHES) { ctx->levels_valid = false; hqhost::flush_tick_caches(); }  // nothing derived survives from the last tick
+        if (ctx->cfg.flags & HQTICK_FLAG_NO_TICK_CACHES) { ctx->scan.columns_changed(); hqhost::flush_tick_caches(); }  // nothing derived survives from the last tick
         memset(out, 0, sizeof(*out));
         ctx->stats = hqtick_kernel_stats{};
         int rc = validate(ctx, s, !use_resident);
@@ -1408,7 +1133,7 @@ bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx-
 hqasg::Env ledger_env(hqtick_ctx *ctx) {
     const hqready::Cols c = ctx->ready.cols();
     return hqasg::Env{ctx->device, ctx->stream, ctx->ws.rows(), ctx->ws.W(), ctx->ws.R(), c.id, c.prio, c.rq, c.n,
-                      ctx->d_levels.as<uint64_t>(), &ctx->ws.ids(), ctx->ws.flags(), ctx->ws.free_rows()};
+                      ctx->scan.levels_dev(), &ctx->ws.ids(), ctx->ws.flags(), ctx->ws.free_rows()};
 }
 int ledger_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->asg.err; return rc; }
 // a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
@@ -1462,7 +1187,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             } else if (synced && ctx->ready.selection_valid() && !ctx->last_ordered && ctx->last_Q && ctx->h_q.ensure(64)) {
                 uint32_t *cntp = ctx->h_q.as<uint32_t>();
                 cntp[0] = 0;
-                restored = hqk::ready_restore_consumed(ctx->d_gkey.as<uint16_t>(), cols.rq, cols.n, ctx->last_Q, ctx->h_q.dev<uint32_t>(), ctx->stream) == hipSuccess &&
+                restored = hqk::ready_restore_consumed(ctx->scan.group_keys(), cols.rq, cols.n, ctx->last_Q, ctx->h_q.dev<uint32_t>(), ctx->stream) == hipSuccess &&
                            hipStreamSynchronize(ctx->stream) == hipSuccess && cntp[0] <= n_sel;
             }
             // nothing of this tick is left to consume; a restore gives the count back what the tick had subtracted when it launched the selection (the kernel may have run for any part of it)
@@ -1514,7 +1239,6 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) { hipStreamDestroy(ctx->stream); delete ctx; return HQTICK_E_DEVICE; }
     if (const char *e = getenv("HQTICK_K2_RIDE_ALONG")) { ctx->k2_own_stream = atoi(e) == 0; ctx->k2_on_hist = atoi(e) == 1; }
     if (const char *e = getenv("HQTICK_WAIT_ON_KERNEL")) ctx->wait_on_kernel = atoi(e) != 0;
-    if (const char *e = getenv("HQTICK_ORDERED_VIEW")) ctx->force_ordered = atoi(e) != 0;  // (tests: every tick on the ordered view)
     {
         bool price = true; uint32_t min_cols = 0;
         if (const char *e = getenv("HQTICK_PRICE")) price = atoi(e) != 0;
@@ -1527,7 +1251,7 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     if (const char *e = getenv("HQTICK_SHARD_MIN_CLASSES")) { long v = atol(e); if (v >= 0) ctx->shard_min_classes = (uint32_t)v; }
     if (ctx->ws.init()) { delete ctx; return HQTICK_E_DEVICE; }
     for (auto &e : ctx->ev) if (hipEventCreate(&e) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
-    if (!ctx->d_flags.ensure(64) || hipMemset(ctx->d_flags.p, 0, 64) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
+    if (ctx->scan.init()) { delete ctx; return HQTICK_E_DEVICE; }
     *out_ctx = ctx;
     return 0;
 }
@@ -1539,20 +1263,18 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
     delete ctx->pricer; ctx->pricer = nullptr;
-    DevBuf *bufs[] = {&ctx->d_set, &ctx->d_flags, &ctx->d_levels, &ctx->d_nlevels, &ctx->d_wave_tab, &ctx->d_hist,
-                      &ctx->d_up, &ctx->d_vflags, &ctx->d_vtmc, &ctx->d_sel_task, &ctx->d_gkey,
-                      &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_blk, &ctx->d_dbg_rq, &ctx->d_dbg_want,
-                      &ctx->d_ord_hist, &ctx->d_ord_tab, &ctx->d_perm, &ctx->d_perm2, &ctx->d_ord_tiles, &ctx->d_inv};
+    DevBuf *bufs[] = {&ctx->d_up, &ctx->d_vflags, &ctx->d_vtmc, &ctx->d_sel_task, &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_blk};
     for (DevBuf *b : bufs) b->release();
+    ctx->scan.release();
     ctx->ready.release();
     ctx->ws.release();
     if (ctx->qctx) { hqtick_destroy(ctx->qctx); ctx->qctx = nullptr; }
-    if (ctx->vctx) { hqtick_destroy(ctx->vctx); ctx->vctx = nullptr; }
+    if (ctx->view_hooks) { ctx->view_hooks->release(); delete ctx->view_hooks; ctx->view_hooks = nullptr; }
     hipSetDevice(ctx->device);
     if (ctx->comm) { rccl_destroy_comm(ctx); }
     ctx->graph.release();
     ctx->asg.release_all();
-    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_a.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_retr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release(); ctx->h_lv.release(); ctx->h_ord.release(); ctx->h_ordh.release();
+    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1573,7 +1295,7 @@ int hqtick_upload_ready(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, co
     for (uint64_t i = 0; i < n; i++) if (task_rq[i] == 0xFFFFFFFFu) return fail(ctx, HQTICK_E_INVALID, "request id 0xFFFFFFFF is reserved");
     HQ_HIP(hipSetDevice(ctx->device));
     if (int rc = ready_fail(ctx, ctx->ready.upload(ready_env(ctx), n, task_id, task_priority, task_rq, sorted != 0))) return rc;
-    ctx->levels_valid = false;
+    ctx->scan.columns_changed();
     return 0;
 }
 
@@ -1612,7 +1334,7 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) {
         os.mark_rq = cols.rq; os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 0;
         HQ_HIP(hqk::order_select(os, ctx->ready.selected_count(), ctx->stream));
     } else
-    HQ_HIP(hqk::select_scatter(cols.id, ctx->d_gkey.as<uint16_t>(), cols.n, ctx->last_Q, ctx->last_G, ctx->last_geom, ctx->d_wave_tab.as<uint32_t>(),
+    HQ_HIP(hqk::select_scatter(cols.id, ctx->scan.group_keys(), cols.n, ctx->last_Q, ctx->last_G, ctx->last_geom, ctx->scan.slice_table(),
                                ctx->h_plan.as<uint32_t>() + ctx->last_tb, d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), nullptr, nullptr, 0,
                                cols.rq, ctx->stream));
     return ready_fail(ctx, ctx->ready.consumed(ready_env(ctx)));
@@ -1740,7 +1462,7 @@ int hqtick_graph_blevel(hqtick_ctx *ctx, uint32_t flags, uint32_t *max_level, ui
     if (r < 0) return graph_fail(ctx, r);
     // the ready set's priorities changed: the next tick rediscovers its levels.  A pending hqtick_ready_consume_last is left alone — its replay reads the group keys, the
     // per-slice counters and the plan of the last tick, none of which the priority rewrite touches.
-    if (upd) ctx->levels_valid = false;
+    if (upd) ctx->scan.columns_changed();
     return r;
 }
 
@@ -2039,6 +1761,32 @@ int hqtick_ready_compact(hqtick_ctx *ctx) {
 
 extern "C" {
 
+// The tail of both queries, on the sub-context: the model over the fake workers K2 has evaluated (fresh: free == total), batches from the scan's runs, the solve, and
+// which of the fake workers it loaded  (query.rs:73-81)
+static int solve_on_fake_workers(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, const WorkerEval &ev_real, const WorkerEval &ev_fake, const Scan &sc,
+                                 hqtick_query_result *out) {
+    const uint32_t Q = s->n_requests;
+    hqhost::Problem pb;
+    fill_problem(pb, s, ctx->cfg, ev_real);
+    hqhost::WorkerSet fw;
+    fw.n = fake->n_workers; fw.R = s->n_resources; fw.id = fake->worker_id; fw.total = fake->worker_total; fw.free_ = fake->worker_total;
+    fw.remaining_ns = fake->worker_remaining_ns; fw.min_util = fake->worker_min_utilization; fw.flags = nullptr; fw.group = nullptr;
+    fw.vflags = ev_fake.flags; fw.vtmc = ev_fake.tmc; fw.n_variant_slots = Q ? s->rq_variant_off[Q] : 0;
+    fw.blocked.assign(fw.n, {});
+    hqhost::group_equal_rows(fw, true);
+    pb.custom = &fw;
+    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
+    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
+    DeviceBlocks dev_blocks(ctx);
+    pb.blocks = &dev_blocks; pb.block_min_classes = ctx->block_min_classes; pb.pricer = ctx->pricer;
+    hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
+    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
+    ctx->q_loaded.assign(fake->n_workers, 0);
+    for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) ctx->q_loaded[wc.first] = 1;
+    out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
+    return 0;
+}
+
 // The what-if query runs on the live Core between two ticks (crates/tako/src/control.rs:125-155): it must not disturb what the ctx keeps
 // resident (ready-set columns, level table, the last tick's selection that hqtick_ready_consume_last replays, the dependency graph).  It
 // therefore runs on a private sub-context — same device, own stream and buffers — created on first use.
@@ -2058,76 +1806,15 @@ static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_quer
     int rc = validate(ctx, s, true);
     if (rc) return rc;
     HQ_HIP(hipSetDevice(ctx->device));
-    const uint32_t R = s->n_resources, Q = s->n_requests;
     if ((rc = ready_fail(ctx, ctx->ready.load(ctx->stream, s, false)))) return rc;  // (the query reads no task id)
-    ctx->levels_valid = false;
+    ctx->scan.columns_changed();
     WorkerEval ev_real, ev_fake;
     if ((rc = eval_workers_sync(ctx, s, fake->n_workers, fake->worker_total, fake->worker_total, fake->worker_remaining_ns, &ev_fake))) return rc;  // fresh fake workers: free == total
     Scan sc;
     if ((rc = phase_a(ctx, s, &ev_real, &sc))) return rc;
-    hqhost::Problem pb;
-    fill_problem(pb, s, ctx->cfg, ev_real);
-    hqhost::WorkerSet fw;
-    fw.n = fake->n_workers; fw.R = R; fw.id = fake->worker_id; fw.total = fake->worker_total; fw.free_ = fake->worker_total;
-    fw.remaining_ns = fake->worker_remaining_ns; fw.min_util = fake->worker_min_utilization; fw.flags = nullptr; fw.group = nullptr;
-    fw.vflags = ev_fake.flags; fw.vtmc = ev_fake.tmc; fw.n_variant_slots = Q ? s->rq_variant_off[Q] : 0;
-    fw.blocked.assign(fw.n, {});
-    hqhost::group_equal_rows(fw, true);
-    pb.custom = &fw;
-    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
-    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    DeviceBlocks dev_blocks(ctx);
-    pb.blocks = &dev_blocks; pb.block_min_classes = ctx->block_min_classes; pb.pricer = ctx->pricer;
-    hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
-    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    ctx->q_loaded.assign(fake->n_workers, 0);
-    for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) ctx->q_loaded[wc.first] = 1;  // query.rs:73-81
-    out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
-    return 0;
+    return solve_on_fake_workers(ctx, s, fake, ev_real, ev_fake, sc, out);
 }
 
-// The census of the resident set (census.hip) in place of phase A: level discovery (K0 / K0b) and the count kernel read the columns of `ctx` on ITS
-// stream — behind every add, remove, append and compaction queued there — and write only buffers of the query sub-context `q`; one synchronisation.
-static int census_resident(hqtick_ctx *ctx, hqtick_ctx *q, uint32_t Q, Scan *sc) {
-    sc->Q = Q; sc->L = 0; sc->G = 0; sc->levels.clear(); sc->hist.clear();
-    runs_from_hist(*sc);
-    q->dbg_census = false;
-    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
-    if (N == 0 || Q == 0 || ctx->ready.live() == 0) return 0;
-    const size_t tab_words = 4 + (size_t)std::min<uint64_t>(hqk::MAX_GROUPS, (uint64_t)Q * hqk::MAX_LEVELS);   // [err x 4][counts]: what the census can write for this Q
-    if (!q->d_set.ensure((size_t)(hqk::PRIO_SET_CAP + hqk::MAX_LEVELS) * 8) || !q->h_lv.ensure((size_t)(hqk::MAX_LEVELS + 4) * 8) || !q->d_flags.ensure(64) ||
-        !q->d_levels.ensure((size_t)(hqk::MAX_LEVELS + 2) * 8) || !q->d_nlevels.ensure(64) || !q->d_hist.ensure((4 + (size_t)hqk::MAX_GROUPS) * 4) || !q->h_a.ensure(tab_words * 4))
-        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc query census");
-    if (!q->set_clean) {   // (k_sort_levels leaves the set EMPTY and the flag words zero behind a discovery that succeeded)
-        HQ_HIP(hipMemsetAsync(q->d_set.p, 0xFF, (size_t)hqk::PRIO_SET_CAP * 8, ctx->stream));
-        HQ_HIP(hipMemsetAsync(q->d_flags.p, 0, 64, ctx->stream));
-    }
-    q->set_clean = false;
-    HQ_HIP(hipMemsetAsync(q->d_hist.p, 0, tab_words * 4, ctx->stream));
-    HQ_HIP(hqk::distinct_priorities(cols.prio, cols.rq, N, q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), ctx->stream));
-    uint32_t *hl = q->h_lv.as<uint32_t>();
-    hl[0] = 0; hl[1] = 0; hl[2] = 0; hl[3] = 0;
-    const uint32_t lv_seq = ++q->lv_seq ? q->lv_seq : ++q->lv_seq;
-    HQ_HIP(hqk::sort_levels(q->d_set.as<uint64_t>(), q->d_flags.as<uint32_t>(), q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->h_lv.dev<uint64_t>(), lv_seq, ctx->stream));
-    HQ_HIP(hqk::ready_census(cols.prio, cols.rq, N, Q, q->d_levels.as<uint64_t>(), q->d_nlevels.as<uint32_t>(), q->d_hist.as<uint32_t>(), ctx->stream));
-    HQ_HIP(hipMemcpyAsync(q->h_a.p, q->d_hist.p, tab_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    const uint32_t L = hl[0];
-    // beyond the dense caps: the ordered view's run table, built on the sub-context's buffers from ctx's columns
-    if (hl[2] || L == 0xFFFFFFFFu || L > hqk::MAX_LEVELS) return build_view(ctx, q, cols.prio, cols.rq, N, Q, ctx->stream, sc, nullptr);
-    q->set_clean = true;
-    if (L == 0) return 0;   // only tombstones
-    if ((uint64_t)L * Q > hqk::MAX_GROUPS) return build_view(ctx, q, cols.prio, cols.rq, N, Q, ctx->stream, sc, nullptr);
-    const uint32_t *h = q->h_a.as<uint32_t>();
-    if (h[0] & 2u) return fail(ctx, HQTICK_E_INVALID, "ready set holds a request id >= n_requests");
-    if (h[0]) return fail(ctx, HQTICK_E_DEVICE, "census: level table inconsistent with the ready set");
-    sc->L = L; sc->G = L * Q;
-    sc->levels.assign(q->h_lv.as<uint64_t>() + 2, q->h_lv.as<uint64_t>() + 2 + L);
-    sc->hist.assign(h + 4, h + 4 + sc->G);
-    q->dbg_census = true; q->dbg_scan_L = sc->L; q->dbg_scan_G = sc->G;
-    runs_from_hist(*sc);
-    return 0;
-}
 
 int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, hqtick_query_result *out, uint64_t *rq_ready) {
     if (!ctx || !out || !fake) return HQTICK_E_INVALID;
@@ -2146,7 +1833,7 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
     sub.prefill_off = nullptr; sub.prefill_priority = nullptr; sub.prefill_task = nullptr; sub.prefill_worker = nullptr;
     sub.n_retracting = 0; sub.retracting_task = nullptr; sub.retracting_worker = nullptr; sub.retracting_redirect_worker = nullptr; sub.retracting_redirect_variant = nullptr;
     if (int rc = validate(ctx, &sub, false)) return rc;
-    const uint32_t R = s->n_resources, Q = s->n_requests;
+    const uint32_t Q = s->n_requests;
     if (s->prefill_off) {   // (queue_levels reads the sizes and priorities of the prefill sets)
         for (uint32_t q = 0; q < Q; q++) if (s->prefill_off[q] > s->prefill_off[q + 1]) return fail(ctx, HQTICK_E_INVALID, "prefill_off not monotone");
         if ((Q ? s->prefill_off[Q] : 0) && !s->prefill_priority) return fail(ctx, HQTICK_E_INVALID, "prefill arrays missing");
@@ -2159,35 +1846,19 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
         if (rc) { ctx->qctx = nullptr; return fail(ctx, rc, "creating the query sub-context failed"); }
     }
     hqtick_ctx *q = ctx->qctx;
+    // the census reads ctx's columns on ctx's stream — behind every add, remove, append and compaction queued there — and writes only the sub-context's scanner
     Scan sc;
-    if (int rc = census_resident(ctx, q, Q, &sc)) return rc;
+    if (int rc = q->scan.census(ctx->stream, ctx->ready.cols(), ctx->ready.live(), Q, &sc)) return fail(ctx, rc, q->scan.err);
     if (rq_ready) {
         for (uint32_t r = 0; r < Q; r++) rq_ready[r] = 0;
         for (uint32_t r = 0; r < Q; r++) for (uint32_t k = sc.run_off[r]; k < sc.run_off[r + 1]; k++) rq_ready[r] += sc.run_cnt[k];
     }
     // batches, model and solve on the sub-context, as hqtick_query
-    int rc;
     WorkerEval ev_real, ev_fake;
-    if ((rc = eval_workers_sync(q, &sub, fake->n_workers, fake->worker_total, fake->worker_total, fake->worker_remaining_ns, &ev_fake))) { ctx->err = q->err; return rc; }
-    hqhost::Problem pb;
-    fill_problem(pb, &sub, q->cfg, ev_real);
-    hqhost::WorkerSet fw;
-    fw.n = fake->n_workers; fw.R = R; fw.id = fake->worker_id; fw.total = fake->worker_total; fw.free_ = fake->worker_total;
-    fw.remaining_ns = fake->worker_remaining_ns; fw.min_util = fake->worker_min_utilization; fw.flags = nullptr; fw.group = nullptr;
-    fw.vflags = ev_fake.flags; fw.vtmc = ev_fake.tmc; fw.n_variant_slots = Q ? s->rq_variant_off[Q] : 0;
-    fw.blocked.assign(fw.n, {});
-    hqhost::group_equal_rows(fw, true);
-    pb.custom = &fw;
-    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, &sub);
-    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    DeviceBlocks dev_blocks(q);
-    pb.blocks = &dev_blocks; pb.block_min_classes = q->block_min_classes; pb.pricer = q->pricer;
-    hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
-    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    q->q_loaded.assign(fake->n_workers, 0);
-    for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) q->q_loaded[wc.first] = 1;  // query.rs:73-81
-    out->n_workers = fake->n_workers; out->is_loaded = q->q_loaded.data(); out->is_optimal = cnt.is_optimal;
-    return 0;
+    int rc = eval_workers_sync(q, &sub, fake->n_workers, fake->worker_total, fake->worker_total, fake->worker_remaining_ns, &ev_fake);
+    if (!rc) rc = solve_on_fake_workers(q, &sub, fake, ev_real, ev_fake, sc, out);
+    if (rc < 0) ctx->err = q->err;
+    return rc;
 }
 
 #ifdef HQTICK_TEST_HOOKS
@@ -2263,71 +1934,69 @@ uint32_t hqtick_debug_last_mn(const uint32_t **rq, const uint32_t **off, const u
 uint32_t hqtick_debug_clock_launches(const hqtick_ctx *ctx) { return ctx ? ctx->ws.clock_launches() : 0u; }
 int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n_levels, double *order_us) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (n_runs) *n_runs = ctx->dbg_order ? ctx->dbg_order_runs : 0;
-    if (n_levels) *n_levels = ctx->dbg_order ? ctx->dbg_order_levels : 0;
-    if (order_us) *order_us = ctx->dbg_order ? ctx->dbg_order_us : 0.0;
-    return ctx->dbg_order ? 1 : 0;
+    const hqscan::Scanner::View &v = ctx->scan.last_view();
+    if (n_runs) *n_runs = v.valid ? v.runs : 0;
+    if (n_levels) *n_levels = v.valid ? v.levels : 0;
+    if (order_us) *order_us = v.valid ? v.us : 0.0;
+    return v.valid ? 1 : 0;
 }
 int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels, uint32_t *n_groups, uint32_t shape[4], uint64_t *levels, uint32_t cap_levels, uint32_t *hist,
                            uint32_t cap_groups) {
     if (!ctx || (which != 0 && which != 1)) return HQTICK_E_INVALID;
-    const hqtick_ctx *c = which == 0 ? ctx : ctx->qctx;
-    if (!c || !(which == 0 ? c->dbg_scan : c->dbg_census)) return 0;
-    const uint32_t L = c->dbg_scan_L, G = c->dbg_scan_G;
-    // both forms keep 16 bytes in front of the counts in h_a: phase A its flag words, the census its four error words
-    const uint64_t *lv = which == 0 ? c->h_levels.data() : c->h_lv.as<uint64_t>() + 2;
-    const uint32_t *hs = reinterpret_cast<const uint32_t *>(c->h_a.as<unsigned char>() + 16);
-    if (n_levels) *n_levels = L;
-    if (n_groups) *n_groups = G;
-    if (shape) for (int i = 0; i < 4; i++) shape[i] = which == 0 ? c->dbg_scan_shape[i] : 0u;
-    if (levels) for (uint32_t i = 0; i < L && i < cap_levels; i++) levels[i] = lv[i];
-    if (hist) for (uint32_t i = 0; i < G && i < cap_groups; i++) hist[i] = hs[i];
+    if (which == 1 && !ctx->qctx) return 0;
+    const hqscan::Scanner::Dense d = which == 0 ? ctx->scan.last_dense() : ctx->qctx->scan.last_census();  // what the last dense scan / the last census (on the query sub-context) left
+    if (!d.valid) return 0;
+    if (n_levels) *n_levels = d.L;
+    if (n_groups) *n_groups = d.G;
+    if (shape) for (int i = 0; i < 4; i++) shape[i] = d.shape[i];
+    if (levels) for (uint32_t i = 0; i < d.L && i < cap_levels; i++) levels[i] = d.levels[i];
+    if (hist) for (uint32_t i = 0; i < d.G && i < cap_groups; i++) hist[i] = d.hist[i];
     return 1;
 }
-// The ordered view by itself ("The view hooks"): built by build_view on a sub-context of its own, so that ctx keeps its permutation, its pending
-// selection, ordered_sticky, levels_valid and its dbg_* fields; every device array comes back by one copy, here and nowhere on a tick's path.
+// The ordered view by itself ("The view hooks"): built by a scanner of its own (ViewHooks), so that ctx keeps its permutation, its pending selection, its
+// sticky flag and its level table; every device array comes back by one copy, here and nowhere on a tick's path.
 int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t counts[4], uint32_t *perm, uint32_t *inv, uint32_t *lrank, uint64_t cap_slots, uint32_t *run_rq,
                             uint32_t *run_start, uint32_t *run_rank, uint64_t *run_prio, uint32_t cap_runs) {
     if (!ctx || !counts) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
     HQ_HIP(hipSetDevice(ctx->device));
-    if (!ctx->vctx) {
-        hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
-        int rc = hqtick_create(&cfg, &ctx->vctx);
-        if (rc) { ctx->vctx = nullptr; return fail(ctx, rc, "creating the view sub-context failed"); }
+    if (!ctx->view_hooks) {
+        ctx->view_hooks = new ViewHooks();
+        if (int rc = ctx->view_hooks->scan.init()) { delete ctx->view_hooks; ctx->view_hooks = nullptr; return fail(ctx, rc, "creating the view sub-context failed"); }
     }
-    hqtick_ctx *v = ctx->vctx;
+    ViewHooks *v = ctx->view_hooks;
     const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
-    v->dbg_view.valid = false; v->dbg_view.rq_copy = false; v->dbg_order = false; v->dbg_order_passes = 0;
+    v->valid = false; v->rq_copy = false;
     for (int i = 0; i < 4; i++) counts[i] = 0;
     Scan sc;
-    if (int rc = build_view(ctx, v, cols.prio, cols.rq, N, n_requests, ctx->stream, &sc, nullptr)) return rc;
+    hqscan::Env env{}; env.stream = ctx->stream;  // (untimed)
+    if (int rc = v->scan.view(env, cols, n_requests, &sc)) return fail(ctx, rc, v->scan.err);
     const uint32_t nr = (uint32_t)sc.run_cnt.size(), n = nr ? sc.run_start.back() + sc.run_cnt.back() : 0u;
-    if ((nr != 0) != v->dbg_order) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the run table and the debug record disagree");
-    counts[0] = n; counts[1] = nr; counts[2] = sc.L; counts[3] = v->dbg_order_passes;
+    if ((nr != 0) != v->scan.last_view().valid) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the run table and the debug record disagree");
+    counts[0] = n; counts[1] = nr; counts[2] = sc.L; counts[3] = v->scan.last_view().passes;
     if (n > cap_slots || N > cap_slots || nr > cap_runs) return fail(ctx, HQTICK_E_CAPACITY, "hqtick_debug_order_view: output arrays too small");
     if (n) {
-        if (perm) HQ_HIP(hipMemcpy(perm, v->d_perm.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (inv) HQ_HIP(hipMemcpy(inv, v->d_inv.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-        if (lrank) HQ_HIP(hipMemcpy(lrank, v->d_inv.as<uint32_t>() + N, (size_t)N * 4, hipMemcpyDeviceToHost));
-        const OrderTabLayout tl = order_tab_layout(n);  // (the run table is in pinned host memory already: build_view has synchronised)
-        const uint8_t *hh = v->h_ord.as<uint8_t>();
+        if (perm) HQ_HIP(hipMemcpy(perm, v->scan.perm(), (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (inv) HQ_HIP(hipMemcpy(inv, v->scan.inv(), (size_t)N * 4, hipMemcpyDeviceToHost));
+        if (lrank) HQ_HIP(hipMemcpy(lrank, v->scan.level_ranks(N), (size_t)N * 4, hipMemcpyDeviceToHost));
+        const hqscan::OrderTabLayout tl = hqscan::order_tab_layout(n);  // (the run table is in pinned host memory already: the view has synchronised)
+        const uint8_t *hh = v->scan.run_table();
         if (run_rq) memcpy(run_rq, hh + tl.o_rq, (size_t)nr * 4);
         if (run_start) memcpy(run_start, hh + tl.o_st, (size_t)nr * 4);
         if (run_rank) memcpy(run_rank, hh + tl.o_rk, (size_t)nr * 4);
         if (run_prio) memcpy(run_prio, hh + tl.o_pr, (size_t)nr * 8);
     }
-    v->dbg_view.ids = cols.id; v->dbg_view.N = N; v->dbg_view.Q = n_requests; v->dbg_view.n_live = n;
-    v->dbg_view.run_off = std::move(sc.run_off); v->dbg_view.run_start = std::move(sc.run_start); v->dbg_view.run_rank = std::move(sc.run_level);
-    v->dbg_view.valid = true;
+    v->ids = cols.id; v->N = N; v->Q = n_requests; v->n_live = n;
+    v->run_off = std::move(sc.run_off); v->run_start = std::move(sc.run_start); v->run_rank = std::move(sc.run_level);
+    v->valid = true;
     return 0;
 }
 
 namespace {
 // the view hqtick_debug_order_view last built, if ctx's columns are still the ones it was built on
-hqtick_ctx *debug_view_of(hqtick_ctx *ctx) {
-    hqtick_ctx *v = ctx->vctx;
-    if (!v || !v->dbg_view.valid || !ctx->ready.resident() || v->dbg_view.ids != ctx->ready.cols().id || v->dbg_view.N != ctx->ready.cols().n) return nullptr;
+ViewHooks *debug_view_of(hqtick_ctx *ctx) {
+    ViewHooks *v = ctx->view_hooks;
+    if (!v || !v->valid || !ctx->ready.resident() || v->ids != ctx->ready.cols().id || v->N != ctx->ready.cols().n) return nullptr;
     return v;
 }
 }  // namespace
@@ -2338,10 +2007,10 @@ hqtick_ctx *debug_view_of(hqtick_ctx *ctx) {
 int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, const uint32_t *q_tnc, uint32_t n_sel, int mark_mode, uint64_t *sel_task, uint32_t *sel_rank,
                               uint32_t *rq_after, uint32_t *err) {
     if (!ctx || !rq_sel_base || !q_tnc || !sel_task || !sel_rank || !err || mark_mode < 0 || mark_mode > 3) return HQTICK_E_INVALID;
-    hqtick_ctx *v = debug_view_of(ctx);
+    ViewHooks *v = debug_view_of(ctx);
     if (!v) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: no view of the current ready set (hqtick_debug_order_view)");
-    const uint32_t Q = v->dbg_view.Q, n = v->dbg_view.n_live, nr = (uint32_t)v->dbg_view.run_start.size();
-    const uint64_t N = v->dbg_view.N;
+    const uint32_t Q = v->Q, n = v->n_live, nr = (uint32_t)v->run_start.size();
+    const uint64_t N = v->N;
     if (Q == 0 || n_sel == 0 || n == 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: nothing to select from");
     if (rq_sel_base[0] != 0 || rq_sel_base[Q] != n_sel) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: rq_sel_base does not span [0, n_sel]");
     for (uint32_t q = 0; q < Q; q++) {
@@ -2352,34 +2021,34 @@ int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, cons
         for (uint32_t p = 0; p < take && p < nw * c; p++)
             if ((uint64_t)(p % nw) * c + p / nw >= take) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: a worker-major destination leaves its request's range");
     }
-    if (mark_mode == 2 && !v->dbg_view.rq_copy) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: restore needs the copy a consume left");
+    if (mark_mode == 2 && !v->rq_copy) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: restore needs the copy a consume left");
     HQ_HIP(hipSetDevice(ctx->device));
     // the tables in HBM, as a tick's plan carries them: [rq_sel_base Q + 1][run_off Q + 1][q_tnc Q][run_start nr][run_rank nr]
     std::vector<uint32_t> tab;
     tab.insert(tab.end(), rq_sel_base, rq_sel_base + Q + 1);
-    tab.insert(tab.end(), v->dbg_view.run_off.begin(), v->dbg_view.run_off.end());
+    tab.insert(tab.end(), v->run_off.begin(), v->run_off.end());
     tab.insert(tab.end(), q_tnc, q_tnc + Q);
-    tab.insert(tab.end(), v->dbg_view.run_start.begin(), v->dbg_view.run_start.end());
-    tab.insert(tab.end(), v->dbg_view.run_rank.begin(), v->dbg_view.run_rank.end());
-    if (!v->d_map.ensure(tab.size() * 4 + 16) || !v->d_sel_task.ensure((size_t)n_sel * 8 + 16) || !v->d_sel_level.ensure((size_t)n_sel * 4 + 16) || !v->d_dbg_rq.ensure(N * 4 + 8))
+    tab.insert(tab.end(), v->run_start.begin(), v->run_start.end());
+    tab.insert(tab.end(), v->run_rank.begin(), v->run_rank.end());
+    if (!v->d_map.ensure(tab.size() * 4 + 16) || !v->d_sel_task.ensure((size_t)n_sel * 8 + 16) || !v->d_sel_rank.ensure((size_t)n_sel * 4 + 16) || !v->d_rq.ensure(N * 4 + 8))
         return fail(ctx, HQTICK_E_DEVICE, "hipMalloc view selection");
     HQ_HIP(hipMemcpy(v->d_map.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-    uint32_t *derr = v->d_ord_hist.as<uint32_t>() + hqk::ORDER_DIGITS * 256 + 2;
+    uint32_t *derr = v->scan.select_err_dev();
     HQ_HIP(hipMemsetAsync(derr, 0, 4, ctx->stream));
     HQ_HIP(hipMemsetAsync(v->d_sel_task.p, 0xFF, (size_t)n_sel * 8, ctx->stream));   // the sentinel: a j the kernel did not write stays 0xFF..FF
-    HQ_HIP(hipMemsetAsync(v->d_sel_level.p, 0xFF, (size_t)n_sel * 4, ctx->stream));
-    if (mark_mode != 2) { HQ_HIP(hipMemcpyAsync(v->d_dbg_rq.p, ctx->ready.cols().rq, N * 4, hipMemcpyDeviceToDevice, ctx->stream)); v->dbg_view.rq_copy = true; }
+    HQ_HIP(hipMemsetAsync(v->d_sel_rank.p, 0xFF, (size_t)n_sel * 4, ctx->stream));
+    if (mark_mode != 2) { HQ_HIP(hipMemcpyAsync(v->d_rq.p, ctx->ready.cols().rq, N * 4, hipMemcpyDeviceToDevice, ctx->stream)); v->rq_copy = true; }
     const uint32_t *d = v->d_map.as<uint32_t>();
     hqk::OrderSelect os{};
-    os.task_id = ctx->ready.cols().id; os.perm = v->d_perm.as<uint32_t>(); os.n_live = n; os.Q = Q; os.n_runs = nr;
+    os.task_id = ctx->ready.cols().id; os.perm = v->scan.perm(); os.n_live = n; os.Q = Q; os.n_runs = nr;
     os.rq_sel_base = d; os.run_off = d + (Q + 1); os.q_tnc = d + 2 * (size_t)(Q + 1); os.run_start = os.q_tnc + Q; os.run_rank = os.run_start + nr;
-    os.sel_task = v->d_sel_task.as<uint64_t>(); os.sel_rank = v->d_sel_level.as<uint32_t>(); os.err = derr;
-    if (mark_mode) { os.mark_rq = v->d_dbg_rq.as<uint32_t>(); os.mark_value = mark_mode == 2 ? 0u : hqk::RQ_TOMBSTONE; os.mark_and_select = mark_mode == 3 ? 1u : 0u; }
+    os.sel_task = v->d_sel_task.as<uint64_t>(); os.sel_rank = v->d_sel_rank.as<uint32_t>(); os.err = derr;
+    if (mark_mode) { os.mark_rq = v->d_rq.as<uint32_t>(); os.mark_value = mark_mode == 2 ? 0u : hqk::RQ_TOMBSTONE; os.mark_and_select = mark_mode == 3 ? 1u : 0u; }
     HQ_HIP(hqk::order_select(os, n_sel, ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     HQ_HIP(hipMemcpy(sel_task, v->d_sel_task.p, (size_t)n_sel * 8, hipMemcpyDeviceToHost));
-    HQ_HIP(hipMemcpy(sel_rank, v->d_sel_level.p, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
-    if (rq_after) HQ_HIP(hipMemcpy(rq_after, v->d_dbg_rq.p, N * 4, hipMemcpyDeviceToHost));
+    HQ_HIP(hipMemcpy(sel_rank, v->d_sel_rank.p, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
+    if (rq_after) HQ_HIP(hipMemcpy(rq_after, v->d_rq.p, N * 4, hipMemcpyDeviceToHost));
     HQ_HIP(hipMemcpy(err, derr, 4, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2387,15 +2056,15 @@ int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, cons
 // k_order_rank_of on that view: (request, position in the view) of the wanted ids against ctx's id and rq columns; 0xFFFFFFFF twice = not a live task of the set
 int hqtick_debug_order_rank_of(hqtick_ctx *ctx, const uint64_t *want, uint32_t n_want, uint32_t *out_rq, uint32_t *out_pos) {
     if (!ctx || (n_want && (!want || !out_rq || !out_pos))) return HQTICK_E_INVALID;
-    hqtick_ctx *v = debug_view_of(ctx);
+    ViewHooks *v = debug_view_of(ctx);
     if (!v) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_rank_of: no view of the current ready set (hqtick_debug_order_view)");
     if (n_want == 0) return 0;
-    if (v->dbg_view.n_live == 0) { for (uint32_t i = 0; i < n_want; i++) out_rq[i] = out_pos[i] = 0xFFFFFFFFu; return 0; }  // (as phase A: no view, no launch)
+    if (v->n_live == 0) { for (uint32_t i = 0; i < n_want; i++) out_rq[i] = out_pos[i] = 0xFFFFFFFFu; return 0; }  // (as phase A: no view, no launch)
     HQ_HIP(hipSetDevice(ctx->device));
-    if (!v->d_dbg_want.ensure((size_t)n_want * 16 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc wanted ids");
-    uint8_t *dw = v->d_dbg_want.as<uint8_t>();
+    if (!v->d_want.ensure((size_t)n_want * 16 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc wanted ids");
+    uint8_t *dw = v->d_want.as<uint8_t>();
     HQ_HIP(hipMemcpy(dw, want, (size_t)n_want * 8, hipMemcpyHostToDevice));
-    HQ_HIP(hqk::order_rank_of(ctx->ready.cols().id, ctx->ready.cols().rq, v->dbg_view.N, v->d_inv.as<uint32_t>(), reinterpret_cast<const uint64_t *>(dw), n_want,
+    HQ_HIP(hqk::order_rank_of(ctx->ready.cols().id, ctx->ready.cols().rq, v->N, v->scan.inv(), reinterpret_cast<const uint64_t *>(dw), n_want,
                               reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 8), reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 12), ctx->stream));
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     HQ_HIP(hipMemcpy(out_rq, dw + (size_t)n_want * 8, (size_t)n_want * 4, hipMemcpyDeviceToHost));
@@ -2550,7 +2219,6 @@ int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     HQ_HIP(hipSetDevice(ctx->device));
     const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n; const hqk::WaveGeom g = ctx->last_geom;
     const uint32_t *d = ctx->d_map.as<uint32_t>();
-    uint32_t *hist_dev = reinterpret_cast<uint32_t *>(ctx->h_a.dev<unsigned char>() + 16);
     if (which == 2) {  // calibration: an EMPTY kernel of K1's grid, each launch bracketed by its own start / stop events like the stats pass of a tick
         double sum = 0.0; int cnt = 0;
         for (int i = 0; i < iters; i++) {
@@ -2569,9 +2237,8 @@ int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     if (as_graph) HQ_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     else HQ_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
     for (int i = 0; i < iters; i++) {
-        if (which == 0) HQ_HIP(hqk::level_hist(cols.prio, cols.rq, N, ctx->d_levels.as<uint64_t>(), ctx->h_levels.data(), ctx->last_L, ctx->last_Q, g, ctx->d_wave_tab.as<uint32_t>(),
-                                              ctx->d_gkey.as<uint16_t>(), ctx->d_flags.as<uint32_t>() + 2, nullptr, ctx->stream));
-        else if (which == 1) HQ_HIP(hqk::select_scatter(cols.id, ctx->d_gkey.as<uint16_t>(), N, ctx->last_Q, ctx->last_G, g, ctx->d_wave_tab.as<uint32_t>(), ctx->h_plan.as<uint32_t>() + ctx->last_tb,
+        if (which == 0) { if (int rc = scan_fail(ctx, ctx->scan.relaunch_level_hist(ctx->stream, cols, ctx->last_L, ctx->last_Q, g))) return rc; }
+        else if (which == 1) HQ_HIP(hqk::select_scatter(cols.id, ctx->scan.group_keys(), N, ctx->last_Q, ctx->last_G, g, ctx->scan.slice_table(), ctx->h_plan.as<uint32_t>() + ctx->last_tb,
                                                         d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, ctx->last_plan_bytes, nullptr, ctx->stream));
         else return fail(ctx, HQTICK_E_INVALID, "which: 0 = level_hist, 1 = select_scatter, 2 = empty kernel of level_hist's grid");
     }
@@ -2587,7 +2254,7 @@ int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
         hipGraphExecDestroy(ge); hipGraphDestroy(gr);
     } else HQ_HIP(hipEventRecord(ctx->ev[11], ctx->stream));
     if (which == 0)  // K1 left raw counts in the slice table: turn them back into offsets
-        HQ_HIP(hqk::scan_waves(ctx->d_wave_tab.as<uint32_t>(), g, ctx->last_G, hist_dev, ctx->d_flags.as<uint32_t>() + 2, reinterpret_cast<uint32_t *>(ctx->h_a.dev<unsigned char>()) + 2, ctx->stream));
+        if (int rc = scan_fail(ctx, ctx->scan.relaunch_scan_waves(ctx->stream, g, ctx->last_G))) return rc;
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0;
     HQ_HIP(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));
