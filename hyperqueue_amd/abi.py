@@ -100,6 +100,28 @@ class GraphStatsC(C.Structure):
                 ("hash_capacity", C.c_uint64), ("hash_tombstones", C.c_uint64), ("bytes_hbm", C.c_uint64), ("last_kernel_us", C.c_double)]
 
 
+# hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
+HQ_CHECK_READY, HQ_CHECK_LEDGER, HQ_CHECK_GRAPH, HQ_CHECK_CROSS, HQ_CHECK_STRICT, HQ_CHECK_ALL = 1, 2, 4, 8, 16, 15
+HQ_INV_NAMES = ("HQ_INV_READY_ORDER", "HQ_INV_READY_COUNT", "HQ_INV_LEDGER_HASH", "HQ_INV_LEDGER_ENTRY", "HQ_INV_LEDGER_TOTALS", "HQ_INV_LEDGER_COUNTS",
+                "HQ_INV_LEDGER_PREFILLED", "HQ_INV_LEDGER_FREE", "HQ_INV_LEDGER_MN", "HQ_INV_GRAPH_HASH", "HQ_INV_GRAPH_TOTALS", "HQ_INV_GRAPH_COUNTER",
+                "HQ_INV_X_READY_ASSIGNED", "HQ_INV_X_READY_WAITING", "HQ_INV_X_RETRACTING", "HQ_INV_S_READY_UNKNOWN", "HQ_INV_S_ASSIGNED_WAITING",
+                "HQ_INV_S_RELEASED_NOWHERE")
+globals().update({n: k for k, n in enumerate(HQ_INV_NAMES)})
+HQ_INV_N = len(HQ_INV_NAMES)
+
+
+class CheckReportC(C.Structure):
+    _fields_ = [("checked", C.c_uint32), ("n_failed", C.c_uint32), ("count", C.c_uint64 * HQ_INV_N), ("first", C.c_uint64 * HQ_INV_N), ("kernel_us", C.c_double)]
+
+
+def parse_check_report(r: "CheckReportC") -> dict:
+    """checked, n_failed, kernel_us, and per invariant NAME its count and first; `failed`: {name: (count, first)} of the violated ones"""
+    d = {"checked": int(r.checked), "n_failed": int(r.n_failed), "kernel_us": float(r.kernel_us),
+         "count": {n: int(r.count[k]) for k, n in enumerate(HQ_INV_NAMES)}, "first": {n: int(r.first[k]) for k, n in enumerate(HQ_INV_NAMES)}}
+    d["failed"] = {n: (d["count"][n], d["first"][n]) for n in HQ_INV_NAMES if d["count"][n]}
+    return d
+
+
 class QueryWorkersC(C.Structure):
     _fields_ = [
         ("n_workers", C.c_uint32),

@@ -113,6 +113,8 @@ class Retracting {
     std::string err;
     Reassigned last;  // what the last response() / workers_removed() reassigned
     uint32_t count() const { return (uint32_t)tab.size(); }
+    // every entry, ascending task id, as f(task, in_queue, has_redirect, target worker id, variant): what the audit (audit.h) uploads for its call
+    template <class F> void for_each(F &&f) const { for (const auto &kv : tab) f(kv.first, kv.second.in_queue, kv.second.has_redirect, kv.second.target_id, kv.second.variant); }
     void add(uint32_t n, const uint64_t *task_id, const uint32_t *worker_id);  // process_retracted outside a tick: back in their queue
     int response(uint32_t worker_id, uint32_t n, const uint64_t *task_id);     // on_retract_response -> tasks that left the table
     void workers_removed(uint32_t n, const uint32_t *worker_id);               // on_remove_worker (ids in any order: sorted here, and only if the table holds a task)

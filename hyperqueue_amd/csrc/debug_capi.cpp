@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "audit_core.h"
 #include "clock_core.h"
 #include "hb_order.h"
 #include "milp.h"
@@ -117,6 +118,22 @@ extern "C" int hqtick_debug_clock_rows(uint32_t n, const int64_t *deadline_ns, i
     std::sort(thr.begin(), thr.end()); thr.erase(std::unique(thr.begin(), thr.end()), thr.end());
     for (uint32_t w = 0; w < n; w++) remaining_out[w] = hqclock::canonical_sorted(deadline_ns[w], now_ns, thr.data(), (uint32_t)thr.size());
     return 0;
+}
+// the audit of the resident state on host arrays: audit_core.h's host backend
+extern "C" int hqtick_debug_audit_host(const hqtick_debug_audit_tables *a, uint32_t parts, int order, hqtick_check_report *out) {
+    if (!a || !out || (parts & ~(HQ_CHECK_ALL | HQ_CHECK_STRICT)) || order < 0 || order > 2 || (a->have & ~31u)) return HQTICK_E_INVALID;
+    hqaudit::State S{};
+    S.have = a->have; S.parts = parts;
+    S.ready = hqaudit::Ready{a->ready_id, a->ready_rq, a->ready_n};
+    S.graph = hqaudit::Graph{a->g_id, a->g_unfinished, a->g_gen, a->g_head, a->g_ht_key, a->g_ht_val, a->g_ht_mask, a->g_run_next, a->g_run_off, a->g_run_len, a->g_edge,
+                             a->g_slots, a->g_runs, a->g_edges, a->g_tasks};
+    S.ledger = hqaudit::Ledger{a->l_key, a->l_worker, a->l_rq, a->l_variant, a->l_mask, a->l_rq_off, a->l_ventry_off, a->l_ent_res, a->l_var_nodes, a->l_ent_kind, a->l_ent_amount,
+                               a->l_Q, a->l_NV, a->l_wid, a->l_W, a->l_R, a->l_total, a->l_free, a->l_counts, a->l_stride, a->l_pf, a->l_pf_stride, a->l_mn_task, a->l_mn_root,
+                               a->l_flags, a->l_n_live, a->l_mn_live, a->l_pf_live};
+    S.retr = hqaudit::Retr{a->r_task, a->r_target, a->r_variant, a->r_flags, a->r_n};
+    const hqaudit::Totals t{a->ready_live, a->g_tasks, a->g_free, a->g_slots};
+    hqaudit::run_host(S, t, order, out);
+    return (int)out->n_failed;
 }
 extern "C" int64_t hqtick_debug_clock_deadline(int64_t now_ns, int64_t remaining_ns) { return hqclock::deadline_of(now_ns, remaining_ns); }
 extern "C" int64_t hqtick_debug_clock_remaining(int64_t deadline_ns, int64_t now_ns) { return hqclock::remaining_of(deadline_ns, now_ns); }

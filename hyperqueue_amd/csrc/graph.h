@@ -93,6 +93,10 @@ class Graph {
     uint64_t n_tasks() const { return n_live_; }
     double last_kernel_us() const { return last_us_; }  // GPU time of the dominant kernel of the last operation (HIP events)
     Stats stats() const;
+    // what the audit (audit.h) reads: the tables as they are, whether there are any, and the host's count of the free-slot stack
+    View audit_view() const { return view(); }
+    bool resident() const { return ready_ && ht_cap != 0; }
+    uint32_t free_slots() const { return free_top; }
     std::string err;
 
   private:

@@ -29,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "audit.h"
 #include "block_solve.h"
 #include "cluster.h"
 #include "price_dev.h"
@@ -140,6 +141,8 @@ struct hqtick_ctx {
     uint32_t block_verify = 2, tick_seq = 0;  // HQTICK_BLOCK_VERIFY: classes of a k_block_solve launch the host re-solves while the kernel runs (host_model.h: Problem::block_verify)
     uint64_t x_calls = 0, x_bytes = 0; double x_us = 0;
     double tl[32] = {}; int ntl = 0;  // debug timeline (us since tick start), hqtick_timeline()
+    hqaudit::Auditor audit;  // hqtick_resident_check (audit.h): nothing of it exists until the first call
+    bool check_resident = false; int audit_depth = 0;  // HQTICK_CHECK_RESIDENT=1: the audit behind every call that changes resident state (audit_depth: inside such a call)
 };
 
 namespace {
@@ -1214,6 +1217,40 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
 
 }  // namespace
 
+// HQTICK_CHECK_RESIDENT=1 (debug; read at hqtick_create like HQTICK_CHECK_CLUSTER): every successful call that changes resident state -- ready set, graph, ledger,
+// cluster upload / drop and membership, b-levels, consume, a tick -- ends with the audit of READY | LEDGER | GRAPH, the parts that must hold after every single call (CROSS and STRICT hold only between
+// whole handlers and are never run here).  A violation turns the call's answer into HQTICK_E_INVALID, with the invariant's name and witness in hqtick_last_error;
+// what the call did stays done.  Calls the library makes on itself (a delta that ends in another) are audited once, when the outermost returns.
+// Not audited: hqtick_cluster_update_workers (it stays asynchronous: the next audited call finds what it broke), hqtick_cluster_set_clock / _set_blocked and the
+// hqtick_retracting_* calls (the deadlines, the blocked pairs and the Retracting table are in none of the three parts).
+namespace {
+struct AuditScope {  // inside a call that changes resident state
+    hqtick_ctx *c;
+    explicit AuditScope(hqtick_ctx *ctx) : c(ctx) { if (c) c->audit_depth++; }
+    ~AuditScope() { if (c) c->audit_depth--; }
+};
+int audited(hqtick_ctx *ctx, int rc) {
+    static const char *const names[HQ_INV_N] = {"HQ_INV_READY_ORDER", "HQ_INV_READY_COUNT", "HQ_INV_LEDGER_HASH", "HQ_INV_LEDGER_ENTRY", "HQ_INV_LEDGER_TOTALS", "HQ_INV_LEDGER_COUNTS",
+                                                "HQ_INV_LEDGER_PREFILLED", "HQ_INV_LEDGER_FREE", "HQ_INV_LEDGER_MN", "HQ_INV_GRAPH_HASH", "HQ_INV_GRAPH_TOTALS", "HQ_INV_GRAPH_COUNTER",
+                                                "HQ_INV_X_READY_ASSIGNED", "HQ_INV_X_READY_WAITING", "HQ_INV_X_RETRACTING", "HQ_INV_S_READY_UNKNOWN", "HQ_INV_S_ASSIGNED_WAITING",
+                                                "HQ_INV_S_RELEASED_NOWHERE"};
+    if (!ctx || !ctx->check_resident || ctx->audit_depth || rc < 0) return rc;
+    hqtick_check_report rep;
+    const int arc = hqtick_resident_check(ctx, HQ_CHECK_READY | HQ_CHECK_LEDGER | HQ_CHECK_GRAPH, &rep);
+    if (arc <= 0) return arc < 0 ? arc : rc;
+    std::string m = "HQTICK_CHECK_RESIDENT: the resident state is inconsistent after this call:";
+    for (uint32_t k = 0; k < HQ_INV_N; k++)
+        if (rep.count[k]) m += std::string(" ") + names[k] + " (" + std::to_string(rep.count[k]) + " violations, first key " + std::to_string(rep.first[k]) + ")";
+    return fail(ctx, HQTICK_E_INVALID, m);
+}
+// the body of such a call: `return with_audit(ctx, [&]() -> int { ... });`
+template <class F> int with_audit(hqtick_ctx *ctx, F &&body) {
+    int rc;
+    { AuditScope scope(ctx); rc = body(); }
+    return audited(ctx, rc);
+}
+}  // namespace
+
 // ================================================================================================ C ABI
 extern "C" {
 
@@ -1233,6 +1270,7 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     ctx->timing = (config->flags & HQTICK_FLAG_NO_KERNEL_TIMING) == 0;
     if (const char *e = getenv("HQTICK_TPW")) { long v = atol(e); if (v >= 256 && v <= (1 << 20) && v % 256 == 0) ctx->tpw_hint = (uint32_t)v; }
     if (const char *e = getenv("HQTICK_BLOCK_PROFILE")) ctx->block_profile = atoi(e) != 0;
+    if (const char *e = getenv("HQTICK_CHECK_RESIDENT")) ctx->check_resident = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_BLOCK_BUDGET")) { long v = atol(e); if (v >= 1 && v <= (1 << 24)) ctx->block_budget = (uint32_t)v; }
     if (const char *e = getenv("HQTICK_BLOCK_MIN_CLASSES")) { long v = atol(e); if (v >= 0) ctx->block_min_classes = (uint32_t)v; }
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
@@ -1274,6 +1312,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     if (ctx->comm) { rccl_destroy_comm(ctx); }
     ctx->graph.release();
     ctx->asg.release_all();
+    ctx->audit.release();
     ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
@@ -1283,12 +1322,12 @@ void hqtick_destroy(hqtick_ctx *ctx) {
 
 const char *hqtick_last_error(const hqtick_ctx *ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
 
-int hqtick_run(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, hqtick_result *out) {
+int hqtick_run(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, hqtick_result *out) { return with_audit(ctx, [&]() -> int {
     if (!ctx || !out) return HQTICK_E_INVALID;
     return run_tick(ctx, snapshot, out, false);
-}
+}); }
 
-int hqtick_upload_ready(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq, int sorted) {
+int hqtick_upload_ready(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq, int sorted) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (n && (!task_id || !task_priority || !task_rq)) return fail(ctx, HQTICK_E_INVALID, "null ready-set column");
     if (sorted) for (uint64_t i = 1; i < n; i++) if (task_id[i - 1] >= task_id[i]) return fail(ctx, HQTICK_E_INVALID, "ready set not sorted by task id");
@@ -1297,17 +1336,17 @@ int hqtick_upload_ready(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, co
     if (int rc = ready_fail(ctx, ctx->ready.upload(ready_env(ctx), n, task_id, task_priority, task_rq, sorted != 0))) return rc;
     ctx->scan.columns_changed();
     return 0;
-}
+}); }
 
-int hqtick_run_resident(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, hqtick_result *out) {
+int hqtick_run_resident(hqtick_ctx *ctx, const hqtick_snapshot *snapshot, hqtick_result *out) { return with_audit(ctx, [&]() -> int {
     if (!ctx || !out) return HQTICK_E_INVALID;
     return run_tick(ctx, snapshot, out, true);
-}
+}); }
 
 // ---- the resident ready set's deltas (f1): arguments validated here, the operations are hqready::ReadySet's (ready.h) ----
 uint64_t hqtick_ready_count(const hqtick_ctx *ctx) { return ctx && ctx->ready.resident() ? ctx->ready.live() : 0; }
 
-int hqtick_ready_consume_last(hqtick_ctx *ctx) {
+int hqtick_ready_consume_last(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
     if (ledger_pending_live(ctx)) {  // the last tick's placement enters the assignment ledger (before the selection's request ids become tombstones)
@@ -1338,16 +1377,16 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) {
                                ctx->h_plan.as<uint32_t>() + ctx->last_tb, d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), nullptr, nullptr, 0,
                                cols.rq, ctx->stream));
     return ready_fail(ctx, ctx->ready.consumed(ready_env(ctx)));
-}
+}); }
 
-int hqtick_ready_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) {
+int hqtick_ready_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) { return with_audit(ctx, [&]() -> int {
     if (!ctx || (n && !task_id)) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
     if (n == 0 || ctx->ready.cols().n == 0) return 0;
     if (n > 0x7FFFFFFFull) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^31 - 1 ids in one delta (the count of removed tasks is the int return value)");
     HQ_HIP(hipSetDevice(ctx->device));
     return ready_fail(ctx, ctx->ready.remove(ready_env(ctx), n, task_id));
-}
+}); }
 
 // The batch of new ready tasks is staged in pinned memory (a pageable hipMemcpy of a few MB costs ~1 ms in page pinning).  The caller can write it there
 // directly: hqtick_ready_add_stage hands out the three column pointers for n tasks, hqtick_ready_add_staged merges what was written (no copy on the host);
@@ -1360,14 +1399,13 @@ int hqtick_ready_add_stage(hqtick_ctx *ctx, uint64_t n, uint64_t **task_id, uint
     return ready_fail(ctx, ctx->ready.stage(n, task_id, task_priority, task_rq));
 }
 
-int hqtick_ready_add_staged(hqtick_ctx *ctx, uint64_t n) {
+int hqtick_ready_add_staged(hqtick_ctx *ctx, uint64_t n) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     return ready_fail(ctx, ctx->ready.add_staged(ready_env(ctx), n));
-}
+}); }
 
-int hqtick_ready_add_packed(hqtick_ctx *ctx, uint64_t n, uint32_t n_id_runs, const uint64_t *id_run_start, const uint32_t *id_run_len, const uint32_t *id_off,
-                            uint32_t n_prio_runs, const uint64_t *prio_run_value, const uint32_t *prio_run_len, const uint16_t *task_rq) {
+int hqtick_ready_add_packed(hqtick_ctx *ctx, uint64_t n, uint32_t n_id_runs, const uint64_t *id_run_start, const uint32_t *id_run_len, const uint32_t *id_off, uint32_t n_prio_runs, const uint64_t *prio_run_value, const uint32_t *prio_run_len, const uint16_t *task_rq) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     if (n == 0) return 0;
@@ -1381,9 +1419,9 @@ int hqtick_ready_add_packed(hqtick_ctx *ctx, uint64_t n, uint32_t n_id_runs, con
     if (tot != n) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_add_packed: the priority runs do not add up to n");
     HQ_HIP(hipSetDevice(ctx->device));
     return ready_fail(ctx, ctx->ready.add_packed(ready_env(ctx), n, n_id_runs, id_run_start, id_run_len, id_off, n_prio_runs, prio_run_value, prio_run_len, task_rq));
-}
+}); }
 
-int hqtick_ready_add(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq) {
+int hqtick_ready_add(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq) { return with_audit(ctx, [&]() -> int {
     if (!ctx || (n && (!task_id || !task_priority || !task_rq))) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready with n = 0 creates an empty one)");
     if (n == 0) return 0;
@@ -1391,7 +1429,7 @@ int hqtick_ready_add(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const
     if (int rc = hqtick_ready_add_stage(ctx, n, &hi, &hp, &hq)) return rc;
     memcpy(hi, task_id, n * 8); memcpy(hp, task_priority, n * 8); memcpy(hq, task_rq, n * 4);
     return hqtick_ready_add_staged(ctx, n);
-}
+}); }
 
 // ---------------------------------------------------------------------------------------------- dependency graph (f1)
 namespace {
@@ -1403,8 +1441,7 @@ int graph_pre(hqtick_ctx *ctx) {
 }
 }  // namespace
 
-int hqtick_graph_add_tasks(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq, const uint32_t *dep_off,
-                           const uint64_t *dep_task_id) {
+int hqtick_graph_add_tasks(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, const uint64_t *task_priority, const uint32_t *task_rq, const uint32_t *dep_off, const uint64_t *dep_task_id) { return with_audit(ctx, [&]() -> int {
     if (!ctx || (n && (!task_id || !task_priority || !task_rq))) return HQTICK_E_INVALID;
     if (n && dep_off && dep_off[n] && !dep_task_id) return HQTICK_E_INVALID;
     if (int rc = graph_pre(ctx)) return rc;
@@ -1412,9 +1449,9 @@ int hqtick_graph_add_tasks(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id,
     if (r < 0) return graph_fail(ctx, r);
     if (r > 0) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), (uint32_t)r))) return rc; }
     return r;
-}
+}); }
 
-int hqtick_graph_finish(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) {
+int hqtick_graph_finish(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) { return with_audit(ctx, [&]() -> int {
     if (!ctx || (n && !task_id)) return HQTICK_E_INVALID;
     if (int rc = graph_pre(ctx)) return rc;
     int r = ctx->graph.finish(n, task_id, ctx->stream);
@@ -1423,9 +1460,9 @@ int hqtick_graph_finish(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id) {
     if (rel) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), rel))) return rc; }
     if (r < 0) return graph_fail(ctx, r);
     return r;
-}
+}); }
 
-int hqtick_graph_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, int recursive) {
+int hqtick_graph_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, int recursive) { return with_audit(ctx, [&]() -> int {
     if (!ctx || (n && !task_id)) return HQTICK_E_INVALID;
     if (int rc = graph_pre(ctx)) return rc;
     int r = ctx->graph.remove(n, task_id, recursive != 0, ctx->stream);
@@ -1434,7 +1471,7 @@ int hqtick_graph_remove(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, in
         if (int rc = ready_fail(ctx, ctx->ready.remove_device(ready_env(ctx), ctx->graph.out_id(), (uint32_t)r)); rc < 0) return rc;
     }
     return r;
-}
+}); }
 
 const uint64_t *hqtick_graph_last_ids(const hqtick_ctx *ctx, uint64_t *n) {
     if (!ctx) { if (n) *n = 0; return nullptr; }
@@ -1451,7 +1488,7 @@ int hqtick_graph_unfinished(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id
     return r < 0 ? graph_fail(ctx, r) : 0;
 }
 
-int hqtick_graph_blevel(hqtick_ctx *ctx, uint32_t flags, uint32_t *max_level, uint32_t *n_ready_updated) {
+int hqtick_graph_blevel(hqtick_ctx *ctx, uint32_t flags, uint32_t *max_level, uint32_t *n_ready_updated) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (flags & ~(uint32_t)HQTICK_BLEVEL_UPDATE_READY) return fail(ctx, HQTICK_E_INVALID, "hqtick_graph_blevel: unknown flag");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_DEVICE, "hipSetDevice");
@@ -1464,7 +1501,7 @@ int hqtick_graph_blevel(hqtick_ctx *ctx, uint32_t flags, uint32_t *max_level, ui
     // per-slice counters and the plan of the last tick, none of which the priority rewrite touches.
     if (upd) ctx->scan.columns_changed();
     return r;
-}
+}); }
 
 int hqtick_graph_priorities(hqtick_ctx *ctx, uint64_t n, const uint64_t *task_id, uint64_t *out) {
     if (!ctx || (n && (!task_id || !out))) return HQTICK_E_INVALID;
@@ -1483,7 +1520,7 @@ int hqtick_graph_get_stats(const hqtick_ctx *ctx, hqtick_graph_stats *out) {
 
 // ---- the resident worker set (row f1: the reactor's worker bookkeeping as deltas): arguments validated here, the operations are hqcluster::WorkerSet's
 // and hqcluster::Retracting's (cluster.h), the ledger's steps (ledger.h) interleaved ----
-int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) {
+int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) { return with_audit(ctx, [&]() -> int {
     if (!ctx || !s) return HQTICK_E_INVALID;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
     if (int rc = validate(ctx, s, false)) return rc;
@@ -1491,7 +1528,7 @@ int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) {
     ctx->asg.on = false; ctx->asg.pending = false;  // a new worker set: the ledger is enabled (seeded) again for it
     ctx->asg.take_requests(s);
     return 0;
-}
+}); }
 
 // what opens every delta of the worker set: there is one
 static int cluster_open(hqtick_ctx *ctx, const char *fn) {
@@ -1509,11 +1546,11 @@ int hqtick_cluster_update_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
     return cluster_fail(ctx, ctx->ws.update_rows(ctx->stream, n, worker_index, free_rows, remaining_ns));
 }
 
-int hqtick_cluster_drop(hqtick_ctx *ctx) {
+int hqtick_cluster_drop(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     ctx->ws.drop(); ctx->asg.on = false; ctx->asg.pending = false;
     return 0;
-}
+}); }
 
 // Clock mode: the termination times stay with the worker set and a tick takes only the clock (hqcluster::WorkerSet::set_clock)
 int hqtick_cluster_set_clock(hqtick_ctx *ctx, int64_t now_ns) {
@@ -1534,8 +1571,7 @@ int hqtick_cluster_deadlines(const hqtick_ctx *ctx, uint32_t *n_workers, const i
 uint32_t hqtick_cluster_last_row_groups(const hqtick_ctx *ctx) { return ctx ? ctx->last_row_groups : 0u; }
 
 // Membership changes.  The order of the steps is load-bearing: the ledger's re-pack runs on an Env that already has the new worker count and still has the old mirror.
-int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint64_t *total_rows, const uint64_t *free_rows, const int64_t *remaining_ns,
-                               const float *min_utilization, const uint8_t *flags, const uint32_t *group) {
+int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint64_t *total_rows, const uint64_t *free_rows, const int64_t *remaining_ns, const float *min_utilization, const uint8_t *flags, const uint32_t *group) { return with_audit(ctx, [&]() -> int {
     if (int rc = cluster_open(ctx, "hqtick_cluster_add_workers")) return rc;
     if (n == 0) return 0;
     if (!worker_id || !total_rows || !free_rows) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_add_workers: null array");
@@ -1549,9 +1585,9 @@ int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *work
     ctx->ws.add_rows(n, worker_id, total_rows, free_rows, remaining_ns, min_utilization, flags, group);
     if (ctx->asg.on) return ledger_fail(ctx, ctx->asg.upload_wids(ledger_env(ctx)));
     return 0;
-}
+}); }
 
-int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) {
+int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) { return with_audit(ctx, [&]() -> int {
     if (int rc = cluster_open(ctx, "hqtick_cluster_remove_workers")) return rc;
     if (n == 0) return 0;
     if (!worker_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_cluster_remove_workers: null array");
@@ -1575,7 +1611,7 @@ int hqtick_cluster_remove_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *w
         }
     }
     return 0;
-}
+}); }
 
 int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant) {
     if (!ctx) return HQTICK_E_INVALID;
@@ -1595,7 +1631,7 @@ int hqtick_cluster_workers(const hqtick_ctx *ctx, uint32_t *n_workers, const uin
     return 0;
 }
 
-int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint8_t *flags) {
+int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint8_t *flags) { return with_audit(ctx, [&]() -> int {
     if (int rc = cluster_open(ctx, "hqtick_cluster_set_flags")) return rc;
     if (int rc = ledger_guard(ctx)) return rc;
     if (n == 0) return 0;
@@ -1607,7 +1643,7 @@ int hqtick_cluster_set_flags(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker
     if (int rc = cluster_fail(ctx, ctx->ws.set_flags(n, worker_id, flags, ctx->asg.on))) return rc;
     if (ctx->asg.on) return ledger_fail(ctx, ctx->asg.upload_flags(ledger_env(ctx)));
     return 0;
-}
+}); }
 
 int hqtick_cluster_worker_flags(const hqtick_ctx *cctx, uint32_t *n_workers, const uint8_t **flags) {
     if (!cctx || !cctx->ws.valid()) return HQTICK_E_INVALID;
@@ -1640,20 +1676,20 @@ int hqtick_retract_response(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, con
 uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? ctx->retr.count() : 0u; }
 
 // ---- assignment ledger (ABI 12; include/hqtick.h): arguments validated here, the operations are hqasg::Ledger's (ledger.h) ----
-int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
+int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
     if (!ctx->ws.valid()) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
     if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: null array");
     HQ_HIP(hipSetDevice(ctx->device));
     return ledger_fail(ctx, ctx->asg.enable(ledger_env(ctx), n, task_id, worker_id, rq, variant, priority));
-}
+}); }
 
-int hqtick_assigned_disable(hqtick_ctx *ctx) {
+int hqtick_assigned_disable(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     ctx->asg.on = false; ctx->asg.pending = false;
     return 0;
-}
+}); }
 
 // what opens every ledger delta: the ledger is on (prefilled: and not a replica's; tracked: and tracks prefilled tasks), no placement is pending, the device is set,
 // the arrays of a batch are there and the batch is one the kernels can index
@@ -1669,20 +1705,20 @@ static int ledger_open(hqtick_ctx *ctx, const char *fn, uint32_t n, bool arrays,
     return 0;
 }
 
-int hqtick_assigned_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) {
+int hqtick_assigned_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) { return with_audit(ctx, [&]() -> int {
     if (int rc = ledger_open(ctx, "hqtick_assigned_add", n, task_id && worker_id && rq && variant && priority)) return rc;
     return ledger_fail(ctx, ctx->asg.add(ledger_env(ctx), n, task_id, worker_id, rq, variant, priority));
-}
+}); }
 
-int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) {
+int hqtick_assigned_release(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) { return with_audit(ctx, [&]() -> int {
     if (int rc = ledger_open(ctx, "hqtick_assigned_release", n, task_id)) return rc;
     return ledger_fail(ctx, ctx->asg.release(ledger_env(ctx), n, task_id));
-}
+}); }
 
-int hqtick_assigned_add_mn(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) {
+int hqtick_assigned_add_mn(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) { return with_audit(ctx, [&]() -> int {
     if (int rc = ledger_open(ctx, "hqtick_assigned_add_mn", n, task_id && rq && priority && worker_off)) return rc;
     return ledger_fail(ctx, ctx->asg.add_mn(ledger_env(ctx), n, task_id, rq, priority, worker_off, worker_id));
-}
+}); }
 
 uint64_t hqtick_assigned_mn_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on ? ctx->asg.mn_live : 0; }
 
@@ -1732,30 +1768,77 @@ int hqtick_cluster_last_requeued_prefilled(const hqtick_ctx *ctx, uint32_t *n, c
 }
 
 // ---- prefilled tasks in the ledger (SingleNodeTaskAssignment::prefilled_tasks) ----
-int hqtick_assigned_track_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint64_t *priority) {
+int hqtick_assigned_track_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint64_t *priority) { return with_audit(ctx, [&]() -> int {
     if (int rc = ledger_open(ctx, "hqtick_assigned_track_prefilled", n, task_id && worker_id && rq && priority, true)) return rc;
     return ledger_fail(ctx, ctx->asg.track_prefilled(ledger_env(ctx), n, task_id, worker_id, rq, priority));
-}
+}); }
 
-int hqtick_assigned_start_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint8_t *variant) {
+int hqtick_assigned_start_prefilled(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint8_t *variant) { return with_audit(ctx, [&]() -> int {
     if (int rc = ledger_open(ctx, "hqtick_assigned_start_prefilled", n, task_id && variant, true, true)) return rc;
     return ledger_fail(ctx, ctx->asg.start_prefilled(ledger_env(ctx), n, task_id, variant));
-}
+}); }
 
-int hqtick_assigned_unprefill(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) {
+int hqtick_assigned_unprefill(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) { return with_audit(ctx, [&]() -> int {
     if (int rc = ledger_open(ctx, "hqtick_assigned_unprefill", n, task_id, true, true)) return rc;
     return ledger_fail(ctx, ctx->asg.unprefill(ledger_env(ctx), n, task_id));
-}
+}); }
 
 uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on && ctx->asg.tracking() ? ctx->asg.pf_live : 0; }
 
-int hqtick_ready_compact(hqtick_ctx *ctx) {
+// The audit of the resident state (audit.h): the views of what this context holds, read through const accessors, handed to hqaudit::Auditor.  Nothing here changes
+// the context: no selection or placement is abandoned, no mirror is synchronised, ctx->err is written only when the call itself fails.
+int hqtick_resident_check(hqtick_ctx *ctx, uint32_t parts, hqtick_check_report *out) {
+    if (!ctx || !out) return HQTICK_E_INVALID;
+    if (parts & ~(HQ_CHECK_ALL | HQ_CHECK_STRICT)) return fail(ctx, HQTICK_E_INVALID, "hqtick_resident_check: undefined bit in parts");
+    HQ_HIP(hipSetDevice(ctx->device));
+    hqaudit::State S{};
+    hqaudit::Totals t{};
+    S.parts = parts;
+    if (ctx->ready.resident()) {
+        const hqready::Cols c = ctx->ready.cols();
+        S.ready = hqaudit::Ready{c.id, c.rq, c.n};
+        S.have |= hqaudit::HAVE_READY;
+        t.ready_live = ctx->ready.live();
+    }
+    if (ctx->graph.resident()) {
+        const hqgraph::View v = ctx->graph.audit_view();
+        const hqgraph::Stats st = ctx->graph.stats();
+        S.graph = hqaudit::Graph{v.id, v.unfinished, v.gen, v.head, v.ht_key, v.ht_val, v.ht_mask, v.run_next, v.run_off, v.run_len, reinterpret_cast<const uint32_t *>(v.edge),
+                                 (uint32_t)st.n_slots, (uint32_t)st.n_runs, (uint32_t)st.n_edges_pool, st.n_tasks};
+        S.have |= hqaudit::HAVE_GRAPH;
+        t.graph_tasks = st.n_tasks; t.graph_slots = st.n_slots; t.graph_free = ctx->graph.free_slots();
+    }
+    hqasg::Ledger::AuditView lv{};
+    hqaudit::ReqHost req{};
+    if (ctx->asg.on && ctx->ws.valid() && ctx->asg.audit_view(ledger_env(ctx), &lv)) {
+        hqaudit::Ledger &l = S.ledger;
+        l.key = lv.t.key; l.worker = lv.t.worker; l.rq = lv.t.rq; l.variant = lv.t.variant; l.mask = lv.t.mask;
+        l.wid = lv.r.wid; l.W = lv.r.W; l.R = lv.r.R; l.total = lv.r.total; l.free_ = lv.r.free_; l.counts = lv.r.counts; l.stride = lv.r.stride; l.pf = lv.r.pf; l.pf_stride = lv.r.pf_stride;
+        l.mn_task = lv.m.task; l.mn_root = lv.m.root; l.flags = lv.m.flags;
+        l.n_live = ctx->asg.n_live; l.mn_live = ctx->asg.mn_live; l.pf_live = ctx->asg.pf_live;
+        req = hqaudit::ReqHost{lv.rq_off, lv.vent_off, lv.ent_res, lv.var_nodes, lv.ent_kind, lv.ent_amt};
+        S.have |= hqaudit::HAVE_LEDGER;
+        if (!(ctx->asg.pending && ctx->ready.selection_live())) S.have |= hqaudit::HAVE_LEDGER_SETTLED;  // (a placement waiting for its consume: the Retracting table is already that tick's)
+        if (ctx->asg.tracking()) S.have |= hqaudit::HAVE_TRACKING;
+    }
+    hqaudit::RetrHost retr;
+    if ((parts & HQ_CHECK_CROSS) && ctx->retr.count())
+        ctx->retr.for_each([&](uint64_t task, bool in_queue, bool has_redirect, uint32_t target, uint8_t variant) {
+            retr.task.push_back(task); retr.target.push_back(target); retr.variant.push_back(variant);
+            retr.flags.push_back((uint8_t)((in_queue ? hqaudit::RETR_IN_QUEUE : 0) | (has_redirect ? hqaudit::RETR_REDIRECT : 0)));
+        });
+    const int rc = ctx->audit.run(ctx->stream, S, t, retr, req, out);
+    if (rc < 0) ctx->err = ctx->audit.err;
+    return rc;
+}
+
+int hqtick_ready_compact(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
     if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
     if (ctx->ready.live() == ctx->ready.cols().n) return 0;  // no tombstone
     HQ_HIP(hipSetDevice(ctx->device));
     return ready_fail(ctx, ctx->ready.compact(ready_env(ctx)));
-}
+}); }
 
 }  // extern "C"
 

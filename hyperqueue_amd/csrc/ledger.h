@@ -73,6 +73,13 @@ class Ledger {
     bool dirty() const { return dirty_; }
     const std::vector<uint32_t> &prefilled_host(uint32_t *stride) const { *stride = pf_stride; return h_pf; }  // pf [W x stride] as sync_mirror read it
     Agg agg() const { return Agg{agg_off.data(), agg_rq.data(), agg_cnt.data(), agg_var.data()}; }
+    // what the audit (audit.h) reads: the device tables as they are and the host's request tables; false: no table yet
+    struct AuditView { Table t; Rows r; MnRows m; const std::vector<uint32_t> *rq_off, *vent_off, *ent_res, *var_nodes; const std::vector<uint8_t> *ent_kind; const std::vector<uint64_t> *ent_amt; };
+    bool audit_view(const Env &e, AuditView *v) const {
+        if (!cap || !mn.cur.p || !buf[B_WIDS].p) return false;
+        *v = AuditView{table(), rows(e), mn_rows(mn.cur, e.W, mn_live), &rq_off, &vent_off, &ent_res, &var_nodes, &ent_kind, &ent_amt};
+        return true;
+    }
     void release_all();
 
   private:

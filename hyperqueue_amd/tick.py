@@ -510,6 +510,13 @@ class Tick:
         self._chk(self._lib.hqtick_graph_unfinished(self._ctx, len(a), a.ctypes.data_as(abi.u64p), out.ctypes.data_as(abi.u32p)))
         return out
 
+    def resident_check(self, parts: int = abi.HQ_CHECK_ALL) -> dict:
+        """hqtick_resident_check: the audit of everything resident, on the device (abi.parse_check_report: checked, n_failed, count / first per invariant name, failed)"""
+        self._lib.hqtick_resident_check.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.CheckReportC)]
+        r = abi.CheckReportC()
+        self._chk(self._lib.hqtick_resident_check(self._ctx, parts, C.byref(r)))
+        return abi.parse_check_report(r)
+
     def graph_stats(self) -> dict:
         st = abi.GraphStatsC()
         self._lib.hqtick_graph_get_stats.argtypes = [C.c_void_p, C.POINTER(abi.GraphStatsC)]

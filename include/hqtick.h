@@ -604,6 +604,81 @@ uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx);
 int hqtick_cluster_last_requeued_prefilled(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id);
 
 /*
+ * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
+ * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
+ * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.
+ *   parts     HQ_CHECK_* bits.  A part whose structure is not resident is skipped (it is missing from report.checked); that is not an error.
+ *   returns   report.n_failed (>= 0); HQTICK_E_INVALID for a NULL argument or an undefined bit in parts; HQTICK_E_DEVICE as everywhere else.
+ * The call may come between any two calls on the context, also between hqtick_run_resident and hqtick_ready_consume_last (the state then is the one before the
+ * tick's placement: the selected tasks are still in the ready set and not yet in the ledger).  It changes no resident byte, abandons no pending selection or
+ * placement, and leaves the "valid until the next call" pointers of the other accessors alone.  Works on sharded and replica contexts, for the parts they can hold.
+ * Its scratch (4 B per graph slot, ledger bucket and count-table cell) is allocated at the first call and freed by hqtick_destroy; a context that never calls it
+ * launches and allocates nothing new.
+ * count[] and first[] are integer sums and 64-bit minima: they do not depend on the order in which the device's threads run.
+ *
+ * The invariants, with the key reported in first[]:
+ *   READY   HQ_INV_READY_ORDER       the physical id column ascends strictly (tombstones keep their ids)                 [the id at the first bad position]
+ *           HQ_INV_READY_COUNT       the rows whose request id is not the tombstone number hqtick_ready_count            [the device's count]
+ *   GRAPH   HQ_INV_GRAPH_HASH        every live slot's id is found at that slot through the hash table                    [task id]
+ *           HQ_INV_GRAPH_TOTALS      live slots == n_tasks, and live slots + free stack == slots ever used                [the device's live count]
+ *           HQ_INV_GRAPH_COUNTER     unfinished[c] == the edges into c whose generation matches, over the run chains of live producers — the
+ *                                    assert_eq!(*unfinished_deps, count) of core.rs:353-367; stale edges and producers that left do not count     [task id]
+ *   CROSS   (each evaluated when both of its sides are resident; what must hold whenever no handler is half done)
+ *           HQ_INV_X_READY_ASSIGNED  no live ready id is a live entry of the assignment ledger, of any kind                [task id]
+ *           HQ_INV_X_READY_WAITING   with a non-empty graph: no live ready id is in the graph with a non-zero counter      [task id]
+ *           HQ_INV_X_RETRACTING      per entry of the Retracting table (core.rs:325-347): in_queue => live in the ready set; a redirect, with the ledger
+ *                                    on => a single-node (not prefilled) ledger entry on the target worker with that variant                     [task id]
+ *   STRICT  (opt-in: holds only for a host that keeps EVERY task in the graph; needs a non-empty graph and the ready set or the ledger)
+ *           HQ_INV_S_READY_UNKNOWN     a live ready id that the graph does not hold                                        [task id]
+ *           HQ_INV_S_ASSIGNED_WAITING  a ledger id that the graph does not hold, or holds with a non-zero counter           [task id]
+ *           HQ_INV_S_RELEASED_NOWHERE  a graph task with counter 0 that is neither live in the ready set nor in the ledger; evaluated only with the ledger
+ *                                      and its prefilled tracking on (else skipped: STRICT stays in checked)                                                        [task id]
+ *   LEDGER  (needs the ledger on; Worker::sanity_check server/worker.rs:236-271 and the multi-node arm of Core::sanity_check)
+ *           HQ_INV_LEDGER_HASH       probing for a live bucket's key finds that bucket: catches a duplicate key and an entry cut off by an EMPTY     [task id]
+ *           HQ_INV_LEDGER_ENTRY      a live entry names a resident worker id and a known request; its variant is below the request's variant count (and has
+ *                                    a column in the count table), or 0xFF on a multi-node request, or 0xFE with prefilled tracking on               [task id]
+ *           HQ_INV_LEDGER_TOTALS     the device's census of single-node / multi-node / prefilled entries equals the host's counts
+ *                                                                                                  [sn | mn << 21 | pf << 42 of the census, each saturated]
+ *           HQ_INV_LEDGER_COUNTS     counts[row][slot] == the live single-node entries of that worker and (rq, variant)          [worker id << 32 | slot]
+ *           HQ_INV_LEDGER_PREFILLED  pf[row][rq] == the live prefilled entries of that worker and request, with tracking on        [worker id << 32 | rq]
+ *           HQ_INV_LEDGER_FREE       for every row with HQ_WORKER_SN: free[row][r] == what resources.clone() followed by remove(rq) per assigned task leaves:
+ *                                    0 if a running (rq, variant) has an ALL entry on r, else total - sum of count x amount, saturating at 0 (the product and
+ *                                    the sum saturate, they never wrap).  Computed from the count table and the request tables.  A release batch in the
+ *                                    "B (ALL), then A (AMOUNT)" order (hqtick_assigned_release above) IS reported: the reference's own check asserts on it;
+ *                                    so is a worker over-committed by hqtick_assigned_start_prefilled once its tasks are released   [worker id << 32 | r]
+ *           HQ_INV_LEDGER_MN         a row's multi-node task is a live 0xFF entry; such a row has the SN bit clear and all-zero counts; every multi-node entry
+ *                                    has exactly one root row, whose worker is the entry's.  (SN clear and no task is allowed: hqtick_assigned_add_mn.)
+ *                                                                                                                         [task id, else worker id]
+ * HQTICK_CHECK_RESIDENT=1 in the environment at hqtick_create (debug, like HQTICK_CHECK_CLUSTER): every successful call that changes resident state -- the ready-set,
+ * graph, ledger, cluster and membership calls, the consume, a tick -- ends with the audit of READY | LEDGER | GRAPH, the parts that must hold after every single call (CROSS
+ * and STRICT hold only between whole handlers and are never run in this mode).  A violation makes that call return HQTICK_E_INVALID with the invariant's name
+ * and witness in hqtick_last_error; what the call did stays done.  hqtick_cluster_update_workers stays asynchronous and is not audited itself; nor are
+ * hqtick_cluster_set_clock, hqtick_cluster_set_blocked and the hqtick_retracting_* calls, which change none of the three parts.
+ */
+#define HQ_CHECK_READY   1u    /* the ready set by itself                                   */
+#define HQ_CHECK_LEDGER  2u    /* the ledger with the worker rows and request tables        */
+#define HQ_CHECK_GRAPH   4u    /* the dependency graph by itself                            */
+#define HQ_CHECK_CROSS   8u    /* between structures: what must hold whenever no handler is half done */
+#define HQ_CHECK_STRICT  16u   /* what holds only for a host that keeps EVERY task in the graph and runs ledger + prefilled tracking */
+#define HQ_CHECK_ALL     15u   /* (STRICT is opt-in) */
+enum {
+    HQ_INV_READY_ORDER = 0, HQ_INV_READY_COUNT = 1,
+    HQ_INV_LEDGER_HASH = 2, HQ_INV_LEDGER_ENTRY = 3, HQ_INV_LEDGER_TOTALS = 4, HQ_INV_LEDGER_COUNTS = 5, HQ_INV_LEDGER_PREFILLED = 6, HQ_INV_LEDGER_FREE = 7, HQ_INV_LEDGER_MN = 8,
+    HQ_INV_GRAPH_HASH = 9, HQ_INV_GRAPH_TOTALS = 10, HQ_INV_GRAPH_COUNTER = 11,
+    HQ_INV_X_READY_ASSIGNED = 12, HQ_INV_X_READY_WAITING = 13, HQ_INV_X_RETRACTING = 14,
+    HQ_INV_S_READY_UNKNOWN = 15, HQ_INV_S_ASSIGNED_WAITING = 16, HQ_INV_S_RELEASED_NOWHERE = 17,
+    HQ_INV_N = 18
+};
+typedef struct hqtick_check_report {
+    uint32_t checked;              /* HQ_CHECK_* parts that were asked for AND present */
+    uint32_t n_failed;             /* invariants with count != 0 */
+    uint64_t count[18];            /* [HQ_INV_N] violations per invariant */
+    uint64_t first[18];            /* [HQ_INV_N] the SMALLEST offending key (above), UINT64_MAX when count == 0 */
+    double   kernel_us;            /* HIP-event time of the audit's device work */
+} hqtick_check_report;
+int hqtick_resident_check(hqtick_ctx *ctx, uint32_t parts, hqtick_check_report *out);
+
+/*
  * Device-resident dependency graph (BASELINE config 5): the `Waiting{unfinished_deps}` counters and the consumer
  * sets of tako's task map live in HBM next to the ready set, so a batch of `Finished` updates releases its consumers into the
  * resident ready set on the device.  A resident ready set must exist (hqtick_upload_ready with n = 0 creates an empty one).

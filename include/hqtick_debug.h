@@ -205,6 +205,29 @@ int hqtick_debug_clock_rows(uint32_t n, const int64_t *deadline_ns, int64_t now_
 int64_t hqtick_debug_clock_deadline(int64_t now_ns, int64_t remaining_ns);
 int64_t hqtick_debug_clock_remaining(int64_t deadline_ns, int64_t now_ns);
 uint32_t hqtick_debug_clock_launches(const hqtick_ctx *ctx);
+
+/* The audit of the resident state (hqtick_resident_check; csrc/audit_core.h) on HOST arrays: the same per-item functions the kernels of csrc/audit.hip run, one
+ * emulated thread after the other, the threads of every pass in the given order (0 ascending, 1 descending, 2 a fixed permutation) -- the report must not depend
+ * on it.  `tables` holds what hqtick.cpp hands the auditor of a context, as host pointers with exactly the lengths named; `have`: bit 0 the ready columns, 1 the
+ * graph, 2 the ledger, 3 no placement waits to enter the ledger, 4 prefilled tracking.  kernel_us of the report is 0.  Returns n_failed, or HQTICK_E_INVALID for a
+ * NULL argument, an undefined bit or an order outside 0..2.  Not a product path: hqtick_resident_check has no CPU implementation. */
+typedef struct hqtick_debug_audit_tables {
+    uint32_t have;
+    /* ready set: ready_n physical rows; ready_live = the host's count (hqtick_ready_count) */
+    uint64_t ready_n, ready_live; const uint64_t *ready_id; const uint32_t *ready_rq;
+    /* graph: g_slots slots ever used, g_runs run records, g_edges edge pool entries (g_edge: 2 u32 each), g_free entries on the free stack, g_tasks live tasks (host) */
+    uint32_t g_slots, g_runs, g_edges, g_free, g_ht_mask; uint64_t g_tasks;
+    const uint64_t *g_id; const uint32_t *g_unfinished, *g_gen, *g_head; const uint64_t *g_ht_key; const uint32_t *g_ht_val, *g_run_next, *g_run_off, *g_run_len, *g_edge;
+    /* ledger: table of l_mask + 1 buckets; request tables (Q requests, NV variant slots, entries); W worker rows of R resources; counts [W x l_stride], pf [W x l_pf_stride]
+     * (NULL without tracking); multi-node columns; the host's counts */
+    uint32_t l_mask, l_Q, l_NV, l_W, l_R, l_stride, l_pf_stride; uint64_t l_n_live, l_mn_live, l_pf_live;
+    const uint64_t *l_key; const uint32_t *l_worker, *l_rq; const uint8_t *l_variant;
+    const uint32_t *l_rq_off, *l_ventry_off, *l_ent_res, *l_var_nodes; const uint8_t *l_ent_kind; const uint64_t *l_ent_amount;
+    const uint32_t *l_wid; const uint64_t *l_total, *l_free; const uint32_t *l_counts, *l_pf; const uint64_t *l_mn_task; const uint8_t *l_mn_root, *l_flags;
+    /* Retracting table: r_flags bit 0 in_queue, bit 1 has a redirect (r_target: worker id, r_variant) */
+    uint32_t r_n; const uint64_t *r_task; const uint32_t *r_target; const uint8_t *r_variant, *r_flags;
+} hqtick_debug_audit_tables;
+int hqtick_debug_audit_host(const hqtick_debug_audit_tables *tables, uint32_t parts, int order, hqtick_check_report *out);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
