@@ -9,7 +9,10 @@
 //   H2D   take/base per group, round-robin tables                         (small)
 //   GPU   K4 select+scatter the taken tasks in queue order -> K5 expand to per-worker records
 //   D2H   assignment records
-// There is no CPU implementation of the scans/mapping: without a HIP device every entry point fails.
+// The stages live in modules of their own, each behind a class that owns its buffers and takes a small Env: the ready set (ready.h), phase A (scan.h), the worker
+// set (cluster.h), the ledger (ledger.h), the mapping plan and phase C (map.h; the plan itself, free of HIP, in map_core.h).  This file keeps the context, the
+// sequence of a tick (TickRun::run), the block solvers and the C ABI's argument checks.
+// There is no CPU implementation of the scans or of the selection and the records: without a HIP device every entry point fails.
 #include "../../include/hqtick.h"
 #ifdef HQTICK_TEST_HOOKS
 #include "../../include/hqtick_debug.h"
@@ -41,6 +44,7 @@
 #include "devbuf.h"
 #include "graph.h"
 #include "ledger.h"
+#include "map.h"
 #include "hb_order.h"
 #include "host_model.h"
 #include "kernels.h"
@@ -58,23 +62,6 @@ double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::
 }  // namespace
 
 namespace {
-// Reusable host scratch of the mapping plan (no per-tick allocation in the steady state).
-struct PlanScratch {
-    std::vector<uint32_t> q_total, pf_n, pf_start, seq_taken, pf_drained, zq_taken, new_pf_total, pfl_size, rq_sel_base;
-    std::vector<uint32_t> key_seg, key_sum, key_rq, key_var_w, key_ord_off, ord_cnt, key_t_off, key_bits_off;
-    std::vector<uint32_t> key_tr;   // per key: c > 0 = stored worker-major by K4 (kernels.h: MapKeys::key_tr)
-    std::vector<uint32_t> list_pos, pf_flag, pf_flag_prev, sn_ok, items, n_assign, asg_qw, has_pf, wm_order, pfq_src, pfq_size, out_off, take_base, mn_first, q_tnc;
-    std::vector<uint8_t> now_mn;
-    // the three per-(key | request, worker) tables of the plan are built IN the pinned buffer K4's ride-along workgroups copy from (a memcpy of ~100 KB per
-    // tick otherwise): [wpos nkeys * W][wcnt nkeys * W][pfl_j Q * W] at its head, the small tables behind them (phase_c)
-    uint32_t *wpos = nullptr, *wcnt = nullptr, *pfl_j = nullptr; size_t pfl_rows = 0, plan_head_words = 0;
-    std::vector<uint32_t> sink_hdr;
-    std::vector<uint64_t> holes;                                 // (rq << 32 | logical position) of Retracting tasks taken this tick
-    std::vector<std::pair<uint32_t, uint32_t>> freed;            // (worker, variant slot) given back by re-targeted redirects
-    std::vector<std::pair<uint32_t, uint64_t>> retract_pairs;  // (old worker, task)
-    // cached worker_map iteration order (emulated) for the last worker-id set
-    std::vector<uint32_t> cached_ids, cached_order;
-};
 // The ordered view by itself (hqtick_debug_order_view and the two hooks that run on the view it built): a scanner of its own, so that the context keeps its
 // permutation, its pending selection and its cached level table; what is known of that view; the hooks' scratch in HBM.
 struct ViewHooks {
@@ -99,35 +86,25 @@ struct hqtick_ctx {
     hqready::ReadySet ready;       // hqtick_upload_ready, hqtick_ready_* (ready.h): the ready set's columns in HBM (resident, or a tick's own), their deltas, the last selection's state
     hqhost::BlockMemo block_memo;  // host class blocks of earlier ticks (host_model.h)
     hqscan::Scanner scan;          // GPU phase A (scan.h): the dense scan with its cached level table, the ordered view, the census — on the query sub-context, a query's
-    bool last_ordered = false;    // the pending selection (ready.selection_valid()) is one of the view: consume / restore replay it with order_select
-    hqk::OrderSelect last_os{};   // ... its tables (HBM copy of the plan, the permutation)
+    hqmap::Mapper map;             // the mapping plan and GPU phase C (map.h): the plan's buffers, the records, the result's host part, the last selection's launch state
     bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))
-    PinBuf h_up, h_up2, h_q, h_plan, h_rec, h_sinkhdr, h_blk, h_k5a;
+    PinBuf h_up, h_up2, h_q, h_blk;
     PinBuf h_blkprof; uint32_t n_blkprof = 0; bool block_profile = false;
     hqprice::DeviceSweeper *pricer = nullptr;  // k_price_sweep: the block sweeps of the coupled placement (csrc/price.hip); HQTICK_PRICE=0 keeps coupled ticks on the host search
     uint32_t block_budget = 4096, block_min_classes = 12;  // k_block_solve: search steps per class before the host solver takes it; classes below which the host solves alone
-    // workers / requests
-    DevBuf d_up, d_vflags, d_vtmc, d_blk;
+    DevBuf d_blk;
     hqcluster::WorkerSet ws;      // hqtick_cluster_* (ABI 5 and 7; cluster.h): the worker / request tables resident in HBM and their host mirror
     hqcluster::Retracting retr;   // hqtick_retracting_* (ABI 7): the table of Retracting tasks
     uint32_t last_row_groups = 0; // hqtick_cluster_last_row_groups
-    bool sweep_inflight = false;  // an early K5a launch not yet covered by a stream synchronisation
     bool wait_on_kernel = true;   // HQ_HIP_LAST; HQTICK_WAIT_ON_KERNEL=0: hipStreamSynchronize at every wait (A/B)
-    // selection + mapping
-    DevBuf d_sel_task, d_sel_level, d_map, d_rec, d_tsweep, d_bits, d_pre;
     hqhost::Problem pb;
-    PlanScratch plan;
     // results (host)
     std::vector<uint32_t> b_rq, b_size, b_limit, b_cut_off, c_size, c_bl_off, bl_rq, bl_size; std::vector<uint8_t> b_lr, b_blk;
-    std::vector<uint32_t> cnt_rq, cnt_worker, cnt_value; std::vector<uint8_t> cnt_variant;
-    std::vector<uint32_t> rec_off, retract_off, red_worker, mn_off, mn_worker, mn_rq; std::vector<uint64_t> rec_task, retract_task, red_task, mn_task, new_free;
-    std::vector<uint8_t> rec_variant, rec_kind, red_variant, red_kind, q_loaded;
+    std::vector<uint8_t> q_loaded;
     hqtick_kernel_stats stats{};
     uint32_t tpw_hint = 0;                            // HQTICK_TPW (tuning knob): tasks per wavefront slice
     uint32_t shard_index = 0, shard_count = 1;       // hqtick_set_shard
     void *sink = nullptr; size_t sink_bytes = 0;      // hqtick_set_record_sink (device memory)
-    // launch state of the last tick (hqtick_time_kernel re-launches K1 / K4 on it)
-    hqk::WaveGeom last_geom{}; uint32_t last_L = 0, last_Q = 0, last_G = 0; size_t last_tb = 0, last_plan_bytes = 0, last_hist_off = 0;
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
     hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
@@ -468,51 +445,30 @@ struct ShardedBlocks : hqhost::BlockSolver {
     }
 };
 
-// One tick, stage by stage.  The stages share the plan scratch of the ctx (no per-tick allocation in the steady state) and a handful of
-// sizes; run() is the only entry point and mirrors run_scheduling_inner (scheduler/main.rs:50-72).
+// The mapping (hqmap::Mapper, map.h): what it is given of the context (ev[4] / ev[5] around K4, ev[1] / ev[6] around K5a, ev[7] / ev[11] around K5b — ev[11] is K5b's
+// completion, which the host waits on), and its errors
+hqmap::Env map_env(hqtick_ctx *ctx, double t0 = 0) {
+    return hqmap::Env{ctx->stream, ctx->ev[4], ctx->ev[5], ctx->ev[1], ctx->ev[6], ctx->ev[7], ctx->ev[11], ctx->timing, ctx->wait_on_kernel, ctx->cfg.flags,
+                      ctx->sink, ctx->sink_bytes, ctx->shard_index, ctx->shard_count, hqmap::Timeline{t0, ctx->tl, &ctx->ntl}};
+}
+int map_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->map.err; return rc; }
+bool transpose_enabled() { const char *e = getenv("HQTICK_TRANSPOSE"); return !(e && atoi(e) == 0); }
+
+// One tick, stage by stage: run() is the only entry point and mirrors run_scheduling_inner (scheduler/main.rs:50-72).  The plan's stages are map_core.h's, on the
+// mapper's plan (no per-tick allocation in the steady state); phase C is the mapper's.
 struct TickRun {
     hqtick_ctx *ctx; const hqtick_snapshot *s; hqtick_result *out; const bool use_resident;
-    PlanScratch &ps; hqhost::Problem &pb;
+    hqmap::Plan &ps; hqhost::Problem &pb;
     const uint32_t W, R, Q;
-    static constexpr uint32_t NONE = 0xFFFFFFFFu;
     WorkerEval ev; Scan sc; hqhost::Counts cnt;
-    uint64_t N = 0; uint32_t L = 0; int status = HQTICK_DONE;
-    uint32_t nkeys = 0, max_count = 0, max_nk = 0, n_bit_words = 0, n_sel = 0, n_pfq = 0, n_rec = 0, max_items = 0;
-    std::vector<uint32_t> pfq_rq;                             // requests that prefill in this tick, ascending
-    std::vector<std::pair<uint32_t, uint32_t>> retr_pos;      // (rq, queue position) of every Retracting task
-    std::vector<std::vector<uint32_t>> key_T;                 // lazily built T_k(s) tables of worker_of()
-    size_t o_rv = 0, o_rk = 0, o_mn = 0, o_fl = 0;            // layout of the pinned record buffer
-    bool sweep_launched = false;  // K5a went out right after the key tables (launch_sweep_early)
-    uint32_t n_tr = 0;            // keys K4 stores worker-major (PlanScratch::key_tr)
-    const bool transpose_on = !(getenv("HQTICK_TRANSPOSE") && atoi(getenv("HQTICK_TRANSPOSE")) == 0);
-    bool may_reorder = false;  // the mapping kernel needs its stable sort: several priority levels, Retracting holes or prefilled tasks inside the queues
-    bool compact = false, delta16 = false; size_t o_rs = 0, o_rf = 0; uint32_t max_out = 0;  // compact emission (HQTICK_FLAG_COMPACT_RECORDS / _DELTA16)
-    uint64_t *h_rec_task = nullptr, *mn_ids = nullptr; uint8_t *h_rec_var = nullptr, *h_rec_kind = nullptr;
-    bool assembled = false;
+    uint64_t N = 0; int status = HQTICK_DONE;
     double t0 = 0;
 
     TickRun(hqtick_ctx *c, const hqtick_snapshot *snap, hqtick_result *o, bool resident)
-        : ctx(c), s(snap), out(o), use_resident(resident), ps(c->plan), pb(c->pb), W(snap->n_workers), R(snap->n_resources), Q(snap->n_requests) {}
+        : ctx(c), s(snap), out(o), use_resident(resident), ps(c->map.plan), pb(c->pb), W(snap->n_workers), R(snap->n_resources), Q(snap->n_requests) {}
 
-    void mark() { if (ctx->ntl < 32) ctx->tl[ctx->ntl++] = now_us() - t0; }
-    uint32_t n_groups() const { return sc.ordered ? (uint32_t)sc.run_cnt.size() : sc.G; }  // entries of the selection plan
-
-    // host mirror of the K5 arithmetic: the worker that receives the task at index idx of key k's take_tasks() vector
-    uint32_t worker_of(uint32_t k, uint32_t idx) {
-        cnt.pairs();  // (rare path: redirects)
-        const auto &pk = cnt.per_key[k];
-        std::vector<uint32_t> &T = key_T[k];
-        if (T.empty()) {
-            uint32_t maxc = 0; for (auto &wc : pk) maxc = std::max(maxc, wc.second);
-            std::vector<uint32_t> ge(maxc + 2, 0);
-            for (auto &wc : pk) ge[wc.second]++;
-            uint32_t more = (uint32_t)pk.size(), acc = 0;
-            for (uint32_t sw = 0; sw <= maxc; sw++) { T.push_back(acc); more -= ge[sw]; acc += more; }
-        }
-        uint32_t sw = (uint32_t)(std::upper_bound(T.begin(), T.end(), idx) - T.begin()) - 1, nth = idx - T[sw];
-        for (auto &wc : pk) if (wc.second > sw) { if (nth == 0) return wc.first; nth--; }
-        return HQ_NO_WORKER;
-    }
+    void mark() { hqmap::Timeline{t0, ctx->tl, &ctx->ntl}.mark(); }
+    int plan_fail(int rc, const char *why) { if (rc) ctx->err = why; return rc; }
 
     // the ready set: uploaded with the snapshot, or already resident
     int load_ready_set() {
@@ -524,523 +480,49 @@ struct TickRun {
         return 0;
     }
 
-    // create_task_mapping as index arithmetic, part 1: the take sequence of every queue and the per-key tables  (mapping.rs:36-157)
-    int plan_keys() {
-        L = sc.L;
-        // per request: logical take sequence = [first level][prefilled][rest] when the prefill priority equals the top
-        // priority of the queue, else [prefilled][all levels]   (taskqueue.rs:320-355)
-        ps.q_total.assign(Q, 0); ps.pf_n.assign(Q, 0); ps.pf_start.assign(Q, 0); ps.seq_taken.assign(Q, 0);
-        for (uint32_t q = 0; q < Q; q++) {
-            const uint32_t r0 = sc.run_off[q], r1 = sc.run_off[q + 1];
-            for (uint32_t r = r0; r < r1; r++) ps.q_total[q] += sc.run_cnt[r];
-            ps.pf_n[q] = s->prefill_off ? s->prefill_off[q + 1] - s->prefill_off[q] : 0;
-            if (ps.pf_n[q]) ps.pf_start[q] = (r0 < r1 && sc.run_prio[r0] == s->prefill_priority[q]) ? sc.run_cnt[r0] : 0;
-        }
-        nkeys = (uint32_t)cnt.keys.size();
-        ps.key_seg.assign(nkeys, 0); ps.key_sum.assign(nkeys, 0); ps.key_rq.assign(nkeys, 0); ps.key_var_w.assign((nkeys + 3) / 4 + 1, 0);
-        ps.key_ord_off.assign(nkeys + 1, 0); ps.key_t_off.assign(nkeys + 1, 0); ps.key_bits_off.assign(nkeys + 1, 0);
-        const bool by_class = cnt.by_class && cnt.wclass.size() == W && cnt.key_col.size() == nkeys;
-        ctx->ready.selection_void();  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
-        {   // the big tables live at the head of the pinned plan buffer; everything else of the plan (phase_c) is a few KB behind them
-            ps.plan_head_words = (size_t)nkeys * W * 2 + (size_t)Q * W;
-            size_t n_cnt0 = 0; for (uint32_t k = 0; k < nkeys; k++) n_cnt0 += cnt.key_size(k);
-            const size_t small = (size_t)9 * (nkeys + 4) + n_cnt0 + (size_t)7 * (Q + 2) + (W + 2) + (size_t)4 * n_groups() + (size_t)2 * s->n_retracting + 64 +
-                                 (sc.ordered ? (size_t)3 * (Q + 2) + (size_t)2 * n_groups() + 8 : 0);  // (the view's tables: run_off, q_tnc, run_start, run_rank)
-            if (!ctx->h_plan.ensure((ps.plan_head_words + small) * 4 + 64)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc plan");
-            ps.wpos = ctx->h_plan.as<uint32_t>(); ps.wcnt = ps.wpos + (size_t)nkeys * W; ps.pfl_j = ps.wcnt + (size_t)nkeys * W; ps.pfl_rows = 0;
-        }
-        if (!by_class) { std::fill(ps.wpos, ps.wpos + (size_t)nkeys * W, NONE); std::fill(ps.wcnt, ps.wcnt + (size_t)nkeys * W, 0u); }  // (by class: every row is written in full below)
-        ps.items.assign(W, 0); ps.n_assign.assign(W, 0); ps.asg_qw.assign((size_t)Q * W, 0);
-        size_t n_cnt = 0; for (uint32_t k = 0; k < nkeys; k++) n_cnt += cnt.key_size(k);
-        ctx->cnt_rq.resize(n_cnt); ctx->cnt_variant.resize(n_cnt); ctx->cnt_worker.resize(n_cnt); ctx->cnt_value.resize(n_cnt); ps.ord_cnt.resize(n_cnt);
-        uint32_t *c_rq = ctx->cnt_rq.data(), *c_w = ctx->cnt_worker.data(), *c_v = ctx->cnt_value.data(), *c_ord = ps.ord_cnt.data(); uint8_t *c_var = ctx->cnt_variant.data();
-        size_t ci = 0;
-        max_count = 0; max_nk = 0;
-        if (by_class) {  // position of every worker in each distinct worker list (Map order), built once per list
-            ps.list_pos.assign(cnt.lists.size() * (size_t)W, NONE);
-            for (size_t l = 0; l < cnt.lists.size(); l++) {
-                uint32_t *lp = ps.list_pos.data() + l * W; const std::vector<uint32_t> &wi = cnt.lists[l].widx;
-                for (uint32_t i = 0; i < wi.size(); i++) lp[wi[i]] = i;
-            }
-        }
-        for (uint32_t k = 0; k < nkeys; k++) {
-            const uint32_t q = cnt.keys[k].first; const uint8_t v = cnt.keys[k].second;
-            ps.key_rq[k] = q; reinterpret_cast<uint8_t *>(ps.key_var_w.data())[k] = v;
-            uint32_t sum = 0, maxc = 0, pos = 0;
-            uint32_t *wp = ps.wpos + (size_t)k * W, *wcn = ps.wcnt + (size_t)k * W, *aq = ps.asg_qw.data() + (size_t)q * W, *items = ps.items.data(), *nas = ps.n_assign.data();
-            if (by_class) {  // separable tick: the count of a worker is its class's; sequential passes instead of scattering (worker, count) pairs
-                const uint32_t *xg = cnt.class_x.data() + cnt.key_col[k], *wcl = cnt.wclass.data(); const uint32_t NCc = cnt.n_cols;
-                const std::vector<uint32_t> &wi = cnt.lists[cnt.key_list[k]].widx;
-                if (cnt.one_class) { const uint32_t c = xg[0]; for (uint32_t w = 0; w < W; w++) { wcn[w] = c; items[w] += c; aq[w] += c; } }  // a cold tick on identical workers (vectorises)
-                else for (uint32_t w = 0; w < W; w++) { const uint32_t c = xg[(size_t)wcl[w] * NCc]; wcn[w] = c; items[w] += c; aq[w] += c; }
-                memcpy(wp, ps.list_pos.data() + (size_t)cnt.key_list[k] * W, (size_t)W * 4);
-                pos = (uint32_t)wi.size();
-                std::fill(c_rq + ci, c_rq + ci + pos, q); memset(c_var + ci, v, pos); memcpy(c_w + ci, wi.data(), (size_t)pos * 4);
-                if (cnt.one_class) { const uint32_t c = xg[0]; std::fill(c_v + ci, c_v + ci + pos, c); std::fill(c_ord + ci, c_ord + ci + pos, c); sum = c * pos; maxc = c; }
-                else for (uint32_t i = 0; i < pos; i++) { const uint32_t c = wcn[wi[i]]; c_v[ci + i] = c; c_ord[ci + i] = c; sum += c; maxc = std::max(maxc, c); }
-                ci += pos;
-            } else for (auto &wc : (cnt.pairs(), cnt.per_key[k])) {  // (worker, count) in the Map's iteration order
-                const uint32_t w = wc.first, c = wc.second;
-                sum += c; maxc = std::max(maxc, c);
-                c_rq[ci] = q; c_var[ci] = v; c_w[ci] = w; c_v[ci] = c; c_ord[ci] = c; ci++;
-                wp[w] = pos++; wcn[w] = c; items[w] += c; nas[w] += c; aq[w] += c;
-            }
-            ps.key_ord_off[k + 1] = (uint32_t)ci;
-            ps.key_t_off[k + 1] = ps.key_t_off[k] + maxc + 1;  // sweeps 0..maxc
-            ps.key_bits_off[k + 1] = ps.key_bits_off[k] + (maxc + 1) * ((pos + 63) / 64);
-            max_count = std::max(max_count, maxc); max_nk = std::max(max_nk, pos);
-            ps.key_seg[k] = ps.seq_taken[q]; ps.key_sum[k] = sum; ps.seq_taken[q] += sum;
-            if (ps.seq_taken[q] > ps.q_total[q] + ps.pf_n[q]) return fail(ctx, HQTICK_E_QUEUE_UNDERFLOW, "solver placed more tasks than the queue holds (reference panics, taskqueue.rs:327)");
-        }
-        if (by_class) memcpy(ps.n_assign.data(), ps.items.data(), (size_t)W * 4);  // equal until the redirects are taken off
-        n_bit_words = ps.key_bits_off[nkeys];
-        // Worker-major selection (kernels.hip: SelPlanN): a request served by ONE key that starts at the head of its queue and gives every one of its workers the same
-        // count — the cold tick on identical workers, and every saturated class of a homogeneous cluster — is written by K4 so that each worker's ids are contiguous.
-        // Only plain queues: no prefill set in front of the request, no Retracting task anywhere in this tick (holes are positions of the queue order).
-        ps.key_tr.assign(nkeys, 0);
-        n_tr = 0;
-        if (transpose_on && s->n_retracting == 0) {
-            std::vector<uint32_t> &nk = ps.pf_drained;  // (scratch: keys per request; plan_redirects re-assigns it)
-            nk.assign(Q, 0);
-            for (uint32_t k = 0; k < nkeys; k++) nk[ps.key_rq[k]]++;
-            for (uint32_t k = 0; k < nkeys; k++) {
-                const uint32_t q = ps.key_rq[k], n = ps.key_ord_off[k + 1] - ps.key_ord_off[k], c = ps.key_t_off[k + 1] - ps.key_t_off[k] - 1;
-                if (nk[q] != 1 || ps.key_seg[k] != 0 || ps.pf_n[q] != 0 || n == 0 || c == 0 || c > 0xFFFFu || n > 0xFFFFu || (uint64_t)n * c != ps.key_sum[k]) continue;
-                ps.key_tr[k] = c; n_tr++;
-            }
-        }
-        // multi-node placements take one task each from the head of their queue (mapping.rs:133-154)
-        ps.mn_first.assign(cnt.mn_rq.size(), 0);
-        for (size_t i = 0; i < cnt.mn_rq.size(); i++) {
-            uint32_t q = cnt.mn_rq[i];
-            ps.mn_first[i] = ps.seq_taken[q]; ps.seq_taken[q] += (uint32_t)cnt.mn_sets[i].size();
-            if (ps.pf_n[q]) return fail(ctx, HQTICK_E_UNSUPPORTED, "multi-node queue with a prefill set");
-            if (ps.seq_taken[q] > ps.q_total[q]) return fail(ctx, HQTICK_E_QUEUE_UNDERFLOW, "multi-node placement exceeds its queue");
-        }
-        return 0;
-    }
-
-    // part 2: tasks that leave a prefill set or are Retracting in their queue — redirects instead of records  (mapping.rs:66-101)
-    int plan_redirects() {
-        // already-prefilled tasks that this tick hands out: Prefilled{old} -> retract + redirect  (mapping.rs:81-101)
-        ps.retract_pairs.clear();
-        ctx->red_task.clear(); ctx->red_worker.clear(); ctx->red_variant.clear();
-        ps.pf_drained.assign(Q, 0);
-        ps.has_pf.assign((size_t)Q * W, 0);  // SingleNodeTaskAssignment::prefilled_tasks as per-(rq, worker) counts
-        if (s->prefilled_off) for (uint32_t w = 0; w < W; w++) for (uint32_t i = s->prefilled_off[w]; i < s->prefilled_off[w + 1]; i++) if (s->prefilled_rq[i] < Q) ps.has_pf[(size_t)s->prefilled_rq[i] * W + w]++;
+    // what the plan reads (map_core.h): the scan, the counts, the snapshot, and of the context plain values
+    hqmap::PlanIn plan_in() {
+        hqmap::PlanIn in{};
+        in.sc = &sc; in.cnt = &cnt; in.s = s; in.rqs = pb.rqs.data(); in.variants = pb.variants.data();
+        in.proactive_filling_reserve = ctx->cfg.proactive_filling_reserve; in.proactive_filling_max = ctx->cfg.proactive_filling_max; in.flags = ctx->cfg.flags;
+        in.sink = ctx->sink != nullptr; in.shard_index = ctx->shard_index; in.shard_count = ctx->shard_count;
+        in.N = N; in.retr_key = ctx->scan.retracting_keys(); in.retr_rank = ctx->scan.retracting_ranks();
         if (ctx->asg.on && ctx->asg.tracking()) {  // the ledger's prefilled counts (its sync_mirror brought them back; a snapshot with prefilled_off was refused)
             uint32_t pf_stride = 0;
             const std::vector<uint32_t> &h_pf = ctx->asg.prefilled_host(&pf_stride);
-            const uint32_t nq = std::min(Q, pf_stride);
-            if (h_pf.size() >= (size_t)W * pf_stride) for (uint32_t w = 0; w < W; w++) for (uint32_t q = 0; q < nq; q++) ps.has_pf[(size_t)q * W + w] = h_pf[(size_t)w * pf_stride + q];
+            if (h_pf.size() >= (size_t)W * pf_stride) { in.ledger_pf = h_pf.data(); in.ledger_pf_stride = pf_stride; }
         }
-        key_T.assign(nkeys, {});
-        ctx->red_kind.clear();
-        for (uint32_t k = 0; k < nkeys; k++) {
-            const uint32_t q = cnt.keys[k].first;
-            if (!ps.pf_n[q]) continue;
-            uint32_t a = std::max(ps.key_seg[k], ps.pf_start[q]), b = std::min(ps.key_seg[k] + ps.key_sum[k], ps.pf_start[q] + ps.pf_n[q]);
-            for (uint32_t p = a; p < b; p++) {
-                uint32_t slot = s->prefill_off[q] + (p - ps.pf_start[q]);
-                uint64_t task = s->prefill_task[slot]; uint32_t oldw = s->prefill_worker[slot];
-                uint32_t neww = worker_of(k, p - ps.key_seg[k]);
-                ps.retract_pairs.push_back({oldw, task});
-                if (oldw < W && ps.has_pf[(size_t)q * W + oldw]) ps.has_pf[(size_t)q * W + oldw]--;
-                ctx->red_task.push_back(task); ctx->red_worker.push_back(neww); ctx->red_variant.push_back(cnt.keys[k].second); ctx->red_kind.push_back(HQ_REDIRECT_FROM_PREFILL);
-                if (neww < W) { ps.asg_qw[(size_t)q * W + neww]--; ps.n_assign[neww]--; }  // a redirect is not a new `assigned` record
-                ps.pf_drained[q]++;
-            }
-        }
-        // ready tasks in state Retracting{old} that this tick takes (mapping.rs:66-80): no `assigned` record, a redirect instead
-        ps.holes.clear(); ps.freed.clear();
-        retr_pos.clear();  // (rq, queue position) of every Retracting task, for the prefill check
-        if (s->n_retracting) {
-            if (N == 0) return fail(ctx, HQTICK_E_INVALID, "retracting tasks without a ready set");
-            const uint32_t nr = s->n_retracting;
-            const uint32_t *rkey = ctx->scan.retracting_keys(), *rrank = ctx->scan.retracting_ranks();
-            for (uint32_t i = 0; i < nr; i++) {
-                if (rkey[i] == 0xFFFFFFFFu || Q == 0) return fail(ctx, HQTICK_E_INVALID, "a retracting task is not in the ready set");
-                uint32_t q, z;                                                                        // request and position in its queue (levels, then id)
-                if (sc.ordered) {  // the view: rkey = rq, rrank = position in the permutation, whose segment of q starts at its first run
-                    q = rkey[i];
-                    if (q >= Q || sc.run_off[q] == sc.run_off[q + 1]) return fail(ctx, HQTICK_E_INVALID, "a retracting task is not in the ready set");
-                    z = rrank[i] - sc.run_start[sc.run_off[q]];
-                } else {
-                    const uint32_t l = rkey[i] / Q; q = rkey[i] % Q;
-                    z = rrank[i]; for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1] && sc.run_level[r] < l; r++) z += sc.run_cnt[r];
-                }
-                const uint32_t p = z < ps.pf_start[q] ? z : z + ps.pf_n[q];                             // position in the logical take sequence
-                retr_pos.push_back({q, z});
-                if (p >= ps.seq_taken[q]) continue;                                                   // stays in its queue
-                uint32_t k = nkeys;
-                for (uint32_t kk = 0; kk < nkeys; kk++) if (ps.key_rq[kk] == q && p >= ps.key_seg[kk] && p < ps.key_seg[kk] + ps.key_sum[kk]) { k = kk; break; }
-                if (k == nkeys) return fail(ctx, HQTICK_E_UNSUPPORTED, "a Retracting task was taken by a multi-node placement");
-                const uint32_t neww = worker_of(k, p - ps.key_seg[k]), oldw = s->retracting_worker[i];
-                const uint8_t v = cnt.keys[k].second;
-                ps.holes.push_back(((uint64_t)q << 32) | p);
-                if (neww < W) { ps.asg_qw[(size_t)q * W + neww]--; ps.n_assign[neww]--; }
-                ctx->red_task.push_back(s->retracting_task[i]); ctx->red_worker.push_back(neww); ctx->red_variant.push_back(v);
-                if (oldw != neww) {
-                    ctx->red_kind.push_back(HQ_REDIRECT_RETARGET);
-                    const uint32_t tw = s->retracting_redirect_worker ? s->retracting_redirect_worker[i] : HQ_NO_WORKER;
-                    if (tw != HQ_NO_WORKER) ps.freed.push_back({tw, pb.rqs[q].first_variant + (s->retracting_redirect_variant ? s->retracting_redirect_variant[i] : 0)});  // remove_sn_task(previous target)
-                } else {
-                    ctx->red_kind.push_back(HQ_REDIRECT_SAME_WORKER);
-                }
-            }
-            std::sort(ps.holes.begin(), ps.holes.end());
-        }
-        // queue tasks taken per request (excluding the prefilled block)
-        ps.zq_taken.assign(Q, 0);
-        for (uint32_t q = 0; q < Q; q++) ps.zq_taken[q] = ps.seq_taken[q] - ps.pf_drained[q];
-        // workers that received a multi-node task are no longer SN (set_mn_task)
-        ps.now_mn.assign(W, 0);
-        for (auto &sets : cnt.mn_sets) for (auto &set : sets) for (uint32_t w : set) ps.now_mn[w] = 1;
-        return 0;
+        in.transpose_on = transpose_enabled();
+        in.storage = hqmap::Mapper::plan_storage; in.user = &ctx->map;  // the big tables are built in the pinned buffer K4's ride-along workgroups copy from
+        return in;
     }
 
-    // part 3: process_proactive_filling  (mapping.rs:159-234)
-    int plan_prefill() {
-        if (s->worker_map_rank) { ps.wm_order.assign(W, 0); for (uint32_t w = 0; w < W; w++) ps.wm_order[s->worker_map_rank[w]] = w; }
-        else {
-            if (ps.cached_ids.size() != W || (W && memcmp(ps.cached_ids.data(), s->worker_id, (size_t)W * 4) != 0)) {
-                ps.cached_ids.assign(s->worker_id, s->worker_id + W);
-                hqhb::insertion_order_u32(s->worker_id, W, ps.cached_order);
-            }
+    // GPU phase C (hqmap::Mapper::phase_c), with what the assignment ledger needs of it
+    int phase_c(const hqmap::Env &me, const hqmap::PlanIn &in) {
+        hqmap::PhaseC pc{};
+        pc.sc = &sc; pc.scan = &ctx->scan; pc.ready = &ctx->ready; pc.in = &in;
+        pc.consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
+        pc.ledger_pfq_rq = ctx->asg.on;
+        if (ps.n_sel && pc.consume_in_tick && ctx->asg.on && s->n_retracting) {  // the redirects of Retracting tasks look their request id up after K4 has tombstoned it
+            pc.saved_rq = ctx->asg.saved_rq(N);
+            if (!pc.saved_rq) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids");
         }
-        const std::vector<uint32_t> &wm_order = s->worker_map_rank ? ps.wm_order : ps.cached_order;  // (no copy of the cached order)
-        ps.sn_ok.resize(W);  // per worker: still a single-node worker after this tick's multi-node placements
-        for (uint32_t w = 0; w < W; w++) ps.sn_ok[w] = ((s->worker_flags ? (s->worker_flags[w] & HQ_WORKER_SN) != 0 : true) && !ps.now_mn[w]) ? 1u : 0u;
-        ps.new_pf_total.assign(Q, 0); ps.pfl_size.assign(Q, 0);
-        ps.pfq_src.clear(); ps.pfq_size.clear(); ps.pfl_rows = 0;
-        pfq_rq.clear();
-        {
-            // state of every queue after the takes: first level that still has tasks
-            std::vector<int64_t> top_run(Q, -1); std::vector<uint32_t> top_left(Q, 0);  // (the run that is the queue's top after the takes)
-            uint64_t global_top = 0;
-            for (uint32_t q = 0; q < Q; q++) {
-                uint32_t left = ps.zq_taken[q];
-                for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) { uint32_t h = sc.run_cnt[r]; if (h > left) { top_run[q] = r; top_left[q] = h - left; break; } left -= h; }
-                if (top_run[q] >= 0) global_top = std::max(global_top, sc.run_prio[top_run[q]]);  // TaskQueues::top_priority  taskqueue.rs:62-68
-            }
-            size_t prev_row = SIZE_MAX;  // the pfl_j row that belongs to pf_flag_prev
-            for (uint32_t q = 0; q < Q; q++) {
-                if (top_run[q] < 0 || sc.run_prio[top_run[q]] != global_top) continue;
-                bool pf_left = ps.pf_n[q] > ps.pf_drained[q];
-                uint32_t tsz = (pf_left && s->prefill_priority[q] != global_top) ? 0 : top_left[q];  // top_size_no_prefill  taskqueue.rs:241-253
-                uint32_t size = tsz > ctx->cfg.proactive_filling_reserve ? tsz - ctx->cfg.proactive_filling_reserve : 0;
-                if (!size) continue;
-                // eligible workers: flags in index order (a branch-free pass), their ranks in worker_map order only when the set differs from the
-                // previous request's (on a saturated tick every worker serves every class: one walk of the order for all requests)
-                const uint32_t *aq = ps.asg_qw.data() + (size_t)q * W, *hp = ps.has_pf.data() + (size_t)q * W;
-                ps.pf_flag.resize(W);
-                uint32_t n_elig = 0;
-                {
-                    uint32_t *fl = ps.pf_flag.data(); const uint32_t *sn = ps.sn_ok.data();
-                    for (uint32_t w = 0; w < W; w++) { const uint32_t f = sn[w] & (aq[w] != 0 ? 1u : 0u) & (hp[w] == 0 ? 1u : 0u); fl[w] = f; n_elig += f; }  // (vectorises)
-                }
-                if (!n_elig) continue;
-                uint32_t psz = std::min(size / n_elig, ctx->cfg.proactive_filling_max);
-                if (!psz) continue;
-                ps.pfl_size[q] = psz;
-                pfq_rq.push_back(q);
-                const size_t o = ps.pfl_rows++ * W;  // (at most Q rows: one per request)
-                if (prev_row != SIZE_MAX && memcmp(ps.pf_flag.data(), ps.pf_flag_prev.data(), (size_t)W * 4) == 0) memcpy(ps.pfl_j + o, ps.pfl_j + prev_row, (size_t)W * 4);
-                else {
-                    uint32_t *row = ps.pfl_j + o; const uint32_t *fl = ps.pf_flag.data();
-                    uint32_t j = 0;
-                    for (uint32_t w : wm_order) { const uint32_t f = fl[w]; row[w] = f ? j : NONE; j += f; }
-                    ps.pf_flag_prev.swap(ps.pf_flag);
-                }
-                prev_row = o;
-                ps.new_pf_total[q] = psz * n_elig;
-            }
+        if (ps.n_sel && ctx->asg.on && ps.n_rec) {  // the ledger's copy of the placement stays in HBM, whatever form the records leave in
+            hqasg::StageCols c{};
+            if (!ctx->asg.stage_for(ps.n_rec, sc.ordered, sc.L, &c)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger staging");
+            pc.stage = hqk::Stage{c.task, c.rq, c.row, c.level, c.meta};
         }
-        for (auto &rp : retr_pos) {  // take_tasks_for_prefill on a Retracting task: the reference asserts task.is_waiting()  (mapping.rs:221)
-            const uint32_t q = rp.first, z = rp.second;
-            if (ps.new_pf_total[q] && z >= ps.zq_taken[q] && z < ps.zq_taken[q] + ps.new_pf_total[q])
-                return fail(ctx, HQTICK_E_UNSUPPORTED, "a Retracting task reached take_tasks_for_prefill: the reference asserts task.is_waiting() (mapping.rs:221)");
-        }
-        return 0;
+        const int rc = map_fail(ctx, ctx->map.phase_c(me, pc));
+        const hqmap::Timings &tm = ctx->map.timings();
+        if (tm.select_us >= 0) ctx->stats.select_us = tm.select_us;
+        if (tm.sweep_us >= 0) ctx->stats.sweep_us = tm.sweep_us;
+        if (tm.other_us >= 0) ctx->stats.other_us = tm.other_us;
+        return rc;
     }
 
-    // part 4: what K4 selects per (level, rq) group, where every worker's records go, capacity checks
-    int plan_outputs() {
-        // ---- selection plan per (level, rq) group ----
-        ps.rq_sel_base.assign(Q + 1, 0);
-        for (uint32_t q = 0; q < Q; q++) ps.rq_sel_base[q + 1] = ps.rq_sel_base[q] + ps.zq_taken[q] + ps.new_pf_total[q];
-        n_sel = ps.rq_sel_base[Q];
-        // (the view selects per request from rq_sel_base alone — order.hip: k_order_select — and needs only the worker-major form per request)
-        const size_t G = sc.ordered ? 0 : sc.G;
-        ps.take_base.assign((size_t)4 * G, 0);  // [take][base][tnc][tsb] per (level, rq) group (kernels.hip: SelPlanN)
-        ps.q_tnc.assign(sc.ordered ? Q : 0, 0);
-        if (!sc.ordered) for (uint32_t q = 0; q < Q; q++) {
-            uint32_t want = ps.zq_taken[q] + ps.new_pf_total[q], cum = 0;
-            for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) {
-                const uint32_t h = sc.run_cnt[r], t = want > cum ? std::min(h, want - cum) : 0, g = sc.run_group[r];
-                ps.take_base[g] = t; ps.take_base[G + g] = ps.rq_sel_base[q] + cum;
-                cum += h;
-            }
-        }
-        if (n_tr) {
-            if (!ps.holes.empty()) return fail(ctx, HQTICK_E_UNSUPPORTED, "internal: worker-major selection on a tick with holes");  // (cannot happen: no Retracting task, no hole)
-            for (uint32_t k = 0; k < nkeys; k++) {
-                if (!ps.key_tr[k]) continue;
-                const uint32_t q = ps.key_rq[k], n = ps.key_ord_off[k + 1] - ps.key_ord_off[k];
-                if (sc.ordered) { ps.q_tnc[q] = (n << 16) | ps.key_tr[k]; continue; }
-                for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) { ps.take_base[2 * G + sc.run_group[r]] = (n << 16) | ps.key_tr[k]; ps.take_base[3 * G + sc.run_group[r]] = ps.rq_sel_base[q]; }
-            }
-        }
-        for (uint32_t q : pfq_rq) { ps.pfq_src.push_back(ps.rq_sel_base[q] + ps.zq_taken[q]); ps.pfq_size.push_back(ps.pfl_size[q]); }
-        n_pfq = (uint32_t)pfq_rq.size();
-        // ---- output offsets ----
-        ps.out_off.assign(W + 1, 0);
-        max_items = 0; max_out = 0;
-        compact = (ctx->cfg.flags & (HQTICK_FLAG_COMPACT_RECORDS | HQTICK_FLAG_COMPACT_DELTA16)) != 0 && !ctx->sink;
-        for (uint32_t w = 0; w < W; w++) {
-            if (ctx->shard_count > 1 && hqhb::hash_worker_id(s->worker_id[w]) % ctx->shard_count != ctx->shard_index) { ps.out_off[w + 1] = ps.out_off[w]; continue; }  // another rank's worker
-            uint32_t npf = 0;
-            for (uint32_t pi = 0; pi < n_pfq; pi++) if (ps.pfl_j[(size_t)pi * W + w] != NONE) npf += ps.pfq_size[pi];
-            ps.out_off[w + 1] = ps.out_off[w] + npf + ps.n_assign[w];
-            max_items = std::max(max_items, ps.items[w]);
-            max_out = std::max(max_out, npf + ps.n_assign[w]);
-        }
-        n_rec = ps.out_off[W];
-        may_reorder = sc.L > 1 || !ps.holes.empty() || (s->prefill_off && s->prefill_off[Q] > 0);
-        if (hqk::expand_mapping_lds(max_items, nkeys, compact ? max_out : 0, may_reorder, sc.ordered) > 150 * 1024) return fail(ctx, HQTICK_E_CAPACITY, "a worker receives more tasks in one tick than the mapping kernel stages in LDS");
-        if (max_nk > hqk::SWEEP_MAX_WORKERS) return fail(ctx, HQTICK_E_CAPACITY, "more than 24576 workers share one (request, variant) placement: beyond the round-robin kernel's LDS staging");
-        return 0;
-    }
-
-    // everything of the result that needs no GPU output: runs while the GPU works on phase C
-    void assemble_host_part() {
-        assembled = true;
-        ctx->rec_off = ps.out_off;
-        ctx->retract_off.assign(W + 1, 0); ctx->retract_task.assign(ps.retract_pairs.size(), 0);
-        {
-            for (auto &rp : ps.retract_pairs) if (rp.first < W) ctx->retract_off[rp.first + 1]++;
-            for (uint32_t w = 0; w < W; w++) ctx->retract_off[w + 1] += ctx->retract_off[w];
-            std::vector<uint32_t> cur(ctx->retract_off.begin(), ctx->retract_off.end() - 1);
-            for (auto &rp : ps.retract_pairs) if (rp.first < W) ctx->retract_task[cur[rp.first]++] = rp.second;  // stable: per worker in emission order
-        }
-        // Worker::insert_sn_task for every placed task (server/worker.rs:188-196 -> workerload.rs:156-165)
-        ctx->new_free.assign(s->worker_free, s->worker_free + (size_t)W * R);
-        for (uint32_t k = 0; k < nkeys; k++) {
-            const hqhost::VariantView &vv = pb.variants[pb.rqs[cnt.keys[k].first].first_variant + cnt.keys[k].second];
-            const uint32_t *wcn = ps.wcnt + (size_t)k * W;  // this key's count per worker (0 = none): the plan's own row
-            for (uint32_t w = 0; w < W; w++) {
-                const uint32_t c = wcn[w];
-                if (!c) continue;
-                for (uint32_t e = 0; e < vv.n_entries; e++) {
-                    uint64_t &f = ctx->new_free[(size_t)w * R + vv.res[e]];
-                    if (vv.kind[e] == HQ_ENTRY_ALL) f = 0; else { uint64_t d = vv.amount[e] * (uint64_t)c; f = f > d ? f - d : 0; }
-                }
-            }
-        }
-        for (auto &fr : ps.freed) {  // remove_sn_task on the previous target of a re-targeted redirect  (worker.rs:223-234 -> workerload.rs:194-202)
-            const hqhost::VariantView &vv = pb.variants[fr.second];
-            for (uint32_t e = 0; e < vv.n_entries; e++) {
-                uint64_t &f = ctx->new_free[(size_t)fr.first * R + vv.res[e]];
-                f = vv.kind[e] == HQ_ENTRY_ALL ? s->worker_total[(size_t)fr.first * R + vv.res[e]] : f + vv.amount[e];
-            }
-        }
-    }
-
-    // K5a needs the key tables only (counts in Map order per key): it goes out as soon as plan_keys() has them, reading its four small tables in place
-    // from pinned memory, and runs while the host plans redirects, prefills and outputs — 5.4 us and a launch boundary off the critical path.
-    int launch_sweep_early() {
-        sweep_launched = false;
-        if (nkeys == 0 || n_bit_words == 0 || max_nk > hqk::SWEEP_MAX_WORKERS) return 0;  // (the capacity error is reported by plan_outputs)
-        if (n_tr == nkeys) { sweep_launched = true; return 0; }  // every key is stored worker-major: no bit row is ever read — no launch at all
-        if (ctx->sweep_inflight) { HQ_HIP(hipStreamSynchronize(ctx->stream)); ctx->sweep_inflight = false; }  // a tick that failed after its early launch: its kernel still reads h_k5a
-        const size_t n_ord = ps.ord_cnt.size(), words = 4 * (size_t)(nkeys + 1) + n_ord;
-        if (!ctx->h_k5a.ensure(words * 4 + 64) || !ctx->d_tsweep.ensure((size_t)ps.key_t_off[nkeys] * 4 + 16) || !ctx->d_bits.ensure((size_t)n_bit_words * 8 + 16) ||
-            !ctx->d_pre.ensure((size_t)n_bit_words * 4 + 16))
-            return fail(ctx, HQTICK_E_DEVICE, "hipMalloc mapping");
-        uint32_t *h = ctx->h_k5a.as<uint32_t>();
-        const uint32_t *d = ctx->h_k5a.dev<uint32_t>();
-        const size_t o_toff = 0, o_ordoff = nkeys + 1, o_boff = 2 * (size_t)(nkeys + 1), o_tr = 3 * (size_t)(nkeys + 1), o_ord = 4 * (size_t)(nkeys + 1);
-        memcpy(h + o_toff, ps.key_t_off.data(), (size_t)(nkeys + 1) * 4); memcpy(h + o_ordoff, ps.key_ord_off.data(), (size_t)(nkeys + 1) * 4);
-        memcpy(h + o_boff, ps.key_bits_off.data(), (size_t)(nkeys + 1) * 4); memcpy(h + o_tr, ps.key_tr.data(), (size_t)nkeys * 4); if (n_ord) memcpy(h + o_ord, ps.ord_cnt.data(), n_ord * 4);
-        hqk::MapKeys mk{};
-        mk.n_keys = nkeys; mk.key_t_off = d + o_toff; mk.key_ord_off = d + o_ordoff; mk.key_bits_off = d + o_boff; mk.ord_cnt = d + o_ord; mk.key_tr = d + o_tr;
-        mk.t_sweep = ctx->d_tsweep.as<uint32_t>(); mk.bits = ctx->d_bits.as<uint64_t>(); mk.pre = ctx->d_pre.as<uint32_t>();
-        if (ctx->timing) hqk::time_next_launch(ctx->ev[1], ctx->ev[6]);
-        HQ_HIP_TIMED(hqk::sweep_bits(mk, max_count, max_nk, ctx->stream));
-        sweep_launched = true; ctx->sweep_inflight = true;
-        return 0;
-    }
-
-    // GPU phase C: selection, round-robin bit rows, per-worker expansion; records land in pinned memory (or the HBM sink)
-    int phase_c() {
-        size_t n_mn_ids = 0; for (auto &sets : cnt.mn_sets) n_mn_ids += sets.size();
-        delta16 = compact && (ctx->cfg.flags & HQTICK_FLAG_COMPACT_DELTA16) != 0;
-        if (compact) {  // [rec_lo u32 x n_rec | units u16 x 4 n_rec][run_span (start, count) x W][runs 12 | 16 B x n_rec] (at most one run per record)
-            o_rs = delta16 ? (size_t)n_rec * 8 : (((size_t)n_rec * 4 + 7) & ~(size_t)7); o_rf = o_rs + (size_t)W * 8;
-            o_rv = o_rk = 0; o_mn = (o_rf + (size_t)n_rec * (delta16 ? 16 : 12) + 7) & ~(size_t)7;
-        } else { o_rv = (size_t)n_rec * 8; o_rk = o_rv + n_rec; o_mn = (o_rk + n_rec + 7) & ~(size_t)7; }
-        o_fl = o_mn + n_mn_ids * 8;
-        const size_t rec_bytes = o_fl + 64;
-        if (!ctx->h_rec.ensure(rec_bytes)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc records");
-        h_rec_task = ctx->h_rec.as<uint64_t>(); h_rec_var = ctx->h_rec.as<uint8_t>() + o_rv; h_rec_kind = ctx->h_rec.as<uint8_t>() + o_rk;
-        mn_ids = reinterpret_cast<uint64_t *>(ctx->h_rec.as<uint8_t>() + o_mn);
-        if (n_sel) {
-            if (!ctx->d_sel_task.ensure((size_t)n_sel * 8) || !ctx->d_sel_level.ensure((size_t)n_sel * (sc.ordered ? 4 : 2) + 4))
-                return fail(ctx, HQTICK_E_DEVICE, "hipMalloc selection");
-            // the plan in one upload: the big tables are already at the head of the pinned buffer (plan_keys / plan_prefill), the small ones go behind them
-            uint32_t *hp = ctx->h_plan.as<uint32_t>();
-            size_t cur = ps.plan_head_words;
-            auto put = [&](const std::vector<uint32_t> &v) { const size_t o = cur; if (!v.empty()) memcpy(hp + cur, v.data(), v.size() * 4); cur += v.size(); if (v.empty()) hp[cur++] = 0; return o; };
-            const size_t o_wpos = 0, o_wcnt = (size_t)nkeys * W, o_pflj = (size_t)2 * nkeys * W;
-            size_t o_rq = put(ps.key_rq), o_var = put(ps.key_var_w), o_seg = put(ps.key_seg), o_ordoff = put(ps.key_ord_off), o_ord = put(ps.ord_cnt), o_toff = put(ps.key_t_off),
-                   o_boff = put(ps.key_bits_off), o_tr = put(ps.key_tr), o_base = put(ps.rq_sel_base), o_pfs = put(ps.pf_start), o_pfn = put(ps.pf_n),
-                   o_pqs = put(ps.pfq_src), o_pqz = put(ps.pfq_size), o_out = put(ps.out_off);
-            const size_t o_pqr = ctx->asg.on ? put(pfq_rq) : 0;  // the ledger's staging names the request of a PREFILL record
-            size_t o_tb = put(ps.take_base);
-            size_t o_roff = 0, o_qtnc = 0, o_rst = 0, o_rrk = 0;  // the view's tables (order.hip: k_order_select)
-            if (sc.ordered) { o_roff = put(sc.run_off); o_qtnc = put(ps.q_tnc); o_rst = put(sc.run_start); o_rrk = put(sc.run_level); }
-            if (cur & 1) hp[cur++] = 0;  // 8-byte alignment for the u64 hole list
-            const size_t o_holes = cur;
-            for (uint64_t hk : ps.holes) { hp[cur++] = (uint32_t)(hk & 0xFFFFFFFFu); hp[cur++] = (uint32_t)(hk >> 32); }
-            if (ps.holes.empty()) { hp[cur++] = 0; hp[cur++] = 0; }
-            const size_t plan_words = cur;
-            if (plan_words * 4 + 16 > ctx->h_plan.cap) return fail(ctx, HQTICK_E_DEVICE, "mapping plan larger than its buffer");  // (sized in plan_keys)
-            if (!ctx->d_map.ensure(plan_words * 4 + 16) ||
-                !ctx->d_tsweep.ensure((size_t)ps.key_t_off[nkeys] * 4 + 16) || !ctx->d_bits.ensure((size_t)n_bit_words * 8 + 16) || !ctx->d_pre.ensure((size_t)n_bit_words * 4 + 16))
-                return fail(ctx, HQTICK_E_DEVICE, "hipMalloc mapping");
-            mark();  // 6: pack
-            const uint32_t *d = ctx->d_map.as<uint32_t>();
-            hqk::MapKeys mk{};
-            mk.n_keys = nkeys; mk.key_rq = d + o_rq; mk.key_variant = reinterpret_cast<const uint8_t *>(d + o_var); mk.key_seg_start = d + o_seg;
-            mk.key_ord_off = d + o_ordoff; mk.ord_cnt = d + o_ord; mk.key_t_off = d + o_toff; mk.key_bits_off = d + o_boff; mk.key_tr = d + o_tr;
-            mk.t_sweep = ctx->d_tsweep.as<uint32_t>(); mk.bits = ctx->d_bits.as<uint64_t>(); mk.pre = ctx->d_pre.as<uint32_t>();
-            mk.wpos = d + o_wpos; mk.wcnt = d + o_wcnt; mk.rq_sel_base = d + o_base; mk.rq_pf_start = d + o_pfs; mk.rq_pf_n = d + o_pfn;
-            mk.n_holes = (uint32_t)ps.holes.size(); mk.holes = reinterpret_cast<const uint64_t *>(d + o_holes);
-            mk.n_pfq = n_pfq; mk.pfq_src = d + o_pqs; mk.pfq_size = d + o_pqz; mk.pfl_j = d + o_pflj; mk.out_off = d + o_out;
-            uint32_t *flags = reinterpret_cast<uint32_t *>(ctx->h_rec.as<uint8_t>() + o_fl);
-            flags[0] = 0;  // K5b reports a capacity overflow straight into this pinned word
-            ctx->ready.selected(n_sel);  // (of the plan whose launch state is recorded below)
-            const hqready::Cols cols = ctx->ready.cols();
-            const bool consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;  // K4 writes the tombstones of what it selects
-            if (consume_in_tick && ctx->asg.on && s->n_retracting) {  // only the redirects of Retracting tasks still look their request id up after K4 has tombstoned it (4 B per slot, device to device)
-                uint32_t *saved = ctx->asg.saved_rq(N);
-                if (!saved) { ctx->ready.selection_void(); return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger request ids"); }
-                HQ_HIP(hipMemcpyAsync(saved, cols.rq, N * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            ctx->last_geom = sc.geom; ctx->last_L = L; ctx->last_Q = Q; ctx->last_G = sc.G; ctx->last_tb = o_tb; ctx->last_plan_bytes = plan_words * 4;
-            ctx->last_ordered = sc.ordered;
-            if (sc.ordered) {  // the plan into HBM, then K4 on the view (order.hip)
-                HQ_HIP(hqk::copy_pinned_to_hbm(ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4, ctx->stream));
-                hqk::OrderSelect os{};
-                os.task_id = cols.id; os.perm = ctx->scan.perm(); os.n_live = sc.run_cnt.empty() ? 0u : sc.run_start.back() + sc.run_cnt.back(); os.Q = Q;
-                os.n_runs = (uint32_t)sc.run_cnt.size(); os.rq_sel_base = d + o_base; os.run_off = d + o_roff; os.run_start = d + o_rst; os.run_rank = d + o_rrk; os.q_tnc = d + o_qtnc;
-                os.sel_task = ctx->d_sel_task.as<uint64_t>(); os.sel_rank = ctx->d_sel_level.as<uint32_t>(); os.err = ctx->scan.select_err_dev();
-                ctx->last_os = os;  // (what hqtick_ready_consume_last and the restore of HQTICK_FLAG_CONSUME_IN_TICK replay)
-                if (consume_in_tick) { os.mark_rq = cols.rq; os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 1; }
-                if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
-                HQ_HIP_TIMED(hqk::order_select(os, n_sel, ctx->stream));
-            } else {
-            if (ctx->timing) hqk::time_next_launch(ctx->ev[4], ctx->ev[5]);
-            HQ_HIP_TIMED(hqk::select_scatter(cols.id, ctx->scan.group_keys(), N, Q, sc.G, sc.geom, ctx->scan.slice_table(), ctx->h_plan.as<uint32_t>() + o_tb,
-                                d + o_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, plan_words * 4,
-                                consume_in_tick ? cols.rq : nullptr, ctx->stream, consume_in_tick ? 1u : 0u));
-            }
-            if (consume_in_tick) ctx->ready.consumed_in_tick();  // (confirmed when the tick returns without an error: run_tick)
-            if (!sweep_launched && n_tr < nkeys) {
-                if (ctx->timing) hqk::time_next_launch(ctx->ev[1], ctx->ev[6]);
-                HQ_HIP_TIMED(hqk::sweep_bits(mk, max_count, max_nk, ctx->stream));
-            }
-            uint8_t *drec = ctx->h_rec.dev<uint8_t>();  // K5b writes the records straight into the caller-visible pinned buffer (PCIe-bound, no copy command)
-            uint64_t *k_task = reinterpret_cast<uint64_t *>(drec); uint8_t *k_var = drec + o_rv, *k_kind = drec + o_rk;
-            if (ctx->sink) {  // multi-GPU: records stay in HBM, laid out for the all-gather (include/hqtick.h)
-                const uint32_t cap = hqtick_sink_capacity_records(W, ctx->sink_bytes);
-                if (n_rec > cap || hqtick_sink_bytes(W, cap) > ctx->sink_bytes) return fail(ctx, HQTICK_E_CAPACITY, "record sink too small for this tick");
-                uint8_t *sk = reinterpret_cast<uint8_t *>(ctx->sink);
-                const size_t so_off = 16, so_task = (so_off + (size_t)(W + 1) * 4 + 7) & ~(size_t)7, so_var = so_task + (size_t)cap * 8, so_kind = so_var + cap;
-                // header + rec_off ride in the plan buffer's tail: stage them in pinned memory and copy with the stream
-                std::vector<uint32_t> &hdr = ps.sink_hdr; hdr.assign(4 + W + 1, 0);
-                hdr[0] = n_rec; hdr[1] = cnt.checksum(); hdr[2] = HQTICK_SINK_MAGIC; hdr[3] = cap;
-                memcpy(hdr.data() + 4, ps.out_off.data(), (size_t)(W + 1) * 4);
-                if (!ctx->h_sinkhdr.ensure(hdr.size() * 4)) return fail(ctx, HQTICK_E_DEVICE, "hipHostMalloc sink header");
-                memcpy(ctx->h_sinkhdr.p, hdr.data(), hdr.size() * 4);
-                HQ_HIP(hipMemcpyAsync(sk, ctx->h_sinkhdr.p, hdr.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-                k_task = reinterpret_cast<uint64_t *>(sk + so_task); k_var = sk + so_var; k_kind = sk + so_kind;
-            }
-            hqk::time_next_launch(ctx->timing ? ctx->ev[7] : nullptr, ctx->ev[11]);  // ev[11]: K5b's completion — what the host waits on below
-            hqk::CompactOut co{};
-            if (compact) co = hqk::CompactOut{reinterpret_cast<uint32_t *>(drec), reinterpret_cast<uint2 *>(drec + o_rs), reinterpret_cast<uint32_t *>(drec + o_rf),
-                                              delta16 ? reinterpret_cast<uint16_t *>(drec) : nullptr};
-            hqk::Stage stg{};
-            if (ctx->asg.on && n_rec) {  // the ledger's copy of the placement stays in HBM, whatever form the records leave in
-                hqasg::StageCols c{};
-                if (!ctx->asg.stage_for(n_rec, sc.ordered, sc.L, &c)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc ledger staging");
-                stg = hqk::Stage{c.task, c.rq, c.row, c.level, c.meta};
-                stg.pfq_rq = ctx->d_map.as<uint32_t>() + o_pqr;
-            }
-            bool expand_is_last = false;
-            if (sc.ordered) HQ_HIP_LAST(hqk::expand_mapping_wide(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint32_t>(), max_items, k_task, k_var, k_kind,
-                                                           reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream, stg), expand_is_last);
-            else HQ_HIP_LAST(hqk::expand_mapping(mk, W, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), Q, max_items, k_task, k_var, k_kind,
-                                reinterpret_cast<uint32_t *>(drec + o_fl), co, max_out, may_reorder, ctx->stream, stg), expand_is_last);
-            if (!cnt.mn_rq.empty()) expand_is_last = false;  // copies of the multi-node task ids follow
-            if (sc.ordered) {  // the selection's guard word follows (order.hip: a position outside its request's segment)
-                HQ_HIP(hipMemcpyAsync(ctx->scan.select_err_host(), ctx->scan.select_err_dev(), 4, hipMemcpyDeviceToHost, ctx->stream));
-                expand_is_last = false;
-            }
-            // multi-node tasks: the heads of their queues
-            {
-                size_t pos = 0;
-                for (size_t i = 0; i < cnt.mn_rq.size(); i++) {
-                    size_t n = cnt.mn_sets[i].size();
-                    HQ_HIP(hipMemcpyAsync(mn_ids + pos, ctx->d_sel_task.as<uint64_t>() + ps.rq_sel_base[cnt.mn_rq[i]] + ps.mn_first[i], n * 8, hipMemcpyDeviceToHost, ctx->stream));
-                    pos += n;
-                }
-            }
-            mark();  // 7: phase C enqueued
-            assemble_host_part();
-            if (expand_is_last) HQ_HIP(hipEventSynchronize(ctx->ev[11])); else HQ_HIP(hipStreamSynchronize(ctx->stream));
-            ctx->sweep_inflight = false;
-            if (flags[0]) return fail(ctx, HQTICK_E_CAPACITY, "mapping kernel capacity exceeded");
-            if (sc.ordered && *ctx->scan.select_err_host()) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the selection left its request's segment");
-            if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[4], ctx->ev[5]); if (us_ >= 0) ctx->stats.select_us = us_; }
-            if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[1], ctx->ev[6]); if (us_ >= 0) ctx->stats.sweep_us = us_; }
-            if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[7], ctx->ev[11]); if (us_ >= 0) ctx->stats.other_us = us_; }
-        }
-        if (!n_sel) ctx->ready.selected(0);
-        if (!n_sel && ctx->sink) {  // nothing placed: still publish an empty, well-formed sink
-            if (hqtick_sink_bytes(W, 0) > ctx->sink_bytes) return fail(ctx, HQTICK_E_CAPACITY, "record sink too small for this tick");
-            std::vector<uint32_t> &hdr = ps.sink_hdr; hdr.assign(4 + W + 1, 0);
-            hdr[1] = cnt.checksum(); hdr[2] = HQTICK_SINK_MAGIC; hdr[3] = hqtick_sink_capacity_records(W, ctx->sink_bytes);
-            HQ_HIP(hipMemcpy(ctx->sink, hdr.data(), hdr.size() * 4, hipMemcpyHostToDevice));
-        }
-        return 0;
-    }
-
-    void finish(double t1, double t2, double t3) {
-        if (!assembled) assemble_host_part();
-        ctx->mn_task.clear(); ctx->mn_off.assign(1, 0); ctx->mn_worker.clear(); ctx->mn_rq.clear();
-        {
-            size_t pos = 0;
-            for (size_t i = 0; i < cnt.mn_rq.size(); i++) for (auto &set : cnt.mn_sets[i]) {
-                ctx->mn_task.push_back(mn_ids[pos++]); ctx->mn_rq.push_back(cnt.mn_rq[i]);
-                for (uint32_t w : set) ctx->mn_worker.push_back(w);
-                ctx->mn_off.push_back((uint32_t)ctx->mn_worker.size());
-            }
-        }
+    void finish(const hqmap::Env &me, double t1, double t2, double t3) {
         out->status = status;
-        out->n_counts = (uint32_t)ctx->cnt_rq.size(); out->count_rq = ctx->cnt_rq.data(); out->count_variant = ctx->cnt_variant.data();
-        out->count_worker = ctx->cnt_worker.data(); out->count_value = ctx->cnt_value.data();
-        out->rec_off = ctx->rec_off.data();
-        if (compact && n_sel) {
-            const uint8_t *hb = ctx->h_rec.as<uint8_t>();
-            out->run_span = reinterpret_cast<const hqtick_run_span *>(hb + o_rs);
-            if (delta16) { out->rec_delta16 = reinterpret_cast<const uint16_t *>(hb); out->runs16 = reinterpret_cast<const hqtick_rec_run16 *>(hb + o_rf); }
-            else { out->rec_task_lo = reinterpret_cast<const uint32_t *>(hb); out->runs = reinterpret_cast<const hqtick_rec_run *>(hb + o_rf); }
-        } else if (!ctx->sink) { out->rec_task = h_rec_task; out->rec_variant = h_rec_var; out->rec_kind = h_rec_kind; }
-        out->retract_off = ctx->retract_off.data(); out->retract_task = ctx->retract_task.data();
-        out->n_redirects = (uint32_t)ctx->red_task.size(); out->redirect_task = ctx->red_task.data(); out->redirect_worker = ctx->red_worker.data(); out->redirect_variant = ctx->red_variant.data(); out->redirect_kind = ctx->red_kind.data();
-        out->n_mn = (uint32_t)ctx->mn_task.size(); out->mn_task = ctx->mn_task.data(); out->mn_worker_off = ctx->mn_off.data(); out->mn_worker = ctx->mn_worker.data();
-        out->new_free = ctx->new_free.data();
+        ctx->map.export_result(me, cnt, out);
         mark();  // 9: result assembled
         double t5 = now_us();
         out->t_total_us = t5 - t0; out->t_scan_us = t1 - t0; out->t_batches_us = t2 - t1; out->t_solve_us = t3 - t2; out->t_mapping_us = t5 - t3;
@@ -1115,18 +597,24 @@ struct TickRun {
         status = HQTICK_DONE;  // scheduler/main.rs:57-68
         if (!cnt.is_optimal) status = cnt.empty() ? HQTICK_NO_PROGRESS : HQTICK_NEED_MORE_COMPUTE;
         // ---------------- host: mapping plan ----------------
-        if ((rc = plan_keys())) return rc;
-        if ((rc = launch_sweep_early())) return rc;
-        if ((rc = plan_redirects())) return rc;
+        const hqmap::PlanIn in = plan_in();
+        const hqmap::Env me = map_env(ctx, t0);
+        hqmap::HostResult &hr = ctx->map.res;
+        const char *why = nullptr;
+        ctx->ready.selection_void();  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
+        if ((rc = plan_fail(hqmap::plan_keys(ps, hr, in, &why), why))) return rc;
+        if ((rc = map_fail(ctx, ctx->map.launch_sweep_early(me)))) return rc;
+        if ((rc = plan_fail(hqmap::plan_redirects(ps, hr, in, &why), why))) return rc;
         mark();  // 3: key tables + retracts
-        if ((rc = plan_prefill())) return rc;
+        if ((rc = plan_fail(hqmap::plan_prefill(ps, hr, in, &why), why))) return rc;
         mark();  // 4: prefill plan
-        if ((rc = plan_outputs())) return rc;
+        if ((rc = plan_fail(hqmap::plan_outputs(ps, hr, in, &why), why))) return rc;
+        if ((rc = map_fail(ctx, ctx->map.check_capacity(sc.ordered)))) return rc;
         mark();  // 5: K5 tables
         // ---------------- GPU phase C ----------------
-        if ((rc = phase_c())) return rc;
+        if ((rc = phase_c(me, in))) return rc;
         mark();  // 8: phase C synced
-        finish(t1, t2, t3);
+        finish(me, t1, t2, t3);
         return status;
     }
 };
@@ -1176,23 +664,12 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         ctx->ready.confirm();
         if (rc < 0) {
             // ... and the tick did not come back (a record sink too small, a mapping capacity exceeded, a failed exchange: errors a host can recover from).  What it took
-            // goes back: this tick's K1 left a valid group key on every task that was live, so the tombstones K4 wrote are recognisable and their request ids
-            // recoverable (k_restore_consumed: one pass over the key and request-id columns).  Only if THAT fails is the set dropped and the host uploads it again.
+            // goes back.  Only if THAT fails is the set dropped and the host uploads it again.
             const std::string why = ctx->err;
             bool restored = false;
             const bool synced = hipStreamSynchronize(ctx->stream) == hipSuccess;
-            const hqready::Cols cols = ctx->ready.cols();
-            const uint32_t n_sel = ctx->ready.selected_count();
-            if (synced && ctx->ready.selection_valid() && ctx->last_ordered) {  // the view: the same selection writes the request ids back
-                hqk::OrderSelect os = ctx->last_os;
-                os.mark_rq = cols.rq; os.mark_value = 0; os.mark_and_select = 0;
-                restored = hqk::order_select(os, n_sel, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
-            } else if (synced && ctx->ready.selection_valid() && !ctx->last_ordered && ctx->last_Q && ctx->h_q.ensure(64)) {
-                uint32_t *cntp = ctx->h_q.as<uint32_t>();
-                cntp[0] = 0;
-                restored = hqk::ready_restore_consumed(ctx->scan.group_keys(), cols.rq, cols.n, ctx->last_Q, ctx->h_q.dev<uint32_t>(), ctx->stream) == hipSuccess &&
-                           hipStreamSynchronize(ctx->stream) == hipSuccess && cntp[0] <= n_sel;
-            }
+            if (synced && ctx->ready.selection_valid())  // the selection once more, giving the request ids back (hqmap::Mapper::replay_selection)
+                restored = ctx->map.replay_selection(ctx->stream, hqmap::REPLAY_RESTORE, ctx->ready.cols(), ctx->scan, ctx->ready.selected_count(), &ctx->h_q) == 0;
             // nothing of this tick is left to consume; a restore gives the count back what the tick had subtracted when it launched the selection (the kernel may have run for any part of it)
             if (restored) ctx->ready.put_back(); else ctx->ready.lost();
             ctx->err = why;
@@ -1200,10 +677,10 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             else { ctx->err += " (HQTICK_FLAG_CONSUME_IN_TICK: the tick had already taken its tasks and they could not be put back; the resident ready set is dropped, upload it again)"; }
         }
     }
-    if (rc >= 0 && retr_resident) ctx->retr.apply_tick(s->worker_id, s->n_workers, ctx->retract_off, ctx->retract_task, ctx->red_task, ctx->red_worker, ctx->red_variant, ctx->red_kind);
+    if (rc >= 0 && retr_resident) ctx->retr.apply_tick(s->worker_id, s->n_workers, ctx->map.res.retract_off, ctx->map.res.retract_task, ctx->map.res.red_task, ctx->map.res.red_worker, ctx->map.res.red_variant, ctx->map.res.red_kind);
     if (rc >= 0 && ctx->asg.on) {  // the placement enters the ledger when it becomes state: now, or at hqtick_ready_consume_last in the two-call form
         const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
-        ctx->asg.collect_tick(s, out, ctx->new_free, ctx->mn_rq, in_tick && s->n_retracting != 0);  // (the column copy is taken only for the redirects of Retracting tasks)
+        ctx->asg.collect_tick(s, out, ctx->map.res.new_free, ctx->map.res.mn_rq, in_tick && s->n_retracting != 0);  // (the column copy is taken only for the redirects of Retracting tasks)
         if (!use_resident || in_tick) {
             if (int r2 = ledger_fail(ctx, ctx->asg.apply_tick(ledger_env(ctx)))) {  // (the tick's tasks have left the ready set: without the placement the ledger is no longer the truth)
                 ctx->asg.on = false; ctx->asg.pending = false;
@@ -1301,8 +778,8 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
     delete ctx->pricer; ctx->pricer = nullptr;
-    DevBuf *bufs[] = {&ctx->d_up, &ctx->d_vflags, &ctx->d_vtmc, &ctx->d_sel_task, &ctx->d_sel_level, &ctx->d_map, &ctx->d_rec, &ctx->d_tsweep, &ctx->d_bits, &ctx->d_pre, &ctx->d_blk};
-    for (DevBuf *b : bufs) b->release();
+    ctx->d_blk.release();
+    ctx->map.release();
     ctx->scan.release();
     ctx->ready.release();
     ctx->ws.release();
@@ -1313,7 +790,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     ctx->graph.release();
     ctx->asg.release_all();
     ctx->audit.release();
-    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_plan.release(); ctx->h_rec.release(); ctx->h_sinkhdr.release(); ctx->h_blk.release(); ctx->h_blkprof.release(); ctx->h_k5a.release();
+    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_blk.release(); ctx->h_blkprof.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1364,18 +841,8 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) { return with_audit(ctx, [&]() ->
     }
     if (!ctx->ready.selection_valid()) return fail(ctx, HQTICK_E_INVALID, "hqtick_ready_consume_last needs a preceding hqtick_run_resident");
     HQ_HIP(hipSetDevice(ctx->device));
-    const uint32_t *d = ctx->d_map.as<uint32_t>();
-    const hqready::Cols cols = ctx->ready.cols();
-    // the selection of the last tick once more, writing tombstones instead of the selected ids (same offsets table, same plan; the view's: the same
-    // permutation — which reads no priority, so hqtick_graph_blevel between the tick and this call changes nothing)
-    if (ctx->last_ordered) {
-        hqk::OrderSelect os = ctx->last_os;
-        os.mark_rq = cols.rq; os.mark_value = hqk::RQ_TOMBSTONE; os.mark_and_select = 0;
-        HQ_HIP(hqk::order_select(os, ctx->ready.selected_count(), ctx->stream));
-    } else
-    HQ_HIP(hqk::select_scatter(cols.id, ctx->scan.group_keys(), cols.n, ctx->last_Q, ctx->last_G, ctx->last_geom, ctx->scan.slice_table(),
-                               ctx->h_plan.as<uint32_t>() + ctx->last_tb, d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), nullptr, nullptr, 0,
-                               cols.rq, ctx->stream));
+    // the selection of the last tick once more, writing tombstones instead of the selected ids (hqmap::Mapper::replay_selection)
+    if (int rc = map_fail(ctx, ctx->map.replay_selection(ctx->stream, hqmap::REPLAY_TOMBSTONE, ctx->ready.cols(), ctx->scan, ctx->ready.selected_count()))) return rc;
     return ready_fail(ctx, ctx->ready.consumed(ready_env(ctx)));
 }); }
 
@@ -2168,14 +1635,18 @@ int hqtick_debug_block_solve_host(uint32_t n_cols, uint32_t n_resources, const u
     return emu.solve(ct, cl, out) ? 0 : HQTICK_E_DEVICE;
 }
 
-// Test hook (include/hqtick_debug.h): the host stages on caller-supplied scan outputs.  No device is touched.
-int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels,
-                             const uint64_t *levels, const uint32_t *hist, hqtick_result *out) {
+// Test hooks (include/hqtick_debug.h): the host stages on caller-supplied scan outputs.  No device is touched.  with_plan: the five stages of the mapping plan
+// (map_core.h) behind the solver, on the Retracting tasks' (key, rank) arrays of the dense form, the plan's big tables in a heap block.
+static uint32_t *heap_storage(void *vec, size_t words) { auto *v = static_cast<std::vector<uint32_t> *>(vec); v->assign(words, 0); return v->data(); }
+static int host_stages(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels, const uint64_t *levels,
+                       const uint32_t *hist, bool with_plan, const uint32_t *retr_key, const uint32_t *retr_rank, hqtick_result *out, std::string *err) {
     if (!config || !s || !out) return HQTICK_E_INVALID;
+    struct KeepError { hqtick_ctx *c; std::string *e; ~KeepError() { if (e) *e = c->err; } };  // the refusal's text, for the hook that hands it out
     static thread_local hqtick_ctx *holder = nullptr;  // owns the result arrays; never creates a stream or a buffer
     if (!holder) holder = new hqtick_ctx();
     hqtick_ctx *ctx = holder;
-    ctx->cfg = *config;
+    KeepError keep{ctx, err};
+    ctx->cfg = *config; ctx->err.clear();
     if (int rc = validate(ctx, s, false)) return rc;
     WorkerEval ev; ev.flags = vflags; ev.tmc = vtmc;
     hqhost::Problem pb;
@@ -2212,15 +1683,47 @@ int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot 
     g_last_stage_us[0] = cnt.t_classify_us; g_last_stage_us[1] = cnt.t_blocks_us; g_last_stage_us[2] = cnt.t_decode_us;
     for (size_t i = 0; i < cnt.mn_rq.size(); i++)
         for (auto &set : cnt.mn_sets[i]) { g_last_mn_rq.push_back(cnt.mn_rq[i]); g_last_mn_worker.insert(g_last_mn_worker.end(), set.begin(), set.end()); g_last_mn_off.push_back((uint32_t)g_last_mn_worker.size()); }
-    ctx->cnt_rq.clear(); ctx->cnt_variant.clear(); ctx->cnt_worker.clear(); ctx->cnt_value.clear();
+    hqmap::HostResult &hr = ctx->map.res;
+    hr.cnt_rq.clear(); hr.cnt_variant.clear(); hr.cnt_worker.clear(); hr.cnt_value.clear();
     cnt.pairs();
     for (size_t k = 0; k < cnt.keys.size(); k++)
-        for (auto &wc : cnt.per_key[k]) { ctx->cnt_rq.push_back(cnt.keys[k].first); ctx->cnt_variant.push_back(cnt.keys[k].second); ctx->cnt_worker.push_back(wc.first); ctx->cnt_value.push_back(wc.second); }
-    out->n_counts = (uint32_t)ctx->cnt_rq.size(); out->count_rq = ctx->cnt_rq.data(); out->count_variant = ctx->cnt_variant.data();
-    out->count_worker = ctx->cnt_worker.data(); out->count_value = ctx->cnt_value.data();
+        for (auto &wc : cnt.per_key[k]) { hr.cnt_rq.push_back(cnt.keys[k].first); hr.cnt_variant.push_back(cnt.keys[k].second); hr.cnt_worker.push_back(wc.first); hr.cnt_value.push_back(wc.second); }
     out->is_optimal = cnt.is_optimal; out->is_canonical = cnt.is_canonical && cnt.is_optimal;
     out->status = cnt.is_optimal ? HQTICK_DONE : (cnt.empty() ? HQTICK_NO_PROGRESS : HQTICK_NEED_MORE_COMPUTE);
+    if (with_plan) {  // (plan_keys writes the counts itself: the same rows, in the same order)
+        static thread_local std::vector<uint32_t> tables;
+        hqmap::Plan &ps = ctx->map.plan;
+        hqmap::PlanIn in{};
+        in.sc = &sc; in.cnt = &cnt; in.s = s; in.rqs = pb.rqs.data(); in.variants = pb.variants.data();
+        in.proactive_filling_reserve = config->proactive_filling_reserve; in.proactive_filling_max = config->proactive_filling_max; in.flags = config->flags;
+        in.shard_count = 1; in.retr_key = retr_key; in.retr_rank = retr_rank; in.transpose_on = transpose_enabled();
+        for (size_t g = 0; g < sc.hist.size(); g++) in.N += sc.hist[g];
+        in.storage = heap_storage; in.user = &tables;
+        const char *why = nullptr; int rc;
+        if ((rc = hqmap::plan_keys(ps, hr, in, &why)) || (rc = hqmap::plan_redirects(ps, hr, in, &why)) || (rc = hqmap::plan_prefill(ps, hr, in, &why)) ||
+            (rc = hqmap::plan_outputs(ps, hr, in, &why)))
+            return fail(ctx, rc, why);
+        hqmap::assemble_host_part(ps, hr, in);
+        out->rec_off = hr.rec_off.data(); out->retract_off = hr.retract_off.data(); out->retract_task = hr.retract_task.data();
+        out->n_redirects = (uint32_t)hr.red_task.size(); out->redirect_task = hr.red_task.data(); out->redirect_worker = hr.red_worker.data();
+        out->redirect_variant = hr.red_variant.data(); out->redirect_kind = hr.red_kind.data(); out->new_free = hr.new_free.data();
+    }
+    out->n_counts = (uint32_t)hr.cnt_rq.size(); out->count_rq = hr.cnt_rq.data(); out->count_variant = hr.cnt_variant.data();
+    out->count_worker = hr.cnt_worker.data(); out->count_value = hr.cnt_value.data();
     return out->status;
+}
+int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels,
+                             const uint64_t *levels, const uint32_t *hist, hqtick_result *out) {
+    return host_stages(config, s, vflags, vtmc, n_levels, levels, hist, false, nullptr, nullptr, out, nullptr);
+}
+int hqtick_debug_host_plan(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels, const uint64_t *levels,
+                           const uint32_t *hist, const uint32_t *retracting_key, const uint32_t *retracting_rank, hqtick_result *out, const char **error) {
+    static thread_local std::string text;
+    if (error) *error = "";
+    if (s && s->n_retracting && (!retracting_key || !retracting_rank)) return HQTICK_E_INVALID;
+    const int rc = host_stages(config, s, vflags, vtmc, n_levels, levels, hist, true, retracting_key, retracting_rank, out, &text);
+    if (rc < 0 && error) *error = text.c_str();
+    return rc;
 }
 
 int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *s, const hqtick_query_workers *fake, const uint8_t *vflags, const uint32_t *vtmc,
@@ -2298,10 +1801,10 @@ int hqtick_set_record_sink(hqtick_ctx *ctx, void *device_ptr, size_t capacity_by
 int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     if (!ctx || !avg_us || iters <= 0) return HQTICK_E_INVALID;
     if (!ctx->ready.selection_valid() || !ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel needs a preceding hqtick_run_resident tick that placed tasks");
-    if (ctx->last_ordered) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel times the dense scan: the last tick took the ordered view");
+    const hqmap::Mapper::Last last = ctx->map.last_selection();
+    if (last.ordered) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel times the dense scan: the last tick took the ordered view");
     HQ_HIP(hipSetDevice(ctx->device));
-    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n; const hqk::WaveGeom g = ctx->last_geom;
-    const uint32_t *d = ctx->d_map.as<uint32_t>();
+    const hqready::Cols cols = ctx->ready.cols(); const hqk::WaveGeom g = last.geom;
     if (which == 2) {  // calibration: an EMPTY kernel of K1's grid, each launch bracketed by its own start / stop events like the stats pass of a tick
         double sum = 0.0; int cnt = 0;
         for (int i = 0; i < iters; i++) {
@@ -2320,9 +1823,8 @@ int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
     if (as_graph) HQ_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     else HQ_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
     for (int i = 0; i < iters; i++) {
-        if (which == 0) { if (int rc = scan_fail(ctx, ctx->scan.relaunch_level_hist(ctx->stream, cols, ctx->last_L, ctx->last_Q, g))) return rc; }
-        else if (which == 1) HQ_HIP(hqk::select_scatter(cols.id, ctx->scan.group_keys(), N, ctx->last_Q, ctx->last_G, g, ctx->scan.slice_table(), ctx->h_plan.as<uint32_t>() + ctx->last_tb,
-                                                        d + ctx->last_tb, ctx->d_sel_task.as<uint64_t>(), ctx->d_sel_level.as<uint16_t>(), ctx->h_plan.dev<void>(), ctx->d_map.p, ctx->last_plan_bytes, nullptr, ctx->stream));
+        if (which == 0) { if (int rc = scan_fail(ctx, ctx->scan.relaunch_level_hist(ctx->stream, cols, last.L, last.Q, g))) return rc; }
+        else if (which == 1) { if (int rc = map_fail(ctx, ctx->map.replay_selection(ctx->stream, hqmap::REPLAY_TIMED, cols, ctx->scan, ctx->ready.selected_count()))) return rc; }
         else return fail(ctx, HQTICK_E_INVALID, "which: 0 = level_hist, 1 = select_scatter, 2 = empty kernel of level_hist's grid");
     }
     if (as_graph) {
@@ -2337,7 +1839,7 @@ int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
         hipGraphExecDestroy(ge); hipGraphDestroy(gr);
     } else HQ_HIP(hipEventRecord(ctx->ev[11], ctx->stream));
     if (which == 0)  // K1 left raw counts in the slice table: turn them back into offsets
-        if (int rc = scan_fail(ctx, ctx->scan.relaunch_scan_waves(ctx->stream, g, ctx->last_G))) return rc;
+        if (int rc = scan_fail(ctx, ctx->scan.relaunch_scan_waves(ctx->stream, g, last.G))) return rc;
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0;
     HQ_HIP(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));

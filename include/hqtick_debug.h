@@ -71,6 +71,15 @@ int hqtick_debug_order_rank_of(hqtick_ctx *ctx, const uint64_t *want, uint32_t n
 int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot *snapshot, const uint8_t *vflags, const uint32_t *vtmc,
                              uint32_t n_levels, const uint64_t *levels, const uint32_t *hist, hqtick_result *out);
 
+/* The same, and behind the solver the host part of the mapping (csrc/map_core.h: create_task_mapping and process_proactive_filling as index arithmetic, the five
+ * stages of the plan).  retracting_key / retracting_rank [snapshot->n_retracting]: what the dense scan reports of every Retracting task — key = level * Q + rq
+ * (0xFFFFFFFF: not in the ready set), rank = its position among the tasks of that (level, rq) in ascending id.  Fills, beyond what hqtick_debug_host_stages
+ * fills, rec_off, retract_off / retract_task, the redirects with their kinds and new_free; the records stay empty (they are K4's and K5's).  A refusal returns
+ * its HQTICK_E_* code and leaves its text in *error (may be NULL; valid until the next call on this thread). */
+int hqtick_debug_host_plan(const hqtick_config *config, const hqtick_snapshot *snapshot, const uint8_t *vflags, const uint32_t *vtmc,
+                           uint32_t n_levels, const uint64_t *levels, const uint32_t *hist, const uint32_t *retracting_key,
+                           const uint32_t *retracting_rank, hqtick_result *out, const char **error);
+
 /* The host stages of hqtick_query (compute_new_worker_query, scheduler/query.rs:12-131) on caller-supplied scan outputs: as above, plus
  * fake_vflags / fake_vtmc [fake->n_workers * NV] = what K2 writes for the fake workers (free == total).  Fills `out` (valid until the next call
  * on this thread). */

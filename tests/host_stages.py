@@ -1,6 +1,6 @@
-"""CPU-side driver of hqtick_debug_host_stages (include/hqtick_debug.h): the tick's HOST stages — create_task_batches +
-run_scheduling_solver, incl. the separable path, the lazy batch-size rows, the elimination of provably empty workers and the exact solver —
-on scan outputs computed here in numpy.  The numpy part restates the CONTRACT of the scan kernels (what K2 writes per (worker, variant),
+"""CPU-side driver of hqtick_debug_host_stages / hqtick_debug_host_plan (include/hqtick_debug.h): the tick's HOST stages — create_task_batches +
+run_scheduling_solver, incl. the separable path, the lazy batch-size rows, the elimination of provably empty workers and the exact solver, and behind them
+the host part of the mapping — on scan outputs computed here in numpy.  The numpy part restates the CONTRACT of the scan kernels (what K2 writes per (worker, variant),
 what K0/K1/K1b produce per (level, rq)); it is test infrastructure, the product never runs it."""
 import ctypes as C
 
@@ -29,6 +29,25 @@ def scan_outputs(sc: abi.SnapshotC):
         li = (len(levels) - 1 - np.searchsorted(asc, prio)).astype(np.int64)  # index in the descending table
         np.add.at(hist, li * Q + rq.astype(np.int64), 1)
     return flags, tmc, levels, hist[: len(levels) * Q]
+
+
+def retracting_positions(sc: abi.SnapshotC, levels):
+    """(key u32[n_retracting], rank u32[n_retracting]) of the Retracting tasks in the dense scan — csrc/kernels.hip: k_rank_of.  key = level * Q + rq
+    (0xFFFFFFFF: not in the ready set), rank = the task's position among the tasks of that (level, rq) in ascending id"""
+    nr, n, Q = int(sc.n_retracting), int(sc.n_ready), sc.n_requests
+    key, rank = np.full(nr, 0xFFFFFFFF, np.uint32), np.zeros(nr, np.uint32)
+    if not nr or not n:
+        return key, rank
+    want = abi._np(sc.retracting_task, nr, np.uint64)
+    ids, prio, rq = abi._np(sc.task_id, n, np.uint64), abi._np(sc.task_priority, n, np.uint64), abi._np(sc.task_rq, n, np.uint32)
+    for i, t in enumerate(want):
+        at = np.flatnonzero(ids == t)
+        if len(at):
+            j = int(at[0])
+            level = int(np.flatnonzero(levels == prio[j])[0])
+            key[i] = level * Q + int(rq[j])
+            rank[i] = int(np.count_nonzero((prio == prio[j]) & (rq == rq[j]) & (ids < t)))
+    return key, rank
 
 
 def request_tables(sc: abi.SnapshotC):
@@ -86,6 +105,27 @@ class HostStages:
         if rc < 0:
             raise tick.HqTickError(rc, "hqtick_debug_host_stages")
         return abi.parse_result(out, len(snap.worker_id), snap.n_resources)
+
+    def plan(self, snap: abi.Snapshot):
+        """hqtick_debug_host_plan: the host stages and the host part of the mapping behind them -> (abi.Result with counts, retracts, redirects with their kinds and
+        new_free filled and the records empty, rec_off u32[W + 1]).  A refusal raises tick.HqTickError with the refusal's text."""
+        sc = snap.to_c()
+        flags, tmc, levels, hist = scan_outputs(sc)
+        key, rank = retracting_positions(sc, levels)
+        out, why = abi.ResultC(), C.c_char_p()
+        z8, z32, z64 = np.zeros(1, np.uint8), np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+        pick = lambda a, z: a if len(a) else z
+        self.lib.hqtick_debug_host_plan.argtypes = [C.POINTER(abi.Config), C.POINTER(abi.SnapshotC), abi.u8p, abi.u32p, C.c_uint32, abi.u64p, abi.u32p, abi.u32p, abi.u32p,
+                                                    C.POINTER(abi.ResultC), C.POINTER(C.c_char_p)]
+        rc = self.lib.hqtick_debug_host_plan(C.byref(self.cfg), C.byref(sc), pick(flags, z8).ctypes.data_as(abi.u8p), pick(tmc, z32).ctypes.data_as(abi.u32p), len(levels),
+                                             pick(levels, z64).ctypes.data_as(abi.u64p), pick(hist, z32).ctypes.data_as(abi.u32p), pick(key, z32).ctypes.data_as(abi.u32p),
+                                             pick(rank, z32).ctypes.data_as(abi.u32p), C.byref(out), C.byref(why))
+        if rc < 0:
+            raise tick.HqTickError(rc, (why.value or b"").decode())
+        W = len(snap.worker_id)
+        rec_off = abi._np(out.rec_off, W + 1, np.uint32).copy() if W else np.zeros(1, np.uint32)
+        out.rec_off = None  # (the records are K4's and K5's: none to parse)
+        return abi.parse_result(out, W, snap.n_resources), rec_off
 
     def query(self, snap: abi.Snapshot, fake_ids, fake_total, fake_remaining=None, fake_min_util=None):
         """same contract as Tick.query, through hqtick_debug_host_query: (is_loaded per fake worker, is_optimal)"""

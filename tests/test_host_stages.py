@@ -1,6 +1,8 @@
 """The tick's HOST stages (batches + placement: separable path, lazy size rows, empty-worker elimination, exact solver) on a machine
 without a GPU, through hqtick_debug_host_stages: same batches and same counts as the canonical oracle on the randomised scenario
-families of the GPU fuzz suite.  (The scan kernels, the selection and the mapping run only on the GPU: tests/test_gpu_*.py.)"""
+families of the GPU fuzz suite — and, through hqtick_debug_host_plan, the host part of the mapping (csrc/map_core.h: retracts, redirects with their
+kinds, free vectors, records per worker) equal to the reference's mapping on the same placement (Oracle.tick_given).  (The scan kernels, the selection and
+the records themselves run only on the GPU: tests/test_gpu_*.py.)"""
 import numpy as np
 import pytest
 
@@ -42,6 +44,41 @@ def _same_host_part(got, want, model):
         assert zw * (1.0 - 1e-4) - 1e-12 <= zg <= zw + 1e-9 * max(1.0, abs(zw)), (zg, zw)
 
 
+MAPPING_ASSERTS = "a Retracting task reached take_tasks_for_prefill: the reference asserts task.is_waiting() (mapping.rs:221)"
+
+
+def _same_mapping_part(hs, snap):
+    """The host part of the mapping on this snapshot (hqtick_debug_host_plan) against the reference's mapping on the SAME placement (Oracle.tick_given on the
+    hook's counts and multi-node placements, which needs no solver and so is never skipped for a solver's limit): per-worker retracts, redirects with their
+    kinds, new_free, and the number of records of every worker — what test_gpu_parity.assert_same compares, minus what needs K4 / K5.  Where the reference
+    asserts (a Retracting task reaching take_tasks_for_prefill), the hook must refuse with HQTICK_E_UNSUPPORTED and that text.  Returns the reference's
+    result, or None where it asserts."""
+    import coupled_cases as cc
+    from hyperqueue_amd import tick
+    from oracle.oracle import Oracle
+
+    got = refusal = None
+    try:
+        got, rec_off = hs.plan(snap)
+        base = got
+    except tick.HqTickError as e:
+        refusal = e
+        base = hs.stages(snap)  # (the same body without the plan: the placement the refused plan was made for)
+    given = list(base.counts) + [(q, 0, w, 1) for (q, ws) in cc.last_mn(hs.lib) for w in ws]
+    try:
+        want = Oracle(hs.cfg, canonical=True).tick_given(snap, given, base.is_optimal)
+    except RuntimeError:
+        assert refusal is not None and refusal.code == abi.HQTICK_E_UNSUPPORTED and MAPPING_ASSERTS in str(refusal), refusal
+        return None
+    assert refusal is None, refusal
+    assert got.counts == want.counts
+    assert got.retracts == want.retracts
+    assert sorted(zip(got.redirects, got.redirect_kinds)) == sorted(zip(want.redirects, want.redirect_kinds))
+    assert (got.new_free == want.new_free).all()
+    assert [int(rec_off[w + 1] - rec_off[w]) for w in range(len(want.records))] == [len(r) for r in want.records]
+    return want
+
+
 @pytest.mark.parametrize("seed", range(150))
 def test_host_stages_fuzz_scenarios(seed):
     import test_gpu_fuzz as f
@@ -54,6 +91,8 @@ def test_host_stages_fuzz_scenarios(seed):
     for _ in range(2):
         snap = e.snapshot()
         got = hs.stages(snap)
+        if seed < 40:
+            _same_mapping_part(hs, snap)
         want = e.schedule(o)
         if not want.is_optimal:
             pytest.skip("oracle hit its limit")
@@ -199,6 +238,7 @@ class _ShadowBackend:
         want = o.tick(snap)
         got = hs.stages(snap)
         _same_host_part(got, want, o.last_model())
+        _same_mapping_part(hs, snap)
         self.flags.append(got.is_canonical == got.is_optimal)
         self.ticks += 1
         return want
@@ -265,6 +305,7 @@ def test_host_stages_prefill_disposal_family(seed):
         for c in which:
             e.new_task(shapes[c].user_priority(prio))
         snap = e.snapshot()
+        _same_mapping_part(hs, snap)
         try:
             want = o.tick(snap)
         except RuntimeError:  # a Retracting task reached the prefill step: the reference asserts there
@@ -282,3 +323,49 @@ def test_host_stages_prefill_disposal_family(seed):
         if answer:
             for t in [t for t in sorted(e.tasks.values(), key=lambda t: t.id) if t.state == 4 and t.id not in e.retaken_variant][:2]:
                 e.retract_response(t.worker, [t.id])
+
+
+def test_prefill_disposal_family_reaches_every_mapping_outcome():
+    """the family above, seeds 0-59 as that test generates them, counted in the oracle's own results: it holds redirects of each of the three kinds, retracts,
+    prefill records and ticks on which the reference asserts — so the mapping comparison of that test is one of every outcome of the plan's redirect and
+    prefill stages.  (Measured with the oracle alone: 10 FROM_PREFILL, 10 RETARGET, 23 SAME_WORKER redirects, 10 retracts, 235 prefill records, 26 seeds that end
+    in the assertion.)"""
+    from hyperqueue_amd.core import SchedEnv, WorkerBuilder as WB
+    from oracle.oracle import Oracle
+
+    kinds, retracts, prefills, asserted = {abi.HQ_REDIRECT_FROM_PREFILL: 0, abi.HQ_REDIRECT_RETARGET: 0, abi.HQ_REDIRECT_SAME_WORKER: 0}, 0, 0, 0
+    for seed in range(60):
+        rng = np.random.default_rng(9000 + seed)
+        cfg = abi.make_config(reserve=int(rng.integers(0, 2)), fill_max=int(rng.integers(1, 4)), time_limit_s=20.0)
+        e = SchedEnv(cfg)
+        o = Oracle(cfg, canonical=True)
+        shapes = [TB().cpus(1), TB().cpus(2)]
+        for c in [int(x) for x in np.random.default_rng(seed).integers(1, 5, size=3)]:
+            e.new_worker(WB(c))
+        prio = 0
+        for round_ in range(5):
+            n_new = int(rng.integers(1, 7)) if round_ else int(rng.integers(8, 16)); which = [int(rng.integers(0, 2)) for _ in range(n_new)]
+            if round_ and rng.random() < 0.7:
+                prio += 1
+            for c in which:
+                e.new_task(shapes[c].user_priority(prio))
+            try:
+                want = o.tick(e.snapshot())
+            except RuntimeError:
+                asserted += 1
+                break
+            for k in want.redirect_kinds:
+                kinds[k] += 1
+            retracts += sum(len(r) for r in want.retracts)
+            prefills += sum(1 for recs in want.records for (_t, _v, kind) in recs if kind == abi.HQ_REC_PREFILL)
+            e.apply(want)
+            k = int(rng.integers(1, 7)); answer = rng.random() < 0.6
+            done = 0
+            for t in sorted(e.tasks.values(), key=lambda t: t.id):
+                if t.state == 1 and done < k:
+                    e.finish_task(t.id, t.worker); done += 1
+            if answer:
+                for t in [t for t in sorted(e.tasks.values(), key=lambda t: t.id) if t.state == 4 and t.id not in e.retaken_variant][:2]:
+                    e.retract_response(t.worker, [t.id])
+    print(kinds, retracts, prefills, asserted)
+    assert all(n >= 1 for n in kinds.values()) and retracts >= 1 and prefills >= 1 and asserted >= 1, (kinds, retracts, prefills, asserted)
