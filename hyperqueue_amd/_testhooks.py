@@ -18,4 +18,11 @@ def load() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise FileNotFoundError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         _LIB = C.CDLL(LIB_PATH)
+        # the deferred row check's hooks (include/hqtick_debug.h): switch (1 / 0 / -1), deferred checks since the last clear, fail the next n (returns those left unused)
+        _LIB.hqtick_debug_set_defer_row_check.argtypes = [C.c_int]
+        _LIB.hqtick_debug_set_defer_row_check.restype = None
+        _LIB.hqtick_debug_deferred_row_checks.argtypes = [C.c_int]
+        _LIB.hqtick_debug_deferred_row_checks.restype = C.c_uint32
+        _LIB.hqtick_debug_fail_row_checks.argtypes = [C.c_uint32]
+        _LIB.hqtick_debug_fail_row_checks.restype = C.c_uint32
     return _LIB

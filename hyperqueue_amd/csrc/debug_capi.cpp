@@ -101,6 +101,13 @@ extern "C" uint32_t hqtick_debug_first_cut(unsigned char *out, uint32_t cap) {
     return (uint32_t)b.size();
 }
 
+// The fast path's row check deferred into phase C's window (csrc/milp.h: CheckHook).  Any of the three installs the hook on this thread; it stays.
+static thread_local hqmilp::CheckHook g_row_check_hook;
+static hqmilp::CheckHook &row_check_hook() { hqmilp::g_check_hook = &g_row_check_hook; return g_row_check_hook; }
+extern "C" void hqtick_debug_set_defer_row_check(int on) { row_check_hook().allow = on; }
+extern "C" uint32_t hqtick_debug_deferred_row_checks(int clear) { hqmilp::CheckHook &h = row_check_hook(); const uint32_t n = h.deferred; if (clear) h.deferred = 0; return n; }
+extern "C" uint32_t hqtick_debug_fail_row_checks(uint32_t n) { hqmilp::CheckHook &h = row_check_hook(); const uint32_t left = h.fail_next; h.fail_next = n; return left; }
+
 // clock mode: the phase function of k_clock_rows over arrays, in the linear form the kernel folds and in the sorted form of the host mirror
 extern "C" int hqtick_debug_clock_rows(uint32_t n, const int64_t *deadline_ns, int64_t now_ns, uint32_t nv, const uint64_t *min_time_ns, int sorted_form, int64_t *remaining_out) {
     if ((n && (!deadline_ns || !remaining_out)) || (nv && !min_time_ns)) return HQTICK_E_INVALID;

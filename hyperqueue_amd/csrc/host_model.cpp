@@ -1375,7 +1375,8 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
         size_t run_blocks = 0; for (const auto &br : m.block_runs) run_blocks += (size_t)br.n_blocks;
         fprintf(stderr, "[model] cuts done at %.3f ms: %d columns, %d rows, %zu terms, %zu worker signatures, %zu (batch, cut, blocker) passes over the workers; %zu equal-block runs over %zu blocks, %zu (cut, blocker) passes decided once\n", (t_model1 - t_model0) / 1e3, m.ncols(), m.nrows(), m.rcol.size(), sig_rep.size(), n_triples, m.block_runs.size(), run_blocks, n_decided_once);
     }
-    hqmilp::Result sol = hqmilp::solve(m, pb.time_limit_s, !pb.certificate_only, hqmilp::REFERENCE_MIP_REL_GAP, pb.pricer);  // :432-438
+    hqmilp::SolveOpts opts; opts.no_fast_path = pb.no_fast_path; opts.defer_row_check = pb.defer_row_check;
+    hqmilp::Result sol = hqmilp::solve(m, pb.time_limit_s, !pb.certificate_only, hqmilp::REFERENCE_MIP_REL_GAP, pb.pricer, &opts);  // :432-438
     if (trace_model) fprintf(stderr, "[model] solve done %.3f ms after the model\n", (clock_us() - t_model1) / 1e3);
     out.pre_us = t_model0 - t_enter; out.model_us = t_model1 - t_model0; out.milp_us = clock_us() - t_model1; out.price_sweeps = sol.price_sweeps; out.price_rounds = sol.price_rounds; out.price_us = sol.price_total_us;
     out.milp_nodes = sol.nodes; out.milp_cols = m.ncols(); out.milp_rows = m.nrows(); out.milp_components = sol.n_components;
@@ -1430,6 +1431,7 @@ Counts run_scheduling_solver(const Problem &pb, const std::vector<TaskBatch> &ba
     hqhb::insertion_order(mn_hash.data(), (uint32_t)mn_hash.size(), ord);
     for (uint32_t k : ord) { out.mn_rq.push_back(mn_list[k]); out.mn_sets.push_back(std::move(mn_sets[k])); }
     if (trace_model) fprintf(stderr, "[model] decoded %.3f ms after the model, %.3f ms after the solver was entered\n", (clock_us() - t_model1) / 1e3, (clock_us() - t_enter) / 1e3);
+    if (sol.row_check.pending) { out.row_check.check = std::move(sol.row_check); out.row_check.model = std::move(m); }  // (the check reads the model: it goes along, nothing is copied)
     return out;
 }
 

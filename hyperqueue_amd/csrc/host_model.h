@@ -128,6 +128,8 @@ struct Problem {
     const WorkerSet *custom = nullptr;   // what-if query: fake workers replace the worker list of the solver
     double time_limit_s = 5.0;
     bool certificate_only = false;       // HQTICK_FLAG_CERTIFICATE_ONLY: the coupled model's solve stops at the rel_gap certificate, as the reference's does
+    bool defer_row_check = false;        // the caller runs the fast path's row check itself (Counts::row_check) and, should it fail, solves again with no_fast_path
+    bool no_fast_path = false;           // this call's coupled model takes the classic path (hqmilp::SolveOpts)
     bool rq_multi_node(uint32_t rq) const { return variants[rqs[rq].first_variant].multi_node(); }
     // Worker::is_capable_to_run_rqv  server/worker.rs:277-296
     bool capable_rqv(const WorkerSet &ws, uint32_t w, uint32_t rq) const {
@@ -173,6 +175,11 @@ struct Counts {
         pairs_built = true;
     }
     size_t key_size(size_t k) const { return pairs_built ? per_key[k].size() : lists[key_list[k]].widx.size(); }  // workers of key k
+    // Problem::defer_row_check: the counts come from a point the sweeps certified whose check against the model's rows has not run yet.  The model (moved here, not
+    // copied) and the point live on until settle_row_check(); false = the counts are void, solve again with Problem::no_fast_path.
+    struct PendingRowCheck { hqmilp::Model model; hqmilp::RowCheck check; } row_check;
+    bool row_check_pending() const { return row_check.check.pending; }
+    bool settle_row_check() { return hqmilp::run_row_check(row_check.model, row_check.check); }
     bool is_optimal = true;
     bool is_canonical = true;  // every solve completed its tie-break phase
     bool empty() const {

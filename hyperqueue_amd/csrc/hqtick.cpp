@@ -97,6 +97,7 @@ struct hqtick_ctx {
     hqcluster::Retracting retr;   // hqtick_retracting_* (ABI 7): the table of Retracting tasks
     uint32_t last_row_groups = 0; // hqtick_cluster_last_row_groups
     bool wait_on_kernel = true;   // HQ_HIP_LAST; HQTICK_WAIT_ON_KERNEL=0: hipStreamSynchronize at every wait (A/B)
+    bool defer_row_check = true;  // the coupled fast path's row check runs while phase C's kernels do; HQTICK_DEFER_ROW_CHECK=0: inside the solve (A/B)
     hqhost::Problem pb;
     // results (host)
     std::vector<uint32_t> b_rq, b_size, b_limit, b_cut_off, c_size, c_bl_off, bl_rq, bl_size; std::vector<uint8_t> b_lr, b_blk;
@@ -498,9 +499,9 @@ struct TickRun {
     }
 
     // GPU phase C (hqmap::Mapper::phase_c), with what the assignment ledger needs of it
-    int phase_c(const hqmap::Env &me, const hqmap::PlanIn &in) {
+    int phase_c(const hqmap::Env &me, const hqmap::PlanIn &in, const std::function<void()> *while_gpu_runs) {
         hqmap::PhaseC pc{};
-        pc.sc = &sc; pc.scan = &ctx->scan; pc.ready = &ctx->ready; pc.in = &in;
+        pc.sc = &sc; pc.scan = &ctx->scan; pc.ready = &ctx->ready; pc.in = &in; pc.while_gpu_runs = while_gpu_runs;
         pc.consume_in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
         pc.ledger_pfq_rq = ctx->asg.on;
         if (ps.n_sel && pc.consume_in_tick && ctx->asg.on && s->n_retracting) {  // the redirects of Retracting tasks look their request id up after K4 has tombstoned it
@@ -518,6 +519,16 @@ struct TickRun {
         if (tm.sweep_us >= 0) ctx->stats.sweep_us = tm.sweep_us;
         if (tm.other_us >= 0) ctx->stats.other_us = tm.other_us;
         return rc;
+    }
+
+    // The fast path's row check may move into phase C's window only where a discarded phase C leaves no trace: no tombstones written by K4, no
+    // ledger staging, no record sink, no replica whose sweeps or records others read, no Retracting task whose redirect is planned from the selection.
+    bool may_defer_row_check() const {
+        const int sw = hqmilp::g_check_hook ? hqmilp::g_check_hook->allow : -1;
+        if (!(sw < 0 ? ctx->defer_row_check : sw != 0)) return false;
+        if (use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK)) return false;
+        if (ctx->asg.on || ctx->sink || ctx->shard_count > 1 || ctx->xfn || ctx->comm) return false;
+        return s->n_retracting == 0;
     }
 
     void finish(const hqmap::Env &me, double t1, double t2, double t3) {
@@ -565,54 +576,76 @@ struct TickRun {
         export_batches(ctx, batches, out);
         mark();  // 1: batches
         const double t2 = now_us();
-        DeviceBlocks dev_blocks(ctx);
-        pb.blocks = &dev_blocks; pb.block_min_classes = ctx->block_min_classes; pb.pricer = ctx->pricer;
-        pb.block_verify = ctx->block_verify; pb.tick_seq = ctx->tick_seq++;
-        pb.memo = (ctx->cfg.flags & (HQTICK_FLAG_NO_BLOCK_MEMO | HQTICK_FLAG_NO_TICK_CACHES)) ? nullptr : &ctx->block_memo;
-        double shard_sweep_us = -1.0;
-        ctx->x_calls = 0; ctx->x_bytes = 0; ctx->x_us = 0;
-        if (CtxExchange::available(ctx)) {  // the ranks of a sharded scheduler split the sweeps and the class blocks (no-ops below their thresholds)
-            CtxExchange xch(ctx);
-            ShardedBlocks sh_blocks(dev_blocks, xch, ctx->shard_min_classes);
-            pb.blocks = &sh_blocks;
-            if (ctx->pricer) {
-                hqprice::ShardedSweeper sh_sweeps(*ctx->pricer, xch, ctx->shard_min_blocks);
-                pb.pricer = &sh_sweeps;
-                cnt = hqhost::run_scheduling_solver(pb, batches);
-                shard_sweep_us = sh_sweeps.stat_sweep_us;
-            } else cnt = hqhost::run_scheduling_solver(pb, batches);
-        } else cnt = hqhost::run_scheduling_solver(pb, batches);
-        pb.blocks = nullptr; pb.pricer = nullptr;
-        ctx->stats.price_sweeps = (uint32_t)cnt.price_sweeps; ctx->stats.price_rounds = (uint32_t)cnt.price_rounds; ctx->stats.price_us = cnt.price_us; ctx->stats.milp_us = cnt.milp_us; ctx->stats.model_us = cnt.model_us; ctx->stats.solve_pre_us = cnt.pre_us;
-        ctx->stats.price_sweep_us = shard_sweep_us >= 0.0 ? shard_sweep_us : (ctx->pricer ? ctx->pricer->stat_sweep_us : 0.0); ctx->stats.milp_cols = (uint32_t)cnt.milp_cols; ctx->stats.milp_rows = (uint32_t)cnt.milp_rows;
-        ctx->stats.n_classes_verified = cnt.blocks_verified; ctx->stats.n_classes_mismatch = cnt.blocks_mismatch; ctx->stats.n_classes_rejected = cnt.blocks_rejected; ctx->stats.n_classes_memo = cnt.blocks_memo;
-        ctx->stats.exchange_calls = (uint32_t)ctx->x_calls; ctx->stats.exchange_bytes = ctx->x_bytes; ctx->stats.exchange_us = ctx->x_us;
-        if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-        ctx->stats.n_classes_device = cnt.blocks_device; ctx->stats.n_classes_host = cnt.blocks_host; ctx->stats.block_steps_max = cnt.block_steps_max; ctx->stats.n_classes = cnt.n_classes;
-        ctx->stats.solve_classify_us = cnt.t_classify_us; ctx->stats.solve_blocks_us = cnt.t_blocks_us; ctx->stats.solve_decode_us = cnt.t_decode_us;
-        mark();  // 2: solve
-        const double t3 = now_us();
-        out->is_optimal = cnt.is_optimal;
-        out->is_canonical = cnt.is_canonical && cnt.is_optimal;
-        status = HQTICK_DONE;  // scheduler/main.rs:57-68
-        if (!cnt.is_optimal) status = cnt.empty() ? HQTICK_NO_PROGRESS : HQTICK_NEED_MORE_COMPUTE;
-        // ---------------- host: mapping plan ----------------
-        const hqmap::PlanIn in = plan_in();
+        // Solve, plan and phase C.  They run twice in one case only: the placement came from the fast path with its row check deferred into phase C's window (below)
+        // and the check failed — then once more with the fast path off, which is what the inline check's failure leads to.
         const hqmap::Env me = map_env(ctx, t0);
-        hqmap::HostResult &hr = ctx->map.res;
-        const char *why = nullptr;
-        ctx->ready.selection_void();  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
-        if ((rc = plan_fail(hqmap::plan_keys(ps, hr, in, &why), why))) return rc;
-        if ((rc = map_fail(ctx, ctx->map.launch_sweep_early(me)))) return rc;
-        if ((rc = plan_fail(hqmap::plan_redirects(ps, hr, in, &why), why))) return rc;
-        mark();  // 3: key tables + retracts
-        if ((rc = plan_fail(hqmap::plan_prefill(ps, hr, in, &why), why))) return rc;
-        mark();  // 4: prefill plan
-        if ((rc = plan_fail(hqmap::plan_outputs(ps, hr, in, &why), why))) return rc;
-        if ((rc = map_fail(ctx, ctx->map.check_capacity(sc.ordered)))) return rc;
-        mark();  // 5: K5 tables
-        // ---------------- GPU phase C ----------------
-        if ((rc = phase_c(me, in))) return rc;
+        const uint32_t tick_seq = ctx->tick_seq++;
+        const int ntl_solve = ctx->ntl;
+        double t3 = t2;
+        bool check_ok = true;
+        const std::function<void()> check = [&]() { if (cnt.row_check_pending()) check_ok = cnt.settle_row_check(); };
+        auto solve_plan_map = [&](bool defer, bool classic) -> int {
+            int rc;
+            DeviceBlocks dev_blocks(ctx);
+            pb.blocks = &dev_blocks; pb.block_min_classes = ctx->block_min_classes; pb.pricer = ctx->pricer;
+            pb.defer_row_check = defer; pb.no_fast_path = classic;
+            pb.block_verify = ctx->block_verify; pb.tick_seq = tick_seq;
+            pb.memo = (ctx->cfg.flags & (HQTICK_FLAG_NO_BLOCK_MEMO | HQTICK_FLAG_NO_TICK_CACHES)) ? nullptr : &ctx->block_memo;
+            double shard_sweep_us = -1.0;
+            ctx->x_calls = 0; ctx->x_bytes = 0; ctx->x_us = 0;
+            if (CtxExchange::available(ctx)) {  // the ranks of a sharded scheduler split the sweeps and the class blocks (no-ops below their thresholds)
+                CtxExchange xch(ctx);
+                ShardedBlocks sh_blocks(dev_blocks, xch, ctx->shard_min_classes);
+                pb.blocks = &sh_blocks;
+                if (ctx->pricer) {
+                    hqprice::ShardedSweeper sh_sweeps(*ctx->pricer, xch, ctx->shard_min_blocks);
+                    pb.pricer = &sh_sweeps;
+                    cnt = hqhost::run_scheduling_solver(pb, batches);
+                    shard_sweep_us = sh_sweeps.stat_sweep_us;
+                } else cnt = hqhost::run_scheduling_solver(pb, batches);
+            } else cnt = hqhost::run_scheduling_solver(pb, batches);
+            pb.blocks = nullptr; pb.pricer = nullptr; pb.defer_row_check = false; pb.no_fast_path = false;
+            ctx->stats.price_sweeps = (uint32_t)cnt.price_sweeps; ctx->stats.price_rounds = (uint32_t)cnt.price_rounds; ctx->stats.price_us = cnt.price_us; ctx->stats.milp_us = cnt.milp_us; ctx->stats.model_us = cnt.model_us; ctx->stats.solve_pre_us = cnt.pre_us;
+            ctx->stats.price_sweep_us = shard_sweep_us >= 0.0 ? shard_sweep_us : (ctx->pricer ? ctx->pricer->stat_sweep_us : 0.0); ctx->stats.milp_cols = (uint32_t)cnt.milp_cols; ctx->stats.milp_rows = (uint32_t)cnt.milp_rows;
+            ctx->stats.n_classes_verified = cnt.blocks_verified; ctx->stats.n_classes_mismatch = cnt.blocks_mismatch; ctx->stats.n_classes_rejected = cnt.blocks_rejected; ctx->stats.n_classes_memo = cnt.blocks_memo;
+            ctx->stats.exchange_calls = (uint32_t)ctx->x_calls; ctx->stats.exchange_bytes = ctx->x_bytes; ctx->stats.exchange_us = ctx->x_us;
+            if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
+            ctx->stats.n_classes_device = cnt.blocks_device; ctx->stats.n_classes_host = cnt.blocks_host; ctx->stats.block_steps_max = cnt.block_steps_max; ctx->stats.n_classes = cnt.n_classes;
+            ctx->stats.solve_classify_us = cnt.t_classify_us; ctx->stats.solve_blocks_us = cnt.t_blocks_us; ctx->stats.solve_decode_us = cnt.t_decode_us;
+            mark();  // 2: solve
+            t3 = now_us();
+            out->is_optimal = cnt.is_optimal;
+            out->is_canonical = cnt.is_canonical && cnt.is_optimal;
+            status = HQTICK_DONE;  // scheduler/main.rs:57-68
+            if (!cnt.is_optimal) status = cnt.empty() ? HQTICK_NO_PROGRESS : HQTICK_NEED_MORE_COMPUTE;
+            // ---------------- host: mapping plan ----------------
+            const hqmap::PlanIn in = plan_in();
+            hqmap::HostResult &hr = ctx->map.res;
+            const char *why = nullptr;
+            ctx->ready.selection_void();  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
+            if ((rc = plan_fail(hqmap::plan_keys(ps, hr, in, &why), why))) return rc;
+            if ((rc = map_fail(ctx, ctx->map.launch_sweep_early(me)))) return rc;
+            if ((rc = plan_fail(hqmap::plan_redirects(ps, hr, in, &why), why))) return rc;
+            mark();  // 3: key tables + retracts
+            if ((rc = plan_fail(hqmap::plan_prefill(ps, hr, in, &why), why))) return rc;
+            mark();  // 4: prefill plan
+            if ((rc = plan_fail(hqmap::plan_outputs(ps, hr, in, &why), why))) return rc;
+            if ((rc = map_fail(ctx, ctx->map.check_capacity(sc.ordered)))) return rc;
+            mark();  // 5: K5 tables
+            // ---------------- GPU phase C ----------------
+            return phase_c(me, in, defer && cnt.row_check_pending() ? &check : nullptr);
+        };
+        rc = solve_plan_map(may_defer_row_check(), false);
+        check();  // (a pass that did not reach phase C's window: the check decides all the same whether its result, an error included, stands)
+        if (!check_ok) {
+            // What the inline check's failure leads to: the classic path's placement.  The discarded pass has left nothing but buffers the second one overwrites
+            // (may_defer_row_check: no tombstones, no ledger staging, no sink) and the selection's launch state, which goes.
+            HQ_HIP(hipStreamSynchronize(ctx->stream));
+            ctx->ready.selection_void(); ctx->map.forget_selection();
+            ctx->ntl = ntl_solve; cnt = hqhost::Counts();
+            rc = solve_plan_map(false, true);
+        }
+        if (rc) return rc;
         mark();  // 8: phase C synced
         finish(me, t1, t2, t3);
         return status;
@@ -754,6 +787,7 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) { hipStreamDestroy(ctx->stream); delete ctx; return HQTICK_E_DEVICE; }
     if (const char *e = getenv("HQTICK_K2_RIDE_ALONG")) { ctx->k2_own_stream = atoi(e) == 0; ctx->k2_on_hist = atoi(e) == 1; }
     if (const char *e = getenv("HQTICK_WAIT_ON_KERNEL")) ctx->wait_on_kernel = atoi(e) != 0;
+    if (const char *e = getenv("HQTICK_DEFER_ROW_CHECK")) ctx->defer_row_check = atoi(e) != 0;
     {
         bool price = true; uint32_t min_cols = 0;
         if (const char *e = getenv("HQTICK_PRICE")) price = atoi(e) != 0;
@@ -1666,16 +1700,23 @@ static int host_stages(const hqtick_config *config, const hqtick_snapshot *s, co
     hqprice::EmulatedSweeper pemu;
     if (g_price_emulation) { pemu.fail_at = g_price_fault; pemu.budget = g_block_budget; if (g_price_min_cols) pemu.min_cols = g_price_min_cols; pb.pricer = &pemu; }
     hqhost::Counts cnt;
-    if (g_xfn && g_xworld > 1) {  // this call is one rank of a sharded scheduler
-        struct FnExchange : hqprice::Exchange { bool allgather(const void *snd, void *rcv, size_t bytes) override { return g_xfn(g_xuser, snd, rcv, bytes) == 0; } } xch;
-        xch.rank = g_xrank; xch.world = g_xworld;
-        ShardedBlocks sh_blocks(emu, xch, g_xmin_classes);
-        hqprice::ShardedSweeper sh_sweeps(pemu, xch, g_xmin_blocks);
-        if (pb.blocks) pb.blocks = &sh_blocks;
-        if (pb.pricer) pb.pricer = &sh_sweeps;
-        cnt = hqhost::run_scheduling_solver(pb, batches);
-        g_xcalls = (uint32_t)xch.n_calls;
-    } else cnt = hqhost::run_scheduling_solver(pb, batches);
+    auto solve = [&]() {
+        if (g_xfn && g_xworld > 1) {  // this call is one rank of a sharded scheduler
+            struct FnExchange : hqprice::Exchange { bool allgather(const void *snd, void *rcv, size_t bytes) override { return g_xfn(g_xuser, snd, rcv, bytes) == 0; } } xch;
+            xch.rank = g_xrank; xch.world = g_xworld;
+            ShardedBlocks sh_blocks(emu, xch, g_xmin_classes);
+            hqprice::ShardedSweeper sh_sweeps(pemu, xch, g_xmin_blocks);
+            if (pb.blocks) pb.blocks = &sh_blocks;
+            if (pb.pricer) pb.pricer = &sh_sweeps;
+            cnt = hqhost::run_scheduling_solver(pb, batches);
+            g_xcalls = (uint32_t)xch.n_calls;
+        } else cnt = hqhost::run_scheduling_solver(pb, batches);
+    };
+    // hqtick_debug_set_defer_row_check(1): the row check of a fast-path placement is this caller's, as in a tick (TickRun::run) — run behind the solver, and a failure
+    // sends the model down the classic path in a second call.  Never as a rank of a sharded scheduler, like the tick.
+    pb.defer_row_check = hqmilp::g_check_hook && hqmilp::g_check_hook->allow == 1 && !(g_xfn && g_xworld > 1);
+    solve();
+    if (cnt.row_check_pending() && !cnt.settle_row_check()) { pb.defer_row_check = false; pb.no_fast_path = true; solve(); }
     if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
     g_last_guard[0] = cnt.blocks_verified; g_last_guard[1] = cnt.blocks_mismatch; g_last_guard[2] = cnt.blocks_rejected;
     g_last_memo = cnt.blocks_memo;

@@ -2,6 +2,8 @@
 #include "map.h"
 
 #include <chrono>
+#include <cstdio>
+#include <cstdlib>
 
 namespace hqmap {
 
@@ -175,7 +177,12 @@ int Mapper::phase_c(const Env &e, const PhaseC &pc) {
         }
         e.tl.mark();  // 7: phase C enqueued
         assemble_host_part(ps, res, *pc.in);
+        static const bool tracing = getenv("HQMILP_TRACE") != nullptr;   // (the solver's trace: the window's lines stand next to its marks)
+        const double tw0 = tracing ? now_us() : 0.0;
+        if (pc.while_gpu_runs) (*pc.while_gpu_runs)();
+        const double tw1 = tracing ? now_us() : 0.0;
         if (expand_is_last) HQ_HIP(hipEventSynchronize(e.k5b_stop)); else HQ_HIP(hipStreamSynchronize(e.stream));
+        if (tracing && n_sel > 1000) fprintf(stderr, "[map] phase C: %.1f us of the caller's work while the kernels ran, then %.1f us waiting for them\n", tw1 - tw0, now_us() - tw1);
         sweep_inflight = false;
         if (flags[0]) return fail(HQTICK_E_CAPACITY, "mapping kernel capacity exceeded");
         if (sc.ordered && *pc.scan->select_err_host()) return fail(HQTICK_E_DEVICE, "ordered view: the selection left its request's segment");
@@ -184,6 +191,7 @@ int Mapper::phase_c(const Env &e, const PhaseC &pc) {
     if (!n_sel) {
         pc.ready->selected(0);
         assemble_host_part(ps, res, *pc.in);
+        if (pc.while_gpu_runs) (*pc.while_gpu_runs)();
     }
     if (!n_sel && e.sink) {  // nothing placed: still publish an empty, well-formed sink
         if (hqtick_sink_bytes(W, 0) > e.sink_bytes) return fail(HQTICK_E_CAPACITY, "record sink too small for this tick");

@@ -3,7 +3,7 @@
 // pinned record buffer — and what it takes to launch the last selection once more:
 //   launch_sweep_early()  K5a right behind plan_keys, on the key tables alone, while the host plans redirects, prefills and outputs
 //   check_capacity()      the two limits of the kernels' LDS staging, directly behind plan_outputs
-//   phase_c()             pack, K4 (dense: select_scatter; view: order_select), K5a unless it went out early, K5b, the host part of the result while they run, the wait
+//   phase_c()             pack, K4 (dense: select_scatter; view: order_select), K5a unless it went out early, K5b, the host part of the result and the caller's own work while they run, the wait
 //   export_result()       the pointers of hqtick_result
 //   replay_selection()    the last selection again: writing tombstones (hqtick_ready_consume_last), giving back what a failed HQTICK_FLAG_CONSUME_IN_TICK tick took,
 //                         or as it was launched (hqtick_time_kernel)
@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <string>
 
 #include "../../include/hqtick.h"
@@ -48,6 +49,9 @@ struct PhaseC {
     bool ledger_pfq_rq;     // pfq_rq rides behind the plan: the ledger's staging names the request of a PREFILL record
     uint32_t *saved_rq;     // where the request-id column is copied before K4 tombstones it (null: not needed)
     hqk::Stage stage;       // K5b's staging of the placement (task == nullptr: none)
+    // (may be null) host work that needs nothing of phase C's output, run once behind assemble_host_part, before the wait — as hqscan::Scanner::scan's.  Not run
+    // when phase_c returns an error before it gets there.
+    const std::function<void()> *while_gpu_runs;
 };
 struct Timings { double select_us = -1, sweep_us = -1, other_us = -1; };  // of the last phase_c(); < 0: not measured
 enum Replay { REPLAY_TOMBSTONE, REPLAY_RESTORE, REPLAY_TIMED };
@@ -64,6 +68,8 @@ class Mapper {
     int phase_c(const Env &e, const PhaseC &pc);
     void export_result(const Env &e, const hqhost::Counts &cnt, hqtick_result *out);
     const Timings &timings() const { return t_; }
+    // The tick discards the phase C it has just waited for (a deferred row check that failed): nothing of its launches is replayed or timed again.
+    void forget_selection() { sweep_launched = false; last_ordered = false; last_os = hqk::OrderSelect{}; last_geom = hqk::WaveGeom{}; last_L = last_Q = last_G = 0; last_tb = last_plan_bytes = 0; t_ = Timings{}; }
     // The last selection (ready.selection_valid()) once more, on the tables its tick left.  REPLAY_RESTORE waits and returns 0 only if the request ids are back
     // (scratch: 64 pinned bytes for the kernel's count); REPLAY_TIMED is the dense K4 as the tick launched it, plan copy included.
     int replay_selection(hipStream_t st, Replay mode, const hqready::Cols &cols, const hqscan::Scanner &scan, uint32_t n_sel, hqbuf::PinBuf *scratch = nullptr);

@@ -1549,18 +1549,56 @@ bool block_runs_on() {
 // exactly what HiGHS accepts there.
 const double ROW_TOL = 1e-6;
 
+// The point against EVERY row and bound of the model, in the model's own units (milp.h).
+bool check_point(const Model &mdl_in, const std::vector<double> &x, double cost_scale, double bound, double rel_gap, double *objective) {
+    const int n = mdl_in.ncols(), m = mdl_in.nrows();
+    if ((int)x.size() != n) return false;
+    bool ok = true;
+    for (int j = 0; j < n && ok; j++) { const double v = x[(size_t)j]; if (v < -1e-9 || std::fabs(v - std::floor(v + 0.5)) > 1e-9 || (mdl_in.kind[j] == COL_BOOL && v > 1.0 + 1e-9)) ok = false; }
+    std::vector<double> lhs_act; std::vector<uint8_t> lhs_seen;   // the activity of a shared list of leading terms: once per list
+    for (int i = 0; i < m && ok; i++) {
+        double a = 0.0;
+        int k0 = mdl_in.roff[i];
+        const int L = mdl_in.row_lhs[i];
+        if (L >= 0) {
+            if ((size_t)L >= lhs_seen.size()) { lhs_seen.resize((size_t)L + 1, 0); lhs_act.resize((size_t)L + 1, 0.0); }
+            if (!lhs_seen[(size_t)L]) { double s = 0.0; for (int k = mdl_in.list_off[L]; k < mdl_in.list_off[L + 1]; k++) s += x[(size_t)mdl_in.list_col[k]]; lhs_act[(size_t)L] = s; lhs_seen[(size_t)L] = 1; }
+            a = lhs_act[(size_t)L];   // (the list's terms: coefficient 1 each, not among the row's stored terms)
+        }
+        for (int k = k0; k < mdl_in.roff[i + 1]; k++) a += mdl_in.rcoef[k] * x[(size_t)mdl_in.rcol[k]];
+        const double tol = std::max(ROW_TOL, 1e-9 * std::max(1.0, std::fabs(mdl_in.rhs[i])));   // (HiGHS's own mip_feasibility_tolerance, see ROW_TOL above)
+        if (mdl_in.rtype[i] != ROW_MIN && a > mdl_in.rhs[i] + tol) ok = false;
+        if (mdl_in.rtype[i] != ROW_MAX && a < mdl_in.rhs[i] - tol) ok = false;
+    }
+    if (!ok) return false;
+    // the certificate once more, on the objective of the ROUNDED point in the model's own costs — not on the value the sweeps reported
+    double z_pt = 0.0;
+    for (int j = 0; j < n; j++) z_pt += mdl_in.obj[j] * std::floor(x[(size_t)j] + 0.5);
+    const double zs = cost_scale > 0.0 ? z_pt / cost_scale : z_pt;
+    if (!(bound * (1.0 + 1e-9) + 1e-12 <= zs + rel_gap * std::fabs(zs))) return false;
+    *objective = z_pt;
+    return true;
+}
+
+thread_local CheckHook *g_check_hook = nullptr;
+bool run_row_check(const Model &m, RowCheck &rc) {
+    rc.pending = false;
+    if (g_check_hook && g_check_hook->fail_next > 0) { g_check_hook->fail_next--; return false; }   // (tests: the fallback of the tick)
+    return check_point(m, rc.x, rc.cost_scale, rc.bound, rc.rel_gap, &rc.objective);
+}
+
 namespace {
 // true: `res` is the model's certified answer
-bool solve_fast(const Model &mdl_in, double time_limit_s, double rel_gap, hqprice::Sweeper *sweeper, const double ts0, Result &res_out) {
+bool solve_fast(const Model &mdl_in, double time_limit_s, double rel_gap, hqprice::Sweeper *sweeper, const double ts0, const SolveOpts *opts, Result &res_out) {
     static const bool tracing_solve = getenv("HQMILP_TRACE") != nullptr;
     auto tmark = [&](const char *what) { if (tracing_solve && mdl_in.ncols() > 1000) fprintf(stderr, "[milp] solve(): %s at %.3f ms\n", what, (wall() - ts0) * 1e3); };
     // ---- the coupled tick's fast path: a large model whose builder said how it is made — one block of columns per worker (col_group), rows that share their leading
     // terms (row_lhs) — goes to the price sweeps AS IT IS (hqprice::solve_model): no snapped copy, no integer-hull pass, no components, no scaled row copy, no
     // column-wise copy for the greedy raise; the sweeps' own exact block solves need none of them.  What comes back certified is checked against every row of the model
-    // right here and returned; anything else (a shape the flattening refuses, no certificate) takes the classic path below from the start, as if this had not run.
+    // (check_point) right here and returned — or, with SolveOpts::defer_row_check, returned with that check pending for the caller to run; anything else (a shape the flattening refuses, no certificate) takes the classic path below from the start, as if this had not run.
     // (c3p at BASELINE size: 1.7 ms of presolve + components + row copy and 1.0 ms of flattening on the build container -> 0.5 ms.)
     static const bool fast_env = !(getenv("HQMILP_FAST") && atoi(getenv("HQMILP_FAST")) == 0);  // (A/B switch)
-    const bool fast_on = g_fast_path < 0 ? fast_env : g_fast_path != 0;                          // (... and the tests' own: tests/test_price.py compares the two paths)
+    const bool fast_on = !(opts && opts->no_fast_path) && (g_fast_path < 0 ? fast_env : g_fast_path != 0);   // (... the call's own, and the tests': tests/test_price.py compares the two paths)
     const int FAST_MIN_COLS = 2048;   // (= LAZY_GREEDY_COLS below: the models that go to the sweeps without an incumbent of the host's)
     const bool hints_there = (int)mdl_in.col_group.size() == mdl_in.ncols() && (int)mdl_in.row_lhs.size() == mdl_in.nrows() && (int)mdl_in.row_lhs_len.size() == mdl_in.nrows();
     const bool takes_it = fast_on && sweeper && rel_gap > 0.0 && mdl_in.ncols() >= FAST_MIN_COLS && mdl_in.ncols() >= (int)sweeper->min_cols && hints_there && (int)mdl_in.start.size() != mdl_in.ncols();
@@ -1581,30 +1619,20 @@ bool solve_fast(const Model &mdl_in, double time_limit_s, double rel_gap, hqpric
         hqprice::Answer pa = hqprice::solve_model(mv, rel_gap, time_limit_s, ts0 + (time_limit_s > 0 ? time_limit_s : 1e18), tracing_solve, *sweeper, &cost_scale);
         if (tracing_solve) fprintf(stderr, "[milp] fast path: ran %d (%s) sweeps %u rounds %u bound %.9f point %.9f, %.3f ms of which %.3f ms inside the sweeps\n", (int)pa.ran, pa.why, pa.sweeps, pa.rounds, pa.ran ? pa.bound : -1.0, pa.x.empty() ? -1.0 : pa.x_value, (wall() - tf0) * 1e3, sweeper->stat_sweep_us / 1e3);
         if (pa.ran && (int)pa.x.size() == n && pa.bound * (1.0 + 1e-9) + 1e-12 <= pa.x_value + rel_gap * std::fabs(pa.x_value)) {
-            // the point against EVERY row and bound of the model, in the model's own units
-            bool ok = true;
-            for (int j = 0; j < n && ok; j++) { const double v = pa.x[(size_t)j]; if (v < -1e-9 || std::fabs(v - std::floor(v + 0.5)) > 1e-9 || (mdl_in.kind[j] == COL_BOOL && v > 1.0 + 1e-9)) ok = false; }
-            std::vector<double> lhs_act; std::vector<uint8_t> lhs_seen;   // the activity of a shared list of leading terms: once per list
-            for (int i = 0; i < m && ok; i++) {
-                double a = 0.0;
-                int k0 = mdl_in.roff[i];
-                const int L = mdl_in.row_lhs[i];
-                if (L >= 0) {
-                    if ((size_t)L >= lhs_seen.size()) { lhs_seen.resize((size_t)L + 1, 0); lhs_act.resize((size_t)L + 1, 0.0); }
-                    if (!lhs_seen[(size_t)L]) { double s = 0.0; for (int k = mdl_in.list_off[L]; k < mdl_in.list_off[L + 1]; k++) s += pa.x[(size_t)mdl_in.list_col[k]]; lhs_act[(size_t)L] = s; lhs_seen[(size_t)L] = 1; }
-                    a = lhs_act[(size_t)L];   // (the list's terms: coefficient 1 each, not among the row's stored terms)
-                }
-                for (int k = k0; k < mdl_in.roff[i + 1]; k++) a += mdl_in.rcoef[k] * pa.x[(size_t)mdl_in.rcol[k]];
-                const double tol = std::max(ROW_TOL, 1e-9 * std::max(1.0, std::fabs(mdl_in.rhs[i])));   // (HiGHS's own mip_feasibility_tolerance, see ROW_TOL below)
-                if (mdl_in.rtype[i] != ROW_MIN && a > mdl_in.rhs[i] + tol) ok = false;
-                if (mdl_in.rtype[i] != ROW_MAX && a < mdl_in.rhs[i] - tol) ok = false;
+            if (opts && opts->defer_row_check) {   // the check is the caller's: the rounded point leaves at once (decode, plan and phase C read nothing else)
+                Result res;
+                res.x.resize((size_t)n);
+                for (int j = 0; j < n; j++) res.x[(size_t)j] = std::floor(pa.x[(size_t)j] + 0.5);
+                res.feasible = true; res.optimal = true; res.canonical = false;
+                res.n_components = 1; res.nodes = pa.sweeps; res.price_sweeps = (int)pa.sweeps; res.price_rounds = (int)pa.rounds; res.price_total_us = (wall() - tf0) * 1e6;
+                res.row_check.pending = true; res.row_check.x = std::move(pa.x); res.row_check.cost_scale = cost_scale; res.row_check.bound = pa.bound; res.row_check.rel_gap = rel_gap;
+                if (g_check_hook) g_check_hook->deferred++;
+                tmark("fast path certified by the sweeps, row check pending");
+                res_out = std::move(res);
+                return true;
             }
             double z_pt = 0.0;
-            if (ok) {   // the certificate once more, on the objective of the ROUNDED point in the model's own costs — not on the value the sweeps reported
-                for (int j = 0; j < n; j++) z_pt += mdl_in.obj[j] * std::floor(pa.x[(size_t)j] + 0.5);
-                const double zs = cost_scale > 0.0 ? z_pt / cost_scale : z_pt;
-                if (!(pa.bound * (1.0 + 1e-9) + 1e-12 <= zs + rel_gap * std::fabs(zs))) ok = false;
-            }
+            const bool ok = check_point(mdl_in, pa.x, cost_scale, pa.bound, rel_gap, &z_pt);
             if (ok) {
                 Result res;
                 res.x = std::move(pa.x);
@@ -1625,9 +1653,9 @@ bool solve_fast(const Model &mdl_in, double time_limit_s, double rel_gap, hqpric
 
 static Result solve_classic(const Model &mdl_in, double time_limit_s, bool canonical, double rel_gap, hqprice::Sweeper *sweeper, const double ts0);
 
-Result solve(const Model &mdl_arg, double time_limit_s, bool canonical, double rel_gap, hqprice::Sweeper *sweeper) {
+Result solve(const Model &mdl_arg, double time_limit_s, bool canonical, double rel_gap, hqprice::Sweeper *sweeper, const SolveOpts *opts) {
     const double ts_entry = wall();
-    { Result r; if (solve_fast(mdl_arg, time_limit_s, rel_gap, sweeper, ts_entry, r)) return r; }
+    { Result r; if (solve_fast(mdl_arg, time_limit_s, rel_gap, sweeper, ts_entry, opts, r)) return r; }
     if (mdl_arg.has_lists()) {   // every other consumer works on the plain form
         Model plain = mdl_arg;
         plain.expand_lists();

@@ -102,9 +102,17 @@ struct Model {
     void end_row() { roff.push_back((int)rcol.size()); }
 };
 
+// The fast path's last step as a value: the point the sweeps returned (NOT rounded), and what the certificate is tested against.
+struct RowCheck {
+    bool pending = false;
+    std::vector<double> x;
+    double cost_scale = 1.0, bound = 0.0, rel_gap = 0.0;
+    double objective = 0.0;   // c.x of the rounded point: written by the check
+};
+
 struct Result {
     std::vector<double> x;   // integral values
-    double objective = 0.0;  // c.x in the model's own (unscaled) coefficients
+    double objective = 0.0;  // c.x in the model's own (unscaled) coefficients (row check pending: 0, the check writes RowCheck::objective)
     bool feasible = false;   // false => the reference's `None` (infeasible / unbounded)   highs.rs:82
     bool optimal = false;    // false with feasible => time limit hit, incumbent returned   highs.rs:73-80; true = certified within rel_gap (below)
     bool canonical = true;   // false: some component's tie-break phase was skipped / cut short (or not requested): x is an optimum, not THE canonical one
@@ -113,6 +121,15 @@ struct Result {
     int price_sweeps = 0, price_rounds = 0;      // block sweeps of the coupled solve / flag configurations tried (0: the host-only search ran)
     double price_bound_us = 0, price_total_us = 0;
     long hull_solves = 0, hull_solves_nonpacking = 0;  // block solves of the root's block-hull rounds, and those of them on blocks that are not packings
+    // "certified by the sweeps, row check pending" (SolveOpts::defer_row_check): x is the rounded point already; whoever holds the model runs run_row_check on
+    // row_check while something else is worth waiting for, and treats false as "this answer never existed" (solve again with SolveOpts::no_fast_path)
+    RowCheck row_check;
+};
+
+// What solve() is told beyond the model, per call.
+struct SolveOpts {
+    bool no_fast_path = false;     // this call takes the classic path whatever the model's size (what set_fast_path(0) does for a thread)
+    bool defer_row_check = false;  // a point the sweeps certified comes back with Result::row_check pending instead of being checked inside solve()
 };
 
 // What the reference calls optimal: solve_bounded sets `time_limit` and nothing else (solver/highs.rs:65-68), so HiGHS runs with its default
@@ -124,7 +141,13 @@ const double REFERENCE_MIP_REL_GAP = 1e-4;
 // more, work-budgeted search with the exact rule; only where that finishes does the tie-break run, otherwise `canonical` comes back false.
 // sweeper (optional): the block sweeps of the coupled solve (csrc/price.h) — on the MI355X in the tick (k_price_sweep), the emulated wavefront in the CPU
 // tests; nullptr: the host-only search.  Used for large components whose columns carry `col_group`.
-Result solve(const Model &m, double time_limit_s, bool canonical = true, double rel_gap = REFERENCE_MIP_REL_GAP, hqprice::Sweeper *sweeper = nullptr);
+Result solve(const Model &m, double time_limit_s, bool canonical = true, double rel_gap = REFERENCE_MIP_REL_GAP, hqprice::Sweeper *sweeper = nullptr, const SolveOpts *opts = nullptr);
+
+// The fast path's check of a certified point: integrality and bounds of every column, EVERY row of the model in the model's own units (a shared list's activity once
+// per list), then the certificate once more on the objective of the rounded point (*objective; written only when the rows hold).  Reads, never writes, the point.
+bool check_point(const Model &m, const std::vector<double> &x, double cost_scale, double bound, double rel_gap, double *objective);
+// A pending check, run by whoever was handed it: check_point on rc.x, rc.pending cleared.  `m` is the model solve() was given.
+bool run_row_check(const Model &m, RowCheck &rc);
 
 // columns by descending cost, ties by ascending index (a stable order of the indices): the order the solver's greedy raises go through the columns in
 void columns_by_cost_desc(const double *c, int n, std::vector<int> &out);
@@ -137,6 +160,10 @@ bool block_runs_on();
 // Test probe (libhqtick_test.so sets one; nullptr in the product): FNV-1a digests of the last coupled model and of what the flattener made of it, and what became of the runs.
 struct Probe { uint64_t model = 0, tables = 0, runs = 0, covered = 0; bool corrupt_runs = false; };
 extern thread_local Probe *g_probe;
+// Test hook of the deferred row check (libhqtick_test.so sets one; nullptr in the product): allow = the A/B switch for this thread (1 on, 0 off, -1 the context's own),
+// deferred = results that left solve() with their check pending, fail_next = that many run_row_check calls return false without looking at the point.
+struct CheckHook { int allow = -1; uint32_t deferred = 0, fail_next = 0; };
+extern thread_local CheckHook *g_check_hook;
 inline uint64_t fnv1a(uint64_t h, const void *p, size_t bytes) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < bytes; i++) h = (h ^ b[i]) * 1099511628211ull; return h; }
 template <class T> inline uint64_t fnv1a_vec(uint64_t h, const std::vector<T> &v) { const uint64_t n = v.size(); h = fnv1a(h, &n, 8); return v.empty() ? h : fnv1a(h, v.data(), v.size() * sizeof(T)); }
 const uint64_t FNV_BASIS = 1469598103934665603ull;

@@ -154,6 +154,16 @@ void hqtick_debug_last_coupled_digest(uint64_t out[4]);
  * give the same tables, cuts and answers in every byte. */
 void hqtick_debug_set_early_sweep(int on);
 uint32_t hqtick_debug_early_sweeps(void);   /* sweeps launched that way on this thread since the last hqtick_debug_set_early_sweep */
+/* The fast path's last step — the certified point against every row and bound of the model — run by the tick while phase C's kernels do, for this
+ * thread: 1 on, 0 off (inside the solve, before the decode), -1 the default (the context's own: on unless HQTICK_DEFER_ROW_CHECK=0 at hqtick_create).  Where a discarded
+ * phase C would leave a trace (HQTICK_FLAG_CONSUME_IN_TICK, the assignment ledger, a record sink, a shard or exchange, Retracting tasks) a tick never defers.
+ * hqtick_debug_host_stages / _host_plan defer only while this is 1, and then run the check right behind the solver.
+ * _deferred_row_checks: placements that left the solver with their check pending on this thread since the count was last cleared (clear != 0 clears it).
+ * _fail_row_checks(n): the next n deferred checks on this thread return false without looking at the point — the caller must come back with what the same call gives
+ * with the fast path off.  Returns how many of the failures armed before were still unused. */
+void hqtick_debug_set_defer_row_check(int on);
+uint32_t hqtick_debug_deferred_row_checks(int clear);
+uint32_t hqtick_debug_fail_row_checks(uint32_t n);
 /* on != 0: this thread's fast-path solves keep their first cut; hqtick_debug_first_cut copies up to cap bytes of the last one to out and returns its size —
  * act [K] and part_act [16 * K] as int64, then c.x, the bound and part_cx [16] as f64 (0: no solve got to its first cut). */
 void hqtick_debug_capture_first_cut(int on);
