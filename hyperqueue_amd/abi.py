@@ -100,6 +100,9 @@ class GraphStatsC(C.Structure):
                 ("hash_capacity", C.c_uint64), ("hash_tombstones", C.c_uint64), ("bytes_hbm", C.c_uint64), ("last_kernel_us", C.c_double)]
 
 
+# hqtick_cancel_last_routes (include/hqtick.h): what a batch position of hqtick_cancel_tasks was
+HQ_CANCEL_NONE, HQ_CANCEL_ASSIGNED, HQ_CANCEL_PREFILLED, HQ_CANCEL_MN, HQ_CANCEL_RETRACTING, HQ_CANCEL_REPEAT = 0, 1, 2, 3, 4, 5
+
 # hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
 HQ_CHECK_READY, HQ_CHECK_LEDGER, HQ_CHECK_GRAPH, HQ_CHECK_CROSS, HQ_CHECK_STRICT, HQ_CHECK_ALL = 1, 2, 4, 8, 16, 15
 HQ_INV_NAMES = ("HQ_INV_READY_ORDER", "HQ_INV_READY_COUNT", "HQ_INV_LEDGER_HASH", "HQ_INV_LEDGER_ENTRY", "HQ_INV_LEDGER_TOTALS", "HQ_INV_LEDGER_COUNTS",

@@ -713,6 +713,72 @@ class SchedEnv:
         self.ready[t.rq].discard(tid)
         t.state = FINISHED
 
+    def cancel_tasks(self, ids) -> Dict[int, List[int]]:
+        """on_cancel_tasks (server/reactor.rs:706-780) for the listed ids, in this order.  Every listed task that is still here takes its transitive consumers with
+        it (collect_recursive_consumers, task.rs:235-250); the `match task.state` runs for the LISTED ids only:
+          Waiting            nothing but leaving its queue with the closure
+          Assigned/Running   remove_sn_task on its worker; the worker is told
+          RunningMultiNode   reset_mn_task on every worker of the task; the ROOT is told
+          Retracting         try_remove_redirection (reactor.rs:592-604: remove_sn_task on the redirect target, if there is a redirect); the worker it is
+                             retracting FROM is told
+          Prefilled          remove_prefilled + remove_prefill_task; its worker is told
+        Then the closure leaves the task map and the queues (remove_tasks_batched).  A listed id that is not here, or that was listed before, changes nothing.
+        Returns running_ids: {worker id: [task ids in the order they were pushed]}.  last_cancel_routes: per listed position (worker id or None, abi.HQ_CANCEL_*)."""
+        messages: Dict[int, List[int]] = {}
+        closure: List[int] = []
+        in_closure: set = set()
+        listed: set = set()
+        self.last_cancel_routes: List[Tuple[Optional[int], int]] = []
+
+        def tell(wid: int, tid: int, kind: int):
+            messages.setdefault(wid, []).append(tid)
+            self.last_cancel_routes.append((wid, kind))
+
+        for tid in ids:
+            t = self.tasks.get(tid)
+            if t is None or t.state == FINISHED:
+                self.last_cancel_routes.append((None, abi.HQ_CANCEL_NONE))
+                continue
+            if tid in listed:
+                self.last_cancel_routes.append((None, abi.HQ_CANCEL_NONE if t.state == WAITING else abi.HQ_CANCEL_REPEAT))
+                continue
+            listed.add(tid)
+            stack = [tid]
+            while stack:
+                x = stack.pop()
+                if x in in_closure or self.tasks[x].state == FINISHED:
+                    continue
+                in_closure.add(x); closure.append(x)
+                stack.extend(self.tasks[x].consumers)
+            if t.state == WAITING:
+                self.last_cancel_routes.append((None, abi.HQ_CANCEL_NONE))
+            elif t.state in (ASSIGNED, RUNNING):
+                w = self.workers[t.worker]
+                w.assigned_tasks.discard(tid)
+                self._add(w, t.rq, t.rv)  # remove_sn_task  server/worker.rs:223-234
+                tell(t.worker, tid, abi.HQ_CANCEL_ASSIGNED)
+            elif t.state == RUNNING_MN:
+                for w_id in t.mn_workers:
+                    self.workers[w_id].mn_task = None  # reset_mn_task  server/worker.rs:168-171
+                tell(t.mn_workers[0], tid, abi.HQ_CANCEL_MN)
+            elif t.state == RETRACTING:
+                if tid in self.redirects:
+                    target, v = self.redirects.pop(tid)
+                    self.workers[target].assigned_tasks.discard(tid)
+                    self._add(self.workers[target], t.rq, v)
+                tell(t.worker, tid, abi.HQ_CANCEL_RETRACTING)
+            elif t.state == PREFILLED:
+                self.workers[t.worker].prefilled_tasks.discard(tid)
+                self.prefill[t.rq][1].remove(tid)
+                tell(t.worker, tid, abi.HQ_CANCEL_PREFILLED)
+            else:
+                raise AssertionError("unreachable in the reference (reactor.rs:768)")
+        for x in closure:
+            t = self.tasks[x]
+            self.ready[t.rq].discard(x)
+            t.state, t.worker = FINISHED, None
+        return messages
+
     # -- bookkeeping used by tests ----------------------------------------------------------------------
     def assigned_counts(self) -> List[int]:
         counts = [0] * len(self.requests)

@@ -94,6 +94,13 @@ hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipSt
 // A multi-node id of the batch leaves the table like the others (counted in C_DONE and C_MN); with m.live != 0 the W x R row pass resets its rows.
 // A prefilled id is not the release's: it is counted as unknown and stays.
 hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s);
+// hqtick_cancel_tasks: the release's four passes in their cancel mode.  A prefilled id of the batch leaves too, as pf_remove takes it (prefilled count
+// down, no free row; counted in C_DONE and C_PF), so the tables end as after release(ids) + pf_remove(ids).  Per batch position the passes write the worker ROW the
+// CancelTasks message goes to (NONE: none) and an HQ_CANCEL_* kind: the entry's worker, the root of a multi-node task; REPEAT for a later position of an id that
+// has an entry.  The Retracting overrides (ids ascending, the worker id each task is retracting FROM; retr_hit [n_retr] NONE on entry) are matched on the device:
+// the first position of such an id is routed to that worker whatever the ledger names, and retr_hit[k] is that position (NONE: the id is not in the batch).
+struct CancelCols { uint32_t *route; uint8_t *kind; const uint64_t *retr_id; const uint32_t *retr_wid; uint32_t *retr_hit; uint32_t n_retr; };
+hipError_t cancel(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
 // A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
 // out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF)

@@ -163,27 +163,43 @@ __global__ void k_insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr
     count_status(ctr, status);
 }
 
+// index of `id` in the ascending ids of the Retracting overrides, NONE if absent
+__device__ __forceinline__ uint32_t retr_find(const CancelCols &cc, uint64_t id) {
+    uint32_t lo = 0, hi = cc.n_retr;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (cc.retr_id[mid] < id) lo = mid + 1; else hi = mid; }
+    return (lo < cc.n_retr && cc.retr_id[lo] == id) ? lo : NONE;
+}
 // release, pass 1: the bucket of every id; the first position of an id in the batch claims it (later ones are duplicates)
-__global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *ctr) {
+// CANCEL (hqtick_cancel_tasks, the same four passes): a prefilled entry is claimed like the others, every position starts with no route, and the first position
+// of an id of the Retracting overrides claims its override the same way
+template <bool CANCEL>
+__global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, CancelCols cc, uint32_t *ctr) {
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     uint32_t b = NONE;
     if (i < n) {
         b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
-        if (b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled task is not running: unknown to a release
+        if (!CANCEL && b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled task is not running: unknown to a release
         pos[i] = b;
         if (b != NONE) atomicMin(&t.claim[b], i);
+        if (CANCEL) {
+            cc.route[i] = NONE; cc.kind[i] = HQ_CANCEL_NONE;
+            const uint32_t k = retr_find(cc, id[i]);
+            if (k != NONE) atomicMin(&cc.retr_hit[k], i);
+        }
     }
     wave_add(&ctr[C_UNKNOWN], i < n && b == NONE);
 }
 // pass 2: per (worker row, resource) the position + 1 of the batch's last ALL entry
-__global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos, uint32_t *last_all, uint32_t *ctr) {
+template <bool CANCEL>
+__global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos, uint32_t *last_all, CancelCols cc, uint32_t *ctr) {
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool dup = false, bad = false;
     if (b != NONE) {
         const uint32_t row = row_of(r, t.worker[b]);
-        if (t.claim[b] != i) { pos[i] = NONE; dup = true; }
+        if (t.claim[b] != i) { pos[i] = NONE; dup = true; if (CANCEL) cc.kind[i] = HQ_CANCEL_REPEAT; }
         else if (t.variant[b] == MN_VARIANT) {}  // a multi-node task: no count, no entry of any resource (its rows are reset by pass 4)
+        else if (CANCEL && t.variant[b] == PF_VARIANT) {}  // a prefilled task: no count in a slot, no free row (pass 3 lowers its prefilled count)
         else if (row == NONE) { pos[i] = NONE; bad = true; t.claim[b] = NONE; }  // (left in the table, unclaimed: a later batch finds it as before)
         else {
             const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
@@ -194,13 +210,20 @@ __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos
     wave_add(&ctr[C_DUP], dup); wave_add(&ctr[C_BAD], bad);
 }
 // pass 3: the AMOUNT entries behind the last ALL of their (row, resource) are summed; the entry leaves the table
-__global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, uint32_t *ctr) {
+// CANCEL: a prefilled entry lowers its prefilled count instead (k_pf_remove's step); before the entry leaves, its position's route (the row of the entry's
+// worker: the root of a multi-node task) and kind are written.  Then the Retracting overrides: the claiming position is routed to the worker the task is
+// retracting from, whatever the ledger said, and any other position of that id is a repeat.
+template <bool CANCEL>
+__global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr) {
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
-    bool mn = false;
+    bool mn = false, pf = false;
     if (b != NONE) {
-        mn = t.variant[b] == MN_VARIANT;
-        if (!mn) {
+        mn = t.variant[b] == MN_VARIANT; pf = CANCEL && t.variant[b] == PF_VARIANT;
+        if (pf) {
+            const uint32_t row = row_of(r, t.worker[b]), rq = t.rq[b];
+            if (row != NONE && r.pf && rq < r.pf_stride) atomicSub(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
+        } else if (!mn) {
             const uint32_t row = row_of(r, t.worker[b]);
             const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
             for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) {
@@ -209,9 +232,18 @@ __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint32_t *
             }
             atomicSub(&r.counts[(size_t)row * r.stride + slot], 1u);
         }
+        if (CANCEL) { cc.route[i] = row_of(r, t.worker[b]); cc.kind[i] = pf ? HQ_CANCEL_PREFILLED : mn ? HQ_CANCEL_MN : HQ_CANCEL_ASSIGNED; }
         t.key[b] = HT_TOMB; t.claim[b] = NONE;
     }
+    if (CANCEL && i < n) {
+        const uint32_t k = retr_find(cc, id[i]);
+        if (k != NONE) {
+            const bool first = cc.retr_hit[k] == i;
+            cc.route[i] = first ? row_of(r, cc.retr_wid[k]) : NONE; cc.kind[i] = first ? HQ_CANCEL_RETRACTING : HQ_CANCEL_REPEAT;
+        }
+    }
     wave_add(&ctr[C_DONE], b != NONE); wave_add(&ctr[C_MN], mn);
+    if (CANCEL) wave_add(&ctr[C_PF], pf);
 }
 // reset_mn_task (worker.rs:172-175) of a row whose multi-node task has left the table: SN bit set, free row = total row, columns cleared
 __device__ __forceinline__ void mn_reset_row(const Table &t, const Rows &r, const MnRows &m, uint32_t row) {
@@ -423,9 +455,17 @@ hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipSt
 }
 hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, ctr);
-    hipLaunchKernelGGL(k_rel_last_all, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, ctr);
-    hipLaunchKernelGGL(k_rel_apply, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, delta, ctr);
+    hipLaunchKernelGGL(k_rel_claim<false>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_last_all<false>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_apply<false>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, CancelCols{}, ctr);
+    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
+    return hipGetLastError();
+}
+hipError_t cancel(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_rel_claim<true>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_last_all<true>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<true>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }

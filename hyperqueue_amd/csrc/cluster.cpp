@@ -334,6 +334,11 @@ int Retracting::response(uint32_t worker_id, uint32_t n, const uint64_t *task_id
     return left;
 }
 
+void Retracting::sources(std::vector<uint64_t> *task_id, std::vector<uint32_t> *worker_id) const {
+    task_id->clear(); worker_id->clear();
+    for (const auto &kv : tab) { task_id->push_back(kv.first); worker_id->push_back(kv.second.old_id); }  // (std::map: ascending task id)
+}
+
 // on_remove_worker's two passes over the Retracting tasks (server/reactor.rs:86-147), one pass over the table however many workers are lost
 void Retracting::workers_removed(uint32_t n, const uint32_t *worker_id) {
     last.clear();

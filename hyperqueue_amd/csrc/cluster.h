@@ -117,6 +117,10 @@ class Retracting {
     template <class F> void for_each(F &&f) const { for (const auto &kv : tab) f(kv.first, kv.second.in_queue, kv.second.has_redirect, kv.second.target_id, kv.second.variant); }
     void add(uint32_t n, const uint64_t *task_id, const uint32_t *worker_id);  // process_retracted outside a tick: back in their queue
     int response(uint32_t worker_id, uint32_t n, const uint64_t *task_id);     // on_retract_response -> tasks that left the table
+    // on_cancel_tasks (reactor.rs:751-761): sources() lists every entry as (task, worker id it is retracting FROM), ascending task id — what hqtick_cancel_tasks hands
+    // the ledger as route overrides; cancel() erases one listed task's entry, redirect included (the ledger has released the target's entry: try_remove_redirection)
+    void sources(std::vector<uint64_t> *task_id, std::vector<uint32_t> *worker_id) const;
+    bool cancel(uint64_t task_id) { return tab.erase(task_id) != 0; }
     void workers_removed(uint32_t n, const uint32_t *worker_id);               // on_remove_worker (ids in any order: sorted here, and only if the table holds a task)
     // the tasks still in a queue as the retracting arrays of a snapshot whose workers are worker_id[0..W)
     int to_snapshot(const uint32_t *worker_id, uint32_t W, hqtick_snapshot *full);

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "audit_core.h"
+#include "cancel_core.h"
 #include "clock_core.h"
 #include "hb_order.h"
 #include "milp.h"
@@ -144,3 +145,11 @@ extern "C" int hqtick_debug_audit_host(const hqtick_debug_audit_tables *a, uint3
 }
 extern "C" int64_t hqtick_debug_clock_deadline(int64_t now_ns, int64_t remaining_ns) { return hqclock::deadline_of(now_ns, remaining_ns); }
 extern "C" int64_t hqtick_debug_clock_remaining(int64_t deadline_ns, int64_t now_ns) { return hqclock::remaining_of(deadline_ns, now_ns); }
+// the grouping of a cancel batch on host arrays: cancel_core.h's phases in the given thread order
+extern "C" int hqtick_debug_cancel_group(uint32_t n, uint32_t W, const uint32_t *route_row, const uint64_t *task_id, const uint32_t *worker_id, int order, uint32_t *n_workers,
+                                         uint32_t *out_worker, uint32_t *out_off, uint64_t *out_task) {
+    if (!n_workers || !out_off || (n && (!route_row || !task_id || !out_task)) || (W && (!worker_id || !out_worker)) || order < 0 || order > 2 || n > 0x7FFFFFFFu) return HQTICK_E_INVALID;
+    uint32_t n_ids = 0;
+    if (!hqcancel::group_on_host(n, W, route_row, task_id, worker_id, order, n_workers, &n_ids, out_worker, out_off, out_task)) return HQTICK_E_DEVICE;
+    return (int)n_ids;
+}

@@ -75,6 +75,8 @@ class Graph {
     int finish(uint64_t n, const uint64_t *id, hipStream_t s);
     // remove: the tasks (and, if recursive, their transitive consumers) leave the graph; returns how many left (sorted ids in out_id()).
     int remove(uint64_t n, const uint64_t *id, bool recursive, hipStream_t s);
+    // ... the same for ids that are already in device memory (hqtick_cancel_tasks: one staged copy for every step), beside out_id() as ReadySet::remove_device is
+    int remove_device(uint64_t n, const uint64_t *dev_id, bool recursive, hipStream_t s);
     // test accessor: Task::get_unfinished_deps; 0xFFFFFFFF for an id that is not in the graph
     int unfinished(uint64_t n, const uint64_t *id, uint32_t *out, hipStream_t s);
     // EXTENSION (no reference counterpart, parity unpinned): the b-level of every task — longest path to a sink of what is still in the graph — into the low 32

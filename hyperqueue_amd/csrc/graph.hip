@@ -723,10 +723,19 @@ int Graph::remove(uint64_t n, const uint64_t *id, bool recursive, hipStream_t s)
     if (!init(s)) return fail(HQTICK_E_DEVICE, "dependency graph: device setup failed");
     if (n_slots == 0) { n_unknown_ = (uint32_t)n; return 0; }
     if (int rc = stage(n, id, s)) return rc;
+    return remove_device(n, d_stage.as<uint64_t>(), recursive, s);
+}
+
+int Graph::remove_device(uint64_t n, const uint64_t *dev_id, bool recursive, hipStream_t s) {
+    n_out_ = 0; n_unknown_ = 0;
+    if (n == 0) return 0;
+    if (n > 0x7FFFFFFFull) return fail(HQTICK_E_CAPACITY, "more than 2^31 ids in one batch");
+    if (!init(s)) return fail(HQTICK_E_DEVICE, "dependency graph: device setup failed");
+    if (n_slots == 0) { n_unknown_ = (uint32_t)n; return 0; }
     View v = view();
     Ctl *c = d_ctl.as<Ctl>();
     G_HIP(hipMemsetAsync(&c->n_out, 0, 24, s));  // n_out, n_unknown, err, n_big, lev_begin, lev_end
-    hipLaunchKernelGGL(k_g_remove_seed, dim3(nblk(n)), dim3(256), 0, s, v, d_stage.as<uint64_t>(), (uint32_t)n, d_okey.as<uint64_t>(), d_oval.as<uint32_t>());
+    hipLaunchKernelGGL(k_g_remove_seed, dim3(nblk(n)), dim3(256), 0, s, v, dev_id, (uint32_t)n, d_okey.as<uint64_t>(), d_oval.as<uint32_t>());
     G_HIP(hipEventRecord(ev0, s));
     if (recursive) {
         for (;;) {

@@ -108,6 +108,7 @@ struct hqtick_ctx {
     void *sink = nullptr; size_t sink_bytes = 0;      // hqtick_set_record_sink (device memory)
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
     hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
+    PinBuf h_cancel_ids; DevBuf d_cancel_ids; uint64_t cancel_ready_removed = 0;  // hqtick_cancel_tasks: the ids' staging and their one device copy; hqtick_cancel_last_ready_removed
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     ViewHooks *view_hooks = nullptr;  // hqtick_debug_order_view's scanner and scratch (test library only), allocated on first use; nothing of it is touched on a tick's path
     ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
@@ -825,6 +826,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     ctx->asg.release_all();
     ctx->audit.release();
     ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_blk.release(); ctx->h_blkprof.release();
+    ctx->h_cancel_ids.release(); ctx->d_cancel_ids.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1285,6 +1287,70 @@ int hqtick_assigned_unprefill(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_
 }); }
 
 uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx) { return ctx && ctx->asg.on && ctx->asg.tracking() ? ctx->asg.pf_live : 0; }
+
+// ---- on_cancel_tasks in one call: the checks and the order of the steps are here, the steps are the graph's, the ready set's, the ledger's and the
+// Retracting table's.  The ids are staged once in pinned memory and copied to the device once; every step reads that copy.
+// What is left when a later step fails after an earlier one succeeded: the earlier ones stay done, as in hqtick_cluster_remove_workers.  After a failed ready-set
+// step the closure has left the graph (hqtick_graph_last_ids names it) and hqtick_ready_remove of those ids finishes that part; after a failed ledger step the graph
+// and the ready set are done and hqtick_assigned_release + hqtick_assigned_unprefill of the ids finish the ledger's (a failure behind the ledger's kernels has
+// already taken the entries out and switched nothing off); the Retracting table is touched last and only after the ledger succeeded, so it never runs ahead of
+// the ledger.  The lists of hqtick_cancel_last_* are empty after any failure.
+int hqtick_cancel_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id) { return with_audit(ctx, [&]() -> int {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_cancel_tasks", n, task_id)) return rc;  // (the guard comes before any step: a refused call changes nothing)
+    ctx->asg.cancel_out = hqasg::Ledger::CancelOut{}; ctx->cancel_ready_removed = 0;
+    if (n == 0) return 0;
+    if (!ctx->h_cancel_ids.ensure((size_t)n * 8 + 8) || !ctx->d_cancel_ids.ensure((size_t)n * 8 + 8)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc cancel staging");
+    memcpy(ctx->h_cancel_ids.p, task_id, (size_t)n * 8);
+    HQ_HIP(hipMemcpyAsync(ctx->d_cancel_ids.p, ctx->h_cancel_ids.p, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t *d_ids = ctx->d_cancel_ids.as<uint64_t>();
+    // 1 / 2: the graph's closure (remove_tasks_batched) and the ready set
+    if (ctx->graph.resident()) {
+        const int r = ctx->graph.remove_device(n, d_ids, true, ctx->stream);
+        if (r < 0) return graph_fail(ctx, r);
+        if (r > 0 && ctx->ready.cols().n) {
+            const int k = ready_fail(ctx, ctx->ready.remove_device(ready_env(ctx), ctx->graph.out_id(), (uint32_t)r));
+            if (k < 0) return k;
+            ctx->cancel_ready_removed = (uint64_t)k;
+        }
+    } else if (ctx->ready.cols().n) {
+        const int k = ready_fail(ctx, ctx->ready.remove_device(ready_env(ctx), d_ids, n));
+        if (k < 0) return k;
+        ctx->cancel_ready_removed = (uint64_t)k;
+    }
+    // 3: the ledger's entries, the routes and the messages; the Retracting table's (task, worker it is retracting from) pairs ride along as overrides
+    std::vector<uint64_t> retr_id; std::vector<uint32_t> retr_wid;
+    ctx->retr.sources(&retr_id, &retr_wid);
+    const uint32_t *hit = nullptr;
+    const int m = ledger_fail(ctx, ctx->asg.cancel(ledger_env(ctx), n, d_ids, (uint32_t)retr_id.size(), retr_id.data(), retr_wid.data(), &hit));
+    if (m < 0) { ctx->asg.cancel_out = hqasg::Ledger::CancelOut{}; return m; }
+    // 4: try_remove_redirection's other half: the listed tasks leave the Retracting table
+    for (size_t k = 0; hit && k < retr_id.size(); k++) if (hit[k] != hqasg::NONE) ctx->retr.cancel(retr_id[k]);
+    return m;
+}); }
+
+int hqtick_cancel_last_messages(const hqtick_ctx *ctx, uint32_t *n_workers, const uint32_t **worker_id, const uint32_t **task_off, const uint64_t **task_id) {
+    static const uint32_t zero_off[1] = {0};
+    if (!ctx) { if (n_workers) *n_workers = 0; if (worker_id) *worker_id = nullptr; if (task_off) *task_off = nullptr; if (task_id) *task_id = nullptr; return HQTICK_E_INVALID; }
+    const hqasg::Ledger::CancelOut &o = ctx->asg.cancel_out;
+    if (n_workers) *n_workers = o.n_workers;
+    if (worker_id) *worker_id = o.worker_id;
+    if (task_off) *task_off = o.task_off ? o.task_off : zero_off;
+    if (task_id) *task_id = o.task_id;
+    return 0;
+}
+
+int hqtick_cancel_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint32_t **worker_id, const uint8_t **kind) {
+    if (!ctx) { if (n) *n = 0; if (worker_id) *worker_id = nullptr; if (kind) *kind = nullptr; return HQTICK_E_INVALID; }
+    const hqasg::Ledger::CancelOut &o = ctx->asg.cancel_out;
+    if (n) *n = o.n;
+    if (worker_id) *worker_id = o.route_wid;
+    if (kind) *kind = o.route_kind;
+    return 0;
+}
+
+uint64_t hqtick_cancel_last_ready_removed(const hqtick_ctx *ctx) { return ctx ? ctx->cancel_ready_removed : 0; }
 
 // The audit of the resident state (audit.h): the views of what this context holds, read through const accessors, handed to hqaudit::Auditor.  Nothing here changes
 // the context: no selection or placement is abandoned, no mirror is synchronised, ctx->err is written only when the call itself fails.

@@ -8,7 +8,7 @@ namespace hqasg {
 void Ledger::release_all() {
     tab.release(); tab2.release(); for (RowPair *r : {&counts, &mn, &pf}) r->release();
     for (DevBuf &b : buf) b.release();
-    h_ctr.release(); h_in.release();
+    h_ctr.release(); h_in.release(); h_cancel.release();
 }
 void Ledger::take_requests(const hqtick_snapshot *s) {
     const uint32_t Q = s->n_requests;
@@ -332,6 +332,51 @@ int Ledger::release(const Env &e, uint32_t n, const uint64_t *id) {
     n_live -= done - done_mn; mn_live -= std::min<uint64_t>(done_mn, mn_live); n_tomb += done; last_unknown = (uint64_t)c[C_UNKNOWN] + c[C_DUP]; dirty_ = true;  // (the others of the batch are released either way)
     if (c[C_BAD]) return fail(HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
     return (int)done;
+}
+// on_cancel_tasks on the ledger (hqtick_cancel_tasks): the release's four passes in their cancel mode, then the grouping of the routes (cancel.h), all behind one
+// set of counters and ONE synchronisation.  The ids are read where the caller staged them on the device; the lists and routes are written into pinned memory.
+int Ledger::cancel(const Env &e, uint32_t n, const uint64_t *d_id, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit) {
+    last_unknown = 0; cancel_out = CancelOut{}; if (retr_hit) *retr_hit = nullptr;
+    if (!n) return 0;
+    if (int rc = sync_req(e)) return rc;
+    const uint32_t W = e.W; const size_t WR = (size_t)W * e.R, nr = n_retr;
+    const hqcancel::Scratch sc = hqcancel::scratch_of(n, W);
+    if (!buf[B_SCRATCH].ensure((size_t)n * 4 + WR * 12 + 16) || !buf[B_CANCEL].ensure(nr * 16 + sc.total * 4 + (size_t)n * 5 + 64)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    if (!h_cancel.ensure(nr * 16 + (size_t)n * 13 + (size_t)W * 8 + 64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc cancel lists");
+    Pack pk{nullptr, buf[B_SCRATCH].as<unsigned char>()};  // [delta W*R u64][pos n u32][last_all W*R u32]
+    uint64_t *d_delta = pk.put<uint64_t>(nullptr, WR); uint32_t *d_pos = pk.put<uint32_t>(nullptr, n), *d_la = pk.put<uint32_t>(nullptr, WR);
+    Pack dk{nullptr, buf[B_CANCEL].as<unsigned char>()};   // [override ids u64][override workers u32] (one copy) [sort scratch u32][route n u32][hit u32][kind n u8]
+    uint64_t *d_rid = dk.put<uint64_t>(nullptr, nr); uint32_t *d_rwid = dk.put<uint32_t>(nullptr, nr), *d_sort = dk.put<uint32_t>(nullptr, sc.total, 8);
+    uint32_t *d_route = dk.put<uint32_t>(nullptr, n), *d_hit = dk.put<uint32_t>(nullptr, nr); uint8_t *d_kind = dk.put<uint8_t>(nullptr, n);
+    Pack hk{h_cancel.as<unsigned char>(), h_cancel.dev<unsigned char>()};  // in: the overrides; out: [ids n u64][hdr 2][workers W][offsets W + 1][route worker n][hit] u32 [kind n u8]
+    const uint64_t *h_rid = hk.put(retr_id, nr); hk.put(retr_wid, nr);
+    uint64_t *o_id = hk.put<uint64_t>(nullptr, n, 8); uint32_t *o_hdr = hk.put<uint32_t>(nullptr, 2), *o_wid = hk.put<uint32_t>(nullptr, W), *o_off = hk.put<uint32_t>(nullptr, (size_t)W + 1);
+    uint32_t *o_rwid = hk.put<uint32_t>(nullptr, n), *o_hit = hk.put<uint32_t>(nullptr, nr); uint8_t *o_kind = hk.put<uint8_t>(nullptr, n);
+    hk.host(o_hdr)[0] = hk.host(o_hdr)[1] = 0; hk.host(o_off)[0] = 0;
+    HQ_HIP(hipMemsetAsync(d_delta, 0, WR * 8, e.stream));
+    HQ_HIP(hipMemsetAsync(d_la, 0, WR * 4, e.stream));
+    if (W) HQ_HIP(hipMemsetAsync(d_sort + sc.start, 0xFF, (size_t)W * 4, e.stream));
+    if (nr) {
+        HQ_HIP(hipMemsetAsync(d_hit, 0xFF, nr * 4, e.stream));
+        HQ_HIP(hipMemcpyAsync(d_rid, hk.host(h_rid), nr * 12, hipMemcpyHostToDevice, e.stream));
+    }
+    const CancelCols cc{d_route, d_kind, d_rid, d_rwid, d_hit, n_retr};
+    const hqcancel::Group g{n, W, d_route, d_kind, d_id, buf[B_WIDS].as<uint32_t>(), d_sort, o_id, o_wid, o_off, o_hdr, o_rwid, o_kind, HQ_NO_WORKER};
+    if (int rc = counted(e.stream, "hqasg::cancel", [&](uint32_t *ctr) {
+            hipError_t r = hqasg::cancel(table(), req(), rows(e), mn_rows(mn.cur, W, mn_live), n, d_id, d_pos, d_la, d_delta, cc, ctr, e.stream);
+            if (r == hipSuccess) r = hqcancel::group(g, e.stream);
+            if (r == hipSuccess && nr) r = hipMemcpyAsync(hk.host(o_hit), d_hit, nr * 4, hipMemcpyDeviceToHost, e.stream);
+            return r; })) return rc;
+    const uint32_t done = c[C_DONE], done_mn = std::min(c[C_MN], done), done_pf = (uint32_t)std::min<uint64_t>(std::min(c[C_PF], done - done_mn), pf_live);
+    if (done_mn) flags_dirty = true;
+    if (done_pf) { pf_live -= done_pf; pf_dirty = true; }
+    n_live -= done - done_mn - done_pf; mn_live -= std::min<uint64_t>(done_mn, mn_live); n_tomb += done; last_unknown = (uint64_t)c[C_UNKNOWN] + c[C_DUP]; dirty_ = true;
+    if (c[C_BAD]) return fail(HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
+    const uint32_t *hdr = hk.host(o_hdr);
+    if (hdr[0] > W || hdr[1] > n) return fail(HQTICK_E_DEVICE, "assignment ledger: the cancel lists are out of range");
+    cancel_out = CancelOut{n, hdr[0], hdr[1], hk.host(o_wid), hk.host(o_off), hk.host(o_id), hk.host(o_rwid), hk.host(o_kind)};
+    if (retr_hit) *retr_hit = hk.host(o_hit);
+    return (int)hdr[1];
 }
 int Ledger::add_mn(const Env &e, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) {
     last_unknown = 0; if (!n) return 0;

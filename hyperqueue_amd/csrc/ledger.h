@@ -12,6 +12,7 @@
 
 #include "../../include/hqtick.h"
 #include "assigned.h"
+#include "cancel.h"
 #include "devbuf.h"
 
 namespace hqasg {
@@ -39,11 +40,18 @@ class Ledger {
     uint64_t n_live = 0, mn_live = 0, pf_live = 0;  // single-node, multi-node and (with tracking()) prefilled entries of the table
     uint64_t last_unknown = 0, last_host_bytes = 0;
     std::vector<uint64_t> rq_task, rq_prio, rq_pf_task; std::vector<uint32_t> rq_rq;  // hqtick_cluster_last_requeued(_prefilled): what the last evict() took out
+    // hqtick_cancel_last_*: what the last cancel() wrote into pinned memory (n positions; n_workers messages holding n_ids ids)
+    struct CancelOut { uint32_t n = 0, n_workers = 0, n_ids = 0; const uint32_t *worker_id = nullptr, *task_off = nullptr; const uint64_t *task_id = nullptr; const uint32_t *route_wid = nullptr; const uint8_t *route_kind = nullptr; };
+    CancelOut cancel_out;
 
     // ---- the C ABI's operations (arguments validated by the caller)
     int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
     int add(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
     int release(const Env &e, uint32_t n, const uint64_t *id);
+    // hqtick_cancel_tasks' ledger step: d_id [n] is DEVICE memory (the call's one copy of the ids); the Retracting overrides are host arrays, ids
+    // ascending.  The tables end as after release(ids) + unprefill(ids); cancel_out holds the messages and routes; *retr_hit [n_retr] (pinned, valid until the next
+    // cancel): the batch position that claimed override k, NONE if the id is not listed.  Returns the number of ids in the messages.
+    int cancel(const Env &e, uint32_t n, const uint64_t *d_id, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
     int add_mn(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid);
     int mn_workers(const Env &e, uint64_t id, uint32_t *n, const uint32_t **wid);
     int lookup(const Env &e, uint32_t n, const uint64_t *id, uint32_t *wid, uint8_t *var);
@@ -133,9 +141,10 @@ class Ledger {
 
     TableCols tab, tab2;      // the hash table; the target of a rebuild
     RowPair counts, mn, pf;   // counts u32 [W x stride]; [mn task u64 W][mn root u8 W][flags u8 W]; pf u32 [W x pf_stride]
-    // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation
-    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_N }; DevBuf buf[B_N];
-    hqbuf::PinBuf h_ctr, h_in;
+    // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation,
+    // a cancel's routes, overrides and sort scratch
+    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_N }; DevBuf buf[B_N];
+    hqbuf::PinBuf h_ctr, h_in, h_cancel;  // (h_cancel: a cancel's overrides in, its lists and routes out)
     const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
     uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones
     uint32_t stride = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)

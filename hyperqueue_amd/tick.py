@@ -448,6 +448,39 @@ class Tick:
         self._chk(f(self._ctx, C.byref(n), C.byref(pt)))
         return abi._np(pt, n.value, np.uint64).tolist() if n.value else []
 
+    # -- on_cancel_tasks in one call (include/hqtick.h) ------------------------------------------------------
+    def cancel_tasks(self, task_id, as_csr: bool = False) -> dict:
+        """hqtick_cancel_tasks for the ids, in this order -> {"messages": {worker id: [ids]} (the CancelTasks lists, workers ascending, ids in batch order; as_csr: the
+        three arrays (worker ids, offsets, ids) as views of the context's pinned memory, valid until the next call),
+        "n_ids": ids in the messages, "route_worker" / "route_kind": per batch position the worker id (HQ_NO_WORKER: none) and the HQ_CANCEL_* kind,
+        "ready_removed": tasks that left the resident ready set, "closure": hqtick_graph_last_ids (what left the graph), "graph_unknown"}"""
+        t = np.ascontiguousarray(task_id, np.uint64)
+        f = self._lib.hqtick_cancel_tasks
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p]
+        n_ids = self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p)))
+        nw = C.c_uint32(); pw, po, pt = abi.u32p(), abi.u32p(), abi.u64p()
+        g = self._lib.hqtick_cancel_last_messages
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u32p), C.POINTER(abi.u32p), C.POINTER(abi.u64p)]
+        self._chk(g(self._ctx, C.byref(nw), C.byref(pw), C.byref(po), C.byref(pt)))
+        messages = {}
+        if nw.value:
+            wid = abi._np(pw, nw.value, np.uint32); off = abi._np(po, nw.value + 1, np.uint32); ids = abi._np(pt, int(off[nw.value]), np.uint64)
+            messages = (wid, off, ids) if as_csr else {int(wid[k]): ids[off[k]:off[k + 1]].tolist() for k in range(nw.value)}
+        elif as_csr:
+            messages = (np.zeros(0, np.uint32), np.zeros(1, np.uint32), np.zeros(0, np.uint64))
+        nr = C.c_uint32(); rw, rk = abi.u32p(), abi.u8p()
+        h = self._lib.hqtick_cancel_last_routes
+        h.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u32p), C.POINTER(abi.u8p)]
+        self._chk(h(self._ctx, C.byref(nr), C.byref(rw), C.byref(rk)))
+        k = nr.value
+        r = self._lib.hqtick_cancel_last_ready_removed
+        r.argtypes = [C.c_void_p]; r.restype = C.c_uint64
+        self._lib.hqtick_graph_last_unknown.restype = C.c_uint64
+        self._lib.hqtick_graph_last_unknown.argtypes = [C.c_void_p]
+        return {"messages": messages, "n_ids": int(n_ids),
+                "route_worker": abi._np(rw, k, np.uint32).copy() if k else np.zeros(0, np.uint32), "route_kind": abi._np(rk, k, np.uint8).copy() if k else np.zeros(0, np.uint8),
+                "ready_removed": int(r(self._ctx)), "closure": self._graph_last_ids(), "graph_unknown": int(self._lib.hqtick_graph_last_unknown(self._ctx))}
+
     # -- device-resident dependency graph (include/hqtick.h, SURVEY §8 f1) --------------------------------------------------
     def _graph_last_ids(self) -> np.ndarray:
         n = C.c_uint64()

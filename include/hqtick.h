@@ -604,6 +604,42 @@ uint64_t hqtick_assigned_prefilled_count(const hqtick_ctx *ctx);
 int hqtick_cluster_last_requeued_prefilled(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id);
 
 /*
+ * Cancelling tasks on the resident state in one call (functions added under ABI 12): on_cancel_tasks (server/reactor.rs:706-780) for the listed
+ * ids, in the caller's order, on everything the context keeps resident.  The ids are staged once; the graph, the ready set and the ledger read that one copy.
+ *   hqtick_cancel_tasks   needs a resident ready set and an enabled ledger; the graph and the prefilled tracking are optional.  The state afterwards:
+ *       graph       with a graph (one that has held a task): as hqtick_graph_remove(ids, 1) leaves it -- the closure leaves the graph and the ready set, and
+ *                   hqtick_graph_last_ids / _last_unknown answer as after that call.  Without one the listed ids leave the ready set as by hqtick_ready_remove.
+ *       ledger      as hqtick_assigned_release(ids) followed by hqtick_assigned_unprefill(ids) leave it: single-node entries give their resources back in batch
+ *                   order with the last-ALL rule, multi-node entries reset their rows, prefilled entries leave and lower their worker's prefilled count;
+ *                   unknown ids and repeats change nothing.  hqtick_assigned_last_unknown: the positions that found no entry or repeated one.
+ *       Retracting  a listed id leaves the table of hqtick_retracting_* (try_remove_redirection, reactor.rs:751-761: the ledger step has released its redirect
+ *                   target's entry): a later hqtick_retract_response for it reassigns nothing.
+ *     Only the listed ids are routed: a consumer in the closure is Waiting with unfinished dependencies and sits nowhere else.
+ *     Returns the number of ids in the messages below; HQTICK_E_INVALID without a resident ready set, with the ledger off or with a two-call tick's placement
+ *     pending (nothing changes then); HQTICK_E_CAPACITY for n > 2^31 - 1; n = 0 returns 0 and leaves empty lists.
+ *     If a step fails after an earlier one succeeded the earlier ones stay done (graph and ready set first, then the ledger, then the table): the ledger calls
+ *     named above finish the job, the lists below are empty.
+ *   hqtick_cancel_last_messages   the CancelTasks lists (running_ids: Map<WorkerId, Vec<TaskId>>) as a CSR: the workers that get a message in ascending worker
+ *       id, task_off[n_workers + 1], and per worker the ids in ascending batch position (the order the reference's Vec was pushed in).  An assigned, running
+ *       or prefilled task goes to its worker, a multi-node task to its root, a Retracting task to the worker it is retracting FROM.
+ *   hqtick_cancel_last_routes     per batch position the worker id (HQ_NO_WORKER: none) and an HQ_CANCEL_* kind.  HQ_CANCEL_REPEAT marks a later position of an
+ *       id that has a ledger entry or is in the Retracting table (an id that sits in neither is HQ_CANCEL_NONE at every position).  A host needs _PREFILLED to take
+ *       the task out of its queue-side prefill sets and _RETRACTING for its own task states.
+ *   hqtick_cancel_last_ready_removed   tasks that left the resident ready set.
+ * The arrays are pinned memory owned by the context, valid until the next hqtick_cancel_tasks.
+ */
+#define HQ_CANCEL_NONE       0
+#define HQ_CANCEL_ASSIGNED   1
+#define HQ_CANCEL_PREFILLED  2
+#define HQ_CANCEL_MN         3
+#define HQ_CANCEL_RETRACTING 4
+#define HQ_CANCEL_REPEAT     5
+int hqtick_cancel_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id);
+int hqtick_cancel_last_messages(const hqtick_ctx *ctx, uint32_t *n_workers, const uint32_t **worker_id, const uint32_t **task_off, const uint64_t **task_id);
+int hqtick_cancel_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint32_t **worker_id, const uint8_t **kind);
+uint64_t hqtick_cancel_last_ready_removed(const hqtick_ctx *ctx);
+
+/*
  * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
  * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
  * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.

@@ -247,6 +247,14 @@ typedef struct hqtick_debug_audit_tables {
     uint32_t r_n; const uint64_t *r_task; const uint32_t *r_target; const uint8_t *r_variant, *r_flags;
 } hqtick_debug_audit_tables;
 int hqtick_debug_audit_host(const hqtick_debug_audit_tables *tables, uint32_t parts, int order, hqtick_check_report *out);
+
+/* The grouping of a cancel batch (hqtick_cancel_tasks; csrc/cancel_core.h) on HOST arrays: the phase functions of csrc/cancel.hip's kernels, one emulated thread
+ * after the other in the given order (0 ascending, 1 descending with the workgroups descending too, 2 a fixed permutation) -- the lists must not depend on it.
+ * route_row [n]: the worker row of every batch position (anything not below W: no message); task_id [n]; worker_id [W]: the ids of the rows.  Out, caller-sized:
+ * out_worker [W], out_off [W + 1], out_task [n], of which the first *n_workers (+ 1) / out_off[*n_workers] are written.  Returns the number of ids in the lists,
+ * HQTICK_E_INVALID for a NULL argument or an order outside 0..2.  Not a product path. */
+int hqtick_debug_cancel_group(uint32_t n, uint32_t W, const uint32_t *route_row, const uint64_t *task_id, const uint32_t *worker_id, int order, uint32_t *n_workers,
+                              uint32_t *out_worker, uint32_t *out_off, uint64_t *out_task);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
