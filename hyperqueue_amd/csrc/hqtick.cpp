@@ -10,17 +10,15 @@
 //   GPU   K4 select+scatter the taken tasks in queue order -> K5 expand to per-worker records
 //   D2H   assignment records
 // The stages live in modules of their own, each behind a class that owns its buffers and takes a small Env: the ready set (ready.h), phase A (scan.h), the worker
-// set (cluster.h), the ledger (ledger.h), the mapping plan and phase C (map.h; the plan itself, free of HIP, in map_core.h).  This file keeps the context, the
-// sequence of a tick (TickRun::run), the block solvers and the C ABI's argument checks.
+// set (cluster.h), the ledger (ledger.h), the placement's solvers and the ranks' exchange (solve.h; what needs no HIP in solve_core.h), the mapping plan and phase C
+// (map.h; the plan itself, free of HIP, in map_core.h).  This file keeps the context, the sequence of a tick (TickRun::run) and the C ABI's argument checks.
 // There is no CPU implementation of the scans or of the selection and the records: without a HIP device every entry point fails.
 #include "../../include/hqtick.h"
 #ifdef HQTICK_TEST_HOOKS
 #include "../../include/hqtick_debug.h"
 #endif
 
-#include <dlfcn.h>
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <chrono>
@@ -28,16 +26,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "audit.h"
-#include "block_solve.h"
 #include "cluster.h"
-#include "price_dev.h"
 #include "ready.h"
 #include "scan.h"
+#include "solve.h"
 #ifdef HQTICK_TEST_HOOKS
 #include "price_emul.h"
 #endif
@@ -45,7 +41,6 @@
 #include "graph.h"
 #include "ledger.h"
 #include "map.h"
-#include "hb_order.h"
 #include "host_model.h"
 #include "kernels.h"
 
@@ -84,15 +79,11 @@ struct hqtick_ctx {
     hipEvent_t ev[14] = {};  // (ev[12] / ev[13]: around the kernels of the ordered view)
     std::string err = "";
     hqready::ReadySet ready;       // hqtick_upload_ready, hqtick_ready_* (ready.h): the ready set's columns in HBM (resident, or a tick's own), their deltas, the last selection's state
-    hqhost::BlockMemo block_memo;  // host class blocks of earlier ticks (host_model.h)
     hqscan::Scanner scan;          // GPU phase A (scan.h): the dense scan with its cached level table, the ordered view, the census — on the query sub-context, a query's
+    hqsolve::Solver solver;        // the placement (solve.h): the block solvers' staging and knobs, the price sweeper, the block memo, the ranks' exchange and communicator
     hqmap::Mapper map;             // the mapping plan and GPU phase C (map.h): the plan's buffers, the records, the result's host part, the last selection's launch state
     bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))
-    PinBuf h_up, h_up2, h_q, h_blk;
-    PinBuf h_blkprof; uint32_t n_blkprof = 0; bool block_profile = false;
-    hqprice::DeviceSweeper *pricer = nullptr;  // k_price_sweep: the block sweeps of the coupled placement (csrc/price.hip); HQTICK_PRICE=0 keeps coupled ticks on the host search
-    uint32_t block_budget = 4096, block_min_classes = 12;  // k_block_solve: search steps per class before the host solver takes it; classes below which the host solves alone
-    DevBuf d_blk;
+    PinBuf h_up, h_up2, h_q;
     hqcluster::WorkerSet ws;      // hqtick_cluster_* (ABI 5 and 7; cluster.h): the worker / request tables resident in HBM and their host mirror
     hqcluster::Retracting retr;   // hqtick_retracting_* (ABI 7): the table of Retracting tasks
     uint32_t last_row_groups = 0; // hqtick_cluster_last_row_groups
@@ -111,14 +102,7 @@ struct hqtick_ctx {
     PinBuf h_cancel_ids; DevBuf d_cancel_ids; uint64_t cancel_ready_removed = 0;  // hqtick_cancel_tasks: the ids' staging and their one device copy; hqtick_cancel_last_ready_removed
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     ViewHooks *view_hooks = nullptr;  // hqtick_debug_order_view's scanner and scratch (test library only), allocated on first use; nothing of it is touched on a tick's path
-    ncclComm_t comm = nullptr; uint32_t comm_rank = 0, comm_world = 0;  // hqtick_comm_init (RCCL, loaded on first use)
-    // sharded placement solve: the ranks split the coupled solve's price sweeps and the separable solve's class blocks, one small all-gather of host
-    // buffers per sweep / per launch — through the host's callback (hqtick_set_exchange) or the library's own RCCL communicator
-    hqtick_exchange_fn xfn = nullptr; void *xuser = nullptr;
-    DevBuf d_xsend, d_xrecv; PinBuf h_xsend, h_xrecv;
-    uint32_t shard_min_blocks = 1025, shard_min_classes = 1025; bool shard_solve = true;
-    uint32_t block_verify = 2, tick_seq = 0;  // HQTICK_BLOCK_VERIFY: classes of a k_block_solve launch the host re-solves while the kernel runs (host_model.h: Problem::block_verify)
-    uint64_t x_calls = 0, x_bytes = 0; double x_us = 0;
+    uint32_t tick_seq = 0;  // the tick counter: moves the block solvers' sample window from tick to tick (host_model.h: Problem::tick_seq)
     double tl[32] = {}; int ntl = 0;  // debug timeline (us since tick start), hqtick_timeline()
     hqaudit::Auditor audit;  // hqtick_resident_check (audit.h): nothing of it exists until the first call
     bool check_resident = false; int audit_depth = 0;  // HQTICK_CHECK_RESIDENT=1: the audit behind every call that changes resident state (audit_depth: inside such a call)
@@ -153,14 +137,15 @@ namespace {
 
 int fail(hqtick_ctx *ctx, int code, const std::string &msg) { ctx->err = msg; return code; }
 
-// duration between two dispatch events in us, or -1 when the pair was not recorded by a launch of this tick (the runtime's error state is
-// cleared: an unrecorded event must not surface as the "last error" of the next launch)
+#ifdef HQTICK_TEST_HOOKS
+// duration between two dispatch events in us, or -1 when the pair was not recorded (hqtick_time_kernel's calibration; the runtime's error state is cleared)
 double elapsed_us(hipEvent_t a, hipEvent_t b) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, a, b) == hipSuccess) return (double)ms * 1000.0;
     (void)hipGetLastError();
     return -1.0;
 }
+#endif
 
 int validate(hqtick_ctx *ctx, const hqtick_snapshot *s, bool need_tasks) {
     if (!s) return fail(ctx, HQTICK_E_INVALID, "null snapshot");
@@ -332,120 +317,11 @@ std::vector<hqhost::QueueLevels> queue_levels(const Scan &sc, const hqtick_snaps
     return qs;
 }
 
-// The per-class blocks of the separable placement on the device (csrc/block_solve.hip): tables staged in ONE pinned, device-mapped buffer
-// that the kernel reads in place (a few dozen bytes per class) and writes its answers into; one launch, one synchronisation.
-struct DeviceBlocks : hqhost::BlockSolver {
-    hqtick_ctx *ctx;
-    explicit DeviceBlocks(hqtick_ctx *c) : ctx(c) {}
-    bool solve(const hqblock::ColTable &ct, const hqblock::ClassTable &cl, const hqblock::Output &out) override { return begin(ct, cl, out) && finish(); }
-    bool overlaps() const override { return true; }
-    // state between begin() and finish()
-    hqblock::Output p_out{}; size_t p_ox = 0, p_ost = 0, p_osteps = 0; uint32_t p_nd = 0, p_nc = 0; bool p_launched = false, p_pending = false;
-    bool begin(const hqblock::ColTable &ct, const hqblock::ClassTable &cl, const hqblock::Output &out) override {
-        p_pending = false;
-        const uint32_t NC = ct.n_cols, R = ct.R, nd = cl.n_classes, ne = ct.ent_off[NC];
-        auto al8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-        const size_t o_off = 0, o_res = al8(o_off + (size_t)(NC + 1) * 4), o_w = al8(o_res + (size_t)ne * 4), o_kind = al8(o_w + (size_t)NC * 4), o_amt = al8(o_kind + ne),
-                     o_pool = o_amt + (size_t)ne * 8, o_free = (o_pool + (size_t)R * 8 + 15) & ~(size_t)15, o_tot = o_free + (size_t)nd * R * 8, o_elig = o_tot + (size_t)nd * R * 8,
-                     o_x = o_elig + (size_t)nd * 8, o_st = o_x + al8((size_t)nd * NC * 4), o_steps = o_st + al8((size_t)nd * 4), bytes = o_steps + al8((size_t)nd * 4) + 64;
-        if (!ctx->h_blk.ensure(bytes)) return false;
-        if (!ctx->d_blk.ensure(o_x + 64)) return false;
-        unsigned char *h = ctx->h_blk.as<unsigned char>(), *d = ctx->d_blk.as<unsigned char>(), *dpin = ctx->h_blk.dev<unsigned char>();
-        memcpy(h + o_off, ct.ent_off, (size_t)(NC + 1) * 4); memcpy(h + o_res, ct.ent_res, (size_t)ne * 4); memcpy(h + o_w, ct.weight, (size_t)NC * 4);
-        memcpy(h + o_kind, ct.ent_kind, ne); memcpy(h + o_amt, ct.ent_amount, (size_t)ne * 8); memcpy(h + o_pool, ct.pool, (size_t)R * 8);
-        memcpy(h + o_free, cl.free_, (size_t)nd * R * 8); memcpy(h + o_tot, cl.total, (size_t)nd * R * 8); memcpy(h + o_elig, cl.elig, (size_t)nd * 8);
-        // inputs: one copy into HBM (929 wavefronts reading the same table through PCIe reads would queue behind each other); outputs: written by the
-        // kernel straight into pinned memory
-        if (hqk::copy_pinned_to_hbm(dpin, d, o_x, ctx->stream) != hipSuccess) return false;  // (a copy kernel, not the copy engine: ~10 us less per launch)
-        hqblock::ColTable dct{NC, R, (const uint32_t *)(d + o_off), (const uint32_t *)(d + o_res), (const uint8_t *)(d + o_kind), (const uint64_t *)(d + o_amt), (const uint32_t *)(d + o_w), (const double *)(d + o_pool), d, (uint32_t)o_free};  // [0, o_free) = the column table: staged into LDS by the kernel
-        hqblock::ClassTable dcl{nd, (const uint64_t *)(d + o_free), (const uint64_t *)(d + o_tot), (const uint64_t *)(d + o_elig)};
-        uint64_t *dprof = nullptr;
-        if (ctx->block_profile) {  // HQTICK_BLOCK_PROFILE=1: per-class stage timestamps (tools/block_profile.py)
-            if (!ctx->h_blkprof.ensure((size_t)nd * 64 + 64)) return false;
-            memset(ctx->h_blkprof.p, 0, (size_t)nd * 64);
-            dprof = ctx->h_blkprof.dev<uint64_t>(); ctx->n_blkprof = nd;
-        }
-        hqblock::Output dout{(uint32_t *)(dpin + o_x), (uint32_t *)(dpin + o_st), (uint32_t *)(dpin + o_steps), dprof};
-        hqk::time_next_launch(ctx->timing ? ctx->ev[9] : nullptr, ctx->ev[10]);
-        const hipError_t be = hqblock::block_solve(dct, dcl, dout, ctx->block_budget, ctx->stream);
-        const bool launched = hqk::take_launch_timer().stop == nullptr && ctx->wait_on_kernel;
-        if (be != hipSuccess) return false;
-        p_out = out; p_ox = o_x; p_ost = o_st; p_osteps = o_steps; p_nd = nd; p_nc = NC; p_launched = launched; p_pending = true;
-        return true;
-    }
-    bool finish() override {
-        if (!p_pending) return false;
-        p_pending = false;
-        if ((p_launched ? hipEventSynchronize(ctx->ev[10]) : hipStreamSynchronize(ctx->stream)) != hipSuccess) return false;  // the kernel's own completion signal (HQ_HIP_LAST)
-        const unsigned char *h = ctx->h_blk.as<unsigned char>();
-        memcpy(p_out.x, h + p_ox, (size_t)p_nd * p_nc * 4); memcpy(p_out.status, h + p_ost, (size_t)p_nd * 4); memcpy(p_out.steps, h + p_osteps, (size_t)p_nd * 4);
-        if (ctx->timing) { const double us_ = elapsed_us(ctx->ev[9], ctx->ev[10]); if (us_ >= 0) ctx->stats.block_solve_us = us_; }
-        ctx->stats.n_classes_device = p_nd;
-        return true;
-    }
-};
-
-// The ranks' exchange of small host buffers (csrc/price.h: Exchange): the host's callback if one is set, else the library's RCCL communicator.
-bool rccl_allgather_host(hqtick_ctx *ctx, const void *send, void *recv, size_t bytes);  // (bottom of this file, next to the other RCCL calls)
-struct CtxExchange : hqprice::Exchange {
-    hqtick_ctx *ctx;
-    explicit CtxExchange(hqtick_ctx *c) : ctx(c) { rank = c->shard_index; world = c->shard_count; }
-    static bool available(const hqtick_ctx *c) { return c->shard_solve && c->shard_count > 1 && (c->xfn || (c->comm && c->comm_world == c->shard_count)); }
-    bool allgather(const void *send, void *recv, size_t bytes) override {
-        if (ctx->xfn) return ctx->xfn(ctx->xuser, send, recv, bytes) == 0;
-        return rccl_allgather_host(ctx, send, recv, bytes);
-    }
-    ~CtxExchange() override { ctx->x_calls += n_calls; ctx->x_bytes += n_bytes; ctx->x_us += us; }
-};
-
-// The class blocks of a separable tick over the ranks: class i of the launch goes to rank i % world (the launch is ordered longest first: a strided deal spreads the
-// hard classes), every rank runs its share through the inner solver, ONE all-gather of (x, status, steps) completes the answer on every rank.  A rank whose inner
-// solver fails reports its classes as unsolved — every rank then sends the same classes to its host solver, and the replicas stay in step.
-struct ShardedBlocks : hqhost::BlockSolver {
-    hqhost::BlockSolver &inner; hqprice::Exchange &ex; uint32_t min_classes;
-    hqblock::Output p_out{}; uint32_t p_nd = 0, p_nc = 0, p_nm = 0; bool p_pass = false, p_inner_ok = false, p_pending = false;
-    std::vector<uint64_t> cfree, ctot, celig; std::vector<uint32_t> dx, dst, dsteps; std::vector<unsigned char> send, recv;
-    ShardedBlocks(hqhost::BlockSolver &in, hqprice::Exchange &e, uint32_t mc) : inner(in), ex(e), min_classes(mc) {}
-    bool overlaps() const override { return inner.overlaps(); }
-    bool solve(const hqblock::ColTable &ct, const hqblock::ClassTable &cl, const hqblock::Output &out) override { return begin(ct, cl, out) && finish(); }
-    bool begin(const hqblock::ColTable &ct, const hqblock::ClassTable &cl, const hqblock::Output &out) override {
-        p_pass = ex.world <= 1 || cl.n_classes < min_classes;
-        if (p_pass) return inner.begin(ct, cl, out);
-        const uint32_t nd = cl.n_classes, R = ct.R, NC = ct.n_cols, W = ex.world, me = ex.rank;
-        const uint32_t nm = nd > me ? (nd - me + W - 1) / W : 0;
-        cfree.resize((size_t)nm * R); ctot.resize((size_t)nm * R); celig.resize(nm);
-        for (uint32_t j = 0; j < nm; j++) {
-            const size_t i = (size_t)me + (size_t)j * W;
-            memcpy(cfree.data() + (size_t)j * R, cl.free_ + i * R, (size_t)R * 8); memcpy(ctot.data() + (size_t)j * R, cl.total + i * R, (size_t)R * 8); celig[j] = cl.elig[i];
-        }
-        dx.assign((size_t)nm * NC, 0); dst.assign(nm, hqblock::ST_UNSUPPORTED); dsteps.assign(nm, 0);
-        p_out = out; p_nd = nd; p_nc = NC; p_nm = nm; p_pending = true;
-        p_inner_ok = nm == 0 || inner.begin(ct, hqblock::ClassTable{nm, cfree.data(), ctot.data(), celig.data()}, hqblock::Output{dx.data(), dst.data(), dsteps.data(), nullptr});
-        return true;  // (whatever the inner solver said: this rank still owes the others its part of the exchange)
-    }
-    bool finish() override {
-        if (p_pass) return inner.finish();
-        if (!p_pending) return false;
-        p_pending = false;
-        if (p_nm && !(p_inner_ok && inner.finish())) { std::fill(dst.begin(), dst.end(), (uint32_t)hqblock::ST_UNSUPPORTED); std::fill(dx.begin(), dx.end(), 0u); }
-        const uint32_t W = ex.world, NC = p_nc, mx = (p_nd + W - 1) / W;
-        const size_t o_st = (size_t)mx * NC * 4, o_steps = o_st + (size_t)mx * 4, bytes = (o_steps + (size_t)mx * 4 + 7) & ~(size_t)7;
-        send.assign(bytes, 0); recv.resize(bytes * W);
-        if (p_nm) { memcpy(send.data(), dx.data(), (size_t)p_nm * NC * 4); memcpy(send.data() + o_st, dst.data(), (size_t)p_nm * 4); memcpy(send.data() + o_steps, dsteps.data(), (size_t)p_nm * 4); }
-        const double t0 = now_us();
-        if (!ex.allgather(send.data(), recv.data(), bytes)) return false;
-        ex.us += now_us() - t0; ex.n_calls++; ex.n_bytes += bytes * W;
-        for (uint32_t r = 0; r < W; r++) {
-            const unsigned char *b = recv.data() + (size_t)r * bytes;
-            const uint32_t nr = p_nd > r ? (p_nd - r + W - 1) / W : 0;
-            for (uint32_t j = 0; j < nr; j++) {
-                const size_t i = (size_t)r + (size_t)j * W;
-                memcpy(p_out.x + i * NC, b + (size_t)j * NC * 4, (size_t)NC * 4); memcpy(p_out.status + i, b + o_st + (size_t)j * 4, 4); memcpy(p_out.steps + i, b + o_steps + (size_t)j * 4, 4);
-            }
-        }
-        return true;
-    }
-};
+// The placement (hqsolve::Solver, solve.h): what it is given of the context (ev[9] / ev[10] around k_block_solve — ev[10] is its completion, which the host waits
+// on), and its errors
+hqsolve::Env solve_env(hqtick_ctx *ctx) { return hqsolve::Env{ctx->device, ctx->stream, ctx->ev[9], ctx->ev[10], ctx->timing, ctx->wait_on_kernel, ctx->shard_index, ctx->shard_count}; }
+int solver_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->solver.err; return rc; }
+bool is_replica(hqtick_ctx *ctx) { return ctx->solver.replica(solve_env(ctx)); }  // others read this context's sweeps or records (a record sink alone is one scheduler's output path)
 
 // The mapping (hqmap::Mapper, map.h): what it is given of the context (ev[4] / ev[5] around K4, ev[1] / ev[6] around K5a, ev[7] / ev[11] around K5b — ev[11] is K5b's
 // completion, which the host waits on), and its errors
@@ -528,7 +404,7 @@ struct TickRun {
         const int sw = hqmilp::g_check_hook ? hqmilp::g_check_hook->allow : -1;
         if (!(sw < 0 ? ctx->defer_row_check : sw != 0)) return false;
         if (use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK)) return false;
-        if (ctx->asg.on || ctx->sink || ctx->shard_count > 1 || ctx->xfn || ctx->comm) return false;
+        if (ctx->asg.on || ctx->sink || is_replica(ctx)) return false;
         return s->n_retracting == 0;
     }
 
@@ -566,7 +442,7 @@ struct TickRun {
             }
             // HQTICK_FLAG_CERTIFICATE_ONLY is for ONE scheduler: replicas (a shard of several, a record sink that is merged with others', an exchange) must return the
             // canonical point — what the merge compares byte for byte — so the flag is ignored there (include/hqtick.h).
-            if (pb.certificate_only && (ctx->shard_count > 1 || ctx->sink || ctx->xfn || ctx->comm)) pb.certificate_only = false;
+            if (pb.certificate_only && (is_replica(ctx) || ctx->sink)) pb.certificate_only = false;
         };
         if ((rc = phase_a(ctx, s, &ev, &sc, &prep))) return rc;
         mark();  // 0: phase A done
@@ -587,29 +463,15 @@ struct TickRun {
         const std::function<void()> check = [&]() { if (cnt.row_check_pending()) check_ok = cnt.settle_row_check(); };
         auto solve_plan_map = [&](bool defer, bool classic) -> int {
             int rc;
-            DeviceBlocks dev_blocks(ctx);
-            pb.blocks = &dev_blocks; pb.block_min_classes = ctx->block_min_classes; pb.pricer = ctx->pricer;
-            pb.defer_row_check = defer; pb.no_fast_path = classic;
-            pb.block_verify = ctx->block_verify; pb.tick_seq = tick_seq;
-            pb.memo = (ctx->cfg.flags & (HQTICK_FLAG_NO_BLOCK_MEMO | HQTICK_FLAG_NO_TICK_CACHES)) ? nullptr : &ctx->block_memo;
-            double shard_sweep_us = -1.0;
-            ctx->x_calls = 0; ctx->x_bytes = 0; ctx->x_us = 0;
-            if (CtxExchange::available(ctx)) {  // the ranks of a sharded scheduler split the sweeps and the class blocks (no-ops below their thresholds)
-                CtxExchange xch(ctx);
-                ShardedBlocks sh_blocks(dev_blocks, xch, ctx->shard_min_classes);
-                pb.blocks = &sh_blocks;
-                if (ctx->pricer) {
-                    hqprice::ShardedSweeper sh_sweeps(*ctx->pricer, xch, ctx->shard_min_blocks);
-                    pb.pricer = &sh_sweeps;
-                    cnt = hqhost::run_scheduling_solver(pb, batches);
-                    shard_sweep_us = sh_sweeps.stat_sweep_us;
-                } else cnt = hqhost::run_scheduling_solver(pb, batches);
-            } else cnt = hqhost::run_scheduling_solver(pb, batches);
-            pb.blocks = nullptr; pb.pricer = nullptr; pb.defer_row_check = false; pb.no_fast_path = false;
+            hqsolve::Stats st;
+            const bool use_memo = !(ctx->cfg.flags & (HQTICK_FLAG_NO_BLOCK_MEMO | HQTICK_FLAG_NO_TICK_CACHES));
+            cnt = ctx->solver.solve(solve_env(ctx), pb, batches, hqsolve::Opts{defer, classic, tick_seq, use_memo}, &st);
+            if (st.block_solve_us >= 0) ctx->stats.block_solve_us = st.block_solve_us;
+            if (st.blocks_finished) ctx->stats.n_classes_device = st.n_classes_launched;
             ctx->stats.price_sweeps = (uint32_t)cnt.price_sweeps; ctx->stats.price_rounds = (uint32_t)cnt.price_rounds; ctx->stats.price_us = cnt.price_us; ctx->stats.milp_us = cnt.milp_us; ctx->stats.model_us = cnt.model_us; ctx->stats.solve_pre_us = cnt.pre_us;
-            ctx->stats.price_sweep_us = shard_sweep_us >= 0.0 ? shard_sweep_us : (ctx->pricer ? ctx->pricer->stat_sweep_us : 0.0); ctx->stats.milp_cols = (uint32_t)cnt.milp_cols; ctx->stats.milp_rows = (uint32_t)cnt.milp_rows;
+            ctx->stats.price_sweep_us = st.price_sweep_us; ctx->stats.milp_cols = (uint32_t)cnt.milp_cols; ctx->stats.milp_rows = (uint32_t)cnt.milp_rows;
             ctx->stats.n_classes_verified = cnt.blocks_verified; ctx->stats.n_classes_mismatch = cnt.blocks_mismatch; ctx->stats.n_classes_rejected = cnt.blocks_rejected; ctx->stats.n_classes_memo = cnt.blocks_memo;
-            ctx->stats.exchange_calls = (uint32_t)ctx->x_calls; ctx->stats.exchange_bytes = ctx->x_bytes; ctx->stats.exchange_us = ctx->x_us;
+            ctx->stats.exchange_calls = st.exchange_calls; ctx->stats.exchange_bytes = st.exchange_bytes; ctx->stats.exchange_us = st.exchange_us;
             if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
             ctx->stats.n_classes_device = cnt.blocks_device; ctx->stats.n_classes_host = cnt.blocks_host; ctx->stats.block_steps_max = cnt.block_steps_max; ctx->stats.n_classes = cnt.n_classes;
             ctx->stats.solve_classify_us = cnt.t_classify_us; ctx->stats.solve_blocks_us = cnt.t_blocks_us; ctx->stats.solve_decode_us = cnt.t_decode_us;
@@ -617,8 +479,7 @@ struct TickRun {
             t3 = now_us();
             out->is_optimal = cnt.is_optimal;
             out->is_canonical = cnt.is_canonical && cnt.is_optimal;
-            status = HQTICK_DONE;  // scheduler/main.rs:57-68
-            if (!cnt.is_optimal) status = cnt.empty() ? HQTICK_NO_PROGRESS : HQTICK_NEED_MORE_COMPUTE;
+            status = hqsolve::tick_status(cnt);
             // ---------------- host: mapping plan ----------------
             const hqmap::PlanIn in = plan_in();
             hqmap::HostResult &hr = ctx->map.res;
@@ -654,7 +515,6 @@ struct TickRun {
 };
 
 // ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12): what hqasg::Ledger (ledger.h) is given of the context
-bool ledger_replica(const hqtick_ctx *ctx) { return ctx->shard_count > 1 || ctx->xfn || ctx->comm; }  // (a record sink alone is one scheduler's output path, not a replica)
 hqasg::Env ledger_env(hqtick_ctx *ctx) {
     const hqready::Cols c = ctx->ready.cols();
     return hqasg::Env{ctx->device, ctx->stream, ctx->ws.rows(), ctx->ws.W(), ctx->ws.R(), c.id, c.prio, c.rq, c.n,
@@ -673,7 +533,7 @@ int ledger_guard(hqtick_ctx *ctx) {
 int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool use_resident) {
     hqtick_snapshot full;
     if (ctx->asg.on && s) {  // the assignment ledger (ABI 12) is the tick's only source of the running tasks
-        if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "assignment ledger on a sharded or replica context");
+        if (is_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "assignment ledger on a sharded or replica context");
         if (s->worker_id || !ctx->ws.valid()) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the tick runs on the resident worker set (HQ_WORKERS_RESIDENT, no worker arrays)");
         if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
         if (ctx->asg.tracking() && s->prefilled_off) return fail(ctx, HQTICK_E_INVALID, "prefilled tracking on: the snapshot must not carry a prefilled CSR as well");
@@ -780,25 +640,13 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     ctx->cfg = *config; ctx->device = config->device_index;
     ctx->timing = (config->flags & HQTICK_FLAG_NO_KERNEL_TIMING) == 0;
     if (const char *e = getenv("HQTICK_TPW")) { long v = atol(e); if (v >= 256 && v <= (1 << 20) && v % 256 == 0) ctx->tpw_hint = (uint32_t)v; }
-    if (const char *e = getenv("HQTICK_BLOCK_PROFILE")) ctx->block_profile = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_CHECK_RESIDENT")) ctx->check_resident = atoi(e) != 0;
-    if (const char *e = getenv("HQTICK_BLOCK_BUDGET")) { long v = atol(e); if (v >= 1 && v <= (1 << 24)) ctx->block_budget = (uint32_t)v; }
-    if (const char *e = getenv("HQTICK_BLOCK_MIN_CLASSES")) { long v = atol(e); if (v >= 0) ctx->block_min_classes = (uint32_t)v; }
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
     if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) { hipStreamDestroy(ctx->stream); delete ctx; return HQTICK_E_DEVICE; }
     if (const char *e = getenv("HQTICK_K2_RIDE_ALONG")) { ctx->k2_own_stream = atoi(e) == 0; ctx->k2_on_hist = atoi(e) == 1; }
     if (const char *e = getenv("HQTICK_WAIT_ON_KERNEL")) ctx->wait_on_kernel = atoi(e) != 0;
     if (const char *e = getenv("HQTICK_DEFER_ROW_CHECK")) ctx->defer_row_check = atoi(e) != 0;
-    {
-        bool price = true; uint32_t min_cols = 0;
-        if (const char *e = getenv("HQTICK_PRICE")) price = atoi(e) != 0;
-        if (const char *e = getenv("HQTICK_PRICE_MIN_COLS")) { long v = atol(e); if (v > 0) min_cols = (uint32_t)v; }
-        if (price) { ctx->pricer = new hqprice::DeviceSweeper(ctx->stream); ctx->pricer->budget = ctx->block_budget; if (min_cols) ctx->pricer->min_cols = min_cols; }
-    }
-    if (const char *e = getenv("HQTICK_BLOCK_VERIFY")) ctx->block_verify = strcmp(e, "all") == 0 ? 0xFFFFFFFFu : (uint32_t)std::max(0L, atol(e));
-    if (const char *e = getenv("HQTICK_SHARD_SOLVE")) ctx->shard_solve = atoi(e) != 0;
-    if (const char *e = getenv("HQTICK_SHARD_MIN_BLOCKS")) { long v = atol(e); if (v >= 0) ctx->shard_min_blocks = (uint32_t)v; }
-    if (const char *e = getenv("HQTICK_SHARD_MIN_CLASSES")) { long v = atol(e); if (v >= 0) ctx->shard_min_classes = (uint32_t)v; }
+    if (ctx->solver.init(ctx->device, ctx->stream)) { delete ctx; return HQTICK_E_DEVICE; }
     if (ctx->ws.init()) { delete ctx; return HQTICK_E_DEVICE; }
     for (auto &e : ctx->ev) if (hipEventCreate(&e) != hipSuccess) { delete ctx; return HQTICK_E_DEVICE; }
     if (ctx->scan.init()) { delete ctx; return HQTICK_E_DEVICE; }
@@ -806,14 +654,11 @@ int hqtick_create(const hqtick_config *config, hqtick_ctx **out_ctx) {
     return 0;
 }
 
-static void rccl_destroy_comm(hqtick_ctx *ctx);
 void hqtick_destroy(hqtick_ctx *ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
-    delete ctx->pricer; ctx->pricer = nullptr;
-    ctx->d_blk.release();
     ctx->map.release();
     ctx->scan.release();
     ctx->ready.release();
@@ -821,11 +666,12 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     if (ctx->qctx) { hqtick_destroy(ctx->qctx); ctx->qctx = nullptr; }
     if (ctx->view_hooks) { ctx->view_hooks->release(); delete ctx->view_hooks; ctx->view_hooks = nullptr; }
     hipSetDevice(ctx->device);
-    if (ctx->comm) { rccl_destroy_comm(ctx); }
+    ctx->solver.comm_destroy(ctx->device);
+    ctx->solver.release();
     ctx->graph.release();
     ctx->asg.release_all();
     ctx->audit.release();
-    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release(); ctx->h_blk.release(); ctx->h_blkprof.release();
+    ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release();
     ctx->h_cancel_ids.release(); ctx->d_cancel_ids.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
@@ -1058,7 +904,7 @@ int hqtick_cluster_drop(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> int {
 // Clock mode: the termination times stay with the worker set and a tick takes only the clock (hqcluster::WorkerSet::set_clock)
 int hqtick_cluster_set_clock(hqtick_ctx *ctx, int64_t now_ns) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_cluster_set_clock: not on a sharded or replica context");
+    if (is_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_cluster_set_clock: not on a sharded or replica context");
     if (int rc = cluster_open(ctx, "hqtick_cluster_set_clock")) return rc;
     if (int rc = ledger_guard(ctx)) return rc;
     return cluster_fail(ctx, ctx->ws.set_clock(now_ns));
@@ -1181,7 +1027,7 @@ uint32_t hqtick_retracting_count(const hqtick_ctx *ctx) { return ctx ? ctx->retr
 // ---- assignment ledger (ABI 12; include/hqtick.h): arguments validated here, the operations are hqasg::Ledger's (ledger.h) ----
 int hqtick_assigned_enable(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) { return with_audit(ctx, [&]() -> int {
     if (!ctx) return HQTICK_E_INVALID;
-    if (ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
+    if (is_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, "hqtick_assigned_enable: not on a sharded or replica context");
     if (!ctx->ws.valid()) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable without a resident worker set (hqtick_cluster_upload)");
     if (n && (!task_id || !worker_id || !rq || !variant || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_enable: null array");
     HQ_HIP(hipSetDevice(ctx->device));
@@ -1198,7 +1044,7 @@ int hqtick_assigned_disable(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> i
 // the arrays of a batch are there and the batch is one the kernels can index
 static int ledger_open(hqtick_ctx *ctx, const char *fn, uint32_t n, bool arrays, bool prefilled = false, bool tracked = false) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (prefilled && ledger_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, std::string(fn) + ": not on a sharded or replica context");
+    if (prefilled && is_replica(ctx)) return fail(ctx, HQTICK_E_UNSUPPORTED, std::string(fn) + ": not on a sharded or replica context");
     if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
     if (int rc = ledger_guard(ctx)) return rc;
     HQ_HIP(hipSetDevice(ctx->device));
@@ -1419,20 +1265,14 @@ static int solve_on_fake_workers(hqtick_ctx *ctx, const hqtick_snapshot *s, cons
     hqhost::Problem pb;
     fill_problem(pb, s, ctx->cfg, ev_real);
     hqhost::WorkerSet fw;
-    fw.n = fake->n_workers; fw.R = s->n_resources; fw.id = fake->worker_id; fw.total = fake->worker_total; fw.free_ = fake->worker_total;
-    fw.remaining_ns = fake->worker_remaining_ns; fw.min_util = fake->worker_min_utilization; fw.flags = nullptr; fw.group = nullptr;
-    fw.vflags = ev_fake.flags; fw.vtmc = ev_fake.tmc; fw.n_variant_slots = Q ? s->rq_variant_off[Q] : 0;
-    fw.blocked.assign(fw.n, {});
+    hqsolve::fake_worker_set(fw, fake, s->n_resources, ev_fake.flags, ev_fake.tmc, Q ? s->rq_variant_off[Q] : 0);
     hqhost::group_equal_rows(fw, true);
     pb.custom = &fw;
     std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
     std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    DeviceBlocks dev_blocks(ctx);
-    pb.blocks = &dev_blocks; pb.block_min_classes = ctx->block_min_classes; pb.pricer = ctx->pricer;
-    hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
+    hqhost::Counts cnt = ctx->solver.solve(solve_env(ctx), pb, batches, hqsolve::Opts{false, false, 0, false}, nullptr);
     if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    ctx->q_loaded.assign(fake->n_workers, 0);
-    for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) ctx->q_loaded[wc.first] = 1;
+    hqsolve::loaded_flags(cnt, fake->n_workers, ctx->q_loaded);
     out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
     return 0;
 }
@@ -1440,14 +1280,17 @@ static int solve_on_fake_workers(hqtick_ctx *ctx, const hqtick_snapshot *s, cons
 // The what-if query runs on the live Core between two ticks (crates/tako/src/control.rs:125-155): it must not disturb what the ctx keeps
 // resident (ready-set columns, level table, the last tick's selection that hqtick_ready_consume_last replays, the dependency graph).  It
 // therefore runs on a private sub-context — same device, own stream and buffers — created on first use.
+static int query_ctx(hqtick_ctx *ctx) {
+    if (ctx->qctx) return 0;
+    hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
+    int rc = hqtick_create(&cfg, &ctx->qctx);
+    if (rc) { ctx->qctx = nullptr; return fail(ctx, rc, "creating the query sub-context failed"); }
+    return 0;
+}
 static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, hqtick_query_result *out);
 int hqtick_query(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, hqtick_query_result *out) {
     if (!ctx || !out || !fake) return HQTICK_E_INVALID;
-    if (!ctx->qctx) {
-        hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
-        int rc = hqtick_create(&cfg, &ctx->qctx);
-        if (rc) { ctx->qctx = nullptr; return fail(ctx, rc, "creating the query sub-context failed"); }
-    }
+    if (int rc = query_ctx(ctx)) return rc;
     int rc = query_on(ctx->qctx, s, fake, out);
     if (rc < 0) ctx->err = ctx->qctx->err;
     return rc;
@@ -1490,11 +1333,7 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
         sub.prefill_off = s->prefill_off; sub.prefill_priority = s->prefill_priority;
     }
     HQ_HIP(hipSetDevice(ctx->device));
-    if (!ctx->qctx) {
-        hqtick_config cfg = ctx->cfg; cfg.flags |= HQTICK_FLAG_NO_KERNEL_TIMING;
-        int rc = hqtick_create(&cfg, &ctx->qctx);
-        if (rc) { ctx->qctx = nullptr; return fail(ctx, rc, "creating the query sub-context failed"); }
-    }
+    if (int rc = query_ctx(ctx)) return rc;
     hqtick_ctx *q = ctx->qctx;
     // the census reads ctx's columns on ctx's stream — behind every add, remove, append and compaction queued there — and writes only the sub-context's scanner
     Scan sc;
@@ -1514,37 +1353,6 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
 #ifdef HQTICK_TEST_HOOKS
 // ---- libhqtick_test.so only (include/hqtick_debug.h): CPU hooks for the test suite.  Not compiled into libhqtick.so. ----
 namespace {
-// k_block_solve's algorithm (csrc/block_core.h) with the wavefront emulated by a loop over its 64 lanes
-struct EmulatedBlocks : hqhost::BlockSolver {
-    uint32_t budget;
-    explicit EmulatedBlocks(uint32_t b) : budget(b) {}
-    bool solve(const hqblock::ColTable &ct, const hqblock::ClassTable &cl, const hqblock::Output &out) override {
-        static thread_local hqblock::Shared *S = new hqblock::Shared();
-        hqblock::HostWave wv;
-        // the column table as ONE 16-byte-aligned allocation, as the tick stages it for the kernel: the emulation then takes the LDS-staging path too
-        const uint32_t NC = ct.n_cols, R = ct.R, ne = ct.ent_off[NC];
-        auto al8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-        const size_t o_res = al8((size_t)(NC + 1) * 4), o_w = al8(o_res + (size_t)ne * 4), o_kind = al8(o_w + (size_t)NC * 4), o_amt = al8(o_kind + ne), o_pool = o_amt + (size_t)ne * 8,
-                     bytes = (o_pool + (size_t)R * 8 + 15) & ~(size_t)15;
-        std::vector<hqblock::V16> store(bytes / 16 + 1);
-        unsigned char *b = reinterpret_cast<unsigned char *>(store.data());
-        memcpy(b, ct.ent_off, (size_t)(NC + 1) * 4); memcpy(b + o_res, ct.ent_res, (size_t)ne * 4); memcpy(b + o_w, ct.weight, (size_t)NC * 4);
-        memcpy(b + o_kind, ct.ent_kind, ne); memcpy(b + o_amt, ct.ent_amount, (size_t)ne * 8); memcpy(b + o_pool, ct.pool, (size_t)R * 8);
-        hqblock::ColTable bt{NC, R, (const uint32_t *)b, (const uint32_t *)(b + o_res), b + o_kind, (const uint64_t *)(b + o_amt), (const uint32_t *)(b + o_w), (const double *)(b + o_pool), b, (uint32_t)bytes};
-        for (uint32_t c = 0; c < cl.n_classes; c++) hqblock::solve_block(wv, *S, (c & 1) ? ct : bt, cl, c, out, budget);  // odd classes: tables read in place
-        if (corrupt_mode && corrupt_class < cl.n_classes && out.status[corrupt_class] == hqblock::ST_OK) {  // fault injection (tests/test_block_solve.py): what a wrong kernel would hand back
-            uint32_t *x = out.x + (size_t)corrupt_class * NC;
-            if (corrupt_mode == 1) { for (uint32_t g = 0; g < NC; g++) if (x[g]) { x[g]--; break; } }               // one task short: feasible, not maximal
-            else if (corrupt_mode == 2) { for (uint32_t g = NC; g-- > 0;) if (x[g]) { x[g] += 1000; break; } }       // does not fit the rows
-            else if (corrupt_mode == 3) {                                                                             // everything on ONE column: corrupt_fill = column << 16 | count
-                const uint32_t col = corrupt_fill >> 16, n = corrupt_fill & 0xFFFFu;
-                if (col < NC) { for (uint32_t g = 0; g < NC; g++) x[g] = 0; x[col] = n; }
-            }
-        }
-        return true;
-    }
-    int corrupt_mode = 0; uint32_t corrupt_class = 0, corrupt_fill = 0;
-};
 thread_local int g_block_emulation = 0, g_price_emulation = 0; thread_local uint32_t g_price_min_cols = 0, g_last_price_sweeps = 0, g_last_price_rounds = 0;
 thread_local uint32_t g_block_budget = 4096, g_last_blocks_device = 0, g_last_blocks_host = 0;
 thread_local uint32_t g_block_verify = 2, g_tick_seq = 0, g_last_guard[3] = {0, 0, 0}; thread_local int g_corrupt_mode = 0; thread_local uint32_t g_corrupt_class = 0, g_corrupt_fill = 0;
@@ -1731,7 +1539,7 @@ int hqtick_debug_block_solve_host(uint32_t n_cols, uint32_t n_resources, const u
     hqblock::ColTable ct{n_cols, n_resources, ent_off, ent_res, ent_kind, ent_amount, weight, pool, nullptr, 0};
     hqblock::ClassTable cl{n_classes, free_, total, elig};
     hqblock::Output out{x, status, steps, nullptr};
-    EmulatedBlocks emu(budget ? budget : 4096);
+    hqsolve::EmulatedBlocks emu(budget ? budget : 4096);
     return emu.solve(ct, cl, out) ? 0 : HQTICK_E_DEVICE;
 }
 
@@ -1759,24 +1567,18 @@ static int host_stages(const hqtick_config *config, const hqtick_snapshot *s, co
     memset(out, 0, sizeof(*out));
     g_last_mn_rq.clear(); g_last_mn_off.assign(1, 0); g_last_mn_worker.clear();
     export_batches(ctx, batches, out);
-    EmulatedBlocks emu(g_block_budget);
+    hqsolve::EmulatedBlocks emu(g_block_budget);
     emu.corrupt_mode = g_corrupt_mode; emu.corrupt_class = g_corrupt_class; emu.corrupt_fill = g_corrupt_fill;
-    if (g_block_emulation) { pb.blocks = &emu; pb.block_min_classes = 1; }
-    pb.block_verify = g_block_verify; pb.tick_seq = g_tick_seq; pb.memo = g_memo;
     hqprice::EmulatedSweeper pemu;
-    if (g_price_emulation) { pemu.fail_at = g_price_fault; pemu.budget = g_block_budget; if (g_price_min_cols) pemu.min_cols = g_price_min_cols; pb.pricer = &pemu; }
+    if (g_price_emulation) { pemu.fail_at = g_price_fault; pemu.budget = g_block_budget; if (g_price_min_cols) pemu.min_cols = g_price_min_cols; }
+    hqsolve::wire(pb, hqsolve::Wiring{g_block_emulation ? &emu : nullptr, 1, g_price_emulation ? &pemu : nullptr, g_block_verify, g_tick_seq, g_memo});
     hqhost::Counts cnt;
     auto solve = [&]() {
         if (g_xfn && g_xworld > 1) {  // this call is one rank of a sharded scheduler
-            struct FnExchange : hqprice::Exchange { bool allgather(const void *snd, void *rcv, size_t bytes) override { return g_xfn(g_xuser, snd, rcv, bytes) == 0; } } xch;
-            xch.rank = g_xrank; xch.world = g_xworld;
-            ShardedBlocks sh_blocks(emu, xch, g_xmin_classes);
-            hqprice::ShardedSweeper sh_sweeps(pemu, xch, g_xmin_blocks);
-            if (pb.blocks) pb.blocks = &sh_blocks;
-            if (pb.pricer) pb.pricer = &sh_sweeps;
-            cnt = hqhost::run_scheduling_solver(pb, batches);
+            hqsolve::FnExchange xch(g_xfn, g_xuser, g_xrank, g_xworld);
+            cnt = hqsolve::run_solver(pb, batches, &xch, g_xmin_classes, g_xmin_blocks);
             g_xcalls = (uint32_t)xch.n_calls;
-        } else cnt = hqhost::run_scheduling_solver(pb, batches);
+        } else cnt = hqsolve::run_solver(pb, batches, nullptr, 0, 0);
     };
     // hqtick_debug_set_defer_row_check(1): the row check of a fast-path placement is this caller's, as in a tick (TickRun::run) — run behind the solver, and a failure
     // sends the model down the classic path in a second call.  Never as a rank of a sharded scheduler, like the tick.
@@ -1796,7 +1598,7 @@ static int host_stages(const hqtick_config *config, const hqtick_snapshot *s, co
     for (size_t k = 0; k < cnt.keys.size(); k++)
         for (auto &wc : cnt.per_key[k]) { hr.cnt_rq.push_back(cnt.keys[k].first); hr.cnt_variant.push_back(cnt.keys[k].second); hr.cnt_worker.push_back(wc.first); hr.cnt_value.push_back(wc.second); }
     out->is_optimal = cnt.is_optimal; out->is_canonical = cnt.is_canonical && cnt.is_optimal;
-    out->status = cnt.is_optimal ? HQTICK_DONE : (cnt.empty() ? HQTICK_NO_PROGRESS : HQTICK_NEED_MORE_COMPUTE);
+    out->status = hqsolve::tick_status(cnt);
     if (with_plan) {  // (plan_keys writes the counts itself: the same rows, in the same order)
         static thread_local std::vector<uint32_t> tables;
         hqmap::Plan &ps = ctx->map.plan;
@@ -1847,10 +1649,7 @@ int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *
     hqhost::Problem pb;
     fill_problem(pb, s, ctx->cfg, ev);
     hqhost::WorkerSet fw;  // as in hqtick_query
-    fw.n = fake->n_workers; fw.R = R; fw.id = fake->worker_id; fw.total = fake->worker_total; fw.free_ = fake->worker_total;
-    fw.remaining_ns = fake->worker_remaining_ns; fw.min_util = fake->worker_min_utilization; fw.flags = nullptr; fw.group = nullptr;
-    fw.vflags = fake_vflags; fw.vtmc = fake_vtmc; fw.n_variant_slots = Q ? s->rq_variant_off[Q] : 0;
-    fw.blocked.assign(fw.n, {});
+    hqsolve::fake_worker_set(fw, fake, R, fake_vflags, fake_vtmc, Q ? s->rq_variant_off[Q] : 0);
     hqhost::group_equal_rows(fw, true);
     pb.custom = &fw;
     Scan sc; sc.Q = Q; sc.L = n_levels; sc.G = n_levels * Q;
@@ -1858,12 +1657,11 @@ int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *
     runs_from_hist(sc);
     std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
     std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    EmulatedBlocks emu(g_block_budget);
+    hqsolve::EmulatedBlocks emu(g_block_budget);
     if (g_block_emulation) { pb.blocks = &emu; pb.block_min_classes = 1; }
     hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
     if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    ctx->q_loaded.assign(fake->n_workers, 0);
-    for (auto &k : cnt.per_key) for (auto &wc : k) if (wc.second > 0) ctx->q_loaded[wc.first] = 1;  // query.rs:73-81
+    hqsolve::loaded_flags(cnt, fake->n_workers, ctx->q_loaded);  // query.rs:73-81
     out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
     return 0;
 }
@@ -1880,7 +1678,7 @@ int hqtick_set_shard(hqtick_ctx *ctx, uint32_t shard_index, uint32_t shard_count
 
 int hqtick_set_exchange(hqtick_ctx *ctx, hqtick_exchange_fn fn, void *user) {
     if (!ctx) return HQTICK_E_INVALID;
-    ctx->xfn = fn; ctx->xuser = fn ? user : nullptr;
+    ctx->solver.set_exchange(fn, user);
     return 0;
 }
 
@@ -1962,9 +1760,8 @@ int hqtick_timeline(const hqtick_ctx *ctx, double *out, int cap) {
 }
 
 const uint64_t *hqtick_block_profile_last(const hqtick_ctx *ctx, uint32_t *n_classes) {
-    if (!ctx || !ctx->block_profile || !ctx->n_blkprof) { if (n_classes) *n_classes = 0; return nullptr; }
-    if (n_classes) *n_classes = ctx->n_blkprof;
-    return ctx->h_blkprof.as<uint64_t>();
+    if (!ctx) { if (n_classes) *n_classes = 0; return nullptr; }
+    return ctx->solver.block_profile_last(n_classes);
 }
 #endif
 
@@ -1981,112 +1778,40 @@ int hqtick_kernel_stats_last(const hqtick_ctx *ctx, hqtick_kernel_stats *out) {
     return 0;
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------- RCCL all-gather of the shards' record sinks
-// north_star: "workers hash-partitioned across the GPUs of one node with a single RCCL allgather over xGMI to merge the assignment vector".
-// librccl is loaded on first use (dlopen), so that a single-GPU host needs no RCCL at all and a process that already carries one (e.g.
-// PyTorch's) shares it.
-namespace {
-struct Rccl {
-    void *h = nullptr;
-    decltype(&ncclGetUniqueId) get_id = nullptr;
-    decltype(&ncclCommInitRank) init_rank = nullptr;
-    decltype(&ncclAllGather) all_gather = nullptr;
-    decltype(&ncclCommDestroy) destroy = nullptr;
-    decltype(&ncclGetErrorString) err = nullptr;
-    bool ok() const { return h && get_id && init_rank && all_gather && destroy && err; }
-};
-Rccl &rccl() {
-    static Rccl r;
-    if (!r.h) {
-        for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) { r.h = dlopen(name, RTLD_NOW | RTLD_GLOBAL); if (r.h) break; }
-        if (r.h) {
-            r.get_id = (decltype(r.get_id))dlsym(r.h, "ncclGetUniqueId"); r.init_rank = (decltype(r.init_rank))dlsym(r.h, "ncclCommInitRank");
-            r.all_gather = (decltype(r.all_gather))dlsym(r.h, "ncclAllGather"); r.destroy = (decltype(r.destroy))dlsym(r.h, "ncclCommDestroy");
-            r.err = (decltype(r.err))dlsym(r.h, "ncclGetErrorString");
-        }
-    }
-    return r;
-}
-}  // namespace
-
-extern "C" {
-
+// ---- the library's own RCCL communicator (hqsolve::Solver, solve.h): arguments validated here ----
 int hqtick_comm_unique_id(void *id_out) {
     if (!id_out) return HQTICK_E_INVALID;
-    Rccl &r = rccl();
-    if (!r.ok()) return HQTICK_E_NO_DEVICE;
-    ncclUniqueId id;
-    if (r.get_id(&id) != ncclSuccess) return HQTICK_E_DEVICE;
-    static_assert(sizeof(id) == HQTICK_COMM_ID_BYTES, "ncclUniqueId size");
-    memcpy(id_out, &id, sizeof(id));
-    return 0;
+    return hqsolve::Solver::comm_unique_id(id_out);
 }
 
 int hqtick_comm_init(hqtick_ctx *ctx, const void *id, uint32_t rank, uint32_t world) {
     if (!ctx || !id || world == 0 || rank >= world) return HQTICK_E_INVALID;
-    Rccl &r = rccl();
-    if (!r.ok()) return fail(ctx, HQTICK_E_NO_DEVICE, "librccl.so could not be loaded");
-    HQ_HIP(hipSetDevice(ctx->device));
-    if (ctx->comm) { r.destroy(ctx->comm); ctx->comm = nullptr; }
-    ncclUniqueId uid; memcpy(&uid, id, sizeof(uid));
-    ncclResult_t rc = r.init_rank(&ctx->comm, (int)world, uid, (int)rank);
-    if (rc != ncclSuccess) { ctx->comm = nullptr; return fail(ctx, HQTICK_E_DEVICE, std::string("ncclCommInitRank: ") + r.err(rc)); }
-    ctx->comm_rank = rank; ctx->comm_world = world;
+    if (int rc = solver_fail(ctx, ctx->solver.comm_init(ctx->device, id, rank, world))) return rc;
     return hqtick_set_shard(ctx, rank, world);
 }
 
 int hqtick_shard_allgather(hqtick_ctx *ctx, void *recv_device, size_t recv_bytes) {
     if (!ctx || !recv_device) return HQTICK_E_INVALID;
-    if (!ctx->comm) return fail(ctx, HQTICK_E_INVALID, "hqtick_shard_allgather without hqtick_comm_init");
+    if (!ctx->solver.has_comm()) return fail(ctx, HQTICK_E_INVALID, "hqtick_shard_allgather without hqtick_comm_init");
     if (!ctx->sink || !ctx->sink_bytes) return fail(ctx, HQTICK_E_INVALID, "hqtick_shard_allgather without a record sink (hqtick_set_record_sink)");
-    if (recv_bytes < (size_t)ctx->comm_world * ctx->sink_bytes) return fail(ctx, HQTICK_E_CAPACITY, "receive buffer smaller than world x sink bytes");
-    HQ_HIP(hipSetDevice(ctx->device));
-    ncclResult_t rc = rccl().all_gather(ctx->sink, recv_device, ctx->sink_bytes, ncclUint8, ctx->comm, ctx->stream);
-    if (rc != ncclSuccess) return fail(ctx, HQTICK_E_DEVICE, std::string("ncclAllGather: ") + rccl().err(rc));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    if (recv_bytes < (size_t)ctx->solver.comm_world() * ctx->sink_bytes) return fail(ctx, HQTICK_E_CAPACITY, "receive buffer smaller than world x sink bytes");
+    return solver_fail(ctx, ctx->solver.allgather_device(solve_env(ctx), ctx->sink, recv_device, ctx->sink_bytes));
 }
-
-}  // extern "C"
-
-namespace {
-// all-gather of a small HOST buffer through the RCCL communicator: staged through HBM (ncclAllGather wants device memory on both sides)
-bool rccl_allgather_host(hqtick_ctx *ctx, const void *send, void *recv, size_t bytes) {
-    if (!ctx->comm || bytes == 0) return false;
-    const size_t total = bytes * ctx->comm_world;
-    if (!ctx->h_xsend.ensure(bytes) || !ctx->h_xrecv.ensure(total) || !ctx->d_xsend.ensure(bytes) || !ctx->d_xrecv.ensure(total)) return false;
-    if (hipSetDevice(ctx->device) != hipSuccess) return false;
-    memcpy(ctx->h_xsend.p, send, bytes);
-    if (hipMemcpyAsync(ctx->d_xsend.p, ctx->h_xsend.p, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return false;
-    if (rccl().all_gather(ctx->d_xsend.p, ctx->d_xrecv.p, bytes, ncclUint8, ctx->comm, ctx->stream) != ncclSuccess) return false;
-    if (hipMemcpyAsync(ctx->h_xrecv.p, ctx->d_xrecv.p, total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return false;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return false;
-    memcpy(recv, ctx->h_xrecv.p, total);
-    return true;
-}
-}  // namespace
-
-extern "C" {
 
 #ifdef HQTICK_TEST_HOOKS
 // libhqtick_test.so: one all-gather of a host buffer through the library's RCCL communicator, as the sharded solve issues it per sweep — for the single-rank
 // round trip of the GPU suite (recv == send) and for timing the exchange's fixed cost (H2D + ncclAllGather + D2H + one stream synchronisation)
 int hqtick_debug_exchange(hqtick_ctx *ctx, const void *send, void *recv, size_t bytes_per_rank) {
     if (!ctx || !send || !recv) return HQTICK_E_INVALID;
-    if (!ctx->comm) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_exchange without hqtick_comm_init");
-    return rccl_allgather_host(ctx, send, recv, bytes_per_rank) ? 0 : fail(ctx, HQTICK_E_DEVICE, "the RCCL exchange failed");
+    if (!ctx->solver.has_comm()) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_exchange without hqtick_comm_init");
+    return ctx->solver.allgather_host(solve_env(ctx), send, recv, bytes_per_rank) ? 0 : fail(ctx, HQTICK_E_DEVICE, "the RCCL exchange failed");
 }
 #endif
 
 int hqtick_comm_destroy(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;
-    if (ctx->comm) { hipSetDevice(ctx->device); rccl().destroy(ctx->comm); ctx->comm = nullptr; }
-    ctx->comm_world = 0; ctx->comm_rank = 0;
+    ctx->solver.comm_destroy(ctx->device);
     return 0;
 }
 
 }  // extern "C"
-
-static void rccl_destroy_comm(hqtick_ctx *ctx) { hqtick_comm_destroy(ctx); }
