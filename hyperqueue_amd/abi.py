@@ -102,6 +102,9 @@ class GraphStatsC(C.Structure):
 
 # hqtick_cancel_last_routes (include/hqtick.h): what a batch position of hqtick_cancel_tasks was
 HQ_CANCEL_NONE, HQ_CANCEL_ASSIGNED, HQ_CANCEL_PREFILLED, HQ_CANCEL_MN, HQ_CANCEL_RETRACTING, HQ_CANCEL_REPEAT = 0, 1, 2, 3, 4, 5
+# hqtick_finish_last_routes (include/hqtick.h): what a batch position of hqtick_finish_tasks was; 1 to 3 are accepted, the others refused
+HQ_FINISH_NONE, HQ_FINISH_ASSIGNED, HQ_FINISH_MN, HQ_FINISH_RETRACTING, HQ_FINISH_REPEAT, HQ_FINISH_WRONG_WORKER, HQ_FINISH_PREFILLED = 0, 1, 2, 3, 4, 5, 6
+HQ_FINISH_ACCEPTED = (HQ_FINISH_ASSIGNED, HQ_FINISH_MN, HQ_FINISH_RETRACTING)
 
 # hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
 HQ_CHECK_READY, HQ_CHECK_LEDGER, HQ_CHECK_GRAPH, HQ_CHECK_CROSS, HQ_CHECK_STRICT, HQ_CHECK_ALL = 1, 2, 4, 8, 16, 15

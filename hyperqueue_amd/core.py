@@ -779,6 +779,88 @@ class SchedEnv:
             t.state, t.worker = FINISHED, None
         return messages
 
+    def finish_tasks(self, pairs) -> List[int]:
+        """task_finished (server/reactor.rs:510-590) for the (task id, reporting worker) pairs, in this order, with the reference's assertions as refusals:
+          Assigned/Running   reported by its worker: remove_sn_task                                                       HQ_FINISH_ASSIGNED
+          RunningMultiNode   reported by its ROOT: reset_mn_task on every worker of the task                              HQ_FINISH_MN
+          Retracting         reported by the worker it is retracting FROM: try_remove_redirection (reactor.rs:592-604:     HQ_FINISH_RETRACTING
+                             remove_sn_task on the redirect target, if there is a redirect); the library's reading where the
+                             reference draws no state: a task the tick had put back on that very worker (no redirect entry,
+                             mapping.rs:69) gives that entry back, and one that still sat in its queue leaves it
+          any of these reported by another worker (assert_eq!(*w_id, worker_id))                                          HQ_FINISH_WRONG_WORKER
+          Prefilled          (unreachable!)                                                                               HQ_FINISH_PREFILLED
+          a later pair of an id an earlier pair was accepted for, from the same reporter (another one: _WRONG_WORKER)     HQ_FINISH_REPEAT
+          Waiting, finished or not here ("Unknown task finished")                                                        HQ_FINISH_NONE
+        A refused pair changes nothing.  An accepted task is Finished and its consumers lose a dependency (reactor.rs:570-580).
+        Returns the consumers that became ready, in the order they did.  last_finish_kinds: per pair its abi.HQ_FINISH_* kind."""
+        released: List[int] = []
+        accepted_by: Dict[int, int] = {}
+        self.last_finish_kinds: List[int] = []
+        for tid, wid in pairs:
+            if tid in accepted_by:
+                self.last_finish_kinds.append(abi.HQ_FINISH_REPEAT if wid == accepted_by[tid] else abi.HQ_FINISH_WRONG_WORKER)
+                continue
+            t = self.tasks.get(tid)
+            if t is None or t.state in (FINISHED, WAITING):
+                self.last_finish_kinds.append(abi.HQ_FINISH_NONE)
+                continue
+            if t.state == PREFILLED:
+                self.last_finish_kinds.append(abi.HQ_FINISH_PREFILLED)
+                continue
+            if wid != (t.mn_workers[0] if t.state == RUNNING_MN else t.worker):
+                self.last_finish_kinds.append(abi.HQ_FINISH_WRONG_WORKER)
+                continue
+            if t.state in (ASSIGNED, RUNNING):
+                w = self.workers[wid]
+                w.assigned_tasks.discard(tid)
+                self._add(w, t.rq, t.rv)  # remove_sn_task  server/worker.rs:223-234
+                kind = abi.HQ_FINISH_ASSIGNED
+            elif t.state == RUNNING_MN:
+                for w_id in t.mn_workers:
+                    self.workers[w_id].mn_task = None  # reset_mn_task  server/worker.rs:168-171
+                kind = abi.HQ_FINISH_MN
+            else:
+                assert t.state == RETRACTING
+                self._drop_redirection(t)
+                self.ready[t.rq].discard(tid)
+                kind = abi.HQ_FINISH_RETRACTING
+            self.last_finish_kinds.append(kind)
+            accepted_by[tid] = wid
+            t.state = FINISHED
+            for c in t.consumers:
+                ct = self.tasks[c]
+                ct.unfinished_deps -= 1
+                if ct.unfinished_deps == 0 and ct.state == WAITING:
+                    self._add_ready(ct)
+                    released.append(c)
+        return released
+
+    def _drop_redirection(self, t: Task):
+        """try_remove_redirection (reactor.rs:592-604) of a Retracting task; a task the tick put back on the worker it is retracting from holds that worker's
+        resources without a redirect entry (mapping.rs:69) and gives them back here as well (the ledger releases whatever entry the id has)"""
+        if t.id in self.redirects:
+            target, v = self.redirects.pop(t.id)
+            self.workers[target].assigned_tasks.discard(t.id)
+            self._add(self.workers[target], t.rq, v)
+        elif t.id in self.retaken_variant:
+            v = self.retaken_variant.pop(t.id)
+            self.workers[t.worker].assigned_tasks.discard(t.id)
+            self._add(self.workers[t.worker], t.rq, v)
+
+    def start_retracting_task(self, tid: int, wid: int, variant: int = 0) -> bool:
+        """task_running's Retracting arm (server/reactor.rs:311-335): reported by the worker it is retracting from, the task is Running there --
+        try_remove_redirection first, insert_sn_task second.  Any other task or reporter: refused, nothing changes -> False."""
+        t = self.tasks.get(tid)
+        if t is None or t.state != RETRACTING or t.worker != wid:
+            return False
+        self._drop_redirection(t)
+        self.ready[t.rq].discard(tid)
+        w = self.workers[wid]
+        t.state, t.rv = RUNNING, variant
+        self._remove(w, t.rq, variant)
+        w.assigned_tasks.add(tid)
+        return True
+
     # -- bookkeeping used by tests ----------------------------------------------------------------------
     def assigned_counts(self) -> List[int]:
         counts = [0] * len(self.requests)

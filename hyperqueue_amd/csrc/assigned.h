@@ -99,8 +99,14 @@ hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t 
 // CancelTasks message goes to (NONE: none) and an HQ_CANCEL_* kind: the entry's worker, the root of a multi-node task; REPEAT for a later position of an id that
 // has an entry.  The Retracting overrides (ids ascending, the worker id each task is retracting FROM; retr_hit [n_retr] NONE on entry) are matched on the device:
 // the first position of such an id is routed to that worker whatever the ledger names, and retr_hit[k] is that position (NONE: the id is not in the batch).
-struct CancelCols { uint32_t *route; uint8_t *kind; const uint64_t *retr_id; const uint32_t *retr_wid; uint32_t *retr_hit; uint32_t n_retr; };
+struct CancelCols { uint32_t *route; uint8_t *kind; const uint64_t *retr_id; const uint32_t *retr_wid; uint32_t *retr_hit; uint32_t n_retr; const uint32_t *reporter; };
 hipError_t cancel(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
+// hqtick_finish_tasks: the four passes in their finish mode.  cc.reporter [n] is the worker id every position was reported by (cc.route is not
+// used: nobody is told).  finish_core.h's rule gives every position an HQ_FINISH_* kind in cc.kind; only the positions whose reporter is the entry's worker (the
+// root of a multi-node task; for an id of the Retracting overrides the worker it is retracting FROM, whatever the ledger names) may claim, the lowest of them
+// wins, and the tables end as after release(the accepted ids in batch order).  A prefilled entry is never claimed.  retr_hit[k]: the position that claimed
+// override k (NONE: none did).  ctr[C_OUT]: the accepted positions (C_DONE of them left the table; the others are Retracting ids without an entry).
+hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
 // A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
 // out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF)

@@ -1,5 +1,6 @@
 // Kernels of the assignment ledger (assigned.h).  gfx950 only.
 #include "assigned.h"
+#include "finish_core.h"
 
 #include "../../include/hqtick.h"
 
@@ -8,6 +9,7 @@ namespace hqasg {
 namespace {
 
 constexpr uint32_t TPB = 256;
+enum RelMode : int { M_RELEASE = 0, M_CANCEL = 1, M_FINISH = 2 };  // what the release's four passes run as (release / hqtick_cancel_tasks / hqtick_finish_tasks)
 inline unsigned nblk(uint64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 __device__ __forceinline__ uint32_t ht_hash(uint64_t k) {  // murmur3 finaliser (graph.hip's)
@@ -172,13 +174,26 @@ __device__ __forceinline__ uint32_t retr_find(const CancelCols &cc, uint64_t id)
 // release, pass 1: the bucket of every id; the first position of an id in the batch claims it (later ones are duplicates)
 // CANCEL (hqtick_cancel_tasks, the same four passes): a prefilled entry is claimed like the others, every position starts with no route, and the first position
 // of an id of the Retracting overrides claims its override the same way
-template <bool CANCEL>
+// FINISH (hqtick_finish_tasks): finish_core.h's rule decides from the entry, the override and the REPORTER of the position what the position is; only a position
+// with an accepted kind is eligible, and it claims the entry and the override of its id alike -- both atomicMin run over the same eligible positions, so both
+// name the same winner whatever order they arrive in.  A refused position keeps pos NONE: the later passes never see it.
+template <int MODE>
 __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, CancelCols cc, uint32_t *ctr) {
+    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     uint32_t b = NONE;
     if (i < n) {
         b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
-        if (!CANCEL && b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled task is not running: unknown to a release
+        if (MODE == M_RELEASE && b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled task is not running: unknown to a release
+        if (FINISH) {
+            const uint32_t k = retr_find(cc, id[i]), rep = cc.reporter[i];
+            const uint32_t cls = b == NONE ? hqfinish::E_SN : t.variant[b] == PF_VARIANT ? hqfinish::E_PF : t.variant[b] == MN_VARIANT ? hqfinish::E_MN : hqfinish::E_SN;
+            const uint32_t kind = hqfinish::kind_before_claim(b != NONE, cls, b != NONE && t.worker[b] == rep, k != NONE, k != NONE && cc.retr_wid[k] == rep);
+            cc.kind[i] = (uint8_t)kind;
+            if (hqfinish::accepted(kind)) { if (k != NONE) atomicMin(&cc.retr_hit[k], i); }
+            else b = NONE;
+            if (b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled entry is never claimed, not even under a Retracting override
+        }
         pos[i] = b;
         if (b != NONE) atomicMin(&t.claim[b], i);
         if (CANCEL) {
@@ -190,14 +205,15 @@ __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *p
     wave_add(&ctr[C_UNKNOWN], i < n && b == NONE);
 }
 // pass 2: per (worker row, resource) the position + 1 of the batch's last ALL entry
-template <bool CANCEL>
+template <int MODE>
 __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos, uint32_t *last_all, CancelCols cc, uint32_t *ctr) {
+    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool dup = false, bad = false;
     if (b != NONE) {
         const uint32_t row = row_of(r, t.worker[b]);
-        if (t.claim[b] != i) { pos[i] = NONE; dup = true; if (CANCEL) cc.kind[i] = HQ_CANCEL_REPEAT; }
+        if (t.claim[b] != i) { pos[i] = NONE; dup = true; if (CANCEL) cc.kind[i] = HQ_CANCEL_REPEAT; if (FINISH) cc.kind[i] = (uint8_t)hqfinish::after_claim(cc.kind[i], true); }
         else if (t.variant[b] == MN_VARIANT) {}  // a multi-node task: no count, no entry of any resource (its rows are reset by pass 4)
         else if (CANCEL && t.variant[b] == PF_VARIANT) {}  // a prefilled task: no count in a slot, no free row (pass 3 lowers its prefilled count)
         else if (row == NONE) { pos[i] = NONE; bad = true; t.claim[b] = NONE; }  // (left in the table, unclaimed: a later batch finds it as before)
@@ -213,8 +229,11 @@ __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos
 // CANCEL: a prefilled entry lowers its prefilled count instead (k_pf_remove's step); before the entry leaves, its position's route (the row of the entry's
 // worker: the root of a multi-node task) and kind are written.  Then the Retracting overrides: the claiming position is routed to the worker the task is
 // retracting from, whatever the ledger said, and any other position of that id is a repeat.
-template <bool CANCEL>
+// FINISH: the kinds are pass 1's; an eligible position of a Retracting id that did not win its override is a repeat (an id with no ledger entry has no other
+// pass to learn that from).  C_OUT counts the accepted positions: those that leave the table and the Retracting ids that had no entry.
+template <int MODE>
 __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr) {
+    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool mn = false, pf = false;
@@ -242,8 +261,18 @@ __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *
             cc.route[i] = first ? row_of(r, cc.retr_wid[k]) : NONE; cc.kind[i] = first ? HQ_CANCEL_RETRACTING : HQ_CANCEL_REPEAT;
         }
     }
+    bool acc = false;
+    if (FINISH && i < n) {
+        uint32_t kind = cc.kind[i];
+        if (kind == HQ_FINISH_RETRACTING) {
+            const uint32_t k = retr_find(cc, id[i]);
+            if (k == NONE || cc.retr_hit[k] != i) { kind = hqfinish::after_claim(kind, true); cc.kind[i] = (uint8_t)kind; }
+        }
+        acc = hqfinish::accepted(kind);
+    }
     wave_add(&ctr[C_DONE], b != NONE); wave_add(&ctr[C_MN], mn);
     if (CANCEL) wave_add(&ctr[C_PF], pf);
+    if (FINISH) wave_add(&ctr[C_OUT], acc);
 }
 // reset_mn_task (worker.rs:172-175) of a row whose multi-node task has left the table: SN bit set, free row = total row, columns cleared
 __device__ __forceinline__ void mn_reset_row(const Table &t, const Rows &r, const MnRows &m, uint32_t row) {
@@ -455,17 +484,25 @@ hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipSt
 }
 hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim<false>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, CancelCols{}, ctr);
-    hipLaunchKernelGGL(k_rel_last_all<false>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, CancelCols{}, ctr);
-    hipLaunchKernelGGL(k_rel_apply<false>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_claim<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_last_all<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, CancelCols{}, ctr);
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
 hipError_t cancel(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim<true>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
-    hipLaunchKernelGGL(k_rel_last_all<true>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
-    hipLaunchKernelGGL(k_rel_apply<true>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
+    hipLaunchKernelGGL(k_rel_claim<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_last_all<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
+    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
+    return hipGetLastError();
+}
+hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_rel_claim<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_last_all<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }

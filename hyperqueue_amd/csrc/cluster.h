@@ -121,6 +121,14 @@ class Retracting {
     // the ledger as route overrides; cancel() erases one listed task's entry, redirect included (the ledger has released the target's entry: try_remove_redirection)
     void sources(std::vector<uint64_t> *task_id, std::vector<uint32_t> *worker_id) const;
     bool cancel(uint64_t task_id) { return tab.erase(task_id) != 0; }
+    // task_finished / task_running of a Retracting task (reactor.rs:547-556, :311-335; hqtick_finish_tasks, hqtick_retracting_started): what the table holds for
+    // one task -- the worker id it is retracting FROM, and whether it still sits in its queue.  The entry itself leaves through cancel().
+    bool find(uint64_t task_id, uint32_t *old_id, bool *in_queue) const {
+        const auto it = tab.find(task_id);
+        if (it == tab.end()) return false;
+        *old_id = it->second.old_id; *in_queue = it->second.in_queue;
+        return true;
+    }
     void workers_removed(uint32_t n, const uint32_t *worker_id);               // on_remove_worker (ids in any order: sorted here, and only if the table holds a task)
     // the tasks still in a queue as the retracting arrays of a snapshot whose workers are worker_id[0..W)
     int to_snapshot(const uint32_t *worker_id, uint32_t W, hqtick_snapshot *full);

@@ -9,6 +9,7 @@
 #include "audit_core.h"
 #include "cancel_core.h"
 #include "clock_core.h"
+#include "finish_core.h"
 #include "hb_order.h"
 #include "milp.h"
 #include "price_emul.h"
@@ -152,4 +153,14 @@ extern "C" int hqtick_debug_cancel_group(uint32_t n, uint32_t W, const uint32_t 
     uint32_t n_ids = 0;
     if (!hqcancel::group_on_host(n, W, route_row, task_id, worker_id, order, n_workers, &n_ids, out_worker, out_off, out_task)) return HQTICK_E_DEVICE;
     return (int)n_ids;
+}
+// the rule of hqtick_finish_tasks on host arrays: finish_core.h's kind_of per position
+extern "C" int hqtick_debug_finish_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *override_found,
+                                        const uint8_t *override_worker_match, const uint8_t *earlier_accepted, uint8_t *kind) {
+    if (n && (!entry_found || !entry_class || !entry_worker_match || !override_found || !override_worker_match || !earlier_accepted || !kind)) return HQTICK_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (entry_class[i] > hqfinish::E_PF) return HQTICK_E_INVALID;
+        kind[i] = (uint8_t)hqfinish::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, override_found[i] != 0, override_worker_match[i] != 0, earlier_accepted[i] != 0);
+    }
+    return (int)n;
 }

@@ -73,6 +73,9 @@ class Graph {
     int add(uint64_t n, const uint64_t *id, const uint64_t *prio, const uint32_t *rq, const uint32_t *dep_off, const uint64_t *dep_id, hipStream_t s);
     // finish: returns the number of released consumers (sorted by id in out_*()); n_unknown() = ids that were not in the graph.
     int finish(uint64_t n, const uint64_t *id, hipStream_t s);
+    // ... the same for ids that are already in device memory (hqtick_finish_tasks: one staged copy for every step).  dev_kind [n] (nullptr: none): the HQ_FINISH_*
+    // kind of every position, device memory; a position whose kind is not an accepted one is not shown to the graph: neither claimed nor counted as unknown.
+    int finish_device(uint64_t n, const uint64_t *dev_id, const uint8_t *dev_kind, hipStream_t s);
     // remove: the tasks (and, if recursive, their transitive consumers) leave the graph; returns how many left (sorted ids in out_id()).
     int remove(uint64_t n, const uint64_t *id, bool recursive, hipStream_t s);
     // ... the same for ids that are already in device memory (hqtick_cancel_tasks: one staged copy for every step), beside out_id() as ReadySet::remove_device is

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "../../include/hqtick.h"
+#include "finish_core.h"
 
 namespace hqgraph {
 
@@ -198,10 +199,11 @@ __device__ __forceinline__ void release_range(const View &v, uint32_t off, uint3
 
 // task_finished, reactor.rs:510-590, in three steps.
 // (1) one thread per finished id: find it, claim it (exactly once even if listed twice), drop it from the table, recycle its slot
-__global__ void __launch_bounds__(256) k_g_finish_claim(View v, const uint64_t *__restrict__ ids, uint32_t n, uint32_t *__restrict__ slot_of) {
+// kind (hqtick_finish_tasks; nullptr: none): the HQ_FINISH_* kind of every position -- a position that was not accepted is skipped: no slot, no claim, not unknown
+__global__ void __launch_bounds__(256) k_g_finish_claim(View v, const uint64_t *__restrict__ ids, const uint8_t *__restrict__ kind, uint32_t n, uint32_t *__restrict__ slot_of) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     uint32_t slot = NONE; bool unknown = false;
-    if (i < n) {
+    if (i < n && !(kind && !hqfinish::accepted(kind[i]))) {
         uint32_t pos = ht_find_pos(v, ids[i]);
         if (pos != NONE) {
             const uint32_t sl = v.ht_val[pos];
@@ -695,21 +697,31 @@ int Graph::finish(uint64_t n, const uint64_t *id, hipStream_t s) {
     if (!init(s)) return fail(HQTICK_E_DEVICE, "dependency graph: device setup failed");
     if (n_slots == 0) { n_unknown_ = (uint32_t)n; return 0; }
     if (int rc = stage(n, id, s)) return rc;
+    return finish_device(n, d_stage.as<uint64_t>(), nullptr, s);
+}
+
+int Graph::finish_device(uint64_t n, const uint64_t *dev_id, const uint8_t *dev_kind, hipStream_t s) {
+    n_out_ = 0; n_unknown_ = 0;
+    if (n == 0) return 0;
+    if (n > 0x03FFFFFFull) return fail(HQTICK_E_CAPACITY, "more than 2^26 finished tasks in one batch");
+    if (!init(s)) return fail(HQTICK_E_DEVICE, "dependency graph: device setup failed");
+    if (n_slots == 0) { n_unknown_ = dev_kind ? 0u : (uint32_t)n; return 0; }  // (hqtick_finish_tasks calls only a graph that has held a task: resident())
     View v = view();
     Ctl *c = d_ctl.as<Ctl>();
     G_HIP(hipMemsetAsync(&c->n_out, 0, 16, s));  // n_out, n_unknown, err, n_big
     // deferred-run list: one entry per started RUN_CHUNK of a run longer than SHORT_RUN
     const uint64_t big_cap = (uint64_t)edge_top / RUN_CHUNK + (uint64_t)edge_top / SHORT_RUN + 64;
     if (!d_big.ensure(big_cap * sizeof(uint2)) || !d_erk.ensure(n * 4 + 64)) return fail(HQTICK_E_DEVICE, "hipMalloc graph staging");
+    const uint32_t free0 = free_top;
     G_HIP(hipEventRecord(ev0, s));
-    hipLaunchKernelGGL(k_g_finish_claim, dim3(nblk(n)), dim3(256), 0, s, v, d_stage.as<uint64_t>(), (uint32_t)n, d_erk.as<uint32_t>());
+    hipLaunchKernelGGL(k_g_finish_claim, dim3(nblk(n)), dim3(256), 0, s, v, dev_id, dev_kind, (uint32_t)n, d_erk.as<uint32_t>());
     hipLaunchKernelGGL(k_g_finish_release, dim3(nblk(n)), dim3(256), 0, s, v, d_erk.as<uint32_t>(), (uint32_t)n, d_okey.as<uint64_t>(), d_oval.as<uint32_t>(), d_big.as<uint2>(), (uint32_t)big_cap);
     hipLaunchKernelGGL(k_g_big_runs, dim3(BIG_GRID), dim3(256), 0, s, v, d_big.as<uint2>(), d_okey.as<uint64_t>(), d_oval.as<uint32_t>());
     G_HIP(hipEventRecord(ev1, s));
     G_HIP(hipGetLastError());
     if (int rc = finish_output(s, true)) return rc;
     const uint32_t e = h_ctl.as<Ctl>()->err;
-    const uint64_t gone = n - n_unknown_;
+    const uint64_t gone = dev_kind ? (uint64_t)(free_top - free0) : n - n_unknown_;  // (every claimed task recycled its slot; with skipped positions n - unknown counts too many)
     n_live_ -= gone;
     if (e & ERR_CAPACITY) return fail(HQTICK_E_CAPACITY, "dependency graph: deferred-run list overflow");
     if (e & ERR_NOT_READY) return fail(HQTICK_E_INVALID, "hqtick_graph_finish: a finished task still had unfinished dependencies");

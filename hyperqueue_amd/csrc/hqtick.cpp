@@ -100,6 +100,7 @@ struct hqtick_ctx {
     hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
     hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
     PinBuf h_cancel_ids; DevBuf d_cancel_ids; uint64_t cancel_ready_removed = 0;  // hqtick_cancel_tasks: the ids' staging and their one device copy; hqtick_cancel_last_ready_removed
+    PinBuf h_finish_in; DevBuf d_finish_in;  // hqtick_finish_tasks: ids and reporting workers, 12 B per position, staged once and copied to the device once
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     ViewHooks *view_hooks = nullptr;  // hqtick_debug_order_view's scanner and scratch (test library only), allocated on first use; nothing of it is touched on a tick's path
     uint32_t tick_seq = 0;  // the tick counter: moves the block solvers' sample window from tick to tick (host_model.h: Problem::tick_seq)
@@ -673,6 +674,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     ctx->audit.release();
     ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release();
     ctx->h_cancel_ids.release(); ctx->d_cancel_ids.release();
+    ctx->h_finish_in.release(); ctx->d_finish_in.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1197,6 +1199,91 @@ int hqtick_cancel_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint32_t
 }
 
 uint64_t hqtick_cancel_last_ready_removed(const hqtick_ctx *ctx) { return ctx ? ctx->cancel_ready_removed : 0; }
+
+// ---- task_finished in one call: the checks and the order of the steps are here, the steps are the ledger's, the Retracting table's, the graph's and
+// the ready set's.  Ids and reporting workers are staged once in pinned memory (12 B per position) and copied to the device once; every step reads that copy.
+// What is left when a later step fails after an earlier one succeeded: the earlier ones stay done.  After a failed ledger step behind its kernels the accepted
+// entries have left the table and hqtick_finish_last_routes is empty; nothing else was touched, and hqtick_assigned_release of the ids + hqtick_graph_finish finish
+// the job for the ids a host knows to be rightly reported.  After a failed ready-set removal of an in-queue Retracting id (the table step) the ledger and the table
+// are done: hqtick_ready_remove of those ids and hqtick_graph_finish of the accepted ids (hqtick_finish_last_routes names them) finish it.  After a failed graph
+// step the ledger and the table are done and hqtick_graph_finish of the accepted ids finishes it; after a failed ready-set add the graph has released the
+// consumers (hqtick_graph_last_ids names them) and hqtick_ready_add of those finishes it.  A finished task that still had dependencies (HQTICK_E_INVALID from
+// the graph) leaves every step done, its consumers in the ready set included, as hqtick_graph_finish does.
+int hqtick_finish_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id) { return with_audit(ctx, [&]() -> int {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_finish_tasks", n, task_id && worker_id)) return rc;  // (the guard comes before any step: a refused call changes nothing)
+    if (n > 0x03FFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^26 finished tasks in one batch");
+    ctx->asg.finish_out = hqasg::Ledger::FinishOut{}; ctx->asg.last_unknown = 0;
+    if (n == 0) return 0;
+    const size_t o_wid = (size_t)n * 8;
+    if (!ctx->h_finish_in.ensure((size_t)n * 12 + 16) || !ctx->d_finish_in.ensure((size_t)n * 12 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc finish staging");
+    memcpy(ctx->h_finish_in.p, task_id, (size_t)n * 8); memcpy(ctx->h_finish_in.as<unsigned char>() + o_wid, worker_id, (size_t)n * 4);
+    HQ_HIP(hipMemcpyAsync(ctx->d_finish_in.p, ctx->h_finish_in.p, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t *d_ids = ctx->d_finish_in.as<uint64_t>();
+    const uint32_t *d_wid = reinterpret_cast<const uint32_t *>(ctx->d_finish_in.as<unsigned char>() + o_wid);
+    // 1: the ledger's entries and the kinds; the Retracting table's (task, worker it is retracting from) pairs ride along as overrides
+    std::vector<uint64_t> retr_id; std::vector<uint32_t> retr_wid;
+    ctx->retr.sources(&retr_id, &retr_wid);
+    const uint32_t *hit = nullptr;
+    const int accepted = ledger_fail(ctx, ctx->asg.finish(ledger_env(ctx), n, d_ids, d_wid, (uint32_t)retr_id.size(), retr_id.data(), retr_wid.data(), &hit));
+    if (accepted < 0) { ctx->asg.finish_out = hqasg::Ledger::FinishOut{}; return accepted; }
+    // 2: try_remove_redirection's other half: the accepted Retracting tasks leave the table, and the resident ready set if they still sat in their queue
+    std::vector<uint64_t> queued;
+    for (size_t k = 0; hit && k < retr_id.size(); k++) {
+        if (hit[k] == hqasg::NONE) continue;
+        uint32_t old_id = 0; bool in_queue = false;
+        if (ctx->retr.find(retr_id[k], &old_id, &in_queue) && in_queue) queued.push_back(retr_id[k]);
+        ctx->retr.cancel(retr_id[k]);
+    }
+    if (!queued.empty() && ctx->ready.cols().n) { if (int rc = ready_fail(ctx, ctx->ready.remove(ready_env(ctx), queued.size(), queued.data())); rc < 0) return rc; }
+    // 3 / 4: the graph (task_finished's consumers, reactor.rs:570-580) sees the accepted positions alone; the released consumers join the ready set
+    if (accepted > 0 && ctx->graph.resident()) {
+        const int r = ctx->graph.finish_device(n, d_ids, ctx->asg.finish_out.d_kind, ctx->stream);
+        const uint32_t rel = ctx->graph.n_out();  // (also when the call reports ERR_NOT_READY: the graph itself is consistent)
+        if (rel) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), ctx->graph.out_id(), ctx->graph.out_prio(), ctx->graph.out_rq(), rel))) return rc; }
+        if (r < 0) return graph_fail(ctx, r);
+    } else if (ctx->graph.resident()) {
+        ctx->graph.finish_device(0, nullptr, nullptr, ctx->stream);  // (nothing accepted: hqtick_graph_last_ids / _last_unknown answer as after an empty hqtick_graph_finish)
+    }
+    return accepted;
+}); }
+
+int hqtick_finish_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind) {
+    if (!ctx) { if (n) *n = 0; if (kind) *kind = nullptr; return HQTICK_E_INVALID; }
+    if (n) *n = ctx->asg.finish_out.n;
+    if (kind) *kind = ctx->asg.finish_out.kind;
+    return 0;
+}
+
+// task_running's Retracting arm (reactor.rs:311-335): host glue over Ledger::release, Retracting::cancel and Ledger::add, in the reference's order -- the
+// redirect's entry leaves first, so a task the tick had put back on the worker it is retracting from (the dummy redirect) can be entered again.
+int hqtick_retracting_started(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant, const uint64_t *priority) { return with_audit(ctx, [&]() -> int {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_retracting_started", n, task_id && worker_id && rq && variant && priority)) return rc;
+    ctx->asg.last_unknown = 0;
+    if (n == 0) return 0;
+    std::vector<uint64_t> s_id, s_prio, queued; std::vector<uint32_t> s_wid, s_rq; std::vector<uint8_t> s_var;
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t old_id = 0; bool in_queue = false;
+        if (!ctx->retr.find(task_id[i], &old_id, &in_queue) || old_id != worker_id[i]) continue;
+        if (std::find(s_id.begin(), s_id.end(), task_id[i]) != s_id.end()) continue;  // (a later position of a started id: the entry is gone by then)
+        s_id.push_back(task_id[i]); s_wid.push_back(worker_id[i]); s_rq.push_back(rq[i]); s_var.push_back(variant[i]); s_prio.push_back(priority[i]);
+        if (in_queue) queued.push_back(task_id[i]);
+    }
+    const uint32_t m = (uint32_t)s_id.size();
+    if (m) {
+        if (int rc = ledger_fail(ctx, ctx->asg.release(ledger_env(ctx), m, s_id.data())); rc < 0) return rc;  // try_remove_redirection (an id without a redirect has no entry: unknown to the release)
+        for (uint64_t t : s_id) ctx->retr.cancel(t);
+        if (!queued.empty() && ctx->ready.cols().n) { if (int rc = ready_fail(ctx, ctx->ready.remove(ready_env(ctx), queued.size(), queued.data())); rc < 0) return rc; }
+        const int k = ledger_fail(ctx, ctx->asg.add(ledger_env(ctx), m, s_id.data(), s_wid.data(), s_rq.data(), s_var.data(), s_prio.data()));  // insert_sn_task on the old worker
+        if (k < 0) return k;
+        if (ctx->asg.last_unknown) return fail(ctx, HQTICK_E_INVALID, "hqtick_retracting_started: an entry names an unknown worker, request or variant");
+    }
+    ctx->asg.last_unknown = n - m;
+    return (int)m;
+}); }
 
 // The audit of the resident state (audit.h): the views of what this context holds, read through const accessors, handed to hqaudit::Auditor.  Nothing here changes
 // the context: no selection or placement is abandoned, no mirror is synchronised, ctx->err is written only when the call itself fails.

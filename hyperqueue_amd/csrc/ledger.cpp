@@ -8,7 +8,7 @@ namespace hqasg {
 void Ledger::release_all() {
     tab.release(); tab2.release(); for (RowPair *r : {&counts, &mn, &pf}) r->release();
     for (DevBuf &b : buf) b.release();
-    h_ctr.release(); h_in.release(); h_cancel.release();
+    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release();
 }
 void Ledger::take_requests(const hqtick_snapshot *s) {
     const uint32_t Q = s->n_requests;
@@ -377,6 +377,43 @@ int Ledger::cancel(const Env &e, uint32_t n, const uint64_t *d_id, uint32_t n_re
     cancel_out = CancelOut{n, hdr[0], hdr[1], hk.host(o_wid), hk.host(o_off), hk.host(o_id), hk.host(o_rwid), hk.host(o_kind)};
     if (retr_hit) *retr_hit = hk.host(o_hit);
     return (int)hdr[1];
+}
+// task_finished on the ledger (hqtick_finish_tasks): the release's four passes in their finish mode behind one set of counters and ONE
+// synchronisation.  Ids and reporters are read where the caller staged them on the device; the kinds and the override hits come back into pinned memory behind
+// the passes, and the kinds stay on the device for the graph's skip input.
+int Ledger::finish(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit) {
+    last_unknown = 0; finish_out = FinishOut{}; if (retr_hit) *retr_hit = nullptr;
+    if (!n) return 0;
+    if (int rc = sync_req(e)) return rc;
+    const size_t WR = (size_t)e.W * e.R, nr = n_retr;
+    if (!buf[B_SCRATCH].ensure((size_t)n * 4 + WR * 12 + 16) || !buf[B_CANCEL].ensure(nr * 16 + (size_t)n + 64)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    if (!h_finish.ensure(nr * 16 + (size_t)n + 64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc finish kinds");
+    Pack pk{nullptr, buf[B_SCRATCH].as<unsigned char>()};  // [delta W*R u64][pos n u32][last_all W*R u32]
+    uint64_t *d_delta = pk.put<uint64_t>(nullptr, WR); uint32_t *d_pos = pk.put<uint32_t>(nullptr, n), *d_la = pk.put<uint32_t>(nullptr, WR);
+    Pack dk{nullptr, buf[B_CANCEL].as<unsigned char>()};   // [override ids u64][override workers u32] (one copy) [hit u32][kind n u8]
+    uint64_t *d_rid = dk.put<uint64_t>(nullptr, nr); uint32_t *d_rwid = dk.put<uint32_t>(nullptr, nr), *d_hit = dk.put<uint32_t>(nullptr, nr); uint8_t *d_kind = dk.put<uint8_t>(nullptr, n);
+    Pack hk{h_finish.as<unsigned char>(), h_finish.dev<unsigned char>()};  // in: the overrides; out: [hit u32][kind n u8]
+    const uint64_t *h_rid = hk.put(retr_id, nr); hk.put(retr_wid, nr);
+    uint32_t *o_hit = hk.put<uint32_t>(nullptr, nr); uint8_t *o_kind = hk.put<uint8_t>(nullptr, n);
+    HQ_HIP(hipMemsetAsync(d_delta, 0, WR * 8, e.stream));
+    HQ_HIP(hipMemsetAsync(d_la, 0, WR * 4, e.stream));
+    if (nr) {
+        HQ_HIP(hipMemsetAsync(d_hit, 0xFF, nr * 4, e.stream));
+        HQ_HIP(hipMemcpyAsync(d_rid, hk.host(h_rid), nr * 12, hipMemcpyHostToDevice, e.stream));
+    }
+    const CancelCols cc{nullptr, d_kind, d_rid, d_rwid, d_hit, n_retr, d_reporter};
+    if (int rc = counted(e.stream, "hqasg::finish", [&](uint32_t *ctr) {
+            hipError_t r = hqasg::finish(table(), req(), rows(e), mn_rows(mn.cur, e.W, mn_live), n, d_id, d_pos, d_la, d_delta, cc, ctr, e.stream);
+            if (r == hipSuccess) r = hipMemcpyAsync(hk.host(o_kind), d_kind, n, hipMemcpyDeviceToHost, e.stream);
+            if (r == hipSuccess && nr) r = hipMemcpyAsync(hk.host(o_hit), d_hit, nr * 4, hipMemcpyDeviceToHost, e.stream);
+            return r; })) return rc;
+    const uint32_t done = c[C_DONE], done_mn = std::min(c[C_MN], done), accepted = std::min(c[C_OUT], n);
+    if (done_mn) flags_dirty = true;
+    n_live -= done - done_mn; mn_live -= std::min<uint64_t>(done_mn, mn_live); n_tomb += done; last_unknown = n - accepted; dirty_ = true;
+    if (c[C_BAD]) return fail(HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
+    finish_out = FinishOut{n, accepted, hk.host(o_kind), d_kind};
+    if (retr_hit) *retr_hit = hk.host(o_hit);
+    return (int)accepted;
 }
 int Ledger::add_mn(const Env &e, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) {
     last_unknown = 0; if (!n) return 0;

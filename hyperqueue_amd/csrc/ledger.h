@@ -43,6 +43,10 @@ class Ledger {
     // hqtick_cancel_last_*: what the last cancel() wrote into pinned memory (n positions; n_workers messages holding n_ids ids)
     struct CancelOut { uint32_t n = 0, n_workers = 0, n_ids = 0; const uint32_t *worker_id = nullptr, *task_off = nullptr; const uint64_t *task_id = nullptr; const uint32_t *route_wid = nullptr; const uint8_t *route_kind = nullptr; };
     CancelOut cancel_out;
+    // hqtick_finish_last_routes: the kinds the last finish() wrote into pinned memory (n positions, `accepted` of them with an accepted kind); d_kind: the same
+    // kinds where the passes left them on the device (the graph's skip input; valid until the next cancel() or finish())
+    struct FinishOut { uint32_t n = 0, accepted = 0; const uint8_t *kind = nullptr; const uint8_t *d_kind = nullptr; };
+    FinishOut finish_out;
 
     // ---- the C ABI's operations (arguments validated by the caller)
     int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
@@ -52,6 +56,11 @@ class Ledger {
     // ascending.  The tables end as after release(ids) + unprefill(ids); cancel_out holds the messages and routes; *retr_hit [n_retr] (pinned, valid until the next
     // cancel): the batch position that claimed override k, NONE if the id is not listed.  Returns the number of ids in the messages.
     int cancel(const Env &e, uint32_t n, const uint64_t *d_id, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
+    // hqtick_finish_tasks' ledger step: d_id / d_reporter [n] are DEVICE memory (the call's one copy of ids and reporting workers); the Retracting
+    // overrides are host arrays, ids ascending.  The tables end as after release(the accepted ids, batch order); finish_out holds the kinds; *retr_hit [n_retr]
+    // (pinned, valid until the next finish): the batch position that was accepted for override k, NONE if none was.  Returns the number of accepted positions;
+    // last_unknown is the number of refused ones.
+    int finish(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
     int add_mn(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid);
     int mn_workers(const Env &e, uint64_t id, uint32_t *n, const uint32_t **wid);
     int lookup(const Env &e, uint32_t n, const uint64_t *id, uint32_t *wid, uint8_t *var);
@@ -144,7 +153,7 @@ class Ledger {
     // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation,
     // a cancel's routes, overrides and sort scratch
     enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_N }; DevBuf buf[B_N];
-    hqbuf::PinBuf h_ctr, h_in, h_cancel;  // (h_cancel: a cancel's overrides in, its lists and routes out)
+    hqbuf::PinBuf h_ctr, h_in, h_cancel, h_finish;  // (h_cancel: a cancel's overrides in, its lists and routes out; h_finish: a finish's overrides in, its kinds out)
     const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
     uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones
     uint32_t stride = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)

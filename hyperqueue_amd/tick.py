@@ -481,6 +481,35 @@ class Tick:
                 "route_worker": abi._np(rw, k, np.uint32).copy() if k else np.zeros(0, np.uint32), "route_kind": abi._np(rk, k, np.uint8).copy() if k else np.zeros(0, np.uint8),
                 "ready_removed": int(r(self._ctx)), "closure": self._graph_last_ids(), "graph_unknown": int(self._lib.hqtick_graph_last_unknown(self._ctx))}
 
+    # -- task_finished in one call (include/hqtick.h) --------------------------------------------------------
+    def finish_tasks(self, task_id, worker_id) -> dict:
+        """hqtick_finish_tasks for the (id, reporting worker) pairs, in this order -> {"accepted": positions accepted (need_scheduling), "kind": per batch position
+        the HQ_FINISH_* kind, "released": hqtick_graph_last_ids (the consumers that joined the ready set), "graph_unknown": hqtick_graph_last_unknown}"""
+        t = np.ascontiguousarray(task_id, np.uint64); w = np.ascontiguousarray(worker_id, np.uint32)
+        assert len(t) == len(w)
+        f = self._lib.hqtick_finish_tasks
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p]
+        accepted = self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p)))
+        n = C.c_uint32(); pk = abi.u8p()
+        g = self._lib.hqtick_finish_last_routes
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pk)))
+        self._lib.hqtick_graph_last_unknown.restype = C.c_uint64
+        self._lib.hqtick_graph_last_unknown.argtypes = [C.c_void_p]
+        return {"accepted": int(accepted), "kind": abi._np(pk, n.value, np.uint8).copy() if n.value else np.zeros(0, np.uint8),
+                "released": self._graph_last_ids(), "graph_unknown": int(self._lib.hqtick_graph_last_unknown(self._ctx))}
+
+    def retracting_started(self, started) -> int:
+        """hqtick_retracting_started for [(task, worker id it runs on, rq, variant, priority)]: task_running of Retracting tasks -> number started"""
+        started = list(started)
+        t = np.ascontiguousarray([e[0] for e in started], np.uint64); w = np.ascontiguousarray([e[1] for e in started], np.uint32)
+        q = np.ascontiguousarray([e[2] for e in started], np.uint32); v = np.ascontiguousarray([e[3] for e in started], np.uint8)
+        p = np.ascontiguousarray([e[4] for e in started], np.uint64)
+        f = self._lib.hqtick_retracting_started
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u32p, abi.u8p, abi.u64p]
+        return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), q.ctypes.data_as(abi.u32p), v.ctypes.data_as(abi.u8p),
+                           p.ctypes.data_as(abi.u64p)))
+
     # -- device-resident dependency graph (include/hqtick.h, SURVEY §8 f1) --------------------------------------------------
     def _graph_last_ids(self) -> np.ndarray:
         n = C.c_uint64()

@@ -640,6 +640,48 @@ int hqtick_cancel_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint32_t
 uint64_t hqtick_cancel_last_ready_removed(const hqtick_ctx *ctx);
 
 /*
+ * Finishing tasks on the resident state in one call (functions added under ABI 12): task_finished (server/reactor.rs:510-590) for a batch of
+ * WorkerTaskUpdate::Finished, in the order the reactor saw them, on everything the context keeps resident.  Ids and reporting workers are staged once (12 B per
+ * position); the ledger and the graph read that one copy.
+ *   hqtick_finish_tasks   worker_id[i] is the worker whose TaskUpdates carried the finish of task_id[i]; a batch may mix workers.  It needs a resident ready set
+ *       and an enabled ledger; the graph and the prefilled tracking are optional.  Every position gets an HQ_FINISH_* kind.  _ASSIGNED, _MN and _RETRACTING are
+ *       ACCEPTED: the reporter is the worker of the single-node entry, the root of the multi-node entry, or -- for an id in the table of hqtick_retracting_* -- the
+ *       worker the task is retracting FROM (the table decides, whatever the ledger names: its entry is the redirect target's).  Every other kind is REFUSED and
+ *       changes nothing anywhere: _NONE (no entry and not in the table: "Unknown task finished"), _WRONG_WORKER (the reference's assert_eq!(*w_id, worker_id)),
+ *       _PREFILLED (unreachable! in the reference), _REPEAT (a later position of an id an earlier position was accepted for).  A refused position claims
+ *       nothing: a later position of the same id with the right worker is still accepted.  The state afterwards, for the accepted positions in batch order:
+ *       ledger      as hqtick_assigned_release(accepted ids) leaves it: the last-ALL rule, multi-node rows reset, SN bits back.  For a Retracting id with a
+ *                   redirect this releases the entry on the redirect target (try_remove_redirection, reactor.rs:592-604); one the tick had put back on the
+ *                   worker it is retracting from gives that entry back.
+ *       Retracting  accepted _RETRACTING ids leave the table of hqtick_retracting_*; one that still sat in its queue leaves the resident ready set too.
+ *       graph       with a graph (one that has held a task): as hqtick_graph_finish(accepted ids) leaves it -- released consumers join the resident ready set, and
+ *                   hqtick_graph_last_ids / _last_unknown answer as after that call.  A refused position is not shown to the graph.  An accepted task that still
+ *                   had dependencies is HQTICK_E_INVALID as there: its consumers still join the ready set and the ledger step stays done.
+ *     Returns the number of accepted positions (the handler's need_scheduling); hqtick_assigned_last_unknown is the number of refused ones.  HQTICK_E_INVALID
+ *     without a resident ready set, with the ledger off, with a two-call tick's placement pending or with a NULL array (nothing changes then); HQTICK_E_CAPACITY
+ *     for n > 2^26; n = 0 returns 0 and leaves an empty kind list.  If a step fails after an earlier one succeeded the earlier ones stay done (the ledger first,
+ *     then the table, then graph and ready set): hqtick_graph_finish of the accepted ids finishes the job.
+ *   hqtick_finish_last_routes   per batch position its HQ_FINISH_* kind: pinned memory owned by the context, valid until the next hqtick_finish_tasks.  Nobody
+ *       is told about a finish, so there are no worker lists; a host needs the kinds for its own task objects and to log what the reference asserts.
+ *   hqtick_retracting_started   task_running's Retracting arm (reactor.rs:311-335): for every id that is in the table with worker_id[i] the worker it is retracting
+ *       FROM, the redirect target's ledger entry is released if there is one, the table entry is erased (with the id's place in the resident ready set, if it
+ *       still sat in its queue), and the task is entered on worker_id[i] with (rq, variant, priority) as by hqtick_assigned_add -- in this order, so a task the
+ *       tick had put back on that very worker can be entered again.  Other ids are refused, change nothing and are counted in hqtick_assigned_last_unknown.
+ *       Returns the number started; the guards are those of hqtick_finish_tasks.
+ */
+#define HQ_FINISH_NONE         0
+#define HQ_FINISH_ASSIGNED     1
+#define HQ_FINISH_MN           2
+#define HQ_FINISH_RETRACTING   3
+#define HQ_FINISH_REPEAT       4
+#define HQ_FINISH_WRONG_WORKER 5
+#define HQ_FINISH_PREFILLED    6
+int hqtick_finish_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id);
+int hqtick_finish_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind);
+int hqtick_retracting_started(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint32_t *rq, const uint8_t *variant,
+                              const uint64_t *priority);
+
+/*
  * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
  * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
  * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.

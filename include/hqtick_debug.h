@@ -255,6 +255,14 @@ int hqtick_debug_audit_host(const hqtick_debug_audit_tables *tables, uint32_t pa
  * HQTICK_E_INVALID for a NULL argument or an order outside 0..2.  Not a product path. */
 int hqtick_debug_cancel_group(uint32_t n, uint32_t W, const uint32_t *route_row, const uint64_t *task_id, const uint32_t *worker_id, int order, uint32_t *n_workers,
                               uint32_t *out_worker, uint32_t *out_off, uint64_t *out_task);
+
+/* The decision rule of hqtick_finish_tasks (csrc/finish_core.h, the function the finish mode of the ledger's release passes calls per position) on HOST arrays,
+ * one entry per evaluated position: entry_found (the ledger has an entry for the id), entry_class (0 single-node, 1 multi-node, 2 prefilled), entry_worker_match
+ * (the reporter is the entry's worker / root), override_found (the id is in the Retracting table), override_worker_match (the reporter is the worker it is
+ * retracting from), earlier_accepted (an earlier position of the batch was accepted for the id).  kind [n]: the HQ_FINISH_* kinds.  Returns n, HQTICK_E_INVALID
+ * for a NULL array or a class above 2.  Not a product path. */
+int hqtick_debug_finish_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *override_found,
+                             const uint8_t *override_worker_match, const uint8_t *earlier_accepted, uint8_t *kind);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
