@@ -176,10 +176,12 @@ struct Counts {
     }
     size_t key_size(size_t k) const { return pairs_built ? per_key[k].size() : lists[key_list[k]].widx.size(); }  // workers of key k
     // Problem::defer_row_check: the counts come from a point the sweeps certified whose check against the model's rows has not run yet.  The model (moved here, not
-    // copied) and the point live on until settle_row_check(); false = the counts are void, solve again with Problem::no_fast_path.
-    struct PendingRowCheck { hqmilp::Model model; hqmilp::RowCheck check; } row_check;
+    // copied) and the point live on until settle_row_check(); false = the counts are void, solve again with Problem::no_fast_path.  The verdict stays with the
+    // counts (row_check_failed), so that whoever settled the check — the caller, or what it handed the check to — need not carry it back.
+    struct PendingRowCheck { hqmilp::Model model; hqmilp::RowCheck check; bool failed = false; } row_check;
     bool row_check_pending() const { return row_check.check.pending; }
-    bool settle_row_check() { return hqmilp::run_row_check(row_check.model, row_check.check); }
+    bool row_check_failed() const { return row_check.failed; }
+    bool settle_row_check() { row_check.failed = !hqmilp::run_row_check(row_check.model, row_check.check); return !row_check.failed; }
     bool is_optimal = true;
     bool is_canonical = true;  // every solve completed its tie-break phase
     bool empty() const {

@@ -11,12 +11,12 @@
 //   D2H   assignment records
 // The stages live in modules of their own, each behind a class that owns its buffers and takes a small Env: the ready set (ready.h), phase A (scan.h), the worker
 // set (cluster.h), the ledger (ledger.h), the placement's solvers and the ranks' exchange (solve.h; what needs no HIP in solve_core.h), the mapping plan and phase C
-// (map.h; the plan itself, free of HIP, in map_core.h).  This file keeps the context, the sequence of a tick (TickRun::run) and the C ABI's argument checks.
+// (map.h; the plan itself, free of HIP, in map_core.h).  The host stages between them — the snapshot's checks, the Problem, the queue levels, the batches' export,
+// the plan's input and stage sequence, the row check's retry, a query's tail — are tick_core.h's, free of HIP and shared with the test hooks.  The context's layout
+// is ctx.h's.  This file keeps the sequence of a tick (TickRun::run), the two queries and the C ABI's argument checks; the test library's hooks on a context live
+// in debug_tick.cpp, so that both libraries link this file's one object.
 // There is no CPU implementation of the scans or of the selection and the records: without a HIP device every entry point fails.
 #include "../../include/hqtick.h"
-#ifdef HQTICK_TEST_HOOKS
-#include "../../include/hqtick_debug.h"
-#endif
 
 #include <hip/hip_runtime.h>
 
@@ -29,22 +29,8 @@
 #include <string>
 #include <vector>
 
-#include "audit.h"
-#include "cluster.h"
-#include "ready.h"
-#include "scan.h"
-#include "solve.h"
-#ifdef HQTICK_TEST_HOOKS
-#include "price_emul.h"
-#endif
-#include "devbuf.h"
-#include "graph.h"
-#include "ledger.h"
-#include "map.h"
-#include "host_model.h"
-#include "kernels.h"
+#include "ctx.h"
 
-using hqbuf::DevBuf;
 using hqbuf::PinBuf;
 using hqcluster::UpView;
 using hqscan::Scan;
@@ -53,150 +39,6 @@ using hqscan::WorkerEval;
 namespace {
 
 double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-}  // namespace
-
-namespace {
-// The ordered view by itself (hqtick_debug_order_view and the two hooks that run on the view it built): a scanner of its own, so that the context keeps its
-// permutation, its pending selection and its cached level table; what is known of that view; the hooks' scratch in HBM.
-struct ViewHooks {
-    hqscan::Scanner scan;
-    bool valid = false; const void *ids = nullptr; uint64_t N = 0; uint32_t Q = 0, n_live = 0; bool rq_copy = false; std::vector<uint32_t> run_off, run_start, run_rank;
-    DevBuf d_map, d_sel_task, d_sel_rank, d_rq, d_want;  // the selection's tables and output, the copy of the request column hqtick_debug_order_select marks, the ids hqtick_debug_order_rank_of looks up
-    void release() { scan.release(); d_map.release(); d_sel_task.release(); d_sel_rank.release(); d_rq.release(); d_want.release(); }
-};
-}  // namespace
-
-struct hqtick_ctx {
-    hqtick_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // K2 (worker evaluation: PCIe-latency-bound reads of the worker tables) runs here, next to K1 + K1b on `stream`
-    bool k2_on_hist = false;       // HQTICK_K2_RIDE_ALONG=1: K2 rides along K1's launch (round 1 / first half of round 2); default: along K1b's
-    bool k2_own_stream = false;    // HQTICK_K2_RIDE_ALONG=0: K2 as its own launch on stream2.  Measured (profiles/r02/README.md): K1 alone then takes 4.8 us instead of
-                                   // 8.2 us (0.31 vs 0.18 of the HBM roofline), but the second stream's launch + synchronisation make phase A 36 us instead of 28 us:
-                                   // the ride-along layout stays the default because the TICK is what counts
-    hipEvent_t ev[14] = {};  // (ev[12] / ev[13]: around the kernels of the ordered view)
-    std::string err = "";
-    hqready::ReadySet ready;       // hqtick_upload_ready, hqtick_ready_* (ready.h): the ready set's columns in HBM (resident, or a tick's own), their deltas, the last selection's state
-    hqscan::Scanner scan;          // GPU phase A (scan.h): the dense scan with its cached level table, the ordered view, the census — on the query sub-context, a query's
-    hqsolve::Solver solver;        // the placement (solve.h): the block solvers' staging and knobs, the price sweeper, the block memo, the ranks' exchange and communicator
-    hqmap::Mapper map;             // the mapping plan and GPU phase C (map.h): the plan's buffers, the records, the result's host part, the last selection's launch state
-    bool timing = true, timing_k1 = false;  // (timing_k1: events around K1 alone, hqtick_set_kernel_timing(ctx, 2))
-    PinBuf h_up, h_up2, h_q;
-    hqcluster::WorkerSet ws;      // hqtick_cluster_* (ABI 5 and 7; cluster.h): the worker / request tables resident in HBM and their host mirror
-    hqcluster::Retracting retr;   // hqtick_retracting_* (ABI 7): the table of Retracting tasks
-    uint32_t last_row_groups = 0; // hqtick_cluster_last_row_groups
-    bool wait_on_kernel = true;   // HQ_HIP_LAST; HQTICK_WAIT_ON_KERNEL=0: hipStreamSynchronize at every wait (A/B)
-    bool defer_row_check = true;  // the coupled fast path's row check runs while phase C's kernels do; HQTICK_DEFER_ROW_CHECK=0: inside the solve (A/B)
-    hqhost::Problem pb;
-    // results (host)
-    std::vector<uint32_t> b_rq, b_size, b_limit, b_cut_off, c_size, c_bl_off, bl_rq, bl_size; std::vector<uint8_t> b_lr, b_blk;
-    std::vector<uint8_t> q_loaded;
-    hqtick_kernel_stats stats{};
-    uint32_t tpw_hint = 0;                            // HQTICK_TPW (tuning knob): tasks per wavefront slice
-    uint32_t shard_index = 0, shard_count = 1;       // hqtick_set_shard
-    void *sink = nullptr; size_t sink_bytes = 0;      // hqtick_set_record_sink (device memory)
-    hqgraph::Graph graph;  // hqtick_graph_*: dependency counters + consumer lists in HBM
-    hqasg::Ledger asg;     // hqtick_assigned_* (ABI 12; ledger.h)
-    PinBuf h_cancel_ids; DevBuf d_cancel_ids; uint64_t cancel_ready_removed = 0;  // hqtick_cancel_tasks: the ids' staging and their one device copy; hqtick_cancel_last_ready_removed
-    PinBuf h_finish_in; DevBuf d_finish_in;  // hqtick_finish_tasks: ids and reporting workers, 12 B per position, staged once and copied to the device once
-    hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
-    ViewHooks *view_hooks = nullptr;  // hqtick_debug_order_view's scanner and scratch (test library only), allocated on first use; nothing of it is touched on a tick's path
-    uint32_t tick_seq = 0;  // the tick counter: moves the block solvers' sample window from tick to tick (host_model.h: Problem::tick_seq)
-    double tl[32] = {}; int ntl = 0;  // debug timeline (us since tick start), hqtick_timeline()
-    hqaudit::Auditor audit;  // hqtick_resident_check (audit.h): nothing of it exists until the first call
-    bool check_resident = false; int audit_depth = 0;  // HQTICK_CHECK_RESIDENT=1: the audit behind every call that changes resident state (audit_depth: inside such a call)
-};
-
-namespace {
-
-#define HQ_HIP(call)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return HQTICK_E_DEVICE; } \
-    } while (0)
-
-// a launch wrapper that was handed a timer (hqk::time_next_launch) but returned without launching must not leave it to the next launch
-#define HQ_HIP_TIMED(call)                                                                                    \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        hqk::take_launch_timer();                                                                             \
-        if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return HQTICK_E_DEVICE; } \
-    } while (0)
-
-// The last launch of a phase carries a stop event (hipExtLaunchKernel: the dispatch's own completion signal), and the host waits on THAT instead of
-// hipStreamSynchronize, which submits a marker packet of its own and returns 5.6 us after the kernel is done where the kernel's signal is seen after 2.8 us
-// (tools/exp/launch_latency.hip, MI355X / ROCm 7.2).  `launched` = the wrapper really launched (it consumed the pending timer); otherwise the
-// caller falls back to the stream.
-#define HQ_HIP_LAST(call, launched)                                                                           \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        (launched) = hqk::take_launch_timer().stop == nullptr && ctx->wait_on_kernel;                        \
-        if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return HQTICK_E_DEVICE; } \
-    } while (0)
-
-int fail(hqtick_ctx *ctx, int code, const std::string &msg) { ctx->err = msg; return code; }
-
-#ifdef HQTICK_TEST_HOOKS
-// duration between two dispatch events in us, or -1 when the pair was not recorded (hqtick_time_kernel's calibration; the runtime's error state is cleared)
-double elapsed_us(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, a, b) == hipSuccess) return (double)ms * 1000.0;
-    (void)hipGetLastError();
-    return -1.0;
-}
-#endif
-
-int validate(hqtick_ctx *ctx, const hqtick_snapshot *s, bool need_tasks) {
-    if (!s) return fail(ctx, HQTICK_E_INVALID, "null snapshot");
-    if (s->n_workers && (!s->worker_id || !s->worker_total || !s->worker_free)) return fail(ctx, HQTICK_E_INVALID, "worker arrays missing");
-    for (uint32_t w = 1; w < s->n_workers; w++) if (s->worker_id[w - 1] >= s->worker_id[w]) return fail(ctx, HQTICK_E_INVALID, "worker ids not ascending");
-    if (s->n_requests && (!s->rq_variant_off || !s->variant_entry_off)) return fail(ctx, HQTICK_E_INVALID, "request arrays missing");
-    for (uint32_t q = 0; q < s->n_requests; q++) {
-        if (s->rq_variant_off[q + 1] <= s->rq_variant_off[q]) return fail(ctx, HQTICK_E_INVALID, "request without variants");
-        if (s->rq_variant_off[q + 1] - s->rq_variant_off[q] > 32) return fail(ctx, HQTICK_E_INVALID, "more than 32 variants");
-    }
-    uint32_t nv = s->n_requests ? s->rq_variant_off[s->n_requests] : 0;
-    for (uint32_t e = 0; e < (nv ? s->variant_entry_off[nv] : 0); e++) {
-        if (s->entry_resource[e] >= s->n_resources) return fail(ctx, HQTICK_E_INVALID, "entry resource id out of range");
-        if (s->entry_kind[e] == HQ_ENTRY_AMOUNT && s->entry_amount[e] == 0) return fail(ctx, HQTICK_E_INVALID, "zero amount request");
-    }
-    if (need_tasks && s->n_ready) {
-        if (!s->task_id || !s->task_priority || !s->task_rq) return fail(ctx, HQTICK_E_INVALID, "ready-set columns missing");
-        for (uint64_t i = 1; i < s->n_ready; i++) if (s->task_id[i - 1] >= s->task_id[i]) return fail(ctx, HQTICK_E_INVALID, "ready set not sorted by task id");
-    }
-    if (s->n_blocked && (!s->blocked_worker || !s->blocked_rq || !s->blocked_variant)) return fail(ctx, HQTICK_E_INVALID, "blocked arrays missing");
-    for (uint32_t k = 0; k < s->n_blocked; k++) {
-        if (s->blocked_worker[k] >= s->n_workers) return fail(ctx, HQTICK_E_INVALID, "blocked worker index");
-        if (s->blocked_rq[k] >= s->n_requests) return fail(ctx, HQTICK_E_INVALID, "blocked request id out of range");
-        if (s->blocked_variant[k] >= s->rq_variant_off[s->blocked_rq[k] + 1] - s->rq_variant_off[s->blocked_rq[k]]) return fail(ctx, HQTICK_E_INVALID, "blocked variant out of range");
-    }
-    if (s->worker_group) for (uint32_t w = 0; w < s->n_workers; w++) if (s->worker_group[w] >= (s->n_groups ? s->n_groups : 1)) return fail(ctx, HQTICK_E_INVALID, "worker_group >= n_groups");
-    // CSR offsets: monotone, and their arrays present.  (The ENTRIES of assigned_* are checked where they are dereferenced — the gap rows of a
-    // tick with priority cuts, host_model.cpp — so that the common tick does not pay a pass over every running task.)
-    if (s->assigned_off) {
-        for (uint32_t w = 0; w < s->n_workers; w++) if (s->assigned_off[w] > s->assigned_off[w + 1]) return fail(ctx, HQTICK_E_INVALID, "assigned_off not monotone");
-        if (s->n_workers && s->assigned_off[s->n_workers] && (!s->assigned_rq || !s->assigned_variant)) return fail(ctx, HQTICK_E_INVALID, "assigned arrays missing");
-    }
-    if (s->prefilled_off) {
-        for (uint32_t w = 0; w < s->n_workers; w++) if (s->prefilled_off[w] > s->prefilled_off[w + 1]) return fail(ctx, HQTICK_E_INVALID, "prefilled_off not monotone");
-        if (s->n_workers && s->prefilled_off[s->n_workers] && !s->prefilled_rq) return fail(ctx, HQTICK_E_INVALID, "prefilled_rq missing");
-    }
-    if (s->prefill_off) {
-        for (uint32_t q = 0; q < s->n_requests; q++) if (s->prefill_off[q] > s->prefill_off[q + 1]) return fail(ctx, HQTICK_E_INVALID, "prefill_off not monotone");
-        const uint32_t np = s->n_requests ? s->prefill_off[s->n_requests] : 0;
-        if (np && (!s->prefill_priority || !s->prefill_task || !s->prefill_worker)) return fail(ctx, HQTICK_E_INVALID, "prefill arrays missing");
-        for (uint32_t i = 0; i < np; i++) if (s->prefill_worker[i] >= s->n_workers) return fail(ctx, HQTICK_E_INVALID, "prefill worker index");
-    }
-    if (s->n_retracting && (!s->retracting_task || !s->retracting_worker)) return fail(ctx, HQTICK_E_INVALID, "retracting arrays missing");
-    for (uint32_t k = 0; k < s->n_retracting; k++) {
-        if (s->retracting_worker[k] >= s->n_workers) return fail(ctx, HQTICK_E_INVALID, "retracting worker index");
-        if (k && s->retracting_task[k - 1] >= s->retracting_task[k]) return fail(ctx, HQTICK_E_INVALID, "retracting tasks not ascending");
-        if (s->retracting_redirect_worker && s->retracting_redirect_worker[k] != HQ_NO_WORKER && s->retracting_redirect_worker[k] >= s->n_workers) return fail(ctx, HQTICK_E_INVALID, "retracting redirect worker index");
-    }
-    return 0;
-}
 
 // Packs worker tables + request tables (cluster.h: TabLayout) into ONE pinned, device-mapped staging buffer that K2 reads in place (every byte
 // crosses PCIe once per workgroup; no H2D copy command).
@@ -212,13 +54,6 @@ int upload_tables(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const u
     return 0;
 }
 
-// ... or from HBM, where a worker set is resident (hqcluster::WorkerSet::tables)
-int cluster_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->ws.err; return rc; }
-
-// the ready set (hqready::ReadySet, ready.h): what it is given of the context (ev[11]: the completion event an append's dispatch carries), and its errors
-hqready::Env ready_env(hqtick_ctx *ctx) { return hqready::Env{ctx->device, ctx->stream, ctx->ev[11], ctx->wait_on_kernel}; }
-int ready_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->ready.err; return rc; }
-
 // K2 on a worker set, synchronous (used for the fake workers of hqtick_query); results land in pinned memory
 int eval_workers_sync(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, const uint64_t *total, const uint64_t *free_, const int64_t *rem, WorkerEval *out) {
     UpView uv; int rc;
@@ -231,54 +66,6 @@ int eval_workers_sync(hqtick_ctx *ctx, const hqtick_snapshot *s, uint32_t W, con
     HQ_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
-
-void fill_problem(hqhost::Problem &pb, const hqtick_snapshot *s, const hqtick_config &cfg, const WorkerEval &ev) {
-    pb.R = s->n_resources; pb.n_groups = s->n_groups ? s->n_groups : 1; pb.time_limit_s = cfg.mip_time_limit_s; pb.certificate_only = (cfg.flags & HQTICK_FLAG_CERTIFICATE_ONLY) != 0;
-    uint32_t nv = s->n_requests ? s->rq_variant_off[s->n_requests] : 0;
-    pb.rqs.resize(s->n_requests); pb.variants.resize(nv);
-    for (uint32_t q = 0; q < s->n_requests; q++) pb.rqs[q] = {s->rq_variant_off[q], s->rq_variant_off[q + 1] - s->rq_variant_off[q]};
-    for (uint32_t v = 0; v < nv; v++) {
-        uint32_t e0 = s->variant_entry_off[v];
-        pb.variants[v] = {s->entry_resource + e0, s->entry_kind + e0, s->entry_amount + e0, s->variant_entry_off[v + 1] - e0,
-                          s->variant_n_nodes ? s->variant_n_nodes[v] : 0, s->variant_weight ? s->variant_weight[v] : 10000,
-                          s->variant_min_time_ns ? s->variant_min_time_ns[v] : 0};
-    }
-    hqhost::WorkerSet &ws = pb.real;
-    ws.n = s->n_workers; ws.R = s->n_resources; ws.id = s->worker_id; ws.total = s->worker_total; ws.free_ = s->worker_free;
-    ws.remaining_ns = s->worker_remaining_ns; ws.min_util = s->worker_min_utilization; ws.flags = s->worker_flags; ws.group = s->worker_group;
-    ws.vflags = ev.flags; ws.vtmc = ev.tmc; ws.n_variant_slots = nv;
-    if (ws.blocked.size() != ws.n || ws.n_blocked_lists) { ws.blocked.assign(ws.n, {}); ws.n_blocked_lists = 0; }  // (4096 empty lists re-made per tick cost more than the batches stage)
-    ws.assigned_off = s->assigned_off; ws.assigned_rq = s->assigned_rq; ws.assigned_variant = s->assigned_variant;
-    ws.agg_off = nullptr; ws.agg_rq = nullptr; ws.agg_cnt = nullptr; ws.agg_variant = nullptr;
-    for (uint32_t k = 0; k < s->n_blocked; k++) ws.blocked[s->blocked_worker[k]].push_back({s->blocked_rq[k], s->blocked_variant[k]});
-    ws.n_blocked_lists = s->n_blocked;
-    hqhost::group_equal_rows(ws, false);  // needs nothing of K2's output: in a tick this runs while the GPU works on phase A
-}
-
-void export_batches(hqtick_ctx *ctx, const std::vector<hqhost::TaskBatch> &batches, hqtick_result *out) {
-    ctx->b_rq.clear(); ctx->b_size.clear(); ctx->b_limit.clear(); ctx->b_lr.clear(); ctx->b_blk.clear();
-    ctx->b_cut_off.assign(1, 0); ctx->c_size.clear(); ctx->c_bl_off.assign(1, 0); ctx->bl_rq.clear(); ctx->bl_size.clear();
-    for (auto &b : batches) {
-        ctx->b_rq.push_back(b.rq); ctx->b_size.push_back(b.size); ctx->b_limit.push_back(b.limit); ctx->b_lr.push_back(b.limit_reached); ctx->b_blk.push_back(b.is_blocker);
-        for (auto &c : b.cuts) {
-            ctx->c_size.push_back(c.size);
-            for (auto &bl : c.blockers) { ctx->bl_rq.push_back(bl.first); ctx->bl_size.push_back(bl.second); }
-            ctx->c_bl_off.push_back((uint32_t)ctx->bl_rq.size());
-        }
-        ctx->b_cut_off.push_back((uint32_t)ctx->c_size.size());
-    }
-    out->n_batches = (uint32_t)ctx->b_rq.size(); out->batch_rq = ctx->b_rq.data(); out->batch_size = ctx->b_size.data(); out->batch_limit = ctx->b_limit.data();
-    out->batch_limit_reached = ctx->b_lr.data(); out->batch_is_blocker = ctx->b_blk.data(); out->batch_cut_off = ctx->b_cut_off.data();
-    out->cut_size = ctx->c_size.data(); out->cut_blocker_off = ctx->c_bl_off.data(); out->blocker_rq = ctx->bl_rq.data(); out->blocker_size = ctx->bl_size.data();
-}
-
-// GPU phase A (hqscan::Scanner, scan.h): what it is given of the context (ev[0] / ev[1] around K0, ev[2] / ev[3] around K1, ev[8] K1b's completion, ev[12] / ev[13]
-// around the kernels of the ordered view), and its errors
-hqscan::Env scan_env(hqtick_ctx *ctx) {
-    return hqscan::Env{ctx->stream, ctx->stream2, ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->ev[8], ctx->ev[12], ctx->ev[13],
-                       ctx->timing, ctx->timing_k1, ctx->wait_on_kernel, ctx->k2_on_hist, ctx->k2_own_stream, ctx->tpw_hint};
-}
-int scan_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->scan.err; return rc; }
 
 // K2's tables for the scanner: from HBM where a worker set is resident, else packed from the snapshot
 struct TablesOf { hqtick_ctx *ctx; const hqtick_snapshot *s; };
@@ -303,35 +90,7 @@ int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc,
     return scan_fail(ctx, rc);
 }
 
-// TaskQueue::iter_priority_sizes (taskqueue.rs:273-302) for every request, from the histogram and the prefill sets
-std::vector<hqhost::QueueLevels> queue_levels(const Scan &sc, const hqtick_snapshot *s) {
-    std::vector<hqhost::QueueLevels> qs(s->n_requests);
-    for (uint32_t q = 0; q < s->n_requests; q++) {
-        auto &lv = qs[q].levels;
-        for (uint32_t r = sc.run_off[q]; r < sc.run_off[q + 1]; r++) lv.push_back({sc.run_prio[r], sc.run_cnt[r]});
-        uint32_t pfn = s->prefill_off ? s->prefill_off[q + 1] - s->prefill_off[q] : 0;
-        if (pfn) {
-            uint64_t pp = s->prefill_priority[q];
-            if (!lv.empty() && lv[0].first == pp) lv[0].second += pfn; else lv.insert(lv.begin(), {pp, pfn});
-        }
-    }
-    return qs;
-}
-
-// The placement (hqsolve::Solver, solve.h): what it is given of the context (ev[9] / ev[10] around k_block_solve — ev[10] is its completion, which the host waits
-// on), and its errors
-hqsolve::Env solve_env(hqtick_ctx *ctx) { return hqsolve::Env{ctx->device, ctx->stream, ctx->ev[9], ctx->ev[10], ctx->timing, ctx->wait_on_kernel, ctx->shard_index, ctx->shard_count}; }
-int solver_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->solver.err; return rc; }
 bool is_replica(hqtick_ctx *ctx) { return ctx->solver.replica(solve_env(ctx)); }  // others read this context's sweeps or records (a record sink alone is one scheduler's output path)
-
-// The mapping (hqmap::Mapper, map.h): what it is given of the context (ev[4] / ev[5] around K4, ev[1] / ev[6] around K5a, ev[7] / ev[11] around K5b — ev[11] is K5b's
-// completion, which the host waits on), and its errors
-hqmap::Env map_env(hqtick_ctx *ctx, double t0 = 0) {
-    return hqmap::Env{ctx->stream, ctx->ev[4], ctx->ev[5], ctx->ev[1], ctx->ev[6], ctx->ev[7], ctx->ev[11], ctx->timing, ctx->wait_on_kernel, ctx->cfg.flags,
-                      ctx->sink, ctx->sink_bytes, ctx->shard_index, ctx->shard_count, hqmap::Timeline{t0, ctx->tl, &ctx->ntl}};
-}
-int map_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->map.err; return rc; }
-bool transpose_enabled() { const char *e = getenv("HQTICK_TRANSPOSE"); return !(e && atoi(e) == 0); }
 
 // One tick, stage by stage: run() is the only entry point and mirrors run_scheduling_inner (scheduler/main.rs:50-72).  The plan's stages are map_core.h's, on the
 // mapper's plan (no per-tick allocation in the steady state); phase C is the mapper's.
@@ -347,7 +106,6 @@ struct TickRun {
         : ctx(c), s(snap), out(o), use_resident(resident), ps(c->map.plan), pb(c->pb), W(snap->n_workers), R(snap->n_resources), Q(snap->n_requests) {}
 
     void mark() { hqmap::Timeline{t0, ctx->tl, &ctx->ntl}.mark(); }
-    int plan_fail(int rc, const char *why) { if (rc) ctx->err = why; return rc; }
 
     // the ready set: uploaded with the snapshot, or already resident
     int load_ready_set() {
@@ -359,19 +117,15 @@ struct TickRun {
         return 0;
     }
 
-    // what the plan reads (map_core.h): the scan, the counts, the snapshot, and of the context plain values
+    // what the plan reads (map_core.h): hqstages::plan_in, and of the context the sink, the shard, the ledger's prefilled counts and the plan's storage
     hqmap::PlanIn plan_in() {
-        hqmap::PlanIn in{};
-        in.sc = &sc; in.cnt = &cnt; in.s = s; in.rqs = pb.rqs.data(); in.variants = pb.variants.data();
-        in.proactive_filling_reserve = ctx->cfg.proactive_filling_reserve; in.proactive_filling_max = ctx->cfg.proactive_filling_max; in.flags = ctx->cfg.flags;
+        hqmap::PlanIn in = hqstages::plan_in(sc, cnt, s, pb, ctx->cfg, N, ctx->scan.retracting_keys(), ctx->scan.retracting_ranks());
         in.sink = ctx->sink != nullptr; in.shard_index = ctx->shard_index; in.shard_count = ctx->shard_count;
-        in.N = N; in.retr_key = ctx->scan.retracting_keys(); in.retr_rank = ctx->scan.retracting_ranks();
         if (ctx->asg.on && ctx->asg.tracking()) {  // the ledger's prefilled counts (its sync_mirror brought them back; a snapshot with prefilled_off was refused)
             uint32_t pf_stride = 0;
             const std::vector<uint32_t> &h_pf = ctx->asg.prefilled_host(&pf_stride);
             if (h_pf.size() >= (size_t)W * pf_stride) { in.ledger_pf = h_pf.data(); in.ledger_pf_stride = pf_stride; }
         }
-        in.transpose_on = transpose_enabled();
         in.storage = hqmap::Mapper::plan_storage; in.user = &ctx->map;  // the big tables are built in the pinned buffer K4's ride-along workgroups copy from
         return in;
     }
@@ -429,13 +183,13 @@ struct TickRun {
         if (ctx->cfg.flags & HQTICK_FLAG_NO_TICK_CACHES) { ctx->scan.columns_changed(); hqhost::flush_tick_caches(); }  // nothing derived survives from the last tick
         memset(out, 0, sizeof(*out));
         ctx->stats = hqtick_kernel_stats{};
-        int rc = validate(ctx, s, !use_resident);
+        int rc = hqstages::validate(s, !use_resident, ctx->err);
         if (rc) return rc;
         HQ_HIP(hipSetDevice(ctx->device));
         if ((rc = load_ready_set())) return rc;
         // ---------------- GPU phase A ----------------
         const std::function<void()> prep = [&]() {   // request/worker views: no GPU output needed yet
-            fill_problem(pb, s, ctx->cfg, ev);
+            hqstages::fill_problem(pb, s, ctx->cfg, ev);
             ctx->last_row_groups = (uint32_t)pb.real.rows.rep.size();
             if (ctx->asg.on && !s->assigned_off) {  // the ledger's per-worker (rq, variant) counts
                 const hqasg::Agg g = ctx->asg.agg();
@@ -449,19 +203,18 @@ struct TickRun {
         mark();  // 0: phase A done
         const double t1 = now_us();
         // ---------------- host: batches + placement ----------------
-        std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
+        std::vector<hqhost::QueueLevels> qlv = hqstages::queue_levels(sc, s);
         std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-        export_batches(ctx, batches, out);
+        hqstages::export_batches(batches, ctx->batches, out);
         mark();  // 1: batches
         const double t2 = now_us();
-        // Solve, plan and phase C.  They run twice in one case only: the placement came from the fast path with its row check deferred into phase C's window (below)
-        // and the check failed — then once more with the fast path off, which is what the inline check's failure leads to.
+        // Solve, plan and phase C.  They run twice in one case only (hqstages::with_row_check): the placement came from the fast path with its row check deferred into
+        // phase C's window (below) and the check failed — then once more with the fast path off, which is what the inline check's failure leads to.
         const hqmap::Env me = map_env(ctx, t0);
         const uint32_t tick_seq = ctx->tick_seq++;
         const int ntl_solve = ctx->ntl;
         double t3 = t2;
-        bool check_ok = true;
-        const std::function<void()> check = [&]() { if (cnt.row_check_pending()) check_ok = cnt.settle_row_check(); };
+        const std::function<void()> check = [&]() { if (cnt.row_check_pending()) cnt.settle_row_check(); };  // (the verdict stays with the counts)
         auto solve_plan_map = [&](bool defer, bool classic) -> int {
             int rc;
             hqsolve::Stats st;
@@ -486,28 +239,24 @@ struct TickRun {
             hqmap::HostResult &hr = ctx->map.res;
             const char *why = nullptr;
             ctx->ready.selection_void();  // the previous tick's plan is overwritten from here on: hqtick_ready_consume_last refers to THIS tick or to none (if it fails)
-            if ((rc = plan_fail(hqmap::plan_keys(ps, hr, in, &why), why))) return rc;
-            if ((rc = map_fail(ctx, ctx->map.launch_sweep_early(me)))) return rc;
-            if ((rc = plan_fail(hqmap::plan_redirects(ps, hr, in, &why), why))) return rc;
-            mark();  // 3: key tables + retracts
-            if ((rc = plan_fail(hqmap::plan_prefill(ps, hr, in, &why), why))) return rc;
-            mark();  // 4: prefill plan
-            if ((rc = plan_fail(hqmap::plan_outputs(ps, hr, in, &why), why))) return rc;
-            if ((rc = map_fail(ctx, ctx->map.check_capacity(sc.ordered)))) return rc;
-            mark();  // 5: K5 tables
+            rc = hqstages::plan_stages(ps, hr, in, &why, [&](int stage) -> int {
+                if (stage == 0) return map_fail(ctx, ctx->map.launch_sweep_early(me));  // K5a's sweep over the key tables, while the host plans on
+                if (stage == 3) { if (int crc = map_fail(ctx, ctx->map.check_capacity(sc.ordered))) return crc; }
+                mark();  // 3: key tables + retracts, 4: prefill plan, 5: K5 tables
+                return 0;
+            });
+            if (rc) { if (why) ctx->err = why; return rc; }  // (a stage's refusal carries its text; the mapper has left its own)
             // ---------------- GPU phase C ----------------
             return phase_c(me, in, defer && cnt.row_check_pending() ? &check : nullptr);
         };
-        rc = solve_plan_map(may_defer_row_check(), false);
-        check();  // (a pass that did not reach phase C's window: the check decides all the same whether its result, an error included, stands)
-        if (!check_ok) {
-            // What the inline check's failure leads to: the classic path's placement.  The discarded pass has left nothing but buffers the second one overwrites
-            // (may_defer_row_check: no tombstones, no ledger staging, no sink) and the selection's launch state, which goes.
+        // What a failed check leads to is what the inline check's failure does: the classic path's placement.  The discarded pass has left nothing but buffers the
+        // second one overwrites (may_defer_row_check: no tombstones, no ledger staging, no sink) and the selection's launch state, which goes.
+        rc = hqstages::with_row_check(cnt, may_defer_row_check(), solve_plan_map, [&]() -> int {
             HQ_HIP(hipStreamSynchronize(ctx->stream));
             ctx->ready.selection_void(); ctx->map.forget_selection();
-            ctx->ntl = ntl_solve; cnt = hqhost::Counts();
-            rc = solve_plan_map(false, true);
-        }
+            ctx->ntl = ntl_solve;
+            return 0;
+        });
         if (rc) return rc;
         mark();  // 8: phase C synced
         finish(me, t1, t2, t3);
@@ -515,13 +264,6 @@ struct TickRun {
     }
 };
 
-// ---------------------------------------------------------------------------------------------- assignment ledger (ABI 12): what hqasg::Ledger (ledger.h) is given of the context
-hqasg::Env ledger_env(hqtick_ctx *ctx) {
-    const hqready::Cols c = ctx->ready.cols();
-    return hqasg::Env{ctx->device, ctx->stream, ctx->ws.rows(), ctx->ws.W(), ctx->ws.R(), c.id, c.prio, c.rq, c.n,
-                      ctx->scan.levels_dev(), &ctx->ws.ids(), ctx->ws.flags(), ctx->ws.free_rows()};
-}
-int ledger_fail(hqtick_ctx *ctx, int rc) { if (rc < 0) ctx->err = ctx->asg.err; return rc; }
 // a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
 // (an add, a remove, a compaction, a graph call, an upload) ends ready.selection_live() — and with it the placement is dropped too: Ledger::pending is read nowhere
 // but here, so the ready set need not know the ledger to clear it
@@ -874,7 +616,7 @@ int hqtick_graph_get_stats(const hqtick_ctx *ctx, hqtick_graph_stats *out) {
 int hqtick_cluster_upload(hqtick_ctx *ctx, const hqtick_snapshot *s) { return with_audit(ctx, [&]() -> int {
     if (!ctx || !s) return HQTICK_E_INVALID;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, HQTICK_E_NO_DEVICE, "hipSetDevice failed");
-    if (int rc = validate(ctx, s, false)) return rc;
+    if (int rc = hqstages::validate(s, false, ctx->err)) return rc;
     if (int rc = cluster_fail(ctx, ctx->ws.upload(ctx->stream, s))) return rc;
     ctx->asg.on = false; ctx->asg.pending = false;  // a new worker set: the ledger is enabled (seeded) again for it
     ctx->asg.take_requests(s);
@@ -1344,24 +1086,13 @@ int hqtick_ready_compact(hqtick_ctx *ctx) { return with_audit(ctx, [&]() -> int 
 
 extern "C" {
 
-// The tail of both queries, on the sub-context: the model over the fake workers K2 has evaluated (fresh: free == total), batches from the scan's runs, the solve, and
-// which of the fake workers it loaded  (query.rs:73-81)
+// The tail of both queries, on the sub-context (hqstages::query_tail), with the sub-context's solver: no deferred check, no forced classic path, no memo
 static int solve_on_fake_workers(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, const WorkerEval &ev_real, const WorkerEval &ev_fake, const Scan &sc,
                                  hqtick_query_result *out) {
-    const uint32_t Q = s->n_requests;
-    hqhost::Problem pb;
-    fill_problem(pb, s, ctx->cfg, ev_real);
-    hqhost::WorkerSet fw;
-    hqsolve::fake_worker_set(fw, fake, s->n_resources, ev_fake.flags, ev_fake.tmc, Q ? s->rq_variant_off[Q] : 0);
-    hqhost::group_equal_rows(fw, true);
-    pb.custom = &fw;
-    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
-    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    hqhost::Counts cnt = ctx->solver.solve(solve_env(ctx), pb, batches, hqsolve::Opts{false, false, 0, false}, nullptr);
-    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    hqsolve::loaded_flags(cnt, fake->n_workers, ctx->q_loaded);
-    out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
-    return 0;
+    auto solve = [&](hqhost::Problem &pb, const std::vector<hqhost::TaskBatch> &batches) {
+        return ctx->solver.solve(solve_env(ctx), pb, batches, hqsolve::Opts{false, false, 0, false}, nullptr);
+    };
+    return hqstages::query_tail(ctx->cfg, s, fake, ev_real, ev_fake, sc, solve, ctx->q_loaded, out, ctx->err);
 }
 
 // The what-if query runs on the live Core between two ticks (crates/tako/src/control.rs:125-155): it must not disturb what the ctx keeps
@@ -1383,7 +1114,7 @@ int hqtick_query(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_w
     return rc;
 }
 static int query_on(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtick_query_workers *fake, hqtick_query_result *out) {
-    int rc = validate(ctx, s, true);
+    int rc = hqstages::validate(s, true, ctx->err);
     if (rc) return rc;
     HQ_HIP(hipSetDevice(ctx->device));
     if ((rc = ready_fail(ctx, ctx->ready.load(ctx->stream, s, false)))) return rc;  // (the query reads no task id)
@@ -1412,7 +1143,7 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
     sub.n_ready = 0; sub.task_id = nullptr; sub.task_priority = nullptr; sub.task_rq = nullptr;
     sub.prefill_off = nullptr; sub.prefill_priority = nullptr; sub.prefill_task = nullptr; sub.prefill_worker = nullptr;
     sub.n_retracting = 0; sub.retracting_task = nullptr; sub.retracting_worker = nullptr; sub.retracting_redirect_worker = nullptr; sub.retracting_redirect_variant = nullptr;
-    if (int rc = validate(ctx, &sub, false)) return rc;
+    if (int rc = hqstages::validate(&sub, false, ctx->err)) return rc;
     const uint32_t Q = s->n_requests;
     if (s->prefill_off) {   // (queue_levels reads the sizes and priorities of the prefill sets)
         for (uint32_t q = 0; q < Q; q++) if (s->prefill_off[q] > s->prefill_off[q + 1]) return fail(ctx, HQTICK_E_INVALID, "prefill_off not monotone");
@@ -1436,324 +1167,6 @@ int hqtick_query_resident(hqtick_ctx *ctx, const hqtick_snapshot *s, const hqtic
     if (rc < 0) ctx->err = q->err;
     return rc;
 }
-
-#ifdef HQTICK_TEST_HOOKS
-// ---- libhqtick_test.so only (include/hqtick_debug.h): CPU hooks for the test suite.  Not compiled into libhqtick.so. ----
-namespace {
-thread_local int g_block_emulation = 0, g_price_emulation = 0; thread_local uint32_t g_price_min_cols = 0, g_last_price_sweeps = 0, g_last_price_rounds = 0;
-thread_local uint32_t g_block_budget = 4096, g_last_blocks_device = 0, g_last_blocks_host = 0;
-thread_local uint32_t g_block_verify = 2, g_tick_seq = 0, g_last_guard[3] = {0, 0, 0}; thread_local int g_corrupt_mode = 0; thread_local uint32_t g_corrupt_class = 0, g_corrupt_fill = 0;
-thread_local double g_last_stage_us[3] = {0, 0, 0};
-}  // namespace
-
-void hqtick_debug_set_block_guard(uint32_t verify, uint32_t tick_seq, int corrupt_mode, uint32_t corrupt_class, uint32_t corrupt_fill) {
-    g_block_verify = verify; g_tick_seq = tick_seq; g_corrupt_mode = corrupt_mode; g_corrupt_class = corrupt_class; g_corrupt_fill = corrupt_fill;
-}
-void hqtick_debug_last_block_guard(uint32_t *verified, uint32_t *mismatch, uint32_t *rejected) {
-    if (verified) *verified = g_last_guard[0]; if (mismatch) *mismatch = g_last_guard[1]; if (rejected) *rejected = g_last_guard[2];
-}
-thread_local hqhost::BlockMemo *g_memo = nullptr; thread_local uint32_t g_last_memo = 0;
-void hqtick_debug_set_block_memo(int on) { if (on && !g_memo) g_memo = new hqhost::BlockMemo(); if (!on) { delete g_memo; g_memo = nullptr; } }
-uint32_t hqtick_debug_last_block_memo(void) { return g_last_memo; }
-void hqtick_debug_set_price_emulation(int on, uint32_t min_cols) { g_price_emulation = on; g_price_min_cols = min_cols; }
-void hqtick_debug_set_fast_path(int on) { hqmilp::set_fast_path(on); }
-void hqtick_debug_check_model_hints(int on) { hqprice::set_check_hints(on != 0); }
-int hqtick_debug_model_hint_mismatches(void) { return hqprice::hint_mismatches(); }
-thread_local int g_price_fault = -1;
-void hqtick_debug_set_price_fault(int fail_at) { g_price_fault = fail_at; }
-// the host stages as ONE RANK of a sharded scheduler: emulated sweeps / class blocks over this rank's share, completed through `fn` (tests/test_sharded.py: gloo)
-thread_local hqtick_exchange_fn g_xfn = nullptr; thread_local void *g_xuser = nullptr; thread_local uint32_t g_xrank = 0, g_xworld = 1, g_xmin_blocks = 1, g_xmin_classes = 1, g_xcalls = 0;
-void hqtick_debug_set_exchange(hqtick_exchange_fn fn, void *user, uint32_t rank, uint32_t world, uint32_t min_blocks, uint32_t min_classes) {
-    g_xfn = fn; g_xuser = user; g_xrank = rank; g_xworld = world ? world : 1; g_xmin_blocks = min_blocks; g_xmin_classes = min_classes;
-}
-uint32_t hqtick_debug_last_exchange_calls(void) { return g_xcalls; }
-void hqtick_debug_last_stage_us(double *out3) { if (out3) for (int i = 0; i < 3; i++) out3[i] = g_last_stage_us[i]; }
-void hqtick_debug_last_price(uint32_t *sweeps, uint32_t *rounds) { if (sweeps) *sweeps = g_last_price_sweeps; if (rounds) *rounds = g_last_price_rounds; }
-static thread_local std::vector<uint32_t> g_last_mn_rq, g_last_mn_off{0}, g_last_mn_worker;
-uint32_t hqtick_debug_last_mn(const uint32_t **rq, const uint32_t **off, const uint32_t **worker) {
-    if (rq) *rq = g_last_mn_rq.data();
-    if (off) *off = g_last_mn_off.data();
-    if (worker) *worker = g_last_mn_worker.data();
-    return (uint32_t)g_last_mn_rq.size();
-}
-uint32_t hqtick_debug_clock_launches(const hqtick_ctx *ctx) { return ctx ? ctx->ws.clock_launches() : 0u; }
-int hqtick_debug_last_order(const hqtick_ctx *ctx, uint32_t *n_runs, uint32_t *n_levels, double *order_us) {
-    if (!ctx) return HQTICK_E_INVALID;
-    const hqscan::Scanner::View &v = ctx->scan.last_view();
-    if (n_runs) *n_runs = v.valid ? v.runs : 0;
-    if (n_levels) *n_levels = v.valid ? v.levels : 0;
-    if (order_us) *order_us = v.valid ? v.us : 0.0;
-    return v.valid ? 1 : 0;
-}
-int hqtick_debug_last_scan(const hqtick_ctx *ctx, int which, uint32_t *n_levels, uint32_t *n_groups, uint32_t shape[4], uint64_t *levels, uint32_t cap_levels, uint32_t *hist,
-                           uint32_t cap_groups) {
-    if (!ctx || (which != 0 && which != 1)) return HQTICK_E_INVALID;
-    if (which == 1 && !ctx->qctx) return 0;
-    const hqscan::Scanner::Dense d = which == 0 ? ctx->scan.last_dense() : ctx->qctx->scan.last_census();  // what the last dense scan / the last census (on the query sub-context) left
-    if (!d.valid) return 0;
-    if (n_levels) *n_levels = d.L;
-    if (n_groups) *n_groups = d.G;
-    if (shape) for (int i = 0; i < 4; i++) shape[i] = d.shape[i];
-    if (levels) for (uint32_t i = 0; i < d.L && i < cap_levels; i++) levels[i] = d.levels[i];
-    if (hist) for (uint32_t i = 0; i < d.G && i < cap_groups; i++) hist[i] = d.hist[i];
-    return 1;
-}
-// The ordered view by itself ("The view hooks"): built by a scanner of its own (ViewHooks), so that ctx keeps its permutation, its pending selection, its
-// sticky flag and its level table; every device array comes back by one copy, here and nowhere on a tick's path.
-int hqtick_debug_order_view(hqtick_ctx *ctx, uint32_t n_requests, uint32_t counts[4], uint32_t *perm, uint32_t *inv, uint32_t *lrank, uint64_t cap_slots, uint32_t *run_rq,
-                            uint32_t *run_start, uint32_t *run_rank, uint64_t *run_prio, uint32_t cap_runs) {
-    if (!ctx || !counts) return HQTICK_E_INVALID;
-    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set (hqtick_upload_ready)");
-    HQ_HIP(hipSetDevice(ctx->device));
-    if (!ctx->view_hooks) {
-        ctx->view_hooks = new ViewHooks();
-        if (int rc = ctx->view_hooks->scan.init()) { delete ctx->view_hooks; ctx->view_hooks = nullptr; return fail(ctx, rc, "creating the view sub-context failed"); }
-    }
-    ViewHooks *v = ctx->view_hooks;
-    const hqready::Cols cols = ctx->ready.cols(); const uint64_t N = cols.n;
-    v->valid = false; v->rq_copy = false;
-    for (int i = 0; i < 4; i++) counts[i] = 0;
-    Scan sc;
-    hqscan::Env env{}; env.stream = ctx->stream;  // (untimed)
-    if (int rc = v->scan.view(env, cols, n_requests, &sc)) return fail(ctx, rc, v->scan.err);
-    const uint32_t nr = (uint32_t)sc.run_cnt.size(), n = nr ? sc.run_start.back() + sc.run_cnt.back() : 0u;
-    if ((nr != 0) != v->scan.last_view().valid) return fail(ctx, HQTICK_E_DEVICE, "ordered view: the run table and the debug record disagree");
-    counts[0] = n; counts[1] = nr; counts[2] = sc.L; counts[3] = v->scan.last_view().passes;
-    if (n > cap_slots || N > cap_slots || nr > cap_runs) return fail(ctx, HQTICK_E_CAPACITY, "hqtick_debug_order_view: output arrays too small");
-    if (n) {
-        if (perm) HQ_HIP(hipMemcpy(perm, v->scan.perm(), (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (inv) HQ_HIP(hipMemcpy(inv, v->scan.inv(), (size_t)N * 4, hipMemcpyDeviceToHost));
-        if (lrank) HQ_HIP(hipMemcpy(lrank, v->scan.level_ranks(N), (size_t)N * 4, hipMemcpyDeviceToHost));
-        const hqscan::OrderTabLayout tl = hqscan::order_tab_layout(n);  // (the run table is in pinned host memory already: the view has synchronised)
-        const uint8_t *hh = v->scan.run_table();
-        if (run_rq) memcpy(run_rq, hh + tl.o_rq, (size_t)nr * 4);
-        if (run_start) memcpy(run_start, hh + tl.o_st, (size_t)nr * 4);
-        if (run_rank) memcpy(run_rank, hh + tl.o_rk, (size_t)nr * 4);
-        if (run_prio) memcpy(run_prio, hh + tl.o_pr, (size_t)nr * 8);
-    }
-    v->ids = cols.id; v->N = N; v->Q = n_requests; v->n_live = n;
-    v->run_off = std::move(sc.run_off); v->run_start = std::move(sc.run_start); v->run_rank = std::move(sc.run_level);
-    v->valid = true;
-    return 0;
-}
-
-namespace {
-// the view hqtick_debug_order_view last built, if ctx's columns are still the ones it was built on
-ViewHooks *debug_view_of(hqtick_ctx *ctx) {
-    ViewHooks *v = ctx->view_hooks;
-    if (!v || !v->valid || !ctx->ready.resident() || v->ids != ctx->ready.cols().id || v->N != ctx->ready.cols().n) return nullptr;
-    return v;
-}
-}  // namespace
-
-// k_order_select on that view.  mark_mode 0: select; 1: consume (RQ_TOMBSTONE at the selected slots, nothing selected); 2: restore (the request ids back, nothing
-// selected); 3: consume and select in one launch (HQTICK_FLAG_CONSUME_IN_TICK).  The marks go to a copy of the rq column — a fresh one for modes 0, 1 and 3, the copy as the
-// previous call left it for mode 2 — never to ctx's column.  The plan is checked on the host before the launch: no destination outside its request's range.
-int hqtick_debug_order_select(hqtick_ctx *ctx, const uint32_t *rq_sel_base, const uint32_t *q_tnc, uint32_t n_sel, int mark_mode, uint64_t *sel_task, uint32_t *sel_rank,
-                              uint32_t *rq_after, uint32_t *err) {
-    if (!ctx || !rq_sel_base || !q_tnc || !sel_task || !sel_rank || !err || mark_mode < 0 || mark_mode > 3) return HQTICK_E_INVALID;
-    ViewHooks *v = debug_view_of(ctx);
-    if (!v) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: no view of the current ready set (hqtick_debug_order_view)");
-    const uint32_t Q = v->Q, n = v->n_live, nr = (uint32_t)v->run_start.size();
-    const uint64_t N = v->N;
-    if (Q == 0 || n_sel == 0 || n == 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: nothing to select from");
-    if (rq_sel_base[0] != 0 || rq_sel_base[Q] != n_sel) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: rq_sel_base does not span [0, n_sel]");
-    for (uint32_t q = 0; q < Q; q++) {
-        if (rq_sel_base[q] > rq_sel_base[q + 1]) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: rq_sel_base not monotone");
-        const uint32_t take = rq_sel_base[q + 1] - rq_sel_base[q], nw = q_tnc[q] >> 16, c = q_tnc[q] & 0xFFFFu;
-        if (!q_tnc[q]) continue;
-        if (nw == 0) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: worker-major form without workers");
-        for (uint32_t p = 0; p < take && p < nw * c; p++)
-            if ((uint64_t)(p % nw) * c + p / nw >= take) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: a worker-major destination leaves its request's range");
-    }
-    if (mark_mode == 2 && !v->rq_copy) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_select: restore needs the copy a consume left");
-    HQ_HIP(hipSetDevice(ctx->device));
-    // the tables in HBM, as a tick's plan carries them: [rq_sel_base Q + 1][run_off Q + 1][q_tnc Q][run_start nr][run_rank nr]
-    std::vector<uint32_t> tab;
-    tab.insert(tab.end(), rq_sel_base, rq_sel_base + Q + 1);
-    tab.insert(tab.end(), v->run_off.begin(), v->run_off.end());
-    tab.insert(tab.end(), q_tnc, q_tnc + Q);
-    tab.insert(tab.end(), v->run_start.begin(), v->run_start.end());
-    tab.insert(tab.end(), v->run_rank.begin(), v->run_rank.end());
-    if (!v->d_map.ensure(tab.size() * 4 + 16) || !v->d_sel_task.ensure((size_t)n_sel * 8 + 16) || !v->d_sel_rank.ensure((size_t)n_sel * 4 + 16) || !v->d_rq.ensure(N * 4 + 8))
-        return fail(ctx, HQTICK_E_DEVICE, "hipMalloc view selection");
-    HQ_HIP(hipMemcpy(v->d_map.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-    uint32_t *derr = v->scan.select_err_dev();
-    HQ_HIP(hipMemsetAsync(derr, 0, 4, ctx->stream));
-    HQ_HIP(hipMemsetAsync(v->d_sel_task.p, 0xFF, (size_t)n_sel * 8, ctx->stream));   // the sentinel: a j the kernel did not write stays 0xFF..FF
-    HQ_HIP(hipMemsetAsync(v->d_sel_rank.p, 0xFF, (size_t)n_sel * 4, ctx->stream));
-    if (mark_mode != 2) { HQ_HIP(hipMemcpyAsync(v->d_rq.p, ctx->ready.cols().rq, N * 4, hipMemcpyDeviceToDevice, ctx->stream)); v->rq_copy = true; }
-    const uint32_t *d = v->d_map.as<uint32_t>();
-    hqk::OrderSelect os{};
-    os.task_id = ctx->ready.cols().id; os.perm = v->scan.perm(); os.n_live = n; os.Q = Q; os.n_runs = nr;
-    os.rq_sel_base = d; os.run_off = d + (Q + 1); os.q_tnc = d + 2 * (size_t)(Q + 1); os.run_start = os.q_tnc + Q; os.run_rank = os.run_start + nr;
-    os.sel_task = v->d_sel_task.as<uint64_t>(); os.sel_rank = v->d_sel_rank.as<uint32_t>(); os.err = derr;
-    if (mark_mode) { os.mark_rq = v->d_rq.as<uint32_t>(); os.mark_value = mark_mode == 2 ? 0u : hqk::RQ_TOMBSTONE; os.mark_and_select = mark_mode == 3 ? 1u : 0u; }
-    HQ_HIP(hqk::order_select(os, n_sel, ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    HQ_HIP(hipMemcpy(sel_task, v->d_sel_task.p, (size_t)n_sel * 8, hipMemcpyDeviceToHost));
-    HQ_HIP(hipMemcpy(sel_rank, v->d_sel_rank.p, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
-    if (rq_after) HQ_HIP(hipMemcpy(rq_after, v->d_rq.p, N * 4, hipMemcpyDeviceToHost));
-    HQ_HIP(hipMemcpy(err, derr, 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// k_order_rank_of on that view: (request, position in the view) of the wanted ids against ctx's id and rq columns; 0xFFFFFFFF twice = not a live task of the set
-int hqtick_debug_order_rank_of(hqtick_ctx *ctx, const uint64_t *want, uint32_t n_want, uint32_t *out_rq, uint32_t *out_pos) {
-    if (!ctx || (n_want && (!want || !out_rq || !out_pos))) return HQTICK_E_INVALID;
-    ViewHooks *v = debug_view_of(ctx);
-    if (!v) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_order_rank_of: no view of the current ready set (hqtick_debug_order_view)");
-    if (n_want == 0) return 0;
-    if (v->n_live == 0) { for (uint32_t i = 0; i < n_want; i++) out_rq[i] = out_pos[i] = 0xFFFFFFFFu; return 0; }  // (as phase A: no view, no launch)
-    HQ_HIP(hipSetDevice(ctx->device));
-    if (!v->d_want.ensure((size_t)n_want * 16 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc wanted ids");
-    uint8_t *dw = v->d_want.as<uint8_t>();
-    HQ_HIP(hipMemcpy(dw, want, (size_t)n_want * 8, hipMemcpyHostToDevice));
-    HQ_HIP(hqk::order_rank_of(ctx->ready.cols().id, ctx->ready.cols().rq, v->N, v->scan.inv(), reinterpret_cast<const uint64_t *>(dw), n_want,
-                              reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 8), reinterpret_cast<uint32_t *>(dw + (size_t)n_want * 12), ctx->stream));
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    HQ_HIP(hipMemcpy(out_rq, dw + (size_t)n_want * 8, (size_t)n_want * 4, hipMemcpyDeviceToHost));
-    HQ_HIP(hipMemcpy(out_pos, dw + (size_t)n_want * 12, (size_t)n_want * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-void hqtick_debug_set_block_emulation(int on, uint32_t budget) { g_block_emulation = on; if (budget) g_block_budget = budget; }
-void hqtick_debug_last_blocks(uint32_t *n_emulated, uint32_t *n_host) { if (n_emulated) *n_emulated = g_last_blocks_device; if (n_host) *n_host = g_last_blocks_host; }
-
-int hqtick_debug_block_solve_host(uint32_t n_cols, uint32_t n_resources, const uint32_t *ent_off, const uint32_t *ent_res, const uint8_t *ent_kind, const uint64_t *ent_amount,
-                                  const uint32_t *weight, const double *pool, uint32_t n_classes, const uint64_t *free_, const uint64_t *total, const uint64_t *elig,
-                                  uint32_t budget, uint32_t *x, uint32_t *status, uint32_t *steps) {
-    hqblock::ColTable ct{n_cols, n_resources, ent_off, ent_res, ent_kind, ent_amount, weight, pool, nullptr, 0};
-    hqblock::ClassTable cl{n_classes, free_, total, elig};
-    hqblock::Output out{x, status, steps, nullptr};
-    hqsolve::EmulatedBlocks emu(budget ? budget : 4096);
-    return emu.solve(ct, cl, out) ? 0 : HQTICK_E_DEVICE;
-}
-
-// Test hooks (include/hqtick_debug.h): the host stages on caller-supplied scan outputs.  No device is touched.  with_plan: the five stages of the mapping plan
-// (map_core.h) behind the solver, on the Retracting tasks' (key, rank) arrays of the dense form, the plan's big tables in a heap block.
-static uint32_t *heap_storage(void *vec, size_t words) { auto *v = static_cast<std::vector<uint32_t> *>(vec); v->assign(words, 0); return v->data(); }
-static int host_stages(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels, const uint64_t *levels,
-                       const uint32_t *hist, bool with_plan, const uint32_t *retr_key, const uint32_t *retr_rank, hqtick_result *out, std::string *err) {
-    if (!config || !s || !out) return HQTICK_E_INVALID;
-    struct KeepError { hqtick_ctx *c; std::string *e; ~KeepError() { if (e) *e = c->err; } };  // the refusal's text, for the hook that hands it out
-    static thread_local hqtick_ctx *holder = nullptr;  // owns the result arrays; never creates a stream or a buffer
-    if (!holder) holder = new hqtick_ctx();
-    hqtick_ctx *ctx = holder;
-    KeepError keep{ctx, err};
-    ctx->cfg = *config; ctx->err.clear();
-    if (int rc = validate(ctx, s, false)) return rc;
-    WorkerEval ev; ev.flags = vflags; ev.tmc = vtmc;
-    hqhost::Problem pb;
-    fill_problem(pb, s, ctx->cfg, ev);
-    Scan sc; sc.Q = s->n_requests; sc.L = n_levels; sc.G = n_levels * s->n_requests;
-    sc.levels.assign(levels, levels + n_levels); sc.hist.assign(hist, hist + (size_t)n_levels * s->n_requests);
-    runs_from_hist(sc);
-    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
-    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    memset(out, 0, sizeof(*out));
-    g_last_mn_rq.clear(); g_last_mn_off.assign(1, 0); g_last_mn_worker.clear();
-    export_batches(ctx, batches, out);
-    hqsolve::EmulatedBlocks emu(g_block_budget);
-    emu.corrupt_mode = g_corrupt_mode; emu.corrupt_class = g_corrupt_class; emu.corrupt_fill = g_corrupt_fill;
-    hqprice::EmulatedSweeper pemu;
-    if (g_price_emulation) { pemu.fail_at = g_price_fault; pemu.budget = g_block_budget; if (g_price_min_cols) pemu.min_cols = g_price_min_cols; }
-    hqsolve::wire(pb, hqsolve::Wiring{g_block_emulation ? &emu : nullptr, 1, g_price_emulation ? &pemu : nullptr, g_block_verify, g_tick_seq, g_memo});
-    hqhost::Counts cnt;
-    auto solve = [&]() {
-        if (g_xfn && g_xworld > 1) {  // this call is one rank of a sharded scheduler
-            hqsolve::FnExchange xch(g_xfn, g_xuser, g_xrank, g_xworld);
-            cnt = hqsolve::run_solver(pb, batches, &xch, g_xmin_classes, g_xmin_blocks);
-            g_xcalls = (uint32_t)xch.n_calls;
-        } else cnt = hqsolve::run_solver(pb, batches, nullptr, 0, 0);
-    };
-    // hqtick_debug_set_defer_row_check(1): the row check of a fast-path placement is this caller's, as in a tick (TickRun::run) — run behind the solver, and a failure
-    // sends the model down the classic path in a second call.  Never as a rank of a sharded scheduler, like the tick.
-    pb.defer_row_check = hqmilp::g_check_hook && hqmilp::g_check_hook->allow == 1 && !(g_xfn && g_xworld > 1);
-    solve();
-    if (cnt.row_check_pending() && !cnt.settle_row_check()) { pb.defer_row_check = false; pb.no_fast_path = true; solve(); }
-    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    g_last_guard[0] = cnt.blocks_verified; g_last_guard[1] = cnt.blocks_mismatch; g_last_guard[2] = cnt.blocks_rejected;
-    g_last_memo = cnt.blocks_memo;
-    g_last_blocks_device = cnt.blocks_device; g_last_blocks_host = cnt.blocks_host; g_last_price_sweeps = (uint32_t)cnt.price_sweeps; g_last_price_rounds = (uint32_t)cnt.price_rounds;
-    g_last_stage_us[0] = cnt.t_classify_us; g_last_stage_us[1] = cnt.t_blocks_us; g_last_stage_us[2] = cnt.t_decode_us;
-    for (size_t i = 0; i < cnt.mn_rq.size(); i++)
-        for (auto &set : cnt.mn_sets[i]) { g_last_mn_rq.push_back(cnt.mn_rq[i]); g_last_mn_worker.insert(g_last_mn_worker.end(), set.begin(), set.end()); g_last_mn_off.push_back((uint32_t)g_last_mn_worker.size()); }
-    hqmap::HostResult &hr = ctx->map.res;
-    hr.cnt_rq.clear(); hr.cnt_variant.clear(); hr.cnt_worker.clear(); hr.cnt_value.clear();
-    cnt.pairs();
-    for (size_t k = 0; k < cnt.keys.size(); k++)
-        for (auto &wc : cnt.per_key[k]) { hr.cnt_rq.push_back(cnt.keys[k].first); hr.cnt_variant.push_back(cnt.keys[k].second); hr.cnt_worker.push_back(wc.first); hr.cnt_value.push_back(wc.second); }
-    out->is_optimal = cnt.is_optimal; out->is_canonical = cnt.is_canonical && cnt.is_optimal;
-    out->status = hqsolve::tick_status(cnt);
-    if (with_plan) {  // (plan_keys writes the counts itself: the same rows, in the same order)
-        static thread_local std::vector<uint32_t> tables;
-        hqmap::Plan &ps = ctx->map.plan;
-        hqmap::PlanIn in{};
-        in.sc = &sc; in.cnt = &cnt; in.s = s; in.rqs = pb.rqs.data(); in.variants = pb.variants.data();
-        in.proactive_filling_reserve = config->proactive_filling_reserve; in.proactive_filling_max = config->proactive_filling_max; in.flags = config->flags;
-        in.shard_count = 1; in.retr_key = retr_key; in.retr_rank = retr_rank; in.transpose_on = transpose_enabled();
-        for (size_t g = 0; g < sc.hist.size(); g++) in.N += sc.hist[g];
-        in.storage = heap_storage; in.user = &tables;
-        const char *why = nullptr; int rc;
-        if ((rc = hqmap::plan_keys(ps, hr, in, &why)) || (rc = hqmap::plan_redirects(ps, hr, in, &why)) || (rc = hqmap::plan_prefill(ps, hr, in, &why)) ||
-            (rc = hqmap::plan_outputs(ps, hr, in, &why)))
-            return fail(ctx, rc, why);
-        hqmap::assemble_host_part(ps, hr, in);
-        out->rec_off = hr.rec_off.data(); out->retract_off = hr.retract_off.data(); out->retract_task = hr.retract_task.data();
-        out->n_redirects = (uint32_t)hr.red_task.size(); out->redirect_task = hr.red_task.data(); out->redirect_worker = hr.red_worker.data();
-        out->redirect_variant = hr.red_variant.data(); out->redirect_kind = hr.red_kind.data(); out->new_free = hr.new_free.data();
-    }
-    out->n_counts = (uint32_t)hr.cnt_rq.size(); out->count_rq = hr.cnt_rq.data(); out->count_variant = hr.cnt_variant.data();
-    out->count_worker = hr.cnt_worker.data(); out->count_value = hr.cnt_value.data();
-    return out->status;
-}
-int hqtick_debug_host_stages(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels,
-                             const uint64_t *levels, const uint32_t *hist, hqtick_result *out) {
-    return host_stages(config, s, vflags, vtmc, n_levels, levels, hist, false, nullptr, nullptr, out, nullptr);
-}
-int hqtick_debug_host_plan(const hqtick_config *config, const hqtick_snapshot *s, const uint8_t *vflags, const uint32_t *vtmc, uint32_t n_levels, const uint64_t *levels,
-                           const uint32_t *hist, const uint32_t *retracting_key, const uint32_t *retracting_rank, hqtick_result *out, const char **error) {
-    static thread_local std::string text;
-    if (error) *error = "";
-    if (s && s->n_retracting && (!retracting_key || !retracting_rank)) return HQTICK_E_INVALID;
-    const int rc = host_stages(config, s, vflags, vtmc, n_levels, levels, hist, true, retracting_key, retracting_rank, out, &text);
-    if (rc < 0 && error) *error = text.c_str();
-    return rc;
-}
-
-int hqtick_debug_host_query(const hqtick_config *config, const hqtick_snapshot *s, const hqtick_query_workers *fake, const uint8_t *vflags, const uint32_t *vtmc,
-                            const uint8_t *fake_vflags, const uint32_t *fake_vtmc, uint32_t n_levels, const uint64_t *levels, const uint32_t *hist,
-                            hqtick_query_result *out) {
-    if (!config || !s || !fake || !out) return HQTICK_E_INVALID;
-    static thread_local hqtick_ctx *holder = nullptr;
-    if (!holder) holder = new hqtick_ctx();
-    hqtick_ctx *ctx = holder;
-    ctx->cfg = *config;
-    if (int rc = validate(ctx, s, false)) return rc;
-    const uint32_t R = s->n_resources, Q = s->n_requests;
-    WorkerEval ev; ev.flags = vflags; ev.tmc = vtmc;
-    hqhost::Problem pb;
-    fill_problem(pb, s, ctx->cfg, ev);
-    hqhost::WorkerSet fw;  // as in hqtick_query
-    hqsolve::fake_worker_set(fw, fake, R, fake_vflags, fake_vtmc, Q ? s->rq_variant_off[Q] : 0);
-    hqhost::group_equal_rows(fw, true);
-    pb.custom = &fw;
-    Scan sc; sc.Q = Q; sc.L = n_levels; sc.G = n_levels * Q;
-    sc.levels.assign(levels, levels + n_levels); sc.hist.assign(hist, hist + (size_t)n_levels * Q);
-    runs_from_hist(sc);
-    std::vector<hqhost::QueueLevels> qlv = queue_levels(sc, s);
-    std::vector<hqhost::TaskBatch> batches = hqhost::create_task_batches(pb, qlv);
-    hqsolve::EmulatedBlocks emu(g_block_budget);
-    if (g_block_emulation) { pb.blocks = &emu; pb.block_min_classes = 1; }
-    hqhost::Counts cnt = hqhost::run_scheduling_solver(pb, batches);
-    if (cnt.error) return fail(ctx, cnt.error, cnt.errmsg);
-    hqsolve::loaded_flags(cnt, fake->n_workers, ctx->q_loaded);  // query.rs:73-81
-    out->n_workers = fake->n_workers; out->is_loaded = ctx->q_loaded.data(); out->is_optimal = cnt.is_optimal;
-    return 0;
-}
-
-#endif  // HQTICK_TEST_HOOKS
 
 int hqtick_set_shard(hqtick_ctx *ctx, uint32_t shard_index, uint32_t shard_count) {
     if (!ctx) return HQTICK_E_INVALID;
@@ -1789,69 +1202,6 @@ int hqtick_set_record_sink(hqtick_ctx *ctx, void *device_ptr, size_t capacity_by
     return 0;
 }
 
-#ifdef HQTICK_TEST_HOOKS  // measurement hooks of the tools (include/hqtick_debug.h): libhqtick_test.so only
-int hqtick_time_kernel(hqtick_ctx *ctx, int which, int iters, double *avg_us) {
-    if (!ctx || !avg_us || iters <= 0) return HQTICK_E_INVALID;
-    if (!ctx->ready.selection_valid() || !ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel needs a preceding hqtick_run_resident tick that placed tasks");
-    const hqmap::Mapper::Last last = ctx->map.last_selection();
-    if (last.ordered) return fail(ctx, HQTICK_E_INVALID, "hqtick_time_kernel times the dense scan: the last tick took the ordered view");
-    HQ_HIP(hipSetDevice(ctx->device));
-    const hqready::Cols cols = ctx->ready.cols(); const hqk::WaveGeom g = last.geom;
-    if (which == 2) {  // calibration: an EMPTY kernel of K1's grid, each launch bracketed by its own start / stop events like the stats pass of a tick
-        double sum = 0.0; int cnt = 0;
-        for (int i = 0; i < iters; i++) {
-            hqk::time_next_launch(ctx->ev[2], ctx->ev[3]);
-            HQ_HIP(hqk::empty_like_level_hist(g, ctx->stream));
-            HQ_HIP(hipStreamSynchronize(ctx->stream));
-            const double us_ = elapsed_us(ctx->ev[2], ctx->ev[3]);
-            if (us_ >= 0) { sum += us_; cnt++; }
-        }
-        *avg_us = cnt ? sum / cnt : 0.0;
-        return 0;
-    }
-    // HQTICK_KTIME_GRAPH: the launches captured into one graph and replayed — no host launch cost between them (a launch call with K1's argument block takes
-    // longer than the kernel runs at 1 M tasks), so (graph duration) / iters is what the GPU spends per launch, kernel boundary included
-    const bool as_graph = getenv("HQTICK_KTIME_GRAPH") != nullptr;
-    if (as_graph) HQ_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    else HQ_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
-    for (int i = 0; i < iters; i++) {
-        if (which == 0) { if (int rc = scan_fail(ctx, ctx->scan.relaunch_level_hist(ctx->stream, cols, last.L, last.Q, g))) return rc; }
-        else if (which == 1) { if (int rc = map_fail(ctx, ctx->map.replay_selection(ctx->stream, hqmap::REPLAY_TIMED, cols, ctx->scan, ctx->ready.selected_count()))) return rc; }
-        else return fail(ctx, HQTICK_E_INVALID, "which: 0 = level_hist, 1 = select_scatter, 2 = empty kernel of level_hist's grid");
-    }
-    if (as_graph) {
-        hipGraph_t gr = nullptr; hipGraphExec_t ge = nullptr;
-        HQ_HIP(hipStreamEndCapture(ctx->stream, &gr));
-        HQ_HIP(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
-        HQ_HIP(hipGraphLaunch(ge, ctx->stream));  // once untimed
-        HQ_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
-        HQ_HIP(hipGraphLaunch(ge, ctx->stream));
-        HQ_HIP(hipEventRecord(ctx->ev[11], ctx->stream));
-        HQ_HIP(hipStreamSynchronize(ctx->stream));
-        hipGraphExecDestroy(ge); hipGraphDestroy(gr);
-    } else HQ_HIP(hipEventRecord(ctx->ev[11], ctx->stream));
-    if (which == 0)  // K1 left raw counts in the slice table: turn them back into offsets
-        if (int rc = scan_fail(ctx, ctx->scan.relaunch_scan_waves(ctx->stream, g, last.G))) return rc;
-    HQ_HIP(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HQ_HIP(hipEventElapsedTime(&ms, ctx->ev[10], ctx->ev[11]));
-    *avg_us = (double)ms * 1000.0 / iters;
-    return 0;
-}
-
-int hqtick_timeline(const hqtick_ctx *ctx, double *out, int cap) {
-    if (!ctx || !out) return 0;
-    int n = ctx->ntl < cap ? ctx->ntl : cap;
-    for (int i = 0; i < n; i++) out[i] = ctx->tl[i];
-    return n;
-}
-
-const uint64_t *hqtick_block_profile_last(const hqtick_ctx *ctx, uint32_t *n_classes) {
-    if (!ctx) { if (n_classes) *n_classes = 0; return nullptr; }
-    return ctx->solver.block_profile_last(n_classes);
-}
-#endif
-
 int hqtick_set_kernel_timing(hqtick_ctx *ctx, int on) {
     if (!ctx) return HQTICK_E_INVALID;
     ctx->timing = on != 0 && on != 2; ctx->timing_k1 = on == 2;  // (any non-zero value but 2 = every measured kernel, as before ABI 9)
@@ -1884,16 +1234,6 @@ int hqtick_shard_allgather(hqtick_ctx *ctx, void *recv_device, size_t recv_bytes
     if (recv_bytes < (size_t)ctx->solver.comm_world() * ctx->sink_bytes) return fail(ctx, HQTICK_E_CAPACITY, "receive buffer smaller than world x sink bytes");
     return solver_fail(ctx, ctx->solver.allgather_device(solve_env(ctx), ctx->sink, recv_device, ctx->sink_bytes));
 }
-
-#ifdef HQTICK_TEST_HOOKS
-// libhqtick_test.so: one all-gather of a host buffer through the library's RCCL communicator, as the sharded solve issues it per sweep — for the single-rank
-// round trip of the GPU suite (recv == send) and for timing the exchange's fixed cost (H2D + ncclAllGather + D2H + one stream synchronisation)
-int hqtick_debug_exchange(hqtick_ctx *ctx, const void *send, void *recv, size_t bytes_per_rank) {
-    if (!ctx || !send || !recv) return HQTICK_E_INVALID;
-    if (!ctx->solver.has_comm()) return fail(ctx, HQTICK_E_INVALID, "hqtick_debug_exchange without hqtick_comm_init");
-    return ctx->solver.allgather_host(solve_env(ctx), send, recv, bytes_per_rank) ? 0 : fail(ctx, HQTICK_E_DEVICE, "the RCCL exchange failed");
-}
-#endif
 
 int hqtick_comm_destroy(hqtick_ctx *ctx) {
     if (!ctx) return HQTICK_E_INVALID;

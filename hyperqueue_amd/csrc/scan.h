@@ -38,7 +38,6 @@ struct Env {
 struct Shape { uint32_t Q, n_retracting; const uint64_t *retracting_task; };  // of the snapshot: requests, and the Retracting tasks whose queue positions the tick needs
 // The worker side of K2: `tables` is invoked once per attempt, right before the launch that carries K2, and enqueues whatever brings the tables up to date.
 struct Workers { uint32_t W, R; size_t slots; int (*tables)(void *user, hqcluster::UpView *uv, std::string *err); void *user; };  // slots: (worker, variant) pairs
-struct WorkerEval { const uint8_t *flags = nullptr; const uint32_t *tmc = nullptr; };  // K2's output, host addresses (valid until the next scan)
 struct Timings { double distinct_us = -1, level_hist_us = -1, scan_us = -1, order_us = -1; };  // of the last scan() / view(); < 0: not measured
 
 class Scanner {

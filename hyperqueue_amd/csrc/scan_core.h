@@ -26,6 +26,8 @@ struct Table {  // what GPU phase A found in the ready set (Scan, scan.h, adds t
     std::vector<uint64_t> run_prio;
 };
 
+struct WorkerEval { const uint8_t *flags = nullptr; const uint32_t *tmc = nullptr; };  // K2's output, host addresses (valid until the next scan)
+
 // the runs of a dense histogram: O(L * Q), which the dense scan's caps bound
 inline void runs_from_hist(Table &sc) {
     const uint32_t Q = sc.Q;
