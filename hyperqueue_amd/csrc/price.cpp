@@ -1,5 +1,6 @@
-// The coupled placement solve by price sweeps: host side (see price.h for the method, price_core.h for what one sweep does per block).
-#include "price.h"
+// The coupled placement solve by price sweeps: host side (see price.h for the method, price_core.h for what one sweep does per block).  The solve itself:
+// master, Kelley loop, rounding, branch-and-price — on the problem that price_flatten.cpp leaves (price_prob.h).
+#include "price_prob.h"
 
 #include <algorithm>
 #include <chrono>
@@ -23,10 +24,8 @@ using hqmilp::lp::LP_OPT;
 using hqmilp::lp::Rows;
 using hqmilp::lp::Tab;
 
-constexpr int KMAX_HOST = 128;   // == price_core.h's KMAX (not included here: this file is host-only and also part of libhqalloc.so)
-constexpr int NMAX_BLOCK = 32, MMAX_BLOCK = 4;
+static_assert(UNBOUNDED == INF, "price_prob.h restates lp_tab.h's INF");
 constexpr double FIRST_PROPOSAL_SCALE = 1.0 / 16.0;   // kelley(): what is evaluated of the first master's proposal (see there)
-constexpr double GRID = 10000.0;  // ResourceAmount fractions per unit  common/resources/amount.rs:7
 constexpr int MAX_ROUNDS = 6;
 constexpr int BP_MAX_NODES = 600;   // nodes of the branch-and-price phase (a deterministic count, like every limit in here)
 // (per second of the caller's configured time limit: generous — what keeps the phase inside the limit is its wall-clock guard at 70 % of it)
@@ -36,240 +35,6 @@ constexpr double BP_MAX_WORK = 3.0e9; // ... and tableau elements its masters ma
 
 double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 thread_local uint32_t g_early_sweeps = 0;   // tests: sweeps launched on the block tables alone (Solver::launch_on_blocks)
-
-struct CapRow { int flat; double rhs; std::vector<std::pair<int, double>> g; };  // x_flat + sum_g coef B_g <= rhs (the column's own coefficient divided out)
-
-struct Prob {
-    HostTables T;
-    std::vector<int> flat_of, model_of;       // model column <-> flat column (-1: global)
-    std::vector<int> gmodel;                   // global columns (model index)
-    std::vector<double> gcost;
-    int K = 0, G = 0;
-    std::vector<double> h;                     // wide rows in <= form
-    std::vector<uint8_t> ge;                   // the row was a `>=` row (entered negated)
-    std::vector<std::vector<std::pair<int, double>>> g_rows;   // per global column: (wide row, coefficient in <= form)
-    // Wide rows with the same left-hand side over the block columns (the cut rows of one batch against its several blockers differ in their flag only) share
-    // ONE activity: the device prices and accumulates per GROUP (T.K groups, price of a group = sum of its rows' prices), and the host keeps the left-hand
-    // sides per group as well — row-wise here, column-wise in T.col_woff / T.w_row / T.w_coef — and expands to rows where a row's own right-hand side matters
-    // (c3p at BASELINE size: 70 wide rows, 16 distinct left-hand sides, 71 680 against 16 384 terms).
-    std::vector<int> grp_of;   // [K] row -> group
-    int KG = 0;
-    std::vector<int> g_off, g_col; std::vector<int32_t> g_coef;   // [KG] the distinct left-hand sides over the flat columns, terms in the model's order
-    std::vector<int> gr_off, gr_row;                              // [KG] the rows of a group, ascending
-    size_t row_terms = 0;                                         // terms of the K rows as the model wrote them (statistics)
-    std::vector<CapRow> caps;
-    std::vector<int32_t> base_cap;
-    std::vector<int> block_of_flat;
-    int n_runs = 0, run_blocks = 0;   // equal-block runs of the model that passed the flattener's comparison, and the blocks they cover (statistics)
-};
-
-// round half away from zero without the call into libm (-msse4.1 gives floor / nearbyint as one instruction, not round); |v| < 2^51
-inline double round_fast(double v) { return (double)(long long)(v + (v >= 0.0 ? 0.5 : -0.5)); }
-long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a < 0 ? -a : a; }
-
-// The groups' left-hand sides -> P's row-wise and column-wise tables (P.grp_of, P.KG set; lhs[g] = (flat column, coefficient) in the model's order)
-void finish_groups(Prob &P, const std::vector<std::vector<std::pair<int, int32_t>>> &lhs) {
-    HostTables &T = P.T;
-    const int KG = P.KG;
-    T.K = (uint32_t)KG;
-    size_t tot = 0; for (auto &l : lhs) tot += l.size();
-    // (sized once and written through pointers: ~16 k terms per tick on c3p, three passes — a push_back per term was a third of the flattening)
-    P.g_off.assign((size_t)KG + 1, 0); P.g_col.resize(tot); P.g_coef.resize(tot);
-    std::vector<uint32_t> gcnt(T.n_cols + 1, 0);
-    {
-        auto *gc = P.g_col.data(); auto *gk = P.g_coef.data(); uint32_t *cnt = gcnt.data() + 1; size_t pos = 0;
-        for (int g = 0; g < KG; g++) {
-            const std::pair<int, int32_t> *l = lhs[(size_t)g].data();
-            for (size_t i = 0, e = lhs[(size_t)g].size(); i < e; i++) { gc[pos] = l[i].first; gk[pos] = l[i].second; cnt[l[i].first]++; pos++; }
-            P.g_off[(size_t)g + 1] = (int)pos;
-        }
-    }
-    T.col_woff.assign(T.n_cols + 1, 0);
-    for (uint32_t f = 0; f < T.n_cols; f++) T.col_woff[f + 1] = T.col_woff[f] + gcnt[f + 1];
-    T.w_row.resize(T.col_woff[T.n_cols]); T.w_coef.resize(T.col_woff[T.n_cols]);
-    {
-        std::vector<uint32_t> &cur = gcnt;   // (the counts are done with: the cursors take their place)
-        for (uint32_t f = 0; f < T.n_cols; f++) cur[f] = T.col_woff[f];
-        uint32_t *cp = cur.data(); uint16_t *wr = T.w_row.data(); auto *wc = T.w_coef.data();
-        const auto *gc = P.g_col.data(); const auto *gk = P.g_coef.data();
-        for (int g = 0; g < KG; g++) for (int e = P.g_off[g], e1 = P.g_off[g + 1]; e < e1; e++) { const uint32_t p = cp[gc[e]]++; wr[p] = (uint16_t)g; wc[p] = gk[e]; }
-    }
-    // rows of every group, ascending
-    P.gr_off.assign((size_t)KG + 1, 0);
-    for (int k = 0; k < P.K; k++) P.gr_off[P.grp_of[k] + 1]++;
-    for (int g = 0; g < KG; g++) P.gr_off[g + 1] += P.gr_off[g];
-    P.gr_row.resize(P.K);
-    { std::vector<int> c2(P.gr_off.begin(), P.gr_off.end() - 1); for (int k = 0; k < P.K; k++) P.gr_row[c2[P.grp_of[k]]++] = k; }
-}
-
-// The component -> blocks + wide rows.  Returns nullptr on success, else what kept the model on the host.
-const char *build(const Request &rq, Prob &P) {
-    const int n = rq.n;
-    if (!rq.col_group) return "no block hints";
-    // blocks in order of their first column (the tick: worker order)
-    std::vector<int> gid; gid.reserve(n);
-    int max_group = -1;
-    for (int j = 0; j < n; j++) max_group = std::max(max_group, rq.col_group[j]);
-    std::vector<int> block_of_group((size_t)max_group + 1, -1);
-    std::vector<int> bsize;
-    std::vector<int> blk(n, -1);
-    for (int j = 0; j < n; j++) {
-        const int g = rq.col_group[j];
-        if (g < 0) { P.gmodel.push_back(j); continue; }
-        if (block_of_group[g] < 0) { block_of_group[g] = (int)bsize.size(); bsize.push_back(0); }
-        blk[j] = block_of_group[g];
-        if (++bsize[blk[j]] > NMAX_BLOCK) return "block with more than 32 columns";
-    }
-    const int nb = (int)bsize.size();
-    if (nb < 8) return "fewer than 8 blocks";
-    P.G = (int)P.gmodel.size();
-    for (int j : P.gmodel) {
-        if (rq.ub[j] != 1.0) return "global column that is not 0/1";
-        if (rq.c[j] < 0.0) return "global column with negative cost";
-        P.gcost.push_back(rq.c[j]);
-    }
-    std::vector<int> gidx(n, -1);
-    for (int g = 0; g < P.G; g++) gidx[P.gmodel[g]] = g;
-    HostTables &T = P.T;
-    T.n_blocks = (uint32_t)nb;
-    T.blk_off.assign((size_t)nb + 1, 0);
-    for (int b = 0; b < nb; b++) T.blk_off[b + 1] = T.blk_off[b] + (uint32_t)bsize[b];
-    T.n_cols = T.blk_off[nb];
-    P.flat_of.assign(n, -1); P.model_of.assign(T.n_cols, -1); P.block_of_flat.assign(T.n_cols, -1);
-    {
-        std::vector<uint32_t> cur(T.blk_off.begin(), T.blk_off.end() - 1);
-        for (int j = 0; j < n; j++) if (blk[j] >= 0) { const int f = (int)cur[blk[j]]++; P.flat_of[j] = f; P.model_of[f] = j; P.block_of_flat[f] = blk[j]; }
-    }
-    T.col_cost.assign(T.n_cols, 0.0); T.col_a.assign((size_t)T.n_cols * MMAX_BLOCK, 0.0); T.col_cap.assign(T.n_cols, 0);
-    T.blk_m.assign(nb, 0); T.blk_cap.assign((size_t)nb * MMAX_BLOCK, 0.0);
-    for (uint32_t f = 0; f < T.n_cols; f++) {
-        const int j = P.model_of[f];
-        if (rq.c[j] < 0.0) return "negative cost";
-        if (!(rq.ub[j] <= 65535.0)) return "column bound above 65535";
-        T.col_cost[f] = rq.c[j];
-        T.col_cap[f] = (int32_t)std::floor(rq.ub[j] + 1e-9);
-    }
-    struct WideTmp { double h; uint8_t ge; std::vector<std::pair<int, int32_t>> cols; std::vector<std::pair<int, double>> g; };
-    std::vector<WideTmp> wide;
-    std::vector<std::pair<int, long long>> ai;  // (one allocation for all block rows)
-    for (int i = 0; i < rq.m; i++) {
-        const int a = rq.roff[i], e = rq.roff[i + 1];
-        if (a == e) continue;
-        const double sc = rq.row_scale[i];
-        int b0 = -2; bool multi = false, has_g = false, nonneg = true;
-        int n_bcols = 0;
-        for (int k = a; k < e; k++) {
-            const int j = rq.rcol[k];
-            if (rq.rcoef[k] < 0.0) nonneg = false;
-            if (blk[j] < 0) { has_g = true; continue; }
-            n_bcols++;
-            if (b0 == -2) b0 = blk[j]; else if (blk[j] != b0) multi = true;
-        }
-        const bool is_le = rq.rlo[i] <= -INF, is_ge = rq.rhi[i] >= INF;
-        if (is_le && is_ge) continue;  // no constraint at all
-        if (!multi && !has_g && b0 >= 0) {  // a row of one block
-            if (rq.row_implied && rq.row_implied[i]) continue;  // implied for integer points by the block's other rows: the sweeps solve the blocks in integers
-            if (is_le && nonneg) {  // no point within the column bounds (which the block carries as caps) can violate it: e.g. the per-worker cut rows of a large cut
-                double amax = 0.0;
-                for (int k = a; k < e; k++) amax += rq.rcoef[k] * rq.ub[rq.rcol[k]];
-                if (amax <= rq.rhi[i] * (1.0 + 1e-12) + 1e-9) continue;
-            }
-            if (!is_le || !nonneg || rq.rhi[i] < 0.0) return "block row that is not a packing row";
-            const int r = T.blk_m[b0];
-            if (r >= MMAX_BLOCK) {
-                if (rq.trace) { fprintf(stderr, "[price] 5th row of block %d: hi %.6f scale %.6f:", b0, rq.rhi[i], sc); for (int k = a; k < e; k++) fprintf(stderr, " %.6f*x%d(ub %.0f)", rq.rcoef[k] * sc, rq.rcol[k], rq.ub[rq.rcol[k]]); fprintf(stderr, "\n"); }
-                return "block with more than 4 rows";
-            }
-            long long g = 0; bool ok = true;
-            ai.clear();
-            for (int k = a; k < e && ok; k++) {
-                const double v = rq.rcoef[k] * sc * GRID, rv = std::round(v);
-                if (rv < 1.0 || std::fabs(v - rv) > 1e-6 * std::max(1.0, rv) || rv >= 4.0e15) ok = false;
-                else { ai.push_back({P.flat_of[rq.rcol[k]], (long long)rv}); g = gcd_ll(g, (long long)rv); }
-            }
-            if (!ok) return "block row off the ResourceAmount grid";
-            const double capv = rq.rhi[i] * sc * GRID;
-            if (capv >= 4.0e15) return "block row capacity too large";
-            const long long capi = (long long)std::floor(capv + 1e-6);
-            if (g < 1) g = 1;
-            for (auto &t : ai) T.col_a[(size_t)t.first * MMAX_BLOCK + r] += (double)(t.second / g);  // (duplicate terms of one row are summed)
-            T.blk_cap[(size_t)b0 * MMAX_BLOCK + r] = (double)(capi / g);
-            T.blk_m[b0] = (uint8_t)(r + 1);
-            continue;
-        }
-        if (!is_le && !is_ge) return "equality or range row across blocks";
-        // vacuous rows: a `<=` row no point within the column bounds can violate, a `>=` row that holds at zero
-        if (is_le && nonneg) {
-            double amax = 0.0;
-            for (int k = a; k < e; k++) amax += rq.rcoef[k] * rq.ub[rq.rcol[k]];
-            if (amax <= rq.rhi[i] * (1.0 + 1e-12) + 1e-9) continue;
-        }
-        if (is_ge && nonneg && rq.rlo[i] <= 1e-12) continue;
-        if (!multi && has_g && n_bcols >= 1 && is_le && nonneg) {  // one block + flags: a conditional bound of the block's column(s)
-            if (n_bcols != 1) return "conditional bound over several columns of a block";
-            CapRow cr; cr.flat = -1; cr.rhs = 0.0;
-            double cx = 0.0;
-            for (int k = a; k < e; k++) if (blk[rq.rcol[k]] >= 0) { cr.flat = P.flat_of[rq.rcol[k]]; cx = rq.rcoef[k]; }
-            if (!(cx > 0.0)) return "conditional bound with a zero coefficient";
-            cr.rhs = rq.rhi[i] / cx;
-            for (int k = a; k < e; k++) if (blk[rq.rcol[k]] < 0) cr.g.push_back({gidx[rq.rcol[k]], rq.rcoef[k] / cx});
-            P.caps.push_back(std::move(cr));
-            continue;
-        }
-        if (n_bcols == 0) return "row over global columns only";
-        WideTmp w; w.ge = is_ge ? 1 : 0;
-        w.cols.reserve((size_t)(e - a));
-        const double sign = is_le ? 1.0 : -1.0;
-        w.h = sign * (is_le ? rq.rhi[i] : rq.rlo[i]) * sc;
-        for (int k = a; k < e; k++) {
-            const int j = rq.rcol[k];
-            const double v = sign * rq.rcoef[k] * sc;
-            if (blk[j] < 0) { w.g.push_back({gidx[j], v}); continue; }
-            const double rv = std::round(v);
-            if (std::fabs(v - rv) > 1e-7 * std::max(1.0, std::fabs(rv)) || std::fabs(rv) > 1.0e9) return "wide row with a non-integer coefficient";
-            if (rv != 0.0) w.cols.push_back({P.flat_of[j], (int32_t)rv});
-        }
-        wide.push_back(std::move(w));
-        if ((int)wide.size() > 1024) return "more than 1024 wide rows";
-    }
-    for (int b = 0; b < nb; b++) if (T.blk_m[b] == 0) {
-        // every resource row of this worker is slack at its column bounds (a nearly idle worker and a short ready set: the caps bind, not the resources).  The kernel
-        // wants a row: the sum of the block's columns against the sum of their caps — never binding either.
-        double total = 0.0;
-        for (uint32_t f = T.blk_off[b]; f < T.blk_off[b + 1]; f++) { T.col_a[(size_t)f * MMAX_BLOCK] = 1.0; total += (double)T.col_cap[f]; }
-        T.blk_cap[(size_t)b * MMAX_BLOCK] = total;
-        T.blk_m[b] = 1;
-    }
-    // every column of a block must be bounded by its block: a cap below 65536 is there (checked above); amounts that do not fit even once leave ub 0
-    P.K = (int)wide.size();
-    if (P.K == 0) return "no wide row";
-    P.h.resize(P.K); P.ge.resize(P.K); P.g_rows.assign(P.G, {});
-    std::vector<uint64_t> sig(P.K);   // a hash of every wide row's left-hand side (the groups of identical left-hand sides below compare hashes first)
-    for (int k = 0; k < P.K; k++) {
-        P.h[k] = wide[k].h; P.ge[k] = wide[k].ge;
-        uint64_t hsh = 1469598103934665603ull;
-        for (auto &t : wide[k].cols) { hsh = (hsh ^ (uint64_t)(uint32_t)t.first) * 1099511628211ull; hsh = (hsh ^ (uint64_t)(uint32_t)t.second) * 1099511628211ull; }
-        sig[k] = hsh; P.row_terms += wide[k].cols.size();
-        for (auto &t : wide[k].g) P.g_rows[t.first].push_back({k, t.second});
-    }
-    // groups of rows with identical left-hand sides
-    P.grp_of.assign(P.K, -1);
-    std::vector<int> rep;
-    // (the hash of the left-hand side first: the rows are a thousand terms long, an ordered map of them compares them term by term)
-    for (int k = 0; k < P.K; k++) {
-        int g = -1;
-        for (size_t i = 0; i < rep.size() && g < 0; i++) if (sig[rep[i]] == sig[k] && wide[rep[i]].cols == wide[k].cols) g = (int)i;
-        if (g < 0) { g = (int)rep.size(); rep.push_back(k); }
-        P.grp_of[k] = g;
-    }
-    P.KG = (int)rep.size();
-    if (P.KG > KMAX_HOST) return "more than 128 distinct wide left-hand sides";
-    std::vector<std::vector<std::pair<int, int32_t>>> lhs((size_t)P.KG);
-    for (int g = 0; g < P.KG; g++) lhs[(size_t)g] = std::move(wide[rep[g]].cols);
-    finish_groups(P, lhs);
-    P.base_cap = T.col_cap;
-    return nullptr;
-}
 
 struct Cut {
     double cx = 0, bnd = 0; std::vector<long long> act; std::vector<double> pi;
@@ -1368,467 +1133,12 @@ Answer run_solver(Solver &S, const double tp0) {
     }
     return ans;
 }
-}  // namespace
 
-namespace {
-
-thread_local bool g_check_hints = false; thread_local int g_hint_mismatches = 0;
 thread_local int g_early_sweep = -1;
 bool early_sweep_on() {
     static const bool env_on = !(getenv("HQPRICE_EARLY_SWEEP") && atoi(getenv("HQPRICE_EARLY_SWEEP")) == 0);   // (A/B switch)
     return g_early_sweep < 0 ? env_on : g_early_sweep != 0;
 }
-// ---- the model as its builder wrote it -> blocks + wide rows (what build() does for a scaled component copy; same tables, same numbering) -------------------------
-// Returns nullptr on success, else what keeps the model on the classic path.  ub: the derived column bounds (model columns), c: obj / cmax.
-// after_blocks (optional) is called once, when the block tables — T.n_blocks, T.n_cols, blk_off, blk_m, blk_cap, col_cost, col_a, col_cap — are final: behind the rows
-// loop, the last run's copies and the never-binding rows.  What follows builds the wide rows' groups and changes none of the eight.
-const char *flatten_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax, const std::function<void()> *after_blocks = nullptr) {
-    const int n = mv.n, m = mv.m;
-    if (!mv.col_group || !mv.row_lhs || !mv.row_lhs_len) return "no structure hints";
-    // blocks in order of their first column (the tick: worker order)
-    int max_group = -1;
-    for (int j = 0; j < n; j++) max_group = std::max(max_group, mv.col_group[j]);
-    std::vector<int> block_of_group((size_t)max_group + 1, -1), bsize, blk(n, -1);
-    for (int j = 0; j < n; j++) {
-        const int g = mv.col_group[j];
-        if (g < 0) { P.gmodel.push_back(j); continue; }
-        if (block_of_group[g] < 0) { block_of_group[g] = (int)bsize.size(); bsize.push_back(0); }
-        blk[j] = block_of_group[g];
-        if (++bsize[blk[j]] > NMAX_BLOCK) return "block with more than 32 columns";
-    }
-    const int nb = (int)bsize.size();
-    if (nb < 8) return "fewer than 8 blocks";
-    cmax = 0.0;
-    for (int j = 0; j < n; j++) cmax = std::max(cmax, std::fabs(mv.obj[j]));
-    if (cmax == 0.0) cmax = 1.0;
-    c.resize(n);
-    for (int j = 0; j < n; j++) c[j] = mv.obj[j] / cmax;
-    P.G = (int)P.gmodel.size();
-    for (int j : P.gmodel) {
-        if (mv.kind[j] != 1) return "global column that is not 0/1";
-        if (c[j] < 0.0) return "global column with negative cost";
-        P.gcost.push_back(c[j]);
-    }
-    std::vector<int> gidx(n, -1);
-    for (int g = 0; g < P.G; g++) gidx[P.gmodel[g]] = g;
-    // ---- column bounds, as hqmilp::solve derives them: a row without a negative coefficient bounds every column it holds by floor(rhs / coef + 1e-9).  A shared list of
-    // leading terms is walked once, against the smallest right-hand side of its rows (the bound is monotone in the right-hand side).
-    const int n_lhs = mv.n_lists;
-    for (int i = 0; i < m; i++) if (mv.row_lhs[i] >= n_lhs) return "bad structure hint";
-    struct Fam { int first = -1, len = 0; bool has_neg = false, scanned = false; double rhs_min = INF;
-                 // of the list's block columns: their block (-2 none yet), more than one block, a global column inside, count, integer coefficients
-                 int b0 = -2; bool multi = false, has_g = false, integral = true; int n_bcols = 0; double amax = 0.0; };
-    std::vector<Fam> fam((size_t)n_lhs);
-    ub.assign(n, INF);
-    for (int j = 0; j < n; j++) if (mv.kind[j] == 1) ub[j] = 1.0;
-    const bool hinted = mv.row_block && mv.col_ub;   // the builder's own bounds of the block columns: the rows of single blocks need not be walked for theirs
-    if (hinted) for (int j = 0; j < n; j++) if (mv.col_ub[j] != UINT32_MAX) ub[j] = std::min(ub[j], (double)mv.col_ub[j]);
-    auto bound_terms = [&](int a, int e, double rhs) { for (int k = a; k < e; k++) if (mv.rcoef[k] > 0.0) { double &u = ub[mv.rcol[k]]; u = std::min(u, std::floor(rhs / mv.rcoef[k] + 1e-9)); } };
-    for (int l = 0; l < n_lhs; l++) for (int k = mv.list_off[l]; k < mv.list_off[l + 1]; k++) if (mv.list_col[k] < 0 || mv.list_col[k] >= n) return "bad structure hint";
-    for (int i = 0; i < m; i++) {
-        const int a = mv.roff[i], e = mv.roff[i + 1];
-        if (a == e && mv.row_lhs[i] < 0) { const double b = mv.rhs[i]; const bool ok = mv.rtype[i] == 1 ? b >= -1e-9 : (mv.rtype[i] == 0 ? b <= 1e-9 : std::fabs(b) <= 1e-9); if (!ok) return "infeasible empty row"; continue; }
-        if (hinted && mv.row_block[i] >= 0) continue;
-        const int L = mv.row_lhs[i];
-        const int tail = a;   // (a shared list's terms are not among the row's stored ones: those are all tail)
-        bool neg = false;
-        if (L >= 0) { Fam &f = fam[(size_t)L]; if (f.first < 0) { f.first = i; f.len = mv.list_off[L + 1] - mv.list_off[L]; } }
-        for (int k = tail; k < e; k++) if (mv.rcoef[k] < 0.0) neg = true;
-        if (mv.rtype[i] == 0 || neg) continue;   // a `>=` row, or a negative coefficient: no bound from here (the multi-node rows that do bound through one are not for this path)
-        if (mv.rhs[i] < -1e-9) return "infeasible row";
-        if (L >= 0) fam[(size_t)L].rhs_min = std::min(fam[(size_t)L].rhs_min, mv.rhs[i]);
-        bound_terms(tail, e, mv.rhs[i]);
-    }
-    for (int l = 0; l < n_lhs; l++) if (fam[(size_t)l].first >= 0 && fam[(size_t)l].rhs_min < INF) {   // coefficient 1: the bound is the right-hand side itself
-        const double bnd = std::floor(fam[(size_t)l].rhs_min + 1e-9);
-        for (int k = mv.list_off[l]; k < mv.list_off[l + 1]; k++) { double &u = ub[mv.list_col[k]]; u = std::min(u, bnd); }
-    }
-    // ---- equal-block runs (milp.h: Model::block_runs).  A hint like the others: every block of a run is compared with the run's first one — whole blocks with consecutive
-    // numbers, the same kinds, bounds (the builder's and the ones derived above), row types, right-hand sides, implied marks, coefficients and block-relative columns, rows
-    // that are their block's alone — and a run that fails anywhere is forgotten: its blocks are then flattened one by one like any other.
-    struct Run { int col0, row0, term0, nbk, nc, nr, nt, b0; };
-    std::vector<Run> runs;
-    if (hinted && mv.block_runs) {
-        long long col_end = 0, row_end = 0;
-        auto holds = [&](const int32_t *r) -> bool {
-            const long long col0 = r[0], row0 = r[1], term0 = r[2], nbk = r[3], nc = r[4], nr = r[5], nt = r[6];
-            if (nbk < 2 || nc < 1 || nc > NMAX_BLOCK || nr < 1 || nt < 1 || col0 < col_end || row0 < row_end) return false;
-            if (col0 + nbk * nc > n || row0 + nbk * nr > m) return false;
-            if (mv.roff[row0] != term0 || (long long)mv.roff[row0 + nbk * nr] != term0 + nbk * nt) return false;
-            const int b0 = blk[col0];
-            if (b0 < 0 || b0 + nbk > nb) return false;
-            for (long long t = 0; t < nt; t++) { const long long rel = (long long)mv.rcol[term0 + t] - col0; if (rel < 0 || rel >= nc) return false; }   // the first block's rows hold its own columns only
-            for (long long q = 0; q < nc; q++) if (blk[col0 + q] != b0) return false;
-            for (long long k = 0; k < nbk; k++) {   // whole blocks, and rows that are their block's alone
-                if (bsize[b0 + k] != nc) return false;
-                const int32_t gk = mv.col_group[col0 + k * nc];
-                const long long rk = row0 + k * nr;
-                for (long long q = 0; q < nr; q++) if (mv.row_lhs[rk + q] >= 0 || mv.row_block[rk + q] != gk) return false;
-            }
-            // every block against the one before it: the arrays compared with themselves, one block further on
-            const size_t cs = (size_t)((nbk - 1) * nc), rs = (size_t)((nbk - 1) * nr), ts = (size_t)((nbk - 1) * nt);
-            { const int *bp = blk.data() + col0; bool ok = true; for (size_t q = 0; q < cs; q++) ok &= bp[q + nc] == bp[q] + 1; if (!ok) return false; }
-            if (memcmp(mv.kind + col0 + nc, mv.kind + col0, cs) != 0 || memcmp(mv.col_ub + col0 + nc, mv.col_ub + col0, cs * sizeof(uint32_t)) != 0) return false;
-            if (memcmp(&ub[col0 + nc], &ub[col0], cs * sizeof(double)) != 0) return false;
-            if (memcmp(mv.rtype + row0 + nr, mv.rtype + row0, rs) != 0 || memcmp(mv.rhs + row0 + nr, mv.rhs + row0, rs * sizeof(double)) != 0) return false;
-            if (mv.row_implied && memcmp(mv.row_implied + row0 + nr, mv.row_implied + row0, rs) != 0) return false;
-            if (memcmp(mv.rcoef + term0 + nt, mv.rcoef + term0, ts * sizeof(double)) != 0) return false;
-            { const int *ro = mv.roff + row0; bool ok = true; for (size_t q = 0; q <= rs; q++) ok &= (long long)ro[q + nr] - ro[q] == nt; if (!ok) return false; }
-            { const int *rc = mv.rcol + term0; bool ok = true; for (size_t q = 0; q < ts; q++) ok &= (long long)rc[q + nt] - rc[q] == nc; if (!ok) return false; }
-            return true;
-        };
-        for (int q = 0; q < mv.n_block_runs; q++) {
-            const int32_t *r = mv.block_runs + (size_t)7 * q;
-            if (!holds(r)) continue;
-            runs.push_back({r[0], r[1], r[2], r[3], r[4], r[5], r[6], blk[r[0]]});
-            col_end = (long long)r[0] + (long long)r[3] * r[4]; row_end = (long long)r[1] + (long long)r[3] * r[5];
-        }
-    }
-    if (hinted && g_check_hints) {   // tests: the builder's column bounds must be what the skipped single-block rows give — not tighter (a point lost), not looser
-        std::vector<double> chk(n, INF);
-        for (int j = 0; j < n; j++) if (mv.kind[j] == 1) chk[j] = 1.0;
-        for (int i = 0; i < m; i++) {
-            if (mv.row_block[i] < 0 || mv.rtype[i] == 0) continue;
-            bool neg = false;
-            for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] < 0.0) neg = true;
-            if (neg) continue;
-            for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] > 0.0) chk[mv.rcol[k]] = std::min(chk[mv.rcol[k]], std::floor(mv.rhs[i] / mv.rcoef[k] + 1e-9));
-        }
-        // ... unless a row that is NOT one block's alone gives it (an unbounded resource's terms carried into the next worker's row make that row such a one): then it is
-        // a bound some row of the model states, which is all a hint has to be — `any` is the tightest bound a single row gives, over all rows
-        std::vector<double> any(chk);
-        for (int i = 0; i < m; i++) {
-            if (mv.row_block[i] >= 0 || mv.rtype[i] == 0) continue;
-            bool neg = false;
-            for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] < 0.0) neg = true;
-            if (neg) continue;
-            for (int k = mv.roff[i]; k < mv.roff[i + 1]; k++) if (mv.rcoef[k] > 0.0) any[mv.rcol[k]] = std::min(any[mv.rcol[k]], std::floor(mv.rhs[i] / mv.rcoef[k] + 1e-9));
-            if (mv.row_lhs[i] >= 0) for (int k = mv.list_off[mv.row_lhs[i]]; k < mv.list_off[mv.row_lhs[i] + 1]; k++) any[mv.list_col[k]] = std::min(any[mv.list_col[k]], std::floor(mv.rhs[i] + 1e-9));
-        }
-        for (int j = 0; j < n; j++) if (mv.col_ub[j] != UINT32_MAX && chk[j] < INF && ((double)mv.col_ub[j] > chk[j] || (double)mv.col_ub[j] < any[j])) { g_hint_mismatches++; return "structure hint: col_ub differs from what the block's rows give"; }
-    }
-    
-    HostTables &T = P.T;
-    T.n_blocks = (uint32_t)nb;
-    T.blk_off.assign((size_t)nb + 1, 0);
-    for (int b = 0; b < nb; b++) T.blk_off[b + 1] = T.blk_off[b] + (uint32_t)bsize[b];
-    T.n_cols = T.blk_off[nb];
-    P.flat_of.assign(n, -1); P.model_of.assign(T.n_cols, -1); P.block_of_flat.assign(T.n_cols, -1);
-    {
-        std::vector<uint32_t> cur(T.blk_off.begin(), T.blk_off.end() - 1);
-        for (int j = 0; j < n; j++) if (blk[j] >= 0) { const int f = (int)cur[blk[j]]++; P.flat_of[j] = f; P.model_of[f] = j; P.block_of_flat[f] = blk[j]; }
-    }
-    T.col_cost.assign(T.n_cols, 0.0); T.col_a.assign((size_t)T.n_cols * MMAX_BLOCK, 0.0); T.col_cap.assign(T.n_cols, 0);
-    T.blk_m.assign(nb, 0); T.blk_cap.assign((size_t)nb * MMAX_BLOCK, 0.0);
-    for (uint32_t f = 0; f < T.n_cols; f++) {
-        const int j = P.model_of[f];
-        if (c[j] < 0.0) return "negative cost";
-        if (!(ub[j] <= 65535.0)) return "column bound above 65535";
-        T.col_cost[f] = c[j];
-        T.col_cap[f] = (int32_t)std::floor(ub[j] + 1e-9);
-    }
-    // ---- the rows
-    struct WideRow { double h; uint8_t ge; int lhs_key; int own = -1; std::vector<std::pair<int, double>> g; };   // lhs_key: 2 * L + (`>=` row), or -1 with its own list `own`
-    std::vector<WideRow> wide;
-    std::vector<std::vector<std::pair<int, int32_t>>> own_lists;   // left-hand sides of wide rows outside every family (sign applied)
-    struct RowMemo { int n = -1; long long g = 1; double raw[32]; double scaled[64]; };
-    RowMemo row_memo[8], memo_big; unsigned memo_next = 0;
-    // what a range of terms looks like to the classification below
-    struct Scan { int b0 = -2; bool multi = false, has_g = false, nonneg = true; int n_bcols = 0; double amax = 0.0; };
-    auto scan = [&](int a, int e, Scan &sc) {
-        for (int k = a; k < e; k++) {
-            const int j = mv.rcol[k];
-            if (mv.rcoef[k] < 0.0) sc.nonneg = false;
-            sc.amax += mv.rcoef[k] * ub[j];
-            if (blk[j] < 0) { sc.has_g = true; continue; }
-            sc.n_bcols++;
-            if (sc.b0 == -2) sc.b0 = blk[j]; else if (blk[j] != sc.b0) sc.multi = true;
-        }
-    };
-    // a run's first block goes through the rows below like any block; what they made of it — rows kept, their order, grid coefficients, capacities — is then copied to
-    // the other blocks of the run, whose rows are passed over.  (Only where no earlier row has touched one of these blocks: the copy is then all there is to them.)
-    size_t run_i = 0; bool run_live = false;
-    auto stamp_run = [&](const Run &R) {
-        const uint32_t f0 = T.blk_off[R.b0];
-        const size_t col_bytes = (size_t)R.nc * MMAX_BLOCK * sizeof(double);
-        for (int k = 1; k < R.nbk; k++) {
-            const int b = R.b0 + k;
-            T.blk_m[b] = T.blk_m[R.b0];
-            memcpy(&T.blk_cap[(size_t)b * MMAX_BLOCK], &T.blk_cap[(size_t)R.b0 * MMAX_BLOCK], MMAX_BLOCK * sizeof(double));
-            memcpy(&T.col_a[(size_t)T.blk_off[b] * MMAX_BLOCK], &T.col_a[(size_t)f0 * MMAX_BLOCK], col_bytes);
-        }
-        P.n_runs++; P.run_blocks += R.nbk;
-    };
-    for (int i = 0; i < m; i++) {
-        if (run_live && i == runs[run_i].row0 + runs[run_i].nr) {
-            stamp_run(runs[run_i]);
-            i = runs[run_i].row0 + runs[run_i].nbk * runs[run_i].nr;
-            run_live = false; run_i++;
-            if (i >= m) break;
-        }
-        if (!run_live && run_i < runs.size() && i == runs[run_i].row0) {
-            bool fresh = true;
-            for (int k = 0; k < runs[run_i].nbk && fresh; k++) if (T.blk_m[runs[run_i].b0 + k] != 0) fresh = false;
-            if (fresh) run_live = true; else run_i++;
-        }
-        const int a = mv.roff[i], e = mv.roff[i + 1];
-        if (a == e && mv.row_lhs[i] < 0) continue;
-        const bool is_le = mv.rtype[i] == 1, is_ge = mv.rtype[i] == 0;
-        const double rhs = mv.rhs[i];
-        const int L = mv.row_lhs[i];
-        Scan sc; const int tail = a;
-        bool fam_row = false;
-        if (L >= 0) {
-            Fam &f = fam[(size_t)L];
-            if (!f.scanned) {   // the list itself, once: which blocks its columns are of, what it can reach at most (coefficient 1 each)
-                f.scanned = true;
-                for (int k = mv.list_off[L]; k < mv.list_off[L + 1]; k++) {
-                    const int j = mv.list_col[k];
-                    f.amax += ub[j];
-                    if (blk[j] < 0) { f.has_g = true; continue; }
-                    f.n_bcols++;
-                    if (f.b0 == -2) f.b0 = blk[j]; else if (blk[j] != f.b0) f.multi = true;
-                }
-            }
-            if (!(f.multi && !f.has_g)) return "shared list that is not a wide left-hand side";   // (one block's list, or a flag inside it: the plain form's business)
-            sc.b0 = f.b0; sc.multi = true; sc.has_g = false; sc.nonneg = true; sc.n_bcols = f.n_bcols; sc.amax = f.amax;
-            fam_row = true;
-        }
-        const int hint_b = (hinted && !fam_row && mv.row_block[i] >= 0 && mv.row_block[i] <= max_group) ? block_of_group[mv.row_block[i]] : -1;
-        if (hint_b >= 0) {   // the builder says: one block's row — no need to look its columns' blocks up
-            if (mv.row_implied && mv.row_implied[i]) continue;
-            sc.b0 = hint_b; sc.n_bcols = e - a;
-            const int32_t hb = mv.row_block[i];
-            for (int k = a; k < e; k++) {
-                if (mv.col_group[mv.rcol[k]] != hb) return "structure hint: a row_block row holds a column of another block";   // (hints are checked, not trusted)
-                if (mv.rcoef[k] < 0.0) sc.nonneg = false;
-                sc.amax += mv.rcoef[k] * ub[mv.rcol[k]];
-            }
-        } else scan(tail, e, sc);   // (a row with a shared list: its own terms behind the list; any other row: all of it)
-        if (!sc.multi && !sc.has_g && sc.b0 >= 0) {  // a row of one block
-            if (mv.row_implied && mv.row_implied[i]) continue;  // implied for integer points by the block's other rows: the sweeps solve the blocks in integers
-            if (is_le && sc.nonneg && sc.amax <= rhs * (1.0 + 1e-12) + 1e-9) continue;  // no point within the column bounds can violate it
-            if (!is_le || !sc.nonneg || rhs < 0.0) return "block row that is not a packing row";
-            const int b0 = sc.b0, r = T.blk_m[b0];
-            if (r >= MMAX_BLOCK) return "block with more than 4 rows";
-            // identical workers repeat the same few coefficient lists: a list seen before (compared as the doubles it is) has its grid integers and their gcd ready —
-            // no product, rounding and 64-bit remainder per term
-            const int nt = e - a;
-            const RowMemo *hit = nullptr;
-            for (const RowMemo &rm : row_memo) if (rm.n == nt && memcmp(rm.raw, mv.rcoef + a, (size_t)nt * sizeof(double)) == 0) { hit = &rm; break; }
-            if (!hit) {
-                if (nt > 64) return "block row with more than 64 terms";
-                long long vi[64], g = 0;
-                for (int k = 0; k < nt; k++) {
-                    const double v = mv.rcoef[a + k] * GRID, rv = round_fast(v);
-                    if (rv < 1.0 || std::fabs(v - rv) > 1e-6 * std::max(1.0, rv) || rv >= 4.0e15) return "block row off the ResourceAmount grid";
-                    vi[k] = (long long)rv;
-                    g = gcd_ll(g, vi[k]);
-                }
-                if (g < 1) g = 1;
-                RowMemo &rm = nt <= 32 ? row_memo[memo_next++ % 8] : memo_big;
-                rm.n = nt <= 32 ? nt : -1; rm.g = g;
-                if (nt <= 32) memcpy(rm.raw, mv.rcoef + a, (size_t)nt * sizeof(double));
-                for (int k = 0; k < nt; k++) rm.scaled[k] = (double)(vi[k] / g);
-                hit = &rm;
-            }
-            const long long g = hit->g;
-            const double capv = rhs * GRID;
-            if (capv >= 4.0e15) return "block row capacity too large";
-            const long long capi = (long long)std::floor(capv + 1e-6);
-            for (int k = 0; k < nt; k++) T.col_a[(size_t)P.flat_of[mv.rcol[a + k]] * MMAX_BLOCK + r] += hit->scaled[k];  // (duplicate terms of one row are summed)
-            T.blk_cap[(size_t)b0 * MMAX_BLOCK + r] = (double)(capi / g);
-            T.blk_m[b0] = (uint8_t)(r + 1);
-            continue;
-        }
-        if (!is_le && !is_ge) return "equality or range row across blocks";
-        if (is_le && sc.nonneg && sc.amax <= rhs * (1.0 + 1e-12) + 1e-9) continue;   // vacuous within the column bounds
-        if (is_ge && sc.nonneg && rhs <= 1e-12) continue;                            // holds at zero
-        if (!sc.multi && sc.has_g && sc.n_bcols >= 1 && is_le && sc.nonneg) {  // one block + flags: a conditional bound of the block's column(s)
-            if (sc.n_bcols != 1) return "conditional bound over several columns of a block";
-            CapRow cr; cr.flat = -1; cr.rhs = 0.0;
-            double cx = 0.0;
-            for (int k = a; k < e; k++) if (blk[mv.rcol[k]] >= 0) { cr.flat = P.flat_of[mv.rcol[k]]; cx = mv.rcoef[k]; }
-            if (!(cx > 0.0)) return "conditional bound with a zero coefficient";
-            cr.rhs = rhs / cx;
-            for (int k = a; k < e; k++) if (blk[mv.rcol[k]] < 0) cr.g.push_back({gidx[mv.rcol[k]], mv.rcoef[k] / cx});
-            P.caps.push_back(std::move(cr));
-            continue;
-        }
-        if (sc.n_bcols == 0) return "row over global columns only";
-        WideRow w; w.ge = is_ge ? 1 : 0;
-        const double sign = is_le ? 1.0 : -1.0;
-        w.h = sign * rhs;
-        if (fam_row) {
-            w.lhs_key = 2 * L + (is_ge ? 1 : 0);
-        } else { w.lhs_key = -1; w.own = (int)own_lists.size(); own_lists.emplace_back(); own_lists.back().reserve((size_t)(e - a)); }
-        for (int k = tail; k < e; k++) {
-            const int j = mv.rcol[k];
-            const double v = sign * mv.rcoef[k];
-            if (blk[j] < 0) { w.g.push_back({gidx[j], v}); continue; }
-            if (fam_row) return "block column behind a shared list";
-            const double rv = round_fast(v);
-            if (std::fabs(v - rv) > 1e-7 * std::max(1.0, std::fabs(rv)) || std::fabs(rv) > 1.0e9) return "wide row with a non-integer coefficient";
-            if (rv != 0.0) own_lists.back().push_back({P.flat_of[j], (int32_t)rv});
-        }
-        P.row_terms += (size_t)(e - a) - w.g.size() + (fam_row ? (size_t)fam[(size_t)L].len : 0);
-        wide.push_back(std::move(w));
-        if ((int)wide.size() > 1024) return "more than 1024 wide rows";
-    }
-    
-    if (run_live) stamp_run(runs[run_i]);   // (a run whose rows are the model's last)
-    for (int b = 0; b < nb; b++) if (T.blk_m[b] == 0) {   // every resource row of this worker is slack at its column bounds: a never-binding row (the kernel wants one)
-        double total = 0.0;
-        for (uint32_t f = T.blk_off[b]; f < T.blk_off[b + 1]; f++) { T.col_a[(size_t)f * MMAX_BLOCK] = 1.0; total += (double)T.col_cap[f]; }
-        T.blk_cap[(size_t)b * MMAX_BLOCK] = total;
-        T.blk_m[b] = 1;
-    }
-    if (after_blocks && *after_blocks) (*after_blocks)();
-    P.K = (int)wide.size();
-    if (P.K == 0) return "no wide row";
-    P.h.resize(P.K); P.ge.resize(P.K); P.g_rows.assign(P.G, {});
-    // groups: rows with the same (list, sign) share one; lists of different families with the same content are merged too (build() does, by content), and the groups are
-    // numbered in the order of their first row — the numbering build() arrives at
-    P.grp_of.assign(P.K, -1);
-    std::vector<std::vector<std::pair<int, int32_t>>> lhs;
-    std::vector<uint64_t> lhs_hash;
-    std::vector<int> group_of_key((size_t)2 * n_lhs, -1);
-    auto materialise = [&](int key, std::vector<std::pair<int, int32_t>> &out) {   // the family's list with the row's sign, zero coefficients dropped
-        const int l = key >> 1;
-        const int32_t sign = (key & 1) ? -1 : 1;
-        const int k0 = mv.list_off[l], k1 = mv.list_off[l + 1];
-        out.resize((size_t)(k1 - k0));
-        std::pair<int, int32_t> *o = out.data(); const int *fo = P.flat_of.data();
-        for (int k = k0; k < k1; k++) o[k - k0] = {fo[mv.list_col[k]], sign};
-    };
-    auto hash_of = [](const std::vector<std::pair<int, int32_t>> &l) { uint64_t h = 1469598103934665603ull; for (auto &t : l) h = (h ^ ((uint64_t)(uint32_t)t.first | ((uint64_t)(uint32_t)t.second << 32))) * 1099511628211ull; return h; };
-    std::vector<std::pair<int, int32_t>> tmp;
-    for (int k = 0; k < P.K; k++) {
-        WideRow &w = wide[(size_t)k];
-        P.h[k] = w.h; P.ge[k] = w.ge;
-        for (auto &t : w.g) P.g_rows[t.first].push_back({k, t.second});
-        if (w.lhs_key >= 0 && group_of_key[(size_t)w.lhs_key] >= 0) { P.grp_of[k] = group_of_key[(size_t)w.lhs_key]; continue; }
-        std::vector<std::pair<int, int32_t>> *l;
-        if (w.lhs_key >= 0) { materialise(w.lhs_key, tmp); l = &tmp; } else l = &own_lists[(size_t)w.own];
-        const uint64_t hsh = hash_of(*l);
-        int g = -1;
-        for (size_t i = 0; i < lhs.size() && g < 0; i++) if (lhs_hash[i] == hsh && lhs[i] == *l) g = (int)i;
-        if (g < 0) { g = (int)lhs.size(); lhs.push_back(std::move(*l)); lhs_hash.push_back(hsh); }
-        if (w.lhs_key >= 0) group_of_key[(size_t)w.lhs_key] = g;
-        P.grp_of[k] = g;
-    }
-    P.KG = (int)lhs.size();
-    if (P.KG > KMAX_HOST) return "more than 128 distinct wide left-hand sides";
-    
-    finish_groups(P, lhs);
-    
-    P.base_cap = T.col_cap;
-    return nullptr;
-}
-
-// FNV-1a over everything the flattening leaves (tests: two ways of getting there must agree in every byte)
-uint64_t digest_of(const Prob &P) {
-    using hqmilp::fnv1a; using hqmilp::fnv1a_vec;
-    const HostTables &T = P.T;
-    uint64_t h = hqmilp::FNV_BASIS;
-    const uint32_t dims[3] = {T.n_blocks, T.n_cols, T.K}; h = fnv1a(h, dims, sizeof dims);
-    h = fnv1a_vec(h, T.blk_off); h = fnv1a_vec(h, T.blk_m); h = fnv1a_vec(h, T.blk_cap); h = fnv1a_vec(h, T.col_cost); h = fnv1a_vec(h, T.col_a); h = fnv1a_vec(h, T.col_cap);
-    h = fnv1a_vec(h, T.col_woff); h = fnv1a_vec(h, T.w_row); h = fnv1a_vec(h, T.w_coef);
-    const int dims2[3] = {P.K, P.G, P.KG}; h = fnv1a(h, dims2, sizeof dims2);
-    h = fnv1a_vec(h, P.h); h = fnv1a_vec(h, P.ge); h = fnv1a_vec(h, P.grp_of); h = fnv1a_vec(h, P.g_off); h = fnv1a_vec(h, P.g_col); h = fnv1a_vec(h, P.g_coef);
-    h = fnv1a_vec(h, P.gr_off); h = fnv1a_vec(h, P.gr_row); h = fnv1a_vec(h, P.gmodel); h = fnv1a_vec(h, P.gcost); h = fnv1a_vec(h, P.flat_of); h = fnv1a_vec(h, P.model_of);
-    h = fnv1a_vec(h, P.block_of_flat); h = fnv1a_vec(h, P.base_cap);
-    for (const CapRow &cr : P.caps) { h = fnv1a(h, &cr.flat, sizeof cr.flat); h = fnv1a(h, &cr.rhs, sizeof cr.rhs); for (auto &t : cr.g) { h = fnv1a(h, &t.first, sizeof t.first); h = fnv1a(h, &t.second, sizeof t.second); } }
-    for (const auto &gr : P.g_rows) { const uint64_t nn = gr.size(); h = fnv1a(h, &nn, 8); for (auto &t : gr) { h = fnv1a(h, &t.first, sizeof t.first); h = fnv1a(h, &t.second, sizeof t.second); } }
-    return h;
-}
-
-const char *build_from_model(const ModelView &mv, Prob &P, std::vector<double> &ub, std::vector<double> &c, double &cmax, const std::function<void()> *after_blocks = nullptr) {
-    const char *why = flatten_model(mv, P, ub, c, cmax, after_blocks);   // (the checking flatten below and flatten_for_probe have no hook)
-    if (!why && g_check_hints && mv.block_runs) {   // tests: everything the runs passed over, flattened block by block after all, must come out the same
-        ModelView plain = mv; plain.block_runs = nullptr; plain.n_block_runs = 0;
-        Prob P2; std::vector<double> ub2, c2; double cmax2 = 0.0;
-        const char *why2 = flatten_model(plain, P2, ub2, c2, cmax2);
-        if (why2 || digest_of(P2) != digest_of(P) || ub2 != ub || c2 != c || cmax2 != cmax) { g_hint_mismatches++; return "structure hint: a block run's tables differ from its blocks' own"; }
-    }
-    if (!why && mv.run_stats) *mv.run_stats += (uint64_t)P.run_blocks;
-    if (!why && mv.tables_digest) *mv.tables_digest = digest_of(P);
-    return why;
-}
-
-// The candidate point of a flag configuration against the flattened model, raised greedily (most valuable columns first) as far as the blocks' rows, the wide rows
-// and the conditional bounds allow — what CompSolver::polish_point does on the component's scaled rows.  The integers are exact here: block rows on their own grid,
-// wide rows with integer coefficients.  x: the model's columns (in / out).
-struct Polisher {
-    const Prob &P; int n;
-    explicit Polisher(const Prob &p, int n_) : P(p), n(n_) {}
-    bool run(std::vector<double> &x, double &value) const {
-        const HostTables &T = P.T; const int K = P.K, G = P.G;
-        if ((int)x.size() != n) return false;
-        std::vector<double> xf(T.n_cols), B(G);
-        for (uint32_t f = 0; f < T.n_cols; f++) { const double v = x[P.model_of[f]], rv = round_fast(v); if (v < -1e-9 || v > (double)P.base_cap[f] + 1e-9 || std::fabs(v - rv) > 1e-9) return false; xf[f] = rv; }
-        for (int g = 0; g < G; g++) { B[g] = x[P.gmodel[g]]; if (B[g] != 0.0 && B[g] != 1.0) return false; }
-        // block rows
-        std::vector<double> bact((size_t)T.n_blocks * MMAX_BLOCK, 0.0);
-        for (uint32_t b = 0; b < T.n_blocks; b++) {
-            double *ba = &bact[(size_t)b * MMAX_BLOCK];
-            for (uint32_t f = T.blk_off[b]; f < T.blk_off[b + 1]; f++) if (xf[f] != 0.0) for (int r = 0; r < MMAX_BLOCK; r++) ba[r] += T.col_a[(size_t)f * MMAX_BLOCK + r] * xf[f];
-            for (int r = 0; r < (int)T.blk_m[b]; r++) if (ba[r] > T.blk_cap[(size_t)b * MMAX_BLOCK + r]) return false;
-        }
-        // wide rows: activity per group, the flags' part per row
-        std::vector<double> ga(P.KG, 0.0), fl(K, 0.0);
-        for (int g = 0; g < P.KG; g++) for (int t = P.g_off[g]; t < P.g_off[g + 1]; t++) ga[g] += (double)P.g_coef[t] * xf[P.g_col[t]];
-        for (int g = 0; g < G; g++) if (B[g] != 0.0) for (auto &t : P.g_rows[g]) fl[t.first] += t.second * B[g];
-        for (int k = 0; k < K; k++) if (ga[P.grp_of[k]] + fl[k] > P.h[k] + 1e-9 * std::max(1.0, std::fabs(P.h[k]))) return false;
-        // conditional bounds with these flags
-        std::vector<double> cap(T.n_cols);
-        for (uint32_t f = 0; f < T.n_cols; f++) cap[f] = (double)P.base_cap[f];
-        for (const CapRow &cr : P.caps) { double r = cr.rhs; for (auto &t : cr.g) r -= t.second * B[t.first]; const double cc = std::floor(r + 1e-9); if (xf[cr.flat] > cc) return false; cap[cr.flat] = std::min(cap[cr.flat], cc); }
-        // The raise goes through the columns by descending cost (ties: ascending model column — CompSolver::polish_point's order).  Raising only ever uses room up, so
-        // a column whose own block has no room for one more of it NOW never gets any: the few that do are found first, and only those are ordered.
-        std::vector<int> order;
-        // (the same holds for the wide rows: a group whose tightest row has no room for the column's coefficient rules the column out for good — on an unsaturated
-        // tick the batch-size rows are tight after the rounding and nearly every worker has room: without this test 60 000 columns were candidates, for nothing)
-        std::vector<double> gslack(P.KG, INF);
-        for (int k = 0; k < K; k++) { const int g = P.grp_of[k]; gslack[g] = std::min(gslack[g], P.h[k] - (ga[g] + fl[k])); }
-        for (uint32_t b = 0; b < T.n_blocks; b++) {
-            const double *ba = &bact[(size_t)b * MMAX_BLOCK], *bc = &T.blk_cap[(size_t)b * MMAX_BLOCK];
-            const int mb = (int)T.blk_m[b];
-            for (uint32_t f = T.blk_off[b]; f < T.blk_off[b + 1]; f++) {
-                if (!(T.col_cost[f] > 0.0) || cap[f] - xf[f] < 1.0) continue;
-                bool room = true;
-                for (uint32_t e = T.col_woff[f]; e < T.col_woff[f + 1] && room; e++) { const double a = (double)T.w_coef[e]; if (a > 0.0 && gslack[T.w_row[e]] < 0.5 * a) room = false; }
-                for (int r = 0; r < mb && room; r++) { const double a = T.col_a[(size_t)f * MMAX_BLOCK + r]; if (a > 0.0 && bc[r] - ba[r] < a) room = false; }
-                if (room) order.push_back((int)f);
-            }
-        }
-        std::sort(order.begin(), order.end(), [&](int p, int q) { return T.col_cost[p] > T.col_cost[q] || (T.col_cost[p] == T.col_cost[q] && P.model_of[p] < P.model_of[q]); });
-        for (int f : order) {
-            double step = cap[f] - xf[f];
-            if (step < 1.0) continue;
-            const uint32_t b = (uint32_t)P.block_of_flat[f];
-            const double *ba = &bact[(size_t)b * MMAX_BLOCK];
-            for (int r = 0; r < (int)T.blk_m[b] && step >= 1.0; r++) { const double a = T.col_a[(size_t)f * MMAX_BLOCK + r]; if (a > 0.0) { const double room = T.blk_cap[(size_t)b * MMAX_BLOCK + r] - ba[r]; if (room < a) { step = 0.0; break; } step = std::min(step, std::floor(room / a + 1e-9)); } }
-            for (uint32_t e = T.col_woff[f]; e < T.col_woff[f + 1] && step >= 1.0; e++) {
-                const double a = (double)T.w_coef[e];
-                if (!(a > 0.0)) continue;   // (a `>=` row entered negated: more of the column only helps it)
-                const int g = T.w_row[e];
-                for (int q = P.gr_off[g]; q < P.gr_off[g + 1]; q++) { const int k = P.gr_row[q]; const double room = P.h[k] - (ga[g] + fl[k]); if (room < 0.5 * a) { step = 0.0; break; } step = std::min(step, std::floor(room / a + 1e-9)); }
-            }
-            if (step < 1.0) continue;
-            xf[f] += step;
-            double *bw = &bact[(size_t)b * MMAX_BLOCK];
-            for (int r = 0; r < MMAX_BLOCK; r++) bw[r] += T.col_a[(size_t)f * MMAX_BLOCK + r] * step;
-            for (uint32_t e = T.col_woff[f]; e < T.col_woff[f + 1]; e++) ga[T.w_row[e]] += (double)T.w_coef[e] * step;
-        }
-        double z = 0.0;
-        for (uint32_t f = 0; f < T.n_cols; f++) { x[P.model_of[f]] = xf[f]; z += T.col_cost[f] * xf[f]; }
-        for (int g = 0; g < G; g++) z += P.gcost[g] * B[g];
-        value = z;
-        return true;
-    }
-};
-
 }  // namespace
 
 Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, double deadline_s, bool trace, Sweeper &sw, double *cost_scale) {
@@ -1840,7 +1150,7 @@ Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, dou
     if (g_capture_cut) g_first_cut.clear();
     std::vector<double> ub, c; double cmax = 1.0;
     const std::function<void()> hook = [&S]() { S.launch_on_blocks(); };
-    if (const char *why = build_from_model(mv, S.P, ub, c, cmax, early_sweep_on() ? &hook : nullptr)) {
+    if (const char *why = flatten(mv, S.P, ub, c, cmax, early_sweep_on() ? &hook : nullptr)) {
         if (S.early_begun) sw.end();   // (refused behind the hook: a sweep may be in flight on tables that S.P owns — end() waits for it)
         Answer ans; ans.why = why; return ans;
     }
@@ -1850,23 +1160,15 @@ Answer solve_model(const ModelView &mv, double rel_gap, double time_limit_s, dou
     return run_solver(S, tp0);
 }
 
-void flatten_for_probe(const ModelView &mv, bool trace) {
-    Prob P; std::vector<double> ub, c; double cmax = 1.0;
-    const char *why = build_from_model(mv, P, ub, c, cmax);
-    if (trace) fprintf(stderr, "[price] flattened for the probe alone: %s\n", why ? why : "tables built");
-}
-
-void set_check_hints(bool on) { g_check_hints = on; g_hint_mismatches = 0; }
 void set_early_sweep(int on) { g_early_sweep = on; g_early_sweeps = 0; }
 uint32_t early_sweeps() { return g_early_sweeps; }
 void capture_first_cut(bool on) { g_capture_cut = on; g_first_cut.clear(); }
 const std::vector<unsigned char> &first_cut_bytes() { return g_first_cut; }
-int hint_mismatches() { return g_hint_mismatches; }
 
 Answer solve(const Request &rq, Sweeper &sw) {
     Solver S(rq, sw);
     const double tp0 = now_us();
-    if (const char *why = build(rq, S.P)) { Answer ans; ans.why = why; return ans; }
+    if (const char *why = flatten(rq, S.P)) { Answer ans; ans.why = why; return ans; }
     return run_solver(S, tp0);
 }
 
