@@ -105,6 +105,10 @@ HQ_CANCEL_NONE, HQ_CANCEL_ASSIGNED, HQ_CANCEL_PREFILLED, HQ_CANCEL_MN, HQ_CANCEL
 # hqtick_finish_last_routes (include/hqtick.h): what a batch position of hqtick_finish_tasks was; 1 to 3 are accepted, the others refused
 HQ_FINISH_NONE, HQ_FINISH_ASSIGNED, HQ_FINISH_MN, HQ_FINISH_RETRACTING, HQ_FINISH_REPEAT, HQ_FINISH_WRONG_WORKER, HQ_FINISH_PREFILLED = 0, 1, 2, 3, 4, 5, 6
 HQ_FINISH_ACCEPTED = (HQ_FINISH_ASSIGNED, HQ_FINISH_MN, HQ_FINISH_RETRACTING)
+# hqtick_fail_last_routes (include/hqtick.h): what a batch position of hqtick_fail_tasks was; 1 to 5 are accepted, the others refused
+(HQ_FAIL_NONE, HQ_FAIL_ASSIGNED, HQ_FAIL_MN, HQ_FAIL_PREFILLED, HQ_FAIL_RETRACTING, HQ_FAIL_WAITING, HQ_FAIL_REPEAT, HQ_FAIL_WRONG_WORKER, HQ_FAIL_NOT_WAITING,
+ HQ_FAIL_GONE) = range(10)
+HQ_FAIL_ACCEPTED = (HQ_FAIL_ASSIGNED, HQ_FAIL_MN, HQ_FAIL_PREFILLED, HQ_FAIL_RETRACTING, HQ_FAIL_WAITING)
 
 # hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
 HQ_CHECK_READY, HQ_CHECK_LEDGER, HQ_CHECK_GRAPH, HQ_CHECK_CROSS, HQ_CHECK_STRICT, HQ_CHECK_ALL = 1, 2, 4, 8, 16, 15

@@ -835,6 +835,87 @@ class SchedEnv:
                     released.append(c)
         return released
 
+    def fail_tasks(self, pairs) -> int:
+        """task_failed (server/reactor.rs:606-704) for the (task id, reporting worker or abi.HQ_NO_WORKER) pairs, in this order, with the reference's assertions
+        as refusals.  What a pair IS follows from the state before the batch and the pairs accepted before it:
+          Assigned/Running   reported by its worker: remove_sn_task (:631-644)                                            HQ_FAIL_ASSIGNED
+          RunningMultiNode   reported by its ROOT: reset_mn_task_workers (:625-628)                                        HQ_FAIL_MN
+          Prefilled          reported by its worker: remove_prefilled + remove_prefill_task (:645-653)                     HQ_FAIL_PREFILLED
+          Retracting         reported by the worker it is retracting FROM: try_remove_redirection (:654-663); one that      HQ_FAIL_RETRACTING
+                             still sat in its queue leaves it with the task
+          any of these reported by another worker (assert_eq!(worker_id, *w))                                             HQ_FAIL_WRONG_WORKER
+          any of these reported by HQ_NO_WORKER (assert!(task.is_waiting()), :668)                                        HQ_FAIL_NOT_WAITING
+          Waiting            reported by HQ_NO_WORKER                                                                      HQ_FAIL_WAITING
+          Waiting, finished or not here, reported by a worker ("Unknown task failed")                                     HQ_FAIL_NONE
+          a later pair of an id an earlier pair was accepted for, with the same reporter                                  HQ_FAIL_REPEAT
+          a pair by HQ_NO_WORKER of a task the closure of an earlier accepted pair has removed                            HQ_FAIL_GONE
+        A refused pair changes nothing.  An accepted task leaves the task map with its transitive consumers (collect_recursive_consumers, task.rs:235-250).
+        Returns the number of accepted pairs.  last_fail_kinds: per pair its abi.HQ_FAIL_* kind; last_fail_consumers: per pair the ascending ids of the
+        consumers it removed (client.on_task_error's argument; empty for a refused pair)."""
+        no = abi.HQ_NO_WORKER
+        accepted_by: Dict[int, int] = {}
+        removed: set = set()
+        self.last_fail_kinds: List[int] = []
+        self.last_fail_consumers: List[List[int]] = []
+        for tid, wid in pairs:
+            t = self.tasks.get(tid)
+            kind = None
+            if tid in accepted_by:
+                prev = accepted_by[tid]
+                if prev == no:
+                    kind = abi.HQ_FAIL_REPEAT if wid == no else abi.HQ_FAIL_NONE
+                else:
+                    kind = abi.HQ_FAIL_REPEAT if wid == prev else abi.HQ_FAIL_NOT_WAITING if wid == no else abi.HQ_FAIL_WRONG_WORKER
+            elif t is None or t.state == FINISHED:
+                kind = abi.HQ_FAIL_GONE if tid in removed and wid == no else abi.HQ_FAIL_NONE
+            elif wid == no:
+                kind = abi.HQ_FAIL_WAITING if t.state == WAITING else abi.HQ_FAIL_NOT_WAITING
+            elif t.state == WAITING:
+                kind = abi.HQ_FAIL_NONE
+            elif wid != (t.mn_workers[0] if t.state == RUNNING_MN else t.worker):
+                kind = abi.HQ_FAIL_WRONG_WORKER
+            self.last_fail_consumers.append([])
+            if kind is not None and kind != abi.HQ_FAIL_WAITING:
+                self.last_fail_kinds.append(kind)
+                continue
+            if kind is None and t.state in (ASSIGNED, RUNNING):
+                w = self.workers[wid]
+                w.assigned_tasks.discard(tid)
+                self._add(w, t.rq, t.rv)  # remove_sn_task  server/worker.rs:223-234
+                kind = abi.HQ_FAIL_ASSIGNED
+            elif kind is None and t.state == RUNNING_MN:
+                for w_id in t.mn_workers:
+                    self.workers[w_id].mn_task = None  # reset_mn_task  server/worker.rs:168-171
+                kind = abi.HQ_FAIL_MN
+            elif kind is None and t.state == PREFILLED:
+                self.workers[wid].prefilled_tasks.discard(tid)
+                self.prefill[t.rq][1].remove(tid)
+                kind = abi.HQ_FAIL_PREFILLED
+            elif kind is None:
+                assert t.state == RETRACTING
+                self._drop_redirection(t)
+                kind = abi.HQ_FAIL_RETRACTING
+            self.last_fail_kinds.append(kind)
+            accepted_by[tid] = wid
+            closure: set = set()
+            stack = list(t.consumers)
+            while stack:
+                x = stack.pop()
+                if x in closure or x == tid or self.tasks[x].state == FINISHED:
+                    continue
+                closure.add(x)
+                stack.extend(self.tasks[x].consumers)
+            for x in closure:
+                ct = self.tasks[x]
+                assert ct.state == WAITING, "a consumer of a failed task is Waiting (reactor.rs:681-684)"
+                self.ready[ct.rq].discard(x)
+                ct.state = FINISHED
+            removed |= closure
+            self.ready[t.rq].discard(tid)
+            t.state, t.worker = FINISHED, None
+            self.last_fail_consumers[-1] = sorted(closure)
+        return len(accepted_by)
+
     def _drop_redirection(self, t: Task):
         """try_remove_redirection (reactor.rs:592-604) of a Retracting task; a task the tick put back on the worker it is retracting from holds that worker's
         resources without a redirect entry (mapping.rs:69) and gives them back here as well (the ledger releases whatever entry the id has)"""

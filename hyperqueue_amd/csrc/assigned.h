@@ -107,6 +107,10 @@ hipError_t cancel(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *
 // wins, and the tables end as after release(the accepted ids in batch order).  A prefilled entry is never claimed.  retr_hit[k]: the position that claimed
 // override k (NONE: none did).  ctr[C_OUT]: the accepted positions (C_DONE of them left the table; the others are Retracting ids without an entry).
 hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
+// hqtick_fail_tasks: the four passes in their fail mode, the finish mode with fail_core.h's rule and HQ_FAIL_* kinds.  A reporter of HQ_NO_WORKER
+// makes a position _WAITING (accepted, nothing here to claim) or _NOT_WAITING; a prefilled entry reported by its worker is claimed and leaves as pf_remove takes it
+// (prefilled count down, no free row; counted in C_DONE and C_PF), so the tables end as after release(accepted ids in batch order) + pf_remove(those ids).
+hipError_t fail(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
 // A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
 // out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF)

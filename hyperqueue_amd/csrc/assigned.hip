@@ -1,5 +1,6 @@
 // Kernels of the assignment ledger (assigned.h).  gfx950 only.
 #include "assigned.h"
+#include "fail_core.h"
 #include "finish_core.h"
 
 #include "../../include/hqtick.h"
@@ -9,7 +10,10 @@ namespace hqasg {
 namespace {
 
 constexpr uint32_t TPB = 256;
-enum RelMode : int { M_RELEASE = 0, M_CANCEL = 1, M_FINISH = 2 };  // what the release's four passes run as (release / hqtick_cancel_tasks / hqtick_finish_tasks)
+enum RelMode : int { M_RELEASE = 0, M_CANCEL = 1, M_FINISH = 2, M_FAIL = 3 };  // what the release's four passes run as (release / hqtick_cancel_tasks / hqtick_finish_tasks / hqtick_fail_tasks)
+// the two modes with a reporter per position share their claims; what differs is the rule and its constants
+template <int MODE> __device__ __forceinline__ bool rep_accepted(uint32_t kind) { return MODE == M_FAIL ? hqfail::accepted(kind) : hqfinish::accepted(kind); }
+template <int MODE> __device__ __forceinline__ uint32_t rep_repeat(uint32_t kind) { return MODE == M_FAIL ? hqfail::after_claim(kind, true) : hqfinish::after_claim(kind, true); }
 inline unsigned nblk(uint64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 __device__ __forceinline__ uint32_t ht_hash(uint64_t k) {  // murmur3 finaliser (graph.hip's)
@@ -177,22 +181,27 @@ __device__ __forceinline__ uint32_t retr_find(const CancelCols &cc, uint64_t id)
 // FINISH (hqtick_finish_tasks): finish_core.h's rule decides from the entry, the override and the REPORTER of the position what the position is; only a position
 // with an accepted kind is eligible, and it claims the entry and the override of its id alike -- both atomicMin run over the same eligible positions, so both
 // name the same winner whatever order they arrive in.  A refused position keeps pos NONE: the later passes never see it.
+// FAIL (hqtick_fail_tasks): the same with fail_core.h's rule.  A prefilled entry reported by its worker IS claimed (pass 3 takes it out as the cancel mode does); a
+// _WAITING position (reporter HQ_NO_WORKER, neither entry nor override) is accepted but has nothing here to claim: the graph step settles its repeats.
 template <int MODE>
 __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, CancelCols cc, uint32_t *ctr) {
-    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH;
+    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH, FAIL = MODE == M_FAIL;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     uint32_t b = NONE;
     if (i < n) {
         b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
         if (MODE == M_RELEASE && b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled task is not running: unknown to a release
-        if (FINISH) {
+        if (FINISH || FAIL) {
             const uint32_t k = retr_find(cc, id[i]), rep = cc.reporter[i];
             const uint32_t cls = b == NONE ? hqfinish::E_SN : t.variant[b] == PF_VARIANT ? hqfinish::E_PF : t.variant[b] == MN_VARIANT ? hqfinish::E_MN : hqfinish::E_SN;
-            const uint32_t kind = hqfinish::kind_before_claim(b != NONE, cls, b != NONE && t.worker[b] == rep, k != NONE, k != NONE && cc.retr_wid[k] == rep);
+            const bool e_match = b != NONE && t.worker[b] == rep, o_match = k != NONE && cc.retr_wid[k] == rep;
+            const uint32_t kind = FAIL ? hqfail::kind_before_claim(b != NONE, cls, e_match, k != NONE, o_match, rep == HQ_NO_WORKER)
+                                       : hqfinish::kind_before_claim(b != NONE, cls, e_match, k != NONE, o_match);
             cc.kind[i] = (uint8_t)kind;
-            if (hqfinish::accepted(kind)) { if (k != NONE) atomicMin(&cc.retr_hit[k], i); }
+            if (rep_accepted<MODE>(kind)) { if (k != NONE) atomicMin(&cc.retr_hit[k], i); }
             else b = NONE;
-            if (b != NONE && t.variant[b] == PF_VARIANT) b = NONE;  // a prefilled entry is never claimed, not even under a Retracting override
+            // a prefilled entry is never claimed under a Retracting override, and by a finish not at all
+            if (b != NONE && t.variant[b] == PF_VARIANT && !(FAIL && kind == HQ_FAIL_PREFILLED)) b = NONE;
         }
         pos[i] = b;
         if (b != NONE) atomicMin(&t.claim[b], i);
@@ -207,15 +216,15 @@ __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *p
 // pass 2: per (worker row, resource) the position + 1 of the batch's last ALL entry
 template <int MODE>
 __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos, uint32_t *last_all, CancelCols cc, uint32_t *ctr) {
-    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH;
+    constexpr bool CANCEL = MODE == M_CANCEL, REPORTED = MODE == M_FINISH || MODE == M_FAIL, PF_LEAVES = MODE == M_CANCEL || MODE == M_FAIL;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool dup = false, bad = false;
     if (b != NONE) {
         const uint32_t row = row_of(r, t.worker[b]);
-        if (t.claim[b] != i) { pos[i] = NONE; dup = true; if (CANCEL) cc.kind[i] = HQ_CANCEL_REPEAT; if (FINISH) cc.kind[i] = (uint8_t)hqfinish::after_claim(cc.kind[i], true); }
+        if (t.claim[b] != i) { pos[i] = NONE; dup = true; if (CANCEL) cc.kind[i] = HQ_CANCEL_REPEAT; if (REPORTED) cc.kind[i] = (uint8_t)rep_repeat<MODE>(cc.kind[i]); }
         else if (t.variant[b] == MN_VARIANT) {}  // a multi-node task: no count, no entry of any resource (its rows are reset by pass 4)
-        else if (CANCEL && t.variant[b] == PF_VARIANT) {}  // a prefilled task: no count in a slot, no free row (pass 3 lowers its prefilled count)
+        else if (PF_LEAVES && t.variant[b] == PF_VARIANT) {}  // a prefilled task: no count in a slot, no free row (pass 3 lowers its prefilled count)
         else if (row == NONE) { pos[i] = NONE; bad = true; t.claim[b] = NONE; }  // (left in the table, unclaimed: a later batch finds it as before)
         else {
             const uint32_t slot = q.rq_off[t.rq[b]] + t.variant[b];
@@ -231,14 +240,16 @@ __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos
 // retracting from, whatever the ledger said, and any other position of that id is a repeat.
 // FINISH: the kinds are pass 1's; an eligible position of a Retracting id that did not win its override is a repeat (an id with no ledger entry has no other
 // pass to learn that from).  C_OUT counts the accepted positions: those that leave the table and the Retracting ids that had no entry.
+// FAIL: as FINISH, and a claimed prefilled entry leaves as in the cancel mode -- its prefilled count drops, no free row and no last-ALL word is touched, so the
+// order-dependent arithmetic of the other positions never sees it.  C_OUT counts the _WAITING positions too.
 template <int MODE>
 __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr) {
-    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH;
+    constexpr bool CANCEL = MODE == M_CANCEL, REPORTED = MODE == M_FINISH || MODE == M_FAIL, PF_LEAVES = MODE == M_CANCEL || MODE == M_FAIL;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool mn = false, pf = false;
     if (b != NONE) {
-        mn = t.variant[b] == MN_VARIANT; pf = CANCEL && t.variant[b] == PF_VARIANT;
+        mn = t.variant[b] == MN_VARIANT; pf = PF_LEAVES && t.variant[b] == PF_VARIANT;
         if (pf) {
             const uint32_t row = row_of(r, t.worker[b]), rq = t.rq[b];
             if (row != NONE && r.pf && rq < r.pf_stride) atomicSub(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
@@ -262,17 +273,17 @@ __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *
         }
     }
     bool acc = false;
-    if (FINISH && i < n) {
+    if (REPORTED && i < n) {
         uint32_t kind = cc.kind[i];
-        if (kind == HQ_FINISH_RETRACTING) {
+        if (kind == (MODE == M_FAIL ? HQ_FAIL_RETRACTING : HQ_FINISH_RETRACTING)) {
             const uint32_t k = retr_find(cc, id[i]);
-            if (k == NONE || cc.retr_hit[k] != i) { kind = hqfinish::after_claim(kind, true); cc.kind[i] = (uint8_t)kind; }
+            if (k == NONE || cc.retr_hit[k] != i) { kind = rep_repeat<MODE>(kind); cc.kind[i] = (uint8_t)kind; }
         }
-        acc = hqfinish::accepted(kind);
+        acc = rep_accepted<MODE>(kind);
     }
     wave_add(&ctr[C_DONE], b != NONE); wave_add(&ctr[C_MN], mn);
-    if (CANCEL) wave_add(&ctr[C_PF], pf);
-    if (FINISH) wave_add(&ctr[C_OUT], acc);
+    if (PF_LEAVES) wave_add(&ctr[C_PF], pf);
+    if (REPORTED) wave_add(&ctr[C_OUT], acc);
 }
 // reset_mn_task (worker.rs:172-175) of a row whose multi-node task has left the table: SN bit set, free row = total row, columns cleared
 __device__ __forceinline__ void mn_reset_row(const Table &t, const Rows &r, const MnRows &m, uint32_t row) {
@@ -503,6 +514,14 @@ hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *
     hipLaunchKernelGGL(k_rel_claim<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
     hipLaunchKernelGGL(k_rel_last_all<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
     hipLaunchKernelGGL(k_rel_apply<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
+    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
+    return hipGetLastError();
+}
+hipError_t fail(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_rel_claim<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_last_all<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }

@@ -19,5 +19,9 @@ struct Group {
 };
 // 3 launches per radix digit of W, then 2: everything is enqueued on s, nothing is waited for
 hipError_t group(const Group &g, hipStream_t s);
+// The stable sort of a grouping alone, for any key below W (hqtick_fail_tasks groups a closure's ascending ids by the batch position that owns them, W = the batch
+// size: graph.hip).  route [n]: the keys, anything not below W counts as W and ends up last; scratch: scratch_of(n, W).total u32 (its start[W] part is not touched).
+// *key / *pos: where in scratch the sorted keys and the positions 0 .. n - 1 in sorted order are.  3 launches per radix digit of W, nothing is waited for.
+hipError_t sort_rows(uint32_t n, uint32_t W, const uint32_t *route, uint32_t *scratch, const uint32_t **key, const uint32_t **pos, hipStream_t s);
 
 }  // namespace hqcancel

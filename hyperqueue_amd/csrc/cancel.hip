@@ -66,15 +66,15 @@ __global__ void __launch_bounds__(BLOCK) k_cancel_lists(FinArgs a) {
 
 }  // namespace
 
-hipError_t group(const Group &g, hipStream_t s) {
-    const Scratch sc = scratch_of(g.n, g.W);
-    uint32_t *key[2] = {g.scratch + sc.key0, g.scratch + sc.key1}, *pos[2] = {g.scratch + sc.pos0, g.scratch + sc.pos1};
-    const uint32_t nt = n_tiles_of(g.n), passes = passes_of(g.W);
+hipError_t sort_rows(uint32_t n, uint32_t W, const uint32_t *route, uint32_t *scratch, const uint32_t **key_out, const uint32_t **pos_out, hipStream_t s) {
+    const Scratch sc = scratch_of(n, W);
+    uint32_t *key[2] = {scratch + sc.key0, scratch + sc.key1}, *pos[2] = {scratch + sc.pos0, scratch + sc.pos1};
+    const uint32_t nt = n_tiles_of(n), passes = passes_of(W);
     int cur = 0;
     for (uint32_t p = 0; p < passes && nt; p++) {
         SortArgs a{};
-        a.n = g.n; a.W = g.W; a.shift = p * 8; a.n_tiles = nt; a.cnt = g.scratch + sc.cnt;
-        if (p == 0) a.route = g.route; else { a.key_in = key[cur]; a.pos_in = pos[cur]; }
+        a.n = n; a.W = W; a.shift = p * 8; a.n_tiles = nt; a.cnt = scratch + sc.cnt;
+        if (p == 0) a.route = route; else { a.key_in = key[cur]; a.pos_in = pos[cur]; }
         const int nxt = p == 0 ? 0 : cur ^ 1;
         a.key_out = key[nxt]; a.pos_out = pos[nxt];
         hipLaunchKernelGGL(k_cancel_count, dim3(nt), dim3(BLOCK), 0, s, a);
@@ -82,8 +82,16 @@ hipError_t group(const Group &g, hipStream_t s) {
         hipLaunchKernelGGL(k_cancel_scatter, dim3(nt), dim3(BLOCK), 0, s, a);
         cur = nxt;
     }
+    *key_out = key[cur]; *pos_out = pos[cur];
+    return hipGetLastError();
+}
+
+hipError_t group(const Group &g, hipStream_t s) {
+    const Scratch sc = scratch_of(g.n, g.W);
+    const uint32_t *key = nullptr, *pos = nullptr;
+    if (hipError_t r = sort_rows(g.n, g.W, g.route, g.scratch, &key, &pos, s); r != hipSuccess) return r;
     FinArgs f{};
-    f.n = g.n; f.W = g.W; f.key = key[cur]; f.pos = pos[cur]; f.id = g.id; f.wid = g.wid; f.route = g.route; f.kind = g.kind; f.start = g.scratch + sc.start;
+    f.n = g.n; f.W = g.W; f.key = key; f.pos = pos; f.id = g.id; f.wid = g.wid; f.route = g.route; f.kind = g.kind; f.start = g.scratch + sc.start;
     f.out_id = g.out_id; f.out_wid = g.out_wid; f.out_off = g.out_off; f.hdr = g.hdr; f.route_wid = g.route_wid; f.route_kind = g.route_kind; f.no_worker = g.no_worker;
     if (g.n) hipLaunchKernelGGL(k_cancel_mark, dim3((g.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, f);
     hipLaunchKernelGGL(k_cancel_lists, dim3(1), dim3(BLOCK), 0, s, f);

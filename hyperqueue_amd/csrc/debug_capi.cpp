@@ -9,6 +9,7 @@
 #include "audit_core.h"
 #include "cancel_core.h"
 #include "clock_core.h"
+#include "fail_core.h"
 #include "finish_core.h"
 #include "hb_order.h"
 #include "milp.h"
@@ -161,6 +162,17 @@ extern "C" int hqtick_debug_finish_kind(uint32_t n, const uint8_t *entry_found, 
     for (uint32_t i = 0; i < n; i++) {
         if (entry_class[i] > hqfinish::E_PF) return HQTICK_E_INVALID;
         kind[i] = (uint8_t)hqfinish::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, override_found[i] != 0, override_worker_match[i] != 0, earlier_accepted[i] != 0);
+    }
+    return (int)n;
+}
+// the rule of hqtick_fail_tasks on host arrays: fail_core.h's kind_of per position
+extern "C" int hqtick_debug_fail_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *override_found,
+                                      const uint8_t *override_worker_match, const uint8_t *reporter_none, const uint8_t *earlier_accepted, uint8_t *kind) {
+    if (n && (!entry_found || !entry_class || !entry_worker_match || !override_found || !override_worker_match || !reporter_none || !earlier_accepted || !kind)) return HQTICK_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (entry_class[i] > hqfail::E_PF) return HQTICK_E_INVALID;
+        kind[i] = (uint8_t)hqfail::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, override_found[i] != 0, override_worker_match[i] != 0, reporter_none[i] != 0,
+                                           earlier_accepted[i] != 0);
     }
     return (int)n;
 }

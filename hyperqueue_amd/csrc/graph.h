@@ -80,6 +80,18 @@ class Graph {
     int remove(uint64_t n, const uint64_t *id, bool recursive, hipStream_t s);
     // ... the same for ids that are already in device memory (hqtick_cancel_tasks: one staged copy for every step), beside out_id() as ReadySet::remove_device is
     int remove_device(uint64_t n, const uint64_t *dev_id, bool recursive, hipStream_t s);
+    // hqtick_fail_tasks' graph step: remove(recursive) of the positions whose dev_kind [n] (device, HQ_FAIL_*) is an accepted one, and per position
+    // the tasks it removes beyond its own: task c belongs to the smallest accepted position whose closure holds it.  The step can only refuse _WAITING positions
+    // (_NONE: the graph does not hold the id, _REPEAT: an earlier _WAITING position of the id, _GONE: an earlier position's closure holds it); *n_refused counts
+    // them and the final kinds are written to dev_kind and to host_kind (pinned memory as the device sees it).  *bad_pos: the smallest position of any other kind
+    // whose root an earlier position reaches (NONE: none; the lists are complete either way).  Returns how many tasks left (sorted ids in out_id()); n_unknown():
+    // accepted positions of a ledger / table kind whose id the graph does not hold.  The host waits grow with the closure's depth, not with n.
+    int fail_device(uint64_t n, const uint64_t *dev_id, uint8_t *dev_kind, uint8_t *host_kind, uint32_t *n_refused, uint32_t *bad_pos, hipStream_t s);
+    int fail_empty(uint64_t n);  // n positions with empty lists (no graph step ran)
+    // the lists of the last fail_device / fail_empty: off [fail_n() + 1] by batch position, ids ascending inside a position; pinned, valid until the next of them
+    uint32_t fail_n() const { return fail_n_; }
+    const uint32_t *fail_off() const { return fail_off_; }
+    const uint64_t *fail_ids() const { return fail_id_; }
     // test accessor: Task::get_unfinished_deps; 0xFFFFFFFF for an id that is not in the graph
     int unfinished(uint64_t n, const uint64_t *id, uint32_t *out, hipStream_t s);
     // EXTENSION (no reference counterpart, parity unpinned): the b-level of every task — longest path to a sink of what is still in the graph — into the low 32
@@ -118,8 +130,9 @@ class Graph {
     hqbuf::DevBuf d_htk, d_htv;
     hqbuf::DevBuf d_rn, d_ro, d_rl, d_edge, d_rn2, d_ro2, d_rl2, d_edge2;
     hqbuf::DevBuf d_bl;
-    hqbuf::DevBuf d_ctl, d_stage, d_eds, d_erk, d_okey, d_oval, d_out_id, d_out_prio, d_out_rq, d_big;
-    hqbuf::PinBuf h_ctl, h_stage, h_out;
+    hqbuf::DevBuf d_ctl, d_stage, d_eds, d_erk, d_okey, d_oval, d_out_id, d_out_prio, d_out_rq, d_big, d_fsort;
+    hqbuf::PinBuf h_ctl, h_stage, h_out, h_fail;
+    uint32_t fail_n_ = 0, fail_len_ = 0; const uint32_t *fail_off_ = nullptr; const uint64_t *fail_id_ = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint64_t cap_slots = 0, n_slots = 0, n_live_ = 0, cap_edges = 0, ht_cap = 0, ht_used = 0;  // ht_used = keys + tombstones
     uint32_t free_top = 0, run_top = 0, edge_top = 0, edges_dead = 0, batch_no = 0;

@@ -5,6 +5,8 @@
 #include <cstring>
 
 #include "../../include/hqtick.h"
+#include "cancel.h"
+#include "fail_core.h"
 #include "finish_core.h"
 
 namespace hqgraph {
@@ -318,6 +320,106 @@ __global__ void __launch_bounds__(256) k_g_remove_finalize(View v, const uint64_
     v.free_slot[atomicAdd(&v.ctl->free_top, 1u)] = sl;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ fail
+// task_failed for a batch (hqtick_fail_tasks): remove(recursive) of the accepted positions' ids, plus the OWNER of every task of the closure -- the
+// smallest accepted batch position whose closure holds it, which is who removes it when the handler runs position by position.  The owner is a minimum over the
+// roots that reach a task, so it is a function of the graph and the batch alone: the order in which atomics arrive never shows.  The labels live in tmp_base (add's
+// per-slot scratch, free between operations) and are computed while the closure's edges still exist, before k_g_remove_finalize.
+// Ctl::pad words of a fail: [0] the smallest position whose root holds a ledger / table kind and is reached from an earlier root (NONE: none), [1] the _WAITING
+// positions the graph refused, [2] whether the last labelling sweep lowered a label.
+enum FailPad : uint32_t { FP_BAD = 0, FP_REFUSED = 1, FP_CHANGED = 2 };
+// (1) one thread per position: an accepted position finds its slot and claims the task for the closure's list (k_g_remove_seed's claim).  An id the graph does not
+// hold: a _WAITING position becomes _NONE ("Unknown task failed"), any other accepted kind counts as unknown as it does for remove.
+__global__ void __launch_bounds__(256) k_g_fail_seed(View v, const uint64_t *__restrict__ ids, uint8_t *__restrict__ kind, uint32_t n, uint32_t *__restrict__ slot_of,
+                                                     uint64_t *__restrict__ okey, uint32_t *__restrict__ oval) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    bool got = false, unknown = false, refused = false; uint32_t sl = NONE;
+    if (i < n) {
+        const uint32_t k = kind[i];
+        if (hqfail::accepted(k)) {
+            sl = ht_find(v, ids[i]);
+            if (sl != NONE) got = atomicExch(&v.unfinished[sl], ST_FREE) != ST_FREE;
+            else if (k == HQ_FAIL_WAITING) { kind[i] = HQ_FAIL_NONE; refused = true; }
+            else unknown = true;
+        }
+        slot_of[i] = sl;
+    }
+    const uint32_t pos = wave_append(&v.ctl->n_out, got);
+    if (got) { okey[pos] = v.id[sl]; oval[pos] = sl; }
+    const uint32_t nu = (uint32_t)__popcll(__ballot(unknown)), nr = (uint32_t)__popcll(__ballot(refused));
+    if ((threadIdx.x & 63) == 0) { if (nu) atomicAdd(&v.ctl->n_unknown, nu); if (nr) atomicAdd(&v.ctl->pad[FP_REFUSED], nr); }
+}
+// (2) behind the BFS: every task of the closure starts without an owner ...
+__global__ void __launch_bounds__(256) k_g_fail_unlabel(View v, const uint32_t *__restrict__ oval, uint32_t total) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q < total) v.tmp_base[oval[q]] = NONE;
+}
+// ... (3) and a root is owned by the smallest accepted position that names it
+__global__ void __launch_bounds__(256) k_g_fail_label_roots(View v, uint32_t n, const uint32_t *__restrict__ slot_of) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n && slot_of[i] != NONE) atomicMin(&v.tmp_base[slot_of[i]], i);
+}
+__global__ void k_g_fail_clear_changed(View v) { v.ctl->pad[FP_CHANGED] = 0; }
+// (4) one labelling sweep over the found closure, wavefront per task: its consumers' owners are lowered to its own (atomicMin: a task first reached at depth 2
+// from position 5 and at depth 3 from position 1 ends with 1).  Sweeps repeat until one lowers nothing; a label read stale only delays that.
+__global__ void __launch_bounds__(256) k_g_fail_sweep(View v, const uint32_t *__restrict__ oval, uint32_t total) {
+    const uint32_t lane = threadIdx.x & 63, n_waves = gridDim.x * 4;
+    bool ch = false;
+    for (uint32_t q = (blockIdx.x * 256 + threadIdx.x) >> 6; q < total; q += n_waves) {
+        const uint32_t slot = oval[q];
+        const uint32_t l = __atomic_load_n(&v.tmp_base[slot], __ATOMIC_RELAXED);
+        if (l == NONE) continue;
+        for (uint32_t r = v.head[slot]; r != NONE; r = v.run_next[r]) {
+            const uint32_t off = v.run_off[r], len = v.run_len[r];
+            for (uint32_t e = lane; e < len; e += 64) {
+                const uint2 ed = v.edge[off + e];
+                if (v.gen[ed.x] == ed.y && atomicMin(&v.tmp_base[ed.x], l) > l) ch = true;
+            }
+        }
+    }
+    if (__ballot(ch) && lane == 0) atomicOr(&v.ctl->pad[FP_CHANGED], 1u);
+}
+// (5) the roots against their final labels.  A position that owns its own task stays accepted.  One whose task is owned by an earlier position OF THE SAME ID
+// is a repeat (only _WAITING positions can meet like that: the ledger's passes have settled the other kinds' claims).  One whose task an earlier position of
+// ANOTHER id reaches is that position's consumer: a _WAITING position becomes _GONE -- every position of that id does, none of them was accepted -- and any other
+// kind cannot occur on a consistent state and is reported (FP_BAD).  Nothing a position reads here is written here.  The final kinds go to the host.
+__global__ void __launch_bounds__(256) k_g_fail_roots(View v, uint8_t *__restrict__ kind, uint8_t *__restrict__ host_kind, uint32_t n, const uint32_t *__restrict__ slot_of) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    bool refused = false;
+    if (i < n) {
+        const uint32_t sl = slot_of[i];
+        if (sl != NONE) {
+            const uint32_t l = v.tmp_base[sl];
+            if (l == i) {}
+            else if (l < n && slot_of[l] == sl) { kind[i] = HQ_FAIL_REPEAT; refused = true; }
+            else if (kind[i] == HQ_FAIL_WAITING) { kind[i] = HQ_FAIL_GONE; refused = true; }
+            else { atomicMin(&v.ctl->pad[FP_BAD], i); }
+        }
+        host_kind[i] = kind[i];
+    }
+    const uint32_t nr = (uint32_t)__popcll(__ballot(refused));
+    if (nr && (threadIdx.x & 63) == 0) atomicAdd(&v.ctl->pad[FP_REFUSED], nr);
+}
+// (6) behind the output's sort by id: the owner of every task of the closure as the key of cancel.h's stable sort.  A task that is the root of its own owner is in
+// nobody's list: NONE, which sorts last.
+__global__ void __launch_bounds__(256) k_g_fail_keys(View v, const uint32_t *__restrict__ oval, const uint32_t *__restrict__ slot_of, uint32_t total, uint32_t n, uint32_t *__restrict__ key) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= total) return;
+    const uint32_t sl = oval[j], l = v.tmp_base[sl];
+    key[j] = l < n && slot_of[l] == sl ? NONE : l;
+}
+// (7) the lists: the ids in sorted order (a stable sort of ascending ids: ascending inside every position), and where position i's begin -- the first key >= i
+__global__ void __launch_bounds__(256) k_g_fail_lists(const uint32_t *__restrict__ key, const uint32_t *__restrict__ pos, const uint64_t *__restrict__ id, uint32_t total, uint32_t n,
+                                                      uint32_t *__restrict__ out_off, uint64_t *__restrict__ out_id) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j < total && key[j] < n) out_id[j] = id[pos[j]];
+    if (j <= n) {
+        uint32_t lo = 0, hi = total;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (key[mid] < j) lo = mid + 1; else hi = mid; }
+        out_off[j] = lo;
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------- misc
 __global__ void __launch_bounds__(256) k_g_unfinished(View v, const uint64_t *__restrict__ ids, uint32_t n, uint32_t *__restrict__ out) {
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -530,9 +632,10 @@ void Graph::clear() {
 
 void Graph::release() {
     for (hqbuf::DevBuf *b : {&d_id, &d_prio, &d_order, &d_rq, &d_unf, &d_gen, &d_head, &d_free, &d_tmpc, &d_tmpb, &d_htk, &d_htv, &d_rn, &d_ro, &d_rl, &d_edge, &d_rn2, &d_ro2,
-                             &d_rl2, &d_edge2, &d_ctl, &d_stage, &d_eds, &d_erk, &d_okey, &d_oval, &d_out_id, &d_out_prio, &d_out_rq, &d_big, &d_bl})
+                             &d_rl2, &d_edge2, &d_ctl, &d_stage, &d_eds, &d_erk, &d_okey, &d_oval, &d_out_id, &d_out_prio, &d_out_rq, &d_big, &d_bl, &d_fsort})
         b->release();
-    h_ctl.release(); h_stage.release(); h_out.release();
+    h_ctl.release(); h_stage.release(); h_out.release(); h_fail.release();
+    fail_n_ = fail_len_ = 0; fail_off_ = nullptr; fail_id_ = nullptr;
     if (ev0) hipEventDestroy(ev0);
     if (ev1) hipEventDestroy(ev1);
     ev0 = ev1 = nullptr; ready_ = false; cap_slots = cap_edges = ht_cap = 0;
@@ -769,6 +872,84 @@ int Graph::remove_device(uint64_t n, const uint64_t *dev_id, bool recursive, hip
     G_HIP(hipGetLastError());
     if (int rc = finish_output(s, false)) return rc;
     n_live_ -= n_out_;
+    return (int)n_out_;
+}
+
+int Graph::fail_empty(uint64_t n) {
+    fail_n_ = 0; fail_len_ = 0;
+    if (!h_fail.ensure((n + 1) * 4 + 64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc fail lists");
+    memset(h_fail.p, 0, (n + 1) * 4);
+    fail_n_ = (uint32_t)n; fail_off_ = h_fail.as<uint32_t>(); fail_id_ = nullptr;
+    return 0;
+}
+
+int Graph::fail_device(uint64_t n, const uint64_t *dev_id, uint8_t *dev_kind, uint8_t *host_kind, uint32_t *n_refused, uint32_t *bad_pos, hipStream_t s) {
+    n_out_ = 0; n_unknown_ = 0; *n_refused = 0; *bad_pos = NONE;
+    if (int rc = fail_empty(n)) return rc;
+    if (n == 0) return 0;
+    if (n > 0x03FFFFFFull) return fail(HQTICK_E_CAPACITY, "more than 2^26 failed tasks in one batch");
+    if (!init(s)) return fail(HQTICK_E_DEVICE, "dependency graph: device setup failed");
+    if (!d_erk.ensure(n * 4 + 64)) return fail(HQTICK_E_DEVICE, "hipMalloc graph staging");
+    View v = view();
+    Ctl *c = d_ctl.as<Ctl>();
+    uint32_t *slot_of = d_erk.as<uint32_t>();
+    uint64_t *okey = d_okey.as<uint64_t>(); uint32_t *oval = d_oval.as<uint32_t>();
+    G_HIP(hipMemsetAsync(&c->n_out, 0, 24, s));  // n_out, n_unknown, err, n_big, lev_begin, lev_end
+    G_HIP(hipMemsetAsync(&c->pad[FP_BAD], 0xFF, 4, s));
+    G_HIP(hipMemsetAsync(&c->pad[FP_REFUSED], 0, 8, s));
+    hipLaunchKernelGGL(k_g_fail_seed, dim3(nblk(n)), dim3(256), 0, s, v, dev_id, dev_kind, (uint32_t)n, slot_of, okey, oval);
+    G_HIP(hipEventRecord(ev0, s));
+    for (;;) {  // the closure, as remove(recursive) finds it
+        for (uint32_t l = 0; l < BFS_LEVELS_PER_SYNC; l++) {
+            hipLaunchKernelGGL(k_g_close_level, dim3(1), dim3(1), 0, s, v);
+            hipLaunchKernelGGL(k_g_remove_expand, dim3(512), dim3(256), 0, s, v, okey, oval);
+        }
+        hipLaunchKernelGGL(k_g_publish, dim3(1), dim3(64), 0, s, v, h_ctl.dev<Ctl>());
+        G_HIP(hipStreamSynchronize(s));
+        const Ctl hc = *h_ctl.as<Ctl>();
+        if (hc.n_out == hc.lev_end) break;  // the last level added nothing
+    }
+    const uint32_t total = h_ctl.as<Ctl>()->n_out;
+    if (total) {
+        const unsigned sweep_grid = std::min<unsigned>(512u, (total + 3) / 4);
+        hipLaunchKernelGGL(k_g_fail_unlabel, dim3(nblk(total)), dim3(256), 0, s, v, oval, total);
+        hipLaunchKernelGGL(k_g_fail_label_roots, dim3(nblk(n)), dim3(256), 0, s, v, (uint32_t)n, slot_of);
+        for (;;) {  // the owners: sweeps to the fixed point, BFS_LEVELS_PER_SYNC of them per wait (at most the closure's depth + 1 sweeps)
+            for (uint32_t l = 0; l < BFS_LEVELS_PER_SYNC; l++) {
+                hipLaunchKernelGGL(k_g_fail_clear_changed, dim3(1), dim3(1), 0, s, v);
+                hipLaunchKernelGGL(k_g_fail_sweep, dim3(sweep_grid), dim3(256), 0, s, v, oval, total);
+            }
+            hipLaunchKernelGGL(k_g_publish, dim3(1), dim3(64), 0, s, v, h_ctl.dev<Ctl>());
+            G_HIP(hipStreamSynchronize(s));
+            if (h_ctl.as<Ctl>()->pad[FP_CHANGED] == 0) break;
+        }
+    }
+    hipLaunchKernelGGL(k_g_fail_roots, dim3(nblk(n)), dim3(256), 0, s, v, dev_kind, host_kind, (uint32_t)n, slot_of);
+    G_HIP(hipEventRecord(ev1, s));
+    if (total) hipLaunchKernelGGL(k_g_remove_finalize, dim3(nblk(total)), dim3(256), 0, s, v, okey, oval, total);
+    G_HIP(hipGetLastError());
+    if (int rc = finish_output(s, false)) return rc;  // (waits: the pad words of k_g_fail_roots are in the published counters)
+    n_live_ -= n_out_;
+    *n_refused = h_ctl.as<Ctl>()->pad[FP_REFUSED]; *bad_pos = h_ctl.as<Ctl>()->pad[FP_BAD];
+    if (n_out_) {
+        // the closure's ascending ids grouped by owner: cancel.h's stable radix sort over (owner, index), W = the batch size
+        const hqcancel::Scratch sc = hqcancel::scratch_of(n_out_, (uint32_t)n);
+        const size_t o_ids = (((size_t)n + 1) * 4 + 7) & ~(size_t)7;
+        fail_n_ = 0; fail_off_ = nullptr; fail_id_ = nullptr;  // (the pinned block may move)
+        if (!d_fsort.ensure((sc.start + (size_t)n_out_) * 4 + 64) || !h_fail.ensure(o_ids + (size_t)n_out_ * 8 + 64)) return fail(HQTICK_E_DEVICE, "hipMalloc fail lists");
+        uint32_t *scratch = d_fsort.as<uint32_t>(), *key_in = scratch + sc.start;
+        const uint32_t *key = nullptr, *pos = nullptr;
+        hipLaunchKernelGGL(k_g_fail_keys, dim3(nblk(n_out_)), dim3(256), 0, s, v, oval, slot_of, n_out_, (uint32_t)n, key_in);
+        G_HIP(hqcancel::sort_rows(n_out_, (uint32_t)n, key_in, scratch, &key, &pos, s));
+        uint32_t *o_off = reinterpret_cast<uint32_t *>(h_fail.dev<unsigned char>());
+        uint64_t *o_id = reinterpret_cast<uint64_t *>(h_fail.dev<unsigned char>() + o_ids);
+        hipLaunchKernelGGL(k_g_fail_lists, dim3(nblk(std::max<uint64_t>(n_out_, n + 1))), dim3(256), 0, s, key, pos, d_out_id.as<uint64_t>(), n_out_, (uint32_t)n, o_off, o_id);
+        G_HIP(hipGetLastError());
+        G_HIP(hipStreamSynchronize(s));
+        fail_n_ = (uint32_t)n; fail_off_ = h_fail.as<uint32_t>(); fail_id_ = reinterpret_cast<const uint64_t *>(h_fail.as<unsigned char>() + o_ids);
+        fail_len_ = fail_off_[n];
+        if (fail_len_ > n_out_) { fail_empty(n); return fail(HQTICK_E_DEVICE, "dependency graph: the fail lists are out of range"); }
+    }
     return (int)n_out_;
 }
 

@@ -417,6 +417,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     ctx->h_up.release(); ctx->h_up2.release(); ctx->h_q.release();
     ctx->h_cancel_ids.release(); ctx->d_cancel_ids.release();
     ctx->h_finish_in.release(); ctx->d_finish_in.release();
+    ctx->h_fail_in.release(); ctx->d_fail_in.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -995,6 +996,85 @@ int hqtick_finish_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t 
     if (!ctx) { if (n) *n = 0; if (kind) *kind = nullptr; return HQTICK_E_INVALID; }
     if (n) *n = ctx->asg.finish_out.n;
     if (kind) *kind = ctx->asg.finish_out.kind;
+    return 0;
+}
+
+// ---- task_failed in one call: composed like hqtick_finish_tasks -- ids and reporting workers staged once, the ledger's passes in their fail mode,
+// the Retracting table, then the graph's closure with its owners and the ready set.  What is left when a later step fails after an earlier one succeeded: the
+// earlier ones stay done (ledger, then table, then graph and ready set), the consumer lists are empty, and hqtick_graph_remove(accepted ids, 1) finishes the job
+// (with hqtick_ready_remove of hqtick_graph_last_ids if it was the ready set's removal that failed).
+int hqtick_fail_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id) { return with_audit(ctx, [&]() -> int {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_fail_tasks", n, task_id && worker_id)) return rc;  // (the guard comes before any step: a refused call changes nothing)
+    if (n > 0x03FFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^26 failed tasks in one batch");
+    ctx->asg.fail_out = hqasg::Ledger::FinishOut{}; ctx->asg.last_unknown = 0;
+    if (int rc = ctx->graph.fail_empty(n)) return graph_fail(ctx, rc);
+    if (n == 0) return 0;
+    const size_t o_wid = (size_t)n * 8;
+    if (!ctx->h_fail_in.ensure((size_t)n * 12 + 16) || !ctx->d_fail_in.ensure((size_t)n * 12 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc fail staging");
+    memcpy(ctx->h_fail_in.p, task_id, (size_t)n * 8); memcpy(ctx->h_fail_in.as<unsigned char>() + o_wid, worker_id, (size_t)n * 4);
+    HQ_HIP(hipMemcpyAsync(ctx->d_fail_in.p, ctx->h_fail_in.p, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t *d_ids = ctx->d_fail_in.as<uint64_t>();
+    const uint32_t *d_wid = reinterpret_cast<const uint32_t *>(ctx->d_fail_in.as<unsigned char>() + o_wid);
+    // 1: the ledger's entries and the kinds; the Retracting table's (task, worker it is retracting from) pairs ride along as overrides
+    std::vector<uint64_t> retr_id; std::vector<uint32_t> retr_wid;
+    ctx->retr.sources(&retr_id, &retr_wid);
+    const uint32_t *hit = nullptr;
+    int accepted = ledger_fail(ctx, ctx->asg.fail_tasks(ledger_env(ctx), n, d_ids, d_wid, (uint32_t)retr_id.size(), retr_id.data(), retr_wid.data(), &hit));
+    if (accepted < 0) { ctx->asg.fail_out = hqasg::Ledger::FinishOut{}; return accepted; }
+    hqasg::Ledger::FinishOut &out = ctx->asg.fail_out;
+    uint8_t *kinds = const_cast<uint8_t *>(out.kind);  // (the ledger's pinned block; the graph step's refusals are written into it)
+    // 2: try_remove_redirection's other half: the accepted Retracting tasks leave the table, and the resident ready set if they still sat in their queue
+    std::vector<uint64_t> queued;
+    for (size_t k = 0; hit && k < retr_id.size(); k++) {
+        if (hit[k] == hqasg::NONE) continue;
+        uint32_t old_id = 0; bool in_queue = false;
+        if (ctx->retr.find(retr_id[k], &old_id, &in_queue) && in_queue) queued.push_back(retr_id[k]);
+        ctx->retr.cancel(retr_id[k]);
+    }
+    if (!queued.empty() && ctx->ready.cols().n) { if (int rc = ready_fail(ctx, ctx->ready.remove(ready_env(ctx), queued.size(), queued.data())); rc < 0) return rc; }
+    // 3 / 4: the accepted ids and their transitive consumers leave graph and ready set; every consumer goes to the smallest accepted position that reaches it
+    if (ctx->graph.resident()) {
+        uint32_t refused = 0, bad = hqasg::NONE;
+        const int r = accepted > 0 ? ctx->graph.fail_device(n, d_ids, const_cast<uint8_t *>(out.d_kind), out.kind_dev, &refused, &bad, ctx->stream)
+                                   : ctx->graph.remove_device(0, nullptr, true, ctx->stream);  // (nothing accepted: hqtick_graph_last_ids / _last_unknown answer as after an empty hqtick_graph_remove)
+        if (r < 0) { ctx->graph.fail_empty(n); return graph_fail(ctx, r); }
+        accepted -= (int)std::min<uint32_t>(refused, (uint32_t)accepted);
+        out.accepted = (uint32_t)accepted; ctx->asg.last_unknown = n - (uint32_t)accepted;
+        if (r > 0 && ctx->ready.cols().n) {
+            if (int rc = ready_fail(ctx, ctx->ready.remove_device(ready_env(ctx), ctx->graph.out_id(), (uint32_t)r)); rc < 0) { ctx->graph.fail_empty(n); return rc; }
+        }
+        if (bad != hqasg::NONE)
+            return fail(ctx, HQTICK_E_INVALID, "hqtick_fail_tasks: task " + std::to_string(task_id[bad]) + " holds a worker and is a transitive consumer of an earlier failed task of the batch");
+    } else {
+        // no graph: a _WAITING id is failed once (a later position is a repeat) and, like a Retracting one, just leaves the ready set if it sits there
+        std::vector<uint64_t> waiting;
+        for (uint32_t i = 0; i < n; i++) {
+            if (kinds[i] != HQ_FAIL_WAITING) continue;
+            if (std::find(waiting.begin(), waiting.end(), task_id[i]) != waiting.end()) { kinds[i] = HQ_FAIL_REPEAT; accepted--; continue; }
+            waiting.push_back(task_id[i]);
+        }
+        out.accepted = (uint32_t)accepted; ctx->asg.last_unknown = n - (uint32_t)accepted;
+        if (!waiting.empty() && ctx->ready.cols().n) { if (int rc = ready_fail(ctx, ctx->ready.remove(ready_env(ctx), waiting.size(), waiting.data())); rc < 0) return rc; }
+    }
+    return accepted;
+}); }
+
+int hqtick_fail_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind) {
+    if (!ctx) { if (n) *n = 0; if (kind) *kind = nullptr; return HQTICK_E_INVALID; }
+    if (n) *n = ctx->asg.fail_out.n;
+    if (kind) *kind = ctx->asg.fail_out.kind;
+    return 0;
+}
+
+int hqtick_fail_last_consumers(const hqtick_ctx *ctx, uint32_t *n, const uint32_t **consumer_off, const uint64_t **consumer_id) {
+    static const uint32_t zero_off[1] = {0};
+    if (!ctx) { if (n) *n = 0; if (consumer_off) *consumer_off = nullptr; if (consumer_id) *consumer_id = nullptr; return HQTICK_E_INVALID; }
+    const bool have = ctx->graph.fail_off() != nullptr;
+    if (n) *n = have ? ctx->graph.fail_n() : 0;
+    if (consumer_off) *consumer_off = have ? ctx->graph.fail_off() : zero_off;
+    if (consumer_id) *consumer_id = have ? ctx->graph.fail_ids() : nullptr;
     return 0;
 }
 

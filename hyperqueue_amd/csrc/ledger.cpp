@@ -8,7 +8,7 @@ namespace hqasg {
 void Ledger::release_all() {
     tab.release(); tab2.release(); for (RowPair *r : {&counts, &mn, &pf}) r->release();
     for (DevBuf &b : buf) b.release();
-    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release();
+    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release();
 }
 void Ledger::take_requests(const hqtick_snapshot *s) {
     const uint32_t Q = s->n_requests;
@@ -381,18 +381,28 @@ int Ledger::cancel(const Env &e, uint32_t n, const uint64_t *d_id, uint32_t n_re
 // task_finished on the ledger (hqtick_finish_tasks): the release's four passes in their finish mode behind one set of counters and ONE
 // synchronisation.  Ids and reporters are read where the caller staged them on the device; the kinds and the override hits come back into pinned memory behind
 // the passes, and the kinds stay on the device for the graph's skip input.
+// task_failed (hqtick_fail_tasks) is the same step in the passes' fail mode with pinned memory of its own (a fail leaves the last finish's kinds
+// alone): prefilled entries leave too, and the graph step behind it may still refuse _WAITING positions, so fail_out's kinds are final only after that.
 int Ledger::finish(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit) {
-    last_unknown = 0; finish_out = FinishOut{}; if (retr_hit) *retr_hit = nullptr;
+    return reported(e, false, n, d_id, d_reporter, n_retr, retr_id, retr_wid, retr_hit);
+}
+int Ledger::fail_tasks(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit) {
+    return reported(e, true, n, d_id, d_reporter, n_retr, retr_id, retr_wid, retr_hit);
+}
+int Ledger::reported(const Env &e, bool failing, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit) {
+    FinishOut &out = failing ? fail_out : finish_out;
+    hqbuf::PinBuf &h_out = failing ? h_fail : h_finish;
+    last_unknown = 0; out = FinishOut{}; if (retr_hit) *retr_hit = nullptr;
     if (!n) return 0;
     if (int rc = sync_req(e)) return rc;
     const size_t WR = (size_t)e.W * e.R, nr = n_retr;
     if (!buf[B_SCRATCH].ensure((size_t)n * 4 + WR * 12 + 16) || !buf[B_CANCEL].ensure(nr * 16 + (size_t)n + 64)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
-    if (!h_finish.ensure(nr * 16 + (size_t)n + 64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc finish kinds");
+    if (!h_out.ensure(nr * 16 + (size_t)n + 64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc finish kinds");
     Pack pk{nullptr, buf[B_SCRATCH].as<unsigned char>()};  // [delta W*R u64][pos n u32][last_all W*R u32]
     uint64_t *d_delta = pk.put<uint64_t>(nullptr, WR); uint32_t *d_pos = pk.put<uint32_t>(nullptr, n), *d_la = pk.put<uint32_t>(nullptr, WR);
     Pack dk{nullptr, buf[B_CANCEL].as<unsigned char>()};   // [override ids u64][override workers u32] (one copy) [hit u32][kind n u8]
     uint64_t *d_rid = dk.put<uint64_t>(nullptr, nr); uint32_t *d_rwid = dk.put<uint32_t>(nullptr, nr), *d_hit = dk.put<uint32_t>(nullptr, nr); uint8_t *d_kind = dk.put<uint8_t>(nullptr, n);
-    Pack hk{h_finish.as<unsigned char>(), h_finish.dev<unsigned char>()};  // in: the overrides; out: [hit u32][kind n u8]
+    Pack hk{h_out.as<unsigned char>(), h_out.dev<unsigned char>()};  // in: the overrides; out: [hit u32][kind n u8]
     const uint64_t *h_rid = hk.put(retr_id, nr); hk.put(retr_wid, nr);
     uint32_t *o_hit = hk.put<uint32_t>(nullptr, nr); uint8_t *o_kind = hk.put<uint8_t>(nullptr, n);
     HQ_HIP(hipMemsetAsync(d_delta, 0, WR * 8, e.stream));
@@ -402,16 +412,18 @@ int Ledger::finish(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_
         HQ_HIP(hipMemcpyAsync(d_rid, hk.host(h_rid), nr * 12, hipMemcpyHostToDevice, e.stream));
     }
     const CancelCols cc{nullptr, d_kind, d_rid, d_rwid, d_hit, n_retr, d_reporter};
-    if (int rc = counted(e.stream, "hqasg::finish", [&](uint32_t *ctr) {
-            hipError_t r = hqasg::finish(table(), req(), rows(e), mn_rows(mn.cur, e.W, mn_live), n, d_id, d_pos, d_la, d_delta, cc, ctr, e.stream);
+    if (int rc = counted(e.stream, failing ? "hqasg::fail" : "hqasg::finish", [&](uint32_t *ctr) {
+            hipError_t r = (failing ? hqasg::fail : hqasg::finish)(table(), req(), rows(e), mn_rows(mn.cur, e.W, mn_live), n, d_id, d_pos, d_la, d_delta, cc, ctr, e.stream);
             if (r == hipSuccess) r = hipMemcpyAsync(hk.host(o_kind), d_kind, n, hipMemcpyDeviceToHost, e.stream);
             if (r == hipSuccess && nr) r = hipMemcpyAsync(hk.host(o_hit), d_hit, nr * 4, hipMemcpyDeviceToHost, e.stream);
             return r; })) return rc;
     const uint32_t done = c[C_DONE], done_mn = std::min(c[C_MN], done), accepted = std::min(c[C_OUT], n);
+    const uint32_t done_pf = failing ? (uint32_t)std::min<uint64_t>(std::min(c[C_PF], done - done_mn), pf_live) : 0u;
     if (done_mn) flags_dirty = true;
-    n_live -= done - done_mn; mn_live -= std::min<uint64_t>(done_mn, mn_live); n_tomb += done; last_unknown = n - accepted; dirty_ = true;
+    if (done_pf) { pf_live -= done_pf; pf_dirty = true; }
+    n_live -= done - done_mn - done_pf; mn_live -= std::min<uint64_t>(done_mn, mn_live); n_tomb += done; last_unknown = n - accepted; dirty_ = true;
     if (c[C_BAD]) return fail(HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
-    finish_out = FinishOut{n, accepted, hk.host(o_kind), d_kind};
+    out = FinishOut{n, accepted, hk.host(o_kind), d_kind, o_kind};
     if (retr_hit) *retr_hit = hk.host(o_hit);
     return (int)accepted;
 }

@@ -45,8 +45,10 @@ class Ledger {
     CancelOut cancel_out;
     // hqtick_finish_last_routes: the kinds the last finish() wrote into pinned memory (n positions, `accepted` of them with an accepted kind); d_kind: the same
     // kinds where the passes left them on the device (the graph's skip input; valid until the next cancel() or finish())
-    struct FinishOut { uint32_t n = 0, accepted = 0; const uint8_t *kind = nullptr; const uint8_t *d_kind = nullptr; };
+    // (kind_dev: the pinned kinds as the device sees them -- the graph step of hqtick_fail_tasks writes the final kinds there)
+    struct FinishOut { uint32_t n = 0, accepted = 0; const uint8_t *kind = nullptr; const uint8_t *d_kind = nullptr; uint8_t *kind_dev = nullptr; };
     FinishOut finish_out;
+    FinishOut fail_out;  // hqtick_fail_last_routes: the same of the last fail_tasks(); `accepted` and the kinds are final after the graph step
 
     // ---- the C ABI's operations (arguments validated by the caller)
     int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
@@ -61,6 +63,9 @@ class Ledger {
     // (pinned, valid until the next finish): the batch position that was accepted for override k, NONE if none was.  Returns the number of accepted positions;
     // last_unknown is the number of refused ones.
     int finish(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
+    // hqtick_fail_tasks' ledger step: finish() in the passes' fail mode.  The tables end as after release(accepted ids, batch order) +
+    // unprefill(accepted ids); fail_out holds the kinds as the ledger sees them (a _WAITING position is accepted here).  Returns the accepted positions.
+    int fail_tasks(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
     int add_mn(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid);
     int mn_workers(const Env &e, uint64_t id, uint32_t *n, const uint32_t **wid);
     int lookup(const Env &e, uint32_t n, const uint64_t *id, uint32_t *wid, uint8_t *var);
@@ -147,13 +152,14 @@ class Ledger {
     int insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free, const uint32_t *col_rq);
     int mn_enter(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid, int check);
     int pf_leave(const Env &e, uint32_t n, const uint64_t *id, const uint8_t *var);
+    int reported(const Env &e, bool failing, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);  // finish() / fail_tasks()
 
     TableCols tab, tab2;      // the hash table; the target of a rebuild
     RowPair counts, mn, pf;   // counts u32 [W x stride]; [mn task u64 W][mn root u8 W][flags u8 W]; pf u32 [W x pf_stride]
     // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation,
     // a cancel's routes, overrides and sort scratch
     enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_N }; DevBuf buf[B_N];
-    hqbuf::PinBuf h_ctr, h_in, h_cancel, h_finish;  // (h_cancel: a cancel's overrides in, its lists and routes out; h_finish: a finish's overrides in, its kinds out)
+    hqbuf::PinBuf h_ctr, h_in, h_cancel, h_finish, h_fail;  // (h_cancel: a cancel's overrides in, its lists and routes out; h_finish / h_fail: a finish's / fail's overrides in, its kinds out)
     const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
     uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones
     uint32_t stride = 0; bool flags_dirty = false;  // (flags_dirty: a ledger call changed the flags column since the mirror read it)

@@ -499,6 +499,36 @@ class Tick:
         return {"accepted": int(accepted), "kind": abi._np(pk, n.value, np.uint8).copy() if n.value else np.zeros(0, np.uint8),
                 "released": self._graph_last_ids(), "graph_unknown": int(self._lib.hqtick_graph_last_unknown(self._ctx))}
 
+    # -- task_failed in one call (include/hqtick.h) ----------------------------------------------------------
+    def fail_tasks(self, task_id, worker_id) -> dict:
+        """hqtick_fail_tasks for the (id, reporting worker or HQ_NO_WORKER) pairs, in this order -> {"accepted": positions accepted, "kind": per batch position the
+        HQ_FAIL_* kind, "consumer_off" [n + 1] / "consumer_id": per position the tasks it removed beyond its own (ascending), "removed": hqtick_graph_last_ids
+        (the accepted ids and all lists), "graph_unknown": hqtick_graph_last_unknown}"""
+        t = np.ascontiguousarray(task_id, np.uint64); w = np.ascontiguousarray(worker_id, np.uint32)
+        assert len(t) == len(w)
+        f = self._lib.hqtick_fail_tasks
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p]
+        accepted = self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p)))
+        return {"accepted": int(accepted), **self.fail_last()}
+
+    def fail_last(self) -> dict:
+        """hqtick_fail_last_routes / hqtick_fail_last_consumers and the graph's last ids as numpy copies (also after a call that returned an error)"""
+        n = C.c_uint32(); pk = abi.u8p()
+        g = self._lib.hqtick_fail_last_routes
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pk)))
+        m = C.c_uint32(); po = abi.u32p(); pi = abi.u64p()
+        h = self._lib.hqtick_fail_last_consumers
+        h.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u32p), C.POINTER(abi.u64p)]
+        self._chk(h(self._ctx, C.byref(m), C.byref(po), C.byref(pi)))
+        off = abi._np(po, m.value + 1, np.uint32).copy()
+        total = int(off[-1])
+        self._lib.hqtick_graph_last_unknown.restype = C.c_uint64
+        self._lib.hqtick_graph_last_unknown.argtypes = [C.c_void_p]
+        return {"kind": abi._np(pk, n.value, np.uint8).copy() if n.value else np.zeros(0, np.uint8), "consumer_off": off,
+                "consumer_id": abi._np(pi, total, np.uint64).copy() if total else np.zeros(0, np.uint64),
+                "removed": self._graph_last_ids(), "graph_unknown": int(self._lib.hqtick_graph_last_unknown(self._ctx))}
+
     def retracting_started(self, started) -> int:
         """hqtick_retracting_started for [(task, worker id it runs on, rq, variant, priority)]: task_running of Retracting tasks -> number started"""
         started = list(started)

@@ -682,6 +682,54 @@ int hqtick_retracting_started(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_
                               const uint64_t *priority);
 
 /*
+ * Failing tasks on the resident state in one call (functions added under ABI 12): task_failed (server/reactor.rs:606-704) for a batch of
+ * WorkerTaskUpdate::Failed and of the server's own task_failed(None, ..) (tasks that crashed on lost workers, reactor.rs:164-183), in the order the reactor saw
+ * them, on everything the context keeps resident.  Ids and reporting workers are staged once (12 B per position); the ledger and the graph read that one copy.
+ *   hqtick_fail_tasks   worker_id[i] is the worker whose TaskUpdates carried the failure of task_id[i], or HQ_NO_WORKER for the server's own call; a batch may mix
+ *       workers.  It needs a resident ready set and an enabled ledger; the graph and the prefilled tracking are optional.  Every position gets an HQ_FAIL_* kind.
+ *       _ASSIGNED, _MN, _PREFILLED, _RETRACTING and _WAITING are ACCEPTED: the reporter is the worker of the single-node or prefilled entry, the root of the
+ *       multi-node entry, the worker a task in the table of hqtick_retracting_* is retracting FROM (the table decides first, whatever the ledger names), or
+ *       HQ_NO_WORKER for an id with neither.  Every other kind is REFUSED and changes nothing anywhere: _NONE ("Unknown task failed"), _WRONG_WORKER (the
+ *       reference's assert_eq!(worker_id, *w)), _NOT_WAITING (assert!(task.is_waiting())), _REPEAT (an earlier position was accepted for the id), _GONE (a
+ *       _WAITING position whose task an earlier accepted position's closure has removed).  A refused position claims nothing: a later position of the same id with
+ *       the right reporter is still accepted.  The kinds follow from the state before the batch and the claims of its positions; the state afterwards is that of
+ *       the handler applied to the accepted positions in batch order:
+ *       ledger      as hqtick_assigned_release(accepted ids) leaves it (the last-ALL rule, multi-node rows reset, SN bits back; for a Retracting id with a redirect
+ *                   the redirect target's entry is released), and a _PREFILLED entry leaves as by hqtick_assigned_unprefill: the prefilled count drops, no free
+ *                   row is touched.  Without prefilled tracking a failing Prefilled task has no entry and is _NONE: the host holds those sets and routes it
+ *                   itself (task_queues.remove_prefilled + hqtick_graph_remove).
+ *       Retracting  accepted _RETRACTING ids leave the table; one that still sat in its queue leaves the resident ready set too.
+ *       graph       with a graph (one that has held a task): the accepted ids and their transitive consumers leave graph and ready set as after
+ *                   hqtick_graph_remove(accepted ids, 1); hqtick_graph_last_ids / _last_unknown answer as after that call.  A _WAITING position whose id the graph
+ *                   does not hold becomes _NONE.  Without a graph _WAITING and _RETRACTING ids just leave the ready set if they sit there.
+ *     Returns the number of accepted positions after the graph step; hqtick_assigned_last_unknown is the number of refused ones.  HQTICK_E_INVALID without a
+ *     resident ready set, with the ledger off, with a two-call tick's placement pending or with a NULL array (nothing changes then); HQTICK_E_CAPACITY for
+ *     n > 2^26; n = 0 returns 0 and leaves empty lists.  If a step fails after an earlier one succeeded the earlier ones stay done (the ledger first, then the
+ *     table, then graph and ready set): hqtick_graph_remove(accepted ids, 1) finishes the job and the consumer lists are empty.  An accepted position of a
+ *     ledger or table kind whose task an earlier accepted position reaches cannot occur on a state hqtick_resident_check accepts: every step completes by the same
+ *     rule and the call returns HQTICK_E_INVALID, naming the task.
+ *   hqtick_fail_last_routes      per batch position its HQ_FAIL_* kind: pinned memory owned by the context, valid until the next hqtick_fail_tasks.
+ *   hqtick_fail_last_consumers   what client.on_task_error wants per failed task: consumer_off [n + 1] by batch position, consumer_id ascending inside a position.
+ *       Task c belongs to the SMALLEST accepted position whose closure holds it -- what the handler applied position by position gives.  A refused position has
+ *       an empty range; the failed task itself is never in its own list; a _GONE position's task is in the list of the position that removed it.  The accepted
+ *       ids and all lists together are hqtick_graph_last_ids.  Pinned memory owned by the context, valid until the next hqtick_fail_tasks; without a graph every
+ *       range is empty.
+ */
+#define HQ_FAIL_NONE         0   /* refused: reporter given, no entry, not in the table */
+#define HQ_FAIL_ASSIGNED     1   /* accepted: single-node entry (Assigned or Running), reporter is its worker */
+#define HQ_FAIL_MN           2   /* accepted: multi-node entry, reporter is its root */
+#define HQ_FAIL_PREFILLED    3   /* accepted: prefilled entry (tracking on), reporter is its worker */
+#define HQ_FAIL_RETRACTING   4   /* accepted: in the Retracting table, reporter is the worker it retracts FROM */
+#define HQ_FAIL_WAITING      5   /* accepted: reporter HQ_NO_WORKER, no entry, not in the table */
+#define HQ_FAIL_REPEAT       6   /* refused: an earlier position was accepted for this id */
+#define HQ_FAIL_WRONG_WORKER 7   /* refused: the reference's assert_eq!(worker_id, *w) */
+#define HQ_FAIL_NOT_WAITING  8   /* refused: reporter HQ_NO_WORKER but the id has an entry or is in the table (assert!(task.is_waiting())) */
+#define HQ_FAIL_GONE         9   /* refused by the graph step: a WAITING position whose id an earlier accepted position's closure removed ("Unknown task failed") */
+int hqtick_fail_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id);
+int hqtick_fail_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind);
+int hqtick_fail_last_consumers(const hqtick_ctx *ctx, uint32_t *n, const uint32_t **consumer_off, const uint64_t **consumer_id);
+
+/*
  * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
  * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
  * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.

@@ -263,6 +263,12 @@ int hqtick_debug_cancel_group(uint32_t n, uint32_t W, const uint32_t *route_row,
  * for a NULL array or a class above 2.  Not a product path. */
 int hqtick_debug_finish_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *override_found,
                              const uint8_t *override_worker_match, const uint8_t *earlier_accepted, uint8_t *kind);
+
+/* The decision rule of hqtick_fail_tasks (csrc/fail_core.h, the function the fail mode of the ledger's release passes calls per position) on HOST arrays, one
+ * entry per evaluated position: the inputs of hqtick_debug_finish_kind and reporter_none (the position was reported by HQ_NO_WORKER).  kind [n]: the HQ_FAIL_*
+ * kinds before the graph step.  Returns n, HQTICK_E_INVALID for a NULL array or a class above 2.  Not a product path. */
+int hqtick_debug_fail_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *override_found,
+                           const uint8_t *override_worker_match, const uint8_t *reporter_none, const uint8_t *earlier_accepted, uint8_t *kind);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
