@@ -109,6 +109,11 @@ HQ_FINISH_ACCEPTED = (HQ_FINISH_ASSIGNED, HQ_FINISH_MN, HQ_FINISH_RETRACTING)
 (HQ_FAIL_NONE, HQ_FAIL_ASSIGNED, HQ_FAIL_MN, HQ_FAIL_PREFILLED, HQ_FAIL_RETRACTING, HQ_FAIL_WAITING, HQ_FAIL_REPEAT, HQ_FAIL_WRONG_WORKER, HQ_FAIL_NOT_WAITING,
  HQ_FAIL_GONE) = range(10)
 HQ_FAIL_ACCEPTED = (HQ_FAIL_ASSIGNED, HQ_FAIL_MN, HQ_FAIL_PREFILLED, HQ_FAIL_RETRACTING, HQ_FAIL_WAITING)
+# hqtick_start_last_routes (include/hqtick.h): what a batch position of hqtick_start_tasks was; 1 to 4 are accepted, the others refused
+(HQ_START_NONE, HQ_START_ASSIGNED, HQ_START_MN, HQ_START_PREFILLED, HQ_START_RETRACTING, HQ_START_REPEAT, HQ_START_WRONG_WORKER, HQ_START_WRONG_VARIANT, HQ_START_RUNNING,
+ HQ_START_BAD_VARIANT) = range(10)
+HQ_START_ACCEPTED = (HQ_START_ASSIGNED, HQ_START_MN, HQ_START_PREFILLED, HQ_START_RETRACTING)
+HQ_START_ELIGIBLE = (HQ_START_ASSIGNED, HQ_START_PREFILLED, HQ_START_RETRACTING)  # the accepted kinds that claim their id (a multi-node position changes nothing)
 
 # hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
 HQ_CHECK_READY, HQ_CHECK_LEDGER, HQ_CHECK_GRAPH, HQ_CHECK_CROSS, HQ_CHECK_STRICT, HQ_CHECK_ALL = 1, 2, 4, 8, 16, 15

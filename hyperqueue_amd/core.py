@@ -342,12 +342,16 @@ class SchedEnv:
         as Waiting (add_ready_task: may dissolve lower-priority prefill sets); a task that is Retracting{old} and was REDIRECTED to the lost worker loses the
         redirect and goes back into its queue, still Retracting{old} (:89-94); its prefilled tasks move from the prefill set into the queue (:97-104).  Then every
         task Retracting{lost worker}: with a redirect it becomes Assigned{target} and the target gets its ComputeTasks message, without one it is Waiting
-        (:124-145).  Returns those messages as (task, target worker id, variant)."""
+        (:124-145).  Returns those messages as (task, target worker id, variant).  last_lost_running: the reference's running_tasks (:72-120), ascending -- the
+        lost worker's Running tasks and its multi-node task if it was the root: what client.on_worker_lost is told and what gets a crash counter."""
         w = self.workers.pop(wid)
         self.worker_map.remove(wid)
+        self.last_lost_running: List[int] = []
         if w.sn():
             for tid in sorted(w.assigned_tasks):
                 t = self.tasks[tid]
+                if t.state == RUNNING:
+                    self.last_lost_running.append(tid)
                 if t.state == RETRACTING:
                     assert self.redirects.pop(tid, None) is not None
                 else:
@@ -365,6 +369,7 @@ class SchedEnv:
             t = self.tasks[tid]
             assert t.state == RUNNING_MN
             if t.mn_workers[0] == wid:  # root: the task returns to its queue, the other nodes are free again
+                self.last_lost_running.append(tid)
                 for other in t.mn_workers[1:]:
                     if other in self.workers:
                         self.workers[other].mn_task = None
@@ -941,6 +946,57 @@ class SchedEnv:
         self._remove(w, t.rq, variant)
         w.assigned_tasks.add(tid)
         return True
+
+    def start_tasks(self, triples) -> int:
+        """task_running (server/reactor.rs:264-355) for the (task id, reporting worker, variant) triples, strictly in this order, over start_task /
+        start_prefilled_task / start_retracting_task, with the reference's assertions as refusals.  What a triple IS follows from the task's state before the
+        batch and from the triples that claimed the id before it:
+          Retracting         reported by the worker it is retracting FROM: the Retracting arm (:311-335)                   HQ_START_RETRACTING
+          Prefilled          reported by its worker: task_from_prefilled_to_started (:299-310)                             HQ_START_PREFILLED
+          either with a variant its request does not have                                                                  HQ_START_BAD_VARIANT
+          Assigned           reported by its worker with its variant (:290-298)                                            HQ_START_ASSIGNED
+          Assigned/Running   with another variant (assert_eq!(*assigned_rv_id, rv_id))                                     HQ_START_WRONG_VARIANT
+          Running            (unreachable!, :346-350)                                                                      HQ_START_RUNNING
+          RunningMultiNode   reported by its ROOT (:336-345): nothing changes, every such triple is accepted               HQ_START_MN
+          any of these reported by another worker                                                                          HQ_START_WRONG_WORKER
+          a later Assigned / Prefilled / Retracting triple of an id an earlier one started                                 HQ_START_REPEAT
+          Waiting, finished or not here                                                                                    HQ_START_NONE
+        A refused triple changes nothing.  Returns the number of accepted triples.  last_start_kinds: per triple its abi.HQ_START_* kind."""
+        before: Dict[int, Optional[Tuple]] = {}
+        claimed: set = set()
+        accepted = 0
+        self.last_start_kinds: List[int] = []
+        for tid, wid, v in triples:
+            t = self.tasks.get(tid)
+            if tid not in before:
+                before[tid] = None if t is None else (t.state, t.mn_workers[0] if t.state == RUNNING_MN else t.worker, t.rv)
+            s = before[tid]
+            if s is None or s[0] in (WAITING, FINISHED):
+                kind = abi.HQ_START_NONE
+            elif wid != s[1]:
+                kind = abi.HQ_START_WRONG_WORKER
+            elif s[0] == RUNNING_MN:
+                kind = abi.HQ_START_MN
+            elif s[0] in (RETRACTING, PREFILLED):
+                kind = abi.HQ_START_BAD_VARIANT if not 0 <= v < len(self.requests[t.rq]) else abi.HQ_START_RETRACTING if s[0] == RETRACTING else abi.HQ_START_PREFILLED
+            elif v != s[2]:
+                kind = abi.HQ_START_WRONG_VARIANT
+            else:
+                kind = abi.HQ_START_RUNNING if s[0] == RUNNING else abi.HQ_START_ASSIGNED
+            if kind in abi.HQ_START_ELIGIBLE:
+                if tid in claimed:
+                    kind = abi.HQ_START_REPEAT
+                else:
+                    claimed.add(tid)
+                    if kind == abi.HQ_START_ASSIGNED:
+                        self.start_task(tid, v)
+                    elif kind == abi.HQ_START_PREFILLED:
+                        self.start_prefilled_task(tid, v)
+                    else:
+                        assert self.start_retracting_task(tid, wid, v)
+            accepted += kind in abi.HQ_START_ACCEPTED
+            self.last_start_kinds.append(kind)
+        return accepted
 
     # -- bookkeeping used by tests ----------------------------------------------------------------------
     def assigned_counts(self) -> List[int]:

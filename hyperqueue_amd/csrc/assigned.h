@@ -5,6 +5,7 @@
 // Layout:
 //   id -> entry: open-addressing hash table (linear probing, tombstones, rebuilt at half load), SoA columns indexed by bucket:
 //     key u64 (HT_EMPTY / HT_TOMB) | worker id u32 | rq u32 | variant u8 | priority u64 | claim u32 (batch position of a release, else NONE)
+//     | run u8 (1: the task was reported running; 0 on every entry that enters, and always on multi-node and prefilled entries)
 //   counts u32 [W x stride]: running tasks per (worker row, variant slot); slot = rq_variant_off[rq] + variant
 //   free / total rows: the resident worker set's own rows in HBM (hqtick_cluster_*), updated in place
 //   multi-node tasks (Worker::mn_task, server/worker.rs:134-175): three more columns per worker row, 10 B per row, re-packed with the count rows
@@ -33,7 +34,7 @@ constexpr uint8_t MN_VARIANT = 0xFF;                     // variant column of a 
 constexpr uint8_t PF_VARIANT = 0xFE;                     // variant column of a prefilled task's entry
 
 struct Table {
-    uint64_t *key; uint32_t *worker; uint32_t *rq; uint8_t *variant; uint64_t *prio; uint32_t *claim;
+    uint64_t *key; uint32_t *worker; uint32_t *rq; uint8_t *variant; uint64_t *prio; uint32_t *claim; uint8_t *run;
     uint32_t mask;  // capacity - 1 (a power of two)
 };
 // the request tables (ResourceRqMap) as the ledger needs them: rq -> variant slots -> entries
@@ -67,6 +68,7 @@ struct Items {
     const uint64_t *id; const uint32_t *wid; const uint32_t *rq; const uint8_t *variant; const uint64_t *prio;
     // rq / priority of an item with rq == RQ_LOOKUP: the ready-set columns, ids ascending
     const uint64_t *col_id; const uint64_t *col_prio; const uint32_t *col_rq; uint64_t col_n;
+    uint8_t run;  // the running byte every entry of the batch enters with (hqtick_retracting_started: 1)
 };
 // a tick's placement as the mapping kernel staged it in HBM (kernels.h: hqk::Stage), one entry per record; meta = variant | kind << 8, entries whose kind
 // is HQ_REC_PREFILL enter as PF_VARIANT entries when the prefilled tasks are tracked (Rows::pf) and are skipped otherwise.  The priority is levels[level] (the dense scan's level table, n_levels entries); levels == nullptr (the ordered view,
@@ -113,8 +115,9 @@ hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *
 hipError_t fail(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
 // A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
-// out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF)
-hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint32_t cap_out, uint32_t *ctr, hipStream_t s);
+// out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF); out_run [cap_out]: its running byte
+hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint8_t *out_run, uint32_t cap_out, uint32_t *ctr,
+                 hipStream_t s);
 // prefilled tasks (r.pf != nullptr in all four).  seed: item i (id, worker id, rq, priority) enters as a PF_VARIANT entry if the worker is resident and has its SN
 // bit, the request exists and the id is new (C_DONE entered; C_BAD / C_DUP refused).  start: the entry of id[i] takes variant[i]: pf count down, (row, slot)
 // count up, free.remove — all commuting atomics, one pass (C_DONE started; C_UNKNOWN not a prefilled entry, C_BAD no such variant).  remove: the entry leaves,
@@ -138,5 +141,16 @@ struct PfMove { const uint32_t *src; uint32_t src_stride; uint32_t *dst; uint32_
 hipError_t repack_counts(const uint32_t *src, uint32_t src_stride, uint32_t W_src, const uint32_t *src_row, uint32_t W_dst, uint32_t *dst, uint32_t dst_stride,
                          uint32_t n_cols, MnRows ms, MnRows md, const uint8_t *new_flags, hipStream_t s, PfMove pf = PfMove{});
 hipError_t lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant, hipStream_t s);
+hipError_t running(Table t, uint32_t n, const uint64_t *id, uint8_t *out_run, hipStream_t s);  // the running byte per id (0xFF: no entry)
+// hqtick_start_tasks: two passes over the staged positions [lo, hi) of a batch, one thread per position.  id / reporter / variant [n] are the
+// staged columns; mask [n] (nullptr: no position is left out) is nonzero for a position the host decides itself (an id of the Retracting table); pos [n] and kind
+// [n] are the passes' own.  start_claim evaluates start_core.h's rule on the tables as they are, writes the provisional kind and lets every _ASSIGNED /
+// _PREFILLED position claim its entry (atomicMin on the claim word).  start_apply: the winner sets the running byte, a prefilled entry also takes the winner's
+// variant with pf_start's arithmetic (all commuting atomics), and the claim word goes back to NONE -- the entry stays in the table, and a word left behind would
+// beat the next batch's claims; a loser becomes _REPEAT.  ctr: C_OUT accepted positions, C_PF started prefills, C_MN multi-node positions.
+struct StartCols { const uint64_t *id; const uint32_t *reporter; const uint8_t *variant; const uint8_t *mask; uint32_t *pos; uint8_t *kind; };
+hipError_t start_claim(Table t, Req q, Rows r, StartCols sc, uint32_t lo, uint32_t hi, hipStream_t s);
+hipError_t start_apply(Table t, Req q, Rows r, StartCols sc, uint32_t lo, uint32_t hi, uint32_t *ctr, hipStream_t s);
+hipError_t start_unclaim(Table t, StartCols sc, uint32_t lo, uint32_t hi, hipStream_t s);  // a start that ends early: the claims of [lo, hi) go back to NONE, nothing starts
 
 }  // namespace hqasg

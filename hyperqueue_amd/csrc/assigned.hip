@@ -2,6 +2,7 @@
 #include "assigned.h"
 #include "fail_core.h"
 #include "finish_core.h"
+#include "start_core.h"
 
 #include "../../include/hqtick.h"
 
@@ -82,13 +83,14 @@ __device__ __forceinline__ void free_remove(uint64_t *f, uint8_t kind, uint64_t 
 __global__ void k_clear(Table t) {
     const uint32_t b = blockIdx.x * TPB + threadIdx.x;
     if (b > t.mask) return;
-    t.key[b] = HT_EMPTY; t.claim[b] = NONE;
+    t.key[b] = HT_EMPTY; t.claim[b] = NONE; t.run[b] = 0;
 }
 
 enum InsertStatus : int { S_SKIP = 0, S_FRESH, S_MOVED, S_DUP, S_BAD, S_FULL, S_PF_IN, S_PF_OUT };  // (S_PF_IN: a prefilled entry entered; S_PF_OUT: one became an assigned entry)
 // the entry (id -> wid, rq, v, prio) enters its bucket and the count of (row, slot) is raised
+// (run: the running byte a fresh entry takes; an entry that is moved to another worker or variant is not running there yet)
 __device__ __forceinline__ int enter(const Table &t, const Req &q, const Rows &r, uint64_t id, uint32_t row, uint32_t wid, uint32_t rq, uint32_t v, uint64_t prio, int upsert,
-                                     int apply_free) {
+                                     int apply_free, uint8_t run = 0) {
     if (row >= r.W || id >= HT_TOMB) return S_BAD;
     if (!variant_ok(q, rq, v) || q.rq_off[rq] + v >= r.stride) return S_BAD;
     int fresh = 0; bool from_pf = false;
@@ -101,6 +103,7 @@ __device__ __forceinline__ int enter(const Table &t, const Req &q, const Rows &r
         if (from_pf) { if (orow != NONE && r.pf && t.rq[b] < r.pf_stride) atomicSub(&r.pf[(size_t)orow * r.pf_stride + t.rq[b]], 1u); }
         else if (orow != NONE) atomicSub(&r.counts[(size_t)orow * r.stride + q.rq_off[t.rq[b]] + t.variant[b]], 1u);
     }
+    if (fresh) t.run[b] = run; else if (t.worker[b] != wid || t.variant[b] != (uint8_t)v) t.run[b] = 0;
     t.worker[b] = wid; t.rq[b] = rq; t.variant[b] = (uint8_t)v; t.prio[b] = prio; t.claim[b] = NONE;
     const uint32_t slot = q.rq_off[rq] + v;
     atomicAdd(&r.counts[(size_t)row * r.stride + slot], 1u);
@@ -115,7 +118,7 @@ __device__ __forceinline__ int enter_pf(const Table &t, const Req &q, const Rows
     const uint32_t b = ht_claim(t, id, &fresh);
     if (b == NONE) return S_FULL;
     if (!fresh) return S_DUP;
-    t.worker[b] = wid; t.rq[b] = rq; t.variant[b] = PF_VARIANT; t.prio[b] = prio; t.claim[b] = NONE;
+    t.worker[b] = wid; t.rq[b] = rq; t.variant[b] = PF_VARIANT; t.prio[b] = prio; t.claim[b] = NONE; t.run[b] = 0;
     atomicAdd(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
     return S_PF_IN;
 }
@@ -144,7 +147,7 @@ __device__ __forceinline__ int insert_one(const Table &t, const Req &q, const Ro
         if (j == ~0ull) return S_BAD;
         rq = it.col_rq[j]; prio = it.col_prio[j];
     }
-    return enter(t, q, r, id, row, wid, rq, v, prio, upsert, apply_free);
+    return enter(t, q, r, id, row, wid, rq, v, prio, upsert, apply_free, it.run);
 }
 __global__ void k_insert(Table t, Req q, Rows r, Items it, int upsert, int apply_free, uint32_t *ctr) {
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
@@ -344,7 +347,7 @@ __global__ void k_mn_enter(Table t, Rows r, MnRows m, MnItems it, const uint32_t
             if (b == NONE) status = S_FULL;
             else if (!fresh) status = S_DUP;
             else {
-                t.worker[b] = it.wid[b0]; t.rq[b] = it.rq[i]; t.variant[b] = MN_VARIANT; t.prio[b] = prio; t.claim[b] = NONE;
+                t.worker[b] = it.wid[b0]; t.rq[b] = it.rq[i]; t.variant[b] = MN_VARIANT; t.prio[b] = prio; t.claim[b] = NONE; t.run[b] = 0;
                 for (uint32_t j = b0; j < b1; j++) {  // set_mn_task (worker.rs:160-166): the free row stays as it is
                     const uint32_t row = row_of(r, it.wid[j]);
                     m.task[row] = id; m.root[row] = j == b0 ? 1 : 0; m.flags[row] = (uint8_t)(m.flags[row] & ~HQ_WORKER_SN);
@@ -356,7 +359,8 @@ __global__ void k_mn_enter(Table t, Rows r, MnRows m, MnItems it, const uint32_t
     count_status(ctr, status);
 }
 
-__global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint32_t cap_out, uint32_t *ctr) {
+__global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint8_t *out_run, uint32_t cap_out,
+                        uint32_t *ctr) {
     const uint32_t b = blockIdx.x * TPB + threadIdx.x;
     const uint64_t k = b <= t.mask ? t.key[b] : HT_EMPTY;
     bool hit = false;
@@ -370,7 +374,7 @@ __global__ void k_evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t
     wave_add(&ctr[C_PF], hit && t.variant[b] == PF_VARIANT);  // (move_prefilled_task_to_ready; the row's prefilled counts go with the row in the re-pack)
     const uint32_t o = wave_append(&ctr[C_OUT], hit);
     if (!hit || o >= cap_out) return;  // (the host sized the output by its live count: more is reported as an error and nothing is written past the end)
-    out_id[o] = k; out_rq[o] = t.rq[b]; out_prio[o] = t.prio[b]; out_var[o] = t.variant[b];
+    out_id[o] = k; out_rq[o] = t.rq[b]; out_prio[o] = t.prio[b]; out_var[o] = t.variant[b]; out_run[o] = t.run[b];
     t.key[b] = HT_TOMB;
 }
 
@@ -416,6 +420,7 @@ __global__ void k_pf_start(Table t, Req q, Rows r, uint32_t n, const uint64_t *i
                 atomicSub(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
                 atomicAdd(&r.counts[(size_t)row * r.stride + slot], 1u);
                 for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) free_remove(&r.free_[(size_t)row * r.R + q.ent_res[e]], q.ent_kind[e], q.ent_amount[e]);
+                t.run[b] = 1;  // (the one thread that took the variant: the task runs)
                 done = true;
             }
         }
@@ -450,7 +455,7 @@ __global__ void k_rehash(Table from, Table to, uint32_t *ctr) {
     if (k < HT_TOMB) {
         int fresh = 0;
         d = ht_claim(to, k, &fresh);
-        if (d != NONE) { to.worker[d] = from.worker[b]; to.rq[d] = from.rq[b]; to.variant[d] = from.variant[b]; to.prio[d] = from.prio[b]; to.claim[d] = NONE; }
+        if (d != NONE) { to.worker[d] = from.worker[b]; to.rq[d] = from.rq[b]; to.variant[d] = from.variant[b]; to.prio[d] = from.prio[b]; to.claim[d] = NONE; to.run[d] = from.run[b]; }
     }
     wave_add(&ctr[C_DONE], k < HT_TOMB && d != NONE); wave_add(&ctr[C_FULL], k < HT_TOMB && d == NONE);
 }
@@ -475,6 +480,63 @@ __global__ void k_lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_
     const uint32_t b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
     out_wid[i] = b == NONE ? HQ_NO_WORKER : t.worker[b];
     out_variant[i] = b == NONE ? (uint8_t)0xFF : t.variant[b];
+}
+__global__ void k_running(Table t, uint32_t n, const uint64_t *id, uint8_t *out_run) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t b = id[i] < HT_TOMB ? ht_find(t, id[i]) : NONE;
+    out_run[i] = b == NONE ? (uint8_t)0xFF : t.run[b];
+}
+
+// ---- hqtick_start_tasks: task_running for the staged positions [lo, hi); a position with a mask byte is the host's (an id of the Retracting table)
+// pass 1: the bucket of every id and start_core.h's rule on the tables as they are.  Only an _ASSIGNED or _PREFILLED position keeps its bucket in pos and claims it;
+// every other position has pos NONE and is final here.
+__global__ void k_start_claim(Table t, Req q, Rows r, StartCols sc, uint32_t lo, uint32_t hi) {
+    const uint32_t i = lo + blockIdx.x * TPB + threadIdx.x;
+    if (i >= hi || (sc.mask && sc.mask[i])) return;
+    const uint64_t id = sc.id[i];
+    const uint32_t b = id < HT_TOMB ? ht_find(t, id) : NONE;
+    uint32_t kind = HQ_START_NONE;
+    if (b != NONE) {
+        const uint32_t ev = t.variant[b], v = sc.variant[i], rq = t.rq[b];
+        const uint32_t cls = ev == PF_VARIANT ? hqstart::E_PF : ev == MN_VARIANT ? hqstart::E_MN : hqstart::E_SN;
+        bool v_exists = false;
+        if (cls == hqstart::E_PF)  // what pf_start wants of the variant: the request has it, its slot and the row are in the tables
+            v_exists = v < PF_VARIANT && variant_ok(q, rq, v) && q.rq_off[rq] + v < r.stride && r.pf && rq < r.pf_stride && row_of(r, t.worker[b]) != NONE;
+        kind = hqstart::kind_before_claim(true, cls, t.worker[b] == sc.reporter[i], ev == v, t.run[b] != 0, v_exists, false, false);
+    }
+    const bool claims = kind == HQ_START_ASSIGNED || kind == HQ_START_PREFILLED;
+    sc.kind[i] = (uint8_t)kind; sc.pos[i] = claims ? b : NONE;
+    if (claims) atomicMin(&t.claim[b], i);
+}
+// pass 2: the winner of a claim starts its task and gives the claim word back; a loser is a repeat
+__global__ void k_start_apply(Table t, Req q, Rows r, StartCols sc, uint32_t lo, uint32_t hi, uint32_t *ctr) {
+    const uint32_t i = lo + blockIdx.x * TPB + threadIdx.x;
+    bool acc = false, pf = false, mn = false;
+    if (i < hi && !(sc.mask && sc.mask[i])) {
+        const uint32_t b = sc.pos[i];
+        if (b == NONE) mn = acc = sc.kind[i] == HQ_START_MN;
+        else if (t.claim[b] != i) sc.kind[i] = HQ_START_REPEAT;
+        else {
+            acc = true; pf = sc.kind[i] == HQ_START_PREFILLED;
+            if (pf) {  // task_from_prefilled_to_started with the winner's variant: k_pf_start's arithmetic; the claim made the writer of the byte unique
+                const uint32_t rq = t.rq[b], v = sc.variant[i], row = row_of(r, t.worker[b]), slot = q.rq_off[rq] + v;
+                t.variant[b] = (uint8_t)v;
+                atomicSub(&r.pf[(size_t)row * r.pf_stride + rq], 1u);
+                atomicAdd(&r.counts[(size_t)row * r.stride + slot], 1u);
+                for (uint32_t e = q.ventry_off[slot]; e < q.ventry_off[slot + 1]; e++) free_remove(&r.free_[(size_t)row * r.R + q.ent_res[e]], q.ent_kind[e], q.ent_amount[e]);
+            }
+            t.run[b] = 1;
+            t.claim[b] = NONE;  // the entry stays: a word left here would beat every later batch's claim of this id
+        }
+    }
+    wave_add(&ctr[C_OUT], acc); wave_add(&ctr[C_PF], pf); wave_add(&ctr[C_MN], mn);
+}
+__global__ void k_start_unclaim(Table t, StartCols sc, uint32_t lo, uint32_t hi) {
+    const uint32_t i = lo + blockIdx.x * TPB + threadIdx.x;
+    if (i >= hi || (sc.mask && sc.mask[i])) return;
+    const uint32_t b = sc.pos[i];
+    if (b != NONE && b <= t.mask) t.claim[b] = NONE;
 }
 
 }  // namespace
@@ -525,9 +587,10 @@ hipError_t fail(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
-hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint32_t cap_out, uint32_t *ctr, hipStream_t s) {
+hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint8_t *out_run, uint32_t cap_out, uint32_t *ctr,
+                 hipStream_t s) {
     if (!n_lost) return hipSuccess;
-    hipLaunchKernelGGL(k_evict, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, n_lost, lost, out_id, out_rq, out_prio, out_var, cap_out, ctr);
+    hipLaunchKernelGGL(k_evict, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, n_lost, lost, out_id, out_rq, out_prio, out_var, out_run, cap_out, ctr);
     return hipGetLastError();
 }
 hipError_t pf_seed(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint64_t *prio, uint32_t *ctr, hipStream_t s) {
@@ -573,6 +636,26 @@ hipError_t mn_reset_rows(Table t, Rows r, MnRows m, hipStream_t s) {
 hipError_t lookup(Table t, uint32_t n, const uint64_t *id, uint32_t *out_wid, uint8_t *out_variant, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_lookup, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, out_wid, out_variant);
+    return hipGetLastError();
+}
+hipError_t running(Table t, uint32_t n, const uint64_t *id, uint8_t *out_run, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_running, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, out_run);
+    return hipGetLastError();
+}
+hipError_t start_claim(Table t, Req q, Rows r, StartCols sc, uint32_t lo, uint32_t hi, hipStream_t s) {
+    if (lo >= hi) return hipSuccess;
+    hipLaunchKernelGGL(k_start_claim, dim3(nblk(hi - lo)), dim3(TPB), 0, s, t, q, r, sc, lo, hi);
+    return hipGetLastError();
+}
+hipError_t start_unclaim(Table t, StartCols sc, uint32_t lo, uint32_t hi, hipStream_t s) {
+    if (lo >= hi) return hipSuccess;
+    hipLaunchKernelGGL(k_start_unclaim, dim3(nblk(hi - lo)), dim3(TPB), 0, s, t, sc, lo, hi);
+    return hipGetLastError();
+}
+hipError_t start_apply(Table t, Req q, Rows r, StartCols sc, uint32_t lo, uint32_t hi, uint32_t *ctr, hipStream_t s) {
+    if (lo >= hi) return hipSuccess;
+    hipLaunchKernelGGL(k_start_apply, dim3(nblk(hi - lo)), dim3(TPB), 0, s, t, q, r, sc, lo, hi, ctr);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include "clock_core.h"
 #include "fail_core.h"
 #include "finish_core.h"
+#include "start_core.h"
 #include "hb_order.h"
 #include "milp.h"
 #include "price_emul.h"
@@ -173,6 +174,19 @@ extern "C" int hqtick_debug_fail_kind(uint32_t n, const uint8_t *entry_found, co
         if (entry_class[i] > hqfail::E_PF) return HQTICK_E_INVALID;
         kind[i] = (uint8_t)hqfail::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, override_found[i] != 0, override_worker_match[i] != 0, reporter_none[i] != 0,
                                            earlier_accepted[i] != 0);
+    }
+    return (int)n;
+}
+// the rule of hqtick_start_tasks on host arrays: start_core.h's kind_of per position
+extern "C" int hqtick_debug_start_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *entry_variant_match,
+                                       const uint8_t *entry_run, const uint8_t *variant_exists, const uint8_t *override_found, const uint8_t *override_worker_match,
+                                       const uint8_t *earlier_eligible, uint8_t *kind) {
+    if (n && (!entry_found || !entry_class || !entry_worker_match || !entry_variant_match || !entry_run || !variant_exists || !override_found || !override_worker_match || !earlier_eligible || !kind))
+        return HQTICK_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (entry_class[i] > hqstart::E_PF) return HQTICK_E_INVALID;
+        kind[i] = (uint8_t)hqstart::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, entry_variant_match[i] != 0, entry_run[i] != 0, variant_exists[i] != 0,
+                                            override_found[i] != 0, override_worker_match[i] != 0, earlier_eligible[i] != 0);
     }
     return (int)n;
 }

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "start_core.h"
 
 using hqbuf::PinBuf;
 using hqcluster::UpView;
@@ -418,6 +419,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     ctx->h_cancel_ids.release(); ctx->d_cancel_ids.release();
     ctx->h_finish_in.release(); ctx->d_finish_in.release();
     ctx->h_fail_in.release(); ctx->d_fail_in.release();
+    ctx->h_start_in.release(); ctx->d_start_in.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1099,13 +1101,100 @@ int hqtick_retracting_started(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_
         if (int rc = ledger_fail(ctx, ctx->asg.release(ledger_env(ctx), m, s_id.data())); rc < 0) return rc;  // try_remove_redirection (an id without a redirect has no entry: unknown to the release)
         for (uint64_t t : s_id) ctx->retr.cancel(t);
         if (!queued.empty() && ctx->ready.cols().n) { if (int rc = ready_fail(ctx, ctx->ready.remove(ready_env(ctx), queued.size(), queued.data())); rc < 0) return rc; }
-        const int k = ledger_fail(ctx, ctx->asg.add(ledger_env(ctx), m, s_id.data(), s_wid.data(), s_rq.data(), s_var.data(), s_prio.data()));  // insert_sn_task on the old worker
+        const int k = ledger_fail(ctx, ctx->asg.add(ledger_env(ctx), m, s_id.data(), s_wid.data(), s_rq.data(), s_var.data(), s_prio.data(), 1));  // insert_sn_task on the old worker; the task runs there
         if (k < 0) return k;
         if (ctx->asg.last_unknown) return fail(ctx, HQTICK_E_INVALID, "hqtick_retracting_started: an entry names an unknown worker, request or variant");
     }
     ctx->asg.last_unknown = n - m;
     return (int)m;
 }); }
+
+// ---- task_running in one call: the checks and the order of the steps are here.  Ids, reporting workers and variants are staged once in pinned memory
+// (13 B per position) and copied to the device once.  The Retracting table is the host's, so the positions it decides are known before any launch: per id of the
+// table the lowest rightly reported position with a variant of the request is the _RETRACTING candidate, later such positions are _REPEAT, wrong reporters
+// _WRONG_WORKER; all of them are masked out for the device.  The claim pass runs once over the whole batch (a kind follows from the tables before the batch and the
+// claims; a candidate's steps touch no entry a device position names); the apply pass is cut at each candidate, because a Retracting start releases the redirect
+// target's entry and enters the task on the old worker, which does not commute with a saturating start on the same row.  The usual batch has no candidate: one
+// segment, one synchronisation.  If a candidate's step fails, the segments and candidates before it stay done and hqtick_start_last_routes is empty.
+int hqtick_start_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint8_t *variant, const uint32_t *rq, const uint64_t *priority) {
+    return with_audit(ctx, [&]() -> int {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_start_tasks", n, task_id && worker_id && variant)) return rc;  // (the guard comes before any step: a refused call changes nothing)
+    if (n > 0x03FFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^26 started tasks in one batch");
+    if (n && ctx->retr.count() && (!rq || !priority)) return fail(ctx, HQTICK_E_INVALID, "hqtick_start_tasks: rq and priority are needed while the Retracting table holds a task");
+    hqasg::Ledger &asg = ctx->asg;
+    asg.start_out = hqasg::Ledger::StartOut{}; asg.last_unknown = 0;
+    if (n == 0) return 0;
+    const size_t o_wid = (size_t)n * 8, o_var = (size_t)n * 12;
+    if (!ctx->h_start_in.ensure((size_t)n * 13 + 16) || !ctx->d_start_in.ensure((size_t)n * 13 + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc start staging");
+    unsigned char *h = ctx->h_start_in.as<unsigned char>(), *d = ctx->d_start_in.as<unsigned char>();
+    memcpy(h, task_id, (size_t)n * 8); memcpy(h + o_wid, worker_id, (size_t)n * 4); memcpy(h + o_var, variant, n);
+    HQ_HIP(hipMemcpyAsync(d, h, (size_t)n * 13, hipMemcpyHostToDevice, ctx->stream));
+    // the positions the Retracting table decides (the mask byte of such a position is its kind; none of the kinds it can take is 0)
+    std::vector<uint8_t> mask; std::vector<uint32_t> cand;
+    if (ctx->retr.count()) {
+        mask.assign(n, 0);
+        std::vector<uint64_t> claimed;
+        for (uint32_t i = 0; i < n; i++) {
+            uint32_t old_id = 0; bool in_queue = false;
+            const bool found = ctx->retr.find(task_id[i], &old_id, &in_queue);
+            if (!found) continue;
+            const bool earlier = std::find(claimed.begin(), claimed.end(), task_id[i]) != claimed.end();
+            const uint32_t kind = hqstart::kind_of(false, hqstart::E_SN, false, false, false, asg.variant_exists(rq[i], variant[i]), true, old_id == worker_id[i], earlier);
+            mask[i] = (uint8_t)kind;
+            if (kind == HQ_START_RETRACTING) { claimed.push_back(task_id[i]); cand.push_back(i); }
+        }
+    }
+    const hqasg::Env e0 = ledger_env(ctx);
+    if (int rc = ledger_fail(ctx, asg.start_begin(e0, n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<const uint32_t *>(d + o_wid), d + o_var, mask.empty() ? nullptr : mask.data(),
+                                                  (uint32_t)cand.size())); rc < 0) return rc;
+    uint32_t lo = 0, started = 0;
+    // (a failed step: the claims of the positions that were not applied are given back, so that the entries can be claimed by a later batch)
+    auto failed = [&](int rc) { const std::string m = ctx->err; asg.start_abort(ledger_env(ctx), lo); ctx->err = m; return rc; };
+    for (uint32_t c : cand) {
+        if (int rc = ledger_fail(ctx, asg.start_segment(ledger_env(ctx), lo, c, false)); rc < 0) return failed(rc);
+        lo = c + 1;
+        // hqtick_retracting_started's steps for this one position: try_remove_redirection, the table entry, its place in the ready set, insert_sn_task running
+        uint32_t old_id = 0; bool in_queue = false;
+        ctx->retr.find(task_id[c], &old_id, &in_queue);
+        if (int rc = ledger_fail(ctx, asg.release(ledger_env(ctx), 1, &task_id[c])); rc < 0) return failed(rc);
+        ctx->retr.cancel(task_id[c]);
+        if (in_queue && ctx->ready.cols().n) { if (int rc = ready_fail(ctx, ctx->ready.remove(ready_env(ctx), 1, &task_id[c])); rc < 0) return failed(rc); }
+        const int k = ledger_fail(ctx, asg.add(ledger_env(ctx), 1, &task_id[c], &worker_id[c], &rq[c], &variant[c], &priority[c], 1));
+        if (k < 0) return failed(k);
+        if (asg.last_unknown) return failed(fail(ctx, HQTICK_E_INVALID, "hqtick_start_tasks: a Retracting task names an unknown worker, request or variant"));
+        started++;
+    }
+    if (int rc = ledger_fail(ctx, asg.start_segment(ledger_env(ctx), lo, n, true)); rc < 0) { asg.start_out = hqasg::Ledger::StartOut{}; return failed(rc); }
+    for (uint32_t i = 0; i < n && !mask.empty(); i++) if (mask[i]) asg.start_out.kind[i] = mask[i];
+    asg.start_out.accepted = std::min(asg.start_out.accepted + started, n);
+    asg.last_unknown = n - asg.start_out.accepted;
+    return (int)asg.start_out.accepted;
+}); }
+
+int hqtick_start_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind) {
+    if (!ctx) { if (n) *n = 0; if (kind) *kind = nullptr; return HQTICK_E_INVALID; }
+    if (n) *n = ctx->asg.start_out.n;
+    if (kind) *kind = ctx->asg.start_out.kind;
+    return 0;
+}
+
+int hqtick_assigned_running(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint8_t *running) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->asg.on) return fail(ctx, HQTICK_E_INVALID, "assignment ledger not enabled (hqtick_assigned_enable)");
+    if (n && (!task_id || !running)) return fail(ctx, HQTICK_E_INVALID, "hqtick_assigned_running: null array");
+    if (!n) return 0;
+    HQ_HIP(hipSetDevice(ctx->device));
+    return ledger_fail(ctx, ctx->asg.running(ledger_env(ctx), n, task_id, running));
+}
+
+int hqtick_cluster_last_requeued_running(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (n) *n = (uint32_t)ctx->asg.rq_run_task.size();
+    if (task_id) *task_id = ctx->asg.rq_run_task.data();
+    return 0;
+}
 
 // The audit of the resident state (audit.h): the views of what this context holds, read through const accessors, handed to hqaudit::Auditor.  Nothing here changes
 // the context: no selection or placement is abandoned, no mirror is synchronised, ctx->err is written only when the call itself fails.

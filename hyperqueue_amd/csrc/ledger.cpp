@@ -8,7 +8,7 @@ namespace hqasg {
 void Ledger::release_all() {
     tab.release(); tab2.release(); for (RowPair *r : {&counts, &mn, &pf}) r->release();
     for (DevBuf &b : buf) b.release();
-    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release();
+    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release(); h_start.release();
 }
 void Ledger::take_requests(const hqtick_snapshot *s) {
     const uint32_t Q = s->n_requests;
@@ -90,7 +90,7 @@ int Ledger::reserve(const Env &e, uint64_t more) {
     return 0;
 }
 // an insert batch (n > 0) from host columns, staged in pinned memory and read in place; c[C_OUT] entered, c[C_BAD] / c[C_DUP] refused
-int Ledger::insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free, const uint32_t *col_rq) {
+int Ledger::insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free, const uint32_t *col_rq, int running) {
     if (int rc = reserve(e, n)) return rc;
     if (int rc = sync_req(e)) return rc;
     Pack pk;
@@ -98,7 +98,7 @@ int Ledger::insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint
     Items it{};
     it.n = n; it.id = pk.put(id, n); it.wid = pk.put(wid, n); it.rq = pk.put(rq, n); it.prio = pk.put(prio, n, 8); it.variant = pk.put(var, n);
     if (!rq) std::fill_n(pk.host(it.rq), n, RQ_LOOKUP);  if (!prio) std::fill_n(pk.host(it.prio), n, (uint64_t)0);
-    it.col_id = e.col_id; it.col_prio = e.col_prio; it.col_rq = col_rq ? col_rq : e.col_rq; it.col_n = e.col_n;
+    it.col_id = e.col_id; it.col_prio = e.col_prio; it.col_rq = col_rq ? col_rq : e.col_rq; it.col_n = e.col_n; it.run = running ? 1 : 0;
     if (int rc = counted(e.stream, "hqasg::insert", [&](uint32_t *ctr) { return insert(table(), req(), rows(e), it, upsert, apply_free, ctr, e.stream); })) return rc;
     if (c[C_FULL]) return fail(HQTICK_E_DEVICE, "assignment ledger: table full");
     n_live += c[C_OUT]; dirty_ = true;
@@ -220,20 +220,20 @@ int Ledger::repack(const Env &e, const std::vector<uint32_t> &src, uint32_t W_ol
 int Ledger::evict(const Env &e, uint32_t n, const uint32_t *worker_id) {
     std::vector<uint32_t> lost(worker_id, worker_id + n); std::sort(lost.begin(), lost.end());
     const uint64_t pf_now = pf_on ? pf_live : 0, cap_out = n_live + mn_live + pf_now + 1;
-    if (!buf[B_SCRATCH].ensure((((size_t)n * 4 + 7) & ~(size_t)7) + cap_out * 21 + 16)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
-    Pack pk{nullptr, buf[B_SCRATCH].as<unsigned char>()};  // [lost n u32][id u64][priority u64][rq u32][variant u8], cap_out each
+    if (!buf[B_SCRATCH].ensure((((size_t)n * 4 + 7) & ~(size_t)7) + cap_out * 22 + 16)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    Pack pk{nullptr, buf[B_SCRATCH].as<unsigned char>()};  // [lost n u32][id u64][priority u64][rq u32][variant u8][running u8], cap_out each
     uint32_t *d_lost = pk.put<uint32_t>(nullptr, n); uint64_t *d_id = pk.put<uint64_t>(nullptr, cap_out, 8), *d_pr = pk.put<uint64_t>(nullptr, cap_out);
-    uint32_t *d_rq = pk.put<uint32_t>(nullptr, cap_out); uint8_t *d_var = pk.put<uint8_t>(nullptr, cap_out);
+    uint32_t *d_rq = pk.put<uint32_t>(nullptr, cap_out); uint8_t *d_var = pk.put<uint8_t>(nullptr, cap_out), *d_run = pk.put<uint8_t>(nullptr, cap_out);
     HQ_HIP(hipMemcpyAsync(d_lost, lost.data(), (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
-    if (int rc = counted(e.stream, "hqasg::evict", [&](uint32_t *ctr) { return hqasg::evict(table(), n, d_lost, d_id, d_rq, d_pr, d_var, (uint32_t)cap_out, ctr, e.stream); })) return rc;
+    if (int rc = counted(e.stream, "hqasg::evict", [&](uint32_t *ctr) { return hqasg::evict(table(), n, d_lost, d_id, d_rq, d_pr, d_var, d_run, (uint32_t)cap_out, ctr, e.stream); })) return rc;
     const uint32_t k = c[C_OUT], k_mn = c[C_MN], k_pf = c[C_PF];
     if (k >= cap_out || (uint64_t)k_mn + k_pf > k || k_mn > mn_live || k_pf > pf_now || k - k_mn - k_pf > n_live) return fail(HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
     if (k_mn) {  // a lost ROOT (reactor.rs:107-128): the task's other rows are free single-node workers again, before the rows are re-packed
         HQ_HIP(mn_reset_rows(table(), rows(e), mn_rows(mn.cur, e.W, mn_live), e.stream));
         flags_dirty = true;
     }
-    std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k); std::vector<uint8_t> var(k);
-    if (k && k_pf) HQ_HIP(hipMemcpy(var.data(), d_var, k, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> id(k), pr(k); std::vector<uint32_t> rq(k); std::vector<uint8_t> var(k ? cap_out + k : 0);  // [variant cap_out][running k]
+    if (k) HQ_HIP(hipMemcpy(var.data(), d_var, (size_t)k * 2 + (cap_out - k), hipMemcpyDeviceToHost));  // (variant and running bytes lie one behind the other: one copy)
     if (k) {
         HQ_HIP(hipMemcpy(id.data(), d_id, (size_t)k * 8, hipMemcpyDeviceToHost));
         HQ_HIP(hipMemcpy(pr.data(), d_pr, (size_t)k * 8, hipMemcpyDeviceToHost));
@@ -244,6 +244,7 @@ int Ledger::evict(const Env &e, uint32_t n, const uint32_t *worker_id) {
     for (uint32_t i : ord) {
         rq_task.push_back(id[i]); rq_prio.push_back(pr[i]); rq_rq.push_back(rq[i]);
         if (k_pf && var[i] == PF_VARIANT) rq_pf_task.push_back(id[i]);  // move_prefilled_task_to_ready: the subset the host takes out of its prefill sets
+        else if (var[i] == MN_VARIANT || (var[i] != PF_VARIANT && var[cap_out + i])) rq_run_task.push_back(id[i]);  // running_tasks (reactor.rs:72-120): reported running, or multi-node
     }
     n_live -= k - k_mn - k_pf; mn_live -= k_mn; n_tomb += k; dirty_ = true;
     if (k_pf) { pf_live -= k_pf; pf_dirty = true; }
@@ -307,9 +308,9 @@ int Ledger::enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t 
     on = true; dirty_ = true;
     return 0;
 }
-int Ledger::add(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio) {
+int Ledger::add(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int running) {
     last_unknown = 0; if (!n) return 0;
-    if (int rc = insert_host(e, n, id, wid, rq, var, prio, 0, 1, nullptr)) return rc;
+    if (int rc = insert_host(e, n, id, wid, rq, var, prio, 0, 1, nullptr, running)) return rc;
     last_unknown = (uint64_t)c[C_BAD] + c[C_DUP];
     return (int)c[C_OUT];
 }
@@ -426,6 +427,52 @@ int Ledger::reported(const Env &e, bool failing, uint32_t n, const uint64_t *d_i
     out = FinishOut{n, accepted, hk.host(o_kind), d_kind, o_kind};
     if (retr_hit) *retr_hit = hk.host(o_hit);
     return (int)accepted;
+}
+// task_running on the ledger (hqtick_start_tasks).  The claim pass runs once over the whole batch: a kind follows from the tables before the batch
+// and the claims, and the caller's own positions between the segments (ids of the Retracting table, masked here) touch no entry a device position names.  What they
+// do touch is the free rows, with saturating arithmetic, so the apply pass runs segment by segment in batch order around them.
+int Ledger::start_begin(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, const uint8_t *d_variant, const uint8_t *mask, uint32_t n_host) {
+    last_unknown = 0; start_out = StartOut{}; start_n = 0; std::fill_n(start_acc, (size_t)C_N, 0u);
+    if (!n) return 0;
+    if (int rc = sync_req(e)) return rc;
+    if (n_host) { if (int rc = reserve(e, 2 * (uint64_t)n_host)) return rc; }  // (each of them leaves a tombstone and enters an entry)
+    if (!buf[B_START].ensure((size_t)n * 6 + 16) || !h_start.ensure((size_t)n * 2 + 16)) return fail(HQTICK_E_DEVICE, "hipMalloc start scratch");
+    Pack dk{nullptr, buf[B_START].as<unsigned char>()};  // [pos n u32][kind n u8][mask n u8]
+    uint32_t *d_pos = dk.put<uint32_t>(nullptr, n); uint8_t *d_kind = dk.put<uint8_t>(nullptr, n), *d_mask = dk.put<uint8_t>(nullptr, n);
+    if (mask) {
+        memcpy(h_start.as<unsigned char>() + n, mask, n);
+        HQ_HIP(hipMemcpyAsync(d_mask, h_start.as<unsigned char>() + n, n, hipMemcpyHostToDevice, e.stream));
+    }
+    start_c = StartCols{d_id, d_reporter, d_variant, mask ? d_mask : nullptr, d_pos, d_kind}; start_n = n;
+    HQ_HIP(start_claim(table(), req(), rows(e), start_c, 0, n, e.stream));
+    return 0;
+}
+int Ledger::start_segment(const Env &e, uint32_t lo, uint32_t hi, bool last) {
+    if (!start_n || (lo >= hi && !last)) return 0;
+    const uint32_t n = start_n;
+    if (int rc = counted(e.stream, "hqasg::start", [&](uint32_t *ctr) {
+            hipError_t r = start_apply(table(), req(), rows(e), start_c, lo, hi, ctr, e.stream);
+            if (r == hipSuccess && last) r = hipMemcpyAsync(h_start.p, start_c.kind, n, hipMemcpyDeviceToHost, e.stream);
+            return r; })) return rc;
+    for (uint32_t k = 0; k < C_N; k++) start_acc[k] += c[k];
+    if (const uint32_t pf_now = (uint32_t)std::min<uint64_t>(c[C_PF], pf_live)) { pf_live -= pf_now; n_live += pf_now; pf_dirty = true; }  // started prefills are assigned entries now
+    if (c[C_OUT]) dirty_ = true;
+    if (last) { start_out = StartOut{n, std::min(start_acc[C_OUT], n), h_start.as<uint8_t>()}; start_n = 0; }
+    return 0;
+}
+void Ledger::start_abort(const Env &e, uint32_t lo) {
+    if (start_n && cap && start_unclaim(table(), start_c, lo, start_n, e.stream) == hipSuccess) hipStreamSynchronize(e.stream);
+    start_n = 0; start_out = StartOut{};
+}
+int Ledger::running(const Env &e, uint32_t n, const uint64_t *task_id, uint8_t *run) {
+    Pack pk;
+    if (int rc = stage_in((size_t)n * 9, &pk)) return rc;
+    const uint64_t *d_id = pk.put(task_id, n); uint8_t *d_r = pk.put<uint8_t>(nullptr, n);
+    HQ_HIP(hqasg::running(table(), n, d_id, d_r, e.stream));
+    HQ_HIP(hipStreamSynchronize(e.stream));
+    memcpy(run, pk.host(d_r), n);
+    int found = 0; for (uint32_t i = 0; i < n; i++) found += run[i] != 0xFF;
+    return found;
 }
 int Ledger::add_mn(const Env &e, uint32_t n, const uint64_t *task_id, const uint32_t *rq, const uint64_t *priority, const uint32_t *worker_off, const uint32_t *worker_id) {
     last_unknown = 0; if (!n) return 0;

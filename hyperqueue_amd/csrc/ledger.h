@@ -40,6 +40,7 @@ class Ledger {
     uint64_t n_live = 0, mn_live = 0, pf_live = 0;  // single-node, multi-node and (with tracking()) prefilled entries of the table
     uint64_t last_unknown = 0, last_host_bytes = 0;
     std::vector<uint64_t> rq_task, rq_prio, rq_pf_task; std::vector<uint32_t> rq_rq;  // hqtick_cluster_last_requeued(_prefilled): what the last evict() took out
+    std::vector<uint64_t> rq_run_task;  // hqtick_cluster_last_requeued_running: its running single-node entries and its multi-node tasks (on_remove_worker's running_tasks)
     // hqtick_cancel_last_*: what the last cancel() wrote into pinned memory (n positions; n_workers messages holding n_ids ids)
     struct CancelOut { uint32_t n = 0, n_workers = 0, n_ids = 0; const uint32_t *worker_id = nullptr, *task_off = nullptr; const uint64_t *task_id = nullptr; const uint32_t *route_wid = nullptr; const uint8_t *route_kind = nullptr; };
     CancelOut cancel_out;
@@ -49,10 +50,13 @@ class Ledger {
     struct FinishOut { uint32_t n = 0, accepted = 0; const uint8_t *kind = nullptr; const uint8_t *d_kind = nullptr; uint8_t *kind_dev = nullptr; };
     FinishOut finish_out;
     FinishOut fail_out;  // hqtick_fail_last_routes: the same of the last fail_tasks(); `accepted` and the kinds are final after the graph step
+    // hqtick_start_last_routes: the kinds of the last start (pinned, n positions); `accepted` counts the device's accepted positions, the caller adds its own
+    struct StartOut { uint32_t n = 0, accepted = 0; uint8_t *kind = nullptr; };
+    StartOut start_out;
 
     // ---- the C ABI's operations (arguments validated by the caller)
     int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
-    int add(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
+    int add(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int running = 0);  // running: the entries' running byte
     int release(const Env &e, uint32_t n, const uint64_t *id);
     // hqtick_cancel_tasks' ledger step: d_id [n] is DEVICE memory (the call's one copy of the ids); the Retracting overrides are host arrays, ids
     // ascending.  The tables end as after release(ids) + unprefill(ids); cancel_out holds the messages and routes; *retr_hit [n_retr] (pinned, valid until the next
@@ -66,6 +70,16 @@ class Ledger {
     // hqtick_fail_tasks' ledger step: finish() in the passes' fail mode.  The tables end as after release(accepted ids, batch order) +
     // unprefill(accepted ids); fail_out holds the kinds as the ledger sees them (a _WAITING position is accepted here).  Returns the accepted positions.
     int fail_tasks(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
+    // hqtick_start_tasks' ledger steps.  start_begin: d_id / d_reporter / d_variant [n] are DEVICE memory (the call's one copy), mask [n] a host
+    // array or nullptr (nonzero: a position the caller decides itself; it is uploaded only then), n_host the number of such positions the caller will start through
+    // release() + add() -- room for them is made first, so that the table is not rebuilt between the claim pass, which runs here over the whole batch, and the
+    // apply passes.  start_segment: the apply pass over [lo, hi) behind one set of counters and one synchronisation; last: the kinds come back with it and
+    // start_out is set (the caller writes the kinds of its own positions into start_out.kind afterwards).  An empty range with !last does nothing.
+    int start_begin(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, const uint8_t *d_variant, const uint8_t *mask, uint32_t n_host);
+    int start_segment(const Env &e, uint32_t lo, uint32_t hi, bool last);
+    void start_abort(const Env &e, uint32_t lo);  // a start that ends early: the claims of the positions [lo, n) are given back
+    bool variant_exists(uint32_t rq, uint32_t v) const { return (size_t)rq + 1 < rq_off.size() && v < rq_off[rq + 1] - rq_off[rq] && v < PF_VARIANT; }
+    int running(const Env &e, uint32_t n, const uint64_t *id, uint8_t *run);  // hqtick_assigned_running
     int add_mn(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid);
     int mn_workers(const Env &e, uint64_t id, uint32_t *n, const uint32_t **wid);
     int lookup(const Env &e, uint32_t n, const uint64_t *id, uint32_t *wid, uint8_t *var);
@@ -78,7 +92,7 @@ class Ledger {
     int upload_flags(const Env &e);
     int repack(const Env &e, const std::vector<uint32_t> &src, uint32_t W_old, const uint8_t *add_flags);
     int evict(const Env &e, uint32_t n, const uint32_t *worker_id);
-    void clear_requeued() { rq_task.clear(); rq_rq.clear(); rq_prio.clear(); rq_pf_task.clear(); }
+    void clear_requeued() { rq_task.clear(); rq_rq.clear(); rq_prio.clear(); rq_pf_task.clear(); rq_run_task.clear(); }
     // ---- a tick
     void abandon_tick() { pending = false; stage_n = 0; }  // (a tick that was never consumed is abandoned, as its selection is; its staging is never read)
     int sync_mirror(const Env &e);  // free rows, flags and counts back on the host; then agg()
@@ -107,10 +121,10 @@ class Ledger {
   private:
     using DevBuf = hqbuf::DevBuf;
     struct TableCols {  // the hash table's columns (assigned.h: Table), `cap` buckets
-        DevBuf key, wid, rq, var, prio, claim;
-        bool ensure(size_t cap) { return key.ensure(cap * 8) && wid.ensure(cap * 4) && rq.ensure(cap * 4) && var.ensure(cap) && prio.ensure(cap * 8) && claim.ensure(cap * 4); }
-        Table view(uint32_t mask) const { return Table{key.as<uint64_t>(), wid.as<uint32_t>(), rq.as<uint32_t>(), var.as<uint8_t>(), prio.as<uint64_t>(), claim.as<uint32_t>(), mask}; }
-        void release() { for (DevBuf *b : {&key, &wid, &rq, &var, &prio, &claim}) b->release(); }
+        DevBuf key, wid, rq, var, prio, claim, run;
+        bool ensure(size_t cap) { return key.ensure(cap * 8) && wid.ensure(cap * 4) && rq.ensure(cap * 4) && var.ensure(cap) && prio.ensure(cap * 8) && claim.ensure(cap * 4) && run.ensure(cap); }
+        Table view(uint32_t mask) const { return Table{key.as<uint64_t>(), wid.as<uint32_t>(), rq.as<uint32_t>(), var.as<uint8_t>(), prio.as<uint64_t>(), claim.as<uint32_t>(), run.as<uint8_t>(), mask}; }
+        void release() { for (DevBuf *b : {&key, &wid, &rq, &var, &prio, &claim, &run}) b->release(); }
     };
     struct RowPair { DevBuf cur, next; void swap() { std::swap(cur, next); } void release() { cur.release(); next.release(); } };  // a per-worker-row table and the target of its next re-pack
     // Columns one behind the other in a buffer that has the room (h: its host side, nullptr for device memory; dv: the same bytes as the device sees them).
@@ -149,7 +163,8 @@ class Ledger {
     int widen(const Env &e, RowPair &t, uint32_t &stride, size_t cols, const char *what);
     int sync_req(const Env &e);
     int reserve(const Env &e, uint64_t more);
-    int insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free, const uint32_t *col_rq);
+    int insert_host(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio, int upsert, int apply_free, const uint32_t *col_rq,
+                    int running = 0);
     int mn_enter(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid, int check);
     int pf_leave(const Env &e, uint32_t n, const uint64_t *id, const uint8_t *var);
     int reported(const Env &e, bool failing, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, uint32_t n_retr, const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);  // finish() / fail_tasks()
@@ -157,8 +172,10 @@ class Ledger {
     TableCols tab, tab2;      // the hash table; the target of a rebuild
     RowPair counts, mn, pf;   // counts u32 [W x stride]; [mn task u64 W][mn root u8 W][flags u8 W]; pf u32 [W x pf_stride]
     // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation,
-    // a cancel's routes, overrides and sort scratch
-    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_N }; DevBuf buf[B_N];
+    // a cancel's routes, overrides and sort scratch, a start's positions, kinds and mask (the host steps between its segments use B_SCRATCH)
+    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_START, B_N }; DevBuf buf[B_N];
+    StartCols start_c{}; uint32_t start_n = 0, start_acc[C_N] = {};  // a start between start_begin and its last segment: its columns, the counters summed over the segments
+    hqbuf::PinBuf h_start;  // a start's mask in, its kinds out
     hqbuf::PinBuf h_ctr, h_in, h_cancel, h_finish, h_fail;  // (h_cancel: a cancel's overrides in, its lists and routes out; h_finish / h_fail: a finish's / fail's overrides in, its kinds out)
     const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
     uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones

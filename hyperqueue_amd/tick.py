@@ -540,6 +540,45 @@ class Tick:
         return self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), q.ctypes.data_as(abi.u32p), v.ctypes.data_as(abi.u8p),
                            p.ctypes.data_as(abi.u64p)))
 
+    # -- task_running in one call (include/hqtick.h) ---------------------------------------------------------
+    def start_tasks(self, task_id, worker_id, variant, rq=None, priority=None) -> dict:
+        """hqtick_start_tasks for the (id, reporting worker, variant) triples, in this order; rq / priority: the tasks' own (None: NULL, allowed while the Retracting
+        table is empty) -> {"accepted": positions accepted, "kind": per batch position the HQ_START_* kind}"""
+        t = np.ascontiguousarray(task_id, np.uint64); w = np.ascontiguousarray(worker_id, np.uint32); v = np.ascontiguousarray(variant, np.uint8)
+        assert len(t) == len(w) == len(v)
+        q = None if rq is None else np.ascontiguousarray(rq, np.uint32); p = None if priority is None else np.ascontiguousarray(priority, np.uint64)
+        assert (q is None or len(q) == len(t)) and (p is None or len(p) == len(t))
+        f = self._lib.hqtick_start_tasks
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u8p, abi.u32p, abi.u64p]
+        accepted = self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), v.ctypes.data_as(abi.u8p),
+                               None if q is None else q.ctypes.data_as(abi.u32p), None if p is None else p.ctypes.data_as(abi.u64p)))
+        return {"accepted": int(accepted), "kind": self.start_last_routes()}
+
+    def start_last_routes(self) -> np.ndarray:
+        """hqtick_start_last_routes as a numpy copy (also after a call that returned an error)"""
+        n = C.c_uint32(); pk = abi.u8p()
+        g = self._lib.hqtick_start_last_routes
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pk)))
+        return abi._np(pk, n.value, np.uint8).copy() if n.value else np.zeros(0, np.uint8)
+
+    def assigned_running(self, task_id) -> np.ndarray:
+        """hqtick_assigned_running: per id the running byte of its ledger entry (0 / 1; 0xFF: no entry)"""
+        t = np.ascontiguousarray(task_id, np.uint64)
+        r = np.zeros(len(t), np.uint8)
+        f = self._lib.hqtick_assigned_running
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u8p]
+        self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), r.ctypes.data_as(abi.u8p)))
+        return r
+
+    def cluster_last_requeued_running(self) -> list:
+        """the ids among cluster_last_requeued() that were running on a lost worker (on_remove_worker's running_tasks), ascending"""
+        n = C.c_uint32(); pt = abi.u64p()
+        f = self._lib.hqtick_cluster_last_requeued_running
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p)]
+        self._chk(f(self._ctx, C.byref(n), C.byref(pt)))
+        return abi._np(pt, n.value, np.uint64).tolist() if n.value else []
+
     # -- device-resident dependency graph (include/hqtick.h, SURVEY §8 f1) --------------------------------------------------
     def _graph_last_ids(self) -> np.ndarray:
         n = C.c_uint64()

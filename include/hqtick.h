@@ -730,6 +730,56 @@ int hqtick_fail_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **
 int hqtick_fail_last_consumers(const hqtick_ctx *ctx, uint32_t *n, const uint32_t **consumer_off, const uint64_t **consumer_id);
 
 /*
+ * Starting tasks on the resident state in one call (functions added under ABI 12): task_running (server/reactor.rs:264-355) for a batch of
+ * WorkerTaskUpdate::Running / RunningPrefilled, in the order the reactor saw them.  Ids, reporting workers and started variants are staged once (13 B per
+ * position).  Every ledger entry carries a RUNNING byte: 0 when it enters (a tick's placement, hqtick_assigned_enable / _add / _add_mn, a prefilled seed, an
+ * upsert that moves the id), 1 once the task was reported running (this call, hqtick_assigned_start_prefilled, hqtick_retracting_started).  Multi-node entries
+ * keep 0: the reference has no Assigned state for them.
+ *   hqtick_start_tasks   worker_id[i] reported task_id[i] running with variant[i]; a batch may mix workers.  rq[i] / priority[i] are the task's own request and
+ *       priority, read only for accepted _RETRACTING positions (as hqtick_retracting_started takes them); both may be NULL while the table of hqtick_retracting_*
+ *       is empty.  It needs a resident ready set and an enabled ledger.  Every position gets an HQ_START_* kind from the state BEFORE the batch:
+ *         id in the Retracting table   reported by the worker it is retracting FROM: _RETRACTING (accepted; the table decides whatever the ledger names);
+ *                                      _BAD_VARIANT if rq[i] has no variant[i]; reported by anyone else: _WRONG_WORKER
+ *         no entry                     _NONE (the task is unknown or Waiting)
+ *         prefilled entry              its worker: _PREFILLED (accepted), _BAD_VARIANT if its request has no such variant; another worker: _WRONG_WORKER
+ *         single-node entry            another worker: _WRONG_WORKER (assert_eq!(*w_id, worker_id)); its worker, another variant: _WRONG_VARIANT
+ *                                      (assert_eq!(*assigned_rv_id, rv_id)); its worker and variant: _RUNNING if it already runs (unreachable! in the reference),
+ *                                      else _ASSIGNED (accepted)
+ *         multi-node entry             the root: _MN (accepted; nothing changes, so every such position is _MN); another worker: _WRONG_WORKER
+ *       Only _ASSIGNED, _PREFILLED and _RETRACTING positions claim their id: the lowest such position wins, the others become _REPEAT.  A refused position
+ *       claims nothing and changes nothing.  The state afterwards is that of the handler applied to the accepted positions in batch order:
+ *         _ASSIGNED    the entry's running byte is set; nothing else changes
+ *         _PREFILLED   as hqtick_assigned_start_prefilled(id, the WINNING position's variant), and the running byte is set
+ *         _RETRACTING  as hqtick_retracting_started for that one position, entered with the running byte set.  Such a start does not commute with a saturating
+ *                      start on the same worker row, so the batch is cut at each of these positions: what comes before it is applied first.
+ *     Returns the number of accepted positions; hqtick_assigned_last_unknown is the number of refused ones.  The handler asks for scheduling
+ *     (ask_for_scheduling(), reactor.rs:313) iff some kind is _RETRACTING.  HQTICK_E_INVALID without a resident ready set, with the ledger off, with a two-call
+ *     tick's placement pending, with a NULL id / worker / variant array, or with rq or priority NULL while the Retracting table holds a task (nothing changes
+ *     then); HQTICK_E_CAPACITY for n > 2^26; n = 0 returns 0 and leaves an empty kind list.  If a step of a _RETRACTING position fails, the positions before it
+ *     stay started and the kind list is empty.
+ *   hqtick_start_last_routes   per batch position its HQ_START_* kind: pinned memory owned by the context, valid until the next hqtick_start_tasks.
+ *   hqtick_assigned_running    per id the running byte of its entry (0 / 1; 0xFF: not in the ledger).  Returns the number found.
+ *   hqtick_cluster_last_requeued_running   the subset of the last hqtick_cluster_last_requeued that is on_remove_worker's running_tasks (reactor.rs:72-120), ids
+ *       ascending: single-node entries whose running byte was set and multi-node tasks whose root was lost -- what client.on_worker_lost is told and what gets a
+ *       crash counter.  Prefilled and merely assigned entries, and a Retracting task's entry on a lost redirect target, are not in it.
+ */
+#define HQ_START_NONE          0   /* refused: no entry, not in the table */
+#define HQ_START_ASSIGNED      1   /* accepted: single-node entry, its worker and variant, not yet running */
+#define HQ_START_MN            2   /* accepted: multi-node entry, reporter is its root; claims nothing */
+#define HQ_START_PREFILLED     3   /* accepted: prefilled entry (tracking on), reporter is its worker */
+#define HQ_START_RETRACTING    4   /* accepted: in the Retracting table, reporter is the worker it retracts FROM */
+#define HQ_START_REPEAT        5   /* refused: an earlier eligible position claimed this id */
+#define HQ_START_WRONG_WORKER  6   /* refused: the reference's assert_eq!(*w_id, worker_id) / assert_eq!(ws[0], worker_id) */
+#define HQ_START_WRONG_VARIANT 7   /* refused: the reference's assert_eq!(*assigned_rv_id, rv_id) */
+#define HQ_START_RUNNING       8   /* refused: the single-node entry already runs (unreachable! in the reference) */
+#define HQ_START_BAD_VARIANT   9   /* refused: the request of a prefilled or Retracting task has no such variant */
+int hqtick_start_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint8_t *variant, const uint32_t *rq,
+                       const uint64_t *priority);
+int hqtick_start_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind);
+int hqtick_assigned_running(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, uint8_t *running);
+int hqtick_cluster_last_requeued_running(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id);
+
+/*
  * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
  * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
  * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.

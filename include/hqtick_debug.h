@@ -269,6 +269,16 @@ int hqtick_debug_finish_kind(uint32_t n, const uint8_t *entry_found, const uint8
  * kinds before the graph step.  Returns n, HQTICK_E_INVALID for a NULL array or a class above 2.  Not a product path. */
 int hqtick_debug_fail_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *override_found,
                            const uint8_t *override_worker_match, const uint8_t *reporter_none, const uint8_t *earlier_accepted, uint8_t *kind);
+
+/* The decision rule of hqtick_start_tasks (csrc/start_core.h, the function the claim pass of the ledger's start calls per position and the host calls for the ids of
+ * the Retracting table) on HOST arrays, one entry per evaluated position: entry_found, entry_class (0 single-node, 1 multi-node, 2 prefilled), entry_worker_match
+ * (the reporter is the entry's worker / root), entry_variant_match (the reported variant is the entry's), entry_run (the entry's running byte), variant_exists (the
+ * request of the entry, or of a Retracting task, has the reported variant), override_found (the id is in the Retracting table), override_worker_match (the reporter
+ * is the worker it is retracting from), earlier_eligible (an earlier eligible position of the batch claimed the id).  kind [n]: the HQ_START_* kinds.  Returns n,
+ * HQTICK_E_INVALID for a NULL array or a class above 2.  Not a product path. */
+int hqtick_debug_start_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *entry_variant_match,
+                            const uint8_t *entry_run, const uint8_t *variant_exists, const uint8_t *override_found, const uint8_t *override_worker_match,
+                            const uint8_t *earlier_eligible, uint8_t *kind);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
