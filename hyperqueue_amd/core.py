@@ -767,10 +767,10 @@ class SchedEnv:
                     self.workers[w_id].mn_task = None  # reset_mn_task  server/worker.rs:168-171
                 tell(t.mn_workers[0], tid, abi.HQ_CANCEL_MN)
             elif t.state == RETRACTING:
-                if tid in self.redirects:
-                    target, v = self.redirects.pop(tid)
-                    self.workers[target].assigned_tasks.discard(tid)
-                    self._add(self.workers[target], t.rq, v)
+                # (as in finish_tasks: a task the tick put back on the worker it is retracting from holds that worker's resources without a redirect entry,
+                # mapping.rs:47,66-80; try_remove_redirection alone would leave a cancelled task in that worker's assigned set.  The library's cancel releases
+                # whatever entry the id has, and so does the mirror)
+                self._drop_redirection(t)
                 tell(t.worker, tid, abi.HQ_CANCEL_RETRACTING)
             elif t.state == PREFILLED:
                 self.workers[t.worker].prefilled_tasks.discard(tid)

@@ -77,6 +77,7 @@ int WorkerSet::upload(hipStream_t st, const hqtick_snapshot *s) {
     rt.assign(h + L.o_amt, h + L.bytes);
     W_ = W; R_ = R; valid_ = true; clock_mode_ = false;
     id.assign(s->worker_id, s->worker_id + W);
+    wmap_ = hqhb::U32Map(); for (uint32_t w = 0; w < W; w++) wmap_.insert(id[w], 0); rank_dirty = true;  // (WorkerIds are minted ascending: a fresh map filled in that order)
     total.assign(s->worker_total, s->worker_total + (size_t)W * R); free_.assign(s->worker_free, s->worker_free + (size_t)W * R);
     rem.assign(W, HQ_NO_TIME_LIMIT); if (s->worker_remaining_ns) rem.assign(s->worker_remaining_ns, s->worker_remaining_ns + W);
     min_util.assign(W, 0.0f); if (s->worker_min_utilization) min_util.assign(s->worker_min_utilization, s->worker_min_utilization + W);
@@ -174,6 +175,8 @@ int WorkerSet::repack(hipStream_t st, const std::vector<uint32_t> &src, uint32_t
 void WorkerSet::add_rows(uint32_t n, const uint32_t *worker_id, const uint64_t *tot, const uint64_t *free_rows, const int64_t *rem_ns, const float *mu, const uint8_t *fl, const uint32_t *grp) {
     const uint32_t R = R_;
     id.insert(id.end(), worker_id, worker_id + n);
+    for (uint32_t i = 0; i < n; i++) wmap_.insert(worker_id[i], 0);
+    rank_dirty = true;
     total.insert(total.end(), tot, tot + (size_t)n * R); free_.insert(free_.end(), free_rows, free_rows + (size_t)n * R);
     for (uint32_t i = 0; i < n; i++) {
         rem.push_back(rem_ns ? rem_ns[i] : (int64_t)HQ_NO_TIME_LIMIT); min_util.push_back(mu ? mu[i] : 0.0f); flags_.push_back(fl ? fl[i] : (uint8_t)HQ_WORKER_SN);
@@ -188,7 +191,7 @@ void WorkerSet::keep_rows(const std::vector<uint32_t> &src) {
     const uint32_t R = R_, W_old = (uint32_t)id.size();
     uint32_t k = 0;
     for (uint32_t w = 0; w < W_old; w++) {
-        if (k == src.size() || src[k] != w) { blocked.erase(id[w]); continue; }
+        if (k == src.size() || src[k] != w) { blocked.erase(id[w]); wmap_.remove(id[w]); rank_dirty = true; continue; }
         if (k != w) {
             id[k] = id[w]; rem[k] = rem[w]; min_util[k] = min_util[w]; flags_[k] = flags_[w]; group[k] = group[w];
             if (clock_mode_) deadline[k] = deadline[w];
@@ -267,7 +270,13 @@ int WorkerSet::complete(const hqtick_snapshot *s, hqtick_snapshot *full) {
         }
     }
     full->n_workers = W; full->worker_id = id.data(); full->worker_total = total.data(); full->worker_free = free_.data(); full->worker_remaining_ns = rem.data();
-    full->worker_min_utilization = min_util.data(); full->worker_flags = flags_.data(); full->worker_group = group.data(); full->n_groups = n_groups; full->worker_map_rank = nullptr;
+    full->worker_min_utilization = min_util.data(); full->worker_flags = flags_.data(); full->worker_group = group.data(); full->n_groups = n_groups;
+    if (rank_dirty) {
+        rank_.assign(W, 0); uint32_t pos = 0;
+        wmap_.for_each([&](uint32_t key, uint32_t) { const auto it = std::lower_bound(id.begin(), id.end(), key); if (it != id.end() && *it == key) rank_[it - id.begin()] = pos++; });
+        rank_dirty = false;
+    }
+    full->worker_map_rank = rank_.data();
     full->n_blocked = (uint32_t)blk_worker.size(); full->blocked_worker = blk_worker.data(); full->blocked_rq = blk_rq.data(); full->blocked_variant = blk_variant.data();
     return 0;
 }

@@ -14,6 +14,7 @@
 
 #include "../../include/hqtick.h"
 #include "devbuf.h"
+#include "hb_table.h"
 #include "kernels.h"
 
 namespace hqcluster {
@@ -90,6 +91,9 @@ class WorkerSet {
     std::vector<int64_t> deadline; hqbuf::DevBuf d_deadline; hqbuf::PinBuf h_deadline;
     std::vector<uint64_t> thr_src, thr;
     std::map<uint32_t, std::vector<std::pair<uint32_t, uint8_t>>> blocked;   // worker id -> (rq, variant)
+    // core.worker_map as the reference's map type keeps it: inserts and removals in the order they happened (a removal leaves the table's size and the other
+    // workers' buckets as they were, so the iteration order is NOT that of the remaining ids inserted afresh); rank_[row] = position in its iteration order
+    hqhb::U32Map wmap_; std::vector<uint32_t> rank_; bool rank_dirty = true;
     std::vector<uint32_t> blk_worker, blk_rq; std::vector<uint8_t> blk_variant; bool blk_dirty = true;  // the same as (worker index, rq, variant) triples
 };
 
@@ -135,8 +139,21 @@ class Retracting {
     // what create_task_mapping did to task states and redirects (mapping.rs:66-101), from the tick's result
     void apply_tick(const uint32_t *worker_id, uint32_t W, const std::vector<uint32_t> &retract_off, const std::vector<uint64_t> &retract_task, const std::vector<uint64_t> &red_task,
                     const std::vector<uint32_t> &red_worker, const std::vector<uint8_t> &red_variant, const std::vector<uint8_t> &red_kind);
+    // A two-call tick of a ledger context becomes state at hqtick_ready_consume_last, and the table with it: hold_tick() keeps apply_tick()'s arguments (copies),
+    // commit_tick() applies them when the placement enters the ledger, drop_tick() forgets them (the tick was abandoned, or another tick begins)
+    void hold_tick(const uint32_t *worker_id, uint32_t W, const std::vector<uint32_t> &retract_off, const std::vector<uint64_t> &retract_task, const std::vector<uint64_t> &red_task,
+                   const std::vector<uint32_t> &red_worker, const std::vector<uint8_t> &red_variant, const std::vector<uint8_t> &red_kind) {
+        held = Held{std::vector<uint32_t>(worker_id, worker_id + W), retract_off, retract_task, red_task, red_worker, red_variant, red_kind}; has_held = true;
+    }
+    void commit_tick() {
+        if (has_held) apply_tick(held.wid.data(), (uint32_t)held.wid.size(), held.retract_off, held.retract_task, held.red_task, held.red_worker, held.red_variant, held.red_kind);
+        drop_tick();
+    }
+    void drop_tick() { has_held = false; held = Held{}; }
 
   private:
+    struct Held { std::vector<uint32_t> wid, retract_off; std::vector<uint64_t> retract_task, red_task; std::vector<uint32_t> red_worker; std::vector<uint8_t> red_variant, red_kind; };
+    Held held; bool has_held = false;
     struct Entry { uint32_t old_id; bool in_queue; bool has_redirect; uint32_t target_id; uint8_t variant; };
     std::map<uint64_t, Entry> tab;
     std::vector<uint64_t> s_task; std::vector<uint32_t> s_worker, s_red_worker; std::vector<uint8_t> s_red_variant;  // to_snapshot's arrays

@@ -82,7 +82,11 @@ int worker_tables(void *user, UpView *uv, std::string *err) {
 int phase_a(hqtick_ctx *ctx, const hqtick_snapshot *s, WorkerEval *ev, Scan *sc, const std::function<void()> *while_gpu_runs = nullptr) {
     TablesOf t{ctx, s};
     const uint32_t W = s->n_workers, Q = s->n_requests;
-    const int rc = ctx->scan.scan(scan_env(ctx), ctx->ready.cols(), hqscan::Shape{Q, s->n_retracting, s->retracting_task},
+    hqready::Cols cols = ctx->ready.cols();
+    // a resident set that holds only tombstones (every task handed out, cancelled or removed since the last compaction) is the empty set: nothing to discover a
+    // level from, nothing to scan -- and still a tick: it may take tasks out of the prefill sets for a worker that has room (mapping.rs:82-104)
+    if (ctx->ready.resident() && ctx->ready.live() == 0) cols.n = 0;
+    const int rc = ctx->scan.scan(scan_env(ctx), cols, hqscan::Shape{Q, s->n_retracting, s->retracting_task},
                                   hqscan::Workers{W, s->n_resources, (size_t)W * (Q ? s->rq_variant_off[Q] : 0), worker_tables, &t}, ev, sc, while_gpu_runs);
     const hqscan::Timings &tm = ctx->scan.timings();
     if (tm.distinct_us >= 0) ctx->stats.distinct_us = tm.distinct_us;
@@ -115,6 +119,7 @@ struct TickRun {
             ctx->scan.columns_changed();
         } else if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "hqtick_run_resident without hqtick_upload_ready");
         N = ctx->ready.cols().n;
+        if (ctx->ready.resident() && ctx->ready.live() == 0) N = 0;  // (only tombstones: phase_a)
         return 0;
     }
 
@@ -266,8 +271,9 @@ struct TickRun {
 };
 
 // a placement waiting for hqtick_ready_consume_last is still live only while the tick's selection is: every ready-set delta that abandons the selection
-// (an add, a remove, a compaction, a graph call, an upload) ends ready.selection_live() — and with it the placement is dropped too: Ledger::pending is read nowhere
-// but here, so the ready set need not know the ledger to clear it
+// (an add, a remove, a compaction, a graph call, an upload) ends ready.selection_live() -- and with it the placement is dropped too, so the ready set need not
+// know the ledger to clear it.  Whether a placement is LIVE is asked here alone; run_tick reads Ledger::pending right after it has set it (hold or apply the
+// Retracting table's part) and hqtick_resident_check reads it together with selection_live()
 bool ledger_pending_live(hqtick_ctx *ctx) { return ctx->asg.pending_live(ctx->ready.selection_live()); }
 int ledger_guard(hqtick_ctx *ctx) {
     if (ctx->asg.on && ledger_pending_live(ctx)) return fail(ctx, HQTICK_E_INVALID, "assignment ledger: the last tick's placement is pending (hqtick_ready_consume_last first)");
@@ -282,7 +288,7 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
         if (s->assigned_off) return fail(ctx, HQTICK_E_INVALID, "assignment ledger on: the snapshot must not carry an assigned CSR as well");
         if (ctx->asg.tracking() && s->prefilled_off) return fail(ctx, HQTICK_E_INVALID, "prefilled tracking on: the snapshot must not carry a prefilled CSR as well");
         HQ_HIP(hipSetDevice(ctx->device));
-        ctx->asg.abandon_tick();
+        ctx->asg.abandon_tick(); ctx->retr.drop_tick();
         ctx->asg.take_requests(s);
         if (ctx->asg.tracking() && ctx->asg.max_variants() >= hqasg::PF_VARIANT) return fail(ctx, HQTICK_E_UNSUPPORTED, "prefilled tracking: a request has 254 or more variants");
         if (int rc = ctx->asg.sync_mirror(ledger_env(ctx))) return ledger_fail(ctx, rc);
@@ -315,9 +321,17 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
             else { ctx->err += " (HQTICK_FLAG_CONSUME_IN_TICK: the tick had already taken its tasks and they could not be put back; the resident ready set is dropped, upload it again)"; }
         }
     }
-    if (rc >= 0 && retr_resident) ctx->retr.apply_tick(s->worker_id, s->n_workers, ctx->map.res.retract_off, ctx->map.res.retract_task, ctx->map.res.red_task, ctx->map.res.red_worker, ctx->map.res.red_variant, ctx->map.res.red_kind);
+    const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
+    // what create_task_mapping did to the Retracting tasks becomes state with the placement: at once, or -- a two-call tick of a ledger context, which a delta may
+    // still abandon -- with the ledger's part at hqtick_ready_consume_last (an abandoned tick then leaves table and ledger agreeing, both as before it)
+    const bool retr_waits = rc >= 0 && retr_resident && ctx->asg.on && use_resident && !in_tick;
+    auto retr_tick = [&](bool hold) {
+        const hqmap::HostResult &r = ctx->map.res;
+        if (hold) ctx->retr.hold_tick(s->worker_id, s->n_workers, r.retract_off, r.retract_task, r.red_task, r.red_worker, r.red_variant, r.red_kind);
+        else ctx->retr.apply_tick(s->worker_id, s->n_workers, r.retract_off, r.retract_task, r.red_task, r.red_worker, r.red_variant, r.red_kind);
+    };
+    if (rc >= 0 && retr_resident && !retr_waits) retr_tick(false);
     if (rc >= 0 && ctx->asg.on) {  // the placement enters the ledger when it becomes state: now, or at hqtick_ready_consume_last in the two-call form
-        const bool in_tick = use_resident && (ctx->cfg.flags & HQTICK_FLAG_CONSUME_IN_TICK) != 0;
         ctx->asg.collect_tick(s, out, ctx->map.res.new_free, ctx->map.res.mn_rq, in_tick && s->n_retracting != 0);  // (the column copy is taken only for the redirects of Retracting tasks)
         if (!use_resident || in_tick) {
             if (int r2 = ledger_fail(ctx, ctx->asg.apply_tick(ledger_env(ctx)))) {  // (the tick's tasks have left the ready set: without the placement the ledger is no longer the truth)
@@ -325,7 +339,12 @@ int run_tick(hqtick_ctx *ctx, const hqtick_snapshot *s, hqtick_result *out, bool
                 ctx->err += " (the assignment ledger is switched off: upload the worker set and enable it again)";
                 return r2;
             }
+        } else if (!ctx->ready.selection_live()) {
+            // two-call form and the tick handed out no ready task: there is no selection to keep the placement pending.  One that has something to enter (a redirect of a
+            // prefilled or Retracting task, a changed free row) holds the empty selection until the consume; one with nothing at all is dropped here, as cheaply as before
+            if (ctx->asg.tick_enters(ledger_env(ctx))) ctx->ready.hold_empty(); else ctx->asg.pending = false;
         }
+        if (retr_waits) retr_tick(ctx->asg.pending);
     }
     return rc;
 }
@@ -458,10 +477,12 @@ int hqtick_ready_consume_last(hqtick_ctx *ctx) { return with_audit(ctx, [&]() ->
     if (ledger_pending_live(ctx)) {  // the last tick's placement enters the assignment ledger (before the selection's request ids become tombstones)
         HQ_HIP(hipSetDevice(ctx->device));
         if (int rc = ledger_fail(ctx, ctx->asg.apply_tick(ledger_env(ctx)))) {
-            ctx->asg.on = false;
+            ctx->asg.on = false; ctx->ready.entered();
             ctx->err += " (the assignment ledger is switched off: upload the worker set and enable it again)";
             return rc;
         }
+        ctx->ready.entered();  // (a held empty selection has nothing to replay: the branch below ends the call)
+        ctx->retr.commit_tick();
     }
     if (!ctx->ready.selection_pending()) {  // nothing handed out since the last consume (or the tick consumed it itself: HQTICK_FLAG_CONSUME_IN_TICK)
         if (!ctx->ready.compact_due()) return 0;
@@ -756,6 +777,7 @@ int hqtick_cluster_worker_flags(const hqtick_ctx *cctx, uint32_t *n_workers, con
 int hqtick_retracting_add(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id) {
     if (!ctx) return HQTICK_E_INVALID;
     if (n && (!task_id || !worker_id)) return fail(ctx, HQTICK_E_INVALID, "hqtick_retracting_add: null array");
+    if (int rc = ledger_guard(ctx)) return rc;  // (a pending placement holds that tick's changes of this table: they are applied to the table as the tick saw it)
     ctx->retr.add(n, task_id, worker_id);
     return 0;
 }
@@ -764,6 +786,7 @@ int hqtick_retract_response(hqtick_ctx *ctx, uint32_t worker_id, uint32_t n, con
                             const uint32_t **assigned_worker_id, const uint8_t **assigned_variant) {
     if (!ctx) return HQTICK_E_INVALID;
     if (n && !task_id) return fail(ctx, HQTICK_E_INVALID, "hqtick_retract_response: null array");
+    if (int rc = ledger_guard(ctx)) return rc;
     const int left = ctx->retr.response(worker_id, n, task_id);
     ctx->retr.last.get(n_assigned, assigned_task, assigned_worker_id, assigned_variant);
     return left;
@@ -1229,7 +1252,7 @@ int hqtick_resident_check(hqtick_ctx *ctx, uint32_t parts, hqtick_check_report *
         l.n_live = ctx->asg.n_live; l.mn_live = ctx->asg.mn_live; l.pf_live = ctx->asg.pf_live;
         req = hqaudit::ReqHost{lv.rq_off, lv.vent_off, lv.ent_res, lv.var_nodes, lv.ent_kind, lv.ent_amt};
         S.have |= hqaudit::HAVE_LEDGER;
-        if (!(ctx->asg.pending && ctx->ready.selection_live())) S.have |= hqaudit::HAVE_LEDGER_SETTLED;  // (a placement waiting for its consume: the Retracting table is already that tick's)
+        if (!(ctx->asg.pending && ctx->ready.selection_live())) S.have |= hqaudit::HAVE_LEDGER_SETTLED;  // (a placement waiting for its consume: a host between the two calls of a tick is half way through a handler)
         if (ctx->asg.tracking()) S.have |= hqaudit::HAVE_TRACKING;
     }
     hqaudit::RetrHost retr;

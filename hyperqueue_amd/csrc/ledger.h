@@ -102,7 +102,9 @@ class Ledger {
     // the tick's redirects and multi-node placements (worker ids) and its new_free wait with its staged records; saved: their request ids are in saved_rq()
     void collect_tick(const hqtick_snapshot *s, const hqtick_result *out, const std::vector<uint64_t> &new_free, const std::vector<uint32_t> &mn_rq, bool saved);
     int apply_tick(const Env &e);  // ... and become ledger state
-    // a waiting placement is live only while the tick's selection is (selection: last_valid && !last_consumed)
+    // what collect_tick() took has something to enter: staged records, redirects, multi-node placements, or free rows that differ from the mirror's (sync_mirror read them for this tick)
+    bool tick_enters(const Env &e) const { return stage_n || !red_id.empty() || !pmn_id.empty() || pend_free != *e.free_; }
+    // a waiting placement is live only while the tick's selection is (selection: ReadySet::selection_live(): a selection not yet consumed, or an empty one held for its placement)
     bool pending_live(bool selection) { if (pending && !selection) pending = false; return pending; }
     uint32_t max_variants() const { uint32_t m = 0; for (size_t q = 0; q + 1 < rq_off.size(); q++) m = std::max(m, rq_off[q + 1] - rq_off[q]); return m; }
     bool tracking() const { return pf_on; }

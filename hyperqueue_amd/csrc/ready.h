@@ -41,8 +41,12 @@ class ReadySet {
     bool compact_due() const { return n_ > 4096 && live_ * 2 < n_; }  // more tombstones than tasks, and enough rows to be worth a pass
     int compact(const Env &e) { return rebuild(e, nullptr, nullptr, nullptr, 0); }
     // ---- the last tick's selection (the launch tables that replay it are the tick's and stay with it)
-    void selection_void() { valid_ = false; }  // the tick is overwriting the plan the selection would be replayed from
-    void selected(uint32_t n_sel) { n_sel_ = n_sel; consumed_ = n_sel == 0; if (n_sel) valid_ = true; }
+    void selection_void() { valid_ = false; held_ = false; }  // the tick is overwriting the plan the selection would be replayed from
+    void selected(uint32_t n_sel) { n_sel_ = n_sel; consumed_ = n_sel == 0; held_ = false; if (n_sel) valid_ = true; }
+    // a tick that selected nothing may still have produced something that becomes state at the consume (redirects, multi-node placements, free rows): its caller
+    // holds the empty selection, which then is live until hqtick_ready_consume_last has entered that (entered()) or a delta abandons it, like any selection
+    void hold_empty() { if (!n_sel_ && consumed_) held_ = true; }
+    void entered() { held_ = false; }
     void consumed_in_tick() { live_ -= n_sel_; consumed_ = true; unconfirmed_ = true; }  // HQTICK_FLAG_CONSUME_IN_TICK: the selection kernel is writing the tombstones itself
     bool unconfirmed() const { return unconfirmed_; }  // ... and its tick has not returned yet
     void confirm() { unconfirmed_ = false; }
@@ -52,11 +56,11 @@ class ReadySet {
     uint32_t selected_count() const { return n_sel_; }
     bool selection_valid() const { return valid_; }
     bool selection_pending() const { return !consumed_; }
-    bool selection_live() const { return valid_ && !consumed_; }
+    bool selection_live() const { return (valid_ && !consumed_) || held_; }
 
   private:
     int fail(int code, const std::string &m) { err = m; return code; }
-    void abandon_selection() { valid_ = false; consumed_ = true; }  // the ONE place a delta invalidates the selection
+    void abandon_selection() { valid_ = false; consumed_ = true; held_ = false; }  // the ONE place a delta invalidates the selection
     bool can_append(uint64_t n_add, uint64_t first_id, uint64_t last_id) const;
     int refused(uint32_t flag_word);  // what the append / merge kernels found wrong with a batch
     int appended(const Env &e, bool waits_on_kernel, uint64_t n_add, uint64_t last_id, const double *trace = nullptr);  // wait, decode, counts, compaction if due
@@ -71,7 +75,7 @@ class ReadySet {
     uint64_t live_ = 0, staged_n = 0;  // (staged_n: tasks stage() made room for, 0: nothing staged)
     uint64_t max_id = 0; bool max_id_valid = false;  // an upper bound of every resident id (the last one after an upload / a rebuild): a batch that starts above it is appended
     uint32_t n_appends = 0;
-    uint32_t n_sel_ = 0; bool consumed_ = true, valid_ = false, unconfirmed_ = false;
+    uint32_t n_sel_ = 0; bool consumed_ = true, valid_ = false, unconfirmed_ = false, held_ = false;
 };
 
 }  // namespace hqready

@@ -253,7 +253,7 @@ class Tick:
         t = np.ascontiguousarray(task_id, np.uint64)
         n = C.c_uint32(); pt, pw, pv = abi.u64p(), abi.u32p(), abi.u8p()
         self._lib.hqtick_retract_response.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, abi.u64p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u8p)]
-        self._chk(self._lib.hqtick_retract_response(self._ctx, int(worker_id), len(t), t.ctypes.data_as(abi.u64p), C.byref(n), C.byref(pt), C.byref(pw), C.byref(pv)))
+        self.last_retract_left = self._chk(self._lib.hqtick_retract_response(self._ctx, int(worker_id), len(t), t.ctypes.data_as(abi.u64p), C.byref(n), C.byref(pt), C.byref(pw), C.byref(pv)))  # tasks that left the table
         k = n.value
         return list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pw, k, np.uint32).tolist(), abi._np(pv, k, np.uint8).tolist())) if k else []
 

@@ -423,7 +423,8 @@ int hqtick_cluster_drop(hqtick_ctx *ctx);
  * hqtick_cluster_update_workers), remaining lifetime, min_utilization, flags, groups and the blocked pairs.  Say so with n_workers = HQ_WORKERS_RESIDENT: such a
  * tick FAILS (HQTICK_E_INVALID) when the library holds no worker set (never uploaded, or hqtick_cluster_drop) instead of running as a legitimate tick of
  * zero workers, which is what n_workers = 0 with NULL arrays means without a resident set (with one, 0 and the current count are accepted as before).
- * worker_map_rank is emulated, and the per-worker CSRs assigned_off / prefilled_off (if given) must have current-count + 1 entries.  The reactor then
+ * worker_map_rank is emulated (the map is filled in id order at hqtick_cluster_upload and then follows hqtick_cluster_add_workers / _remove_workers as
+ * core.worker_map follows on_new_worker / on_remove_worker: a removal leaves the map's size and the other workers' places as they were), and the per-worker CSRs assigned_off / prefilled_off (if given) must have current-count + 1 entries.  The reactor then
  * no longer flattens W x R worker arrays per tick.
  */
 int hqtick_cluster_add_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id, const uint64_t *total_rows, const uint64_t *free_rows,
@@ -520,7 +521,13 @@ int hqtick_cluster_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uin
  * old target) with the free rows of result.new_free — enters the ledger when it becomes state: at hqtick_ready_consume_last in the two-call form, inside the
  * tick under HQTICK_FLAG_CONSUME_IN_TICK (a tick that fails leaves ledger and free rows as they were), at once after hqtick_run.  Until a pending placement
  * is consumed, ledger and membership calls are HQTICK_E_INVALID; a tick that is not consumed (any ready-set or graph delta, another tick) is abandoned with
- * its selection and never enters.  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
+ * its selection and never enters.  A placement is pending whenever it has something to enter -- records, redirects, multi-node placements or a free row that
+ * changed -- also when the tick handed out no ready task at all (its only output the redirect of a prefilled task to a worker with room): that tick, too, waits
+ * for hqtick_ready_consume_last, which then enters it without replaying a selection, and a delta abandons it like any other.  A two-call tick that has nothing
+ * to enter leaves nothing pending.  With a resident Retracting table (HQ_RETRACTING_RESIDENT) what the tick did to Retracting tasks becomes state at the same
+ * moment as the placement, so an abandoned tick leaves the table, too, as it was; hqtick_retracting_add and hqtick_retract_response are refused in between
+ * like the ledger calls.  A resident ready set that holds only tombstones is the empty set: the tick
+ * runs (it may still redirect prefilled tasks).  If entering the placement itself fails (a device allocation), the ledger is switched off and the call says so: the
  * tasks have left the ready set, so the host uploads the worker set and enables the ledger again from its own view.
  * Remaining lifetimes: hqtick_cluster_update_workers needs the free rows of every row it lists, which a ledger host no longer holds, so time limits running
  * down go through the clock instead (hqtick_cluster_set_clock above: 8 bytes per tick, no rows).  hqtick_cluster_update_workers remains for corrections by a host

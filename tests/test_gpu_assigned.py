@@ -75,7 +75,7 @@ def test_ledger_follows_sched_env(seed):
                 if new_msgs:
                     a.retracting_add([t for (_, t) in new_msgs], [w for (w, _) in new_msgs])
             try:
-                # (the resident worker set emulates worker_map_rank — a map built by inserting ascending ids, include/hqtick.h — so B ticks on that too)
+                # (the resident worker set emulates worker_map_rank, include/hqtick.h; no scenario here loses a worker at a size where the map's history shows, so B ticks on a map of the ids present)
                 want = b.tick(dataclasses.replace(snap, worker_map_rank=None, _keep=[]))
             except HqTickError as err:
                 assert err.code == abi.HQTICK_E_UNSUPPORTED

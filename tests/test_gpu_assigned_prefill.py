@@ -1,6 +1,6 @@
 """Prefilled tasks in the assignment ledger (hqtick_assigned_track_prefilled / _start_prefilled / _unprefill / _prefilled_count,
 hqtick_cluster_last_requeued_prefilled).  As in test_gpu_assigned_mn.py, context A keeps the ledger — here with prefilled tracking on and NO
-prefilled CSR in its snapshots — and context B runs today's protocol on SchedEnv's full snapshot (worker_map_rank=None): every tick of A equals B's, and
+prefilled CSR in its snapshots — and context B runs today's protocol on SchedEnv's full snapshot (its worker_map_rank included): every tick of A equals B's, and
 after every event A's free rows, assigned tasks and prefilled tasks equal SchedEnv's."""
 import dataclasses
 import os
@@ -44,7 +44,9 @@ def _ledger_tick(t, snap, prefilled_csr=False):
 
 
 def _b_snap(snap):
-    return dataclasses.replace(snap, worker_map_rank=None, _keep=[])
+    # (with SchedEnv's own worker_map_rank: the resident worker set keeps the worker map with its removals, as core.worker_map does, so after a lost worker A
+    # walks the workers in the reference's order and no longer in that of the remaining ids inserted afresh, which worker_map_rank=None stands for)
+    return dataclasses.replace(snap, _keep=[])
 
 
 def _n_kind(res, kind):

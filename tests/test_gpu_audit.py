@@ -232,22 +232,7 @@ def test_clean_after_every_step_and_a_twin_that_never_audits_ends_the_same():
     assert audited == plain
 
 
-def _sanity_check_free(e):
-    """Worker::sanity_check (server/worker.rs:236-271) on the SchedEnv mirror: resources.clone(), then remove(rq) per assigned task, against free_resources.
-    -> the (worker id << 32 | resource) keys where they differ.  The generator of those scenarios starts prefilled tasks on workers that have no room for them
-    (SchedEnv.start_prefilled_task subtracts with saturation, as the reference does), and a later release then adds back more than was taken: states the
-    reference's own check asserts on, and that the audit must report -- exactly those, no others."""
-    R, bad = e.n_resources, []
-    for wid, w in e.workers.items():
-        if not w.sn():
-            continue
-        want = list(w.total) + [0] * (R - len(w.total))
-        for tid in w.assigned_tasks:
-            for (r, kind, a) in e._variant(e.tasks[tid].rq, e._assigned_variant(tid, wid))["entries"]:
-                want[r] = max(0, want[r] - a) if kind == abi.HQ_ENTRY_AMOUNT else 0
-        have = list(w.free) + [0] * (R - len(w.free))
-        bad += [wid << 32 | r for r in range(R) if want[r] != have[r]]
-    return bad
+from resident_checks import sanity_check_free as _sanity_check_free  # noqa: E402  (Worker::sanity_check on the mirror)
 
 
 class _AuditHost:

@@ -12,6 +12,7 @@ import pytest
 
 import cancel_cases as cc
 import finish_cases as fc
+import resident_checks as rc
 from hyperqueue_amd import abi, core, workloads
 from hyperqueue_amd.core import SchedEnv, TaskBuilder as TB, WorkerBuilder as WB
 
@@ -68,12 +69,7 @@ def _finish_checked(a, e, pairs, overfull=False):
     return got
 
 
-def _ledger_matches(a, e):
-    assert a.assigned_mn_count() == sum(1 for t in e.tasks.values() if t.state == core.RUNNING_MN)
-    assert a.assigned_prefilled_count() == sum(1 for t in e.tasks.values() if t.state == core.PREFILLED)
-    assert a.assigned_count() == sum(len(w.assigned_tasks) for w in e.workers.values())
-    sn = [abi.HQ_WORKER_SN if e.workers[w].sn() else 0 for w in sorted(e.workers)]
-    assert [f & abi.HQ_WORKER_SN for f in a.cluster_worker_flags().tolist()] == sn
+_ledger_matches = rc.ledger_matches  # (tests/resident_checks.py)
 
 
 def _ready_is(a, e):

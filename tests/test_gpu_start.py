@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import cancel_cases as cc
+import resident_checks as rc
 import start_cases as sc
 import test_gpu_finish as gf
 from hyperqueue_amd import abi, core, workloads
@@ -42,34 +43,7 @@ def _cols(e, triples):
             [e.tasks[x].priority if x in e.tasks else 0 for x in ids])
 
 
-def _running_want(e, ids):
-    """the running byte per id as the mirror's states give it: Running 1; Assigned, Prefilled, multi-node and a Retracting task's entry on its redirect target
-    (or on its own worker, retaken) 0; no entry 0xFF"""
-    out = []
-    for x in ids:
-        t = e.tasks.get(x)
-        if t is None or t.state in (core.WAITING, core.FINISHED):
-            out.append(NO_ENTRY)
-        elif t.state == core.RETRACTING:
-            out.append(0 if x in e.redirects or x in e.retaken_variant else NO_ENTRY)
-        else:
-            out.append(1 if t.state == core.RUNNING else 0)
-    return out
-
-
-def _entries_match(a, e):
-    """running bytes, workers and variants of every id the mirror ever had"""
-    ids = sorted(e.tasks)
-    assert a.assigned_running(ids).tolist() == _running_want(e, ids)
-    lw, lv = a.assigned_lookup(ids)
-    for x, w, v in zip(ids, lw.tolist(), lv.tolist()):
-        t = e.tasks[x]
-        if t.state in (core.ASSIGNED, core.RUNNING):
-            assert (w, v) == (t.worker, t.rv), x
-        elif t.state == core.PREFILLED:
-            assert (w, v) == (t.worker, 0xFE), x
-        elif t.state == core.RUNNING_MN:
-            assert (w, v) == (t.mn_workers[0], 0xFF), x
+_running_want, _entries_match = rc.running_want, rc.entries_match  # (the comparison itself: tests/resident_checks.py)
 
 
 def _start_checked(a, e, triples, overfull=False):
