@@ -114,6 +114,14 @@ HQ_FAIL_ACCEPTED = (HQ_FAIL_ASSIGNED, HQ_FAIL_MN, HQ_FAIL_PREFILLED, HQ_FAIL_RET
  HQ_START_BAD_VARIANT) = range(10)
 HQ_START_ACCEPTED = (HQ_START_ASSIGNED, HQ_START_MN, HQ_START_PREFILLED, HQ_START_RETRACTING)
 HQ_START_ELIGIBLE = (HQ_START_ASSIGNED, HQ_START_PREFILLED, HQ_START_RETRACTING)  # the accepted kinds that claim their id (a multi-node position changes nothing)
+# hqtick_reject_last_routes (include/hqtick.h): what a batch position of hqtick_reject_tasks was; 1 to 4 are accepted, the others refused
+(HQ_REJECT_NONE, HQ_REJECT_ASSIGNED, HQ_REJECT_PREFILLED, HQ_REJECT_RETRACTING, HQ_REJECT_REDIRECTED, HQ_REJECT_REPEAT, HQ_REJECT_WRONG_WORKER, HQ_REJECT_WRONG_VARIANT,
+ HQ_REJECT_RUNNING, HQ_REJECT_BAD_VARIANT, HQ_REJECT_MN) = range(11)
+HQ_REJECT_ACCEPTED = (HQ_REJECT_ASSIGNED, HQ_REJECT_PREFILLED, HQ_REJECT_RETRACTING, HQ_REJECT_REDIRECTED)
+HQ_REJECT_ELIGIBLE = HQ_REJECT_ACCEPTED  # every accepted kind changes its task and claims its id
+HQ_REJECT_BLOCKS = HQ_REJECT_ACCEPTED + (HQ_REJECT_WRONG_WORKER, HQ_REJECT_WRONG_VARIANT)  # the kinds whose position ran block_request (if it names a variant the request has)
+HQ_REJECT_SCHEDULES = (HQ_REJECT_ASSIGNED, HQ_REJECT_PREFILLED, HQ_REJECT_RETRACTING)  # task_reject returns true: the handler asks for scheduling
+HQ_VARIANT_NONE = 0xFF  # the variant byte of a RejectRequest that names none
 
 # hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
 HQ_CHECK_READY, HQ_CHECK_LEDGER, HQ_CHECK_GRAPH, HQ_CHECK_CROSS, HQ_CHECK_STRICT, HQ_CHECK_ALL = 1, 2, 4, 8, 16, 15

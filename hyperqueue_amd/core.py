@@ -998,6 +998,92 @@ class SchedEnv:
             self.last_start_kinds.append(kind)
         return accepted
 
+    def reject_tasks(self, triples) -> int:
+        """task_reject (server/reactor.rs:365-445) for the (task id, reporting worker, rejected variant or None) triples, strictly in this order, the
+        Retracting arms included, with the reference's unreachable!() arms as refusals.  What a triple IS follows from the task's state before the batch and from
+        the triples that claimed the id before it:
+          Retracting         reported by the worker it is retracting FROM: with a redirect the task is Assigned on the target (:420-431) HQ_REJECT_REDIRECTED
+                             without one it is Waiting again; it already sits in its queue                                               HQ_REJECT_RETRACTING
+          RunningMultiNode   (unreachable!)                                                                                             HQ_REJECT_MN
+          any held task reported by another worker, or by one that is not here                                                          HQ_REJECT_WRONG_WORKER
+          a variant the task's request does not have                                                                                    HQ_REJECT_BAD_VARIANT
+          Prefilled          reported by its worker, any variant or None                                                                HQ_REJECT_PREFILLED
+          Running            (unreachable!)                                                                                             HQ_REJECT_RUNNING
+          Assigned           None or another variant than it was assigned with                                                          HQ_REJECT_WRONG_VARIANT
+          Assigned           its worker and variant: remove_sn_task, back to its queue                                                  HQ_REJECT_ASSIGNED
+          a later accepted triple of an id an earlier one claimed                                                                       HQ_REJECT_REPEAT
+          Waiting, finished or not here                                                                                                 HQ_REJECT_NONE
+        worker.block_request(request, variant) runs first (:389-391) for the kinds in abi.HQ_REJECT_BLOCKS when a variant is named, the request has it and the
+        reporter is a worker of the set.  Two deviations from the reference, as in csrc/reject_core.h: an Assigned or Prefilled task reported by the wrong worker
+        is refused after its block (the reference requeues it without releasing it); a reporter that is not here blocks nothing.
+        The requeued tasks join their queues (add_ready_task with its prefill disposal) after the last triple, ids ascending: the batch is one call, and the
+        process_retracted a disposal asks of the host can only follow it (a Prefilled task rejected later in the batch than the arrival that would have dissolved
+        its set is therefore rejected as Prefilled, not as Retracting; it ends Waiting in its queue either way).
+        Returns the number of accepted triples.  last_reject_kinds: per triple its abi.HQ_REJECT_* kind; last_reject_requeued: [(task, rq, priority)], ids
+        ascending; last_reject_reassigned: [(task, target worker, variant)] in batch order."""
+        before: Dict[int, Optional[Tuple]] = {}
+        claimed: set = set()
+        accepted = 0
+        self.last_reject_kinds: List[int] = []
+        self.last_reject_reassigned: List[Tuple[int, int, int]] = []
+        requeued: List[int] = []
+        for tid, wid, v in triples:
+            t = self.tasks.get(tid)
+            if tid not in before:
+                before[tid] = None if t is None else (t.state, t.worker, t.rv, tid in self.redirects)
+            s = before[tid]
+            v_none = v is None
+            v_exists = not v_none and t is not None and 0 <= v < len(self.requests[t.rq])
+            bad = not v_none and not v_exists
+            if s is None or s[0] in (WAITING, FINISHED):
+                kind = abi.HQ_REJECT_NONE
+            elif s[0] == RETRACTING:
+                kind = abi.HQ_REJECT_WRONG_WORKER if wid != s[1] else abi.HQ_REJECT_BAD_VARIANT if bad else abi.HQ_REJECT_REDIRECTED if s[3] else abi.HQ_REJECT_RETRACTING
+            elif s[0] == RUNNING_MN:
+                kind = abi.HQ_REJECT_MN
+            elif wid != s[1]:
+                kind = abi.HQ_REJECT_WRONG_WORKER
+            elif bad:
+                kind = abi.HQ_REJECT_BAD_VARIANT
+            elif s[0] == PREFILLED:
+                kind = abi.HQ_REJECT_PREFILLED
+            elif s[0] == RUNNING:
+                kind = abi.HQ_REJECT_RUNNING
+            elif v_none or v != s[2]:
+                kind = abi.HQ_REJECT_WRONG_VARIANT
+            else:
+                kind = abi.HQ_REJECT_ASSIGNED
+            if kind in abi.HQ_REJECT_ELIGIBLE:
+                if tid in claimed:
+                    kind = abi.HQ_REJECT_REPEAT
+                else:
+                    claimed.add(tid)
+            if kind in abi.HQ_REJECT_BLOCKS and v_exists and wid in self.workers:
+                self.workers[wid].blocked_requests.add((t.rq, v))
+            if kind == abi.HQ_REJECT_ASSIGNED:
+                w = self.workers[wid]
+                w.assigned_tasks.discard(tid)
+                self._add(w, t.rq, t.rv)  # remove_sn_task  server/worker.rs:223-234
+                t.state, t.worker = WAITING, None
+                requeued.append(tid)
+            elif kind == abi.HQ_REJECT_PREFILLED:
+                self.workers[wid].prefilled_tasks.discard(tid)
+                self.prefill[t.rq][1].remove(tid)
+                t.state, t.worker = WAITING, None
+                requeued.append(tid)
+            elif kind == abi.HQ_REJECT_REDIRECTED:
+                target, rv = self.redirects.pop(tid)
+                t.state, t.worker, t.rv = ASSIGNED, target, rv
+                self.last_reject_reassigned.append((tid, target, rv))
+            elif kind == abi.HQ_REJECT_RETRACTING:
+                t.state, t.worker = WAITING, None
+            accepted += kind in abi.HQ_REJECT_ACCEPTED
+            self.last_reject_kinds.append(kind)
+        for tid in sorted(requeued):
+            self._add_ready(self.tasks[tid])
+        self.last_reject_requeued = [(tid, self.tasks[tid].rq, self.tasks[tid].priority) for tid in sorted(requeued)]
+        return accepted
+
     # -- bookkeeping used by tests ----------------------------------------------------------------------
     def assigned_counts(self) -> List[int]:
         counts = [0] * len(self.requests)

@@ -113,6 +113,25 @@ hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *
 // makes a position _WAITING (accepted, nothing here to claim) or _NOT_WAITING; a prefilled entry reported by its worker is claimed and leaves as pf_remove takes it
 // (prefilled count down, no free row; counted in C_DONE and C_PF), so the tables end as after release(accepted ids in batch order) + pf_remove(those ids).
 hipError_t fail(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s);
+// hqtick_reject_tasks: the four passes in their reject mode, the fail mode with reject_core.h's rule and HQ_REJECT_* kinds, then the requeue's
+// compaction.  variant [n] is the rejected variant per position (0xFF: None), rq_in [n] (nullptr with n_retr == 0) the request of a position the Retracting
+// overrides decide.  An override position never claims a ledger entry (a redirect target's entry stays); its kind comes back as _RETRACTING and the host settles it
+// against _REDIRECTED.  An _ASSIGNED entry leaves as by release, a _PREFILLED one as by pf_remove (C_DONE / C_PF); before its key becomes a tombstone the apply pass
+// records (priority, request) at its position and sets flag[i].  blk_rq [n]: the request whose (request, variant[i]) pair the position adds to its reporter's
+// blocked set by the kind pass 1 gave it (NONE: none; the host drops those of positions that ended as _REPEAT).
+// The compaction reads the flags through perm [n] -- the positions by ascending (id, position), staged by the host -- so the output order is that of the ids and
+// does not depend on the order atomics arrive in: a count per 256-position slice, hqk::scan_waves over the slice table (slices [>= n_slices rounded up to 16], the
+// total lands in *total), a write of the three dense columns into out_* (device, for the merge) and o_* (pinned, for the host).  Claims make every id accepted at
+// most once, so the ids come out strictly ascending.  ctr[C_OUT]: the accepted positions.
+struct RejectCols {
+    const uint8_t *variant; const uint32_t *rq_in; const uint32_t *perm;
+    uint32_t *blk_rq; uint8_t *flag; uint64_t *rec_prio; uint32_t *rec_rq;
+    uint32_t *slices; uint32_t *total;
+    uint64_t *out_id; uint64_t *out_prio; uint32_t *out_rq;
+    uint64_t *o_id; uint64_t *o_prio; uint32_t *o_rq;
+};
+hipError_t reject(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, RejectCols rj, uint32_t *ctr,
+                  hipStream_t s);
 // every entry of the workers `lost` (sorted ids) leaves the table; (id, rq, priority) appended to out_* [cap_out] (order undefined), count in ctr[C_OUT].
 // A multi-node entry is its ROOT's (on_remove_worker, reactor.rs:107-128): a lost root evicts the task, a lost non-root leaves the entry alone.
 // out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF); out_run [cap_out]: its running byte

@@ -1,7 +1,9 @@
 // Kernels of the assignment ledger (assigned.h).  gfx950 only.
 #include "assigned.h"
 #include "fail_core.h"
+#include "kernels.h"
 #include "finish_core.h"
+#include "reject_core.h"
 #include "start_core.h"
 
 #include "../../include/hqtick.h"
@@ -11,10 +13,13 @@ namespace hqasg {
 namespace {
 
 constexpr uint32_t TPB = 256;
-enum RelMode : int { M_RELEASE = 0, M_CANCEL = 1, M_FINISH = 2, M_FAIL = 3 };  // what the release's four passes run as (release / hqtick_cancel_tasks / hqtick_finish_tasks / hqtick_fail_tasks)
-// the two modes with a reporter per position share their claims; what differs is the rule and its constants
-template <int MODE> __device__ __forceinline__ bool rep_accepted(uint32_t kind) { return MODE == M_FAIL ? hqfail::accepted(kind) : hqfinish::accepted(kind); }
-template <int MODE> __device__ __forceinline__ uint32_t rep_repeat(uint32_t kind) { return MODE == M_FAIL ? hqfail::after_claim(kind, true) : hqfinish::after_claim(kind, true); }
+enum RelMode : int { M_RELEASE = 0, M_CANCEL = 1, M_FINISH = 2, M_FAIL = 3, M_REJECT = 4 };  // what the release's four passes run as (release / hqtick_cancel_tasks / hqtick_finish_tasks / hqtick_fail_tasks / hqtick_reject_tasks)
+// the three modes with a reporter per position share their claims; what differs is the rule and its constants
+template <int MODE> __device__ __forceinline__ bool rep_accepted(uint32_t kind) { return MODE == M_REJECT ? hqreject::accepted(kind) : MODE == M_FAIL ? hqfail::accepted(kind) : hqfinish::accepted(kind); }
+template <int MODE> __device__ __forceinline__ uint32_t rep_repeat(uint32_t kind) {
+    return MODE == M_REJECT ? hqreject::after_claim(kind, true) : MODE == M_FAIL ? hqfail::after_claim(kind, true) : hqfinish::after_claim(kind, true);
+}
+template <int MODE> __device__ __forceinline__ uint32_t rep_retracting() { return MODE == M_REJECT ? HQ_REJECT_RETRACTING : MODE == M_FAIL ? HQ_FAIL_RETRACTING : HQ_FINISH_RETRACTING; }
 inline unsigned nblk(uint64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 __device__ __forceinline__ uint32_t ht_hash(uint64_t k) {  // murmur3 finaliser (graph.hip's)
@@ -186,9 +191,12 @@ __device__ __forceinline__ uint32_t retr_find(const CancelCols &cc, uint64_t id)
 // name the same winner whatever order they arrive in.  A refused position keeps pos NONE: the later passes never see it.
 // FAIL (hqtick_fail_tasks): the same with fail_core.h's rule.  A prefilled entry reported by its worker IS claimed (pass 3 takes it out as the cancel mode does); a
 // _WAITING position (reporter HQ_NO_WORKER, neither entry nor override) is accepted but has nothing here to claim: the graph step settles its repeats.
+// REJECT (hqtick_reject_tasks): reject_core.h's rule, which also reads the rejected variant, the running byte and the request tables (q, r and rj are read in this
+// mode alone).  A position the overrides decide claims its override and never an entry: a redirect target's entry stays where it is.  The pair the position
+// blocks follows from the same inputs and is written here; a position that later loses its claim keeps it, and the host drops it by the final kind.
 template <int MODE>
-__global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, CancelCols cc, uint32_t *ctr) {
-    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH, FAIL = MODE == M_FAIL;
+__global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *pos, CancelCols cc, uint32_t *ctr, Req q, Rows r, RejectCols rj) {
+    constexpr bool CANCEL = MODE == M_CANCEL, FINISH = MODE == M_FINISH, FAIL = MODE == M_FAIL, REJECT = MODE == M_REJECT;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     uint32_t b = NONE;
     if (i < n) {
@@ -206,6 +214,20 @@ __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *p
             // a prefilled entry is never claimed under a Retracting override, and by a finish not at all
             if (b != NONE && t.variant[b] == PF_VARIANT && !(FAIL && kind == HQ_FAIL_PREFILLED)) b = NONE;
         }
+        if (REJECT) {
+            const uint32_t k = retr_find(cc, id[i]), rep = cc.reporter[i], v = rj.variant[i];
+            const uint32_t ev = b == NONE ? 0u : t.variant[b];
+            const uint32_t cls = ev == PF_VARIANT ? hqreject::E_PF : ev == MN_VARIANT ? hqreject::E_MN : hqreject::E_SN;
+            const uint32_t rq = k != NONE ? (rj.rq_in ? rj.rq_in[i] : NONE) : b != NONE ? t.rq[b] : NONE;  // the request of the task: the caller's for an override, else the entry's
+            const bool v_none = v == 0xFFu, v_exists = !v_none && v < PF_VARIANT && rq != NONE && variant_ok(q, rq, v);
+            const uint32_t kind = hqreject::kind_before_claim(b != NONE, cls, b != NONE && t.worker[b] == rep, ev == v, b != NONE && t.run[b] != 0, v_none, v_exists, k != NONE,
+                                                              k != NONE && cc.retr_wid[k] == rep, false);
+            cc.kind[i] = (uint8_t)kind;
+            rj.blk_rq[i] = hqreject::blocks(kind, v_none, v_exists, row_of(r, rep) != NONE) ? rq : NONE;
+            rj.flag[i] = 0;
+            if (k != NONE) { if (hqreject::accepted(kind)) atomicMin(&cc.retr_hit[k], i); b = NONE; }
+            else if (!hqreject::accepted(kind)) b = NONE;
+        }
         pos[i] = b;
         if (b != NONE) atomicMin(&t.claim[b], i);
         if (CANCEL) {
@@ -219,7 +241,7 @@ __global__ void k_rel_claim(Table t, uint32_t n, const uint64_t *id, uint32_t *p
 // pass 2: per (worker row, resource) the position + 1 of the batch's last ALL entry
 template <int MODE>
 __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos, uint32_t *last_all, CancelCols cc, uint32_t *ctr) {
-    constexpr bool CANCEL = MODE == M_CANCEL, REPORTED = MODE == M_FINISH || MODE == M_FAIL, PF_LEAVES = MODE == M_CANCEL || MODE == M_FAIL;
+    constexpr bool CANCEL = MODE == M_CANCEL, REPORTED = MODE == M_FINISH || MODE == M_FAIL || MODE == M_REJECT, PF_LEAVES = MODE == M_CANCEL || MODE == M_FAIL || MODE == M_REJECT;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool dup = false, bad = false;
@@ -245,9 +267,12 @@ __global__ void k_rel_last_all(Table t, Req q, Rows r, uint32_t n, uint32_t *pos
 // pass to learn that from).  C_OUT counts the accepted positions: those that leave the table and the Retracting ids that had no entry.
 // FAIL: as FINISH, and a claimed prefilled entry leaves as in the cancel mode -- its prefilled count drops, no free row and no last-ALL word is touched, so the
 // order-dependent arithmetic of the other positions never sees it.  C_OUT counts the _WAITING positions too.
+// REJECT: as FAIL; every entry that leaves goes back into the ready set, so its priority and request are recorded at its position, with its flag, before the key
+// becomes a tombstone (the compaction behind this pass makes the dense columns of them).  No claimed entry stays, so no claim word is left behind.
 template <int MODE>
-__global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr) {
-    constexpr bool CANCEL = MODE == M_CANCEL, REPORTED = MODE == M_FINISH || MODE == M_FAIL, PF_LEAVES = MODE == M_CANCEL || MODE == M_FAIL;
+__global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *id, const uint32_t *pos, const uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr,
+                            RejectCols rj) {
+    constexpr bool CANCEL = MODE == M_CANCEL, REPORTED = MODE == M_FINISH || MODE == M_FAIL || MODE == M_REJECT, PF_LEAVES = MODE == M_CANCEL || MODE == M_FAIL || MODE == M_REJECT;
     const uint32_t i = blockIdx.x * TPB + threadIdx.x;
     const uint32_t b = i < n ? pos[i] : NONE;
     bool mn = false, pf = false;
@@ -266,6 +291,7 @@ __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *
             atomicSub(&r.counts[(size_t)row * r.stride + slot], 1u);
         }
         if (CANCEL) { cc.route[i] = row_of(r, t.worker[b]); cc.kind[i] = pf ? HQ_CANCEL_PREFILLED : mn ? HQ_CANCEL_MN : HQ_CANCEL_ASSIGNED; }
+        if (MODE == M_REJECT) { rj.rec_prio[i] = t.prio[b]; rj.rec_rq[i] = t.rq[b]; rj.flag[i] = 1; }
         t.key[b] = HT_TOMB; t.claim[b] = NONE;
     }
     if (CANCEL && i < n) {
@@ -278,7 +304,7 @@ __global__ void k_rel_apply(Table t, Req q, Rows r, uint32_t n, const uint64_t *
     bool acc = false;
     if (REPORTED && i < n) {
         uint32_t kind = cc.kind[i];
-        if (kind == (MODE == M_FAIL ? HQ_FAIL_RETRACTING : HQ_FINISH_RETRACTING)) {
+        if (kind == rep_retracting<MODE>()) {
             const uint32_t k = retr_find(cc, id[i]);
             if (k == NONE || cc.retr_hit[k] != i) { kind = rep_repeat<MODE>(kind); cc.kind[i] = (uint8_t)kind; }
         }
@@ -539,6 +565,42 @@ __global__ void k_start_unclaim(Table t, StartCols sc, uint32_t lo, uint32_t hi)
     if (b != NONE && b <= t.mask) t.claim[b] = NONE;
 }
 
+// ---- hqtick_reject_tasks: the requeue's compaction.  perm lists the batch positions by ascending (id, position); the apply pass left a flag, a
+// priority and a request at every position whose entry went back.  One wavefront per 256-entry slice of perm, as the ready set's rebuild walks its columns.
+// pass 1: flagged positions per slice
+__global__ void __launch_bounds__(TPB) k_rej_count(RejectCols rj, uint32_t n, uint32_t n_slices) {
+    const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
+    if (wave >= n_slices) return;
+    uint32_t c = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint32_t j = wave * 256 + (uint32_t)u * 64 + lane;
+        const uint32_t p = j < n ? rj.perm[j] : NONE;
+        c += (uint32_t)__popcll(__ballot(p < n && rj.flag[p] != 0));
+    }
+    if (lane == 0) rj.slices[wave] = c;
+}
+// pass 2 (behind the scan of the slice table): entry j of perm lands at slice offset + flagged entries before it in the slice
+__global__ void __launch_bounds__(TPB) k_rej_compact(RejectCols rj, const uint64_t *id, uint32_t n, uint32_t n_slices) {
+    const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = __lane_id();
+    if (wave >= n_slices) return;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t run = rj.slices[wave];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint32_t j = wave * 256 + (uint32_t)u * 64 + lane;
+        const uint32_t p = j < n ? rj.perm[j] : NONE;
+        const bool f = p < n && rj.flag[p] != 0;
+        const uint64_t b = __ballot(f);
+        const uint32_t dst = run + (uint32_t)__popcll(b & lt);
+        run += (uint32_t)__popcll(b);
+        if (!f || dst >= n) continue;  // (at most n flags: the bound holds whatever perm lists)
+        const uint64_t k = id[p], pr = rj.rec_prio[p]; const uint32_t rq = rj.rec_rq[p];
+        rj.out_id[dst] = k; rj.out_prio[dst] = pr; rj.out_rq[dst] = rq;
+        rj.o_id[dst] = k; rj.o_prio[dst] = pr; rj.o_rq[dst] = rq;
+    }
+}
+
 }  // namespace
 
 hipError_t clear(Table t, hipStream_t s) {
@@ -557,34 +619,47 @@ hipError_t insert_staged(Table t, Req q, Rows r, Staged st, uint32_t *ctr, hipSt
 }
 hipError_t release(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_claim<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, CancelCols{}, ctr, q, r, RejectCols{});
     hipLaunchKernelGGL(k_rel_last_all<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, CancelCols{}, ctr);
-    hipLaunchKernelGGL(k_rel_apply<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, CancelCols{}, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_RELEASE>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, CancelCols{}, ctr, RejectCols{});
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
 hipError_t cancel(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_claim<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr, q, r, RejectCols{});
     hipLaunchKernelGGL(k_rel_last_all<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
-    hipLaunchKernelGGL(k_rel_apply<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_CANCEL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr, RejectCols{});
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
 hipError_t finish(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_claim<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr, q, r, RejectCols{});
     hipLaunchKernelGGL(k_rel_last_all<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
-    hipLaunchKernelGGL(k_rel_apply<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_FINISH>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr, RejectCols{});
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
     return hipGetLastError();
 }
 hipError_t fail(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, uint32_t *ctr, hipStream_t s) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_rel_claim<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr);
+    hipLaunchKernelGGL(k_rel_claim<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr, q, r, RejectCols{});
     hipLaunchKernelGGL(k_rel_last_all<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
-    hipLaunchKernelGGL(k_rel_apply<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_FAIL>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr, RejectCols{});
     if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
+    return hipGetLastError();
+}
+hipError_t reject(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *id, uint32_t *pos, uint32_t *last_all, uint64_t *delta, CancelCols cc, RejectCols rj, uint32_t *ctr,
+                  hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_rel_claim<M_REJECT>, dim3(nblk(n)), dim3(TPB), 0, s, t, n, id, pos, cc, ctr, q, r, rj);
+    hipLaunchKernelGGL(k_rel_last_all<M_REJECT>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, pos, last_all, cc, ctr);
+    hipLaunchKernelGGL(k_rel_apply<M_REJECT>, dim3(nblk(n)), dim3(TPB), 0, s, t, q, r, n, id, pos, last_all, delta, cc, ctr, rj);
+    if (r.W && r.R) hipLaunchKernelGGL(k_rel_rows, dim3(nblk((uint64_t)r.W * r.R)), dim3(TPB), 0, s, t, r, m, last_all, delta);
+    const uint32_t n_slices = (n + 255) / 256;
+    hipLaunchKernelGGL(k_rej_count, dim3((n_slices + 3) / 4), dim3(TPB), 0, s, rj, n, n_slices);
+    if (hipError_t e = hqk::scan_waves(rj.slices, hqk::WaveGeom{256, n_slices, 4, (n_slices + 15u) & ~15u}, 1, rj.total, nullptr, nullptr, s); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rej_compact, dim3((n_slices + 3) / 4), dim3(TPB), 0, s, rj, id, n, n_slices);
     return hipGetLastError();
 }
 hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint8_t *out_run, uint32_t cap_out, uint32_t *ctr,

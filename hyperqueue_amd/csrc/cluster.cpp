@@ -223,6 +223,34 @@ int WorkerSet::set_blocked(uint32_t worker_id, uint32_t n, const uint32_t *rq, c
     blk_dirty = true;
     return 0;
 }
+int WorkerSet::block(uint32_t worker_id, uint32_t rq, uint8_t variant) {
+    if (!std::binary_search(id.begin(), id.end(), worker_id)) return 0;
+    auto &v = blocked[worker_id];
+    if (std::find(v.begin(), v.end(), std::make_pair(rq, variant)) != v.end()) return 0;
+    v.push_back({rq, variant}); blk_dirty = true;
+    return 1;
+}
+int WorkerSet::enable_request(uint32_t worker_id, uint32_t rq, uint8_t variant) {
+    if (!std::binary_search(id.begin(), id.end(), worker_id)) return fail(HQTICK_E_INVALID, "hqtick_cluster_enable_request: unknown worker id");
+    const auto it = blocked.find(worker_id);
+    if (it == blocked.end()) return 0;
+    const auto p = std::find(it->second.begin(), it->second.end(), std::make_pair(rq, variant));
+    if (p == it->second.end()) return 0;
+    it->second.erase(p);
+    if (it->second.empty()) blocked.erase(it);
+    blk_dirty = true;
+    return 1;
+}
+int WorkerSet::blocked_of(uint32_t worker_id, uint32_t *n, const uint32_t **rq, const uint8_t **variant) {
+    if (!std::binary_search(id.begin(), id.end(), worker_id)) return fail(HQTICK_E_INVALID, "hqtick_cluster_blocked: unknown worker id");
+    bo_rq.clear(); bo_variant.clear();
+    const auto it = blocked.find(worker_id);
+    if (it != blocked.end()) for (const auto &p : it->second) { bo_rq.push_back(p.first); bo_variant.push_back(p.second); }
+    if (n) *n = (uint32_t)bo_rq.size();
+    if (rq) *rq = bo_rq.data();
+    if (variant) *variant = bo_variant.data();
+    return 0;
+}
 
 int WorkerSet::set_flags(uint32_t n, const uint32_t *worker_id, const uint8_t *fl, bool sn_is_the_ledgers) {
     std::vector<uint32_t> row;
@@ -334,13 +362,17 @@ void Retracting::add(uint32_t n, const uint64_t *task_id, const uint32_t *worker
 int Retracting::response(uint32_t worker_id, uint32_t n, const uint64_t *task_id) {
     last.clear();
     int left = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        auto it = tab.find(task_id[i]);
-        if (it == tab.end() || it->second.old_id != worker_id) continue;  // "retracted task is in invalid state"  reactor.rs:476-481
-        if (it->second.has_redirect) last.push(task_id[i], it->second.target_id, it->second.variant);
-        tab.erase(it); left++;
-    }
+    for (uint32_t i = 0; i < n; i++) left += take(worker_id, task_id[i], &last) ? 1 : 0;
     return left;
+}
+
+bool Retracting::take(uint32_t worker_id, uint64_t task_id, Reassigned *out, bool *redirected) {
+    auto it = tab.find(task_id);
+    if (it == tab.end() || it->second.old_id != worker_id) return false;  // "retracted task is in invalid state"  reactor.rs:476-481
+    if (it->second.has_redirect) out->push(task_id, it->second.target_id, it->second.variant);
+    if (redirected) *redirected = it->second.has_redirect;
+    tab.erase(it);
+    return true;
 }
 
 void Retracting::sources(std::vector<uint64_t> *task_id, std::vector<uint32_t> *worker_id) const {

@@ -63,6 +63,11 @@ class WorkerSet {
     void add_rows(uint32_t n, const uint32_t *worker_id, const uint64_t *total, const uint64_t *free_rows, const int64_t *rem, const float *min_util, const uint8_t *flags, const uint32_t *group);
     void keep_rows(const std::vector<uint32_t> &src);
     int set_blocked(uint32_t worker_id, uint32_t n, const uint32_t *rq, const uint8_t *variant);
+    // one pair of one worker's blocked set (hqtick_reject_tasks, hqtick_cluster_enable_request / _blocked): block() adds it unless it is there (1: added, 0: it was
+    // there or the worker is unknown), enable_request() removes it (1 / 0; unknown worker: HQTICK_E_INVALID), blocked_of() reads the set in the order it was added
+    int block(uint32_t worker_id, uint32_t rq, uint8_t variant);
+    int enable_request(uint32_t worker_id, uint32_t rq, uint8_t variant);
+    int blocked_of(uint32_t worker_id, uint32_t *n, const uint32_t **rq, const uint8_t **variant);
     int set_flags(uint32_t n, const uint32_t *worker_id, const uint8_t *flags, bool sn_is_the_ledgers);  // the host part
     // ---- a tick
     // *full = *s; a snapshot without worker arrays gets the worker side and the blocked triples of a valid set
@@ -95,6 +100,7 @@ class WorkerSet {
     // workers' buckets as they were, so the iteration order is NOT that of the remaining ids inserted afresh); rank_[row] = position in its iteration order
     hqhb::U32Map wmap_; std::vector<uint32_t> rank_; bool rank_dirty = true;
     std::vector<uint32_t> blk_worker, blk_rq; std::vector<uint8_t> blk_variant; bool blk_dirty = true;  // the same as (worker index, rq, variant) triples
+    std::vector<uint32_t> bo_rq; std::vector<uint8_t> bo_variant;  // blocked_of's columns
 };
 
 // Tasks a tick or a lost worker made Assigned{redirect target}: the host sends their ComputeTasks messages (hqtick_retract_response, hqtick_cluster_last_reassigned)
@@ -121,6 +127,9 @@ class Retracting {
     template <class F> void for_each(F &&f) const { for (const auto &kv : tab) f(kv.first, kv.second.in_queue, kv.second.has_redirect, kv.second.target_id, kv.second.variant); }
     void add(uint32_t n, const uint64_t *task_id, const uint32_t *worker_id);  // process_retracted outside a tick: back in their queue
     int response(uint32_t worker_id, uint32_t n, const uint64_t *task_id);     // on_retract_response -> tasks that left the table
+    // what response() does for one id, also task_reject's Retracting arm (reactor.rs:412-436; hqtick_reject_tasks): the task leaves the table if it is retracting from
+    // `worker_id`; a redirect is appended to `out` (the task is Assigned on the target).  *redirected: whether it had one.  false: not in the table / another worker
+    bool take(uint32_t worker_id, uint64_t task_id, Reassigned *out, bool *redirected = nullptr);
     // on_cancel_tasks (reactor.rs:751-761): sources() lists every entry as (task, worker id it is retracting FROM), ascending task id — what hqtick_cancel_tasks hands
     // the ledger as route overrides; cancel() erases one listed task's entry, redirect included (the ledger has released the target's entry: try_remove_redirection)
     void sources(std::vector<uint64_t> *task_id, std::vector<uint32_t> *worker_id) const;

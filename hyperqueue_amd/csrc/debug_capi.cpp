@@ -12,6 +12,7 @@
 #include "fail_core.h"
 #include "finish_core.h"
 #include "start_core.h"
+#include "reject_core.h"
 #include "hb_order.h"
 #include "milp.h"
 #include "price_emul.h"
@@ -187,6 +188,22 @@ extern "C" int hqtick_debug_start_kind(uint32_t n, const uint8_t *entry_found, c
         if (entry_class[i] > hqstart::E_PF) return HQTICK_E_INVALID;
         kind[i] = (uint8_t)hqstart::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, entry_variant_match[i] != 0, entry_run[i] != 0, variant_exists[i] != 0,
                                             override_found[i] != 0, override_worker_match[i] != 0, earlier_eligible[i] != 0);
+    }
+    return (int)n;
+}
+// the rule of hqtick_reject_tasks on host arrays: reject_core.h's kind_of and blocks per position
+extern "C" int hqtick_debug_reject_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *entry_variant_match,
+                                        const uint8_t *entry_run, const uint8_t *variant_none, const uint8_t *variant_exists, const uint8_t *override_found,
+                                        const uint8_t *override_worker_match, const uint8_t *override_redirect, const uint8_t *earlier_eligible, const uint8_t *reporter_resident,
+                                        uint8_t *kind, uint8_t *blocks) {
+    if (n && (!entry_found || !entry_class || !entry_worker_match || !entry_variant_match || !entry_run || !variant_none || !variant_exists || !override_found || !override_worker_match ||
+              !override_redirect || !earlier_eligible || !reporter_resident || !kind))
+        return HQTICK_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (entry_class[i] > hqreject::E_PF) return HQTICK_E_INVALID;
+        kind[i] = (uint8_t)hqreject::kind_of(entry_found[i] != 0, entry_class[i], entry_worker_match[i] != 0, entry_variant_match[i] != 0, entry_run[i] != 0, variant_none[i] != 0,
+                                             variant_exists[i] != 0, override_found[i] != 0, override_worker_match[i] != 0, override_redirect[i] != 0, earlier_eligible[i] != 0);
+        if (blocks) blocks[i] = hqreject::blocks(kind[i], variant_none[i] != 0, variant_exists[i] != 0, reporter_resident[i] != 0) ? 1 : 0;
     }
     return (int)n;
 }

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "reject_core.h"
 #include "start_core.h"
 
 using hqbuf::PinBuf;
@@ -439,6 +440,7 @@ void hqtick_destroy(hqtick_ctx *ctx) {
     ctx->h_finish_in.release(); ctx->d_finish_in.release();
     ctx->h_fail_in.release(); ctx->d_fail_in.release();
     ctx->h_start_in.release(); ctx->d_start_in.release();
+    ctx->h_reject_in.release(); ctx->d_reject_in.release();
     for (auto &e : ctx->ev) if (e) hipEventDestroy(e);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     if (ctx->stream2) hipStreamDestroy(ctx->stream2);
@@ -1217,6 +1219,95 @@ int hqtick_cluster_last_requeued_running(const hqtick_ctx *ctx, uint32_t *n, con
     if (n) *n = (uint32_t)ctx->asg.rq_run_task.size();
     if (task_id) *task_id = ctx->asg.rq_run_task.data();
     return 0;
+}
+
+// ---- task_reject in one call: the checks and the order of the steps are here.  Ids, reporting workers, the permutation of the positions by
+// ascending (id, position), the requests (only while the Retracting table holds a task) and the variants are staged once in pinned memory and copied to the device
+// once.  1: the ledger's passes in their reject mode give every position its kind, take the _ASSIGNED and _PREFILLED entries out and leave the requeued tasks as
+// three dense ascending columns on the device (one synchronisation).  2: the Retracting table's part on the host, as hqtick_retract_response does it for one id;
+// with a redirect the kind becomes _REDIRECTED.  3: the blocks, in batch order.  4: the columns join the resident ready set (ReadySet::add_device, the graph's
+// path; its own wait).  Host waits per call: one, two when something is requeued.  Every buffer of the four steps is ensured before the first change, the merge's
+// included (ReadySet::ensure_add).  If the merge still fails (a device error), the entries have left the ledger and hqtick_ready_add of
+// hqtick_reject_last_requeued finishes the job.
+int hqtick_reject_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint8_t *variant, const uint32_t *rq) {
+    return with_audit(ctx, [&]() -> int {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_reject_tasks", n, task_id && worker_id && variant)) return rc;  // (the guard comes before any step: a refused call changes nothing)
+    if (n > 0x03FFFFFFu) return fail(ctx, HQTICK_E_CAPACITY, "more than 2^26 rejected tasks in one batch");
+    const bool with_rq = ctx->retr.count() != 0;
+    if (n && with_rq && !rq) return fail(ctx, HQTICK_E_INVALID, "hqtick_reject_tasks: rq is needed while the Retracting table holds a task");
+    hqasg::Ledger &asg = ctx->asg;
+    asg.reject_out = hqasg::Ledger::RejectOut{}; asg.last_unknown = 0; ctx->reject_reassigned.clear();
+    if (n == 0) return 0;
+    const size_t o_wid = (size_t)n * 8, o_perm = (size_t)n * 12, o_rq = (size_t)n * 16, o_var = o_rq + (with_rq ? (size_t)n * 4 : 0), bytes = o_var + n;
+    if (!ctx->h_reject_in.ensure(bytes + 16) || !ctx->d_reject_in.ensure(bytes + 16)) return fail(ctx, HQTICK_E_DEVICE, "hipMalloc reject staging");
+    std::vector<uint64_t> retr_id; std::vector<uint32_t> retr_wid;
+    ctx->retr.sources(&retr_id, &retr_wid);
+    if (int rc = ledger_fail(ctx, asg.reject_ensure(ledger_env(ctx), n, (uint32_t)retr_id.size()))) return rc;
+    if (int rc = ready_fail(ctx, ctx->ready.ensure_add(std::min<uint64_t>(n, asg.n_live + asg.pf_live)))) return rc;  // (at most every single-node and prefilled entry goes back)
+    unsigned char *h = ctx->h_reject_in.as<unsigned char>(), *d = ctx->d_reject_in.as<unsigned char>();
+    memcpy(h, task_id, (size_t)n * 8); memcpy(h + o_wid, worker_id, (size_t)n * 4); memcpy(h + o_var, variant, n);
+    if (with_rq) memcpy(h + o_rq, rq, (size_t)n * 4);
+    uint32_t *perm = reinterpret_cast<uint32_t *>(h + o_perm);  // the positions by ascending (id, position): the order the requeued columns come out in
+    for (uint32_t i = 0; i < n; i++) perm[i] = i;
+    std::stable_sort(perm, perm + n, [&](uint32_t a, uint32_t b) { return task_id[a] < task_id[b]; });
+    HQ_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    // 1: the ledger
+    const uint32_t *hit = nullptr;
+    const int accepted = ledger_fail(ctx, asg.reject(ledger_env(ctx), n, reinterpret_cast<const uint64_t *>(d), reinterpret_cast<const uint32_t *>(d + o_wid), d + o_var,
+                                                     with_rq ? reinterpret_cast<const uint32_t *>(d + o_rq) : nullptr, reinterpret_cast<const uint32_t *>(d + o_perm),
+                                                     (uint32_t)retr_id.size(), retr_id.data(), retr_wid.data(), &hit));
+    if (accepted < 0) { asg.reject_out = hqasg::Ledger::RejectOut{}; return accepted; }
+    hqasg::Ledger::RejectOut &out = asg.reject_out;
+    // 2: the Retracting tasks leave the table in batch order; one with a redirect is Assigned on its target (the target's ledger entry is already there)
+    std::vector<uint32_t> hits;
+    for (size_t k = 0; hit && k < retr_id.size(); k++) if (hit[k] != hqasg::NONE && hit[k] < n) hits.push_back(hit[k]);
+    std::sort(hits.begin(), hits.end());
+    for (uint32_t i : hits) {
+        bool redirected = false;
+        if (ctx->retr.take(worker_id[i], task_id[i], &ctx->reject_reassigned, &redirected) && redirected) out.kind[i] = HQ_REJECT_REDIRECTED;
+    }
+    // 3: worker.block_request per position (reactor.rs:389-391), in batch order; a position that lost its claim blocks nothing
+    for (uint32_t i = 0; i < n; i++)
+        if (out.blk_rq[i] != hqasg::NONE && hqreject::blocks_kind(out.kind[i])) ctx->ws.block(worker_id[i], out.blk_rq[i], variant[i]);
+    // 4: add_ready_task for what left the ledger (reactor.rs:440-442), device columns into the device merge
+    if (out.n_requeued) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), out.d_id, out.d_prio, out.d_rq, out.n_requeued))) return rc; }
+    return accepted;
+}); }
+
+int hqtick_reject_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind) {
+    if (!ctx) { if (n) *n = 0; if (kind) *kind = nullptr; return HQTICK_E_INVALID; }
+    if (n) *n = ctx->asg.reject_out.n;
+    if (kind) *kind = ctx->asg.reject_out.kind;
+    return 0;
+}
+
+int hqtick_reject_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority) {
+    if (!ctx) return HQTICK_E_INVALID;
+    const hqasg::Ledger::RejectOut &o = ctx->asg.reject_out;
+    if (n) *n = o.n_requeued;
+    if (task_id) *task_id = o.rq_id;
+    if (rq) *rq = o.rq_rq;
+    if (priority) *priority = o.rq_prio;
+    return 0;
+}
+
+int hqtick_reject_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant) {
+    if (!ctx) return HQTICK_E_INVALID;
+    ctx->reject_reassigned.get(n, task_id, worker_id, variant);
+    return 0;
+}
+
+int hqtick_cluster_enable_request(hqtick_ctx *ctx, uint32_t worker_id, uint32_t rq, uint8_t variant) {
+    if (int rc = cluster_open(ctx, "hqtick_cluster_enable_request")) return rc;
+    return cluster_fail(ctx, ctx->ws.enable_request(worker_id, rq, variant));
+}
+
+int hqtick_cluster_blocked(const hqtick_ctx *cctx, uint32_t worker_id, uint32_t *n, const uint32_t **rq, const uint8_t **variant) {
+    hqtick_ctx *ctx = const_cast<hqtick_ctx *>(cctx);  // (the answer's columns are the set's scratch)
+    if (int rc = cluster_open(ctx, "hqtick_cluster_blocked")) return rc;
+    return cluster_fail(ctx, ctx->ws.blocked_of(worker_id, n, rq, variant));
 }
 
 // The audit of the resident state (audit.h): the views of what this context holds, read through const accessors, handed to hqaudit::Auditor.  Nothing here changes

@@ -8,7 +8,7 @@ namespace hqasg {
 void Ledger::release_all() {
     tab.release(); tab2.release(); for (RowPair *r : {&counts, &mn, &pf}) r->release();
     for (DevBuf &b : buf) b.release();
-    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release(); h_start.release();
+    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release(); h_start.release(); h_reject.release();
 }
 void Ledger::take_requests(const hqtick_snapshot *s) {
     const uint32_t Q = s->n_requests;
@@ -425,6 +425,66 @@ int Ledger::reported(const Env &e, bool failing, uint32_t n, const uint64_t *d_i
     n_live -= done - done_mn - done_pf; mn_live -= std::min<uint64_t>(done_mn, mn_live); n_tomb += done; last_unknown = n - accepted; dirty_ = true;
     if (c[C_BAD]) return fail(HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
     out = FinishOut{n, accepted, hk.host(o_kind), d_kind, o_kind};
+    if (retr_hit) *retr_hit = hk.host(o_hit);
+    return (int)accepted;
+}
+// task_reject on the ledger (hqtick_reject_tasks): reported()'s step in the passes' reject mode with the requeue's compaction behind it, still one
+// set of counters and one synchronisation.  The requeued columns stay in buf[B_REJECT] for the ready set's merge and are written into pinned memory by the same
+// kernel; nothing of them is read on the host before the merge.
+namespace {
+struct RejectSizes { size_t scratch, cancel, reject, pinned; };
+RejectSizes reject_sizes(uint32_t n, uint32_t n_retr, size_t WR) {
+    const size_t nr = n_retr, slices = (((size_t)n + 255) / 256 + 15) & ~(size_t)15;
+    return RejectSizes{(size_t)n * 4 + WR * 12 + 16, nr * 16 + (size_t)n + 64, (size_t)n * 37 + slices * 4 + 128, nr * 16 + (size_t)n * 25 + 128};
+}
+}  // namespace
+int Ledger::reject_ensure(const Env &e, uint32_t n, uint32_t n_retr) {
+    const RejectSizes z = reject_sizes(n, n_retr, (size_t)e.W * e.R);
+    if (!buf[B_SCRATCH].ensure(z.scratch) || !buf[B_CANCEL].ensure(z.cancel) || !buf[B_REJECT].ensure(z.reject)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    if (!h_reject.ensure(z.pinned) || !h_ctr.ensure(64) || !buf[B_CTR].ensure(64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc reject lists");
+    return 0;
+}
+int Ledger::reject(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, const uint8_t *d_variant, const uint32_t *d_rq, const uint32_t *d_perm, uint32_t n_retr,
+                   const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit) {
+    last_unknown = 0; reject_out = RejectOut{}; if (retr_hit) *retr_hit = nullptr;
+    if (!n) return 0;
+    if (int rc = reject_ensure(e, n, n_retr)) return rc;
+    if (int rc = sync_req(e)) return rc;
+    const size_t WR = (size_t)e.W * e.R, nr = n_retr, slices = (((size_t)n + 255) / 256 + 15) & ~(size_t)15;
+    Pack pk{nullptr, buf[B_SCRATCH].as<unsigned char>()};  // [delta W*R u64][pos n u32][last_all W*R u32]
+    uint64_t *d_delta = pk.put<uint64_t>(nullptr, WR); uint32_t *d_pos = pk.put<uint32_t>(nullptr, n), *d_la = pk.put<uint32_t>(nullptr, WR);
+    Pack dk{nullptr, buf[B_CANCEL].as<unsigned char>()};   // [override ids u64][override workers u32] (one copy) [hit u32][kind n u8]
+    uint64_t *d_rid = dk.put<uint64_t>(nullptr, nr); uint32_t *d_rwid = dk.put<uint32_t>(nullptr, nr), *d_hit = dk.put<uint32_t>(nullptr, nr); uint8_t *d_kind = dk.put<uint8_t>(nullptr, n);
+    Pack rk{nullptr, buf[B_REJECT].as<unsigned char>()};   // [record priority n u64][out id n u64][out priority n u64][blocks n u32][record rq n u32][out rq n u32][slices u32][flag n u8]
+    uint64_t *d_rprio = rk.put<uint64_t>(nullptr, n, 8), *d_oid = rk.put<uint64_t>(nullptr, n), *d_oprio = rk.put<uint64_t>(nullptr, n);
+    uint32_t *d_blk = rk.put<uint32_t>(nullptr, n), *d_rrq = rk.put<uint32_t>(nullptr, n), *d_orq = rk.put<uint32_t>(nullptr, n), *d_slices = rk.put<uint32_t>(nullptr, slices, 16);  // (the scan reads the table in 16-byte groups)
+    uint8_t *d_flag = rk.put<uint8_t>(nullptr, n);
+    Pack hk{h_reject.as<unsigned char>(), h_reject.dev<unsigned char>()};  // in: the overrides; out: [requeued id n u64][priority n u64][rq n u32][blocks n u32][hit u32][total u32][kind n u8]
+    const uint64_t *h_rid = hk.put(retr_id, nr); hk.put(retr_wid, nr);
+    uint64_t *o_id = hk.put<uint64_t>(nullptr, n, 8), *o_prio = hk.put<uint64_t>(nullptr, n);
+    uint32_t *o_rq = hk.put<uint32_t>(nullptr, n), *o_blk = hk.put<uint32_t>(nullptr, n), *o_hit = hk.put<uint32_t>(nullptr, nr), *o_total = hk.put<uint32_t>(nullptr, 1);
+    uint8_t *o_kind = hk.put<uint8_t>(nullptr, n);
+    *hk.host(o_total) = 0;
+    HQ_HIP(hipMemsetAsync(d_delta, 0, WR * 8, e.stream));
+    HQ_HIP(hipMemsetAsync(d_la, 0, WR * 4, e.stream));
+    if (nr) {
+        HQ_HIP(hipMemsetAsync(d_hit, 0xFF, nr * 4, e.stream));
+        HQ_HIP(hipMemcpyAsync(d_rid, hk.host(h_rid), nr * 12, hipMemcpyHostToDevice, e.stream));
+    }
+    const CancelCols cc{nullptr, d_kind, d_rid, d_rwid, d_hit, n_retr, d_reporter};
+    const RejectCols rj{d_variant, d_rq, d_perm, d_blk, d_flag, d_rprio, d_rrq, d_slices, o_total, d_oid, d_oprio, d_orq, o_id, o_prio, o_rq};
+    if (int rc = counted(e.stream, "hqasg::reject", [&](uint32_t *ctr) {
+            hipError_t r = hqasg::reject(table(), req(), rows(e), mn_rows(mn.cur, e.W, mn_live), n, d_id, d_pos, d_la, d_delta, cc, rj, ctr, e.stream);
+            if (r == hipSuccess) r = hipMemcpyAsync(hk.host(o_kind), d_kind, n, hipMemcpyDeviceToHost, e.stream);
+            if (r == hipSuccess) r = hipMemcpyAsync(hk.host(o_blk), d_blk, (size_t)n * 4, hipMemcpyDeviceToHost, e.stream);
+            if (r == hipSuccess && nr) r = hipMemcpyAsync(hk.host(o_hit), d_hit, nr * 4, hipMemcpyDeviceToHost, e.stream);
+            return r; })) return rc;
+    const uint32_t done = c[C_DONE], accepted = std::min(c[C_OUT], n), done_pf = (uint32_t)std::min<uint64_t>(std::min(c[C_PF], done), pf_live);
+    if (done_pf) { pf_live -= done_pf; pf_dirty = true; }
+    n_live -= done - done_pf; n_tomb += done; last_unknown = n - accepted; dirty_ = true;
+    if (c[C_BAD]) return fail(HQTICK_E_DEVICE, "assignment ledger: an entry names a worker that is not in the resident set");
+    if (*hk.host(o_total) != done) return fail(HQTICK_E_DEVICE, "assignment ledger: the requeued columns are out of sync with the entries that left");
+    reject_out = RejectOut{n, accepted, done, hk.host(o_kind), hk.host(o_blk), hk.host(o_id), hk.host(o_prio), hk.host(o_rq), d_oid, d_oprio, d_orq};
     if (retr_hit) *retr_hit = hk.host(o_hit);
     return (int)accepted;
 }

@@ -53,6 +53,12 @@ class Ledger {
     // hqtick_start_last_routes: the kinds of the last start (pinned, n positions); `accepted` counts the device's accepted positions, the caller adds its own
     struct StartOut { uint32_t n = 0, accepted = 0; uint8_t *kind = nullptr; };
     StartOut start_out;
+    // hqtick_reject_last_routes / _last_requeued: the kinds of the last reject (pinned, n positions; the caller settles _REDIRECTED in them), per position the request
+    // whose pair it blocks (NONE: none), and what went back into the ready set: n_requeued ids ascending with request and priority, pinned for the host and in
+    // device memory (d_*) for the merge
+    struct RejectOut { uint32_t n = 0, accepted = 0, n_requeued = 0; uint8_t *kind = nullptr; const uint32_t *blk_rq = nullptr; const uint64_t *rq_id = nullptr, *rq_prio = nullptr;
+                       const uint32_t *rq_rq = nullptr; const uint64_t *d_id = nullptr, *d_prio = nullptr; const uint32_t *d_rq = nullptr; };
+    RejectOut reject_out;
 
     // ---- the C ABI's operations (arguments validated by the caller)
     int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
@@ -78,6 +84,13 @@ class Ledger {
     int start_begin(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, const uint8_t *d_variant, const uint8_t *mask, uint32_t n_host);
     int start_segment(const Env &e, uint32_t lo, uint32_t hi, bool last);
     void start_abort(const Env &e, uint32_t lo);  // a start that ends early: the claims of the positions [lo, n) are given back
+    // hqtick_reject_tasks' ledger step: the release's passes in their reject mode and the requeue's compaction behind one set of counters and ONE
+    // synchronisation.  d_id / d_reporter / d_variant / d_perm [n] are DEVICE memory (the call's one copy; d_perm: the positions by ascending (id, position)),
+    // d_rq [n] too, or nullptr with n_retr == 0.  The tables end as after release(_ASSIGNED ids, batch order) + unprefill(_PREFILLED ids); reject_out holds the
+    // kinds as the ledger sees them, the blocks and the requeued columns.  reject_ensure makes every buffer first, so that a failed allocation changes nothing.
+    int reject_ensure(const Env &e, uint32_t n, uint32_t n_retr);
+    int reject(const Env &e, uint32_t n, const uint64_t *d_id, const uint32_t *d_reporter, const uint8_t *d_variant, const uint32_t *d_rq, const uint32_t *d_perm, uint32_t n_retr,
+               const uint64_t *retr_id, const uint32_t *retr_wid, const uint32_t **retr_hit);
     bool variant_exists(uint32_t rq, uint32_t v) const { return (size_t)rq + 1 < rq_off.size() && v < rq_off[rq + 1] - rq_off[rq] && v < PF_VARIANT; }
     int running(const Env &e, uint32_t n, const uint64_t *id, uint8_t *run);  // hqtick_assigned_running
     int add_mn(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *rq, const uint64_t *prio, const uint32_t *off, const uint32_t *wid);
@@ -175,9 +188,11 @@ class Ledger {
     RowPair counts, mn, pf;   // counts u32 [W x stride]; [mn task u64 W][mn root u8 W][flags u8 W]; pf u32 [W x pf_stride]
     // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation,
     // a cancel's routes, overrides and sort scratch, a start's positions, kinds and mask (the host steps between its segments use B_SCRATCH)
-    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_START, B_N }; DevBuf buf[B_N];
+    // a reject's blocks, records, slice table and requeued columns
+    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_START, B_REJECT, B_N }; DevBuf buf[B_N];
     StartCols start_c{}; uint32_t start_n = 0, start_acc[C_N] = {};  // a start between start_begin and its last segment: its columns, the counters summed over the segments
     hqbuf::PinBuf h_start;  // a start's mask in, its kinds out
+    hqbuf::PinBuf h_reject;  // a reject's overrides in; its hits, kinds, blocks, requeued count and columns out
     hqbuf::PinBuf h_ctr, h_in, h_cancel, h_finish, h_fail;  // (h_cancel: a cancel's overrides in, its lists and routes out; h_finish / h_fail: a finish's / fail's overrides in, its kinds out)
     const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
     uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones

@@ -114,6 +114,14 @@ int ReadySet::add_columns(const Env &e, const uint64_t *id, const uint64_t *prio
 }
 
 // Drops the tombstones and merges `n_add` new tasks (device arrays, ids ascending; none: a compaction) into the alternate columns; swaps them in.
+int ReadySet::ensure_add(uint64_t n_add) {  // (rebuild's own sizes, for the largest batch the caller may bring)
+    const uint64_t N = n_, new_n = live_ + n_add, room = new_n + std::max<uint64_t>(new_n, 4096);
+    if (!d_id2.ensure(room * 8 + 8) || !d_prio2.ensure(room * 8 + 8) || !d_rq2.ensure(room * 4 + 8) || !h_flag.ensure(64)) return fail(HQTICK_E_DEVICE, "hipMalloc ready set (rebuild)");
+    const uint32_t n_slices = (uint32_t)((N + 255) / 256), stride = (n_slices + 15u) & ~15u;
+    if (N && (!d_slice.ensure((size_t)stride * 4 + 64) || !d_pre8.ensure(N + 16))) return fail(HQTICK_E_DEVICE, "hipMalloc slice table");
+    return 0;
+}
+
 int ReadySet::rebuild(const Env &e, const uint64_t *aid, const uint64_t *aprio, const uint32_t *arq, uint32_t n_add) {
     const uint64_t N = n_, new_n = live_ + n_add;
     // (a rebuild leaves room behind the columns: the next fresh batches are appended)

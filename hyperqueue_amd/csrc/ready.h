@@ -36,6 +36,7 @@ class ReadySet {
     int add_packed(const Env &e, uint64_t n, uint32_t n_id_runs, const uint64_t *id_run_start, const uint32_t *id_run_len, const uint32_t *id_off, uint32_t n_prio_runs,
                    const uint64_t *prio_run_value, const uint32_t *prio_run_len, const uint16_t *task_rq);  // (the run tables validated by the caller)
     int add_device(const Env &e, const uint64_t *id, const uint64_t *prio, const uint32_t *rq, uint32_t n) { return rebuild(e, id, prio, rq, n); }  // the graph's releases: no id range on the host, always merged
+    int ensure_add(uint64_t n_add);  // every buffer a later add_device of up to n_add tasks needs, so that a caller can rule its allocation failure out before it changes anything else
     int remove(const Env &e, uint64_t n, const uint64_t *host_ids);  // >= 0: how many were in the set
     int remove_device(const Env &e, const uint64_t *dev_ids, uint32_t n);
     bool compact_due() const { return n_ > 4096 && live_ * 2 < n_; }  // more tombstones than tasks, and enough rows to be worth a pass

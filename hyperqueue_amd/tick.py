@@ -579,6 +579,56 @@ class Tick:
         self._chk(f(self._ctx, C.byref(n), C.byref(pt)))
         return abi._np(pt, n.value, np.uint64).tolist() if n.value else []
 
+    # -- task_reject / request_enabled in one call (include/hqtick.h) ------------------------------------------
+    def reject_tasks(self, task_id, worker_id, variant, rq=None) -> dict:
+        """hqtick_reject_tasks for the (id, reporting worker, rejected variant) triples, in this order; a variant of None or 0xFF names none; rq: the tasks' own
+        requests (None: NULL, allowed while the Retracting table is empty) -> {"accepted": positions accepted, "kind": per batch position the HQ_REJECT_* kind,
+        "requeued": [(task, rq, priority)] that went back into the ready set, ids ascending, "reassigned": [(task, redirect target, variant)]}"""
+        t = np.ascontiguousarray(task_id, np.uint64); w = np.ascontiguousarray(worker_id, np.uint32)
+        v = np.ascontiguousarray([abi.HQ_VARIANT_NONE if x is None else x for x in variant], np.uint8)
+        assert len(t) == len(w) == len(v)
+        q = None if rq is None else np.ascontiguousarray(rq, np.uint32)
+        assert q is None or len(q) == len(t)
+        f = self._lib.hqtick_reject_tasks
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u64p, abi.u32p, abi.u8p, abi.u32p]
+        accepted = self._chk(f(self._ctx, len(t), t.ctypes.data_as(abi.u64p), w.ctypes.data_as(abi.u32p), v.ctypes.data_as(abi.u8p), None if q is None else q.ctypes.data_as(abi.u32p)))
+        return dict(accepted=int(accepted), **self.reject_last())
+
+    def reject_last(self) -> dict:
+        """hqtick_reject_last_routes / _last_requeued / _last_reassigned as copies (also after a call that returned an error)"""
+        n = C.c_uint32(); pk = abi.u8p()
+        g = self._lib.hqtick_reject_last_routes
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pk)))
+        kind = abi._np(pk, n.value, np.uint8).copy() if n.value else np.zeros(0, np.uint8)
+        pt, pq, pp = abi.u64p(), abi.u32p(), abi.u64p()
+        g = self._lib.hqtick_reject_last_requeued
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u64p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pt), C.byref(pq), C.byref(pp)))
+        k = n.value
+        requeued = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pq, k, np.uint32).tolist(), abi._np(pp, k, np.uint64).tolist())) if k else []
+        pw, pv = abi.u32p(), abi.u8p()
+        g = self._lib.hqtick_reject_last_reassigned
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pt), C.byref(pw), C.byref(pv)))
+        k = n.value
+        reassigned = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pw, k, np.uint32).tolist(), abi._np(pv, k, np.uint8).tolist())) if k else []
+        return dict(kind=kind, requeued=requeued, reassigned=reassigned)
+
+    def cluster_enable_request(self, worker_id: int, rq: int, variant: int) -> int:
+        """hqtick_cluster_enable_request (request_enabled): the pair leaves the worker's blocked set -> 1 if it was there, else 0"""
+        f = self._lib.hqtick_cluster_enable_request
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8]
+        return self._chk(f(self._ctx, int(worker_id), int(rq), int(variant)))
+
+    def cluster_blocked(self, worker_id: int) -> list:
+        """hqtick_cluster_blocked: [(rq, variant)] of one worker's blocked set, in the order the pairs were added"""
+        n = C.c_uint32(); pq, pv = abi.u32p(), abi.u8p()
+        f = self._lib.hqtick_cluster_blocked
+        f.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(abi.u32p), C.POINTER(abi.u8p)]
+        self._chk(f(self._ctx, int(worker_id), C.byref(n), C.byref(pq), C.byref(pv)))
+        return list(zip(abi._np(pq, n.value, np.uint32).tolist(), abi._np(pv, n.value, np.uint8).tolist())) if n.value else []
+
     # -- device-resident dependency graph (include/hqtick.h, SURVEY §8 f1) --------------------------------------------------
     def _graph_last_ids(self) -> np.ndarray:
         n = C.c_uint64()

@@ -787,6 +787,69 @@ int hqtick_assigned_running(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id
 int hqtick_cluster_last_requeued_running(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id);
 
 /*
+ * Rejecting tasks on the resident state in one call (functions added under ABI 12): task_reject and request_enabled (server/reactor.rs:365-460) for a
+ * batch of WorkerTaskUpdate::RejectRequest, in the order the reactor saw them.  Ids, reporting workers, rejected variants and the order of the positions by
+ * ascending (id, position) are staged once (17 B per position, 21 B while the Retracting table holds a task).
+ *   hqtick_reject_tasks   worker_id[i] rejected task_id[i] with variant[i] (0xFF: None, as in the records); a batch may mix workers and arms.  rq[i] is the task's
+ *       own request, read only for the positions the Retracting table decides (the table holds no request, and a Retracting task without a redirect has no ledger
+ *       entry); it may be NULL while that table is empty.  No priority is passed: a requeued task's request and priority are its ledger entry's own.  It needs a
+ *       resident ready set and an enabled ledger.  Every position gets an HQ_REJECT_* kind from the state BEFORE the batch:
+ *         id in the Retracting table   reported by the worker it is retracting FROM: _REDIRECTED if the table holds a redirect (accepted: the task is Assigned on the
+ *                                      target, reactor.rs:420-431; it leaves the table, the target's ledger entry stays, and the triple is in
+ *                                      hqtick_reject_last_reassigned for the ComputeTasks message), else _RETRACTING (accepted: it leaves the table; the task is
+ *                                      already a member of the ready set and is not added again); _BAD_VARIANT if a variant is named that rq[i] does not have;
+ *                                      reported by anyone else: _WRONG_WORKER
+ *         no entry                     _NONE (the task is unknown, Waiting or Ready)
+ *         multi-node entry             _MN (refused: unreachable! in the reference)
+ *         entry of another worker      _WRONG_WORKER
+ *         a variant is named that the entry's request does not have   _BAD_VARIANT
+ *         prefilled entry              its worker, any variant, None included: _PREFILLED (accepted)
+ *         single-node entry            _RUNNING if it already runs (refused: unreachable! in the reference); None or a variant that is not the entry's:
+ *                                      _WRONG_VARIANT (resource_rq_variant != Some(*rv_id)); its worker and variant: _ASSIGNED (accepted)
+ *       Only the four accepted kinds claim their id: the lowest such position wins, the others become _REPEAT.  The state afterwards is that of the handler applied
+ *       to the accepted positions in batch order:
+ *         _ASSIGNED    the entry leaves as by hqtick_assigned_release (count, free row and the last-ALL arithmetic in batch order)
+ *         _PREFILLED   the entry leaves as by hqtick_assigned_unprefill
+ *         both         go back into the resident ready set with the entry's request and priority (add_ready_task, :440-442), merged on the device; the last tick's
+ *                      selection is abandoned, as by any delta.  The graph is not touched: the task is still in the task map.
+ *       Blocks (worker.block_request, :389-391, runs before the state is looked at): the pair (request of the task, variant[i]) joins worker_id[i]'s blocked set for
+ *       every position of kind _ASSIGNED, _PREFILLED, _RETRACTING, _REDIRECTED, _WRONG_WORKER or _WRONG_VARIANT whose variant is not None, whose request has that
+ *       variant and whose reporter is a resident worker; a pair already blocked is not added twice.  _NONE, _REPEAT, _MN, _RUNNING and _BAD_VARIANT change nothing.
+ *       Two deliberate deviations: an Assigned or Prefilled task reported by the wrong worker is refused after its block (the reference requeues it without
+ *       releasing it, a state its own sanity_check rejects); a reporter that is not a resident worker is _WRONG_WORKER and blocks nothing.
+ *     Returns the number of accepted positions; hqtick_assigned_last_unknown is the number of refused ones.  The handler asks for scheduling (task_reject returns
+ *     true) iff some kind is _ASSIGNED, _PREFILLED or _RETRACTING.  HQTICK_E_INVALID without a resident ready set, with the ledger off, with a two-call tick's
+ *     placement pending, with a NULL id / worker / variant array, or with rq NULL while the Retracting table holds a task (nothing changes then);
+ *     HQTICK_E_CAPACITY for n > 2^26; n = 0 returns 0 and leaves an empty kind list.  Every buffer is ensured before the first change.
+ *     A WorkerTaskUpdate batch that interleaves EnableRequest with rejects is cut by the host at each EnableRequest.
+ *   hqtick_reject_last_routes      per batch position its HQ_REJECT_* kind: pinned memory owned by the context, valid until the next hqtick_reject_tasks.
+ *   hqtick_reject_last_requeued    what went back into the ready set: ids ascending with request and priority, pinned memory, valid until the next
+ *       hqtick_reject_tasks.  The host needs it for check_dispose_prefill / process_retracted of its queue-side prefill sets and for its Task objects.
+ *   hqtick_reject_last_reassigned  the _REDIRECTED tasks as (task, redirect target, variant) in batch order: the ComputeTasks messages the host sends.
+ *   hqtick_cluster_enable_request  request_enabled (:447-460): the pair leaves the worker's blocked set.  Returns 1 if it was there, 0 if not (nothing changes);
+ *       HQTICK_E_INVALID for an unknown worker.  Works without the ledger.
+ *   hqtick_cluster_blocked         one worker's blocked pairs in the order they were added (valid until the next change of that worker's set); without the ledger too.
+ *       hqtick_cluster_set_blocked keeps its meaning: it replaces the worker's whole set.
+ */
+#define HQ_REJECT_NONE          0   /* refused: no entry, not in the table */
+#define HQ_REJECT_ASSIGNED      1   /* accepted: single-node entry, its worker and variant, not running: released and requeued */
+#define HQ_REJECT_PREFILLED     2   /* accepted: prefilled entry reported by its worker: unprefilled and requeued */
+#define HQ_REJECT_RETRACTING    3   /* accepted: in the Retracting table without a redirect, reporter is the worker it retracts FROM */
+#define HQ_REJECT_REDIRECTED    4   /* accepted: in the Retracting table with a redirect: Assigned on the target */
+#define HQ_REJECT_REPEAT        5   /* refused: an earlier accepted position claimed this id */
+#define HQ_REJECT_WRONG_WORKER  6   /* refused after its block: the entry / the table names another worker, or the reporter is not resident */
+#define HQ_REJECT_WRONG_VARIANT 7   /* refused after its block: None, or not the variant the single-node entry was assigned with */
+#define HQ_REJECT_RUNNING       8   /* refused: the single-node entry already runs (unreachable! in the reference) */
+#define HQ_REJECT_BAD_VARIANT   9   /* refused: the task's request has no such variant */
+#define HQ_REJECT_MN           10   /* refused: multi-node entry (unreachable! in the reference) */
+int hqtick_reject_tasks(hqtick_ctx *ctx, uint32_t n, const uint64_t *task_id, const uint32_t *worker_id, const uint8_t *variant, const uint32_t *rq);
+int hqtick_reject_last_routes(const hqtick_ctx *ctx, uint32_t *n, const uint8_t **kind);
+int hqtick_reject_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority);
+int hqtick_reject_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant);
+int hqtick_cluster_enable_request(hqtick_ctx *ctx, uint32_t worker_id, uint32_t rq, uint8_t variant);
+int hqtick_cluster_blocked(const hqtick_ctx *ctx, uint32_t worker_id, uint32_t *n, const uint32_t **rq, const uint8_t **variant);
+
+/*
  * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
  * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
  * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.

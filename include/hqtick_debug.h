@@ -279,6 +279,18 @@ int hqtick_debug_fail_kind(uint32_t n, const uint8_t *entry_found, const uint8_t
 int hqtick_debug_start_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *entry_variant_match,
                             const uint8_t *entry_run, const uint8_t *variant_exists, const uint8_t *override_found, const uint8_t *override_worker_match,
                             const uint8_t *earlier_eligible, uint8_t *kind);
+
+/* The decision rule of hqtick_reject_tasks (csrc/reject_core.h, the function the claim pass of the ledger's reject calls per position and the host settles the
+ * Retracting table's positions with) on HOST arrays, one entry per evaluated position: entry_found, entry_class (0 single-node, 1 multi-node, 2 prefilled),
+ * entry_worker_match (the reporter is the entry's worker), entry_variant_match (the rejected variant is the entry's), entry_run (the entry's running byte),
+ * variant_none (the position names no variant), variant_exists (the request of the entry, or of a Retracting task, has the named variant), override_found (the id is
+ * in the Retracting table), override_worker_match (the reporter is the worker it is retracting from), override_redirect (the table holds a redirect),
+ * earlier_eligible (an earlier accepted position of the batch claimed the id), reporter_resident.  kind [n]: the HQ_REJECT_* kinds; blocks [n] (may be NULL): 1 if
+ * the position adds its pair to the reporter's blocked set.  Returns n, HQTICK_E_INVALID for a NULL array or a class above 2.  Not a product path. */
+int hqtick_debug_reject_kind(uint32_t n, const uint8_t *entry_found, const uint8_t *entry_class, const uint8_t *entry_worker_match, const uint8_t *entry_variant_match,
+                             const uint8_t *entry_run, const uint8_t *variant_none, const uint8_t *variant_exists, const uint8_t *override_found,
+                             const uint8_t *override_worker_match, const uint8_t *override_redirect, const uint8_t *earlier_eligible, const uint8_t *reporter_resident,
+                             uint8_t *kind, uint8_t *blocks);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
