@@ -49,6 +49,7 @@ def make_config(reserve: int = 16, fill_max: int = 40, time_limit_s: float = 60.
 
 
 class SnapshotC(C.Structure):
+    # (Snapshot.to_c also sets `_arrays` on the instance, a plain Python attribute outside _fields_: the numpy arrays the pointers below point into, kept alive with the struct)
     _fields_ = [
         ("n_resources", C.c_uint32),
         ("n_workers", C.c_uint32),
@@ -121,6 +122,9 @@ HQ_REJECT_ACCEPTED = (HQ_REJECT_ASSIGNED, HQ_REJECT_PREFILLED, HQ_REJECT_RETRACT
 HQ_REJECT_ELIGIBLE = HQ_REJECT_ACCEPTED  # every accepted kind changes its task and claims its id
 HQ_REJECT_BLOCKS = HQ_REJECT_ACCEPTED + (HQ_REJECT_WRONG_WORKER, HQ_REJECT_WRONG_VARIANT)  # the kinds whose position ran block_request (if it names a variant the request has)
 HQ_REJECT_SCHEDULES = (HQ_REJECT_ASSIGNED, HQ_REJECT_PREFILLED, HQ_REJECT_RETRACTING)  # task_reject returns true: the handler asks for scheduling
+# hqtick_lose_last_tasks (include/hqtick.h): what a lost worker's ledger entry was
+(HQ_LOSE_ASSIGNED, HQ_LOSE_RUNNING, HQ_LOSE_PREFILLED, HQ_LOSE_MN_ROOT, HQ_LOSE_REDIRECT) = range(5)
+HQ_LOSE_RUNNING_TASKS = (HQ_LOSE_RUNNING, HQ_LOSE_MN_ROOT)  # on_remove_worker's running_tasks: what client.on_worker_lost is told and what gets a crash counter
 HQ_VARIANT_NONE = 0xFF  # the variant byte of a RejectRequest that names none
 
 # hqtick_resident_check (include/hqtick.h): the parts, the invariants in the order of the report's arrays, the report
@@ -273,11 +277,15 @@ class Snapshot:
         """resident_workers: leave the worker side out (worker_id == NULL, n_workers = 0, no blocked triples) — the library completes it from the
         worker set it keeps itself (hqtick_cluster_upload / _add_workers / _remove_workers / _set_blocked / _update_workers, ABI 7); the per-worker
         CSRs of running and prefilled tasks still travel (they belong to the task side of the reactor's state)."""
-        keep = self._keep
-        keep.clear()
+        # the arrays the struct points to live as long as the struct does: an earlier to_c() of this snapshot stays valid when another one follows
+        # (Tick.cluster_upload(snap) calls to_c() itself); the snapshot keeps the last call's list, as before
+        keep = []
+        self._keep.clear()
+        self._keep.append(keep)
         W = len(self.worker_id)
         R = self.n_resources
         s = SnapshotC()
+        s._arrays = keep
 
         def put(name, arr, dtype, typ):
             a = _arr(arr, dtype)

@@ -22,7 +22,7 @@ TEST_LIB = os.path.join(HERE, "libhqtick_test.so")
 SOURCES = ["hqtick.cpp", "ledger.cpp", "audit.cpp", "cluster.cpp", "ready.cpp", "scan.cpp", "map.cpp", "solve.cpp", "host_model.cpp", "milp.cpp", "price.cpp", "price_flatten.cpp", "price_shard.cpp", "kernels.hip", "order.hip", "census.hip", "graph.hip", "assigned.hip", "cancel.hip", "audit.hip", "wire.hip", "wire_table.hip", "block_solve.hip", "price.hip"]
 HOOKED = ["wire.hip", "wire_table.hip"]          # sources that carry #ifdef HQTICK_TEST_HOOKS sections
 TEST_ONLY = ["debug_capi.cpp", "debug_tick.cpp", "price_emul.cpp"]  # sources of the test library only
-HEADERS = ["kernels.h", "block_core.h", "price_core.h", "price.h", "price_prob.h", "price_emul.h", "price_dev.h", "lp_tab.h", "dev_wave.h", "block_solve.h", "graph.h", "assigned.h", "cancel.h", "cancel_core.h", "finish_core.h", "fail_core.h", "start_core.h", "reject_core.h", "ledger.h", "audit.h", "audit_core.h", "cluster.h", "ready.h", "scan.h", "scan_core.h", "map.h", "map_core.h", "solve.h", "solve_core.h", "ctx.h", "tick_core.h", "devbuf.h", "host_model.h", "milp.h", "hb_order.h", "wire_core.h", "wire_table_core.h", "clock_core.h",
+HEADERS = ["kernels.h", "block_core.h", "price_core.h", "price.h", "price_prob.h", "price_emul.h", "price_dev.h", "lp_tab.h", "dev_wave.h", "block_solve.h", "graph.h", "assigned.h", "cancel.h", "cancel_core.h", "finish_core.h", "fail_core.h", "start_core.h", "reject_core.h", "lose_core.h", "ledger.h", "audit.h", "audit_core.h", "cluster.h", "ready.h", "scan.h", "scan_core.h", "map.h", "map_core.h", "solve.h", "solve_core.h", "ctx.h", "tick_core.h", "devbuf.h", "host_model.h", "milp.h", "hb_order.h", "wire_core.h", "wire_table_core.h", "clock_core.h",
            os.path.join("..", "..", "include", "hqwire.h"), os.path.join("..", "..", "include", "hqtick.h"), os.path.join("..", "..", "include", "hqtick_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall", "-Wno-unused-result", "-Wno-unused-value",
          "-msse4.1"]  # host side: floor / round / nearbyint as one instruction instead of a call into libm (every x86-64 host of an MI355X has it; no FMA, so no result changes)

@@ -389,6 +389,95 @@ class SchedEnv:
                 self.retaken_variant.pop(t.id, None)
         return sent
 
+    def lose_workers(self, wids) -> int:
+        """on_remove_worker (server/reactor.rs:64-186) for a batch of lost workers as ONE call (hqtick_lose_workers): what remove_worker does for each of them on
+        the states BEFORE the batch.  Every task a lost worker held leaves it with an abi.HQ_LOSE_* kind:
+          Assigned / Running on it                              HQ_LOSE_ASSIGNED / HQ_LOSE_RUNNING: Waiting
+          Prefilled on it                                       HQ_LOSE_PREFILLED: Waiting, out of its queue-side prefill set (move_prefilled_task_to_ready: a plain add)
+          a multi-node task whose root it is                    HQ_LOSE_MN_ROOT: Waiting, its other workers are free again
+          Retracting{old} and REDIRECTED to it                  HQ_LOSE_REDIRECT: the redirect is dropped, the task stays Retracting{old} (:90-96)
+        A lost NON-root of a multi-node task whose root stays only leaves the task's worker list (last_lose_mn_left); if the root is lost in the same batch the
+        task is HQ_LOSE_MN_ROOT of its root and nothing else.  Then every task Retracting{a lost worker}: with a redirect (to a worker that stays: one to a lost
+        worker was dropped above) it is Assigned{target} and the target gets its ComputeTasks message, without one it is Waiting.
+        The requeued tasks join their queues after the last worker, ids ascending -- add_ready_task with its prefill disposal, a plain add for the prefilled ones:
+        the batch is one call, and the process_retracted a disposal asks of the host can only follow it (reject_tasks has the same boundary).  For one worker this
+        is remove_worker exactly.
+        Returns the number of requeued tasks.  last_lose_per_worker: per lost worker, in the caller's order, [(task, rq, priority, kind)] ids ascending;
+        last_lose_requeued: [(task, rq, priority)] ids ascending; last_lose_reassigned: [(task, target worker, variant)] ids ascending; last_lose_mn_left:
+        [(task, lost worker, root worker)] by task, then in the caller's order."""
+        wids = list(wids)
+        assert len(set(wids)) == len(wids) and all(w in self.workers for w in wids), wids
+        lost = set(wids)
+        per_worker: List[List[Tuple[int, int]]] = []
+        requeued: Dict[int, bool] = {}  # task -> a plain add (it was prefilled)
+        mn_left: List[Tuple[int, int, int]] = []
+        for wid in wids:
+            w = self.workers[wid]
+            rows: List[Tuple[int, int]] = []
+            if w.sn():
+                for tid in sorted(w.assigned_tasks):
+                    t = self.tasks[tid]
+                    if t.state == RETRACTING:
+                        assert self.redirects.pop(tid, None) is not None
+                        rows.append((tid, abi.HQ_LOSE_REDIRECT))
+                    else:
+                        assert t.state in (ASSIGNED, RUNNING) and t.worker == wid
+                        rows.append((tid, abi.HQ_LOSE_RUNNING if t.state == RUNNING else abi.HQ_LOSE_ASSIGNED))
+                        t.state, t.worker, t.rv = WAITING, None, None
+                    requeued[tid] = False
+                for tid in sorted(w.prefilled_tasks):
+                    t = self.tasks[tid]
+                    assert t.state == PREFILLED and t.worker == wid
+                    t.state, t.worker = WAITING, None
+                    self.prefill[t.rq][1].remove(tid)
+                    rows.append((tid, abi.HQ_LOSE_PREFILLED))
+                    requeued[tid] = True
+            else:
+                tid, _is_root = w.mn_task
+                t = self.tasks[tid]
+                if t.state == RUNNING_MN and t.mn_workers[0] == wid:
+                    rows.append((tid, abi.HQ_LOSE_MN_ROOT))
+                    requeued[tid] = False
+                elif t.state == RUNNING_MN and t.mn_workers[0] not in lost:
+                    mn_left.append((tid, wid, t.mn_workers[0]))
+            per_worker.append(sorted(rows))
+        for rows in per_worker:
+            for tid, kind in rows:
+                if kind == abi.HQ_LOSE_MN_ROOT:
+                    t = self.tasks[tid]
+                    for other in t.mn_workers[1:]:
+                        if other in self.workers:
+                            self.workers[other].mn_task = None
+                    t.state, t.mn_workers = WAITING, None
+        for tid, wid, _root in mn_left:
+            t = self.tasks[tid]
+            t.mn_workers = [x for x in t.mn_workers if x != wid]
+        for wid in wids:
+            self.workers.pop(wid)
+            self.worker_map.remove(wid)
+        sent = []
+        for t in sorted(self.tasks.values(), key=lambda t: t.id):
+            if t.state == RETRACTING and t.worker in lost:
+                if t.id in self.redirects:
+                    target, v = self.redirects.pop(t.id)
+                    t.state, t.worker, t.rv = ASSIGNED, target, v
+                    sent.append((t.id, target, v))
+                else:
+                    t.state, t.worker = WAITING, None
+                self.retaken_variant.pop(t.id, None)
+        for tid in sorted(requeued):
+            t = self.tasks[tid]
+            if requeued[tid]:
+                self.ready[t.rq].add(tid)
+            else:
+                self._add_ready(t)
+        info = lambda tid: (tid, self.tasks[tid].rq, self.tasks[tid].priority)
+        self.last_lose_per_worker = [[info(tid) + (kind,) for tid, kind in rows] for rows in per_worker]
+        self.last_lose_requeued = [info(tid) for tid in sorted(requeued)]
+        self.last_lose_reassigned = sent
+        self.last_lose_mn_left = sorted(mn_left, key=lambda m: (m[0], wids.index(m[1])))
+        return len(requeued)
+
     def new_worker_cpus(self, cpus: int) -> int:
         return self.new_worker(WorkerBuilder(cpus))
 

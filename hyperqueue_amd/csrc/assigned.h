@@ -137,6 +137,28 @@ hipError_t reject(Table t, Req q, Rows r, MnRows m, uint32_t n, const uint64_t *
 // out_var [cap_out]: the entry's variant column (PF_VARIANT: it was prefilled; counted in C_PF); out_run [cap_out]: its running byte
 hipError_t evict(Table t, uint32_t n_lost, const uint32_t *lost, uint64_t *out_id, uint32_t *out_rq, uint64_t *out_prio, uint8_t *out_var, uint8_t *out_run, uint32_t cap_out, uint32_t *ctr,
                  hipStream_t s);
+// hqtick_lose_workers: the eviction with outputs whose order does not depend on the order atomics arrive in.  All pointers are device memory
+// unless said otherwise; lose_core.h has the rule and the phases.
+//   lose_evict   evict()'s pass over the table: a hit appends (id, bucket) to skey / sval [cap_out] (order undefined) and becomes a tombstone; its other columns
+//                stay where they are for the gather.  Counts as evict() (C_OUT, C_MN, C_PF).  With m.live, behind it on the stream: per lost worker i of the
+//                caller's order `call` [n_lost], mn_task[i] / mn_root[i] (pinned) = the multi-node task its row holds as a NON-root and that task's root worker id,
+//                if the task is still in the table (its root stays); HT_EMPTY otherwise.  mn_reset_rows comes after it.
+//   lose_sort    hqgraph::sort_pairs over the k pairs is the caller's (graph.h); lose_gather reads them sorted: position j takes the columns of bucket sval[j] --
+//                the three dense columns of the merge (id, prio, rq: device) and, through the same stores, the flat list (o_*: pinned), the kind by
+//                hqlose::kind_of_entry and the index of the entry's worker in the caller's list (lost [n_lost] sorted ids, lost_idx [n_lost] their indices).
+//   lose_group   hqcancel::sort_rows of the worker indices (scratch: hqcancel::scratch_of(k, n_lost).total u32), then offsets and CSR columns (pinned).
+struct LoseCols {
+    uint32_t n_lost; const uint32_t *lost, *lost_idx, *call;
+    uint64_t *skey; uint32_t *sval;
+    uint64_t *id, *prio; uint32_t *rq, *widx; uint8_t *kind;
+    uint64_t *o_id, *o_prio; uint32_t *o_rq;
+    uint32_t *scratch;
+    uint32_t *c_off; uint64_t *c_id, *c_prio; uint32_t *c_rq; uint8_t *c_kind;
+    uint64_t *mn_task; uint32_t *mn_root;
+};
+hipError_t lose_evict(Table t, Rows r, MnRows m, LoseCols lc, uint32_t cap_out, uint32_t *ctr, hipStream_t s);
+hipError_t lose_gather(Table t, LoseCols lc, uint32_t k, hipStream_t s);
+hipError_t lose_group(LoseCols lc, uint32_t k, hipStream_t s);
 // prefilled tasks (r.pf != nullptr in all four).  seed: item i (id, worker id, rq, priority) enters as a PF_VARIANT entry if the worker is resident and has its SN
 // bit, the request exists and the id is new (C_DONE entered; C_BAD / C_DUP refused).  start: the entry of id[i] takes variant[i]: pf count down, (row, slot)
 // count up, free.remove — all commuting atomics, one pass (C_DONE started; C_UNKNOWN not a prefilled entry, C_BAD no such variant).  remove: the entry leaves,

@@ -1,6 +1,8 @@
 // Kernels of the assignment ledger (assigned.h).  gfx950 only.
 #include "assigned.h"
+#include "cancel.h"
 #include "fail_core.h"
+#include "lose_core.h"
 #include "kernels.h"
 #include "finish_core.h"
 #include "reject_core.h"
@@ -601,7 +603,80 @@ __global__ void __launch_bounds__(TPB) k_rej_compact(RejectCols rj, const uint64
     }
 }
 
+// ---- hqtick_lose_workers.  The append of the eviction is the only place where the order of arrival shows; the sort by id behind it removes it,
+// and everything after the sort writes position j from the sorted arrays alone.
+// index of worker id w in the sorted list (NONE: not lost)
+__device__ __forceinline__ uint32_t lost_find(const uint32_t *lost, uint32_t n_lost, uint32_t w) {
+    uint32_t lo = 0, hi = n_lost;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (lost[mid] < w) lo = mid + 1; else hi = mid; }
+    return lo < n_lost && lost[lo] == w ? lo : NONE;
+}
+// k_evict's pass; a hit leaves (id, bucket) for the sort instead of its columns
+__global__ void __launch_bounds__(TPB) k_lose_evict(Table t, LoseCols lc, uint32_t cap_out, uint32_t *ctr) {
+    const uint32_t b = blockIdx.x * TPB + threadIdx.x;
+    const uint64_t k = b <= t.mask ? t.key[b] : HT_EMPTY;
+    const bool hit = k < HT_TOMB && lost_find(lc.lost, lc.n_lost, t.worker[b]) != NONE;
+    const uint8_t v = hit ? t.variant[b] : (uint8_t)0;
+    wave_add(&ctr[C_MN], hit && v == MN_VARIANT);
+    wave_add(&ctr[C_PF], hit && v == PF_VARIANT);
+    const uint32_t o = wave_append(&ctr[C_OUT], hit);
+    if (!hit || o >= cap_out) return;  // (sized by the host's live count: more is reported as an error and nothing is written past the end)
+    lc.skey[o] = k; lc.sval[o] = b;
+    t.key[b] = HT_TOMB;
+}
+// the lost NON-root members of multi-node tasks, one thread per lost worker of the caller's list; behind the eviction (a task whose root was lost with it is no
+// longer found) and before the rows are reset or re-packed
+__global__ void __launch_bounds__(TPB) k_lose_mn(Table t, Rows r, MnRows m, LoseCols lc) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= lc.n_lost) return;
+    uint64_t task = HT_EMPTY; uint32_t root = NONE;
+    const uint32_t row = row_of(r, lc.call[i]);
+    if (row != NONE && m.task[row] != HT_EMPTY && m.root[row] == 0) {
+        const uint32_t b = ht_find(t, m.task[row]);
+        if (b != NONE) { task = m.task[row]; root = t.worker[b]; }
+    }
+    lc.mn_task[i] = task; lc.mn_root[i] = root;
+}
+// sorted position j: the entry's columns from its bucket (the tombstone left them), the kind, the worker's index in the caller's list
+__global__ void __launch_bounds__(TPB) k_lose_gather(Table t, LoseCols lc, uint32_t k) {
+    const uint32_t j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= k) return;
+    const uint64_t id = lc.skey[j];
+    const uint32_t b = lc.sval[j] & t.mask;  // (a bucket the eviction wrote; the mask keeps every read inside the table whatever the pair holds)
+    const uint64_t pr = t.prio[b]; const uint32_t rq = t.rq[b]; const uint8_t v = t.variant[b];
+    const uint32_t at = lost_find(lc.lost, lc.n_lost, t.worker[b]);
+    lc.id[j] = id; lc.prio[j] = pr; lc.rq[j] = rq;
+    lc.o_id[j] = id; lc.o_prio[j] = pr; lc.o_rq[j] = rq;
+    lc.kind[j] = (uint8_t)hqlose::kind_of_entry(v == MN_VARIANT ? hqlose::E_MN : v == PF_VARIANT ? hqlose::E_PF : hqlose::E_SN, t.run[b] != 0);
+    lc.widx[j] = at != NONE ? lc.lost_idx[at] : 0u;  // (every evicted entry's worker is in the list; 0 keeps the key a valid index if the table were damaged)
+}
+// offsets and CSR columns from the sorted worker indices: lose_core.h's two phases, one thread per offset and per element
+__global__ void __launch_bounds__(TPB) k_lose_group(hqlose::GroupArgs a) {
+    const uint32_t g = blockIdx.x * TPB + threadIdx.x;
+    hqlose::grp_p_offset(a, g);
+    hqlose::grp_p_gather(a, g);
+}
+
 }  // namespace
+
+hipError_t lose_evict(Table t, Rows r, MnRows m, LoseCols lc, uint32_t cap_out, uint32_t *ctr, hipStream_t s) {
+    hipLaunchKernelGGL(k_lose_evict, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t, lc, cap_out, ctr);
+    if (m.live && lc.n_lost) hipLaunchKernelGGL(k_lose_mn, dim3(nblk(lc.n_lost)), dim3(TPB), 0, s, t, r, m, lc);
+    return hipGetLastError();
+}
+hipError_t lose_gather(Table t, LoseCols lc, uint32_t k, hipStream_t s) {
+    if (!k) return hipSuccess;
+    hipLaunchKernelGGL(k_lose_gather, dim3(nblk(k)), dim3(TPB), 0, s, t, lc, k);
+    return hipGetLastError();
+}
+hipError_t lose_group(LoseCols lc, uint32_t k, hipStream_t s) {
+    const uint32_t *key = nullptr, *pos = nullptr;
+    if (k) { if (hipError_t rc = hqcancel::sort_rows(k, lc.n_lost, lc.widx, lc.scratch, &key, &pos, s); rc != hipSuccess) return rc; }
+    const hqlose::GroupArgs a{k, lc.n_lost, key, pos, lc.id, lc.prio, lc.rq, lc.kind, lc.c_off, lc.c_id, lc.c_prio, lc.c_rq, lc.c_kind};
+    hipLaunchKernelGGL(k_lose_group, dim3(nblk((uint64_t)k > (uint64_t)lc.n_lost + 1 ? (uint64_t)k : (uint64_t)lc.n_lost + 1)), dim3(TPB), 0, s, a);
+    return hipGetLastError();
+}
+
 
 hipError_t clear(Table t, hipStream_t s) {
     hipLaunchKernelGGL(k_clear, dim3(nblk((uint64_t)t.mask + 1)), dim3(TPB), 0, s, t);

@@ -68,6 +68,8 @@ struct hqtick_ctx {
     hqbuf::PinBuf h_start_in; hqbuf::DevBuf d_start_in;    // hqtick_start_tasks: ids, reporting workers and variants, 13 B per position, staged once and copied to the device once
     hqbuf::PinBuf h_reject_in; hqbuf::DevBuf d_reject_in;  // hqtick_reject_tasks: ids, reporting workers, the order by (id, position), requests (only with Retracting tasks) and variants, staged once
     hqcluster::Reassigned reject_reassigned;               // hqtick_reject_last_reassigned
+    hqcluster::Reassigned lose_reassigned;                 // hqtick_lose_last_reassigned
+    std::vector<uint64_t> lose_mn_task; std::vector<uint32_t> lose_mn_lost, lose_mn_root;  // hqtick_lose_last_mn_left
     hqbuf::PinBuf h_finish_in; hqbuf::DevBuf d_finish_in;  // hqtick_finish_tasks: ids and reporting workers, 12 B per position, staged once and copied to the device once
     hqtick_ctx *qctx = nullptr;  // hqtick_query's private sub-context
     ViewHooks *view_hooks = nullptr;  // hqtick_debug_order_view's scanner and scratch (test library only), allocated on first use; nothing of it is touched on a tick's path

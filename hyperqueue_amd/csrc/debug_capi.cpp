@@ -11,6 +11,7 @@
 #include "clock_core.h"
 #include "fail_core.h"
 #include "finish_core.h"
+#include "lose_core.h"
 #include "start_core.h"
 #include "reject_core.h"
 #include "hb_order.h"
@@ -206,4 +207,23 @@ extern "C" int hqtick_debug_reject_kind(uint32_t n, const uint8_t *entry_found, 
         if (blocks) blocks[i] = hqreject::blocks(kind[i], variant_none[i] != 0, variant_exists[i] != 0, reporter_resident[i] != 0) ? 1 : 0;
     }
     return (int)n;
+}
+// the rule of hqtick_lose_workers on host arrays: lose_core.h's kind_of_entry and settle per evicted entry
+extern "C" int hqtick_debug_lose_kind(uint32_t n, const uint8_t *entry_class, const uint8_t *entry_run, const uint8_t *redirect_target, uint8_t *kind, uint8_t *running) {
+    if (n && (!entry_class || !entry_run || !redirect_target || !kind)) return HQTICK_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (entry_class[i] > hqlose::E_PF) return HQTICK_E_INVALID;
+        kind[i] = (uint8_t)hqlose::settle(hqlose::kind_of_entry(entry_class[i], entry_run[i] != 0), redirect_target[i] != 0);
+        if (running) running[i] = hqlose::is_running(kind[i]) ? 1 : 0;
+    }
+    return (int)n;
+}
+// the grouping of hqtick_lose_workers on host arrays: cancel_core.h's stable sort and lose_core.h's two phases in the given thread order
+extern "C" int hqtick_debug_lose_group(uint32_t k, uint32_t n_workers, const uint64_t *task_id, const uint64_t *priority, const uint32_t *rq, const uint8_t *kind, const uint32_t *worker_index,
+                                       int order, uint32_t *out_off, uint64_t *out_task, uint64_t *out_priority, uint32_t *out_rq, uint8_t *out_kind) {
+    if (!n_workers || !out_off || order < 0 || order > 2 || k > 0x7FFFFFFFu || (k && (!task_id || !priority || !rq || !kind || !worker_index || !out_task || !out_priority || !out_rq || !out_kind)))
+        return HQTICK_E_INVALID;
+    for (uint32_t j = 0; j < k; j++) if (worker_index[j] >= n_workers || (j && task_id[j] <= task_id[j - 1])) return HQTICK_E_INVALID;
+    if (!hqlose::group_on_host(k, n_workers, task_id, priority, rq, kind, worker_index, order, out_off, out_task, out_priority, out_rq, out_kind)) return HQTICK_E_DEVICE;
+    return (int)k;
 }

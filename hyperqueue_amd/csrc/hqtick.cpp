@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "lose_core.h"
 #include "reject_core.h"
 #include "start_core.h"
 
@@ -1308,6 +1309,96 @@ int hqtick_cluster_blocked(const hqtick_ctx *cctx, uint32_t worker_id, uint32_t 
     hqtick_ctx *ctx = const_cast<hqtick_ctx *>(cctx);  // (the answer's columns are the set's scratch)
     if (int rc = cluster_open(ctx, "hqtick_cluster_blocked")) return rc;
     return cluster_fail(ctx, ctx->ws.blocked_of(worker_id, n, rq, variant));
+}
+
+// ---- on_remove_worker in one call: hqtick_cluster_remove_workers' sequence, in the order that function documents as load-bearing, with the
+// ledger's step replaced by Ledger::lose and the merge by ReadySet::add_device.  1: the eviction (one wait, for the count); the sort by id, the gather, the grouping
+// by lost worker, the non-root members and the reset of lost roots' rows are enqueued behind it.  2: the two re-packs; the ledger's waits for everything enqueued
+// so far, so the pinned lists are final behind it.  3: the host settles _REDIRECT from the Retracting table (which stays in host memory), orders the non-root
+// members, and the table follows (Retracting::workers_removed).  4: the worker ids, then the merge of the three device columns (its own wait).  Every buffer of
+// steps 1 and 4 is ensured before the first change.
+int hqtick_lose_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id) { return with_audit(ctx, [&]() -> int {
+    if (int rc = cluster_open(ctx, "hqtick_lose_workers")) return rc;
+    if (!ctx->ready.resident()) return fail(ctx, HQTICK_E_INVALID, "no resident ready set");
+    if (int rc = ledger_open(ctx, "hqtick_lose_workers", n, worker_id != nullptr)) return rc;
+    hqasg::Ledger &asg = ctx->asg;
+    const uint32_t W = ctx->ws.W();
+    std::vector<uint32_t> src;
+    if (n) { if (int rc = cluster_fail(ctx, ctx->ws.plan_remove(n, worker_id, &src))) return rc; }  // unknown or repeated ids: refused before anything changes
+    asg.lose_out = hqasg::Ledger::LoseOut{}; ctx->lose_reassigned.clear(); ctx->lose_mn_task.clear(); ctx->lose_mn_lost.clear(); ctx->lose_mn_root.clear();
+    if (n == 0) return 0;
+    if (int rc = ledger_fail(ctx, asg.lose_ensure(ledger_env(ctx), n))) return rc;
+    if (int rc = ready_fail(ctx, ctx->ready.ensure_add(asg.lose_bound()))) return rc;
+    asg.clear_requeued();  // (the hqtick_cluster_last_requeued* lists answer for hqtick_cluster_remove_workers only: empty behind this call)
+    // 1: the lost workers' entries leave the ledger
+    const int k = ledger_fail(ctx, asg.lose(ledger_env(ctx), n, worker_id));
+    if (k < 0) return k;
+    const hqasg::Ledger::LoseOut out = asg.lose_out;
+    asg.lose_out = hqasg::Ledger::LoseOut{};  // (until the lists are final)
+    // 2: the rows leave the worker set and the ledger's row tables
+    if (int rc = cluster_fail(ctx, ctx->ws.repack(ctx->stream, src, 0, nullptr, nullptr, nullptr))) return rc;
+    if (int rc = asg.repack(ledger_env(ctx), src, W, nullptr)) return ledger_fail(ctx, rc);
+    ctx->ws.keep_rows(src);
+    // 3: the lists are final.  A single-node entry on the redirect TARGET of a Retracting task is the redirect's (reactor.rs:90-96)
+    std::vector<std::pair<uint32_t, uint32_t>> index_of(n);  // (worker id, index in the caller's list), by id
+    for (uint32_t i = 0; i < n; i++) index_of[i] = {worker_id[i], i};
+    std::sort(index_of.begin(), index_of.end());
+    if (out.off[n] != out.n) return fail(ctx, HQTICK_E_DEVICE, "assignment ledger: the lost workers' lists are out of sync with the entries that left");
+    ctx->retr.for_each([&](uint64_t task, bool, bool has_redirect, uint32_t target, uint8_t) {
+        if (!has_redirect) return;
+        const auto it = std::lower_bound(index_of.begin(), index_of.end(), std::make_pair(target, 0u));
+        if (it == index_of.end() || it->first != target) return;
+        const uint64_t *lo = out.c_id + out.off[it->second], *hi = out.c_id + out.off[it->second + 1], *at = std::lower_bound(lo, hi, task);
+        if (at != hi && *at == task) out.c_kind[at - out.c_id] = (uint8_t)hqlose::settle(out.c_kind[at - out.c_id], true);
+    });
+    std::vector<std::pair<uint64_t, uint32_t>> left;  // the non-root members: ascending task id, then the caller's order
+    for (uint32_t i = 0; i < n; i++) if (out.mn_task[i] != hqasg::HT_EMPTY) left.push_back({out.mn_task[i], i});
+    std::sort(left.begin(), left.end());
+    for (const auto &m : left) { ctx->lose_mn_task.push_back(m.first); ctx->lose_mn_lost.push_back(worker_id[m.second]); ctx->lose_mn_root.push_back(out.mn_root[m.second]); }
+    ctx->retr.workers_removed(n, worker_id);
+    ctx->lose_reassigned = ctx->retr.last;
+    asg.lose_out = out;
+    // 4: the worker ids of the new rows; add_ready_task for what left the ledger, device columns into the device merge
+    if (int rc = asg.upload_wids(ledger_env(ctx))) return ledger_fail(ctx, rc);
+    if (out.n) { if (int rc = ready_fail(ctx, ctx->ready.add_device(ready_env(ctx), out.d_id, out.d_prio, out.d_rq, out.n))) return rc; }
+    return k;
+}); }
+
+int hqtick_lose_last_tasks(const hqtick_ctx *ctx, uint32_t *n_workers, const uint32_t **task_off, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority, const uint8_t **kind) {
+    if (!ctx) return HQTICK_E_INVALID;
+    const hqasg::Ledger::LoseOut &o = ctx->asg.lose_out;
+    if (n_workers) *n_workers = o.n_workers;
+    if (task_off) *task_off = o.off;
+    if (task_id) *task_id = o.c_id;
+    if (rq) *rq = o.c_rq;
+    if (priority) *priority = o.c_prio;
+    if (kind) *kind = o.c_kind;
+    return 0;
+}
+
+int hqtick_lose_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority) {
+    if (!ctx) return HQTICK_E_INVALID;
+    const hqasg::Ledger::LoseOut &o = ctx->asg.lose_out;
+    if (n) *n = o.n;
+    if (task_id) *task_id = o.f_id;
+    if (rq) *rq = o.f_rq;
+    if (priority) *priority = o.f_prio;
+    return 0;
+}
+
+int hqtick_lose_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant) {
+    if (!ctx) return HQTICK_E_INVALID;
+    ctx->lose_reassigned.get(n, task_id, worker_id, variant);
+    return 0;
+}
+
+int hqtick_lose_last_mn_left(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **lost_worker_id, const uint32_t **root_worker_id) {
+    if (!ctx) return HQTICK_E_INVALID;
+    if (n) *n = (uint32_t)ctx->lose_mn_task.size();
+    if (task_id) *task_id = ctx->lose_mn_task.data();
+    if (lost_worker_id) *lost_worker_id = ctx->lose_mn_lost.data();
+    if (root_worker_id) *root_worker_id = ctx->lose_mn_root.data();
+    return 0;
 }
 
 // The audit of the resident state (audit.h): the views of what this context holds, read through const accessors, handed to hqaudit::Auditor.  Nothing here changes

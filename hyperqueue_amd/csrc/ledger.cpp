@@ -1,6 +1,9 @@
 // hqasg::Ledger — the host side of the assignment ledger (ledger.h; kernels: assigned.hip).
 #include "ledger.h"
 
+#include "graph.h"
+#include "lose_core.h"
+
 namespace hqasg {
 
 #define HQ_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(HQTICK_E_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
@@ -8,7 +11,7 @@ namespace hqasg {
 void Ledger::release_all() {
     tab.release(); tab2.release(); for (RowPair *r : {&counts, &mn, &pf}) r->release();
     for (DevBuf &b : buf) b.release();
-    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release(); h_start.release(); h_reject.release();
+    h_ctr.release(); h_in.release(); h_cancel.release(); h_finish.release(); h_fail.release(); h_start.release(); h_reject.release(); h_lose.release();
 }
 void Ledger::take_requests(const hqtick_snapshot *s) {
     const uint32_t Q = s->n_requests;
@@ -249,6 +252,63 @@ int Ledger::evict(const Env &e, uint32_t n, const uint32_t *worker_id) {
     n_live -= k - k_mn - k_pf; mn_live -= k_mn; n_tomb += k; dirty_ = true;
     if (k_pf) { pf_live -= k_pf; pf_dirty = true; }
     return 0;
+}
+
+// evict() for hqtick_lose_workers: the same pass over the table, but a hit leaves (id, bucket) and everything that follows the count stays on the
+// device -- hqgraph::sort_pairs by id, the gather of the buckets' columns (three dense columns for the merge, the same stores into pinned memory, kind and worker
+// index), hqcancel::sort_rows by worker index with lose_core.h's offsets and CSR columns, the non-root members of the lost rows.  Nothing of it is read here.
+int Ledger::lose_ensure(const Env &e, uint32_t n) {
+    (void)e;
+    const uint64_t cap_out = lose_bound() + 1;
+    if (cap_out > 0x7FFFFFFFull) return fail(HQTICK_E_CAPACITY, "assignment ledger: more than 2^31 - 2 entries");
+    const hqlose::DevLayout D = hqlose::dev_layout(cap_out, hqgraph::sort_capacity(cap_out), n);
+    const hqlose::PinLayout P = hqlose::pin_layout(cap_out, n);
+    if (!buf[B_LOSE].ensure(D.bytes) || !buf[B_CTR].ensure(64)) return fail(HQTICK_E_DEVICE, "hipMalloc ledger scratch");
+    if (!h_lose.ensure(P.bytes) || !h_ctr.ensure(64)) return fail(HQTICK_E_DEVICE, "hipHostMalloc lost-worker lists");
+    return 0;
+}
+int Ledger::lose(const Env &e, uint32_t n, const uint32_t *worker_id) {
+    lose_out = LoseOut{};
+    if (int rc = lose_ensure(e, n)) return rc;
+    const uint64_t pf_now = pf_on ? pf_live : 0, cap_out = lose_bound() + 1;
+    const hqlose::DevLayout D = hqlose::dev_layout(cap_out, hqgraph::sort_capacity(cap_out), n);
+    const hqlose::PinLayout P = hqlose::pin_layout(cap_out, n);
+    unsigned char *d = buf[B_LOSE].as<unsigned char>(), *h = h_lose.as<unsigned char>(), *hd = h_lose.dev<unsigned char>();
+    auto dev = [&](size_t o) { return d + o; };
+    // in: the lost ids sorted, the index of each in the caller's list, the caller's list -- one copy
+    uint32_t *in = reinterpret_cast<uint32_t *>(h + P.in);
+    std::vector<uint32_t> ord(n); for (uint32_t i = 0; i < n; i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return worker_id[x] < worker_id[y]; });
+    for (uint32_t i = 0; i < n; i++) { in[i] = worker_id[ord[i]]; in[n + i] = ord[i]; in[2 * (size_t)n + i] = worker_id[i]; }
+    uint64_t *h_mn_task = reinterpret_cast<uint64_t *>(h + P.m_task); uint32_t *h_mn_root = reinterpret_cast<uint32_t *>(h + P.m_root), *h_off = reinterpret_cast<uint32_t *>(h + P.off);
+    std::fill_n(h_mn_task, (size_t)n, HT_EMPTY); std::fill_n(h_mn_root, (size_t)n, NONE); std::fill_n(h_off, (size_t)n + 1, 0u);
+    HQ_HIP(hipMemcpyAsync(dev(D.lost), in, (size_t)n * 12, hipMemcpyHostToDevice, e.stream));
+    LoseCols lc{};
+    lc.n_lost = n; lc.lost = reinterpret_cast<uint32_t *>(dev(D.lost)); lc.lost_idx = reinterpret_cast<uint32_t *>(dev(D.lost_idx)); lc.call = reinterpret_cast<uint32_t *>(dev(D.call));
+    lc.skey = reinterpret_cast<uint64_t *>(dev(D.skey)); lc.sval = reinterpret_cast<uint32_t *>(dev(D.sval));
+    lc.id = reinterpret_cast<uint64_t *>(dev(D.id)); lc.prio = reinterpret_cast<uint64_t *>(dev(D.prio)); lc.rq = reinterpret_cast<uint32_t *>(dev(D.rq));
+    lc.widx = reinterpret_cast<uint32_t *>(dev(D.widx)); lc.kind = dev(D.kind); lc.scratch = reinterpret_cast<uint32_t *>(dev(D.scratch));
+    lc.o_id = reinterpret_cast<uint64_t *>(hd + P.f_id); lc.o_prio = reinterpret_cast<uint64_t *>(hd + P.f_prio); lc.o_rq = reinterpret_cast<uint32_t *>(hd + P.f_rq);
+    lc.c_off = reinterpret_cast<uint32_t *>(hd + P.off); lc.c_id = reinterpret_cast<uint64_t *>(hd + P.c_id); lc.c_prio = reinterpret_cast<uint64_t *>(hd + P.c_prio);
+    lc.c_rq = reinterpret_cast<uint32_t *>(hd + P.c_rq); lc.c_kind = hd + P.c_kind;
+    lc.mn_task = reinterpret_cast<uint64_t *>(hd + P.m_task); lc.mn_root = reinterpret_cast<uint32_t *>(hd + P.m_root);
+    if (int rc = counted(e.stream, "hqasg::lose_evict", [&](uint32_t *ctr) { return lose_evict(table(), rows(e), mn_rows(mn.cur, e.W, mn_live), lc, (uint32_t)cap_out, ctr, e.stream); })) return rc;
+    const uint32_t k = c[C_OUT], k_mn = c[C_MN], k_pf = c[C_PF];
+    if (k >= cap_out || (uint64_t)k_mn + k_pf > k || k_mn > mn_live || k_pf > pf_now || k - k_mn - k_pf > n_live) return fail(HQTICK_E_DEVICE, "assignment ledger: eviction count out of sync");
+    n_live -= k - k_mn - k_pf; mn_live -= k_mn; n_tomb += k; dirty_ = true;  // (the entries are gone whatever happens below)
+    if (k_pf) { pf_live -= k_pf; pf_dirty = true; }
+    if (k) {
+        HQ_HIP(hqgraph::sort_pairs(lc.skey, lc.sval, k, e.stream));
+        HQ_HIP(lose_gather(table(), lc, k, e.stream));
+    }
+    HQ_HIP(lose_group(lc, k, e.stream));
+    if (k_mn) {  // a lost ROOT (reactor.rs:107-128): the task's other rows are free single-node workers again, before the rows are re-packed
+        HQ_HIP(mn_reset_rows(table(), rows(e), mn_rows(mn.cur, e.W, mn_live + k_mn), e.stream));
+        flags_dirty = true;
+    }
+    lose_out = LoseOut{n, k, h_off, reinterpret_cast<uint64_t *>(h + P.c_id), reinterpret_cast<uint64_t *>(h + P.c_prio), reinterpret_cast<uint32_t *>(h + P.c_rq), h + P.c_kind,
+                       reinterpret_cast<uint64_t *>(h + P.f_id), reinterpret_cast<uint64_t *>(h + P.f_prio), reinterpret_cast<uint32_t *>(h + P.f_rq), h_mn_task, h_mn_root, lc.id, lc.prio, lc.rq};
+    return (int)k;
 }
 
 // the host mirror (free rows, counts) from the device tables: one synchronisation, two copies; then the assigned CSR of the host stages

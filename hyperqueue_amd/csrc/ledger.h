@@ -59,6 +59,13 @@ class Ledger {
     struct RejectOut { uint32_t n = 0, accepted = 0, n_requeued = 0; uint8_t *kind = nullptr; const uint32_t *blk_rq = nullptr; const uint64_t *rq_id = nullptr, *rq_prio = nullptr;
                        const uint32_t *rq_rq = nullptr; const uint64_t *d_id = nullptr, *d_prio = nullptr; const uint32_t *d_rq = nullptr; };
     RejectOut reject_out;
+    // hqtick_lose_last_tasks / _last_requeued / _last_mn_left: what the last lose() wrote into pinned memory -- the CSR over the n_workers lost workers in the
+    // caller's order (the caller settles _REDIRECT in c_kind), the n evicted tasks as one ascending list (f_*), per lost worker the multi-node task it left as a
+    // non-root and that task's root (HT_EMPTY: none) -- and the same three columns in device memory (d_*) for the merge
+    struct LoseOut { uint32_t n_workers = 0, n = 0; const uint32_t *off = nullptr; const uint64_t *c_id = nullptr, *c_prio = nullptr; const uint32_t *c_rq = nullptr; uint8_t *c_kind = nullptr;
+                     const uint64_t *f_id = nullptr, *f_prio = nullptr; const uint32_t *f_rq = nullptr; const uint64_t *mn_task = nullptr; const uint32_t *mn_root = nullptr;
+                     const uint64_t *d_id = nullptr, *d_prio = nullptr; const uint32_t *d_rq = nullptr; };
+    LoseOut lose_out;
 
     // ---- the C ABI's operations (arguments validated by the caller)
     int enable(const Env &e, uint32_t n, const uint64_t *id, const uint32_t *wid, const uint32_t *rq, const uint8_t *var, const uint64_t *prio);
@@ -105,6 +112,14 @@ class Ledger {
     int upload_flags(const Env &e);
     int repack(const Env &e, const std::vector<uint32_t> &src, uint32_t W_old, const uint8_t *add_flags);
     int evict(const Env &e, uint32_t n, const uint32_t *worker_id);
+    // hqtick_lose_workers' ledger step: evict() with everything behind the count on the device.  One synchronisation, for the count; the sort by
+    // id, the gather, the grouping by lost worker and the reset of lost roots' rows are enqueued behind it and NOT waited for -- lose_out's pinned columns are
+    // final after the next synchronisation of the stream, which is the row tables' re-pack (repack() below) in the caller's sequence.  The tables end as after
+    // evict(); returns the number of evicted entries.  lose_ensure makes every buffer first (sized by the entries the ledger holds), so that a failed allocation
+    // changes nothing.
+    int lose_ensure(const Env &e, uint32_t n);
+    int lose(const Env &e, uint32_t n, const uint32_t *worker_id);
+    uint64_t lose_bound() const { return n_live + mn_live + (pf_on ? pf_live : 0); }  // at most this many entries leave
     void clear_requeued() { rq_task.clear(); rq_rq.clear(); rq_prio.clear(); rq_pf_task.clear(); rq_run_task.clear(); }
     // ---- a tick
     void abandon_tick() { pending = false; stage_n = 0; }  // (a tick that was never consumed is abandoned, as its selection is; its staging is never read)
@@ -188,11 +203,12 @@ class Ledger {
     RowPair counts, mn, pf;   // counts u32 [W x stride]; [mn task u64 W][mn root u8 W][flags u8 W]; pf u32 [W x pf_stride]
     // request tables, worker ids in row order, kernel scratch, the request ids before K4, a re-pack's row map, K5b's staging, counters of one operation,
     // a cancel's routes, overrides and sort scratch, a start's positions, kinds and mask (the host steps between its segments use B_SCRATCH)
-    // a reject's blocks, records, slice table and requeued columns
-    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_START, B_REJECT, B_N }; DevBuf buf[B_N];
+    // a reject's blocks, records, slice table and requeued columns; a lost-worker call's pairs, columns and sort scratch (lose_core.h: DevLayout)
+    enum { B_REQ, B_WIDS, B_SCRATCH, B_SAVED_RQ, B_BATCH, B_STAGE, B_CTR, B_CANCEL, B_START, B_REJECT, B_LOSE, B_N }; DevBuf buf[B_N];
     StartCols start_c{}; uint32_t start_n = 0, start_acc[C_N] = {};  // a start between start_begin and its last segment: its columns, the counters summed over the segments
     hqbuf::PinBuf h_start;  // a start's mask in, its kinds out
     hqbuf::PinBuf h_reject;  // a reject's overrides in; its hits, kinds, blocks, requeued count and columns out
+    hqbuf::PinBuf h_lose;    // a lost-worker call's worker lists in; its flat list, CSR and non-root members out (lose_core.h: PinLayout)
     hqbuf::PinBuf h_ctr, h_in, h_cancel, h_finish, h_fail;  // (h_cancel: a cancel's overrides in, its lists and routes out; h_finish / h_fail: a finish's / fail's overrides in, its kinds out)
     const uint32_t *c = nullptr;              // the last operation's counters (h_ctr)
     uint32_t cap = 0; uint64_t n_tomb = 0;    // buckets (a power of two), tombstones

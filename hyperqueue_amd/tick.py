@@ -615,6 +615,48 @@ class Tick:
         reassigned = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pw, k, np.uint32).tolist(), abi._np(pv, k, np.uint8).tolist())) if k else []
         return dict(kind=kind, requeued=requeued, reassigned=reassigned)
 
+    # -- on_remove_worker in one call (include/hqtick.h) ----------------------------------------------------------
+    def lose_workers(self, worker_ids) -> dict:
+        """hqtick_lose_workers for the lost workers, in this order -> {"n_requeued": tasks that went back into the ready set, "per_worker": per lost worker (the
+        caller's order) its [(task, rq, priority, HQ_LOSE_* kind)], ids ascending, "requeued": [(task, rq, priority)] of all of them, ids ascending, "reassigned":
+        [(task, redirect target, variant)], "mn_left": [(task, lost worker, root worker)]}"""
+        ids = np.ascontiguousarray(worker_ids, np.uint32)
+        f = self._lib.hqtick_lose_workers
+        f.argtypes = [C.c_void_p, C.c_uint32, abi.u32p]
+        n = self._chk(f(self._ctx, len(ids), ids.ctypes.data_as(abi.u32p) if len(ids) else None))
+        return dict(n_requeued=int(n), **self.lose_last())
+
+    def lose_last(self) -> dict:
+        """hqtick_lose_last_tasks / _last_requeued / _last_reassigned / _last_mn_left as copies (also after a call that returned an error)"""
+        n = C.c_uint32(); po, pt, pq, pp, pk = abi.u32p(), abi.u64p(), abi.u32p(), abi.u64p(), abi.u8p()
+        g = self._lib.hqtick_lose_last_tasks
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u32p), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u64p), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(po), C.byref(pt), C.byref(pq), C.byref(pp), C.byref(pk)))
+        per_worker = []
+        if n.value:
+            off = abi._np(po, n.value + 1, np.uint32).tolist()
+            k = off[-1]
+            rows = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pq, k, np.uint32).tolist(), abi._np(pp, k, np.uint64).tolist(), abi._np(pk, k, np.uint8).tolist())) if k else []
+            per_worker = [rows[off[i]:off[i + 1]] for i in range(n.value)]
+        g = self._lib.hqtick_lose_last_requeued
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u64p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pt), C.byref(pq), C.byref(pp)))
+        k = n.value
+        requeued = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pq, k, np.uint32).tolist(), abi._np(pp, k, np.uint64).tolist())) if k else []
+        pw, pv = abi.u32p(), abi.u8p()
+        g = self._lib.hqtick_lose_last_reassigned
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u8p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pt), C.byref(pw), C.byref(pv)))
+        k = n.value
+        reassigned = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pw, k, np.uint32).tolist(), abi._np(pv, k, np.uint8).tolist())) if k else []
+        pr = abi.u32p()
+        g = self._lib.hqtick_lose_last_mn_left
+        g.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(abi.u64p), C.POINTER(abi.u32p), C.POINTER(abi.u32p)]
+        self._chk(g(self._ctx, C.byref(n), C.byref(pt), C.byref(pw), C.byref(pr)))
+        k = n.value
+        mn_left = list(zip(abi._np(pt, k, np.uint64).tolist(), abi._np(pw, k, np.uint32).tolist(), abi._np(pr, k, np.uint32).tolist())) if k else []
+        return dict(per_worker=per_worker, requeued=requeued, reassigned=reassigned, mn_left=mn_left)
+
     def cluster_enable_request(self, worker_id: int, rq: int, variant: int) -> int:
         """hqtick_cluster_enable_request (request_enabled): the pair leaves the worker's blocked set -> 1 if it was there, else 0"""
         f = self._lib.hqtick_cluster_enable_request

@@ -850,6 +850,51 @@ int hqtick_cluster_enable_request(hqtick_ctx *ctx, uint32_t worker_id, uint32_t 
 int hqtick_cluster_blocked(const hqtick_ctx *ctx, uint32_t worker_id, uint32_t *n, const uint32_t **rq, const uint8_t **variant);
 
 /*
+ * Losing workers on the resident state in one call (functions added under ABI 12): on_remove_worker (server/reactor.rs:64-186) for a batch of lost
+ * workers, with what the handler needs per worker.  hqtick_cluster_remove_workers stays as it is; this call leaves the same resident state and reports more.
+ *   hqtick_lose_workers   the workers worker_id[0 .. n) are lost.  It needs a resident worker set, a resident ready set and an enabled ledger.  Every ledger entry
+ *       of a lost worker leaves the ledger (a multi-node entry is its ROOT's: a lost root evicts the task and frees the task's other rows, a lost non-root only
+ *       leaves), the rows leave the worker set and the ledger's row tables, the Retracting table follows (an entry retracting FROM a lost worker leaves -- with a
+ *       redirect to a worker that stays the task is Assigned there and reported by hqtick_lose_last_reassigned; an entry whose redirect TARGET is lost loses the
+ *       redirect and is back in its queue), and the evicted tasks go back into the resident ready set with their entries' own request and priority, merged on
+ *       the device: ready set, ledger entries, counts, free rows, prefilled counts, multi-node rows and flags, worker rows, blocked sets and Retracting table are
+ *       those hqtick_cluster_remove_workers leaves for the same list.  The evicted entries are sorted, classified and grouped on the device; no column of a
+ *       requeued task crosses PCIe as input to the merge.
+ *       Returns the number of tasks that went back into the ready set.  HQTICK_E_INVALID without a worker set, without a resident ready set, with the ledger off,
+ *       with a two-call tick's placement pending, with a NULL array, or with an unknown or repeated worker id (nothing changes then); n = 0 returns 0 and leaves
+ *       every list empty.  Every buffer of the eviction, the grouping and the merge is ensured before the first change.  If a later step still fails, what the
+ *       lists hold says how far the call came: a failure of the eviction or of a re-pack (a device error) leaves all five lists EMPTY, and the host uploads the
+ *       worker set and enables the ledger again from its own view; a failure of the last step -- the worker ids of the new rows, or the merge, which also refuses a
+ *       requeued id the host had put into the ready set itself (HQTICK_E_INVALID) -- leaves the five lists FILLED: the workers are gone, the entries have left the
+ *       ledger, the Retracting table has followed, the ready set is as it was, and hqtick_ready_add of hqtick_lose_last_requeued finishes the job.
+ *       The host keeps these jobs: instance ids, crash counters, hqtick_fail_tasks(id, HQ_NO_WORKER) for a task over its crash limit, the prefill disposal an
+ *       arrival triggers (check_dispose_prefill / process_retracted), the messages.
+ *   hqtick_lose_last_tasks   a CSR over the lost workers in the CALLER'S order: worker i held task_id[task_off[i] .. task_off[i + 1]), ids ascending inside a
+ *       worker, each with its entry's request and priority and an HQ_LOSE_* kind.  The union of the lists is exactly hqtick_lose_last_requeued.
+ *   hqtick_lose_last_requeued    the same tasks as one list, ids strictly ascending, with request and priority.
+ *   hqtick_lose_last_reassigned  (task, redirect target, variant) of the Retracting tasks that are Assigned on their target now: the ComputeTasks messages.
+ *   hqtick_lose_last_mn_left     one (task, lost worker, root worker) triple per lost worker that was a NON-root member of a multi-node task whose root stays
+ *       (the reference's ws.retain(|x| x != worker_id)): ascending by task id, then in the caller's order of the lost workers.  A task whose root is lost in the
+ *       same batch is not listed: it is _MN_ROOT in its root's list.
+ *   All five lists are memory owned by the context (the columns of the first two pinned), valid until the next hqtick_lose_workers; no other call touches them.
+ *   After hqtick_lose_workers the hqtick_cluster_last_requeued / _prefilled / _running accessors are EMPTY (they answer for hqtick_cluster_remove_workers only);
+ *   hqtick_cluster_last_reassigned reads the Retracting table's own last list and therefore repeats hqtick_lose_last_reassigned until the next
+ *   hqtick_cluster_remove_workers / hqtick_retract_response.
+ */
+#define HQ_LOSE_ASSIGNED   0   /* single-node entry, not running: task object Waiting, instance id bumped */
+#define HQ_LOSE_RUNNING    1   /* single-node entry, running: as above, and one of the worker's running_tasks (on_worker_lost, crash counter) */
+#define HQ_LOSE_PREFILLED  2   /* prefilled entry (tracking on): move_prefilled_task_to_ready, leaves the queue-side prefill set, no crash counter */
+#define HQ_LOSE_MN_ROOT    3   /* multi-node entry whose root this worker is: one of running_tasks; the other workers' rows are free single-node rows again */
+#define HQ_LOSE_REDIRECT   4   /* single-node entry of a Retracting task whose redirect TARGET this worker is: the redirect is dropped, the task is back in its
+                                  queue and stays Retracting{old} (reactor.rs:90-96), or is Waiting if `old` is lost in the same batch */
+int hqtick_lose_workers(hqtick_ctx *ctx, uint32_t n, const uint32_t *worker_id);
+int hqtick_lose_last_tasks(const hqtick_ctx *ctx, uint32_t *n_workers, const uint32_t **task_off, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority,
+                           const uint8_t **kind);
+int hqtick_lose_last_requeued(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **rq, const uint64_t **priority);
+int hqtick_lose_last_reassigned(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **worker_id, const uint8_t **variant);
+int hqtick_lose_last_mn_left(const hqtick_ctx *ctx, uint32_t *n, const uint64_t **task_id, const uint32_t **lost_worker_id, const uint32_t **root_worker_id);
+
+/*
  * Audit of the resident state (function added under ABI 12): the counterpart of Core::sanity_check (server/core.rs:280-436) for what the
  * library holds in HBM.  The host that could compare the structures with a second copy no longer keeps one, so the comparison runs on the device, where the
  * state is: read-only kernels on the context's stream, behind every queued delta, reporting per invariant how many keys violate it and the smallest one.

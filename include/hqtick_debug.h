@@ -291,6 +291,20 @@ int hqtick_debug_reject_kind(uint32_t n, const uint8_t *entry_found, const uint8
                              const uint8_t *entry_run, const uint8_t *variant_none, const uint8_t *variant_exists, const uint8_t *override_found,
                              const uint8_t *override_worker_match, const uint8_t *override_redirect, const uint8_t *earlier_eligible, const uint8_t *reporter_resident,
                              uint8_t *kind, uint8_t *blocks);
+
+/* The rule of hqtick_lose_workers (csrc/lose_core.h: the function the gather kernel calls per evicted entry, and the one the host settles the Retracting table's
+ * redirect targets with) on HOST arrays, one entry per evicted ledger entry: entry_class (0 single-node, 1 multi-node, 2 prefilled), entry_run (the entry's running
+ * byte), redirect_target (the id is in the Retracting table with the lost worker as its redirect target).  kind [n]: the HQ_LOSE_* kinds; running [n] (may be
+ * NULL): 1 if the task is one of on_remove_worker's running_tasks.  Returns n, HQTICK_E_INVALID for a NULL array or a class above 2.  Not a product path. */
+int hqtick_debug_lose_kind(uint32_t n, const uint8_t *entry_class, const uint8_t *entry_run, const uint8_t *redirect_target, uint8_t *kind, uint8_t *running);
+
+/* The grouping of hqtick_lose_workers (csrc/lose_core.h) on HOST arrays: the evicted entries as the gather leaves them -- task_id [k] strictly ascending with
+ * priority, rq, kind and worker_index [k] (the index of the entry's worker in the caller's list, below n_workers) -- through the stable sort of csrc/cancel_core.h
+ * and the two phases of the group kernel, one emulated thread after the other in the given order (0 ascending, 1 descending, 2 a fixed permutation): the CSR must
+ * not depend on it.  Out, caller-sized: out_off [n_workers + 1], the four columns [k].  Returns k, HQTICK_E_INVALID for a NULL argument, n_workers == 0, an index
+ * not below n_workers, ids that do not ascend or an order outside 0..2.  Not a product path. */
+int hqtick_debug_lose_group(uint32_t k, uint32_t n_workers, const uint64_t *task_id, const uint64_t *priority, const uint32_t *rq, const uint8_t *kind, const uint32_t *worker_index,
+                            int order, uint32_t *out_off, uint64_t *out_task, uint64_t *out_priority, uint32_t *out_rq, uint8_t *out_kind);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
